@@ -21,10 +21,11 @@ Workloads (BASELINE.json configs):
   mixed           configs[3]: 65536 ch/GPU, AM/USB/LSB/NBFM by c mod 4, 10x time binning
   million         configs[4]: 2^20 channels in total, 2^20/N per GPU (strong scaling)
   decim4          the decimating front end: 16384 ch/GPU, IQ at 48 kHz, 125-tap channel filters
-The default run also times `wf`, `mixed`, `million`, `decim4` and the variants DESIGN.md discusses briefly after the
-main measurement and reports them, each with its own rooflines, under "extra" in the same JSON line.
-Every run ends with the parity hash of SURVEY.md 8e: each rank's checksums of a probe of its channel block, cross-checked
-by its neighbour rank ("parity" in the JSON; a mismatch is an error).
+A plain run sets up, warms up, times the K steps and prints the line (`--dump-outputs DIR`: and writes what the last
+timed step computed).  With `--full` the default workload also times `wf`, `mixed`, `million`, `decim4` and the variants
+DESIGN.md discusses briefly after the main measurement and reports them, each with its own rooflines, under "extra" in the
+same JSON line, next to the CPU baseline; and a `--full` run ends with the parity hash of SURVEY.md 8e: each rank's
+checksums of a probe of its channel block, cross-checked by its neighbour rank ("parity" in the JSON; a mismatch is an error).
 """
 import argparse
 import json
@@ -477,9 +478,44 @@ class EnergyProbe:
                 "source": "rocm_smi energy accumulator of this rank's GPU over the timed region"}
 
 
+DUMP_BUDGET_BYTES = 64 * 10 ** 6        # --dump-outputs: all arrays together
+DUMP_MAX_CHANNELS = 256
+DUMP_SEED = 0x5D5D
+
+
+def dump_outputs(L, eng, out_dir, channels, lines, do_audio):
+    """--dump-outputs: the device results of the last step for a fixed, seeded sample of the ctx's channels (the same channels for the
+    same arguments), as float32 .npy files: wf_lines [lines, k, 1024] (int16 sums of `averaging` byte lines), pcm [k, samples] (int16),
+    rssi [k, frames] (dBm).  Row by row, so that a batch whose whole results do not fit the host is never copied back."""
+    import ctypes as C
+    per_ch = 4 * (lines * L.NFFT + (eng.audio_frames * (L.FRAME + 1) if do_audio else 0))
+    k = max(1, min(channels, DUMP_MAX_CHANNELS, DUMP_BUDGET_BYTES // max(per_ch, 1)))
+    chans = np.sort(np.random.default_rng(DUMP_SEED).choice(channels, k, replace=False))
+    if do_audio:
+        wf, pcm, rssi = eng.fetch_rows(chans, lines)
+        arrays = {"wf_lines": wf, "pcm": pcm, "rssi": rssi}
+    else:
+        wf = np.empty((lines, k, L.NFFT), np.int16)
+        wptr, n = L._P(), C.c_uint32(0)
+        L.check(L.lib.ssdr_wf_device(eng._ctx, C.byref(wptr), C.byref(n)), "ssdr_wf_device")
+        if lines > n.value:
+            raise RuntimeError("the last step left %d waterfall lines, not %d" % (n.value, lines))
+        row = L.NFFT * 2
+        for i, c in enumerate(chans):
+            for ln in range(lines):
+                L.check(L.lib.ssdr_copy_from_device(eng._ctx, wf[ln, i].ctypes.data, C.c_void_p(wptr.value + (ln * eng.n_ch + int(c)) * row), row),
+                      "ssdr_copy_from_device")
+        arrays = {"wf_lines": wf}
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a.astype(np.float32))
+
+
 def measure(S, L, torch, rdv, rank, world, local_rank, workload, channels, sframes, steps, warmup, spinup,
-            concurrent=0, host_feed=0, hop=1024, fused=1, exact=0, first_channel_id=None, overlap=1):
+            concurrent=0, host_feed=0, hop=1024, fused=1, exact=0, first_channel_id=None, overlap=1, dump=""):
     """Spin the clocks up, W warm-up steps, then exactly `steps` timed steps between barrier + synchronize pairs.
+    The channel state is reset between the spin-up and the warm-up steps: what the timed steps compute depends on W and `steps` alone,
+    not on how many steps the spin-up took.  dump: a directory for the last step's results (dump_outputs(), rank 0).
     -> dict(value, ms_per_step, stages, ...)."""
     _, _, _, modes, do_wf, do_audio = WORKLOADS[workload]
     n_frames = 2 * sframes
@@ -501,16 +537,18 @@ def measure(S, L, torch, rdv, rank, world, local_rank, workload, channels, sfram
         raise SetupFailed("%s on %d channels x %d superframes: set-up failed on %s" % (
             workload, channels, sframes, ("this rank (%d): %s: %s" % (rank, type(err).__name__, str(err)[:160])) if err else "another rank"))
 
+    lines_ready = [0]                                     # waterfall lines the last step left on the device
+
     def step():
         if do_wf:
-            eng.run_wf(fetch=False)
+            lines_ready[0] = eng.run_wf(fetch=False)
         if do_audio:
             eng.run_audio(fetch=False)
 
     chain_kind = [0]                                      # which way ssdr_run_chain went: 0 two stages, 1 ssdr_fused_am_kernel, 2 ssdr_chain_ws_kernel
     if do_wf and do_audio:
         def step():                                       # noqa: F811  (ssdr_run_chain: a one-read kernel where the
-            chain_kind[0] = eng.run_chain()[1]            #  configuration allows it and --fused is not 0, else the two kernels)
+            lines_ready[0], chain_kind[0] = eng.run_chain()   #  configuration allows it and --fused is not 0, else the two kernels)
 
     inflight = [0]
     if host_feed:
@@ -542,6 +580,8 @@ def measure(S, L, torch, rdv, rank, world, local_rank, workload, channels, sfram
         for _ in range(8):
             step()
         eng.sync()
+    if not host_feed:
+        eng.reset_state()                   # the spin-up ran for a time, not a number of steps: start the counted steps from a fresh state
     for _ in range(warmup):
         step()
     eng.sync()
@@ -569,6 +609,8 @@ def measure(S, L, torch, rdv, rank, world, local_rank, workload, channels, sfram
     au_ms, au_n = eng.kernel_stats(L.K_AUDIO)
     fu_ms, fu_n = eng.kernel_stats(L.K_FUSED)
     paths = eng.audio_paths()
+    if dump and rank == 0:
+        dump_outputs(L, eng, dump, channels, lines_ready[0], do_audio)
     eng.close()
     units = rdv.sum_over_ranks(channels) * sframes * steps     # channel-superframes, whole job (blocks may differ by one channel)
     # algorithmic bytes per launch: WF 4096 B in + 2048/N B out per line;
@@ -964,7 +1006,15 @@ def main():
     ap.add_argument("--host-feed-extra", type=int, default=1, help="0: skip extra.hub_feed (the pipelined feed through IQHub; takes 8 GiB of pinned host memory)")
     ap.add_argument("--dry-run", action="store_true",
                     help="control flow only (ranks, rendezvous over gloo, channel blocks, JSON line), no GPU work: the CPU test of --gpus")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline figure as well: the parity hash, the extra workloads and variants (extra), "
+                         "the CPU baseline.  Without it a run sets up, warms up, times the steps and prints the line")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps, write what the last one computed as DIR/<name>.npy (float32): waterfall lines, PCM "
+                         "and RSSI of a fixed, seeded sample of rank 0's channels (at most %d MB in all)" % (DUMP_BUDGET_BYTES // 10 ** 6))
     args = ap.parse_args()
+    if args.dump_outputs and args.host_feed:
+        raise SystemExit("bench.py: --dump-outputs takes the resident-input path only (--host-feed 0)")
 
     rank, local_rank, world = check_world(args.gpus)
     if world == 0:
@@ -989,8 +1039,11 @@ def main():
         fake = lambda fid: [(fid * 2654435761 + k * 40503 + 12345) & 0xFFFFFFFFFFFFFFFF for k in range(3)]      # noqa: E731
         firsts = [int(v[0]) for v in rdv.gather_ints([first_id])]
         nxt = firsts[(rank + 1) % world]
-        own, cross = fake(first_id), fake(nxt if os.environ.get("SSDR_DRYRUN_BREAK_RANK") != str(rank) else nxt + 1)
-        parity = parity_report(rdv, world, firsts, own, cross, "dry run: stand-in checksums")
+        if args.full:
+            own, cross = fake(first_id), fake(nxt if os.environ.get("SSDR_DRYRUN_BREAK_RANK") != str(rank) else nxt + 1)
+            parity = parity_report(rdv, world, firsts, own, cross, "dry run: stand-in checksums")
+        else:
+            parity = {"ranks_agree": True, "skipped": "not a --full run"}
         if args.host_feed in (3, 4):                              # the multi-rank hub line's control flow: barrier, sum over ranks, max wall, per-rank values
             units = float(channels * sframes * args.steps)
             own_wall = 1e-3 * (rank + 1)
@@ -1002,7 +1055,7 @@ def main():
             rdv.close()
             return
         dry_extra = None
-        if world > 1 and args.workload == "full" and not args.no_extra:
+        if world > 1 and args.full and args.workload == "full" and not args.no_extra:
             def fake_run(wl, ch, sf, first, nsteps):               # the arithmetic of measure(): all ranks' units over the slowest rank's wall
                 own_wall = 1e-3 * (rank + 1)
                 if os.environ.get("SSDR_DRYRUN_FAIL_SETUP") == "%s:%d" % (wl, rank):
@@ -1054,12 +1107,12 @@ def main():
         rdv.close()
         return
     m = measure(S, L, torch, rdv, rank, world, local_rank, args.workload, channels, sframes, args.steps, args.warmup,
-                args.spinup, args.concurrent, args.host_feed, args.hop, args.fused, args.exact, first_id, args.overlap)
+                args.spinup, args.concurrent, args.host_feed, args.hop, args.fused, args.exact, first_id, args.overlap, args.dump_outputs)
     # SURVEY.md 8e parity hash (untimed): every rank hashes a probe of its own channel block and of the NEXT rank's block;
     # rank r's view of block r+1 must equal rank r+1's own (at N = 1: a second fresh ctx must reproduce the first)
     firsts = [int(v[0]) for v in rdv.gather_ints([first_id])]
-    if args.no_parity_probe:
-        parity = {"ranks_agree": True, "skipped": "--no-parity-probe"}
+    if not args.full or args.no_parity_probe:
+        parity = {"ranks_agree": True, "skipped": "--no-parity-probe" if args.full else "not a --full run"}
     else:
         own = parity_probe(S, local_rank, args.workload, first_id, fused=args.fused)
         cross = parity_probe(S, local_rank, args.workload, firsts[(rank + 1) % world], fused=0)
@@ -1133,7 +1186,7 @@ def main():
                                   "unit": "GB/s", "frac": b / ms / 1e6 / HBM_PEAK_GBPS, "traffic": None, "avg_kernel_ms": ms,
                                   "algorithmic_bytes_per_launch": b}
 
-    if world > 1 and args.workload == "full" and not args.no_extra and not args.host_feed:
+    if world > 1 and args.full and args.workload == "full" and not args.no_extra and not args.host_feed:
         # the driver's single N > 1 command: after the weak-scaling `full` figure (which stays `value`, so N = 1 agrees with BENCH), every rank
         # times configs[4] (its 2^20 / N block: the strong-scaling curve) and configs[3], same barrier / max-wall rule (review r5, item 1)
         def run_one(wl, ch, sf, first, nsteps):
@@ -1147,7 +1200,7 @@ def main():
                 parity = dict(parity, ranks_agree=False, extra_mismatch=k)
                 full["parity"] = parity
 
-    if rank == 0 and world == 1 and args.workload == "full" and not args.no_extra and not args.host_feed:
+    if rank == 0 and world == 1 and args.full and args.workload == "full" and not args.no_extra and not args.host_feed:
         extra = {}
 
         def chain_frac(e, ch, sf, navg, hop=1024):
@@ -1224,7 +1277,7 @@ def main():
     full["roofline"]["stages"] = summary
 
     if rank == 0:
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             try:
                 full["cpu_baseline"] = cpu_baseline(args.workload)
             except Exception as ex:                                      # noqa: BLE001  (a box that cannot start 256 workers still reports its GPU line)

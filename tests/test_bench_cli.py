@@ -48,21 +48,28 @@ def check_multi_rank_extras(d, world):
 
 
 def test_two_ranks_also_time_the_million_channel_and_mixed_configurations():
-    p = run(["--gpus", "2", "--dry-run"])
+    p = run(["--gpus", "2", "--dry-run", "--full"])
     assert p.returncode == 0, p.stderr
     d = last_json(p)
     check_multi_rank_extras(d, 2)
     assert d["channels_total"] == 2 * 65536                       # the main figure is still the weak-scaling `full` one
     # --no-extra and the other workloads: the main measurement only
-    assert "extra" not in last_json(run(["--gpus", "2", "--dry-run", "--no-extra"]))
-    assert "extra" not in last_json(run(["--gpus", "2", "--dry-run", "--workload", "mixed"]))
-    assert "extra" not in last_json(run(["--gpus", "1", "--dry-run"]))
+    assert "extra" not in last_json(run(["--gpus", "2", "--dry-run", "--full", "--no-extra"]))
+    assert "extra" not in last_json(run(["--gpus", "2", "--dry-run", "--full", "--workload", "mixed"]))
+    assert "extra" not in last_json(run(["--gpus", "1", "--dry-run", "--full"]))
+
+
+def test_a_plain_run_measures_the_headline_only():
+    """without --full: no extra workloads, no parity ring -- set-up, warm-up, the timed steps and the line"""
+    d = last_json(run(["--gpus", "2", "--dry-run"]))
+    assert "extra" not in d and d["parity"] == {"ranks_agree": True, "skipped": "not a --full run"}
+    assert d["n_gpus"] == 2 and d["channels_total"] == 2 * 65536
 
 
 def test_a_rank_that_cannot_set_an_extra_up_makes_all_ranks_skip_it_together():
     """one rank out of memory for configs[4] must not leave the others at a barrier: the set-up result is agreed (MIN all-reduce),
     the extra is reported as an error, the next one runs, the line is printed and the exit code is 0"""
-    p = run(["--gpus", "3", "--dry-run"], {"SSDR_DRYRUN_FAIL_SETUP": "million:1"})
+    p = run(["--gpus", "3", "--dry-run", "--full"], {"SSDR_DRYRUN_FAIL_SETUP": "million:1"})
     assert p.returncode == 0, p.stderr
     d = last_json(p)
     assert "error" in d["extra"]["million"] and "set-up failed" in d["extra"]["million"]["error"]
@@ -97,18 +104,18 @@ def test_without_a_gpu_every_rank_fails_loudly():
 def test_parity_hash_gather_and_mismatch_is_an_error():
     """every rank's probe checksums are gathered, rank r's view of rank r+1's block is compared with that
     rank's own, and a disagreement fails the run (exit code != 0) after the JSON line was printed."""
-    p = run(["--gpus", "3", "--dry-run"])
+    p = run(["--gpus", "3", "--dry-run", "--full"])
     assert p.returncode == 0, p.stderr
     d = last_json(p)
     par = d["parity"]
     assert par["ranks_agree"] and par["mismatching_ranks"] == [] and par["first_channel_ids"] == [0, 65536, 131072]
     assert len(par["checksums"]) == 3 and all(len(c) == 3 and all(len(x) == 16 for x in c) for c in par["checksums"])
     assert len({tuple(c) for c in par["checksums"]}) == 3          # different blocks hash differently
-    p = run(["--gpus", "3", "--dry-run"], {"SSDR_DRYRUN_BREAK_RANK": "1"})
+    p = run(["--gpus", "3", "--dry-run", "--full"], {"SSDR_DRYRUN_BREAK_RANK": "1"})
     assert p.returncode != 0
     d = last_json(p)
     assert not d["parity"]["ranks_agree"] and d["parity"]["mismatching_ranks"] == [1]
-    p = run(["--gpus", "2", "--dry-run", "--workload", "million"])
+    p = run(["--gpus", "2", "--dry-run", "--full", "--workload", "million"])
     assert last_json(p)["parity"]["first_channel_ids"] == [0, 1 << 19]
 
 
@@ -159,7 +166,7 @@ def test_eight_ranks_meet_over_gloo_shard_a_million_channels_and_close_the_parit
     (gloo: no RCCL anywhere on this path), 2^20 channels in eight blocks of 131 072, the parity ring r -> r + 1 -> ... -> 0"""
     port = 29500 + os.getpid() % 2000
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "8", "--master-addr", "127.0.0.1",
-           "--master-port", str(port), BENCH, "--gpus", "8", "--dry-run", "--workload", "million"]
+           "--master-port", str(port), BENCH, "--gpus", "8", "--dry-run", "--full", "--workload", "million"]
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT")}
     p = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=600)
     assert p.returncode == 0, p.stderr[-2000:]
@@ -174,7 +181,7 @@ def test_eight_ranks_under_the_drivers_command_return_both_scaling_curves():
     """exactly the driver's N = 8 command line (default workload): the weak-scaling `full` figure plus extra.million / extra.mixed"""
     port = 31500 + os.getpid() % 2000
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "8", "--master-addr", "127.0.0.1",
-           "--master-port", str(port), BENCH, "--gpus", "8", "--steps", "20", "--warmup", "3", "--dry-run"]
+           "--master-port", str(port), BENCH, "--gpus", "8", "--steps", "20", "--warmup", "3", "--dry-run", "--full"]
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT")}
     p = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=600)
     assert p.returncode == 0, p.stderr[-2000:]
