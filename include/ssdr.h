@@ -175,6 +175,31 @@ int ssdr_audio_flags(ssdr_ctx *ctx, uint8_t *flags_out, int out_is_device);
  * before the byte order): iq_out int16 [n_ch][n_frames*512][2] interleaved I,Q = saturate(rint(y g)) of the filtered
  * baseband y and the AGC gain g.  Rows of channels in other modes are zero.  SSDR_ESTATE if no channel is in IQ mode. */
 int ssdr_audio_iq(ssdr_ctx *ctx, int16_t *iq_out, int out_is_device);
+/* Impulse noise blanker, the KiwiSDR's "SET nb=<gate_us> th=<thresh>" (kiwi/client.py set_noise_blanker).  It works on the raw
+ * int16 IQ of a channel, before the NCO and the channel filter, in integers only.  Per frame f of M = 512 D input samples:
+ *   p[n]    = I*I + Q*Q (uint32, exact)
+ *   S_f     = sum over the frame's UNBLANKED input of floor(p[n] / M)
+ *   L_f     = min(S_{f-1}, S_{f-2})                  (both 0 after a reset: nothing is blanked in the first two frames)
+ *   trigger = L_f > 0 and p[n] > thresh * L_f        (uint64)
+ *   G       = ceil(gate_us * D * kiwi_rate / 1e6)    (float64; ssdr_nb_gate_samples)
+ *   a trigger at m zeroes samples m .. m + G - 1, into the next frame (and the next call) where it reaches that far; nothing looks ahead.
+ * Ranges: gate_us 1..10000, thresh 2..1000; gate_us = 0 or thresh = 0 turns the channel's blanker off; anything else is SSDR_EINVAL,
+ * and then no channel is changed.  Every channel it names has its blanker state reset (the two sums, the samples left to blank);
+ * its NCO, filter, AGC and discriminator state are left alone.  ssdr_reset_state resets the blanker state too; ssdr_set_decimation and
+ * ssdr_set_kiwi_rate recompute G from gate_us.
+ * The blanker is audio only: the waterfall and the ADC-overflow flags (ssdr_audio_flags) see the input as it came; the filter, its
+ * history (ssdr_get_state), the PCM, the RSSI and ssdr_audio_iq see the blanked samples.  Channels with the blanker
+ * on run their own instantiation of the audio kernels; while any channel blanks, ssdr_run_chain runs the two stages side by side
+ * (*fused = 0) and ssdr_checkpoint_save / _load return SSDR_ESTATE.  Measured cost of the audio stage with every channel blanking
+ * (DESIGN.md section 5): 1.16 x on the general path, 1.19 x on a mixed-mode batch.  With D > 1 ONE blanking channel puts every channel of
+ * the ctx on the decimating kernel's blanker twin (same results for the others): 1.09 x at D = 2, 1.23 x at D = 4, whichever channels blank. */
+int ssdr_set_noise_blanker(ssdr_ctx *ctx, uint32_t first, uint32_t count, const uint32_t *gate_us, const uint32_t *thresh);
+/* The gate in input samples for gate_us at D * kiwi_rate (host only).  SSDR_EINVAL outside the ranges above. */
+int ssdr_nb_gate_samples(uint32_t gate_us, uint32_t decim, uint32_t kiwi_rate, uint32_t *g);
+/* The blank mask of the last ssdr_run_audio: mask_out uint8 [n_ch][n_frames * 512 * D / 8], bit i of byte j = input sample 8 j + i
+ * of the call was zeroed.  Rows of channels whose blanker is off are zero.  SSDR_ESTATE if no channel has the blanker on, or the
+ * last ssdr_run_audio ran without it. */
+int ssdr_audio_nb_mask(ssdr_ctx *ctx, uint8_t *mask_out, int out_is_device);
 /* Both stages on the current batch, results kept on the device (ssdr_wf_device / ssdr_audio_device / ssdr_audio_flags): what
  * ssdr_run_wf followed by ssdr_run_audio do, with results that are theirs bit for bit.  *fused (may be NULL) tells which way it went:
  *   1  every channel is on the reference's full-band AM passband, N = 1, hop 1024, 12 kHz IQ, no zoom, an even number of at least 8

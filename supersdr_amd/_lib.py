@@ -87,6 +87,9 @@ _SIGS = {
     "ssdr_run_audio": (C.c_int, [_P, _P, _P, C.c_int]),
     "ssdr_audio_flags": (C.c_int, [_P, _P, C.c_int]),
     "ssdr_audio_iq": (C.c_int, [_P, _P, C.c_int]),
+    "ssdr_set_noise_blanker": (C.c_int, [_P, C.c_uint32, C.c_uint32, _P, _P]),
+    "ssdr_nb_gate_samples": (C.c_int, [C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint32)]),
+    "ssdr_audio_nb_mask": (C.c_int, [_P, _P, C.c_int]),
     "ssdr_run_chain": (C.c_int, [_P, C.POINTER(C.c_uint32), C.POINTER(C.c_int)]),
     "ssdr_set_fused": (C.c_int, [_P, C.c_int]),
     "ssdr_set_chain_floors": (C.c_int, [_P, C.c_uint32, C.c_uint32]),

@@ -191,6 +191,20 @@ struct ssdr_ctx {
     float *d_wire_rssi = nullptr;
     uint32_t *d_wire_gps = nullptr;
     uint32_t wire_run_frames = 0;
+    // impulse noise blanker (ssdr_set_noise_blanker): created at its first use, so a ctx that never blanks runs as before it existed
+    std::vector<uint32_t> h_nb_gate_us, h_nb_thresh;    // [n_ch] as set; 0: off
+    uint32_t nb_on = 0;                                 // channels whose blanker is on
+    uint64_t nb_gen = 0;                                // counts the changes of which channels blank
+    SsdrNbChan *d_nb = nullptr;                         // [n_ch] gate in samples, threshold, carried sums and samples left to blank
+    uint32_t nb_off[SSDR_PATH_COUNT] = {}, nb_n[SSDR_PATH_COUNT] = {};     // d_chan_list behind the paths' lists: the blanking channels by path
+    hipStream_t nb_stream[SSDR_PATH_COUNT] = {};        // their kernels beside the others (with path_stream: five side streams at most)
+    hipEvent_t ev_nb[SSDR_PATH_COUNT] = {};
+    uint8_t *d_nb_mask = nullptr;                       // [n_ch][n_frames * 64 D] blank mask of the last audio run
+    size_t nb_mask_bytes = 0;
+    bool nb_mask_valid = false;                         // the last ssdr_run_audio ran the blanker
+    uint32_t nb_mask_frames = 0, nb_mask_decim = 1;
+    std::vector<uint8_t> nb_mask_on;                    // which channels blanked in that run
+    uint64_t nb_mask_gen = ~0ull;
 };
 
 static int get_event(ssdr_ctx *c, hipEvent_t *e)
@@ -267,7 +281,8 @@ void ssdr_destroy(ssdr_ctx *c)
     void *ptrs[] = {c->d_win, c->d_thr, c->d_tw, c->d_lut, c->d_consts, c->d_taps, c->d_state, c->d_hist, c->d_chan_list, c->d_ws_list, c->d_wf_tail, c->d_wf_acc[0], c->d_wf_acc[1],
                     c->d_iq_own, c->d_wf_out, c->d_pcm, c->d_rssi, c->d_flags, c->d_scratch, c->d_db2col, c->d_color, c->d_play,
                     c->d_play_taps, c->d_play_hist, c->d_play_hist_alt, c->d_play_rs_taps, c->d_play_out, c->d_wfdata, c->d_wfpend, c->d_trace, c->d_trace_y, c->d_smeter,
-                    c->d_smeter_in, c->d_post_sel, c->d_wire, c->d_wire_rssi, c->d_play_mono, c->d_line1, c->d_dbchan1, c->d_color1, c->d_tw64, c->d_wire_gps, c->d_iq_out, c->d_zoom_taps, c->d_zoom_dphi, c->d_zoom_phase, c->d_zoom_hist, c->d_zoom_out};
+                    c->d_smeter_in, c->d_post_sel, c->d_wire, c->d_wire_rssi, c->d_play_mono, c->d_line1, c->d_dbchan1, c->d_color1, c->d_tw64, c->d_wire_gps, c->d_iq_out, c->d_zoom_taps, c->d_zoom_dphi, c->d_zoom_phase, c->d_zoom_hist, c->d_zoom_out,
+                    c->d_nb, c->d_nb_mask};
     for (void *p : ptrs)
         if (p) (void)hipFree(p);
     if (c->ev0) (void)hipEventDestroy(c->ev0);
@@ -281,6 +296,10 @@ void ssdr_destroy(ssdr_ctx *c)
     for (int i = 0; i < SSDR_PATH_COUNT - 1; i++) {
         if (c->path_stream[i]) { (void)hipStreamSynchronize(c->path_stream[i]); (void)hipStreamDestroy(c->path_stream[i]); }
         if (c->ev_path[i]) (void)hipEventDestroy(c->ev_path[i]);
+    }
+    for (int i = 0; i < SSDR_PATH_COUNT; i++) {
+        if (c->nb_stream[i]) { (void)hipStreamSynchronize(c->nb_stream[i]); (void)hipStreamDestroy(c->nb_stream[i]); }
+        if (c->ev_nb[i]) (void)hipEventDestroy(c->ev_nb[i]);
     }
     if (c->own_stream) (void)hipStreamDestroy(c->own_stream);
     delete c;
@@ -341,6 +360,7 @@ int ssdr_table(int which, float *out, uint32_t n) SSDR_GUARD
 static int zoom_restart(ssdr_ctx *c, uint32_t first, uint32_t count, bool restart_group = true);
 static int join_audio(ssdr_ctx *c);
 static int drain_audio(ssdr_ctx *c);
+static int nb_upload(ssdr_ctx *c, uint32_t first, uint32_t count);
 
 int ssdr_reset_state(ssdr_ctx *c, uint32_t first, uint32_t count) SSDR_GUARD
 {
@@ -365,6 +385,7 @@ int ssdr_reset_state(ssdr_ctx *c, uint32_t first, uint32_t count) SSDR_GUARD
         HIP_TRY(hipMemsetAsync(c->d_wf_tail + (size_t)first * (SSDR_NFFT / 2), 0, (size_t)count * (SSDR_NFFT / 2) * 4, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
     if (first == 0 && count == c->n_ch) { c->wf_phase = 0; c->synth_sample0 = 0; c->audio_started = false; }
+    { int rcn = nb_upload(c, first, count); if (rcn != SSDR_OK) return rcn; }      // the blanker starts over (its gate at the current rate)
     return zoom_restart(c, first, count, false);         // the zoomed streams of these channels start over as well
 } SSDR_UNGUARD
 
@@ -756,12 +777,15 @@ static int ensure_chan_list(ssdr_ctx *c, hipStream_t s)
 {
     if (!c->chan_list_dirty) return SSDR_OK;
     std::vector<uint32_t> list(c->n_ch);
-    uint32_t pos = 0, off[SSDR_PATH_COUNT], cnt[SSDR_PATH_COUNT];
-    for (int p = 0; p < SSDR_PATH_COUNT; p++) {
-        off[p] = pos;
+    // the paths' lists, then the lists of the channels that blank, by path (empty while no channel blanks: the list is the same)
+    uint32_t pos = 0, off[2 * SSDR_PATH_COUNT], cnt[2 * SSDR_PATH_COUNT];
+    for (int g = 0; g < 2 * SSDR_PATH_COUNT; g++) {
+        const int p = g % SSDR_PATH_COUNT;
+        const bool blank = g >= SSDR_PATH_COUNT;
+        off[g] = pos;
         for (uint32_t ch = 0; ch < c->n_ch; ch++)
-            if (ssdr_audio_path(c->h_consts[ch]) == p) list[pos++] = ch;
-        cnt[p] = pos - off[p];
+            if (ssdr_audio_path(c->h_consts[ch]) == p && (c->nb_on && c->h_nb_thresh[ch] != 0) == blank) list[pos++] = ch;
+        cnt[g] = pos - off[g];
     }
     HIP_TRY(hipMemcpyAsync(c->d_chan_list, list.data(), (size_t)c->n_ch * sizeof(uint32_t), hipMemcpyHostToDevice, s));
     // the chain list of the wave-specialised kernel: consecutive channels of the sorted list form pairs (so a pair is of one path,
@@ -789,7 +813,10 @@ static int ensure_chan_list(ssdr_ctx *c, hipStream_t s)
     HIP_TRY(hipMemcpyAsync(c->d_ws_list, ws.data(), ((size_t)c->n_ch + 1) * sizeof(uint32_t), hipMemcpyHostToDevice, s));
     c->ws_ticket = 0;
     HIP_TRY(hipStreamSynchronize(s));    // `list` goes out of scope
-    for (int p = 0; p < SSDR_PATH_COUNT; p++) { c->path_off[p] = off[p]; c->path_n[p] = cnt[p]; }
+    for (int p = 0; p < SSDR_PATH_COUNT; p++) {
+        c->path_off[p] = off[p]; c->path_n[p] = cnt[p];
+        c->nb_off[p] = off[SSDR_PATH_COUNT + p]; c->nb_n[p] = cnt[SSDR_PATH_COUNT + p];
+    }
     c->chan_list_dirty = false;
     return SSDR_OK;
 }
@@ -990,6 +1017,16 @@ int ssdr_run_audio(ssdr_ctx *c, int16_t *pcm_out, float *rssi_out, int out_is_de
         HIP_TRY(hipMalloc(&c->d_flags, (size_t)c->n_ch * c->in_frames));
         c->flags_frames = c->in_frames;
     }
+    const size_t nb_mask_need = c->nb_on ? (size_t)c->n_ch * c->in_frames * 64 * c->decim : 0;     // one bit per input sample
+    if (c->nb_mask_bytes < nb_mask_need) {
+        { int rcd = drain_audio(c); if (rcd != SSDR_OK) return rcd; }
+        HIP_TRY(hipStreamSynchronize(c->stream));
+        if (c->d_nb_mask) { HIP_TRY(hipFree(c->d_nb_mask)); c->d_nb_mask = nullptr; }
+        c->nb_mask_bytes = 0;
+        c->nb_mask_valid = false;
+        HIP_TRY(hipMalloc(&c->d_nb_mask, nb_mask_need));
+        c->nb_mask_bytes = nb_mask_need;
+    }
     SsdrAudioArgs a;
     a.iq = c->d_iq;
     a.ch_stride = (uint64_t)in_len(c, c->in_frames);
@@ -1033,6 +1070,7 @@ int ssdr_run_audio(ssdr_ctx *c, int16_t *pcm_out, float *rssi_out, int out_is_de
     { int rcl = ensure_chan_list(c, s); if (rcl != SSDR_OK) return rcl; }
     c->audio_started = true;
     c->audio_run_frames = c->in_frames;
+    c->nb_mask_valid = false;
     if (c->fuse_next) {                      // waterfall + full-band AM audio in one kernel: one read of the input
         SsdrFusedArgs fa;
         fa.wf = c->fused_wf;
@@ -1060,37 +1098,60 @@ int ssdr_run_audio(ssdr_ctx *c, int16_t *pcm_out, float *rssi_out, int out_is_de
     }
     // one kernel per non-empty path: the first on the stream itself, the others beside it on their own streams
     // (fork and join by events); the stage is timed between two events on `s`
-    if (c->decim > 1 && (c->path_n[SSDR_PATH_DELAY4] || c->path_n[SSDR_PATH_AM_RAW]))
+    if (c->decim > 1 && (c->path_n[SSDR_PATH_DELAY4] || c->path_n[SSDR_PATH_AM_RAW] || c->nb_n[SSDR_PATH_DELAY4] || c->nb_n[SSDR_PATH_AM_RAW]))
         return SSDR_ESTATE;                   // the decimating kernel is the general path: no channel may be compiled for a shift path
     if ((rc = timed_begin(c, s)) != SSDR_OK) return rc;
     if (c->decim > 1) {                       // ONE kernel over all channels (it takes no channel list)
         a.chan_list = c->d_chan_list;
         a.list_n = c->n_ch;
-        HIP_TRY(ssdr_launch_audio_dec(a, c->decim, s));
+        if (c->nb_on) {                       // ... or, once a channel blanks, its blanker twin over the list of all channels
+            const SsdrNbArgs na = {a, c->d_nb, c->d_nb_mask};
+            HIP_TRY(ssdr_launch_audio_dec_nb(na, c->decim, s));
+        } else {
+            HIP_TRY(ssdr_launch_audio_dec(a, c->decim, s));
+        }
     } else {
+        // launch groups: the three paths, then the three paths' channels that blank (their kernels' blanker twins)
         int n_paths = 0, n_side = 0;
-        for (int p = 0; p < SSDR_PATH_COUNT; p++) n_paths += c->path_n[p] != 0;
+        for (int g = 0; g < 2 * SSDR_PATH_COUNT; g++) n_paths += (g < SSDR_PATH_COUNT ? c->path_n[g] : c->nb_n[g - SSDR_PATH_COUNT]) != 0;
         const bool side = n_paths > 1 && !c->audio_serial;
         if (side) HIP_TRY(hipEventRecord(c->ev_fork, s));
         bool first = true;
-        for (int p = 0; p < SSDR_PATH_COUNT; p++) {
-            if (!c->path_n[p]) continue;
-            a.chan_list = c->d_chan_list + c->path_off[p];
-            a.list_n = c->path_n[p];
+        for (int g = 0; g < 2 * SSDR_PATH_COUNT; g++) {
+            const int p = g % SSDR_PATH_COUNT;
+            const bool blank = g >= SSDR_PATH_COUNT;
+            const uint32_t n = blank ? c->nb_n[p] : c->path_n[p];
+            if (!n) continue;
+            a.chan_list = c->d_chan_list + (blank ? c->nb_off[p] : c->path_off[p]);
+            a.list_n = n;
+            const SsdrNbArgs na = {a, c->d_nb, c->d_nb_mask};
             if (first || !side) {
-                HIP_TRY(ssdr_launch_audio(a, p, s));
+                HIP_TRY(blank ? ssdr_launch_audio_nb(na, p, s) : ssdr_launch_audio(a, p, s));
             } else {
-                hipStream_t ps = c->path_stream[n_side];
+                const bool own = n_side < SSDR_PATH_COUNT - 1;
+                hipStream_t ps = own ? c->path_stream[n_side] : c->nb_stream[n_side - (SSDR_PATH_COUNT - 1)];
+                hipEvent_t pe = own ? c->ev_path[n_side] : c->ev_nb[n_side - (SSDR_PATH_COUNT - 1)];
                 HIP_TRY(hipStreamWaitEvent(ps, c->ev_fork, 0));
-                HIP_TRY(ssdr_launch_audio(a, p, ps));
-                HIP_TRY(hipEventRecord(c->ev_path[n_side], ps));
+                HIP_TRY(blank ? ssdr_launch_audio_nb(na, p, ps) : ssdr_launch_audio(a, p, ps));
+                HIP_TRY(hipEventRecord(pe, ps));
                 n_side++;
             }
             first = false;
         }
-        for (int i = 0; i < n_side; i++) HIP_TRY(hipStreamWaitEvent(s, c->ev_path[i], 0));
+        for (int i = 0; i < n_side; i++)
+            HIP_TRY(hipStreamWaitEvent(s, i < SSDR_PATH_COUNT - 1 ? c->ev_path[i] : c->ev_nb[i - (SSDR_PATH_COUNT - 1)], 0));
     }
     if ((rc = timed_end(c, SSDR_K_AUDIO, s)) != SSDR_OK) return rc;
+    if (c->nb_on) {
+        c->nb_mask_valid = true;
+        c->nb_mask_frames = c->in_frames;
+        c->nb_mask_decim = c->decim;
+        if (c->nb_mask_gen != c->nb_gen) {
+            c->nb_mask_on.resize(c->n_ch);
+            for (uint32_t ch = 0; ch < c->n_ch; ch++) c->nb_mask_on[ch] = c->h_nb_thresh[ch] != 0;
+            c->nb_mask_gen = c->nb_gen;
+        }
+    }
     const hipMemcpyKind kind = out_is_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
     if (pcm_out) HIP_TRY(hipMemcpyAsync(pcm_out, c->d_pcm, (size_t)c->n_ch * c->in_frames * SSDR_FRAME * 2, kind, s));
     if (rssi_out) HIP_TRY(hipMemcpyAsync(rssi_out, c->d_rssi, (size_t)c->n_ch * c->in_frames * sizeof(float), kind, s));
@@ -1114,7 +1175,8 @@ int ssdr_run_chain(ssdr_ctx *c, uint32_t *lines_ready, int *fused) SSDR_GUARD
     const bool hop512 = c->hop == SSDR_NFFT / 2;            // (one line per frame: any frame count; hop 1024 needs whole lines)
     // (N > 1 and hop 512 are opt-in, ssdr_set_fused(ctx, 2): there the two stages side by side are faster)
     // (with float64 bins: the float64 counterpart, ssdr_fused_exact_am_kernel -- hop 1024 and N = 1 only)
-    const bool eligible = n_am == c->n_ch && c->decim == 1 && (hop512 || !(c->in_frames & 1u)) &&
+    // (no one-read kernel takes a channel that blanks: ssdr_set_noise_blanker)
+    const bool eligible = c->nb_on == 0 && n_am == c->n_ch && c->decim == 1 && (hop512 || !(c->in_frames & 1u)) &&
                           c->in_frames >= 8 &&
                           !c->concurrent && c->fused_grid != 0 && c->fused_enabled >= ((hop512 || c->n_avg > 1) ? 2 : 1) && c->zoom == 1 &&
                           (c->fused_enabled >= 2 || c->n_ch >= c->am_floor) &&
@@ -1123,7 +1185,7 @@ int ssdr_run_chain(ssdr_ctx *c, uint32_t *lines_ready, int *fused) SSDR_GUARD
     // read of the input.  By default where it is also the faster way (profiles/r06_ab_chain_ws.txt): when every channel runs the general path
     // (a filter to apply: the stages side by side are bound by the board's power cap there, and the second read of the input is energy);
     // for every batch it can take with ssdr_set_fused(ctx, 3) (full-band channels among them: 1 % slower than side by side, 39 % less HBM traffic)
-    const bool ws_can = c->ws_grid != 0 && c->decim == 1 && !hop512 && !(c->in_frames & 1u) && !c->concurrent && c->zoom == 1 && !c->exact_bins;
+    const bool ws_can = c->nb_on == 0 && c->ws_grid != 0 && c->decim == 1 && !hop512 && !(c->in_frames & 1u) && !c->concurrent && c->zoom == 1 && !c->exact_bins;
     const bool eligible_ws = !eligible && ws_can &&
                              (c->fused_enabled >= 3 || (c->fused_enabled >= 1 && c->sum_paths[SSDR_PATH_GENERAL] == c->n_ch && c->in_frames >= 8 &&
                                                         c->n_ch >= c->ws_floor));
@@ -1235,6 +1297,92 @@ int ssdr_audio_flags(ssdr_ctx *c, uint8_t *flags_out, int out_is_device) SSDR_GU
     HIP_TRY(hipMemcpyAsync(flags_out, c->d_flags, (size_t)c->n_ch * c->audio_run_frames,
                            out_is_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, c->stream));
     if (!out_is_device) HIP_TRY(hipStreamSynchronize(c->stream));
+    return SSDR_OK;
+} SSDR_UNGUARD
+
+// ---- impulse noise blanker ---------------------------------------------------------------------------------------------
+int ssdr_nb_gate_samples(uint32_t gate_us, uint32_t decim, uint32_t kiwi_rate, uint32_t *g) SSDR_GUARD
+{
+    if (!g || gate_us < 1 || gate_us > 10000 || (decim != 1 && decim != 2 && decim != 4) ||
+        (kiwi_rate != SSDR_RATE && kiwi_rate != SSDR_RATE_WIDE))
+        return SSDR_EINVAL;
+    *g = (uint32_t)std::ceil((double)gate_us * (double)decim * (double)kiwi_rate / 1e6);     // < 512 D over the whole range
+    return SSDR_OK;
+} SSDR_UNGUARD
+
+// the blanker state of channels [first, first + count) as set, at the current input rate, started over
+static int nb_upload(ssdr_ctx *c, uint32_t first, uint32_t count)
+{
+    if (!c->d_nb || !count) return SSDR_OK;
+    std::vector<SsdrNbChan> q(count);
+    for (uint32_t i = 0; i < count; i++) {
+        memset(&q[i], 0, sizeof q[i]);
+        const uint32_t gate_us = c->h_nb_gate_us[first + i], th = c->h_nb_thresh[first + i];
+        if (th && ssdr_nb_gate_samples(gate_us, c->decim, c->kiwi_rate, &q[i].gate) == SSDR_OK) q[i].thresh = th;
+        else q[i].gate = 0;
+    }
+    { int rcj = join_audio(c); if (rcj != SSDR_OK) return rcj; }
+    HIP_TRY(hipMemcpyAsync(c->d_nb + first, q.data(), count * sizeof(SsdrNbChan), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return SSDR_OK;
+}
+
+int ssdr_set_noise_blanker(ssdr_ctx *c, uint32_t first, uint32_t count, const uint32_t *gate_us, const uint32_t *thresh) SSDR_GUARD
+{
+    if (!c || (uint64_t)first + count > c->n_ch || (count && (!gate_us || !thresh))) return SSDR_EINVAL;
+    for (uint32_t i = 0; i < count; i++) {                  // all or nothing: every channel is checked before any is changed
+        if (gate_us[i] == 0 || thresh[i] == 0) continue;    // off
+        if (gate_us[i] > 10000 || thresh[i] < 2 || thresh[i] > 1000) return SSDR_EINVAL;
+    }
+    if (!count) return SSDR_OK;
+    HIP_TRY(hipSetDevice(c->device));
+    if (!c->d_nb) {                                         // first use: state, side streams
+        c->h_nb_gate_us.assign(c->n_ch, 0u);
+        c->h_nb_thresh.assign(c->n_ch, 0u);
+        for (int i = 0; i < SSDR_PATH_COUNT; i++) {
+            if (!c->nb_stream[i]) HIP_TRY(hipStreamCreateWithFlags(&c->nb_stream[i], hipStreamNonBlocking));
+            if (!c->ev_nb[i]) HIP_TRY(hipEventCreateWithFlags(&c->ev_nb[i], hipEventDisableTiming));
+        }
+        { int rcj = join_audio(c); if (rcj != SSDR_OK) return rcj; }
+        SsdrNbChan *d = nullptr;
+        HIP_TRY(hipMalloc(&d, (size_t)c->n_ch * sizeof(SsdrNbChan)));
+        c->d_nb = d;
+        HIP_TRY(hipMemsetAsync(c->d_nb, 0, (size_t)c->n_ch * sizeof(SsdrNbChan), c->stream));
+    }
+    uint32_t on = c->nb_on;
+    for (uint32_t i = 0; i < count; i++) {
+        const bool was = c->h_nb_thresh[first + i] != 0, is = gate_us[i] != 0 && thresh[i] != 0;
+        on = on - (was ? 1u : 0u) + (is ? 1u : 0u);
+        c->h_nb_gate_us[first + i] = is ? gate_us[i] : 0u;
+        c->h_nb_thresh[first + i] = is ? thresh[i] : 0u;
+    }
+    c->nb_on = on;
+    c->nb_gen++;
+    c->chan_list_dirty = true;
+    return nb_upload(c, first, count);
+} SSDR_UNGUARD
+
+int ssdr_audio_nb_mask(ssdr_ctx *c, uint8_t *mask_out, int out_is_device) SSDR_GUARD
+{
+    if (!c || !mask_out) return SSDR_EINVAL;
+    if (!c->nb_on || !c->nb_mask_valid || !c->d_nb_mask) return SSDR_ESTATE;
+    HIP_TRY(hipSetDevice(c->device));
+    { int rcj = join_audio(c); if (rcj != SSDR_OK) return rcj; }
+    const size_t row = (size_t)c->nb_mask_frames * 64 * c->nb_mask_decim;
+    const hipMemcpyKind kind = out_is_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
+    HIP_TRY(hipMemcpyAsync(mask_out, c->d_nb_mask, (size_t)c->n_ch * row, kind, c->stream));
+    // the rows of channels that did not blank hold nothing of this run: zeros, a run of such channels at a time
+    for (uint32_t ch = 0; ch < c->n_ch;) {
+        if (c->nb_mask_on[ch]) { ch++; continue; }
+        uint32_t end = ch;
+        while (end < c->n_ch && !c->nb_mask_on[end]) end++;
+        if (out_is_device) HIP_TRY(hipMemsetAsync(mask_out + (size_t)ch * row, 0, (size_t)(end - ch) * row, c->stream));
+        ch = end;
+    }
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    if (!out_is_device)
+        for (uint32_t ch = 0; ch < c->n_ch; ch++)
+            if (!c->nb_mask_on[ch]) memset(mask_out + (size_t)ch * row, 0, row);
     return SSDR_OK;
 } SSDR_UNGUARD
 
@@ -1688,6 +1836,7 @@ int ssdr_checkpoint_save(ssdr_ctx *c, void *blob) SSDR_GUARD
     { int rcj = join_audio(c); if (rcj != SSDR_OK) return rcj; }
     const size_t n = c->n_ch;
     if (c->zoom > 1) return SSDR_ESTATE;                     // the zoomed waterfall stream (phase, history, centres) is not part of the blob
+    if (c->nb_on) return SSDR_ESTATE;                        // nor is the noise blanker's state
     SsdrCkptHeader h = {kCkptMagic, kCkptVersion, c->n_ch, c->n_avg, c->wf_phase, c->audio_started ? 1u : 0u, c->kiwi_rate,
                         c->d_play_hist ? 1u : 0u, c->synth_sample0, c->hop, c->decim};
     char *p = static_cast<char *>(blob);
@@ -1732,7 +1881,7 @@ int ssdr_checkpoint_load(ssdr_ctx *c, const void *blob, uint64_t bytes) SSDR_GUA
     std::vector<float> ktaps(n * SSDR_NTAP_MAX);
     for (size_t i = 0; i < n; i++)
         if (ssdr_compile_params_host(&prm[i], &kc[i], ktaps.data() + i * SSDR_NTAP_MAX, h.decim, h.kiwi_rate) != SSDR_OK) return SSDR_EINVAL;
-    if (!c->feed.empty() || c->zoom > 1) return SSDR_ESTATE;
+    if (!c->feed.empty() || c->zoom > 1 || c->nb_on) return SSDR_ESTATE;
     std::vector<double> play_hist;                          // play_buffer state that arrives before its buffers exist: applied at first use
     if (h.has_play && !c->d_play_hist) {
         const double *q = reinterpret_cast<const double *>(static_cast<const char *>(blob) + sizeof h + n * (sizeof(ssdr_chan_consts) +

@@ -51,9 +51,10 @@ __host__ __device__ constexpr int dec_streams_per_phase(int D) { return dec_phas
 // registers, then those take the same two regions -- and every stream's history (its last HOCT_S octets) lives in a small area of
 // its own, copied in front of the stream when its phase begins and refreshed by the lanes that hold the frame's tail when they file
 // it.  Same sums in the same order: stream 0 first, taps ascending.
-template <int D>
+// BLANK: the noise blanker on the lane's 8 D raw inputs right after the loads, as in channel_frames.
+template <int D, bool BLANK = false>
 SSDR_DEV void channel_frames_dec(const SsdrAudioArgs &a, const uint32_t ch, const int l, const ssdr_chan_consts &kc,
-                                 float2 *s_z, float2 *s_h, float *s_taps)
+                                 float2 *s_z, float2 *s_h, float *s_taps, SsdrNbChan *nb = nullptr, uint8_t *nb_mask = nullptr)
 {
     constexpr int SLOTS = SSDR_NTAP_MAX / D;             // tap slots per stream
     constexpr int HOCT_S = SSDR_HIST / D / 8;            // history octets per stream
@@ -114,6 +115,12 @@ SSDR_DEV void channel_frames_dec(const SsdrAudioArgs &a, const uint32_t ch, cons
     uint8_t *flag_row = a.flags + (uint64_t)ch * a.n_frames;
     float rssi_sum = 0.0f;
     uint32_t flag_keep = 0;
+    NbRun nbs = {0, 0, 0, 0, 0};
+    uint32_t nb_last = 0;                                // the lane's blank mask of the last frame (the raw tail is filed blanked)
+    if constexpr (BLANK) {
+        const SsdrNbChan q = nb[ch];
+        nbs = {q.gate, q.thresh, q.s1, q.s2, q.left};
+    }
 
     for (uint32_t f = 0; f < a.n_frames; f++, src += SSDR_FRAME * D, dst += SSDR_FRAME) {
         if ((f & 63u) == 0) {
@@ -125,6 +132,13 @@ SSDR_DEV void channel_frames_dec(const SsdrAudioArgs &a, const uint32_t ch, cons
         for (int i = 0; i < NB / 4; i++) {
             const u32x4 v = SSDR_DEC_LOAD(reinterpret_cast<const u32x4 *>(src) + i);
             rw[4 * i] = v.x; rw[4 * i + 1] = v.y; rw[4 * i + 2] = v.z; rw[4 * i + 3] = v.w;
+        }
+        bool nb_clip = false;
+        if constexpr (BLANK) {
+            nb_last = nb_frame<NB>(rw, l, nbs, nb_clip);
+            uint8_t *mp = nb_mask + (uint64_t)f * 64 * D + D * l;
+            if constexpr (D == 2) *reinterpret_cast<uint16_t *>(mp) = (uint16_t)nb_last;
+            else *reinterpret_cast<uint32_t *>(mp) = nb_last;
         }
         float p[8], aud[8], yr[8], yi[8];
         {
@@ -170,7 +184,7 @@ SSDR_DEV void channel_frames_dec(const SsdrAudioArgs &a, const uint32_t ch, cons
                 }
             }
             lds_sync();
-            const bool clip = wave_any(amax >= 32767.0f);
+            const bool clip = BLANK ? nb_clip : wave_any(amax >= 32767.0f);     // (the flag reports the input as it came)
 #pragma unroll
             for (int j = 0; j < 8; j++) { yr[j] = 0.0f; yi[j] = 0.0f; }
             // the D stream filters, one after the other into the same accumulators: stream 0 first, taps ascending
@@ -253,7 +267,14 @@ SSDR_DEV void channel_frames_dec(const SsdrAudioArgs &a, const uint32_t ch, cons
             const u32x4 *lp = reinterpret_cast<const u32x4 *>(src - SSDR_FRAME * D);
             u32x4 *hp = reinterpret_cast<u32x4 *>(hist + NB * (l - (64 - TAIL_LANES)));
 #pragma unroll
-            for (int i = 0; i < NB / 4; i++) hp[i] = lp[i];
+            for (int i = 0; i < NB / 4; i++) {
+                u32x4 v = lp[i];
+                if constexpr (BLANK) {
+#pragma unroll
+                    for (int k = 0; k < 4; k++) v[k] = (nb_last >> (4 * i + k)) & 1u ? 0u : v[k];
+                }
+                hp[i] = v;
+            }
         }
         if (l == 0) {
             st.phi1 = phi1; st.phi2 = phi2; st.dc = dc; st.agc_d = agc_d;
@@ -261,6 +282,11 @@ SSDR_DEV void channel_frames_dec(const SsdrAudioArgs &a, const uint32_t ch, cons
             for (int i = 0; i < 8; i++) st.agc_m[i] = agc_m[i];
             st.prev_re = prev_re; st.prev_im = prev_im;
             a.state[ch] = st;
+            if constexpr (BLANK) {
+                SsdrNbChan q = nb[ch];
+                q.s1 = nbs.s1; q.s2 = nbs.s2; q.left = nbs.left;
+                nb[ch] = q;
+            }
         }
     }
 }
@@ -276,6 +302,24 @@ __global__ __launch_bounds__(SSDR_AUDIO_BLOCK) __attribute__((amdgpu_waves_per_e
     const uint32_t ch = blockIdx.x;
     if (ch >= a.n_ch) return;
     channel_frames_dec<D>(a, ch, l, a.consts[ch], s_z, s_h, s_taps);
+}
+
+// the same with the noise blanker, over the channels of a list (ssdr_api.cpp: every channel of the ctx once any blanker is on -- a
+// channel whose blanker is off never triggers, bit for bit the kernel above).  D = 2: the 4 waves per SIMD of the kernel above (127
+// registers, no spill).  D = 4: the kernel above fills the 168 registers of three waves exactly, and the blanker holds the lane's 32 raw
+// inputs across its two scans: held to three waves it spills 46 registers to scratch, at two it spills none (220 registers)
+template <int D>
+__global__ __launch_bounds__(SSDR_AUDIO_BLOCK) __attribute__((amdgpu_waves_per_eu(dec_phased(D) ? 2 : 4, 8))) void ssdr_audio_dec_nb_kernel(SsdrNbArgs a)
+{
+    constexpr int HOCT_S = SSDR_HIST / D / 8;
+    __shared__ __attribute__((aligned(16))) float2 s_z[dec_streams_per_phase(D) * (HOCT_S + 64) * OCT];
+    __shared__ __attribute__((aligned(16))) float2 s_h[dec_phased(D) ? D * HOCT_S * OCT : 1];
+    __shared__ __attribute__((aligned(16))) float s_taps[SSDR_NTAP_MAX + 8];
+    const int l = threadIdx.x;
+    if (blockIdx.x >= a.au.list_n) return;
+    const uint32_t ch = a.au.chan_list[blockIdx.x];
+    channel_frames_dec<D, true>(a.au, ch, l, a.au.consts[ch], s_z, s_h, s_taps, a.nb,
+                                a.mask + (uint64_t)ch * a.au.n_frames * 64 * D);
 }
 
 // One kernel per frame path: the paths differ by a factor of two in registers (the general path holds a 16-sample FIR
@@ -294,6 +338,23 @@ __global__ __launch_bounds__(SSDR_AUDIO_BLOCK) __attribute__((amdgpu_waves_per_e
     if (blockIdx.x >= a.list_n) return;
     const uint32_t ch = a.chan_list[blockIdx.x];
     channel_frames<PATH>(a, ch, l, a.consts[ch], s_z, s_taps);
+}
+
+// the same with the noise blanker (the channels of a path whose blanker is on: ssdr_api.cpp keeps them in lists of their own), held to
+// the waves per SIMD its twin above reaches (general 120 registers: 4; lane shift 86: 5; full-band AM 61: 8) and spilling nothing there
+// (128 / 92 / 64 registers; the blanker's frame step keeps nothing per sample live across the frame loop: nb_frame)
+__host__ __device__ constexpr int nb_waves(int path) { return path == PATH_GENERAL ? 4 : (path == PATH_DELAY4 ? 5 : 8); }
+template <int PATH>
+__global__ __launch_bounds__(SSDR_AUDIO_BLOCK) __attribute__((amdgpu_waves_per_eu(nb_waves(PATH), 8))) void ssdr_audio_nb_kernel(SsdrNbArgs a)
+{
+    constexpr bool FIR = PATH == PATH_GENERAL;
+    __shared__ __attribute__((aligned(16))) float2 s_z[FIR ? NOCT * OCT : 1];
+    __shared__ __attribute__((aligned(16))) float s_taps[FIR ? SSDR_NTAP_MAX + 8 : 1];
+    const int l = threadIdx.x;
+    if (blockIdx.x >= a.au.list_n) return;
+    const uint32_t ch = a.au.chan_list[blockIdx.x];
+    channel_frames<PATH, NoTap, true>(a.au, ch, l, a.au.consts[ch], s_z, s_taps, NoTap(), a.nb,
+                                      a.mask + (uint64_t)ch * a.au.n_frames * 64);
 }
 
 // ---------------------------------------------------------------- synthetic IQ (bench input)
@@ -402,6 +463,28 @@ hipError_t ssdr_launch_audio_dec(const SsdrAudioArgs &a, uint32_t decim, hipStre
 {
     if (decim == 2) hipLaunchKernelGGL(ssdr_audio_dec_kernel<2>, dim3(a.n_ch), dim3(SSDR_AUDIO_BLOCK), 0, stream, a);
     else if (decim == 4) hipLaunchKernelGGL(ssdr_audio_dec_kernel<4>, dim3(a.n_ch), dim3(SSDR_AUDIO_BLOCK), 0, stream, a);
+    else return hipErrorInvalidValue;
+    return hipGetLastError();
+}
+
+hipError_t ssdr_launch_audio_nb(const SsdrNbArgs &a, int path, hipStream_t stream)
+{
+    if (!a.au.list_n) return hipSuccess;
+    const dim3 grid(a.au.list_n), block(SSDR_AUDIO_BLOCK);
+    switch (path) {
+    case SSDR_PATH_GENERAL: hipLaunchKernelGGL(ssdr_audio_nb_kernel<PATH_GENERAL>, grid, block, 0, stream, a); break;
+    case SSDR_PATH_DELAY4: hipLaunchKernelGGL(ssdr_audio_nb_kernel<PATH_DELAY4>, grid, block, 0, stream, a); break;
+    case SSDR_PATH_AM_RAW: hipLaunchKernelGGL(ssdr_audio_nb_kernel<PATH_AM_RAW>, grid, block, 0, stream, a); break;
+    default: return hipErrorInvalidValue;
+    }
+    return hipGetLastError();
+}
+
+hipError_t ssdr_launch_audio_dec_nb(const SsdrNbArgs &a, uint32_t decim, hipStream_t stream)
+{
+    if (!a.au.list_n) return hipSuccess;
+    if (decim == 2) hipLaunchKernelGGL(ssdr_audio_dec_nb_kernel<2>, dim3(a.au.list_n), dim3(SSDR_AUDIO_BLOCK), 0, stream, a);
+    else if (decim == 4) hipLaunchKernelGGL(ssdr_audio_dec_nb_kernel<4>, dim3(a.au.list_n), dim3(SSDR_AUDIO_BLOCK), 0, stream, a);
     else return hipErrorInvalidValue;
     return hipGetLastError();
 }

@@ -30,9 +30,12 @@ enum { PATH_GENERAL = SSDR_PATH_GENERAL, PATH_DELAY4 = SSDR_PATH_DELAY4, PATH_AM
 //   PATH_AM_RAW   PATH_DELAY4 and mode AM: |x e^{j phi}| = |x|, so the envelope, the AGC level and the RSSI do not
 //                 depend on the NCO at all; the power of a sample is taken exactly in integers (I*I + Q*Q, one
 //                 v_dot2) and rounded once
-template <int PATH, typename Tap = NoTap>
+// BLANK: the impulse noise blanker (nb_frame) zeroes samples right after the loads; the tap, the ADC-overflow flag and nb_mask see
+// the input as it came, everything else -- the NCO, the filter, the FIR history in HBM -- the blanked samples.  nb: the channel's
+// blanker state, nb_mask: its mask row.  A separate instantiation: the kernels without it are the same code as before it existed.
+template <int PATH, typename Tap = NoTap, bool BLANK = false>
 SSDR_DEV void channel_frames(const SsdrAudioArgs &a, const uint32_t ch, const int l, const ssdr_chan_consts &kc,
-                             float2 *s_z, float *s_taps, const Tap &tap = Tap())
+                             float2 *s_z, float *s_taps, const Tap &tap = Tap(), SsdrNbChan *nb = nullptr, uint8_t *nb_mask = nullptr)
 {
     const uint32_t mode = kc.mode;
     const uint32_t tap_groups = kc.tap_groups;           // fma(0, z, acc) == acc exactly: all-zero 4-tap groups are skipped
@@ -110,6 +113,11 @@ SSDR_DEV void channel_frames(const SsdrAudioArgs &a, const uint32_t ch, const in
     }
     float rssi_sum = 0.0f;
     uint32_t flag_keep = 0;
+    NbRun nbs = {0, 0, 0, 0, 0};
+    if constexpr (BLANK) {
+        const SsdrNbChan q = nb[ch];
+        nbs = {q.gate, q.thresh, q.s1, q.s2, q.left};
+    }
 
     for (uint32_t f = 0; f < a.n_frames; f++, src += SSDR_FRAME, dst += SSDR_FRAME) {
         if ((f & 63u) == 0) {                               // the next 64 frames' phasors, one per lane
@@ -128,6 +136,14 @@ SSDR_DEV void channel_frames(const SsdrAudioArgs &a, const uint32_t ch, const in
             raw1 = SSDR_AUDIO_LOAD(reinterpret_cast<const u32x4 *>(src) + 1);
         }
         tap(f, raw0, raw1);
+        bool nb_clip = false;
+        if constexpr (BLANK) {
+            uint32_t r[8] = {raw0.x, raw0.y, raw0.z, raw0.w, raw1.x, raw1.y, raw1.z, raw1.w};
+            const uint32_t m = nb_frame<8>(r, l, nbs, nb_clip);
+            raw0 = u32x4{r[0], r[1], r[2], r[3]};
+            raw1 = u32x4{r[4], r[5], r[6], r[7]};
+            nb_mask[(uint64_t)f * 64 + l] = (uint8_t)m;
+        }
         const uint32_t rw[8] = {raw0.x, raw0.y, raw0.z, raw0.w, raw1.x, raw1.y, raw1.z, raw1.w};
         float p[8], aud[8];
         float yr[8], yi[8];                                 // the channel filter's output (unused on the full-band AM path)
@@ -238,6 +254,7 @@ SSDR_DEV void channel_frames(const SsdrAudioArgs &a, const uint32_t ch, const in
             if (mode == SSDR_MODE_IQ && a.iq_out)           // wave-uniform: I,Q pairs of the filtered baseband under the same gain
                 iq_pack_store(yr, yi, g, a.iq_out + ((uint64_t)ch * a.n_frames + f) * SSDR_FRAME + 8 * l);
         }
+        if constexpr (BLANK) clip = nb_clip;                // the flag reports the input as it came
         rssi_flag_step(p, clip, f, a.n_frames, l, cal, rssi_sum, flag_keep, rssi_row, flag_row);
 
         // 7. carry: phases advance one frame; the frame tail becomes the FIR history
@@ -278,6 +295,11 @@ SSDR_DEV void channel_frames(const SsdrAudioArgs &a, const uint32_t ch, const in
             for (int i = 0; i < 8; i++) st.agc_m[i] = agc_m[i];
             st.prev_re = prev_re; st.prev_im = prev_im;
             a.state[ch] = st;
+            if constexpr (BLANK) {
+                SsdrNbChan q = nb[ch];
+                q.s1 = nbs.s1; q.s2 = nbs.s2; q.left = nbs.left;
+                nb[ch] = q;
+            }
         }
     }
 }

@@ -52,6 +52,7 @@ SSDR_DEV uint32_t from_prev_lane_u(uint32_t lane0_value, uint32_t x)
 }
 // I*I + Q*Q of one raw sample, exactly, in one instruction (v_dot2_i32_i16; both components -32768 give 2^31, read unsigned)
 typedef short s16x2 __attribute__((ext_vector_type(2)));
+typedef unsigned short u16x2 __attribute__((ext_vector_type(2)));
 SSDR_DEV uint32_t iq_power(uint32_t raw)
 {
     uint32_t p;                                     // the three-operand form with a literal 0: the compiler's choice, the
@@ -342,4 +343,74 @@ SSDR_DEV bool raw_clipped(const uint32_t (&rw)[8])
         c = c || lo >= 32767 || lo <= -32767 || hi >= 32767 || hi <= -32767;
     }
     return c;
+}
+
+// ---- impulse noise blanker (ssdr_set_noise_blanker; the definition is tests/nb_ref.py) ----------------
+// Integer scans across the lanes, the SSDR_SCAN6 steps: an exact sum and an exact max, so any order gives the same value.
+SSDR_DEV uint32_t scan_add_u(uint32_t x)
+{
+#define STEP(C, M) asm("s_nop 1\n\tv_add_u32_dpp %0, %0, %0" SSDR_DPP(C, M) : "+v"(x));
+    SSDR_SCAN6(STEP)
+#undef STEP
+    return x;
+}
+SSDR_DEV uint32_t scan_max_u(uint32_t x)
+{
+#define STEP(C, M) asm("s_nop 1\n\tv_max_u32_dpp %0, %0, %0" SSDR_DPP(C, M) : "+v"(x));
+    SSDR_SCAN6(STEP)
+#undef STEP
+    return x;
+}
+
+// the blanker's carried state of one channel in registers (wave-uniform): SsdrNbChan without the padding
+struct NbRun { uint32_t gate, thresh, s1, s2, left; };
+
+// One frame of the blanker on a lane's N = 8 D consecutive raw samples (the frame is 64 N of them): zeroes the blanked ones in
+// place and returns the lane's mask (bit j = sample N l + j).  `clip` comes back as the ADC-overflow flag of the UNBLANKED samples.
+//   p = I*I + Q*Q exactly; S = sum of p >> log2(64 N) over the unblanked frame; trigger: p > thresh * min(S_{f-1}, S_{f-2}) (uint64,
+//   never while that minimum is 0); a trigger at m blanks m .. m + gate - 1, into the next frame if need be
+template <int N>
+SSDR_DEV uint32_t nb_frame(uint32_t (&rw)[N], int l, NbRun &s, bool &clip)
+{
+    constexpr uint32_t M = 64u * N;
+    constexpr int SHIFT = __builtin_ctz(M);
+    const uint32_t lmin = s.s1 < s.s2 ? s.s1 : s.s2;
+    const uint64_t t64 = (uint64_t)s.thresh * lmin;
+    const uint32_t tc = (t64 == 0 || t64 >= 0xFFFFFFFFull) ? 0xFFFFFFFFu : (uint32_t)t64;   // p <= 2^31: "p > tc" is the uint64 test
+    uint32_t part = 0, trig = 0;                    // part <= N 2^31 / M = 2^25: the frame's sum fits in 32 bits; trig: bit j = trigger
+    u16x2 rails = {0xFFFFu, 0xFFFFu};               // min over the lane's samples of (component + 32769) mod 2^16, per half
+#pragma unroll
+    for (int j = 0; j < N; j++) {
+        const uint32_t p = iq_power(rw[j]);
+        part += p >> SHIFT;
+        trig |= (uint32_t)(p > tc) << j;
+        rails = __builtin_elementwise_min(rails, __builtin_bit_cast(u16x2, rw[j]) + (u16x2){32769u, 32769u});
+    }
+    // ADC overflow as the frame paths decide it, |I| or |Q| >= 32767: a component is -32768, -32767 or 32767 exactly when
+    // (component + 32769) mod 2^16 < 3 -- one packed add and one packed min per sample, no branch
+    clip = wave_any(rails.x < 3u || rails.y < 3u);
+    // blanking ends (exclusive) as sample indices of this frame: a trigger at n ends at n + gate; the last one before a sample decides
+    const uint32_t n0 = (uint32_t)(N * l);
+    const uint32_t le = trig ? n0 + (31u - (uint32_t)__builtin_clz(trig)) + s.gate : 0u;
+    const uint32_t sc = scan_max_u(le);
+    const uint32_t from_left = from_prev_lane_u(0u, sc);
+    const uint32_t e = s.left > from_left ? s.left : from_left;
+    // ... counted from the lane's first sample: a trigger at j ends at j + gate, a scalar -- written with the lane's index n0 + j in
+    // them, the compiler kept the N ends n0 + j + gate in registers across the whole frame loop (they spilled at the twins' occupancy)
+    int d = (int)e - (int)n0;
+    uint32_t mask = 0;
+#pragma unroll
+    for (int j = 0; j < N; j++) {
+        d = (trig >> j) & 1u ? j + (int)s.gate : d;
+        const bool b = j < d;
+        mask |= (uint32_t)b << j;
+        rw[j] = b ? 0u : rw[j];
+    }
+    const uint32_t sum = lane63_u(scan_add_u(part));
+    const uint32_t last = lane63_u(sc);
+    const uint32_t ef = s.left > last ? s.left : last;
+    s.left = ef > M ? ef - M : 0u;                  // gate < M: a gate reaches into the next frame at most
+    s.s2 = s.s1;
+    s.s1 = sum;
+    return mask;
 }

@@ -55,6 +55,12 @@ struct SsdrAudioArgs {
     const uint32_t *chan_list;               // channels of this launch (one frame path), list_n of them
     uint32_t list_n;
 };
+// the impulse noise blanker of one channel (ssdr_set_noise_blanker): gate in input samples and threshold (both 0: off), the
+// unblanked frame sums S_{f-1}, S_{f-2} and the samples still to blank at the start of the next frame.  32 B.
+struct SsdrNbChan { uint32_t gate, thresh, s1, s2, left, pad[3]; };
+// the audio kernels with the blanker instantiated (ssdr_audio_nb_kernel / ssdr_audio_dec_nb_kernel): the chain's arguments, the
+// blanker state [n_ch] and the blank mask [n_ch][n_frames * 64 D] (bit i of byte j: sample 8 j + i of the channel's input)
+struct SsdrNbArgs { SsdrAudioArgs au; SsdrNbChan *nb; uint8_t *mask; };
 // frame paths of the audio kernel (ssdr_audio.hip): chosen per channel from its compiled constants
 enum { SSDR_PATH_GENERAL = 0, SSDR_PATH_DELAY4 = 1, SSDR_PATH_AM_RAW = 2, SSDR_PATH_COUNT = 3 };
 static inline int ssdr_audio_path(const ssdr_chan_consts &k)
@@ -175,6 +181,8 @@ hipError_t ssdr_launch_wf_exact(const SsdrWfArgs &a, const double2 *tw, hipStrea
 hipError_t ssdr_wf_blocks_per_cu(int *blocks);
 hipError_t ssdr_launch_audio(const SsdrAudioArgs &a, int path, hipStream_t stream);
 hipError_t ssdr_launch_audio_dec(const SsdrAudioArgs &a, uint32_t decim, hipStream_t stream);
+hipError_t ssdr_launch_audio_nb(const SsdrNbArgs &a, int path, hipStream_t stream);            // the channels of a.au.chan_list
+hipError_t ssdr_launch_audio_dec_nb(const SsdrNbArgs &a, uint32_t decim, hipStream_t stream);
 hipError_t ssdr_launch_synth(const SsdrSynthArgs &a, hipStream_t stream);
 hipError_t ssdr_launch_sqrt_selftest(unsigned long long *mismatch, hipStream_t stream);
 hipError_t ssdr_launch_sqrt_values(const float *in, float *out_scaled, float *out_int, uint32_t n, hipStream_t stream);

@@ -48,6 +48,37 @@ def table(which):
     return out
 
 
+def nb_gate_samples(gate_us, decim=1, kiwi_rate=L.RATE):
+    """The noise blanker's gate in input samples: ceil(gate_us * decim * kiwi_rate / 1e6) (ssdr_nb_gate_samples; ValueError out of range)"""
+    g = C.c_uint32()
+    if not (0 <= int(gate_us) < 2 ** 32) or lib.ssdr_nb_gate_samples(int(gate_us), int(decim), int(kiwi_rate), C.byref(g)) != L.OK:
+        raise ValueError("noise blanker gate %r us at decimation %r, %r Hz: out of range (1..10000 us)" % (gate_us, decim, kiwi_rate))
+    return g.value
+
+
+NB_GATE_US = (1, 10000)         # ssdr_set_noise_blanker's ranges; 0 in either turns the blanker off
+NB_THRESH = (2, 1000)
+
+
+def check_noise_blanker(gate_us, thresh):
+    """ValueError unless (gate_us, thresh) is something ssdr_set_noise_blanker takes: both in range, or either 0 (off)"""
+    g, t = int(gate_us), int(thresh)
+    if g == 0 or t == 0:
+        if g < 0 or t < 0:
+            raise ValueError("noise blanker gate %r us, threshold %r: negative" % (gate_us, thresh))
+        return
+    if not (NB_GATE_US[0] <= g <= NB_GATE_US[1] and NB_THRESH[0] <= t <= NB_THRESH[1]):
+        raise ValueError("noise blanker gate %r us, threshold %r: out of range (gate 1..10000 us, threshold 2..1000, 0 = off)"
+                         % (gate_us, thresh))
+
+
+def _nb_array(v, n, name):
+    a = np.broadcast_to(np.asarray(v, np.int64), (n,))
+    if ((a < 0) | (a >= 2 ** 32)).any():
+        raise ValueError("noise blanker %s %r: out of range" % (name, v))
+    return np.ascontiguousarray(a, np.uint32)
+
+
 # run_chain's channel-count floors of every new SsdrEngine: None = the library's (from the device); (0, 0) = none -- what a test suite that wants the
 # one-read kernels on its small batches sets (tests/conftest.py)
 DEFAULT_CHAIN_FLOORS = None
@@ -256,6 +287,22 @@ class SsdrEngine:
         last run_audio."""
         out = np.empty((self.n_ch, self.audio_frames), np.uint8)
         check(lib.ssdr_audio_flags(self._ctx, out.ctypes.data, 0), "ssdr_audio_flags")
+        return out
+
+    def set_noise_blanker(self, first, gate_us, thresh):
+        """The impulse noise blanker of channels first, first + 1, ... ("SET nb=<gate_us> th=<thresh>"): gate_us 1..10000, thresh 2..1000,
+        either 0 = off (array-likes, one entry per channel; a scalar with the other's length).  Resets those channels' blanker state.
+        A value that is not a uint32 (negative, or 2**32 and up) raises ValueError before the library is called; one the library refuses
+        (outside the ranges above) raises SsdrError (SSDR_EINVAL).  Either way no channel is changed."""
+        n = max(np.size(gate_us), np.size(thresh))
+        g, t = _nb_array(gate_us, n, "gate"), _nb_array(thresh, n, "threshold")
+        check(lib.ssdr_set_noise_blanker(self._ctx, int(first), n, g.ctypes.data, t.ctypes.data), "ssdr_set_noise_blanker")
+
+    def audio_nb_mask(self):
+        """-> uint8 [n_ch, n_frames*512*D/8]: the samples the blanker zeroed in the last run_audio, bit i of byte j = input sample
+        8 j + i (rows of channels whose blanker is off: 0)"""
+        out = np.empty((self.n_ch, self.audio_frames * L.FRAME * self.decim // 8), np.uint8)
+        check(lib.ssdr_audio_nb_mask(self._ctx, out.ctypes.data, 0), "ssdr_audio_nb_mask")
         return out
 
     def audio_iq(self):

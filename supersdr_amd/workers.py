@@ -40,7 +40,7 @@ import numpy as np
 
 from . import _lib as L
 from ._lib import Db2colChan, PlayChan
-from .engine import SsdrEngine, default_params
+from .engine import SsdrEngine, check_noise_blanker, default_params
 
 IQ_SPAN_KHZ = L.RATE / 1000.0          # what one channel's GPU waterfall covers: the IQ band around its centre (12 kHz; hub.iq_span_khz)
 
@@ -371,6 +371,13 @@ class IQHub:
             self.engine.set_params(channel, [p])     # raises for parameters the library refuses; the old ones stay
             self._n_iq_mode += (p.mode == L.MODE_IQ) - (self.params(channel).mode == L.MODE_IQ)
             self._params[int(channel)] = p
+
+    def set_noise_blanker(self, channel, gate_us, thresh):
+        """"SET nb=<gate_us> th=<thresh>" of one channel (ssdr_set_noise_blanker; either 0 = off): resets the channel's blanker state,
+        nothing else.  ValueError out of range, and then nothing changes."""
+        check_noise_blanker(gate_us, thresh)
+        with self._lock:
+            self.engine.set_noise_blanker(channel, [int(gate_us)], [int(thresh)])
 
     def set_wf_center(self, channel, offset_hz):
         """zoom centre of one channel, Hz from the centre of its IQ band (restarts that channel's zoomed stream)"""
@@ -763,6 +770,9 @@ class GpuStream:
     channel's ssdr_chan_params (a13):
         "SET mod=%s low_cut=%d high_cut=%d freq=%.3f"                    utils_supersdr.py:976, 1028
         "SET agc=%d hang=%d thresh=%d slope=%d decay=%d manGain=%d"      :979, 1023
+    "SET nb=%d th=%d" (kiwi/client.py set_noise_blanker) sets the channel's impulse noise blanker (ssdr_set_noise_blanker: gate in
+    microseconds 1..10000, threshold 2..1000, either 0 = off); a value out of range raises ValueError.  Kiwi's newer "SET nb algo=..."
+    interface is not this one and is ignored, as is "SET squelch=..." (no squelch here).
     "SET zoom=%d start=%d" (:741, 839) is remembered (`zoom`, `start`); the rest (auth, keepalive, compression, ...)
     has no meaning without a server and is accepted.  A modulation without a demodulator here, or a frequency outside
     the channel's IQ band, raises ValueError instead of being demodulated as something else.  "SET mod=iq" selects the
@@ -804,6 +814,12 @@ class GpuStream:
                              agc_slope=float(kv.get("slope", 0)), agc_decay=float(kv.get("decay", 4000)),
                              agc_man_gain=float(kv.get("manGain", 50)))
             self.hub.set_params(self.channel, q)
+        elif "nb" in kv:
+            if "th" not in kv:
+                raise ValueError("SET nb= without th=: %r" % (msg,))
+            gate, thresh = int(kv["nb"]), int(kv["th"])
+            check_noise_blanker(gate, thresh)
+            self.hub.set_noise_blanker(self.channel, gate, thresh)
         elif "zoom" in kv:
             self.zoom, self.start = int(kv["zoom"]), int(kv.get("start", 0))
 
