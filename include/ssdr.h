@@ -331,6 +331,36 @@ int ssdr_wire_gps(ssdr_ctx *ctx, uint32_t *gps_out);
  * independent streams of n_bytes each (host memory, [n_streams][n_bytes]); state int32 [n_streams][2] =
  * {index, prev} in/out (zero it per W/F line, keep it across SND frames); out int16 [n_streams][2*n_bytes]. */
 int ssdr_adpcm_decode(ssdr_ctx *ctx, const uint8_t *data, uint32_t n_streams, uint32_t n_bytes, int32_t *state, int16_t *out);
+/* Its encoder, the stand-alone twin: the standard IMA encoder run in lockstep with the decoder above (tests/adpcm_ref.py is the
+ * definition).  pcm int16 [n_streams][n_samples] (host memory), n_samples even and > 0; state int32
+ * [n_streams][2] = {index, prev} in/out (index 0..88, prev an int16 value, else SSDR_EINVAL); out uint8 [n_streams][n_samples/2],
+ * low nibble first. */
+int ssdr_adpcm_encode(ssdr_ctx *ctx, const int16_t *pcm, uint32_t n_streams, uint32_t n_samples, int32_t *state, uint8_t *out);
+
+/* -- wire compression: the KiwiSDR's "SET compression=1" (SND) and "SET wf_comp=1" (W/F), kiwi/client.py:296-305
+ * A channel flagged for SND has the PCM of every audio run encoded on the GPU: ssdr_run_audio, ssdr_run_chain (every *fused
+ * path; with the stages side by side on the audio stage's stream) launch the encoder behind the audio stage, so the channel's
+ * encoder state -- which persists for the whole connection, as the client's decoder does (kiwi/client.py:461-464) -- advances
+ * exactly once per batch.  A frame is 256 bytes for 512 samples.  Channels in SSDR_MODE_IQ are never compressed: their rows are
+ * zero and their state does not move.  A channel flagged for W/F has every byte line of ssdr_run_wf (N = 1) encoded from
+ * (0, 0): the 1024 bytes as samples 0..255 and 10 samples repeating the last one, 517 bytes (the client decodes 1034 samples
+ * and keeps 1024, :476-479).  With no flag set nothing is launched.  The encoder is timed as SSDR_K_ADPCM (with profiling on).
+ * While any flag is set ssdr_feed_open and ssdr_checkpoint_save / _load return SSDR_ESTATE.  ssdr_reset_state leaves the
+ * encoder state alone: it belongs to the link, not to the DSP. */
+/* Channels [first, first + count): snd_on / wf_on uint8 [count], 0 off, anything else on; either pointer may be NULL (that flag
+ * stays as it is).  An SND flag going from 0 to 1 resets the channel's encoder state to (0, 0), where a new decoder starts;
+ * setting one that is already on does not.  SSDR_ESTATE while a pipelined feed is open. */
+int ssdr_set_compression(ssdr_ctx *ctx, uint32_t first, uint32_t count, const uint8_t *snd_on, const uint8_t *wf_on);
+/* The flagged channels, ascending (which: 0 SND, 1 W/F): *count of them; list (may be NULL) receives them.  The rows of
+ * ssdr_audio_adpcm / ssdr_wf_adpcm are in this order. */
+int ssdr_compression_channels(ssdr_ctx *ctx, int which, uint32_t *list, uint32_t *count);
+/* The SND payloads of the last audio run: out uint8 [n_snd][n_frames * 256], a row per SND-flagged channel.  SSDR_ESTATE if no
+ * SND flag is set, or there has been no audio run with the flags as they are. */
+int ssdr_audio_adpcm(ssdr_ctx *ctx, uint8_t *out, int out_is_device);
+/* The W/F payloads of the last ssdr_run_wf: out uint8 [*lines][n_wf][517] (out may be NULL: *lines only).  *lines = 0 when that
+ * run's N was not 1 (only byte lines go on the wire).  SSDR_ESTATE if no W/F flag is set, or there has been no ssdr_run_wf with the
+ * flags as they are. */
+int ssdr_wf_adpcm(ssdr_ctx *ctx, uint8_t *out, uint32_t *lines, int out_is_device);
 
 /* -- pipelined host feed: the path a live ingest takes (KiwiSDRStream._process_iq_samples -> batches, kiwi/client.py:493)
  *
@@ -414,7 +444,7 @@ int ssdr_set_profiling(ssdr_ctx *ctx, int on);                  /* HIP-event pai
 /* bit 0: run the audio stage on a second stream beside the waterfall kernel (which then takes one workgroup per CU);
  * bit 1: run the audio stage's per-path kernels one after the other instead of side by side (measurement only) */
 int ssdr_set_concurrent(ssdr_ctx *ctx, int on);
-enum { SSDR_K_WF = 0, SSDR_K_AUDIO = 1, SSDR_K_SYNTH = 2, SSDR_K_DB2COL = 3, SSDR_K_PLAY = 4, SSDR_K_WIRE = 5, SSDR_K_TRACE = 6, SSDR_K_SMETER = 7, SSDR_K_FUSED = 8, SSDR_K_ZOOM = 9, SSDR_K_COUNT = 10 };
+enum { SSDR_K_WF = 0, SSDR_K_AUDIO = 1, SSDR_K_SYNTH = 2, SSDR_K_DB2COL = 3, SSDR_K_PLAY = 4, SSDR_K_WIRE = 5, SSDR_K_TRACE = 6, SSDR_K_SMETER = 7, SSDR_K_FUSED = 8, SSDR_K_ZOOM = 9, SSDR_K_ADPCM = 10, SSDR_K_COUNT = 11 };
 int ssdr_kernel_stats(ssdr_ctx *ctx, int which, float *total_ms, uint32_t *launches, int reset);
 /* channels per frame path of the audio stage (one kernel each, timed together as SSDR_K_AUDIO): counts[0] general
  * (NCO -> FIR), counts[1] full-band lane shift, counts[2] full-band AM (no NCO, no FIR) */

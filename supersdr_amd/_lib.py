@@ -13,7 +13,7 @@ NFFT, FRAME, RATE, NTAP_MAX, HIST = 1024, 512, 12000, 128, 128
 OK, EINVAL, ENOMEM, EHIP, ENODEV, ESTATE = 0, -1, -2, -3, -4, -5
 MODE_AM, MODE_LSB, MODE_USB, MODE_CW, MODE_NBFM, MODE_IQ = range(6)
 MODE_BY_NAME = {"am": 0, "lsb": 1, "usb": 2, "cw": 3, "nbfm": 4, "nfm": 4, "iq": 5}
-K_WF, K_AUDIO, K_SYNTH, K_DB2COL, K_PLAY, K_WIRE, K_TRACE, K_SMETER, K_FUSED, K_ZOOM = range(10)
+K_WF, K_AUDIO, K_SYNTH, K_DB2COL, K_PLAY, K_WIRE, K_TRACE, K_SMETER, K_FUSED, K_ZOOM, K_ADPCM = range(11)
 T_WINDOW, T_TWIDDLE_RE, T_TWIDDLE_IM, T_DB_THRESH = range(4)
 
 
@@ -111,6 +111,11 @@ _SIGS = {
     "ssdr_push_iq_wire": (C.c_int, [_P, _P, C.c_uint32, _P]),
     "ssdr_wire_gps": (C.c_int, [_P, _P]),
     "ssdr_adpcm_decode": (C.c_int, [_P, _P, C.c_uint32, C.c_uint32, _P, _P]),
+    "ssdr_adpcm_encode": (C.c_int, [_P, _P, C.c_uint32, C.c_uint32, _P, _P]),
+    "ssdr_set_compression": (C.c_int, [_P, C.c_uint32, C.c_uint32, _P, _P]),
+    "ssdr_compression_channels": (C.c_int, [_P, C.c_int, _P, C.POINTER(C.c_uint32)]),
+    "ssdr_audio_adpcm": (C.c_int, [_P, _P, C.c_int]),
+    "ssdr_wf_adpcm": (C.c_int, [_P, _P, C.POINTER(C.c_uint32), C.c_int]),
     "ssdr_feed_open": (C.c_int, [_P, C.c_uint32, C.c_uint32, C.c_uint32]),
     "ssdr_feed_slot": (C.c_int, [_P, C.POINTER(_P)]),
     "ssdr_feed_submit": (C.c_int, [_P]),

@@ -205,6 +205,20 @@ struct ssdr_ctx {
     uint32_t nb_mask_frames = 0, nb_mask_decim = 1;
     std::vector<uint8_t> nb_mask_on;                    // which channels blanked in that run
     uint64_t nb_mask_gen = ~0ull;
+    // IMA-ADPCM wire compression (ssdr_set_compression): created at its first use; with no flag set nothing is launched
+    std::vector<uint8_t> h_comp_snd, h_comp_wf;         // [n_ch] flags
+    std::vector<uint32_t> h_comp_list;                  // [2][n_ch] the flagged channels, ascending: SND, then W/F (mirror of d_comp_list)
+    uint32_t comp_snd_n = 0, comp_wf_n = 0;
+    uint32_t *d_comp_list = nullptr;
+    int32_t *d_adpcm_state = nullptr;                   // [n_ch][2] the SND encoder's (index, prev): the link's, not the DSP's
+    uint8_t *d_snd_adpcm = nullptr;                     // [comp_snd_n][n_frames * 256] of the last audio run
+    size_t snd_adpcm_bytes = 0;
+    bool snd_adpcm_valid = false;
+    uint32_t snd_adpcm_frames = 0;
+    uint8_t *d_wf_adpcm = nullptr;                      // [lines][comp_wf_n][517] of the last ssdr_run_wf
+    size_t wf_adpcm_bytes = 0;
+    bool wf_adpcm_valid = false;
+    uint32_t wf_adpcm_lines = 0;
 };
 
 static int get_event(ssdr_ctx *c, hipEvent_t *e)
@@ -282,7 +296,7 @@ void ssdr_destroy(ssdr_ctx *c)
                     c->d_iq_own, c->d_wf_out, c->d_pcm, c->d_rssi, c->d_flags, c->d_scratch, c->d_db2col, c->d_color, c->d_play,
                     c->d_play_taps, c->d_play_hist, c->d_play_hist_alt, c->d_play_rs_taps, c->d_play_out, c->d_wfdata, c->d_wfpend, c->d_trace, c->d_trace_y, c->d_smeter,
                     c->d_smeter_in, c->d_post_sel, c->d_wire, c->d_wire_rssi, c->d_play_mono, c->d_line1, c->d_dbchan1, c->d_color1, c->d_tw64, c->d_wire_gps, c->d_iq_out, c->d_zoom_taps, c->d_zoom_dphi, c->d_zoom_phase, c->d_zoom_hist, c->d_zoom_out,
-                    c->d_nb, c->d_nb_mask};
+                    c->d_nb, c->d_nb_mask, c->d_comp_list, c->d_adpcm_state, c->d_snd_adpcm, c->d_wf_adpcm};
     for (void *p : ptrs)
         if (p) (void)hipFree(p);
     if (c->ev0) (void)hipEventDestroy(c->ev0);
@@ -902,6 +916,86 @@ static int validate_wf_batch(const ssdr_ctx *c)
     return SSDR_OK;
 }
 
+// ---- IMA-ADPCM wire compression: the encoder behind the stages (ssdr_set_compression) -------------------------------------
+// room for the SND payloads of an audio run of the current batch
+static int adpcm_snd_alloc(ssdr_ctx *c)
+{
+    const size_t need = (size_t)c->comp_snd_n * c->in_frames * (SSDR_FRAME / 2);
+    if (c->snd_adpcm_bytes >= need) return SSDR_OK;
+    { int rcd = drain_audio(c); if (rcd != SSDR_OK) return rcd; }
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    if (c->d_snd_adpcm) { HIP_TRY(hipFree(c->d_snd_adpcm)); c->d_snd_adpcm = nullptr; }
+    c->snd_adpcm_bytes = 0;
+    c->snd_adpcm_valid = false;
+    HIP_TRY(hipMalloc(&c->d_snd_adpcm, need));
+    c->snd_adpcm_bytes = need;
+    return SSDR_OK;
+}
+// the SND payloads of the audio stage just queued on `s` (its PCM), behind it on the same stream: the state advances once per batch
+static int adpcm_snd_launch(ssdr_ctx *c, hipStream_t s)
+{
+    if (!c->comp_snd_n) return SSDR_OK;
+    SsdrAdpcmArgs e;
+    e.src = c->d_pcm;
+    e.row_stride = (uint64_t)c->in_frames * SSDR_FRAME;
+    e.line_stride = 0;
+    e.list = c->d_comp_list;
+    e.n_sel = c->comp_snd_n;
+    e.n_lines = 1;
+    e.n_samples = c->in_frames * SSDR_FRAME;
+    e.consts = c->d_consts;
+    e.state = c->d_adpcm_state;
+    e.out = c->d_snd_adpcm;
+    e.out_stride = (uint64_t)c->in_frames * (SSDR_FRAME / 2);
+    int rc;
+    if (c->profiling && (rc = timed_begin(c, s)) != SSDR_OK) return rc;       // (untimed otherwise: ssdr_elapsed_ms stays the stage's)
+    HIP_TRY(ssdr_launch_adpcm_enc(e, s));
+    if (c->profiling && (rc = timed_end(c, SSDR_K_ADPCM, s)) != SSDR_OK) return rc;
+    c->snd_adpcm_valid = true;
+    c->snd_adpcm_frames = c->in_frames;
+    return SSDR_OK;
+}
+// room for the W/F payloads of `lines` byte lines (the encoder only ever runs on the main stream)
+static int adpcm_wf_alloc(ssdr_ctx *c, uint32_t lines)
+{
+    const size_t need = (size_t)c->comp_wf_n * lines * SSDR_ADPCM_WF_BYTES;
+    if (c->wf_adpcm_bytes >= need) return SSDR_OK;
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    if (c->d_wf_adpcm) { HIP_TRY(hipFree(c->d_wf_adpcm)); c->d_wf_adpcm = nullptr; }
+    c->wf_adpcm_bytes = 0;
+    c->wf_adpcm_valid = false;
+    HIP_TRY(hipMalloc(&c->d_wf_adpcm, need));
+    c->wf_adpcm_bytes = need;
+    return SSDR_OK;
+}
+// the W/F payloads of the lines the waterfall stage just queued on `s`: only byte lines (N = 1) go on the wire
+static int adpcm_wf_launch(ssdr_ctx *c, hipStream_t s, uint32_t n_avg)
+{
+    if (!c->comp_wf_n) return SSDR_OK;
+    const uint32_t lines = n_avg == 1 ? c->wf_lines_ready : 0;
+    if (lines) {
+        SsdrAdpcmArgs e;
+        e.src = c->d_wf_out;
+        e.row_stride = SSDR_NFFT;
+        e.line_stride = (uint64_t)c->n_ch * SSDR_NFFT;
+        e.list = c->d_comp_list + c->n_ch;
+        e.n_sel = c->comp_wf_n;
+        e.n_lines = lines;
+        e.n_samples = SSDR_NFFT;
+        e.consts = nullptr;
+        e.state = nullptr;
+        e.out = c->d_wf_adpcm;
+        e.out_stride = SSDR_ADPCM_WF_BYTES;
+        int rc;
+        if (c->profiling && (rc = timed_begin(c, s)) != SSDR_OK) return rc;
+        HIP_TRY(ssdr_launch_adpcm_enc_wf(e, s));
+        if (c->profiling && (rc = timed_end(c, SSDR_K_ADPCM, s)) != SSDR_OK) return rc;
+    }
+    c->wf_adpcm_valid = true;
+    c->wf_adpcm_lines = lines;
+    return SSDR_OK;
+}
+
 int ssdr_run_wf(ssdr_ctx *c, int16_t *wf_sum_out, uint32_t *lines_ready, int out_is_device) SSDR_GUARD
 {
     if (!c) return SSDR_EINVAL;
@@ -940,6 +1034,8 @@ int ssdr_run_wf(ssdr_ctx *c, int16_t *wf_sum_out, uint32_t *lines_ready, int out
         HIP_TRY(hipMalloc(&c->d_wf_out, (size_t)n_out * c->n_ch * SSDR_NFFT * 2));
         c->wf_out_lines = n_out;
     }
+    if (c->comp_wf_n && c->n_avg == 1) { int rca = adpcm_wf_alloc(c, n_out); if (rca != SSDR_OK) return rca; }
+    c->wf_adpcm_valid = false;
     SsdrWfArgs a;
     a.iq = wf_src;
     a.ch_stride = wf_stride;
@@ -986,6 +1082,7 @@ int ssdr_run_wf(ssdr_ctx *c, int16_t *wf_sum_out, uint32_t *lines_ready, int out
     if (c->wf_phase) c->wf_acc_cur ^= 1;             // a partial group was written to acc_out
     c->wf_lines_ready = n_out;
     if (lines_ready) *lines_ready = n_out;
+    if (!c->fuse_next) { int rca = adpcm_wf_launch(c, c->stream, c->n_avg); if (rca != SSDR_OK) return rca; }   // (fused: ssdr_run_audio)
     if (wf_sum_out && n_out) {
         const size_t bytes = (size_t)n_out * c->n_ch * SSDR_NFFT * 2;
         HIP_TRY(hipMemcpyAsync(wf_sum_out, c->d_wf_out, bytes, out_is_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, c->stream));
@@ -1027,6 +1124,8 @@ int ssdr_run_audio(ssdr_ctx *c, int16_t *pcm_out, float *rssi_out, int out_is_de
         HIP_TRY(hipMalloc(&c->d_nb_mask, nb_mask_need));
         c->nb_mask_bytes = nb_mask_need;
     }
+    { int rca = adpcm_snd_alloc(c); if (rca != SSDR_OK) return rca; }
+    c->snd_adpcm_valid = false;
     SsdrAudioArgs a;
     a.iq = c->d_iq;
     a.ch_stride = (uint64_t)in_len(c, c->in_frames);
@@ -1094,6 +1193,8 @@ int ssdr_run_audio(ssdr_ctx *c, int16_t *pcm_out, float *rssi_out, int out_is_de
         if (fa.wf.tail)          // hop 512: only now may the carried half-line (the kernel's line 0 read it) become this batch's last one
             HIP_TRY(hipMemcpy2DAsync(c->d_wf_tail, (SSDR_NFFT / 2) * 4, fa.wf.iq + (size_t)(fa.wf.n_lines - 1) * SSDR_FRAME,
                                      fa.wf.ch_stride * 4, (SSDR_NFFT / 2) * 4, c->n_ch, hipMemcpyDeviceToDevice, s));
+        if ((rc = adpcm_snd_launch(c, s)) != SSDR_OK) return rc;          // the encoders behind the one-read kernel
+        if ((rc = adpcm_wf_launch(c, s, fa.wf.n_avg)) != SSDR_OK) return rc;
         return SSDR_OK;
     }
     // one kernel per non-empty path: the first on the stream itself, the others beside it on their own streams
@@ -1152,6 +1253,7 @@ int ssdr_run_audio(ssdr_ctx *c, int16_t *pcm_out, float *rssi_out, int out_is_de
             c->nb_mask_gen = c->nb_gen;
         }
     }
+    if ((rc = adpcm_snd_launch(c, s)) != SSDR_OK) return rc;
     const hipMemcpyKind kind = out_is_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
     if (pcm_out) HIP_TRY(hipMemcpyAsync(pcm_out, c->d_pcm, (size_t)c->n_ch * c->in_frames * SSDR_FRAME * 2, kind, s));
     if (rssi_out) HIP_TRY(hipMemcpyAsync(rssi_out, c->d_rssi, (size_t)c->n_ch * c->in_frames * sizeof(float), kind, s));
@@ -1449,7 +1551,8 @@ int ssdr_feed_close(ssdr_ctx *c) SSDR_GUARD
 int ssdr_feed_open(ssdr_ctx *c, uint32_t n_frames, uint32_t depth, uint32_t flags) SSDR_GUARD
 {
     if (!c || n_frames == 0 || (n_frames & 1u) || depth < 2 || depth > 16 || (flags & ~(uint32_t)(SSDR_FEED_WIRE | SSDR_FEED_POST | SSDR_FEED_LAZY_OUT))) return SSDR_EINVAL;
-    if (!c->feed.empty() || c->concurrent || c->decim != 1 || c->zoom != 1) return SSDR_ESTATE;      // the feed's slots are sized for un-zoomed 12 kHz IQ
+    if (!c->feed.empty() || c->concurrent || c->decim != 1 || c->zoom != 1) return SSDR_ESTATE;
+    if (c->comp_snd_n || c->comp_wf_n) return SSDR_ESTATE;                  // no wire compression in the slot pipeline      // the feed's slots are sized for un-zoomed 12 kHz IQ
     HIP_TRY(hipSetDevice(c->device));
     const bool post = (flags & SSDR_FEED_POST) != 0;
     if (post) { int rcp = ensure_play(c); if (rcp != SSDR_OK) return rcp; }
@@ -1837,6 +1940,7 @@ int ssdr_checkpoint_save(ssdr_ctx *c, void *blob) SSDR_GUARD
     const size_t n = c->n_ch;
     if (c->zoom > 1) return SSDR_ESTATE;                     // the zoomed waterfall stream (phase, history, centres) is not part of the blob
     if (c->nb_on) return SSDR_ESTATE;                        // nor is the noise blanker's state
+    if (c->comp_snd_n || c->comp_wf_n) return SSDR_ESTATE;   // nor the wire encoders'
     SsdrCkptHeader h = {kCkptMagic, kCkptVersion, c->n_ch, c->n_avg, c->wf_phase, c->audio_started ? 1u : 0u, c->kiwi_rate,
                         c->d_play_hist ? 1u : 0u, c->synth_sample0, c->hop, c->decim};
     char *p = static_cast<char *>(blob);
@@ -1881,7 +1985,7 @@ int ssdr_checkpoint_load(ssdr_ctx *c, const void *blob, uint64_t bytes) SSDR_GUA
     std::vector<float> ktaps(n * SSDR_NTAP_MAX);
     for (size_t i = 0; i < n; i++)
         if (ssdr_compile_params_host(&prm[i], &kc[i], ktaps.data() + i * SSDR_NTAP_MAX, h.decim, h.kiwi_rate) != SSDR_OK) return SSDR_EINVAL;
-    if (!c->feed.empty() || c->zoom > 1 || c->nb_on) return SSDR_ESTATE;
+    if (!c->feed.empty() || c->zoom > 1 || c->nb_on || c->comp_snd_n || c->comp_wf_n) return SSDR_ESTATE;
     std::vector<double> play_hist;                          // play_buffer state that arrives before its buffers exist: applied at first use
     if (h.has_play && !c->d_play_hist) {
         const double *q = reinterpret_cast<const double *>(static_cast<const char *>(blob) + sizeof h + n * (sizeof(ssdr_chan_consts) +
@@ -2366,6 +2470,139 @@ int ssdr_adpcm_decode(ssdr_ctx *c, const uint8_t *data, uint32_t n_streams, uint
     if (d_st) (void)hipFree(d_st);
     if (d_out) (void)hipFree(d_out);
     return rc;
+} SSDR_UNGUARD
+
+int ssdr_adpcm_encode(ssdr_ctx *c, const int16_t *pcm, uint32_t n_streams, uint32_t n_samples, int32_t *state, uint8_t *out) SSDR_GUARD
+{
+    if (!c || !pcm || !state || !out || n_streams == 0 || n_samples == 0 || (n_samples & 1u)) return SSDR_EINVAL;
+    for (uint32_t i = 0; i < n_streams; i++)
+        if (state[2 * i] < 0 || state[2 * i] > 88 || state[2 * i + 1] < -32768 || state[2 * i + 1] > 32767) return SSDR_EINVAL;
+    HIP_TRY(hipSetDevice(c->device));
+    int16_t *d_in = nullptr;
+    int32_t *d_st = nullptr;
+    uint8_t *d_out = nullptr;
+    const size_t n_in = (size_t)n_streams * n_samples;
+    int rc = [&]() -> int {
+        HIP_TRY(hipMalloc(&d_in, n_in * 2));
+        HIP_TRY(hipMalloc(&d_st, (size_t)n_streams * 8));
+        HIP_TRY(hipMalloc(&d_out, n_in / 2));
+        HIP_TRY(hipMemcpyAsync(d_in, pcm, n_in * 2, hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(hipMemcpyAsync(d_st, state, (size_t)n_streams * 8, hipMemcpyHostToDevice, c->stream));
+        SsdrAdpcmArgs e;
+        e.src = d_in;
+        e.row_stride = n_samples;
+        e.line_stride = 0;
+        e.list = nullptr;
+        e.n_sel = n_streams;
+        e.n_lines = 1;
+        e.n_samples = n_samples;
+        e.consts = nullptr;
+        e.state = d_st;
+        e.out = d_out;
+        e.out_stride = n_samples / 2;
+        HIP_TRY(ssdr_launch_adpcm_enc(e, c->stream));
+        HIP_TRY(hipMemcpyAsync(out, d_out, n_in / 2, hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(hipMemcpyAsync(state, d_st, (size_t)n_streams * 8, hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(hipStreamSynchronize(c->stream));
+        return SSDR_OK;
+    }();
+    if (d_in) (void)hipFree(d_in);
+    if (d_st) (void)hipFree(d_st);
+    if (d_out) (void)hipFree(d_out);
+    return rc;
+} SSDR_UNGUARD
+
+int ssdr_set_compression(ssdr_ctx *c, uint32_t first, uint32_t count, const uint8_t *snd_on, const uint8_t *wf_on) SSDR_GUARD
+{
+    if (!c || (uint64_t)first + count > c->n_ch) return SSDR_EINVAL;
+    if (!c->feed.empty()) return SSDR_ESTATE;
+    if (!count || (!snd_on && !wf_on)) return SSDR_OK;
+    HIP_TRY(hipSetDevice(c->device));
+    if (!c->d_comp_list) {                                  // first use: flags, channel lists, encoder state
+        c->h_comp_snd.assign(c->n_ch, 0);
+        c->h_comp_wf.assign(c->n_ch, 0);
+        c->h_comp_list.assign(2 * (size_t)c->n_ch, 0u);
+        { int rcj = join_audio(c); if (rcj != SSDR_OK) return rcj; }
+        int32_t *st = nullptr;
+        HIP_TRY(hipMalloc(&st, (size_t)c->n_ch * 8));
+        c->d_adpcm_state = st;
+        HIP_TRY(hipMemsetAsync(c->d_adpcm_state, 0, (size_t)c->n_ch * 8, c->stream));
+        uint32_t *l = nullptr;
+        HIP_TRY(hipMalloc(&l, 2 * (size_t)c->n_ch * sizeof(uint32_t)));
+        c->d_comp_list = l;
+        HIP_TRY(hipStreamSynchronize(c->stream));
+    }
+    std::vector<uint32_t> fresh;                            // channels whose SND flag goes from 0 to 1: a new decoder starts at (0, 0)
+    bool snd_changed = false, wf_changed = false;
+    for (uint32_t i = 0; i < count; i++) {
+        const uint32_t ch = first + i;
+        if (snd_on) {
+            const uint8_t on = snd_on[i] != 0;
+            if (on != c->h_comp_snd[ch]) {
+                snd_changed = true;
+                if (on) fresh.push_back(ch);
+                c->h_comp_snd[ch] = on;
+            }
+        }
+        if (wf_on) {
+            const uint8_t on = wf_on[i] != 0;
+            if (on != c->h_comp_wf[ch]) { wf_changed = true; c->h_comp_wf[ch] = on; }
+        }
+    }
+    if (!snd_changed && !wf_changed) return SSDR_OK;
+    uint32_t ns = 0, nw = 0;
+    for (uint32_t ch = 0; ch < c->n_ch; ch++) {
+        if (c->h_comp_snd[ch]) c->h_comp_list[ns++] = ch;
+        if (c->h_comp_wf[ch]) c->h_comp_list[c->n_ch + nw++] = ch;
+    }
+    { int rcj = join_audio(c); if (rcj != SSDR_OK) return rcj; }     // an encoder in flight reads the lists and the state
+    HIP_TRY(hipMemcpyAsync(c->d_comp_list, c->h_comp_list.data(), 2 * (size_t)c->n_ch * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
+    for (size_t i = 0; i < fresh.size();) {                 // (index, prev) = (0, 0), a run of consecutive channels at a time
+        size_t j = i + 1;
+        while (j < fresh.size() && fresh[j] == fresh[j - 1] + 1) j++;
+        HIP_TRY(hipMemsetAsync(c->d_adpcm_state + 2 * (size_t)fresh[i], 0, (j - i) * 8, c->stream));
+        i = j;
+    }
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    c->comp_snd_n = ns;
+    c->comp_wf_n = nw;
+    if (snd_changed) c->snd_adpcm_valid = false;           // the rows of the last run were another selection's
+    if (wf_changed) c->wf_adpcm_valid = false;
+    return SSDR_OK;
+} SSDR_UNGUARD
+
+int ssdr_compression_channels(ssdr_ctx *c, int which, uint32_t *list, uint32_t *count) SSDR_GUARD
+{
+    if (!c || !count || (which != 0 && which != 1)) return SSDR_EINVAL;
+    const uint32_t n = which == 0 ? c->comp_snd_n : c->comp_wf_n;
+    *count = n;
+    if (list && n) memcpy(list, c->h_comp_list.data() + (which == 0 ? 0 : (size_t)c->n_ch), (size_t)n * sizeof(uint32_t));
+    return SSDR_OK;
+} SSDR_UNGUARD
+
+int ssdr_audio_adpcm(ssdr_ctx *c, uint8_t *out, int out_is_device) SSDR_GUARD
+{
+    if (!c || !out) return SSDR_EINVAL;
+    if (!c->comp_snd_n || !c->snd_adpcm_valid) return SSDR_ESTATE;
+    HIP_TRY(hipSetDevice(c->device));
+    { int rcj = join_audio(c); if (rcj != SSDR_OK) return rcj; }
+    const size_t bytes = (size_t)c->comp_snd_n * c->snd_adpcm_frames * (SSDR_FRAME / 2);
+    HIP_TRY(hipMemcpyAsync(out, c->d_snd_adpcm, bytes, out_is_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return SSDR_OK;
+} SSDR_UNGUARD
+
+int ssdr_wf_adpcm(ssdr_ctx *c, uint8_t *out, uint32_t *lines, int out_is_device) SSDR_GUARD
+{
+    if (!c || !lines) return SSDR_EINVAL;
+    if (!c->comp_wf_n || !c->wf_adpcm_valid) return SSDR_ESTATE;
+    *lines = c->wf_adpcm_lines;
+    if (!out || !c->wf_adpcm_lines) return SSDR_OK;
+    HIP_TRY(hipSetDevice(c->device));
+    const size_t bytes = (size_t)c->wf_adpcm_lines * c->comp_wf_n * SSDR_ADPCM_WF_BYTES;
+    HIP_TRY(hipMemcpyAsync(out, c->d_wf_adpcm, bytes, out_is_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return SSDR_OK;
 } SSDR_UNGUARD
 
 int ssdr_set_wf_lines(ssdr_ctx *c, const int16_t *wf_sum, uint32_t lines) SSDR_GUARD

@@ -146,6 +146,23 @@ hipError_t ssdr_launch_smeter(const SsdrSmeterArgs &a, hipStream_t stream);
 hipError_t ssdr_launch_checksum(const void *data, uint64_t n_words, unsigned long long *out, hipStream_t stream);
 hipError_t ssdr_launch_adpcm(const uint8_t *data, uint32_t n_streams, uint32_t n_bytes, int32_t *state, int16_t *out,
                              hipStream_t stream);
+// IMA-ADPCM encoder (ssdr_adpcm_enc.hip): one lane per row of samples, rows = n_lines * n_sel; row (line, pos) reads
+// src + line * line_stride + list[pos] * row_stride (list null: pos) and writes out + row * out_stride (n_samples / 2 bytes, + 5 for W/F)
+#define SSDR_ADPCM_WF_PAD 10                 // W/F lines: samples repeating the last byte behind the 1024 (kiwi/client.py:476-479)
+#define SSDR_ADPCM_WF_BYTES ((SSDR_NFFT + SSDR_ADPCM_WF_PAD) / 2)
+struct SsdrAdpcmArgs {
+    const int16_t *src;
+    uint64_t row_stride, line_stride;        // samples
+    const uint32_t *list;                    // [n_sel] channels, ascending (null: row pos is channel pos)
+    uint32_t n_sel, n_lines;
+    uint32_t n_samples;                      // per row, even
+    const ssdr_chan_consts *consts;          // SND: rows of IQ-mode channels are zero and their state stays (null: no such check)
+    int32_t *state;                          // [channel][2] index, prev; in and out (null: every row starts at (0, 0))
+    uint8_t *out;
+    uint64_t out_stride;                     // bytes
+};
+hipError_t ssdr_launch_adpcm_enc(const SsdrAdpcmArgs &a, hipStream_t stream);        // SND frames / stand-alone streams
+hipError_t ssdr_launch_adpcm_enc_wf(const SsdrAdpcmArgs &a, hipStream_t stream);     // W/F lines: n_samples 1024, + the pad
 #define SSDR_ZOOM_HIST 256                   // raw input samples carried per channel (>= 32 Z - 2 for Z <= 8)
 #define SSDR_ZOOM_TAPS_MAX 255
 struct SsdrZoomArgs {

@@ -538,6 +538,69 @@ class SsdrEngine:
                                     out.ctypes.data), "ssdr_adpcm_decode")
         return out
 
+    def adpcm_encode(self, pcm, state=None):
+        """pcm int16 [n_streams, n_samples] (n_samples even); state int32 [n_streams, 2] {index, prev} (updated in place; None: (0, 0))
+        -> uint8 [n_streams, n_samples // 2].  The IMA encoder whose bytes adpcm_decode (kiwi/client.py:58-87) turns back into its
+        reconstruction, the state of both ends in step (tests/adpcm_ref.py)."""
+        pcm = np.ascontiguousarray(pcm, np.int16)
+        if pcm.ndim == 1:
+            pcm = pcm[None]
+        if state is None:
+            state = np.zeros((pcm.shape[0], 2), np.int32)
+        assert state.dtype == np.int32 and state.flags.c_contiguous and state.shape == (pcm.shape[0], 2)
+        out = np.empty((pcm.shape[0], pcm.shape[1] // 2), np.uint8)
+        check(lib.ssdr_adpcm_encode(self._ctx, pcm.ctypes.data, pcm.shape[0], pcm.shape[1], state.ctypes.data, out.ctypes.data),
+              "ssdr_adpcm_encode")
+        return out
+
+    def set_compression(self, channels, snd=None, wf=None):
+        """"SET compression=" (snd) / "SET wf_comp=" (wf) of `channels` (an int, or an iterable of channels): a bool, or one per channel;
+        None leaves that flag as it is.  An SND flag going on restarts the channel's encoder at (0, 0).  One library call per run
+        of consecutive channels."""
+        ch = np.atleast_1d(np.asarray(channels, np.int64))
+        if ch.size == 0 or (snd is None and wf is None):
+            return
+        if ((ch < 0) | (ch >= self.n_ch)).any():
+            raise ValueError("channels out of range 0..%d" % (self.n_ch - 1))
+        flags = [None if v is None else np.ascontiguousarray(np.broadcast_to(np.asarray(v) != 0, ch.shape), np.uint8) for v in (snd, wf)]
+        order = np.argsort(ch, kind="stable")
+        ch = ch[order]
+        flags = [None if f is None else np.ascontiguousarray(f[order]) for f in flags]
+        cuts = np.flatnonzero(np.diff(ch) != 1) + 1
+        for lo, hi in zip(np.r_[0, cuts], np.r_[cuts, ch.size]):
+            lo, hi = int(lo), int(hi)
+            ptrs = [None if f is None else f[lo:hi].ctypes.data for f in flags]
+            check(lib.ssdr_set_compression(self._ctx, int(ch[lo]), hi - lo, ptrs[0], ptrs[1]), "ssdr_set_compression")
+
+    def compression_channels(self, which):
+        """the flagged channels, ascending: which = "snd" or "wf" (the row order of audio_adpcm / wf_adpcm)"""
+        w = {"snd": 0, "wf": 1}[which]
+        n = C.c_uint32()
+        check(lib.ssdr_compression_channels(self._ctx, w, None, C.byref(n)), "ssdr_compression_channels")
+        out = np.empty(n.value, np.uint32)
+        check(lib.ssdr_compression_channels(self._ctx, w, out.ctypes.data if n.value else None, C.byref(n)), "ssdr_compression_channels")
+        return out
+
+    def audio_adpcm(self):
+        """-> uint8 [n_snd, audio_frames * 256]: the SND payloads of the last audio run, a row per channel of compression_channels("snd")
+        (rows of channels in "SET mod=iq": zero)"""
+        n = C.c_uint32()
+        check(lib.ssdr_compression_channels(self._ctx, 0, None, C.byref(n)), "ssdr_compression_channels")
+        out = np.empty((n.value, self.audio_frames * L.FRAME // 2), np.uint8)
+        check(lib.ssdr_audio_adpcm(self._ctx, out.ctypes.data, 0), "ssdr_audio_adpcm")
+        return out
+
+    def wf_adpcm(self):
+        """-> uint8 [lines, n_wf, 517]: the W/F payloads of the last run_wf, a row per channel of compression_channels("wf")
+        (no lines when that run summed N > 1 lines)"""
+        n, lines = C.c_uint32(), C.c_uint32()
+        check(lib.ssdr_compression_channels(self._ctx, 1, None, C.byref(n)), "ssdr_compression_channels")
+        check(lib.ssdr_wf_adpcm(self._ctx, None, C.byref(lines), 0), "ssdr_wf_adpcm")
+        out = np.empty((lines.value, n.value, 517), np.uint8)
+        if out.size:
+            check(lib.ssdr_wf_adpcm(self._ctx, out.ctypes.data, C.byref(lines), 0), "ssdr_wf_adpcm")
+        return out
+
     def set_wf_lines(self, wf_sum):
         """int16 [lines, n_ch, 1024]: stand in for the output of run_wf (golden-vector tests of run_db2col)."""
         wf_sum = np.ascontiguousarray(wf_sum, np.int16)

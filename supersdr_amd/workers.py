@@ -52,6 +52,7 @@ class Frame(np.ndarray):
     play_block = None
     rec_block = None
     iq_block = None                     # "SET mod=iq": int16 [512, 2] I,Q of the frame (the PCM samples are its I column)
+    adpcm = None                        # "SET compression=1": the frame's 256-byte IMA-ADPCM payload (bytes)
     adc_overflow = False
     rssi = -127.0
 
@@ -66,6 +67,15 @@ class Frame(np.ndarray):
         return f
 
 
+class WfLine(np.ndarray):
+    """A waterfall line in a wf_queue item (int16[1024]) of a channel with "SET wf_comp=1": also carries the line's 517-byte
+    IMA-ADPCM payload (`adpcm`, bytes).  Lines of other channels are plain arrays."""
+    adpcm = None
+
+    def __array_finalize__(self, obj):
+        pass
+
+
 class SuperframeResult:
     """What one GPU run of the hub produced, as the arrays the engine returned (all channels, no per-channel objects):
     wf int16 [lines, n_ch, 1024] sums of n_avg byte lines, pcm int16 [n_ch, frames*512], rssi float32 [n_ch, frames],
@@ -76,8 +86,11 @@ class SuperframeResult:
     On a lazy_out hub (SSDR_FEED_LAZY_OUT) wf / pcm / rssi / flags / wire_rssi too have one row per channel of out_channels (the attached
     channels at the batch's submit) instead of one per channel; out_channels None: one per channel.
     In pipeline mode the arrays are views of the feed's pinned slots: valid until `depth - 1` further superframes have
-    been collected (copy what must live longer)."""
-    __slots__ = ("seq", "wf", "n_avg", "color", "chans", "pcm", "rssi", "flags", "play", "mono", "iq", "wire_rssi", "post_channels", "out_channels")
+    been collected (copy what must live longer).
+    With wire compression on some channels (IQHub.set_compression): snd_adpcm uint8 [n, frames*256] / wf_adpcm uint8 [lines, n, 517],
+    a row per channel of snd_adpcm_channels / wf_adpcm_channels (None: no channel compresses)."""
+    __slots__ = ("seq", "wf", "n_avg", "color", "chans", "pcm", "rssi", "flags", "play", "mono", "iq", "wire_rssi", "post_channels", "out_channels",
+                 "snd_adpcm", "wf_adpcm", "snd_adpcm_channels", "wf_adpcm_channels")
 
     def __init__(self, **kw):
         for k in self.__slots__:
@@ -255,6 +268,7 @@ class IQHub:
         self._params = {}                            # channel -> ChanParams, for the channels that were given any
         self._default_params = default_params("am")
         self._n_iq_mode = 0
+        self._comp_snd, self._comp_wf = [], []       # channels with "SET compression=1" / "SET wf_comp=1", sorted (the engine's row order)
         self._want_n = np.ones(self.n_ch, np.int32)  # averaging_n asked for by each channel's waterfall client
         self._want_all = {1: self.n_ch}              # N -> channels that want it (all channels / channels with a client)
         self._want_cli = {}
@@ -378,6 +392,36 @@ class IQHub:
         check_noise_blanker(gate_us, thresh)
         with self._lock:
             self.engine.set_noise_blanker(channel, [int(gate_us)], [int(thresh)])
+
+    def compression(self, channel):
+        """-> (snd, wf): whether the channel's SND frames / W/F lines are IMA-ADPCM compressed"""
+        c = int(channel)
+        with self._lock:
+            return c in self._comp_snd, c in self._comp_wf
+
+    def set_compression(self, channel, snd=None, wf=None):
+        """"SET compression=" (snd) / "SET wf_comp=" (wf) of one channel: True / False, None leaves that flag as it is.  Frames and
+        lines produced from the next superframe on carry their ADPCM payload (Frame.adpcm, WfLine.adpcm).  Turning SND compression on
+        restarts the channel's encoder at (0, 0), where a new client's decoder starts; a request that changes nothing does not reach
+        the engine.  The pipelined hub refuses (ValueError) before the engine is touched."""
+        if self.pipeline:
+            raise ValueError("wire compression needs the synchronous hub (the pipelined feed does not run the encoder)")
+        import bisect
+        c = int(channel)
+        if not 0 <= c < self.n_ch:
+            raise IndexError("channel %d of %d" % (c, self.n_ch))
+        with self._lock:
+            s_now, w_now = c in self._comp_snd, c in self._comp_wf
+            s_new = s_now if snd is None else bool(snd)
+            w_new = w_now if wf is None else bool(wf)
+            if (s_new, w_new) == (s_now, w_now):
+                return
+            self.engine.set_compression(c, snd=None if s_new == s_now else s_new, wf=None if w_new == w_now else w_new)
+            for now, new, lst in ((s_now, s_new, self._comp_snd), (w_now, w_new, self._comp_wf)):
+                if new and not now:
+                    bisect.insort(lst, c)
+                elif now and not new:
+                    lst.remove(c)
 
     def set_wf_center(self, channel, offset_hz):
         """zoom centre of one channel, Hz from the centre of its IQ band (restarts that channel's zoomed stream)"""
@@ -584,6 +628,8 @@ class IQHub:
         wire_rssi = eng.push_iq_wire(batch) if self.wire else eng.push_iq(batch)
         n_avg = self.averaging_n
         wf = eng.run_wf()                             # [lines, n_ch, 1024]
+        wf_sel = list(self._comp_wf) if self._comp_wf else None
+        wf_adpcm = eng.wf_adpcm() if wf_sel else None                           # [lines, n_wf, 517] ("SET wf_comp=1")
         color = chans = None
         if self.gpu_post and (self._n_wf_clients or self._n_snd_clients):
             self._sync_display_state()
@@ -593,6 +639,8 @@ class IQHub:
         pcm, rssi = eng.run_audio()                   # [n_ch, frames*512], [n_ch, frames]
         flags = eng.audio_flags()                     # [n_ch, frames] SND header bit 1 (utils_supersdr.py:1066-1067)
         iqo = eng.audio_iq() if self._n_iq_mode else None                        # channels in "SET mod=iq"
+        snd_sel = list(self._comp_snd) if self._comp_snd else None
+        snd_adpcm = eng.audio_adpcm() if snd_sel else None                      # [n_snd, frames*256] ("SET compression=1")
         play = mono = None
         if self.gpu_post and self._n_snd_clients:
             rec = self._sync_recording()
@@ -601,7 +649,8 @@ class IQHub:
                 mono = eng.playbuffer_mono()
         self.superframes += 1
         self._hand_out(SuperframeResult(seq=self.superframes, wf=wf, n_avg=n_avg, color=color, chans=chans, pcm=pcm, rssi=rssi,
-                                        flags=flags, play=play, mono=mono, iq=iqo, wire_rssi=wire_rssi, post_channels=self._post_sel))
+                                        flags=flags, play=play, mono=mono, iq=iqo, wire_rssi=wire_rssi, post_channels=self._post_sel,
+                                        snd_adpcm=snd_adpcm, wf_adpcm=wf_adpcm, snd_adpcm_channels=snd_sel, wf_adpcm_channels=wf_sel))
 
     def _hand_out(self, r):
         self.last = r
@@ -610,6 +659,8 @@ class IQHub:
         P, wf, pcm = self.play_len, r.wf, r.pcm
         pos = None if r.post_channels is None else {c: i for i, c in enumerate(r.post_channels)}      # row of a channel in the post results
         opos = None if r.out_channels is None else (pos if r.out_channels is r.post_channels else {c: i for i, c in enumerate(r.out_channels)})
+        wpos = {} if r.wf_adpcm is None or not len(r.wf_adpcm) else {c: i for i, c in enumerate(r.wf_adpcm_channels)}
+        spos = {} if r.snd_adpcm is None else {c: i for i, c in enumerate(r.snd_adpcm_channels)}
         for c in self._wf_att:
             q = self.wf_queue._q[c]
             pc = c if pos is None else pos.get(c)
@@ -617,12 +668,17 @@ class IQHub:
             if oc is None:
                 continue
             has_post = r.color is not None and self.wf_clients[c] is not None and pc is not None
+            wc = wpos.get(c)
             for i in range(len(wf)):
                 post = None
                 if has_post:
                     k = r.chans[pc]
                     post = (r.color[i, pc].copy(), k.low_clip_db, k.high_clip_db, k.dynamic_range, k.wf_min_db, k.wf_max_db)
-                _put_drop_oldest(q, (wf[i, oc].copy(), r.n_avg, post))
+                line = wf[i, oc].copy()
+                if wc is not None:
+                    line = line.view(WfLine)
+                    line.adpcm = r.wf_adpcm[i, wc].tobytes()
+                _put_drop_oldest(q, (line, r.n_avg, post))
         for c in self._snd_att:
             q = self.snd_queue._q[c]
             iq_mode = r.iq is not None and self.params(c).mode == L.MODE_IQ
@@ -631,12 +687,16 @@ class IQHub:
             if oc is None:
                 continue
             has_play = r.play is not None and pc is not None
+            sc = None if iq_mode else spos.get(c)           # (IQ-mode SND is never compressed)
             for f in range(pcm.shape[1] // L.FRAME):
-                _put_drop_oldest(q, Frame.make(
+                fr = Frame.make(
                     pcm[oc, f * L.FRAME:(f + 1) * L.FRAME], r.rssi[oc, f],
                     r.play[pc, f * P:(f + 1) * P].copy() if has_play else None,
                     r.mono[pc, f * P:(f + 1) * P].copy() if has_play and r.mono is not None else None, r.flags[oc, f],
-                    r.iq[c, f * L.FRAME:(f + 1) * L.FRAME].copy() if iq_mode else None))
+                    r.iq[c, f * L.FRAME:(f + 1) * L.FRAME].copy() if iq_mode else None)
+                if sc is not None:
+                    fr.adpcm = r.snd_adpcm[sc, f * (L.FRAME // 2):(f + 1) * (L.FRAME // 2)].tobytes()
+                _put_drop_oldest(q, fr)
 
     def _run_pipelined(self, batch):
         eng = self.engine
@@ -773,7 +833,15 @@ class GpuStream:
     "SET nb=%d th=%d" (kiwi/client.py set_noise_blanker) sets the channel's impulse noise blanker (ssdr_set_noise_blanker: gate in
     microseconds 1..10000, threshold 2..1000, either 0 = off); a value out of range raises ValueError.  Kiwi's newer "SET nb algo=..."
     interface is not this one and is ignored, as is "SET squelch=..." (no squelch here).
-    "SET zoom=%d start=%d" (:741, 839) is remembered (`zoom`, `start`); the rest (auth, keepalive, compression, ...)
+    "SET compression=%d" on an SND stream and "SET wf_comp=%d" on a W/F stream (kiwi/client.py:296-305) switch the channel's wire
+    compression (IQHub.set_compression: 0 off, any other integer on; not an integer: ValueError; the other stream kind ignores
+    them).  A compressed SND frame carries 256 bytes of IMA ADPCM for 512 samples, its encoder state kept for the whole connection
+    and started at (0, 0) when the flag goes on -- where the client's decoder starts; a compressed W/F line carries 517 bytes encoded
+    from (0, 0) (the 1024 bytes and 10 samples of tail).  Mode iq frames are never compressed.  A frame goes out compressed if and
+    only if it was produced with the flag on: frames queued before the switch still go out raw, the race a real link has too.  A
+    frame the hub's drop-oldest queue drops desynchronises the client's SND decoder, as a frame lost on a real link would.
+    close_connection turns a flag this stream turned on off again, so the next connection starts from (0, 0).
+    "SET zoom=%d start=%d" (:741, 839) is remembered (`zoom`, `start`); the rest (auth, keepalive, ...)
     has no meaning without a server and is accepted.  A modulation without a demodulator here, or a frequency outside
     the channel's IQ band, raises ValueError instead of being demodulated as something else.  "SET mod=iq" selects the
     channel's filtered baseband itself (SSDR_MODE_IQ): its SND frames then carry I,Q pairs behind a GNSS stamp.
@@ -787,6 +855,7 @@ class GpuStream:
         self.zoom = self.start = None
         self.seq = 0
         self.closed = False
+        self._comp_on = False                        # this stream turned the channel's compression on
         self._greeting = deque()
         if hasattr(hub, "attach"):                   # this channel has a listener now: its results are queued from here on
             hub.attach(self.channel, wf=(kind != "SND"), snd=(kind == "SND"))
@@ -820,8 +889,20 @@ class GpuStream:
             gate, thresh = int(kv["nb"]), int(kv["th"])
             check_noise_blanker(gate, thresh)
             self.hub.set_noise_blanker(self.channel, gate, thresh)
+        elif "compression" in kv or "wf_comp" in kv:
+            key = "compression" if self.kind == "SND" else "wf_comp"
+            if key in kv:
+                self._set_compression(int(kv[key]) != 0)
         elif "zoom" in kv:
             self.zoom, self.start = int(kv["zoom"]), int(kv.get("start", 0))
+
+    def _set_compression(self, on):
+        """the channel's flag for this stream's kind; the hub (and its engine) only hear of a change"""
+        i = 0 if self.kind == "SND" else 1
+        now = self.hub.compression(self.channel)[i] if hasattr(self.hub, "compression") else False
+        if on != now:
+            self.hub.set_compression(self.channel, **{("snd" if i == 0 else "wf"): on})
+        self._comp_on = on
 
     def _retune(self, kv):
         mode = kv["mod"].lower()
@@ -849,10 +930,14 @@ class GpuStream:
                 f = self.hub.snd_queue[self.channel].get(timeout=self.timeout)
                 if f.iq_block is not None:           # the channel is in "SET mod=iq": I,Q pairs behind a GNSS stamp
                     return snd_iq_frame(f.iq_block, f.rssi, self._next_seq(), adc_overflow=f.adc_overflow)
+                if getattr(f, "adpcm", None) is not None:      # produced with "SET compression=1"
+                    return snd_adpcm_frame(f.adpcm, f.rssi, self._next_seq(), adc_overflow=f.adc_overflow)
                 return snd_frame(f, f.rssi, self._next_seq(), adc_overflow=f.adc_overflow)
             while True:                              # a line summed for some client's N > 1 is not a wire line: skip it
                 line, n, _ = self.hub.wf_queue[self.channel].get(timeout=self.timeout)
                 if n == 1:
+                    if getattr(line, "adpcm", None) is not None:   # produced with "SET wf_comp=1"
+                        return wf_adpcm_frame(line.adpcm, self._next_seq())
                     return wf_frame(line, self._next_seq())
         except queue.Empty:
             return None                              # what a cleanly closed connection returns (:1053-1058)
@@ -862,6 +947,9 @@ class GpuStream:
         return self.seq
 
     def close_connection(self, *a, **k):
+        if self._comp_on and not self.closed:        # the next connection's decoder starts from (0, 0): so does its encoder
+            self._comp_on = False
+            self.hub.set_compression(self.channel, **{("snd" if self.kind == "SND" else "wf"): False})
         self.closed = True
 
 
@@ -876,6 +964,18 @@ def snd_frame(pcm, rssi, seq=0, adc_overflow=False):
     smeter = int(min(max(round((float(rssi) + 127.0) * 10.0), 0), 65535))
     return bytearray(b"SND" + struct.pack("<BI", 2 if adc_overflow else 0, seq) + struct.pack(">H", smeter) +
                      np.asarray(pcm, np.int16).astype(">i2").tobytes())
+
+
+def wf_adpcm_frame(payload, seq=0, x_bin=0, flags_zoom=0):
+    """One W/F message with "SET wf_comp=1": the header of wf_frame, then the line's 517 bytes of IMA ADPCM (kiwi/client.py:476-479)"""
+    return bytearray(b"W/F\x00" + struct.pack("<III", x_bin, flags_zoom, seq) + bytes(payload))
+
+
+def snd_adpcm_frame(payload, rssi, seq=0, adc_overflow=False):
+    """One SND message with "SET compression=1": the header of snd_frame, then 256 bytes of IMA ADPCM for 512 samples
+    (kiwi/client.py:461-464)"""
+    smeter = int(min(max(round((float(rssi) + 127.0) * 10.0), 0), 65535))
+    return bytearray(b"SND" + struct.pack("<BI", 2 if adc_overflow else 0, seq) + struct.pack(">H", smeter) + bytes(payload))
 
 
 def snd_iq_frame(iq, rssi, seq=0, adc_overflow=False, gps=(0, 0, 0, 0)):
