@@ -362,6 +362,48 @@ int ssdr_audio_adpcm(ssdr_ctx *ctx, uint8_t *out, int out_is_device);
  * flags as they are. */
 int ssdr_wf_adpcm(ssdr_ctx *ctx, uint8_t *out, uint32_t *lines, int out_is_device);
 
+/* -- audio squelch: the KiwiSDR's "SET squelch=<v> max=<m>" (kiwi/client.py:255-256, the old server's SetSquelch(v, max)) and
+ * "SET squelch=<v> param=<tail_s>" (the current server).  On a KiwiSDR squelch is server-side DSP, so the reference has no code
+ * for it: tests/squelch_ref.py is this project's definition, modelled on what the Kiwi server does.
+ * Squelch works on the audio stage's outputs, per channel, behind the AGC and in front of everything that reads the PCM (the
+ * ADPCM encoder, ssdr_run_playbuffer, ssdr_output_checksum, the copies out): a closed frame has its 512 samples set to 0; its
+ * RSSI and its ADC-overflow flag stay.  A channel carries two settings and its current mode picks the one that acts:
+ *   SSDR_MODE_NBFM  the noise squelch (fm_level v 0..99, 0 = off; fm_max m 0..65535), per frame of PCM x:
+ *       d[n] = x[n] - 2 x[n-1] + x[n-2]   (x[-1], x[-2]: the last two UNSQUELCHED samples of the frame before; 0 after a reset)
+ *       N_f  = (sum d[n]^2) >> 9          (uint64)
+ *       A_f  = N_f on the first frame after a reset, else A_{f-1} + floor((N_f - A_{f-1}) / 4)
+ *       T = floor(m (99 - v) / 99), Tc = T + (T >> 2); the first frame is open iff A_f <= T*T; after that an open channel closes
+ *       when A_f > Tc*Tc and a closed one opens when A_f <= T*T
+ *   SSDR_MODE_IQ    never squelched; the state does not move
+ *   other modes     the RSSI squelch (rssi_level v 0..99 dB over the noise floor, 0 = off; tail_frames 0..1024):
+ *       F_f = the minimum of the channel's previous (up to) 64 frame RSSIs; while fewer than 8 are stored the frame is open;
+ *       a frame meets the condition when r_f >= F_f + (float) v (one float32 add) and is open if it or one of the tail_frames
+ *       frames before it met it; every frame's r_f enters the ring, open or closed
+ * The kernel (SSDR_K_SQUELCH with profiling on) runs behind the audio stage inside ssdr_run_audio and every path of ssdr_run_chain,
+ * over the channels whose acting setting is on, in front of the ADPCM encoder; with no such channel nothing is launched (and
+ * before the first nonzero level nothing is allocated).
+ * While any channel has a level above 0 in either setting (acting or not: a mode change could make it act) ssdr_feed_open and
+ * ssdr_checkpoint_save / _load return SSDR_ESTATE, and while a pipelined feed is open ssdr_set_squelch returns SSDR_ESTATE: the
+ * rule the noise blanker and the wire encoders follow. */
+typedef struct ssdr_squelch_params {
+    uint32_t fm_level;      /* "squelch=<v> max=<m>": v 0..99, 0 = off */
+    uint32_t fm_max;        /* m 0..65535 */
+    uint32_t rssi_level;    /* "squelch=<v> param=<tail_s>": v dB over the floor 0..99, 0 = off */
+    uint32_t tail_frames;   /* 0..1024 (ssdr_squelch_tail_frames) */
+} ssdr_squelch_params;
+/* Channels [first, first + count): p [count].  A value outside the ranges is SSDR_EINVAL, and then no channel is changed.  Every
+ * channel it names has its squelch state reset (so do ssdr_reset_state, and a mode change through ssdr_set_params for that
+ * channel's squelch state only). */
+int ssdr_set_squelch(ssdr_ctx *ctx, uint32_t first, uint32_t count, const ssdr_squelch_params *p);
+int ssdr_get_squelch(ssdr_ctx *ctx, uint32_t first, uint32_t count, ssdr_squelch_params *p);
+/* Which frames of the last audio run were zeroed: closed_out uint8 [n_ch][n_frames], 1 = closed.  Rows of channels whose acting
+ * setting is off are zero.  SSDR_ESTATE if no channel squelches, or there has been no audio run with the settings (and modes) as
+ * they are. */
+int ssdr_audio_squelch(ssdr_ctx *ctx, uint8_t *closed_out, int out_is_device);
+/* The tail of "param=<tail_s>" in frames (host only): round(tail_s * kiwi_rate / 512), halves up.  SSDR_EINVAL for a rate other
+ * than 12000 / 20250, a negative or NaN tail_s, or more than 1024 frames. */
+int ssdr_squelch_tail_frames(double tail_s, uint32_t kiwi_rate, uint32_t *frames);
+
 /* -- pipelined host feed: the path a live ingest takes (KiwiSDRStream._process_iq_samples -> batches, kiwi/client.py:493)
  *
  * ssdr_push_iq + ssdr_run_* from pageable host memory serialise copy-in, kernels and copy-out.  The feed keeps `depth`
@@ -444,7 +486,7 @@ int ssdr_set_profiling(ssdr_ctx *ctx, int on);                  /* HIP-event pai
 /* bit 0: run the audio stage on a second stream beside the waterfall kernel (which then takes one workgroup per CU);
  * bit 1: run the audio stage's per-path kernels one after the other instead of side by side (measurement only) */
 int ssdr_set_concurrent(ssdr_ctx *ctx, int on);
-enum { SSDR_K_WF = 0, SSDR_K_AUDIO = 1, SSDR_K_SYNTH = 2, SSDR_K_DB2COL = 3, SSDR_K_PLAY = 4, SSDR_K_WIRE = 5, SSDR_K_TRACE = 6, SSDR_K_SMETER = 7, SSDR_K_FUSED = 8, SSDR_K_ZOOM = 9, SSDR_K_ADPCM = 10, SSDR_K_COUNT = 11 };
+enum { SSDR_K_WF = 0, SSDR_K_AUDIO = 1, SSDR_K_SYNTH = 2, SSDR_K_DB2COL = 3, SSDR_K_PLAY = 4, SSDR_K_WIRE = 5, SSDR_K_TRACE = 6, SSDR_K_SMETER = 7, SSDR_K_FUSED = 8, SSDR_K_ZOOM = 9, SSDR_K_ADPCM = 10, SSDR_K_SQUELCH = 11, SSDR_K_COUNT = 12 };
 int ssdr_kernel_stats(ssdr_ctx *ctx, int which, float *total_ms, uint32_t *launches, int reset);
 /* channels per frame path of the audio stage (one kernel each, timed together as SSDR_K_AUDIO): counts[0] general
  * (NCO -> FIR), counts[1] full-band lane shift, counts[2] full-band AM (no NCO, no FIR) */

@@ -13,7 +13,7 @@ NFFT, FRAME, RATE, NTAP_MAX, HIST = 1024, 512, 12000, 128, 128
 OK, EINVAL, ENOMEM, EHIP, ENODEV, ESTATE = 0, -1, -2, -3, -4, -5
 MODE_AM, MODE_LSB, MODE_USB, MODE_CW, MODE_NBFM, MODE_IQ = range(6)
 MODE_BY_NAME = {"am": 0, "lsb": 1, "usb": 2, "cw": 3, "nbfm": 4, "nfm": 4, "iq": 5}
-K_WF, K_AUDIO, K_SYNTH, K_DB2COL, K_PLAY, K_WIRE, K_TRACE, K_SMETER, K_FUSED, K_ZOOM, K_ADPCM = range(11)
+K_WF, K_AUDIO, K_SYNTH, K_DB2COL, K_PLAY, K_WIRE, K_TRACE, K_SMETER, K_FUSED, K_ZOOM, K_ADPCM, K_SQUELCH = range(12)
 T_WINDOW, T_TWIDDLE_RE, T_TWIDDLE_IM, T_DB_THRESH = range(4)
 
 
@@ -61,6 +61,13 @@ class ChanState(C.Structure):
                 ("agc_m", C.c_float * 8), ("prev_re", C.c_float), ("prev_im", C.c_float), ("pad", C.c_uint32 * 2)]
 
 
+class SquelchParams(C.Structure):
+    """ssdr_squelch_params: "SET squelch=<v> max=<m>" (fm_level, fm_max: the NBFM noise squelch) and "SET squelch=<v> param=<tail_s>"
+    (rssi_level, tail_frames: the RSSI squelch of the other modes); a level of 0 is off"""
+    _fields_ = [("fm_level", C.c_uint32), ("fm_max", C.c_uint32), ("rssi_level", C.c_uint32), ("tail_frames", C.c_uint32)]
+
+
+assert C.sizeof(SquelchParams) == 16
 assert C.sizeof(ChanConsts) == 64 and C.sizeof(ChanState) == 64 and C.sizeof(ChanParams) == 88
 assert C.sizeof(Db2colChan) == 48 and C.sizeof(PlayChan) == 16
 WIRE_BODY = 17 + FRAME * 4
@@ -116,6 +123,10 @@ _SIGS = {
     "ssdr_compression_channels": (C.c_int, [_P, C.c_int, _P, C.POINTER(C.c_uint32)]),
     "ssdr_audio_adpcm": (C.c_int, [_P, _P, C.c_int]),
     "ssdr_wf_adpcm": (C.c_int, [_P, _P, C.POINTER(C.c_uint32), C.c_int]),
+    "ssdr_set_squelch": (C.c_int, [_P, C.c_uint32, C.c_uint32, C.POINTER(SquelchParams)]),
+    "ssdr_get_squelch": (C.c_int, [_P, C.c_uint32, C.c_uint32, C.POINTER(SquelchParams)]),
+    "ssdr_audio_squelch": (C.c_int, [_P, _P, C.c_int]),
+    "ssdr_squelch_tail_frames": (C.c_int, [C.c_double, C.c_uint32, C.POINTER(C.c_uint32)]),
     "ssdr_feed_open": (C.c_int, [_P, C.c_uint32, C.c_uint32, C.c_uint32]),
     "ssdr_feed_slot": (C.c_int, [_P, C.POINTER(_P)]),
     "ssdr_feed_submit": (C.c_int, [_P]),

@@ -219,6 +219,19 @@ struct ssdr_ctx {
     size_t wf_adpcm_bytes = 0;
     bool wf_adpcm_valid = false;
     uint32_t wf_adpcm_lines = 0;
+    // audio squelch (ssdr_set_squelch): host settings at its first call, device memory at the first nonzero level; with no
+    // channel squelching nothing is launched
+    std::vector<ssdr_squelch_params> h_sq;              // [n_ch] as set
+    uint32_t sq_set_n = 0;                              // channels with a level above 0 in either setting
+    std::vector<uint32_t> h_sq_list;                    // the channels whose acting setting is on, ascending (mirror of d_sq_list)
+    uint32_t sq_n = 0;
+    bool sq_dirty = false;                              // settings or modes changed since the list was made
+    SsdrSquelchChan *d_sq = nullptr;                    // [n_ch] settings + carried state
+    uint32_t *d_sq_list = nullptr;                      // [n_ch]
+    uint8_t *d_sq_closed = nullptr;                     // [sq_n][n_frames] of the last audio run
+    size_t sq_closed_bytes = 0;
+    bool sq_valid = false;
+    uint32_t sq_frames = 0;
 };
 
 static int get_event(ssdr_ctx *c, hipEvent_t *e)
@@ -296,7 +309,7 @@ void ssdr_destroy(ssdr_ctx *c)
                     c->d_iq_own, c->d_wf_out, c->d_pcm, c->d_rssi, c->d_flags, c->d_scratch, c->d_db2col, c->d_color, c->d_play,
                     c->d_play_taps, c->d_play_hist, c->d_play_hist_alt, c->d_play_rs_taps, c->d_play_out, c->d_wfdata, c->d_wfpend, c->d_trace, c->d_trace_y, c->d_smeter,
                     c->d_smeter_in, c->d_post_sel, c->d_wire, c->d_wire_rssi, c->d_play_mono, c->d_line1, c->d_dbchan1, c->d_color1, c->d_tw64, c->d_wire_gps, c->d_iq_out, c->d_zoom_taps, c->d_zoom_dphi, c->d_zoom_phase, c->d_zoom_hist, c->d_zoom_out,
-                    c->d_nb, c->d_nb_mask, c->d_comp_list, c->d_adpcm_state, c->d_snd_adpcm, c->d_wf_adpcm};
+                    c->d_nb, c->d_nb_mask, c->d_comp_list, c->d_adpcm_state, c->d_snd_adpcm, c->d_wf_adpcm, c->d_sq, c->d_sq_list, c->d_sq_closed};
     for (void *p : ptrs)
         if (p) (void)hipFree(p);
     if (c->ev0) (void)hipEventDestroy(c->ev0);
@@ -375,6 +388,7 @@ static int zoom_restart(ssdr_ctx *c, uint32_t first, uint32_t count, bool restar
 static int join_audio(ssdr_ctx *c);
 static int drain_audio(ssdr_ctx *c);
 static int nb_upload(ssdr_ctx *c, uint32_t first, uint32_t count);
+static int squelch_upload(ssdr_ctx *c, uint32_t first, uint32_t count);
 
 int ssdr_reset_state(ssdr_ctx *c, uint32_t first, uint32_t count) SSDR_GUARD
 {
@@ -400,6 +414,7 @@ int ssdr_reset_state(ssdr_ctx *c, uint32_t first, uint32_t count) SSDR_GUARD
     HIP_TRY(hipStreamSynchronize(c->stream));
     if (first == 0 && count == c->n_ch) { c->wf_phase = 0; c->synth_sample0 = 0; c->audio_started = false; }
     { int rcn = nb_upload(c, first, count); if (rcn != SSDR_OK) return rcn; }      // the blanker starts over (its gate at the current rate)
+    { int rcq = squelch_upload(c, first, count); if (rcq != SSDR_OK) return rcq; } // and the squelch
     return zoom_restart(c, first, count, false);         // the zoomed streams of these channels start over as well
 } SSDR_UNGUARD
 
@@ -414,11 +429,24 @@ int ssdr_set_params(ssdr_ctx *c, uint32_t first, uint32_t count, const ssdr_chan
         const int rc = ssdr_compile_params_host(p + i, &k[i], taps.data() + (size_t)i * SSDR_NTAP_MAX, c->decim, c->kiwi_rate);
         if (rc != SSDR_OK) return rc;
     }
+    std::vector<uint32_t> sq_reset;                         // channels with a squelch setting whose mode changes: another setting acts
+    if (c->sq_set_n)
+        for (uint32_t i = 0; i < count; i++) {
+            const ssdr_squelch_params &q = c->h_sq[first + i];
+            if ((q.fm_level || q.rssi_level) && c->h_consts[first + i].mode != k[i].mode) sq_reset.push_back(first + i);
+        }
     for (uint32_t i = 0; i < count; i++) c->h_params[first + i] = p[i];
     for (uint32_t i = 0; i < count; i++) c->h_consts[first + i] = k[i];
     c->chan_list_dirty = true;
     c->summary_dirty = true;
     { int rcj = join_audio(c); if (rcj != SSDR_OK) return rcj; }
+    for (size_t i = 0; i < sq_reset.size();) {              // their squelch state only, a run of consecutive channels at a time
+        size_t j = i + 1;
+        while (j < sq_reset.size() && sq_reset[j] == sq_reset[j - 1] + 1) j++;
+        { int rcq = squelch_upload(c, sq_reset[i], (uint32_t)(j - i)); if (rcq != SSDR_OK) return rcq; }
+        i = j;
+    }
+    if (!sq_reset.empty()) { c->sq_dirty = true; c->sq_valid = false; }
     HIP_TRY(hipMemcpyAsync(c->d_consts + first, k.data(), count * sizeof(ssdr_chan_consts), hipMemcpyHostToDevice, c->stream));
     HIP_TRY(hipMemcpyAsync(c->d_taps + (size_t)first * SSDR_NTAP_MAX, taps.data(), taps.size() * sizeof(float),
                            hipMemcpyHostToDevice, c->stream));
@@ -996,6 +1024,86 @@ static int adpcm_wf_launch(ssdr_ctx *c, hipStream_t s, uint32_t n_avg)
     return SSDR_OK;
 }
 
+// ---- audio squelch: the kernel behind the audio stage, in front of the encoder (ssdr_set_squelch) ---------------------------
+static inline bool squelch_acts(const ssdr_squelch_params &q, uint32_t mode)
+{
+    if (mode == SSDR_MODE_IQ) return false;
+    return mode == SSDR_MODE_NBFM ? q.fm_level != 0 : q.rssi_level != 0;
+}
+// the settings of channels [first, first + count) as set, their state started over
+static int squelch_upload(ssdr_ctx *c, uint32_t first, uint32_t count)
+{
+    if (!c->d_sq || !count) return SSDR_OK;
+    std::vector<SsdrSquelchChan> q(count);
+    for (uint32_t i = 0; i < count; i++) {
+        memset(&q[i], 0, sizeof q[i]);
+        const ssdr_squelch_params &p = c->h_sq[first + i];
+        q[i].fm_level = p.fm_level; q[i].fm_max = p.fm_max; q[i].rssi_level = p.rssi_level; q[i].tail_frames = p.tail_frames;
+        q[i].open = 1u;
+    }
+    { int rcj = join_audio(c); if (rcj != SSDR_OK) return rcj; }
+    HIP_TRY(hipMemcpyAsync(c->d_sq + first, q.data(), count * sizeof(SsdrSquelchChan), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return SSDR_OK;
+}
+// the list of the channels whose acting setting is on, after a change of settings or modes
+static int squelch_refresh(ssdr_ctx *c)
+{
+    if (!c->sq_dirty) return SSDR_OK;
+    uint32_t n = 0;
+    if (c->sq_set_n) {
+        c->h_sq_list.resize(c->n_ch);
+        for (uint32_t ch = 0; ch < c->n_ch; ch++)
+            if (squelch_acts(c->h_sq[ch], c->h_consts[ch].mode)) c->h_sq_list[n++] = ch;
+    }
+    if (n) {
+        { int rcj = join_audio(c); if (rcj != SSDR_OK) return rcj; }     // a kernel in flight reads the list
+        HIP_TRY(hipMemcpyAsync(c->d_sq_list, c->h_sq_list.data(), (size_t)n * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(hipStreamSynchronize(c->stream));
+    }
+    c->sq_n = n;
+    c->sq_dirty = false;
+    c->sq_valid = false;
+    return SSDR_OK;
+}
+// the list up to date, and room for the closed flags of an audio run of the current batch
+static int squelch_prepare(ssdr_ctx *c)
+{
+    if (!c->sq_set_n && !c->sq_dirty) return SSDR_OK;
+    { int rcr = squelch_refresh(c); if (rcr != SSDR_OK) return rcr; }
+    const size_t need = (size_t)c->sq_n * c->in_frames;
+    if (c->sq_closed_bytes >= need) return SSDR_OK;
+    { int rcd = drain_audio(c); if (rcd != SSDR_OK) return rcd; }
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    if (c->d_sq_closed) { HIP_TRY(hipFree(c->d_sq_closed)); c->d_sq_closed = nullptr; }
+    c->sq_closed_bytes = 0;
+    c->sq_valid = false;
+    HIP_TRY(hipMalloc(&c->d_sq_closed, need));
+    c->sq_closed_bytes = need;
+    return SSDR_OK;
+}
+// squelch the PCM of the audio stage just queued on `s`, behind it on the same stream: the state advances once per batch
+static int squelch_launch(ssdr_ctx *c, hipStream_t s)
+{
+    if (!c->sq_n) return SSDR_OK;
+    SsdrSquelchArgs q;
+    q.pcm = c->d_pcm;
+    q.rssi = c->d_rssi;
+    q.n_frames = c->in_frames;
+    q.list = c->d_sq_list;
+    q.list_n = c->sq_n;
+    q.consts = c->d_consts;
+    q.chan = c->d_sq;
+    q.closed = c->d_sq_closed;
+    int rc;
+    if (c->profiling && (rc = timed_begin(c, s)) != SSDR_OK) return rc;       // (untimed otherwise: ssdr_elapsed_ms stays the stage's)
+    HIP_TRY(ssdr_launch_squelch(q, s));
+    if (c->profiling && (rc = timed_end(c, SSDR_K_SQUELCH, s)) != SSDR_OK) return rc;
+    c->sq_valid = true;
+    c->sq_frames = c->in_frames;
+    return SSDR_OK;
+}
+
 int ssdr_run_wf(ssdr_ctx *c, int16_t *wf_sum_out, uint32_t *lines_ready, int out_is_device) SSDR_GUARD
 {
     if (!c) return SSDR_EINVAL;
@@ -1126,6 +1234,8 @@ int ssdr_run_audio(ssdr_ctx *c, int16_t *pcm_out, float *rssi_out, int out_is_de
     }
     { int rca = adpcm_snd_alloc(c); if (rca != SSDR_OK) return rca; }
     c->snd_adpcm_valid = false;
+    { int rcq = squelch_prepare(c); if (rcq != SSDR_OK) return rcq; }
+    c->sq_valid = false;
     SsdrAudioArgs a;
     a.iq = c->d_iq;
     a.ch_stride = (uint64_t)in_len(c, c->in_frames);
@@ -1193,7 +1303,8 @@ int ssdr_run_audio(ssdr_ctx *c, int16_t *pcm_out, float *rssi_out, int out_is_de
         if (fa.wf.tail)          // hop 512: only now may the carried half-line (the kernel's line 0 read it) become this batch's last one
             HIP_TRY(hipMemcpy2DAsync(c->d_wf_tail, (SSDR_NFFT / 2) * 4, fa.wf.iq + (size_t)(fa.wf.n_lines - 1) * SSDR_FRAME,
                                      fa.wf.ch_stride * 4, (SSDR_NFFT / 2) * 4, c->n_ch, hipMemcpyDeviceToDevice, s));
-        if ((rc = adpcm_snd_launch(c, s)) != SSDR_OK) return rc;          // the encoders behind the one-read kernel
+        if ((rc = squelch_launch(c, s)) != SSDR_OK) return rc;            // squelch, then the encoders, behind the one-read kernel
+        if ((rc = adpcm_snd_launch(c, s)) != SSDR_OK) return rc;
         if ((rc = adpcm_wf_launch(c, s, fa.wf.n_avg)) != SSDR_OK) return rc;
         return SSDR_OK;
     }
@@ -1253,6 +1364,7 @@ int ssdr_run_audio(ssdr_ctx *c, int16_t *pcm_out, float *rssi_out, int out_is_de
             c->nb_mask_gen = c->nb_gen;
         }
     }
+    if ((rc = squelch_launch(c, s)) != SSDR_OK) return rc;
     if ((rc = adpcm_snd_launch(c, s)) != SSDR_OK) return rc;
     const hipMemcpyKind kind = out_is_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
     if (pcm_out) HIP_TRY(hipMemcpyAsync(pcm_out, c->d_pcm, (size_t)c->n_ch * c->in_frames * SSDR_FRAME * 2, kind, s));
@@ -1552,7 +1664,7 @@ int ssdr_feed_open(ssdr_ctx *c, uint32_t n_frames, uint32_t depth, uint32_t flag
 {
     if (!c || n_frames == 0 || (n_frames & 1u) || depth < 2 || depth > 16 || (flags & ~(uint32_t)(SSDR_FEED_WIRE | SSDR_FEED_POST | SSDR_FEED_LAZY_OUT))) return SSDR_EINVAL;
     if (!c->feed.empty() || c->concurrent || c->decim != 1 || c->zoom != 1) return SSDR_ESTATE;
-    if (c->comp_snd_n || c->comp_wf_n) return SSDR_ESTATE;                  // no wire compression in the slot pipeline      // the feed's slots are sized for un-zoomed 12 kHz IQ
+    if (c->comp_snd_n || c->comp_wf_n || c->sq_set_n) return SSDR_ESTATE;   // no wire compression and no squelch in the slot pipeline      // the feed's slots are sized for un-zoomed 12 kHz IQ
     HIP_TRY(hipSetDevice(c->device));
     const bool post = (flags & SSDR_FEED_POST) != 0;
     if (post) { int rcp = ensure_play(c); if (rcp != SSDR_OK) return rcp; }
@@ -1941,6 +2053,7 @@ int ssdr_checkpoint_save(ssdr_ctx *c, void *blob) SSDR_GUARD
     if (c->zoom > 1) return SSDR_ESTATE;                     // the zoomed waterfall stream (phase, history, centres) is not part of the blob
     if (c->nb_on) return SSDR_ESTATE;                        // nor is the noise blanker's state
     if (c->comp_snd_n || c->comp_wf_n) return SSDR_ESTATE;   // nor the wire encoders'
+    if (c->sq_set_n) return SSDR_ESTATE;                     // nor the squelch's
     SsdrCkptHeader h = {kCkptMagic, kCkptVersion, c->n_ch, c->n_avg, c->wf_phase, c->audio_started ? 1u : 0u, c->kiwi_rate,
                         c->d_play_hist ? 1u : 0u, c->synth_sample0, c->hop, c->decim};
     char *p = static_cast<char *>(blob);
@@ -1985,7 +2098,7 @@ int ssdr_checkpoint_load(ssdr_ctx *c, const void *blob, uint64_t bytes) SSDR_GUA
     std::vector<float> ktaps(n * SSDR_NTAP_MAX);
     for (size_t i = 0; i < n; i++)
         if (ssdr_compile_params_host(&prm[i], &kc[i], ktaps.data() + i * SSDR_NTAP_MAX, h.decim, h.kiwi_rate) != SSDR_OK) return SSDR_EINVAL;
-    if (!c->feed.empty() || c->zoom > 1 || c->nb_on || c->comp_snd_n || c->comp_wf_n) return SSDR_ESTATE;
+    if (!c->feed.empty() || c->zoom > 1 || c->nb_on || c->comp_snd_n || c->comp_wf_n || c->sq_set_n) return SSDR_ESTATE;
     std::vector<double> play_hist;                          // play_buffer state that arrives before its buffers exist: applied at first use
     if (h.has_play && !c->d_play_hist) {
         const double *q = reinterpret_cast<const double *>(static_cast<const char *>(blob) + sizeof h + n * (sizeof(ssdr_chan_consts) +
@@ -2602,6 +2715,86 @@ int ssdr_wf_adpcm(ssdr_ctx *c, uint8_t *out, uint32_t *lines, int out_is_device)
     const size_t bytes = (size_t)c->wf_adpcm_lines * c->comp_wf_n * SSDR_ADPCM_WF_BYTES;
     HIP_TRY(hipMemcpyAsync(out, c->d_wf_adpcm, bytes, out_is_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
+    return SSDR_OK;
+} SSDR_UNGUARD
+
+int ssdr_squelch_tail_frames(double tail_s, uint32_t kiwi_rate, uint32_t *frames) SSDR_GUARD
+{
+    if (!frames || (kiwi_rate != SSDR_RATE && kiwi_rate != SSDR_RATE_WIDE)) return SSDR_EINVAL;
+    const double x = tail_s * (double)kiwi_rate / (double)SSDR_FRAME;
+    if (!(x >= 0.0) || x + 0.5 >= 1025.0) return SSDR_EINVAL;
+    *frames = (uint32_t)std::floor(x + 0.5);
+    return SSDR_OK;
+} SSDR_UNGUARD
+
+int ssdr_set_squelch(ssdr_ctx *c, uint32_t first, uint32_t count, const ssdr_squelch_params *p) SSDR_GUARD
+{
+    if (!c || (uint64_t)first + count > c->n_ch || (count && !p)) return SSDR_EINVAL;
+    for (uint32_t i = 0; i < count; i++)                    // all or nothing: every channel is checked before any is changed
+        if (p[i].fm_level > 99 || p[i].fm_max > 65535 || p[i].rssi_level > 99 || p[i].tail_frames > 1024) return SSDR_EINVAL;
+    if (!c->feed.empty()) return SSDR_ESTATE;
+    if (!count) return SSDR_OK;
+    HIP_TRY(hipSetDevice(c->device));
+    bool any = false;
+    for (uint32_t i = 0; i < count; i++) any = any || p[i].fm_level || p[i].rssi_level;
+    if (!c->d_sq && any) {                                  // the first nonzero level: state and list
+        { int rcj = join_audio(c); if (rcj != SSDR_OK) return rcj; }
+        SsdrSquelchChan *d = nullptr;
+        HIP_TRY(hipMalloc(&d, (size_t)c->n_ch * sizeof(SsdrSquelchChan)));
+        c->d_sq = d;
+        if (!c->d_sq_list) {
+            uint32_t *l = nullptr;
+            HIP_TRY(hipMalloc(&l, (size_t)c->n_ch * sizeof(uint32_t)));
+            c->d_sq_list = l;
+        }
+        if (c->h_sq.empty()) c->h_sq.assign(c->n_ch, ssdr_squelch_params{0u, 0u, 0u, 0u});
+        { int rcu = squelch_upload(c, 0, c->n_ch); if (rcu != SSDR_OK) return rcu; }     // every other channel: as set so far, fresh
+    }
+    if (c->h_sq.empty()) c->h_sq.assign(c->n_ch, ssdr_squelch_params{0u, 0u, 0u, 0u});
+    uint32_t set_n = c->sq_set_n;
+    for (uint32_t i = 0; i < count; i++) {
+        const ssdr_squelch_params &was = c->h_sq[first + i];
+        set_n = set_n - ((was.fm_level || was.rssi_level) ? 1u : 0u) + ((p[i].fm_level || p[i].rssi_level) ? 1u : 0u);
+        c->h_sq[first + i] = p[i];
+    }
+    c->sq_set_n = set_n;
+    c->sq_dirty = true;
+    c->sq_valid = false;
+    return squelch_upload(c, first, count);
+} SSDR_UNGUARD
+
+int ssdr_get_squelch(ssdr_ctx *c, uint32_t first, uint32_t count, ssdr_squelch_params *p) SSDR_GUARD
+{
+    if (!c || (uint64_t)first + count > c->n_ch || (count && !p)) return SSDR_EINVAL;
+    for (uint32_t i = 0; i < count; i++) p[i] = c->h_sq.empty() ? ssdr_squelch_params{0u, 0u, 0u, 0u} : c->h_sq[first + i];
+    return SSDR_OK;
+} SSDR_UNGUARD
+
+int ssdr_audio_squelch(ssdr_ctx *c, uint8_t *closed_out, int out_is_device) SSDR_GUARD
+{
+    if (!c || !closed_out) return SSDR_EINVAL;
+    if (c->sq_dirty || !c->sq_n || !c->sq_valid) return SSDR_ESTATE;       // (a change of settings or modes since the run: not that run's)
+    HIP_TRY(hipSetDevice(c->device));
+    { int rcj = join_audio(c); if (rcj != SSDR_OK) return rcj; }
+    const size_t row = c->sq_frames;
+    // the rows of the listed channels, a run of consecutive channels at a time; every other row is zero
+    if (out_is_device) {
+        HIP_TRY(hipMemsetAsync(closed_out, 0, (size_t)c->n_ch * row, c->stream));
+        for (uint32_t i = 0; i < c->sq_n;) {
+            uint32_t j = i + 1;
+            while (j < c->sq_n && c->h_sq_list[j] == c->h_sq_list[j - 1] + 1) j++;
+            HIP_TRY(hipMemcpyAsync(closed_out + (size_t)c->h_sq_list[i] * row, c->d_sq_closed + (size_t)i * row, (size_t)(j - i) * row,
+                                   hipMemcpyDeviceToDevice, c->stream));
+            i = j;
+        }
+        HIP_TRY(hipStreamSynchronize(c->stream));
+        return SSDR_OK;
+    }
+    std::vector<uint8_t> rows((size_t)c->sq_n * row);
+    HIP_TRY(hipMemcpyAsync(rows.data(), c->d_sq_closed, rows.size(), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    memset(closed_out, 0, (size_t)c->n_ch * row);
+    for (uint32_t i = 0; i < c->sq_n; i++) memcpy(closed_out + (size_t)c->h_sq_list[i] * row, rows.data() + (size_t)i * row, row);
     return SSDR_OK;
 } SSDR_UNGUARD
 

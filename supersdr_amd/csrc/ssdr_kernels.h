@@ -163,7 +163,30 @@ struct SsdrAdpcmArgs {
 };
 hipError_t ssdr_launch_adpcm_enc(const SsdrAdpcmArgs &a, hipStream_t stream);        // SND frames / stand-alone streams
 hipError_t ssdr_launch_adpcm_enc_wf(const SsdrAdpcmArgs &a, hipStream_t stream);     // W/F lines: n_samples 1024, + the pad
-#define SSDR_ZOOM_HIST 256                   // raw input samples carried per channel (>= 32 Z - 2 for Z <= 8)
+// audio squelch (ssdr_squelch.hip): one wave per listed channel, in place on the PCM of the audio stage just run.  A channel's
+// settings as set (ssdr_squelch_params) and its carried state: the last two unsquelched samples, A, primed / open (noise
+// squelch), the ring of frame RSSIs with its count and position and the frames of tail left (RSSI squelch).  312 B.
+#define SSDR_SQUELCH_RING 64
+#define SSDR_SQUELCH_MIN_FILL 8
+struct SsdrSquelchChan {
+    uint32_t fm_level, fm_max, rssi_level, tail_frames;
+    int32_t x1, x2;
+    int64_t a;
+    uint32_t primed, open, ring_count, ring_pos, tail_left, pad;
+    float ring[SSDR_SQUELCH_RING];
+};
+struct SsdrSquelchArgs {
+    int16_t *pcm;                            // [n_ch][n_frames*512], closed frames zeroed in place
+    const float *rssi;                       // [n_ch][n_frames]
+    uint32_t n_frames;
+    const uint32_t *list;                    // [list_n] the channels whose acting setting is on, ascending
+    uint32_t list_n;
+    const ssdr_chan_consts *consts;          // (mode: SSDR_MODE_NBFM -> the noise squelch, else the RSSI squelch)
+    SsdrSquelchChan *chan;                   // [n_ch]
+    uint8_t *closed;                         // [list_n][n_frames] 1 where the frame was zeroed
+};
+hipError_t ssdr_launch_squelch(const SsdrSquelchArgs &a, hipStream_t stream);
+#define SSDR_ZOOM_HIST 256                  // raw input samples carried per channel (>= 32 Z - 2 for Z <= 8)
 #define SSDR_ZOOM_TAPS_MAX 255
 struct SsdrZoomArgs {
     const uint32_t *iq;                      // [n_ch][ch_stride] input dwords

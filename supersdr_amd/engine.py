@@ -72,6 +72,28 @@ def check_noise_blanker(gate_us, thresh):
                          % (gate_us, thresh))
 
 
+SQUELCH_LEVEL = (0, 99)         # ssdr_set_squelch's ranges; a level of 0 turns that setting off
+SQUELCH_FM_MAX = (0, 65535)
+SQUELCH_TAIL_FRAMES = (0, 1024)
+
+
+def squelch_tail_frames(tail_s, kiwi_rate=L.RATE):
+    """The tail of "SET squelch=<v> param=<tail_s>" in frames: round(tail_s * kiwi_rate / 512) (ssdr_squelch_tail_frames; ValueError
+    for a negative tail or one of more than 1024 frames)"""
+    n = C.c_uint32()
+    if lib.ssdr_squelch_tail_frames(float(tail_s), int(kiwi_rate), C.byref(n)) != L.OK:
+        raise ValueError("squelch tail %r s at %r Hz: out of range (0..1024 frames of 512 samples)" % (tail_s, kiwi_rate))
+    return n.value
+
+
+def check_squelch(fm_level=0, fm_max=0, rssi_level=0, tail_frames=0):
+    """ValueError unless the four are something ssdr_set_squelch takes"""
+    for v, (lo, hi), name in ((fm_level, SQUELCH_LEVEL, "fm_level"), (fm_max, SQUELCH_FM_MAX, "fm_max"),
+                              (rssi_level, SQUELCH_LEVEL, "rssi_level"), (tail_frames, SQUELCH_TAIL_FRAMES, "tail_frames")):
+        if not lo <= int(v) <= hi:
+            raise ValueError("squelch %s %r: out of range %d..%d" % (name, v, lo, hi))
+
+
 def _nb_array(v, n, name):
     a = np.broadcast_to(np.asarray(v, np.int64), (n,))
     if ((a < 0) | (a >= 2 ** 32)).any():
@@ -303,6 +325,32 @@ class SsdrEngine:
         8 j + i (rows of channels whose blanker is off: 0)"""
         out = np.empty((self.n_ch, self.audio_frames * L.FRAME * self.decim // 8), np.uint8)
         check(lib.ssdr_audio_nb_mask(self._ctx, out.ctypes.data, 0), "ssdr_audio_nb_mask")
+        return out
+
+    def set_squelch(self, first, settings):
+        """The audio squelch of channels first, first + 1, ...: settings is a sequence of (fm_level, fm_max, rssi_level, tail_frames), one per
+        channel ("SET squelch=<v> max=<m>": the NBFM noise squelch; "SET squelch=<v> param=<tail_s>": the RSSI squelch of the other
+        modes; levels 0..99 with 0 = off, fm_max 0..65535, tail_frames 0..1024).  Resets those channels' squelch state.  A value that is
+        not a uint32 raises ValueError before the library is called; one the library refuses raises SsdrError (SSDR_EINVAL).  Either way
+        no channel is changed."""
+        a = np.asarray(settings, np.int64).reshape(-1, 4)
+        if ((a < 0) | (a >= 2 ** 32)).any():
+            raise ValueError("squelch settings %r: out of range" % (settings,))
+        arr = (L.SquelchParams * len(a))(*[L.SquelchParams(*[int(v) for v in row]) for row in a])
+        check(lib.ssdr_set_squelch(self._ctx, int(first), len(a), arr), "ssdr_set_squelch")
+
+    def squelch(self, first=0, count=None):
+        """-> uint32 [count, 4]: fm_level, fm_max, rssi_level, tail_frames of channels first .. first + count - 1 as set"""
+        count = self.n_ch - first if count is None else count
+        arr = (L.SquelchParams * max(count, 1))()
+        check(lib.ssdr_get_squelch(self._ctx, int(first), int(count), arr), "ssdr_get_squelch")
+        return np.array([[q.fm_level, q.fm_max, q.rssi_level, q.tail_frames] for q in arr[:count]], np.uint32).reshape(count, 4)
+
+    def audio_squelch(self):
+        """-> uint8 [n_ch, n_frames]: 1 where the squelch zeroed the frame in the last audio run (rows of channels whose acting setting
+        is off: 0)"""
+        out = np.empty((self.n_ch, self.audio_frames), np.uint8)
+        check(lib.ssdr_audio_squelch(self._ctx, out.ctypes.data, 0), "ssdr_audio_squelch")
         return out
 
     def audio_iq(self):

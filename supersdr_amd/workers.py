@@ -40,7 +40,7 @@ import numpy as np
 
 from . import _lib as L
 from ._lib import Db2colChan, PlayChan
-from .engine import SsdrEngine, check_noise_blanker, default_params
+from .engine import SsdrEngine, check_noise_blanker, check_squelch, default_params
 
 IQ_SPAN_KHZ = L.RATE / 1000.0          # what one channel's GPU waterfall covers: the IQ band around its centre (12 kHz; hub.iq_span_khz)
 
@@ -53,6 +53,7 @@ class Frame(np.ndarray):
     rec_block = None
     iq_block = None                     # "SET mod=iq": int16 [512, 2] I,Q of the frame (the PCM samples are its I column)
     adpcm = None                        # "SET compression=1": the frame's 256-byte IMA-ADPCM payload (bytes)
+    squelched = False                   # "SET squelch=": the squelch was closed for this frame (its samples are 0)
     adc_overflow = False
     rssi = -127.0
 
@@ -88,9 +89,11 @@ class SuperframeResult:
     In pipeline mode the arrays are views of the feed's pinned slots: valid until `depth - 1` further superframes have
     been collected (copy what must live longer).
     With wire compression on some channels (IQHub.set_compression): snd_adpcm uint8 [n, frames*256] / wf_adpcm uint8 [lines, n, 517],
-    a row per channel of snd_adpcm_channels / wf_adpcm_channels (None: no channel compresses)."""
+    a row per channel of snd_adpcm_channels / wf_adpcm_channels (None: no channel compresses).
+    With a squelch acting on some channel (IQHub.set_squelch): squelched uint8 [n_ch, frames], 1 where the frame was zeroed (None: no
+    channel squelches)."""
     __slots__ = ("seq", "wf", "n_avg", "color", "chans", "pcm", "rssi", "flags", "play", "mono", "iq", "wire_rssi", "post_channels", "out_channels",
-                 "snd_adpcm", "wf_adpcm", "snd_adpcm_channels", "wf_adpcm_channels")
+                 "snd_adpcm", "wf_adpcm", "snd_adpcm_channels", "wf_adpcm_channels", "squelched")
 
     def __init__(self, **kw):
         for k in self.__slots__:
@@ -268,6 +271,8 @@ class IQHub:
         self._params = {}                            # channel -> ChanParams, for the channels that were given any
         self._default_params = default_params("am")
         self._n_iq_mode = 0
+        self._squelch = {}                           # channel -> (fm_level, fm_max, rssi_level, tail_frames), for the channels that were given any
+        self._sq_act = set()                         # channels whose setting acts in their current mode (the engine squelches them)
         self._comp_snd, self._comp_wf = [], []       # channels with "SET compression=1" / "SET wf_comp=1", sorted (the engine's row order)
         self._want_n = np.ones(self.n_ch, np.int32)  # averaging_n asked for by each channel's waterfall client
         self._want_all = {1: self.n_ch}              # N -> channels that want it (all channels / channels with a client)
@@ -382,9 +387,14 @@ class IQHub:
         if self.pipeline and p.mode == L.MODE_IQ:    # the feed's slots hand out PCM rows only (an IQ channel's row carries I)
             raise ValueError("mod=iq needs the synchronous hub: the pipelined feed does not return I,Q pairs")
         with self._lock:
+            sq = self._squelch.get(int(channel))
+            acts = sq is not None and _squelch_acts(sq, p.mode)
+            if acts and not hasattr(self.engine, "set_squelch"):   # the mode change would put a stored setting to work
+                raise ValueError("channel %d has a squelch set for mode %d and this engine has no squelch" % (int(channel), p.mode))
             self.engine.set_params(channel, [p])     # raises for parameters the library refuses; the old ones stay
             self._n_iq_mode += (p.mode == L.MODE_IQ) - (self.params(channel).mode == L.MODE_IQ)
             self._params[int(channel)] = p
+            (self._sq_act.add if acts else self._sq_act.discard)(int(channel))
 
     def set_noise_blanker(self, channel, gate_us, thresh):
         """"SET nb=<gate_us> th=<thresh>" of one channel (ssdr_set_noise_blanker; either 0 = off): resets the channel's blanker state,
@@ -392,6 +402,37 @@ class IQHub:
         check_noise_blanker(gate_us, thresh)
         with self._lock:
             self.engine.set_noise_blanker(channel, [int(gate_us)], [int(thresh)])
+
+    def squelch(self, channel):
+        """-> (fm_level, fm_max, rssi_level, tail_frames) of the channel as set (all 0: never set, or off)"""
+        with self._lock:
+            return self._squelch.get(int(channel), (0, 0, 0, 0))
+
+    def set_squelch(self, channel, fm_level=None, fm_max=None, rssi_level=None, tail_frames=None):
+        """The audio squelch of one channel (ssdr_set_squelch); None leaves a value as it is.  fm_level / fm_max: "SET squelch=<v>
+        max=<m>", the noise squelch that acts while the channel is in NBFM (v 0..99, 0 = off; m 0..65535).  rssi_level / tail_frames:
+        "SET squelch=<v> param=<tail_s>", the RSSI squelch of every other mode but iq (v dB over the noise floor 0..99, 0 = off; the
+        tail in frames 0..1024).  ValueError out of range, and then nothing changes.  The setting is stored here and handed to the
+        engine when the engine has set_squelch; a setting that would act in the channel's current mode on an engine without it,
+        or any level above 0 on the pipelined hub (the feed does not run the squelch), is a ValueError.  Resets the channel's
+        squelch state."""
+        c = int(channel)
+        if not 0 <= c < self.n_ch:
+            raise IndexError("channel %d of %d" % (c, self.n_ch))
+        with self._lock:
+            old = self._squelch.get(c, (0, 0, 0, 0))
+            new = tuple(int(o if v is None else v) for o, v in zip(old, (fm_level, fm_max, rssi_level, tail_frames)))
+            check_squelch(*new)
+            acts = _squelch_acts(new, self.params(c).mode)
+            if self.pipeline:
+                if new[0] or new[2]:
+                    raise ValueError("squelch needs the synchronous hub (the pipelined feed does not run it)")
+            elif hasattr(self.engine, "set_squelch"):
+                self.engine.set_squelch(c, [new])
+            elif acts:
+                raise ValueError("this engine has no squelch (set_squelch)")
+            self._squelch[c] = new
+            (self._sq_act.add if acts else self._sq_act.discard)(c)
 
     def compression(self, channel):
         """-> (snd, wf): whether the channel's SND frames / W/F lines are IMA-ADPCM compressed"""
@@ -641,6 +682,7 @@ class IQHub:
         iqo = eng.audio_iq() if self._n_iq_mode else None                        # channels in "SET mod=iq"
         snd_sel = list(self._comp_snd) if self._comp_snd else None
         snd_adpcm = eng.audio_adpcm() if snd_sel else None                      # [n_snd, frames*256] ("SET compression=1")
+        closed = eng.audio_squelch() if self._sq_act else None                  # [n_ch, frames] ("SET squelch=")
         play = mono = None
         if self.gpu_post and self._n_snd_clients:
             rec = self._sync_recording()
@@ -650,7 +692,8 @@ class IQHub:
         self.superframes += 1
         self._hand_out(SuperframeResult(seq=self.superframes, wf=wf, n_avg=n_avg, color=color, chans=chans, pcm=pcm, rssi=rssi,
                                         flags=flags, play=play, mono=mono, iq=iqo, wire_rssi=wire_rssi, post_channels=self._post_sel,
-                                        snd_adpcm=snd_adpcm, wf_adpcm=wf_adpcm, snd_adpcm_channels=snd_sel, wf_adpcm_channels=wf_sel))
+                                        snd_adpcm=snd_adpcm, wf_adpcm=wf_adpcm, snd_adpcm_channels=snd_sel, wf_adpcm_channels=wf_sel,
+                                        squelched=closed))
 
     def _hand_out(self, r):
         self.last = r
@@ -696,6 +739,8 @@ class IQHub:
                     r.iq[c, f * L.FRAME:(f + 1) * L.FRAME].copy() if iq_mode else None)
                 if sc is not None:
                     fr.adpcm = r.snd_adpcm[sc, f * (L.FRAME // 2):(f + 1) * (L.FRAME // 2)].tobytes()
+                if r.squelched is not None and r.squelched[c, f]:
+                    fr.squelched = True
                 _put_drop_oldest(q, fr)
 
     def _run_pipelined(self, batch):
@@ -801,6 +846,14 @@ class IQHub:
         self.engine.close()
 
 
+def _squelch_acts(setting, mode):
+    """whether (fm_level, fm_max, rssi_level, tail_frames) squelches a channel in `mode`: NBFM the noise squelch, iq nothing, the
+    rest the RSSI squelch"""
+    if mode == L.MODE_IQ:
+        return False
+    return bool(setting[0]) if mode == L.MODE_NBFM else bool(setting[2])
+
+
 def _fill_struct_array(arr, proto):
     """every element of a ctypes array = proto, without a Python loop over the channels"""
     n, size = len(arr), C.sizeof(proto)
@@ -832,7 +885,14 @@ class GpuStream:
         "SET agc=%d hang=%d thresh=%d slope=%d decay=%d manGain=%d"      :979, 1023
     "SET nb=%d th=%d" (kiwi/client.py set_noise_blanker) sets the channel's impulse noise blanker (ssdr_set_noise_blanker: gate in
     microseconds 1..10000, threshold 2..1000, either 0 = off); a value out of range raises ValueError.  Kiwi's newer "SET nb algo=..."
-    interface is not this one and is ignored, as is "SET squelch=..." (no squelch here).
+    interface is not this one and is ignored.
+    "SET squelch=%d max=%d" (kiwi/client.py set_squelch, :255-256) sets the channel's NBFM noise squelch (level 0..99, 0 = off; max
+    0..65535) and "SET squelch=%d param=%g", the current server's spelling, its RSSI squelch for the other modes (dB over the noise
+    floor 0..99, 0 = off; the tail in seconds, turned into frames at the hub's kiwi_rate: at most 1024 frames) -- IQHub.set_squelch,
+    ssdr_set_squelch.  The channel's mode picks the setting that acts: the max= form on a channel that is not in NBFM changes no
+    output until the channel goes to "SET mod=nbfm".  A closed frame goes out with its 512 samples 0 (and is what the ADPCM encoder
+    encodes with "SET compression=1"); RSSI and the ADC-overflow bit stay.  A missing second key, a non-number or a value out of
+    range raises ValueError.  close_connection turns a squelch this stream turned on off again.
     "SET compression=%d" on an SND stream and "SET wf_comp=%d" on a W/F stream (kiwi/client.py:296-305) switch the channel's wire
     compression (IQHub.set_compression: 0 off, any other integer on; not an integer: ValueError; the other stream kind ignores
     them).  A compressed SND frame carries 256 bytes of IMA ADPCM for 512 samples, its encoder state kept for the whole connection
@@ -856,6 +916,7 @@ class GpuStream:
         self.seq = 0
         self.closed = False
         self._comp_on = False                        # this stream turned the channel's compression on
+        self._squelch_on = False                     # ... and its squelch
         self._greeting = deque()
         if hasattr(hub, "attach"):                   # this channel has a listener now: its results are queued from here on
             hub.attach(self.channel, wf=(kind != "SND"), snd=(kind == "SND"))
@@ -889,12 +950,30 @@ class GpuStream:
             gate, thresh = int(kv["nb"]), int(kv["th"])
             check_noise_blanker(gate, thresh)
             self.hub.set_noise_blanker(self.channel, gate, thresh)
+        elif "squelch" in kv:
+            self._set_squelch(kv, msg)
         elif "compression" in kv or "wf_comp" in kv:
             key = "compression" if self.kind == "SND" else "wf_comp"
             if key in kv:
                 self._set_compression(int(kv[key]) != 0)
         elif "zoom" in kv:
             self.zoom, self.start = int(kv["zoom"]), int(kv.get("start", 0))
+
+    def _set_squelch(self, kv, msg):
+        """both spellings: "squelch=<v> max=<m>" (the NBFM noise squelch) and "squelch=<v> param=<tail_s>" (the RSSI squelch)"""
+        from .engine import squelch_tail_frames
+        if ("max" in kv) == ("param" in kv):
+            raise ValueError("SET squelch= needs max= or param=: %r" % (msg,))
+        level = int(kv["squelch"])
+        if "max" in kv:
+            new = dict(fm_level=level, fm_max=int(kv["max"]))
+        else:
+            new = dict(rssi_level=level, tail_frames=squelch_tail_frames(float(kv["param"]), int(getattr(self.hub, "kiwi_rate", L.RATE))))
+        check_squelch(**new)
+        if hasattr(self.hub, "set_squelch"):
+            self.hub.set_squelch(self.channel, **new)
+            now = self.hub.squelch(self.channel)
+            self._squelch_on = bool(now[0] or now[2])
 
     def _set_compression(self, on):
         """the channel's flag for this stream's kind; the hub (and its engine) only hear of a change"""
@@ -950,6 +1029,9 @@ class GpuStream:
         if self._comp_on and not self.closed:        # the next connection's decoder starts from (0, 0): so does its encoder
             self._comp_on = False
             self.hub.set_compression(self.channel, **{("snd" if self.kind == "SND" else "wf"): False})
+        if self._squelch_on and not self.closed:     # the next connection starts with the squelch off, as on a server
+            self._squelch_on = False
+            self.hub.set_squelch(self.channel, fm_level=0, rssi_level=0)
         self.closed = True
 
 
