@@ -74,6 +74,43 @@ def encode(pcm, state=None):
     return out, rec, new
 
 
+def encode_stream(pcm, state=None):
+    """encode() of ONE stream in plain Python integers -> (uint8 [n_samples // 2], the new state int32 [2]).  The same steps as
+    encode(), to which tests/test_stage_matrix_inputs.py holds it byte for byte; for streams of 10^5 samples, where encode()'s
+    per-sample NumPy calls are the slow part."""
+    x = [int(v) for v in np.asarray(pcm).reshape(-1)]
+    if len(x) % 2:
+        raise ValueError("an even number of samples per stream")
+    index, prev = (0, 0) if state is None else (int(state[0]), int(state[1]))
+    if not (0 <= index <= 88 and -32768 <= prev <= 32767):
+        raise ValueError("state out of range")
+    step_t, adj_t = [int(v) for v in STEP], [int(v) for v in ADJ]
+    codes = bytearray(len(x))
+    for i, s in enumerate(x):
+        step = step_t[index]
+        d = s - prev
+        code = 0
+        if d < 0:
+            code, d = 8, -d
+        diff = step >> 3
+        if d >= step:
+            code |= 4
+            d -= step
+            diff += step
+        if d >= step >> 1:
+            code |= 2
+            d -= step >> 1
+            diff += step >> 1
+        if d >= step >> 2:
+            code |= 1
+            diff += step >> 2
+        prev = max(-32768, prev - diff) if code & 8 else min(32767, prev + diff)
+        index = min(88, max(0, index + adj_t[code]))
+        codes[i] = code
+    c = np.frombuffer(bytes(codes), np.uint8)
+    return (c[0::2] | (c[1::2] << 4)).astype(np.uint8), np.array([index, prev], np.int32)
+
+
 def encode_wf_lines(lines):
     """byte lines int [n, 1024] (values 0..255) -> uint8 [n, 517]: each line from (0, 0), WF_PAD samples of its last byte behind it"""
     b = np.asarray(lines, np.int64)

@@ -135,6 +135,29 @@ def closed_mask(pcm, rssi, mode, fm_level=0, fm_max=0, rssi_level=0, tail=0, sta
     return out
 
 
+def fm_trace(pcm, fm_level, fm_max, truncate=False):
+    """The NBFM noise squelch of one channel from a fresh state, frame by frame -> list of (N_f, A_{f-1}, A_f, closed).
+    truncate=True is NOT the definition: it rounds (N_f - A_{f-1}) / 4 towards zero where the definition floors -- what a kernel
+    that divided instead of shifting would compute; for tests that prove an input tells the two apart."""
+    check(fm_level, fm_max, 0, 0)
+    st = State()
+    pcm = np.asarray(pcm, np.int16)
+    t, tc = fm_thresholds(fm_level, fm_max)
+    out = []
+    for f in range(pcm.shape[0] // FRAME):
+        n = noise_power(pcm[f * FRAME:(f + 1) * FRAME], st)
+        before = st.a
+        if not st.primed:
+            st.a, st.primed = n, True
+            st.open = st.a <= t * t
+        else:
+            q = n - st.a
+            st.a += (-((-q) // 4) if q < 0 else q // 4) if truncate else q >> 2
+            st.open = (not st.a > tc * tc) if st.open else st.a <= t * t
+        out.append((n, before, st.a, not st.open))
+    return out
+
+
 def squelch(pcm, rssi, mode, fm_level=0, fm_max=0, rssi_level=0, tail=0, state=None):
     """One channel -> (pcm with the closed frames zeroed, closed mask)"""
     m = closed_mask(pcm, rssi, mode, fm_level, fm_max, rssi_level, tail, state)
