@@ -404,6 +404,47 @@ int ssdr_audio_squelch(ssdr_ctx *ctx, uint8_t *closed_out, int out_is_device);
  * than 12000 / 20250, a negative or NaN tail_s, or more than 1024 frames. */
 int ssdr_squelch_tail_frames(double tail_s, uint32_t kiwi_rate, uint32_t *frames);
 
+/* -- audio de-emphasis: the KiwiSDR's "SET de_emp=<n>" (AM) and "SET de_emp=<n> nfm=1" (NBFM).  On a KiwiSDR de-emphasis is
+ * server-side DSP, so the reference has no code for it: tests/deemp_ref.py is this project's definition.
+ * Per channel a one-pole low-pass runs on the int16 PCM x, its state S an int32 in Q8, carried from frame to frame and from call
+ * to call (0 after a reset):
+ *       X = x[n] << 8
+ *       S = S + (((X - S) * a) >> 16)      (int64 product, arithmetic shift: floor)
+ *       y[n] = (S + 128) >> 8              (arithmetic shift; 0 < a < 65536 keeps |S| <= 32768 * 256, so y is an int16 as it is)
+ * a = round(65536 (1 - exp(-1 / (rate tau)))) with rate = ssdr_set_kiwi_rate's (the PCM rate at every decimation) and tau = 75 us
+ * (setting 1) or 50 us (setting 2); the four values are literals (ssdr_deemp_coeff): 43962, 53158 at 12000 Hz and 31611, 41127 at
+ * 20250 Hz.  A channel carries two settings, each 0 (off), 1 or 2, and its current mode picks the one that acts:
+ *   SSDR_MODE_NBFM  nfm        SSDR_MODE_AM  am        LSB, USB, CW, IQ  never filtered; the state does not move
+ * The filter sits behind the AGC AND behind the squelch, in front of everything else that reads the PCM (the ADPCM encoder,
+ * ssdr_run_playbuffer, ssdr_output_checksum, the copies out): the noise squelch judges the un-de-emphasised discriminator noise,
+ * and a closed frame reaches the filter as zeros -- so with both on, a closed frame's PCM is the filter's decay (0 from about
+ * its 20th sample on), not 512 hard zeros; ssdr_audio_squelch still reports the frame as closed.  RSSI, the ADC-overflow flag,
+ * ssdr_audio_squelch and ssdr_audio_iq are untouched.
+ * The kernel (ssdr_deemp.hip) runs inside ssdr_run_audio and every path of ssdr_run_chain over the channels whose acting setting
+ * is on; with no such channel nothing is launched, and before the first nonzero setting nothing is allocated.  It has no
+ * SSDR_K_* slot: ssdr_deemphasis_stats is its own.  Cost: a first version of the
+ * kernel took 0.87 x the audio stage's time on an MI355X with every channel of a 65536-channel general-path batch filtering, 0.68 x with
+ * 1 % of them, 0.67 x and 0.60 x on BASELINE configs[3]'s mix (the squelch kernel: 0.18 x) -- bound by memory waits that the present
+ * kernel no longer has; the present kernel has not been timed yet (tools/deemp_probe.py).
+ * While any channel has a nonzero setting (acting or not: a mode change could make it act) ssdr_feed_open and
+ * ssdr_checkpoint_save / _load return SSDR_ESTATE, and while a pipelined feed is open ssdr_set_deemphasis returns SSDR_ESTATE. */
+typedef struct ssdr_deemp_params {
+    uint32_t am;            /* "de_emp=<n>" / "de_emp=<n> nfm=0": 0 off, 1 = 75 us, 2 = 50 us */
+    uint32_t nfm;           /* "de_emp=<n> nfm=1": the same */
+} ssdr_deemp_params;
+/* Channels [first, first + count): p [count].  A value above 2 or a range outside the ctx is SSDR_EINVAL, and then no channel
+ * is changed.  Every channel it names has S reset (so do ssdr_reset_state, ssdr_set_kiwi_rate and ssdr_set_decimation for every
+ * channel, and a mode change through ssdr_set_params for that channel only). */
+int ssdr_set_deemphasis(ssdr_ctx *ctx, uint32_t first, uint32_t count, const ssdr_deemp_params *p);
+int ssdr_get_deemphasis(ssdr_ctx *ctx, uint32_t first, uint32_t count, ssdr_deemp_params *p);
+/* a of a setting (1, 2) at a rate (12000, 20250), host only; anything else is SSDR_EINVAL */
+int ssdr_deemp_coeff(uint32_t setting, uint32_t kiwi_rate, uint32_t *a);
+/* S of channels [first, first + count) as the last audio run left it (for tests) */
+int ssdr_get_deemp_state(ssdr_ctx *ctx, uint32_t first, uint32_t count, int32_t *S);
+/* The de-emphasis kernel's launches since the last reset, and with ssdr_set_profiling on their summed time (a HIP-event pair per
+ * launch; launches made with profiling off count, and add no time). */
+int ssdr_deemphasis_stats(ssdr_ctx *ctx, float *total_ms, uint32_t *launches, int reset);
+
 /* -- pipelined host feed: the path a live ingest takes (KiwiSDRStream._process_iq_samples -> batches, kiwi/client.py:493)
  *
  * ssdr_push_iq + ssdr_run_* from pageable host memory serialise copy-in, kernels and copy-out.  The feed keeps `depth`

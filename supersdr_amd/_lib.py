@@ -68,6 +68,14 @@ class SquelchParams(C.Structure):
 
 
 assert C.sizeof(SquelchParams) == 16
+
+
+class DeempParams(C.Structure):
+    """ssdr_deemp_params: "SET de_emp=<n>" (am) and "SET de_emp=<n> nfm=1" (nfm); each 0 = off, 1 = 75 us, 2 = 50 us"""
+    _fields_ = [("am", C.c_uint32), ("nfm", C.c_uint32)]
+
+
+assert C.sizeof(DeempParams) == 8
 assert C.sizeof(ChanConsts) == 64 and C.sizeof(ChanState) == 64 and C.sizeof(ChanParams) == 88
 assert C.sizeof(Db2colChan) == 48 and C.sizeof(PlayChan) == 16
 WIRE_BODY = 17 + FRAME * 4
@@ -127,6 +135,11 @@ _SIGS = {
     "ssdr_get_squelch": (C.c_int, [_P, C.c_uint32, C.c_uint32, C.POINTER(SquelchParams)]),
     "ssdr_audio_squelch": (C.c_int, [_P, _P, C.c_int]),
     "ssdr_squelch_tail_frames": (C.c_int, [C.c_double, C.c_uint32, C.POINTER(C.c_uint32)]),
+    "ssdr_set_deemphasis": (C.c_int, [_P, C.c_uint32, C.c_uint32, C.POINTER(DeempParams)]),
+    "ssdr_get_deemphasis": (C.c_int, [_P, C.c_uint32, C.c_uint32, C.POINTER(DeempParams)]),
+    "ssdr_deemp_coeff": (C.c_int, [C.c_uint32, C.c_uint32, C.POINTER(C.c_uint32)]),
+    "ssdr_get_deemp_state": (C.c_int, [_P, C.c_uint32, C.c_uint32, C.POINTER(C.c_int32)]),
+    "ssdr_deemphasis_stats": (C.c_int, [_P, C.POINTER(C.c_float), C.POINTER(C.c_uint32), C.c_int]),
     "ssdr_feed_open": (C.c_int, [_P, C.c_uint32, C.c_uint32, C.c_uint32]),
     "ssdr_feed_slot": (C.c_int, [_P, C.POINTER(_P)]),
     "ssdr_feed_submit": (C.c_int, [_P]),

@@ -232,6 +232,17 @@ struct ssdr_ctx {
     size_t sq_closed_bytes = 0;
     bool sq_valid = false;
     uint32_t sq_frames = 0;
+    // audio de-emphasis (ssdr_set_deemphasis): host settings at its first call, device memory at the first nonzero setting; with
+    // no acting channel nothing is launched
+    std::vector<ssdr_deemp_params> h_de;                // [n_ch] as set
+    uint32_t de_set_n = 0;                              // channels with a nonzero setting, acting or not
+    std::vector<uint32_t> h_de_list;                    // [2 n_ch]: the acting channels, ascending, and from n_ch on their coefficients
+    uint32_t de_n = 0;
+    bool de_dirty = false;                              // settings, modes or the rate changed since the list was made
+    int32_t *d_de_state = nullptr;                      // [n_ch] S
+    uint32_t *d_de_list = nullptr;                      // [2 n_ch], as h_de_list
+    float de_ms = 0.0f;                                 // the kernel's own timing (not an SSDR_K_* slot): ssdr_deemphasis_stats
+    uint32_t de_launches = 0;
 };
 
 static int get_event(ssdr_ctx *c, hipEvent_t *e)
@@ -241,6 +252,7 @@ static int get_event(ssdr_ctx *c, hipEvent_t *e)
     return SSDR_OK;
 }
 // HIP events on the stream the kernel is launched on, bracketing exactly one launch.
+constexpr int kTimedDeemp = SSDR_K_COUNT;               // `which` of the de-emphasis kernel: timed beside the SSDR_K_* slots, not in them
 static int timed_begin(ssdr_ctx *c, hipStream_t s = nullptr)
 {
     if (!s) s = c->stream;
@@ -273,7 +285,8 @@ static int resolve_pending(ssdr_ctx *c)
         float ms = 0.0f;
         HIP_TRY(hipEventSynchronize(p.e1));
         HIP_TRY(hipEventElapsedTime(&ms, p.e0, p.e1));
-        if (p.which >= 0) { c->k_ms[p.which] += ms; c->k_n[p.which] += 1; c->last_ms = ms; }
+        if (p.which == kTimedDeemp) c->de_ms += ms;          // (its launches are counted where they are made)
+        else if (p.which >= 0) { c->k_ms[p.which] += ms; c->k_n[p.which] += 1; c->last_ms = ms; }
         c->free_events.push_back(p.e0);
         c->free_events.push_back(p.e1);
     }
@@ -309,7 +322,7 @@ void ssdr_destroy(ssdr_ctx *c)
                     c->d_iq_own, c->d_wf_out, c->d_pcm, c->d_rssi, c->d_flags, c->d_scratch, c->d_db2col, c->d_color, c->d_play,
                     c->d_play_taps, c->d_play_hist, c->d_play_hist_alt, c->d_play_rs_taps, c->d_play_out, c->d_wfdata, c->d_wfpend, c->d_trace, c->d_trace_y, c->d_smeter,
                     c->d_smeter_in, c->d_post_sel, c->d_wire, c->d_wire_rssi, c->d_play_mono, c->d_line1, c->d_dbchan1, c->d_color1, c->d_tw64, c->d_wire_gps, c->d_iq_out, c->d_zoom_taps, c->d_zoom_dphi, c->d_zoom_phase, c->d_zoom_hist, c->d_zoom_out,
-                    c->d_nb, c->d_nb_mask, c->d_comp_list, c->d_adpcm_state, c->d_snd_adpcm, c->d_wf_adpcm, c->d_sq, c->d_sq_list, c->d_sq_closed};
+                    c->d_nb, c->d_nb_mask, c->d_comp_list, c->d_adpcm_state, c->d_snd_adpcm, c->d_wf_adpcm, c->d_sq, c->d_sq_list, c->d_sq_closed, c->d_de_state, c->d_de_list};
     for (void *p : ptrs)
         if (p) (void)hipFree(p);
     if (c->ev0) (void)hipEventDestroy(c->ev0);
@@ -389,6 +402,7 @@ static int join_audio(ssdr_ctx *c);
 static int drain_audio(ssdr_ctx *c);
 static int nb_upload(ssdr_ctx *c, uint32_t first, uint32_t count);
 static int squelch_upload(ssdr_ctx *c, uint32_t first, uint32_t count);
+static int deemp_reset(ssdr_ctx *c, uint32_t first, uint32_t count);
 
 int ssdr_reset_state(ssdr_ctx *c, uint32_t first, uint32_t count) SSDR_GUARD
 {
@@ -415,6 +429,7 @@ int ssdr_reset_state(ssdr_ctx *c, uint32_t first, uint32_t count) SSDR_GUARD
     if (first == 0 && count == c->n_ch) { c->wf_phase = 0; c->synth_sample0 = 0; c->audio_started = false; }
     { int rcn = nb_upload(c, first, count); if (rcn != SSDR_OK) return rcn; }      // the blanker starts over (its gate at the current rate)
     { int rcq = squelch_upload(c, first, count); if (rcq != SSDR_OK) return rcq; } // and the squelch
+    { int rce = deemp_reset(c, first, count); if (rce != SSDR_OK) return rce; }    // and the de-emphasis
     return zoom_restart(c, first, count, false);         // the zoomed streams of these channels start over as well
 } SSDR_UNGUARD
 
@@ -435,6 +450,12 @@ int ssdr_set_params(ssdr_ctx *c, uint32_t first, uint32_t count, const ssdr_chan
             const ssdr_squelch_params &q = c->h_sq[first + i];
             if ((q.fm_level || q.rssi_level) && c->h_consts[first + i].mode != k[i].mode) sq_reset.push_back(first + i);
         }
+    std::vector<uint32_t> de_reset;                         // ... and the same for the de-emphasis
+    if (c->de_set_n)
+        for (uint32_t i = 0; i < count; i++) {
+            const ssdr_deemp_params &q = c->h_de[first + i];
+            if ((q.am || q.nfm) && c->h_consts[first + i].mode != k[i].mode) de_reset.push_back(first + i);
+        }
     for (uint32_t i = 0; i < count; i++) c->h_params[first + i] = p[i];
     for (uint32_t i = 0; i < count; i++) c->h_consts[first + i] = k[i];
     c->chan_list_dirty = true;
@@ -447,6 +468,13 @@ int ssdr_set_params(ssdr_ctx *c, uint32_t first, uint32_t count, const ssdr_chan
         i = j;
     }
     if (!sq_reset.empty()) { c->sq_dirty = true; c->sq_valid = false; }
+    for (size_t i = 0; i < de_reset.size();) {
+        size_t j = i + 1;
+        while (j < de_reset.size() && de_reset[j] == de_reset[j - 1] + 1) j++;
+        { int rce = deemp_reset(c, de_reset[i], (uint32_t)(j - i)); if (rce != SSDR_OK) return rce; }
+        i = j;
+    }
+    if (!de_reset.empty()) c->de_dirty = true;
     HIP_TRY(hipMemcpyAsync(c->d_consts + first, k.data(), count * sizeof(ssdr_chan_consts), hipMemcpyHostToDevice, c->stream));
     HIP_TRY(hipMemcpyAsync(c->d_taps + (size_t)first * SSDR_NTAP_MAX, taps.data(), taps.size() * sizeof(float),
                            hipMemcpyHostToDevice, c->stream));
@@ -1104,6 +1132,70 @@ static int squelch_launch(ssdr_ctx *c, hipStream_t s)
     return SSDR_OK;
 }
 
+// ---- audio de-emphasis: the kernel behind the squelch, in front of the encoder (ssdr_set_deemphasis) -------------------------
+// a = round(65536 (1 - exp(-1 / (rate tau)))), tau 75 us (setting 1) / 50 us (setting 2): literals, so that no libm decides a bit
+static uint32_t deemp_coeff(uint32_t setting, uint32_t kiwi_rate)
+{
+    if (kiwi_rate == SSDR_RATE) return setting == 1 ? 43962u : 53158u;
+    return setting == 1 ? 31611u : 41127u;
+}
+static inline uint32_t deemp_acting(const ssdr_deemp_params &q, uint32_t mode)
+{
+    return mode == SSDR_MODE_NBFM ? q.nfm : (mode == SSDR_MODE_AM ? q.am : 0u);
+}
+// S of channels [first, first + count) back to 0
+static int deemp_reset(ssdr_ctx *c, uint32_t first, uint32_t count)
+{
+    if (!c->d_de_state || !count) return SSDR_OK;
+    { int rcj = join_audio(c); if (rcj != SSDR_OK) return rcj; }
+    HIP_TRY(hipMemsetAsync(c->d_de_state + first, 0, (size_t)count * sizeof(int32_t), c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return SSDR_OK;
+}
+// the list of the acting channels and their coefficients, after a change of settings, modes or the rate
+static int deemp_prepare(ssdr_ctx *c)
+{
+    if (!c->de_dirty) return SSDR_OK;
+    uint32_t n = 0;
+    if (c->de_set_n) {
+        c->h_de_list.resize((size_t)2 * c->n_ch);
+        for (uint32_t ch = 0; ch < c->n_ch; ch++) {
+            const uint32_t setting = deemp_acting(c->h_de[ch], c->h_consts[ch].mode);
+            if (!setting) continue;
+            c->h_de_list[n] = ch;
+            c->h_de_list[(size_t)c->n_ch + n] = deemp_coeff(setting, c->kiwi_rate);
+            n++;
+        }
+    }
+    if (n) {
+        { int rcj = join_audio(c); if (rcj != SSDR_OK) return rcj; }     // a kernel in flight reads the list
+        HIP_TRY(hipMemcpyAsync(c->d_de_list, c->h_de_list.data(), (size_t)n * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(hipMemcpyAsync(c->d_de_list + c->n_ch, c->h_de_list.data() + c->n_ch, (size_t)n * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(hipStreamSynchronize(c->stream));
+    }
+    c->de_n = n;
+    c->de_dirty = false;
+    return SSDR_OK;
+}
+// filter the PCM of the audio stage (and squelch) just queued on `s`, behind them on the same stream
+static int deemp_launch(ssdr_ctx *c, hipStream_t s)
+{
+    if (!c->de_n) return SSDR_OK;
+    SsdrDeempArgs q;
+    q.pcm = c->d_pcm;
+    q.n_samples = c->in_frames * SSDR_FRAME;
+    q.list = c->d_de_list;
+    q.coef = c->d_de_list + c->n_ch;
+    q.list_n = c->de_n;
+    q.state = c->d_de_state;
+    int rc;
+    if (c->profiling && (rc = timed_begin(c, s)) != SSDR_OK) return rc;       // (untimed otherwise: ssdr_elapsed_ms stays the stage's)
+    HIP_TRY(ssdr_launch_deemp(q, s));
+    if (c->profiling && (rc = timed_end(c, kTimedDeemp, s)) != SSDR_OK) return rc;
+    c->de_launches++;
+    return SSDR_OK;
+}
+
 int ssdr_run_wf(ssdr_ctx *c, int16_t *wf_sum_out, uint32_t *lines_ready, int out_is_device) SSDR_GUARD
 {
     if (!c) return SSDR_EINVAL;
@@ -1236,6 +1328,7 @@ int ssdr_run_audio(ssdr_ctx *c, int16_t *pcm_out, float *rssi_out, int out_is_de
     c->snd_adpcm_valid = false;
     { int rcq = squelch_prepare(c); if (rcq != SSDR_OK) return rcq; }
     c->sq_valid = false;
+    { int rce = deemp_prepare(c); if (rce != SSDR_OK) return rce; }
     SsdrAudioArgs a;
     a.iq = c->d_iq;
     a.ch_stride = (uint64_t)in_len(c, c->in_frames);
@@ -1303,7 +1396,8 @@ int ssdr_run_audio(ssdr_ctx *c, int16_t *pcm_out, float *rssi_out, int out_is_de
         if (fa.wf.tail)          // hop 512: only now may the carried half-line (the kernel's line 0 read it) become this batch's last one
             HIP_TRY(hipMemcpy2DAsync(c->d_wf_tail, (SSDR_NFFT / 2) * 4, fa.wf.iq + (size_t)(fa.wf.n_lines - 1) * SSDR_FRAME,
                                      fa.wf.ch_stride * 4, (SSDR_NFFT / 2) * 4, c->n_ch, hipMemcpyDeviceToDevice, s));
-        if ((rc = squelch_launch(c, s)) != SSDR_OK) return rc;            // squelch, then the encoders, behind the one-read kernel
+        if ((rc = squelch_launch(c, s)) != SSDR_OK) return rc;            // squelch, de-emphasis, then the encoders, behind the one-read kernel
+        if ((rc = deemp_launch(c, s)) != SSDR_OK) return rc;
         if ((rc = adpcm_snd_launch(c, s)) != SSDR_OK) return rc;
         if ((rc = adpcm_wf_launch(c, s, fa.wf.n_avg)) != SSDR_OK) return rc;
         return SSDR_OK;
@@ -1365,6 +1459,7 @@ int ssdr_run_audio(ssdr_ctx *c, int16_t *pcm_out, float *rssi_out, int out_is_de
         }
     }
     if ((rc = squelch_launch(c, s)) != SSDR_OK) return rc;
+    if ((rc = deemp_launch(c, s)) != SSDR_OK) return rc;
     if ((rc = adpcm_snd_launch(c, s)) != SSDR_OK) return rc;
     const hipMemcpyKind kind = out_is_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
     if (pcm_out) HIP_TRY(hipMemcpyAsync(pcm_out, c->d_pcm, (size_t)c->n_ch * c->in_frames * SSDR_FRAME * 2, kind, s));
@@ -1664,7 +1759,7 @@ int ssdr_feed_open(ssdr_ctx *c, uint32_t n_frames, uint32_t depth, uint32_t flag
 {
     if (!c || n_frames == 0 || (n_frames & 1u) || depth < 2 || depth > 16 || (flags & ~(uint32_t)(SSDR_FEED_WIRE | SSDR_FEED_POST | SSDR_FEED_LAZY_OUT))) return SSDR_EINVAL;
     if (!c->feed.empty() || c->concurrent || c->decim != 1 || c->zoom != 1) return SSDR_ESTATE;
-    if (c->comp_snd_n || c->comp_wf_n || c->sq_set_n) return SSDR_ESTATE;   // no wire compression and no squelch in the slot pipeline      // the feed's slots are sized for un-zoomed 12 kHz IQ
+    if (c->comp_snd_n || c->comp_wf_n || c->sq_set_n || c->de_set_n) return SSDR_ESTATE;   // no wire compression, squelch or de-emphasis in the slot pipeline      // the feed's slots are sized for un-zoomed 12 kHz IQ
     HIP_TRY(hipSetDevice(c->device));
     const bool post = (flags & SSDR_FEED_POST) != 0;
     if (post) { int rcp = ensure_play(c); if (rcp != SSDR_OK) return rcp; }
@@ -2054,6 +2149,7 @@ int ssdr_checkpoint_save(ssdr_ctx *c, void *blob) SSDR_GUARD
     if (c->nb_on) return SSDR_ESTATE;                        // nor is the noise blanker's state
     if (c->comp_snd_n || c->comp_wf_n) return SSDR_ESTATE;   // nor the wire encoders'
     if (c->sq_set_n) return SSDR_ESTATE;                     // nor the squelch's
+    if (c->de_set_n) return SSDR_ESTATE;                     // nor the de-emphasis's
     SsdrCkptHeader h = {kCkptMagic, kCkptVersion, c->n_ch, c->n_avg, c->wf_phase, c->audio_started ? 1u : 0u, c->kiwi_rate,
                         c->d_play_hist ? 1u : 0u, c->synth_sample0, c->hop, c->decim};
     char *p = static_cast<char *>(blob);
@@ -2098,7 +2194,7 @@ int ssdr_checkpoint_load(ssdr_ctx *c, const void *blob, uint64_t bytes) SSDR_GUA
     std::vector<float> ktaps(n * SSDR_NTAP_MAX);
     for (size_t i = 0; i < n; i++)
         if (ssdr_compile_params_host(&prm[i], &kc[i], ktaps.data() + i * SSDR_NTAP_MAX, h.decim, h.kiwi_rate) != SSDR_OK) return SSDR_EINVAL;
-    if (!c->feed.empty() || c->zoom > 1 || c->nb_on || c->comp_snd_n || c->comp_wf_n || c->sq_set_n) return SSDR_ESTATE;
+    if (!c->feed.empty() || c->zoom > 1 || c->nb_on || c->comp_snd_n || c->comp_wf_n || c->sq_set_n || c->de_set_n) return SSDR_ESTATE;
     std::vector<double> play_hist;                          // play_buffer state that arrives before its buffers exist: applied at first use
     if (h.has_play && !c->d_play_hist) {
         const double *q = reinterpret_cast<const double *>(static_cast<const char *>(blob) + sizeof h + n * (sizeof(ssdr_chan_consts) +
@@ -2418,6 +2514,7 @@ int ssdr_set_kiwi_rate(ssdr_ctx *c, uint32_t kiwi_rate) SSDR_GUARD
     std::vector<ssdr_chan_params> all = c->h_params;
     const uint32_t keep = c->kiwi_rate;
     c->kiwi_rate = kiwi_rate;
+    c->de_dirty = true;                                           // the de-emphasis coefficients are the rate's
     int rc = ssdr_set_params(c, 0, c->n_ch, all.data());
     if (rc == SSDR_OK) {
         c->have_input = false;
@@ -2795,6 +2892,78 @@ int ssdr_audio_squelch(ssdr_ctx *c, uint8_t *closed_out, int out_is_device) SSDR
     HIP_TRY(hipStreamSynchronize(c->stream));
     memset(closed_out, 0, (size_t)c->n_ch * row);
     for (uint32_t i = 0; i < c->sq_n; i++) memcpy(closed_out + (size_t)c->h_sq_list[i] * row, rows.data() + (size_t)i * row, row);
+    return SSDR_OK;
+} SSDR_UNGUARD
+
+int ssdr_deemp_coeff(uint32_t setting, uint32_t kiwi_rate, uint32_t *a) SSDR_GUARD
+{
+    if (!a || setting < 1 || setting > 2 || (kiwi_rate != SSDR_RATE && kiwi_rate != SSDR_RATE_WIDE)) return SSDR_EINVAL;
+    *a = deemp_coeff(setting, kiwi_rate);
+    return SSDR_OK;
+} SSDR_UNGUARD
+
+int ssdr_set_deemphasis(ssdr_ctx *c, uint32_t first, uint32_t count, const ssdr_deemp_params *p) SSDR_GUARD
+{
+    if (!c || (uint64_t)first + count > c->n_ch || (count && !p)) return SSDR_EINVAL;
+    for (uint32_t i = 0; i < count; i++)                    // all or nothing: every channel is checked before any is changed
+        if (p[i].am > 2 || p[i].nfm > 2) return SSDR_EINVAL;
+    if (!c->feed.empty()) return SSDR_ESTATE;
+    if (!count) return SSDR_OK;
+    HIP_TRY(hipSetDevice(c->device));
+    bool any = false;
+    for (uint32_t i = 0; i < count; i++) any = any || p[i].am || p[i].nfm;
+    if (!c->d_de_state && any) {                            // the first nonzero setting: state and list
+        { int rcj = join_audio(c); if (rcj != SSDR_OK) return rcj; }
+        if (!c->d_de_list) {
+            uint32_t *l = nullptr;
+            HIP_TRY(hipMalloc(&l, (size_t)2 * c->n_ch * sizeof(uint32_t)));
+            c->d_de_list = l;
+        }
+        int32_t *d = nullptr;
+        HIP_TRY(hipMalloc(&d, (size_t)c->n_ch * sizeof(int32_t)));
+        c->d_de_state = d;
+        { int rcr = deemp_reset(c, 0, c->n_ch); if (rcr != SSDR_OK) return rcr; }
+    }
+    if (c->h_de.empty()) c->h_de.assign(c->n_ch, ssdr_deemp_params{0u, 0u});
+    uint32_t set_n = c->de_set_n;
+    for (uint32_t i = 0; i < count; i++) {
+        const ssdr_deemp_params &was = c->h_de[first + i];
+        set_n = set_n - ((was.am || was.nfm) ? 1u : 0u) + ((p[i].am || p[i].nfm) ? 1u : 0u);
+        c->h_de[first + i] = p[i];
+    }
+    c->de_set_n = set_n;
+    c->de_dirty = true;
+    return deemp_reset(c, first, count);
+} SSDR_UNGUARD
+
+int ssdr_get_deemphasis(ssdr_ctx *c, uint32_t first, uint32_t count, ssdr_deemp_params *p) SSDR_GUARD
+{
+    if (!c || (uint64_t)first + count > c->n_ch || (count && !p)) return SSDR_EINVAL;
+    for (uint32_t i = 0; i < count; i++) p[i] = c->h_de.empty() ? ssdr_deemp_params{0u, 0u} : c->h_de[first + i];
+    return SSDR_OK;
+} SSDR_UNGUARD
+
+int ssdr_get_deemp_state(ssdr_ctx *c, uint32_t first, uint32_t count, int32_t *S) SSDR_GUARD
+{
+    if (!c || (uint64_t)first + count > c->n_ch || (count && !S)) return SSDR_EINVAL;
+    if (!count) return SSDR_OK;
+    if (!c->d_de_state) { memset(S, 0, (size_t)count * sizeof(int32_t)); return SSDR_OK; }
+    HIP_TRY(hipSetDevice(c->device));
+    { int rcj = join_audio(c); if (rcj != SSDR_OK) return rcj; }
+    HIP_TRY(hipMemcpyAsync(S, c->d_de_state + first, (size_t)count * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return SSDR_OK;
+} SSDR_UNGUARD
+
+int ssdr_deemphasis_stats(ssdr_ctx *c, float *total_ms, uint32_t *launches, int reset) SSDR_GUARD
+{
+    if (!c) return SSDR_EINVAL;
+    HIP_TRY(hipSetDevice(c->device));
+    int rc = resolve_pending(c);
+    if (rc != SSDR_OK) return rc;
+    if (total_ms) *total_ms = c->de_ms;
+    if (launches) *launches = c->de_launches;
+    if (reset) { c->de_ms = 0.0f; c->de_launches = 0; }
     return SSDR_OK;
 } SSDR_UNGUARD
 

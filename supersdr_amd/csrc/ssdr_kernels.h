@@ -186,6 +186,17 @@ struct SsdrSquelchArgs {
     uint8_t *closed;                         // [list_n][n_frames] 1 where the frame was zeroed
 };
 hipError_t ssdr_launch_squelch(const SsdrSquelchArgs &a, hipStream_t stream);
+// audio de-emphasis (ssdr_deemp.hip): one lane per listed channel, in place on the PCM behind the squelch.  The list holds the
+// channels whose acting setting is on and, beside each, its coefficient a (ssdr_deemp_coeff); S is the carried Q8 state.
+struct SsdrDeempArgs {
+    int16_t *pcm;                            // [n_ch][n_samples], 16-byte aligned
+    uint32_t n_samples;                      // n_frames * 512
+    const uint32_t *list;                    // [list_n] channels, ascending
+    const uint32_t *coef;                    // [list_n] a of list[i]
+    uint32_t list_n;
+    int32_t *state;                          // [n_ch] S
+};
+hipError_t ssdr_launch_deemp(const SsdrDeempArgs &a, hipStream_t stream);
 #define SSDR_ZOOM_HIST 256                  // raw input samples carried per channel (>= 32 Z - 2 for Z <= 8)
 #define SSDR_ZOOM_TAPS_MAX 255
 struct SsdrZoomArgs {

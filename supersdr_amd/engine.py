@@ -94,6 +94,26 @@ def check_squelch(fm_level=0, fm_max=0, rssi_level=0, tail_frames=0):
             raise ValueError("squelch %s %r: out of range %d..%d" % (name, v, lo, hi))
 
 
+DEEMP_SETTING = (0, 2)          # ssdr_set_deemphasis: 0 off, 1 = 75 us, 2 = 50 us
+
+
+def deemp_coeff(setting, rate=L.RATE):
+    """a of the de-emphasis filter S += ((X - S) * a) >> 16 for setting 1 (75 us) / 2 (50 us) at 12000 / 20250 Hz (ssdr_deemp_coeff;
+    ValueError for anything else)"""
+    a = C.c_uint32()
+    if not 0 <= int(setting) < 2 ** 32 or not 0 <= int(rate) < 2 ** 32 or \
+            lib.ssdr_deemp_coeff(int(setting), int(rate), C.byref(a)) != L.OK:
+        raise ValueError("de-emphasis setting %r at %r Hz: no such filter (1 or 2 at 12000 or 20250 Hz)" % (setting, rate))
+    return a.value
+
+
+def check_deemphasis(am=None, nfm=None):
+    """ValueError unless the two are something ssdr_set_deemphasis takes (None: not given)"""
+    for v, name in ((am, "am"), (nfm, "nfm")):
+        if v is not None and not DEEMP_SETTING[0] <= int(v) <= DEEMP_SETTING[1]:
+            raise ValueError("de-emphasis %s %r: out of range %d..%d" % (name, v, DEEMP_SETTING[0], DEEMP_SETTING[1]))
+
+
 def _nb_array(v, n, name):
     a = np.broadcast_to(np.asarray(v, np.int64), (n,))
     if ((a < 0) | (a >= 2 ** 32)).any():
@@ -352,6 +372,38 @@ class SsdrEngine:
         out = np.empty((self.n_ch, self.audio_frames), np.uint8)
         check(lib.ssdr_audio_squelch(self._ctx, out.ctypes.data, 0), "ssdr_audio_squelch")
         return out
+
+    def set_deemphasis(self, first, params):
+        """The audio de-emphasis of channels first, first + 1, ...: params is a sequence of (am, nfm), one per channel ("SET de_emp=<n>":
+        am, acts while the channel is in AM; "SET de_emp=<n> nfm=1": nfm, acts in NBFM; each 0 = off, 1 = 75 us, 2 = 50 us).  Resets
+        those channels' filter state.  A value that is not a uint32 raises ValueError before the library is called; one the library
+        refuses raises SsdrError (SSDR_EINVAL).  Either way no channel is changed."""
+        a = np.asarray(params, np.int64).reshape(-1, 2)
+        if ((a < 0) | (a >= 2 ** 32)).any():
+            raise ValueError("de-emphasis settings %r: out of range" % (params,))
+        arr = (L.DeempParams * len(a))(*[L.DeempParams(int(row[0]), int(row[1])) for row in a])
+        check(lib.ssdr_set_deemphasis(self._ctx, int(first), len(a), arr), "ssdr_set_deemphasis")
+
+    def deemphasis(self, first=0, count=None):
+        """-> uint32 [count, 2]: am, nfm of channels first .. first + count - 1 as set"""
+        count = self.n_ch - first if count is None else count
+        arr = (L.DeempParams * max(count, 1))()
+        check(lib.ssdr_get_deemphasis(self._ctx, int(first), int(count), arr), "ssdr_get_deemphasis")
+        return np.array([[q.am, q.nfm] for q in arr[:count]], np.uint32).reshape(count, 2)
+
+    def deemp_state(self, first=0, count=None):
+        """-> int32 [count]: the filter state S (Q8) of channels first .. first + count - 1 as the last audio run left it"""
+        count = self.n_ch - first if count is None else count
+        out = np.zeros(max(count, 1), np.int32)
+        check(lib.ssdr_get_deemp_state(self._ctx, int(first), int(count), out.ctypes.data_as(C.POINTER(C.c_int32))),
+              "ssdr_get_deemp_state")
+        return out[:count]
+
+    def deemp_stats(self, reset=False):
+        """-> (total_ms, launches) of the de-emphasis kernel since the last reset (the time only with set_profiling on)"""
+        ms, n = C.c_float(), C.c_uint32()
+        check(lib.ssdr_deemphasis_stats(self._ctx, C.byref(ms), C.byref(n), 1 if reset else 0), "ssdr_deemphasis_stats")
+        return ms.value, n.value
 
     def audio_iq(self):
         """-> int16 [n_ch, n_frames*512, 2]: I,Q of the channels in "iq" mode for the last run_audio (rows of other modes: 0)"""

@@ -40,7 +40,7 @@ import numpy as np
 
 from . import _lib as L
 from ._lib import Db2colChan, PlayChan
-from .engine import SsdrEngine, check_noise_blanker, check_squelch, default_params
+from .engine import SsdrEngine, check_deemphasis, check_noise_blanker, check_squelch, default_params
 
 IQ_SPAN_KHZ = L.RATE / 1000.0          # what one channel's GPU waterfall covers: the IQ band around its centre (12 kHz; hub.iq_span_khz)
 
@@ -272,6 +272,7 @@ class IQHub:
         self._default_params = default_params("am")
         self._n_iq_mode = 0
         self._squelch = {}                           # channel -> (fm_level, fm_max, rssi_level, tail_frames), for the channels that were given any
+        self._deemp = {}                             # channel -> (am, nfm), for the channels that were given any
         self._sq_act = set()                         # channels whose setting acts in their current mode (the engine squelches them)
         self._comp_snd, self._comp_wf = [], []       # channels with "SET compression=1" / "SET wf_comp=1", sorted (the engine's row order)
         self._want_n = np.ones(self.n_ch, np.int32)  # averaging_n asked for by each channel's waterfall client
@@ -433,6 +434,32 @@ class IQHub:
                 raise ValueError("this engine has no squelch (set_squelch)")
             self._squelch[c] = new
             (self._sq_act.add if acts else self._sq_act.discard)(c)
+
+    def deemphasis(self, channel):
+        """-> (am, nfm) of the channel as set (both 0: never set, or off)"""
+        with self._lock:
+            return self._deemp.get(int(channel), (0, 0))
+
+    def set_deemphasis(self, channel, am=None, nfm=None):
+        """The audio de-emphasis of one channel (ssdr_set_deemphasis); None leaves a value as it is.  am: "SET de_emp=<n>", the filter
+        that acts while the channel is in AM; nfm: "SET de_emp=<n> nfm=1", the one that acts in NBFM; each 0 = off, 1 = 75 us,
+        2 = 50 us.  ValueError out of range, and then nothing changes.  A nonzero setting on an engine without set_deemphasis, or on
+        the pipelined hub (the feed does not run the filter), is a ValueError.  Resets the channel's filter state."""
+        c = int(channel)
+        if not 0 <= c < self.n_ch:
+            raise IndexError("channel %d of %d" % (c, self.n_ch))
+        check_deemphasis(am, nfm)
+        with self._lock:
+            old = self._deemp.get(c, (0, 0))
+            new = tuple(int(o if v is None else v) for o, v in zip(old, (am, nfm)))
+            if self.pipeline:
+                if new[0] or new[1]:
+                    raise ValueError("de-emphasis needs the synchronous hub (the pipelined feed does not run it)")
+            elif hasattr(self.engine, "set_deemphasis"):
+                self.engine.set_deemphasis(c, [new])
+            elif new[0] or new[1]:
+                raise ValueError("this engine has no de-emphasis (set_deemphasis)")
+            self._deemp[c] = new
 
     def compression(self, channel):
         """-> (snd, wf): whether the channel's SND frames / W/F lines are IMA-ADPCM compressed"""
@@ -893,6 +920,12 @@ class GpuStream:
     output until the channel goes to "SET mod=nbfm".  A closed frame goes out with its 512 samples 0 (and is what the ADPCM encoder
     encodes with "SET compression=1"); RSSI and the ADC-overflow bit stay.  A missing second key, a non-number or a value out of
     range raises ValueError.  close_connection turns a squelch this stream turned on off again.
+    "SET de_emp=%d" and "SET de_emp=%d nfm=0" set the channel's AM de-emphasis and "SET de_emp=%d nfm=1" its NBFM de-emphasis (0 off,
+    1 = 75 us, 2 = 50 us) on an SND stream -- IQHub.set_deemphasis, ssdr_set_deemphasis; a W/F stream ignores them.  The channel's
+    mode picks the setting that acts, and lsb / usb / cw / iq are never filtered.  The filter runs behind the squelch: a closed frame
+    goes out as the filter's decay to 0.  A non-integer, a value outside 0..2 or nfm outside 0..1 raises ValueError.
+    close_connection turns a de-emphasis this stream turned on off again -- judged, like the squelch, by the channel's settings after this
+    stream's last "SET de_emp=": any setting left nonzero then, also one that somebody else made, counts as this stream's.
     "SET compression=%d" on an SND stream and "SET wf_comp=%d" on a W/F stream (kiwi/client.py:296-305) switch the channel's wire
     compression (IQHub.set_compression: 0 off, any other integer on; not an integer: ValueError; the other stream kind ignores
     them).  A compressed SND frame carries 256 bytes of IMA ADPCM for 512 samples, its encoder state kept for the whole connection
@@ -917,6 +950,7 @@ class GpuStream:
         self.closed = False
         self._comp_on = False                        # this stream turned the channel's compression on
         self._squelch_on = False                     # ... and its squelch
+        self._deemp_on = False                       # ... and its de-emphasis
         self._greeting = deque()
         if hasattr(hub, "attach"):                   # this channel has a listener now: its results are queued from here on
             hub.attach(self.channel, wf=(kind != "SND"), snd=(kind == "SND"))
@@ -952,6 +986,9 @@ class GpuStream:
             self.hub.set_noise_blanker(self.channel, gate, thresh)
         elif "squelch" in kv:
             self._set_squelch(kv, msg)
+        elif "de_emp" in kv:
+            if self.kind == "SND":
+                self._set_deemphasis(kv, msg)
         elif "compression" in kv or "wf_comp" in kv:
             key = "compression" if self.kind == "SND" else "wf_comp"
             if key in kv:
@@ -974,6 +1011,17 @@ class GpuStream:
             self.hub.set_squelch(self.channel, **new)
             now = self.hub.squelch(self.channel)
             self._squelch_on = bool(now[0] or now[2])
+
+    def _set_deemphasis(self, kv, msg):
+        """"de_emp=<n>" / "de_emp=<n> nfm=0": the AM setting; "de_emp=<n> nfm=1": the NBFM one"""
+        n, nfm = int(kv["de_emp"]), int(kv.get("nfm", 0))
+        if nfm not in (0, 1):
+            raise ValueError("SET de_emp= with nfm outside 0..1: %r" % (msg,))
+        new = dict(nfm=n) if nfm else dict(am=n)
+        check_deemphasis(**new)
+        if hasattr(self.hub, "set_deemphasis"):
+            self.hub.set_deemphasis(self.channel, **new)
+            self._deemp_on = any(self.hub.deemphasis(self.channel))
 
     def _set_compression(self, on):
         """the channel's flag for this stream's kind; the hub (and its engine) only hear of a change"""
@@ -1032,6 +1080,9 @@ class GpuStream:
         if self._squelch_on and not self.closed:     # the next connection starts with the squelch off, as on a server
             self._squelch_on = False
             self.hub.set_squelch(self.channel, fm_level=0, rssi_level=0)
+        if self._deemp_on and not self.closed:       # ... and with the de-emphasis off
+            self._deemp_on = False
+            self.hub.set_deemphasis(self.channel, am=0, nfm=0)
         self.closed = True
 
 
