@@ -22,6 +22,12 @@ static thread_local char g_hip_err[256] = "";
             return e_ == hipErrorOutOfMemory ? SSDR_ENOMEM : SSDR_EHIP;                 \
         }                                                                               \
     } while (0)
+// ... and a code of ours: evaluated once, handed on unless it is SSDR_OK
+#define SSDR_TRY(expr)                                                                  \
+    do {                                                                                \
+        const int rc_ = (expr);                                                         \
+        if (rc_ != SSDR_OK) return rc_;                                                 \
+    } while (0)
 
 // "Never throws": every `int` entry point is a function-try-block.  A host allocation that fails (std::vector, std::bad_alloc)
 // or anything else thrown below the C boundary comes back as a return code, like the reference's own policy of turning errors into
@@ -244,6 +250,31 @@ struct ssdr_ctx {
     float de_ms = 0.0f;                                 // the kernel's own timing (not an SSDR_K_* slot): ssdr_deemphasis_stats
     uint32_t de_launches = 0;
 };
+// Every device buffer a ctx owns (the feed slots' own: ssdr_feed_close) -- what ssdr_destroy frees.  One line per section of the
+// struct above, in its order: a new `d_` member joins its section's line HERE, and tests/test_gpu_parity.py's
+// test_contexts_release_their_device_memory gets a call that allocates it.
+static void free_owned(ssdr_ctx *c)
+{
+    void *const owned[] = {
+        c->d_wf_tail,
+        c->d_win, c->d_thr, c->d_tw64, c->d_tw, c->d_lut,                                                             // tables
+        c->d_zoom_taps, c->d_zoom_dphi, c->d_zoom_phase, c->d_zoom_hist, c->d_zoom_out,                               // zoom stage
+        c->d_consts, c->d_taps, c->d_state, c->d_hist, c->d_chan_list, c->d_ws_list, c->d_wf_acc[0], c->d_wf_acc[1],  // per-channel
+        c->d_iq_own,                                                                                                  // input batch
+        c->d_wf_out, c->d_pcm, c->d_rssi, c->d_iq_out, c->d_flags,                                                    // outputs
+        c->d_line1, c->d_dbchan1, c->d_color1,                                                                        // pipelined host feed
+        c->d_scratch,                                                                                                 // measurement
+        c->d_post_sel, c->d_db2col, c->d_color, c->d_play, c->d_play_taps, c->d_play_hist, c->d_play_rs_taps, c->d_play_hist_alt,
+        c->d_wfdata, c->d_wfpend, c->d_trace, c->d_trace_y, c->d_smeter, c->d_smeter_in, c->d_play_out, c->d_play_mono,
+        c->d_wire, c->d_wire_rssi, c->d_wire_gps,                                                                     // post-processing
+        c->d_nb, c->d_nb_mask,                                                                                        // noise blanker
+        c->d_comp_list, c->d_adpcm_state, c->d_snd_adpcm, c->d_wf_adpcm,                                              // wire compression
+        c->d_sq, c->d_sq_list, c->d_sq_closed,                                                                        // squelch
+        c->d_de_state, c->d_de_list,                                                                                  // de-emphasis
+    };
+    for (void *p : owned)
+        if (p) (void)hipFree(p);
+}
 
 static int get_event(ssdr_ctx *c, hipEvent_t *e)
 {
@@ -258,9 +289,8 @@ static int timed_begin(ssdr_ctx *c, hipStream_t s = nullptr)
     if (!s) s = c->stream;
     if (c->profiling) {
         ssdr_ctx::Pending p{nullptr, nullptr, -1};
-        int rc;
-        if ((rc = get_event(c, &p.e0)) != SSDR_OK) return rc;
-        if ((rc = get_event(c, &p.e1)) != SSDR_OK) return rc;
+        SSDR_TRY(get_event(c, &p.e0));
+        SSDR_TRY(get_event(c, &p.e1));
         c->pending.push_back(p);
         HIP_TRY(hipEventRecord(p.e0, s));
     } else {
@@ -293,6 +323,78 @@ static int resolve_pending(ssdr_ctx *c)
     c->pending.clear();
     return SSDR_OK;
 }
+// one launch on `s`, bracketed by timed_begin / timed_end only while profiling: what runs behind a stage is untimed otherwise, so
+// that ssdr_elapsed_ms stays the stage's.  `launch` returns a code (its HIP_TRY names the kernel in ssdr_last_hip_error)
+template <class F> static int timed_launch(ssdr_ctx *c, int which, hipStream_t s, F launch)
+{
+    if (c->profiling) SSDR_TRY(timed_begin(c, s));
+    SSDR_TRY(launch());
+    if (c->profiling) SSDR_TRY(timed_end(c, which, s));
+    return SSDR_OK;
+}
+
+// An audio stage that ran beside the waterfall kernel (stream2) and has not been joined yet: everything that follows on the
+// main stream and touches what it reads or writes (input, constants, state, PCM, RSSI, flags) waits for it first.
+static int join_audio(ssdr_ctx *c)
+{
+    if (c->audio_pending) { HIP_TRY(hipStreamWaitEvent(c->stream, c->ev_a, 0)); c->audio_pending = false; }
+    return SSDR_OK;
+}
+// ... and before a buffer it uses is freed on the host side
+static int drain_audio(ssdr_ctx *c)
+{
+    if (c->audio_pending) { HIP_TRY(hipStreamSynchronize(c->stream2)); c->audio_pending = false; }
+    return SSDR_OK;
+}
+
+// a device buffer back to the runtime, once what is queued on the main stream has finished with it
+template <class T> static int release(ssdr_ctx *c, T *&ptr)
+{
+    if (!ptr) return SSDR_OK;
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    HIP_TRY(hipFree(ptr));
+    ptr = nullptr;
+    return SSDR_OK;
+}
+// room for `need` units of `unit_bytes` in a buffer that holds `cap` of them.  While the allocation is under way the ctx says
+// "no buffer, no room", so one that fails leaves it consistent.  (Buffers that share one capacity: ensure_audio_out, ssdr_push_iq_wire.)
+template <class T> static int grow(ssdr_ctx *c, T *&ptr, size_t &cap, size_t need, size_t unit_bytes)
+{
+    if (cap >= need) return SSDR_OK;
+    SSDR_TRY(release(c, ptr));
+    cap = 0;
+    HIP_TRY(hipMalloc(&ptr, need * unit_bytes));
+    cap = need;
+    return SSDR_OK;
+}
+// a result on the main stream to the caller's buffer, host or device.  Each getter keeps its own rule for when the call waits.
+enum CopySync { kSyncHost /* only for a host destination */, kSyncAlways, kSyncLater /* the caller does, behind more copies */ };
+static int copy_out(ssdr_ctx *c, void *dst, const void *src, size_t bytes, int out_is_device, CopySync sync)
+{
+    HIP_TRY(hipMemcpyAsync(dst, src, bytes, out_is_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, c->stream));
+    if (sync == kSyncAlways || (sync == kSyncHost && !out_is_device)) HIP_TRY(hipStreamSynchronize(c->stream));
+    return SSDR_OK;
+}
+// fn(i, n) for every run list[i], list[i] + 1, ... of n consecutive channel numbers in an ascending list
+template <class F> static int for_each_run(const uint32_t *list, size_t len, F fn)
+{
+    for (size_t i = 0; i < len;) {
+        size_t j = i + 1;
+        while (j < len && list[j] == list[j - 1] + 1) j++;
+        SSDR_TRY(fn(i, j - i));
+        i = j;
+    }
+    return SSDR_OK;
+}
+// a channel list made on the host to the device: behind an audio stage in flight (it reads the list), there when the call returns
+static int upload_list(ssdr_ctx *c, uint32_t *d_dst, const uint32_t *h_src, size_t n)
+{
+    if (!n) return SSDR_OK;
+    SSDR_TRY(join_audio(c));
+    HIP_TRY(hipMemcpyAsync(d_dst, h_src, n * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return SSDR_OK;
+}
 
 extern "C" {
 
@@ -318,13 +420,7 @@ void ssdr_destroy(ssdr_ctx *c)
     (void)hipSetDevice(c->device);
     (void)ssdr_feed_close(c);
     if (c->own_stream) (void)hipStreamSynchronize(c->own_stream);
-    void *ptrs[] = {c->d_win, c->d_thr, c->d_tw, c->d_lut, c->d_consts, c->d_taps, c->d_state, c->d_hist, c->d_chan_list, c->d_ws_list, c->d_wf_tail, c->d_wf_acc[0], c->d_wf_acc[1],
-                    c->d_iq_own, c->d_wf_out, c->d_pcm, c->d_rssi, c->d_flags, c->d_scratch, c->d_db2col, c->d_color, c->d_play,
-                    c->d_play_taps, c->d_play_hist, c->d_play_hist_alt, c->d_play_rs_taps, c->d_play_out, c->d_wfdata, c->d_wfpend, c->d_trace, c->d_trace_y, c->d_smeter,
-                    c->d_smeter_in, c->d_post_sel, c->d_wire, c->d_wire_rssi, c->d_play_mono, c->d_line1, c->d_dbchan1, c->d_color1, c->d_tw64, c->d_wire_gps, c->d_iq_out, c->d_zoom_taps, c->d_zoom_dphi, c->d_zoom_phase, c->d_zoom_hist, c->d_zoom_out,
-                    c->d_nb, c->d_nb_mask, c->d_comp_list, c->d_adpcm_state, c->d_snd_adpcm, c->d_wf_adpcm, c->d_sq, c->d_sq_list, c->d_sq_closed, c->d_de_state, c->d_de_list};
-    for (void *p : ptrs)
-        if (p) (void)hipFree(p);
+    free_owned(c);
     if (c->ev0) (void)hipEventDestroy(c->ev0);
     if (c->ev1) (void)hipEventDestroy(c->ev1);
     for (auto &p : c->pending) { (void)hipEventDestroy(p.e0); (void)hipEventDestroy(p.e1); }
@@ -398,8 +494,6 @@ int ssdr_table(int which, float *out, uint32_t n) SSDR_GUARD
 } SSDR_UNGUARD
 
 static int zoom_restart(ssdr_ctx *c, uint32_t first, uint32_t count, bool restart_group = true);
-static int join_audio(ssdr_ctx *c);
-static int drain_audio(ssdr_ctx *c);
 static int nb_upload(ssdr_ctx *c, uint32_t first, uint32_t count);
 static int squelch_upload(ssdr_ctx *c, uint32_t first, uint32_t count);
 static int deemp_reset(ssdr_ctx *c, uint32_t first, uint32_t count);
@@ -409,7 +503,7 @@ int ssdr_reset_state(ssdr_ctx *c, uint32_t first, uint32_t count) SSDR_GUARD
     if (!c || (uint64_t)first + count > c->n_ch) return SSDR_EINVAL;
     if (!count) return SSDR_OK;
     HIP_TRY(hipSetDevice(c->device));
-    { int rcj = join_audio(c); if (rcj != SSDR_OK) return rcj; }
+    SSDR_TRY(join_audio(c));
     std::vector<ssdr_chan_consts> k(count);
     HIP_TRY(hipMemcpyAsync(k.data(), c->d_consts + first, count * sizeof(ssdr_chan_consts), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
@@ -427,9 +521,9 @@ int ssdr_reset_state(ssdr_ctx *c, uint32_t first, uint32_t count) SSDR_GUARD
         HIP_TRY(hipMemsetAsync(c->d_wf_tail + (size_t)first * (SSDR_NFFT / 2), 0, (size_t)count * (SSDR_NFFT / 2) * 4, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
     if (first == 0 && count == c->n_ch) { c->wf_phase = 0; c->synth_sample0 = 0; c->audio_started = false; }
-    { int rcn = nb_upload(c, first, count); if (rcn != SSDR_OK) return rcn; }      // the blanker starts over (its gate at the current rate)
-    { int rcq = squelch_upload(c, first, count); if (rcq != SSDR_OK) return rcq; } // and the squelch
-    { int rce = deemp_reset(c, first, count); if (rce != SSDR_OK) return rce; }    // and the de-emphasis
+    SSDR_TRY(nb_upload(c, first, count));      // the blanker starts over (its gate at the current rate)
+    SSDR_TRY(squelch_upload(c, first, count)); // and the squelch
+    SSDR_TRY(deemp_reset(c, first, count));    // and the de-emphasis
     return zoom_restart(c, first, count, false);         // the zoomed streams of these channels start over as well
 } SSDR_UNGUARD
 
@@ -440,10 +534,8 @@ int ssdr_set_params(ssdr_ctx *c, uint32_t first, uint32_t count, const ssdr_chan
     HIP_TRY(hipSetDevice(c->device));
     std::vector<ssdr_chan_consts> k(count);
     std::vector<float> taps((size_t)count * SSDR_NTAP_MAX);
-    for (uint32_t i = 0; i < count; i++) {
-        const int rc = ssdr_compile_params_host(p + i, &k[i], taps.data() + (size_t)i * SSDR_NTAP_MAX, c->decim, c->kiwi_rate);
-        if (rc != SSDR_OK) return rc;
-    }
+    for (uint32_t i = 0; i < count; i++)
+        SSDR_TRY(ssdr_compile_params_host(p + i, &k[i], taps.data() + (size_t)i * SSDR_NTAP_MAX, c->decim, c->kiwi_rate));
     std::vector<uint32_t> sq_reset;                         // channels with a squelch setting whose mode changes: another setting acts
     if (c->sq_set_n)
         for (uint32_t i = 0; i < count; i++) {
@@ -460,20 +552,11 @@ int ssdr_set_params(ssdr_ctx *c, uint32_t first, uint32_t count, const ssdr_chan
     for (uint32_t i = 0; i < count; i++) c->h_consts[first + i] = k[i];
     c->chan_list_dirty = true;
     c->summary_dirty = true;
-    { int rcj = join_audio(c); if (rcj != SSDR_OK) return rcj; }
-    for (size_t i = 0; i < sq_reset.size();) {              // their squelch state only, a run of consecutive channels at a time
-        size_t j = i + 1;
-        while (j < sq_reset.size() && sq_reset[j] == sq_reset[j - 1] + 1) j++;
-        { int rcq = squelch_upload(c, sq_reset[i], (uint32_t)(j - i)); if (rcq != SSDR_OK) return rcq; }
-        i = j;
-    }
+    SSDR_TRY(join_audio(c));
+    // their squelch state only, a run of consecutive channels at a time
+    SSDR_TRY(for_each_run(sq_reset.data(), sq_reset.size(), [&](size_t i, size_t n) { return squelch_upload(c, sq_reset[i], (uint32_t)n); }));
     if (!sq_reset.empty()) { c->sq_dirty = true; c->sq_valid = false; }
-    for (size_t i = 0; i < de_reset.size();) {
-        size_t j = i + 1;
-        while (j < de_reset.size() && de_reset[j] == de_reset[j - 1] + 1) j++;
-        { int rce = deemp_reset(c, de_reset[i], (uint32_t)(j - i)); if (rce != SSDR_OK) return rce; }
-        i = j;
-    }
+    SSDR_TRY(for_each_run(de_reset.data(), de_reset.size(), [&](size_t i, size_t n) { return deemp_reset(c, de_reset[i], (uint32_t)n); }));
     if (!de_reset.empty()) c->de_dirty = true;
     HIP_TRY(hipMemcpyAsync(c->d_consts + first, k.data(), count * sizeof(ssdr_chan_consts), hipMemcpyHostToDevice, c->stream));
     HIP_TRY(hipMemcpyAsync(c->d_taps + (size_t)first * SSDR_NTAP_MAX, taps.data(), taps.size() * sizeof(float),
@@ -781,8 +864,7 @@ int ssdr_kernel_stats(ssdr_ctx *c, int which, float *total_ms, uint32_t *launche
 {
     if (!c || which < 0 || which >= SSDR_K_COUNT) return SSDR_EINVAL;
     HIP_TRY(hipSetDevice(c->device));
-    int rc = resolve_pending(c);
-    if (rc != SSDR_OK) return rc;
+    SSDR_TRY(resolve_pending(c));
     if (total_ms) *total_ms = c->k_ms[which];
     if (launches) *launches = c->k_n[which];
     if (reset) { c->k_ms[which] = 0.0f; c->k_n[which] = 0; }
@@ -794,8 +876,7 @@ int ssdr_elapsed_ms(ssdr_ctx *c, float *ms) SSDR_GUARD
     if (!c || !ms) return SSDR_EINVAL;
     HIP_TRY(hipSetDevice(c->device));
     if (c->profiling) {
-        int rc = resolve_pending(c);
-        if (rc != SSDR_OK) return rc;
+        SSDR_TRY(resolve_pending(c));
         *ms = c->last_ms;
         return SSDR_OK;
     }
@@ -812,20 +893,6 @@ int ssdr_sync(ssdr_ctx *c) SSDR_GUARD
     if (c->concurrent || c->audio_pending) HIP_TRY(hipStreamSynchronize(c->stream2));
     return SSDR_OK;
 } SSDR_UNGUARD
-
-// An audio stage that ran beside the waterfall kernel (stream2) and has not been joined yet: everything that follows on the
-// main stream and touches what it reads or writes (input, constants, state, PCM, RSSI, flags) waits for it first.
-static int join_audio(ssdr_ctx *c)
-{
-    if (c->audio_pending) { HIP_TRY(hipStreamWaitEvent(c->stream, c->ev_a, 0)); c->audio_pending = false; }
-    return SSDR_OK;
-}
-// ... and before a buffer it uses is freed on the host side
-static int drain_audio(ssdr_ctx *c)
-{
-    if (c->audio_pending) { HIP_TRY(hipStreamSynchronize(c->stream2)); c->audio_pending = false; }
-    return SSDR_OK;
-}
 
 // what the per-call decisions need to know about the channels' constants, counted once per change of them
 static void chan_summary(ssdr_ctx *c)
@@ -896,26 +963,37 @@ static inline size_t in_len(const ssdr_ctx *c, uint32_t n_frames) { return (size
 
 static int ensure_input(ssdr_ctx *c, uint32_t n_frames)
 {
-    { int rcj = join_audio(c); if (rcj != SSDR_OK) return rcj; }
-    const size_t need = (size_t)n_frames * c->decim;             // capacity is kept in 512-sample units
-    if (c->iq_own_frames < need) {
-        if (c->d_iq_own) { HIP_TRY(hipStreamSynchronize(c->stream)); HIP_TRY(hipFree(c->d_iq_own)); c->d_iq_own = nullptr; c->iq_own_frames = 0; }
-        HIP_TRY(hipMalloc(&c->d_iq_own, (size_t)c->n_ch * need * SSDR_FRAME * 4));
-        c->iq_own_frames = need;
-    }
+    SSDR_TRY(join_audio(c));
+    // (capacity is kept in 512-sample units)
+    return grow(c, c->d_iq_own, c->iq_own_frames, (size_t)n_frames * c->decim, (size_t)c->n_ch * SSDR_FRAME * 4);
+}
+// room for the results of an audio run of n_frames frames: PCM and RSSI under one capacity (the caller drains the audio first)
+static int ensure_audio_out(ssdr_ctx *c, uint32_t n_frames)
+{
+    if (c->audio_frames >= n_frames) return SSDR_OK;
+    SSDR_TRY(release(c, c->d_pcm));
+    SSDR_TRY(release(c, c->d_rssi));
+    c->audio_frames = 0;
+    HIP_TRY(hipMalloc(&c->d_pcm, (size_t)c->n_ch * n_frames * SSDR_FRAME * 2));
+    HIP_TRY(hipMalloc(&c->d_rssi, (size_t)c->n_ch * n_frames * sizeof(float)));
+    c->audio_frames = n_frames;
     return SSDR_OK;
+}
+// ... and for `lines` output lines of the waterfall stage
+static int ensure_wf_out(ssdr_ctx *c, uint32_t lines)
+{
+    return grow(c, c->d_wf_out, c->wf_out_lines, lines, (size_t)c->n_ch * SSDR_NFFT * 2);
 }
 
 int ssdr_push_iq(ssdr_ctx *c, const int16_t *iq, uint32_t n_frames, int is_device) SSDR_GUARD
 {
     if (!c || !iq || n_frames == 0) return SSDR_EINVAL;
     HIP_TRY(hipSetDevice(c->device));
-    { int rcj = join_audio(c); if (rcj != SSDR_OK) return rcj; }
+    SSDR_TRY(join_audio(c));
     if (is_device) {
         c->d_iq = reinterpret_cast<const uint32_t *>(iq);
     } else {
-        int rc = ensure_input(c, n_frames);
-        if (rc != SSDR_OK) return rc;
+        SSDR_TRY(ensure_input(c, n_frames));
         HIP_TRY(hipMemcpyAsync(c->d_iq_own, iq, (size_t)c->n_ch * in_len(c, n_frames) * 4, hipMemcpyHostToDevice, c->stream));
         c->d_iq = c->d_iq_own;
     }
@@ -928,8 +1006,7 @@ int ssdr_synth_iq(ssdr_ctx *c, uint32_t n_frames, uint32_t seed, uint32_t first_
 {
     if (!c || n_frames == 0) return SSDR_EINVAL;
     HIP_TRY(hipSetDevice(c->device));
-    int rc = ensure_input(c, n_frames);
-    if (rc != SSDR_OK) return rc;
+    SSDR_TRY(ensure_input(c, n_frames));
     SsdrSynthArgs a;
     a.iq = c->d_iq_own;
     a.ch_stride = (uint64_t)in_len(c, n_frames);
@@ -938,9 +1015,9 @@ int ssdr_synth_iq(ssdr_ctx *c, uint32_t n_frames, uint32_t seed, uint32_t first_
     a.seed = seed;
     a.first_channel_id = first_channel_id;
     a.sample0 = c->synth_sample0;
-    if ((rc = timed_begin(c)) != SSDR_OK) return rc;
+    SSDR_TRY(timed_begin(c));
     HIP_TRY(ssdr_launch_synth(a, c->stream));
-    if ((rc = timed_end(c, SSDR_K_SYNTH)) != SSDR_OK) return rc;
+    SSDR_TRY(timed_end(c, SSDR_K_SYNTH));
     c->synth_sample0 += a.n_samples;
     c->d_iq = c->d_iq_own;
     c->in_frames = n_frames;
@@ -978,14 +1055,9 @@ static int adpcm_snd_alloc(ssdr_ctx *c)
 {
     const size_t need = (size_t)c->comp_snd_n * c->in_frames * (SSDR_FRAME / 2);
     if (c->snd_adpcm_bytes >= need) return SSDR_OK;
-    { int rcd = drain_audio(c); if (rcd != SSDR_OK) return rcd; }
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    if (c->d_snd_adpcm) { HIP_TRY(hipFree(c->d_snd_adpcm)); c->d_snd_adpcm = nullptr; }
-    c->snd_adpcm_bytes = 0;
+    SSDR_TRY(drain_audio(c));
     c->snd_adpcm_valid = false;
-    HIP_TRY(hipMalloc(&c->d_snd_adpcm, need));
-    c->snd_adpcm_bytes = need;
-    return SSDR_OK;
+    return grow(c, c->d_snd_adpcm, c->snd_adpcm_bytes, need, 1);
 }
 // the SND payloads of the audio stage just queued on `s` (its PCM), behind it on the same stream: the state advances once per batch
 static int adpcm_snd_launch(ssdr_ctx *c, hipStream_t s)
@@ -1003,10 +1075,7 @@ static int adpcm_snd_launch(ssdr_ctx *c, hipStream_t s)
     e.state = c->d_adpcm_state;
     e.out = c->d_snd_adpcm;
     e.out_stride = (uint64_t)c->in_frames * (SSDR_FRAME / 2);
-    int rc;
-    if (c->profiling && (rc = timed_begin(c, s)) != SSDR_OK) return rc;       // (untimed otherwise: ssdr_elapsed_ms stays the stage's)
-    HIP_TRY(ssdr_launch_adpcm_enc(e, s));
-    if (c->profiling && (rc = timed_end(c, SSDR_K_ADPCM, s)) != SSDR_OK) return rc;
+    SSDR_TRY(timed_launch(c, SSDR_K_ADPCM, s, [&]() -> int { HIP_TRY(ssdr_launch_adpcm_enc(e, s)); return SSDR_OK; }));
     c->snd_adpcm_valid = true;
     c->snd_adpcm_frames = c->in_frames;
     return SSDR_OK;
@@ -1016,13 +1085,8 @@ static int adpcm_wf_alloc(ssdr_ctx *c, uint32_t lines)
 {
     const size_t need = (size_t)c->comp_wf_n * lines * SSDR_ADPCM_WF_BYTES;
     if (c->wf_adpcm_bytes >= need) return SSDR_OK;
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    if (c->d_wf_adpcm) { HIP_TRY(hipFree(c->d_wf_adpcm)); c->d_wf_adpcm = nullptr; }
-    c->wf_adpcm_bytes = 0;
     c->wf_adpcm_valid = false;
-    HIP_TRY(hipMalloc(&c->d_wf_adpcm, need));
-    c->wf_adpcm_bytes = need;
-    return SSDR_OK;
+    return grow(c, c->d_wf_adpcm, c->wf_adpcm_bytes, need, 1);
 }
 // the W/F payloads of the lines the waterfall stage just queued on `s`: only byte lines (N = 1) go on the wire
 static int adpcm_wf_launch(ssdr_ctx *c, hipStream_t s, uint32_t n_avg)
@@ -1042,10 +1106,7 @@ static int adpcm_wf_launch(ssdr_ctx *c, hipStream_t s, uint32_t n_avg)
         e.state = nullptr;
         e.out = c->d_wf_adpcm;
         e.out_stride = SSDR_ADPCM_WF_BYTES;
-        int rc;
-        if (c->profiling && (rc = timed_begin(c, s)) != SSDR_OK) return rc;
-        HIP_TRY(ssdr_launch_adpcm_enc_wf(e, s));
-        if (c->profiling && (rc = timed_end(c, SSDR_K_ADPCM, s)) != SSDR_OK) return rc;
+        SSDR_TRY(timed_launch(c, SSDR_K_ADPCM, s, [&]() -> int { HIP_TRY(ssdr_launch_adpcm_enc_wf(e, s)); return SSDR_OK; }));
     }
     c->wf_adpcm_valid = true;
     c->wf_adpcm_lines = lines;
@@ -1069,7 +1130,7 @@ static int squelch_upload(ssdr_ctx *c, uint32_t first, uint32_t count)
         q[i].fm_level = p.fm_level; q[i].fm_max = p.fm_max; q[i].rssi_level = p.rssi_level; q[i].tail_frames = p.tail_frames;
         q[i].open = 1u;
     }
-    { int rcj = join_audio(c); if (rcj != SSDR_OK) return rcj; }
+    SSDR_TRY(join_audio(c));
     HIP_TRY(hipMemcpyAsync(c->d_sq + first, q.data(), count * sizeof(SsdrSquelchChan), hipMemcpyHostToDevice, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
     return SSDR_OK;
@@ -1084,11 +1145,7 @@ static int squelch_refresh(ssdr_ctx *c)
         for (uint32_t ch = 0; ch < c->n_ch; ch++)
             if (squelch_acts(c->h_sq[ch], c->h_consts[ch].mode)) c->h_sq_list[n++] = ch;
     }
-    if (n) {
-        { int rcj = join_audio(c); if (rcj != SSDR_OK) return rcj; }     // a kernel in flight reads the list
-        HIP_TRY(hipMemcpyAsync(c->d_sq_list, c->h_sq_list.data(), (size_t)n * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
-        HIP_TRY(hipStreamSynchronize(c->stream));
-    }
+    SSDR_TRY(upload_list(c, c->d_sq_list, c->h_sq_list.data(), n));
     c->sq_n = n;
     c->sq_dirty = false;
     c->sq_valid = false;
@@ -1098,17 +1155,12 @@ static int squelch_refresh(ssdr_ctx *c)
 static int squelch_prepare(ssdr_ctx *c)
 {
     if (!c->sq_set_n && !c->sq_dirty) return SSDR_OK;
-    { int rcr = squelch_refresh(c); if (rcr != SSDR_OK) return rcr; }
+    SSDR_TRY(squelch_refresh(c));
     const size_t need = (size_t)c->sq_n * c->in_frames;
     if (c->sq_closed_bytes >= need) return SSDR_OK;
-    { int rcd = drain_audio(c); if (rcd != SSDR_OK) return rcd; }
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    if (c->d_sq_closed) { HIP_TRY(hipFree(c->d_sq_closed)); c->d_sq_closed = nullptr; }
-    c->sq_closed_bytes = 0;
+    SSDR_TRY(drain_audio(c));
     c->sq_valid = false;
-    HIP_TRY(hipMalloc(&c->d_sq_closed, need));
-    c->sq_closed_bytes = need;
-    return SSDR_OK;
+    return grow(c, c->d_sq_closed, c->sq_closed_bytes, need, 1);
 }
 // squelch the PCM of the audio stage just queued on `s`, behind it on the same stream: the state advances once per batch
 static int squelch_launch(ssdr_ctx *c, hipStream_t s)
@@ -1123,10 +1175,7 @@ static int squelch_launch(ssdr_ctx *c, hipStream_t s)
     q.consts = c->d_consts;
     q.chan = c->d_sq;
     q.closed = c->d_sq_closed;
-    int rc;
-    if (c->profiling && (rc = timed_begin(c, s)) != SSDR_OK) return rc;       // (untimed otherwise: ssdr_elapsed_ms stays the stage's)
-    HIP_TRY(ssdr_launch_squelch(q, s));
-    if (c->profiling && (rc = timed_end(c, SSDR_K_SQUELCH, s)) != SSDR_OK) return rc;
+    SSDR_TRY(timed_launch(c, SSDR_K_SQUELCH, s, [&]() -> int { HIP_TRY(ssdr_launch_squelch(q, s)); return SSDR_OK; }));
     c->sq_valid = true;
     c->sq_frames = c->in_frames;
     return SSDR_OK;
@@ -1147,7 +1196,7 @@ static inline uint32_t deemp_acting(const ssdr_deemp_params &q, uint32_t mode)
 static int deemp_reset(ssdr_ctx *c, uint32_t first, uint32_t count)
 {
     if (!c->d_de_state || !count) return SSDR_OK;
-    { int rcj = join_audio(c); if (rcj != SSDR_OK) return rcj; }
+    SSDR_TRY(join_audio(c));
     HIP_TRY(hipMemsetAsync(c->d_de_state + first, 0, (size_t)count * sizeof(int32_t), c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
     return SSDR_OK;
@@ -1167,12 +1216,8 @@ static int deemp_prepare(ssdr_ctx *c)
             n++;
         }
     }
-    if (n) {
-        { int rcj = join_audio(c); if (rcj != SSDR_OK) return rcj; }     // a kernel in flight reads the list
-        HIP_TRY(hipMemcpyAsync(c->d_de_list, c->h_de_list.data(), (size_t)n * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
-        HIP_TRY(hipMemcpyAsync(c->d_de_list + c->n_ch, c->h_de_list.data() + c->n_ch, (size_t)n * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
-        HIP_TRY(hipStreamSynchronize(c->stream));
-    }
+    SSDR_TRY(upload_list(c, c->d_de_list, c->h_de_list.data(), n));
+    SSDR_TRY(upload_list(c, c->d_de_list + c->n_ch, c->h_de_list.data() + c->n_ch, n));
     c->de_n = n;
     c->de_dirty = false;
     return SSDR_OK;
@@ -1188,12 +1233,27 @@ static int deemp_launch(ssdr_ctx *c, hipStream_t s)
     q.coef = c->d_de_list + c->n_ch;
     q.list_n = c->de_n;
     q.state = c->d_de_state;
-    int rc;
-    if (c->profiling && (rc = timed_begin(c, s)) != SSDR_OK) return rc;       // (untimed otherwise: ssdr_elapsed_ms stays the stage's)
-    HIP_TRY(ssdr_launch_deemp(q, s));
-    if (c->profiling && (rc = timed_end(c, kTimedDeemp, s)) != SSDR_OK) return rc;
+    SSDR_TRY(timed_launch(c, kTimedDeemp, s, [&]() -> int { HIP_TRY(ssdr_launch_deemp(q, s)); return SSDR_OK; }));
     c->de_launches++;
     return SSDR_OK;
+}
+
+// ---- the tail of the audio stage: squelch, de-emphasis, SND encoder -- one order, whichever kernel did the stage's work ---------
+// lists and room, before anything of the run is launched
+static int audio_tail_prepare(ssdr_ctx *c)
+{
+    SSDR_TRY(adpcm_snd_alloc(c));
+    c->snd_adpcm_valid = false;
+    SSDR_TRY(squelch_prepare(c));
+    c->sq_valid = false;
+    return deemp_prepare(c);
+}
+// behind the kernel that wrote the PCM, on its stream `s`
+static int audio_tail_launch(ssdr_ctx *c, hipStream_t s)
+{
+    SSDR_TRY(squelch_launch(c, s));
+    SSDR_TRY(deemp_launch(c, s));
+    return adpcm_snd_launch(c, s);
 }
 
 int ssdr_run_wf(ssdr_ctx *c, int16_t *wf_sum_out, uint32_t *lines_ready, int out_is_device) SSDR_GUARD
@@ -1202,25 +1262,20 @@ int ssdr_run_wf(ssdr_ctx *c, int16_t *wf_sum_out, uint32_t *lines_ready, int out
     if (!c->have_input) return SSDR_ESTATE;
     const bool hop512 = c->hop == SSDR_NFFT / 2;
     const bool zoomed = c->zoom > 1;
-    { const int rcv = validate_wf_batch(c); if (rcv != SSDR_OK) return rcv; }
+    SSDR_TRY(validate_wf_batch(c));
     const uint32_t halves = c->in_frames * c->decim / c->zoom;
     HIP_TRY(hipSetDevice(c->device));
     const uint32_t *wf_src = c->d_iq;                                // what the waterfall kernel reads: the input, or the zoomed stream
     uint64_t wf_stride = (uint64_t)in_len(c, c->in_frames);
     if (zoomed) {
         const uint32_t n_in = (uint32_t)in_len(c, c->in_frames), n_out = n_in / c->zoom;
-        if (c->zoom_out_samples < n_out) {
-            if (c->d_zoom_out) { HIP_TRY(hipStreamSynchronize(c->stream)); HIP_TRY(hipFree(c->d_zoom_out)); c->d_zoom_out = nullptr; c->zoom_out_samples = 0; }
-            HIP_TRY(hipMalloc(&c->d_zoom_out, (size_t)c->n_ch * n_out * 4));
-            c->zoom_out_samples = n_out;
-        }
+        SSDR_TRY(grow(c, c->d_zoom_out, c->zoom_out_samples, n_out, (size_t)c->n_ch * 4));
         SsdrZoomArgs z;
         z.iq = c->d_iq; z.ch_stride = wf_stride; z.n_ch = c->n_ch; z.n_in = n_in; z.zoom = c->zoom; z.ntap = c->zoom_ntap;
         z.taps = c->d_zoom_taps; z.dphi = c->d_zoom_dphi; z.phase = c->d_zoom_phase; z.hist = c->d_zoom_hist; z.out = c->d_zoom_out;
-        int rcz;
-        if ((rcz = timed_begin(c)) != SSDR_OK) return rcz;
+        SSDR_TRY(timed_begin(c));
         HIP_TRY(ssdr_launch_zoom(z, c->stream));
-        if ((rcz = timed_end(c, SSDR_K_ZOOM)) != SSDR_OK) return rcz;
+        SSDR_TRY(timed_end(c, SSDR_K_ZOOM));
         wf_src = c->d_zoom_out;
         wf_stride = n_out;
         c->zoom_run_samples = n_out;
@@ -1229,12 +1284,8 @@ int ssdr_run_wf(ssdr_ctx *c, int16_t *wf_sum_out, uint32_t *lines_ready, int out
     const uint32_t total = c->wf_phase + n_lines;
     const uint32_t n_out = total / c->n_avg;
     const uint32_t n_groups = (total + c->n_avg - 1) / c->n_avg;
-    if (c->wf_out_lines < n_out) {
-        if (c->d_wf_out) { HIP_TRY(hipStreamSynchronize(c->stream)); HIP_TRY(hipFree(c->d_wf_out)); c->d_wf_out = nullptr; c->wf_out_lines = 0; }
-        HIP_TRY(hipMalloc(&c->d_wf_out, (size_t)n_out * c->n_ch * SSDR_NFFT * 2));
-        c->wf_out_lines = n_out;
-    }
-    if (c->comp_wf_n && c->n_avg == 1) { int rca = adpcm_wf_alloc(c, n_out); if (rca != SSDR_OK) return rca; }
+    SSDR_TRY(ensure_wf_out(c, n_out));
+    if (c->comp_wf_n && c->n_avg == 1) SSDR_TRY(adpcm_wf_alloc(c, n_out));
     c->wf_adpcm_valid = false;
     SsdrWfArgs a;
     a.iq = wf_src;
@@ -1266,14 +1317,13 @@ int ssdr_run_wf(ssdr_ctx *c, int16_t *wf_sum_out, uint32_t *lines_ready, int out
     }
     const uint64_t need = (items + SSDR_WF_BLOCK / 64 - 1) / (SSDR_WF_BLOCK / 64);
     const uint32_t grid = (uint32_t)(need < wf_grid ? need : wf_grid);
-    int rc;
     if (c->fuse_next) {                      // the fused superframe kernel does this stage's work: ssdr_run_audio launches it
         c->fused_wf = a;
     } else {
-        if ((rc = timed_begin(c)) != SSDR_OK) return rc;
+        SSDR_TRY(timed_begin(c));
         if (c->exact_bins) HIP_TRY(ssdr_launch_wf_exact(a, c->d_tw64, c->stream));
         else HIP_TRY(ssdr_launch_wf(a, grid ? grid : 1, c->stream));
-        if ((rc = timed_end(c, SSDR_K_WF)) != SSDR_OK) return rc;
+        SSDR_TRY(timed_end(c, SSDR_K_WF));
     }
     if (hop512 && !c->fuse_next) // the batch's last half-line is the next batch's first: [n_ch] rows of 2 KB out of the input
         HIP_TRY(hipMemcpy2DAsync(c->d_wf_tail, (SSDR_NFFT / 2) * 4, wf_src + (size_t)(halves - 1) * SSDR_FRAME,
@@ -1282,12 +1332,8 @@ int ssdr_run_wf(ssdr_ctx *c, int16_t *wf_sum_out, uint32_t *lines_ready, int out
     if (c->wf_phase) c->wf_acc_cur ^= 1;             // a partial group was written to acc_out
     c->wf_lines_ready = n_out;
     if (lines_ready) *lines_ready = n_out;
-    if (!c->fuse_next) { int rca = adpcm_wf_launch(c, c->stream, c->n_avg); if (rca != SSDR_OK) return rca; }   // (fused: ssdr_run_audio)
-    if (wf_sum_out && n_out) {
-        const size_t bytes = (size_t)n_out * c->n_ch * SSDR_NFFT * 2;
-        HIP_TRY(hipMemcpyAsync(wf_sum_out, c->d_wf_out, bytes, out_is_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, c->stream));
-        if (!out_is_device) HIP_TRY(hipStreamSynchronize(c->stream));
-    }
+    if (!c->fuse_next) SSDR_TRY(adpcm_wf_launch(c, c->stream, c->n_avg));   // (fused: ssdr_run_audio)
+    if (wf_sum_out && n_out) SSDR_TRY(copy_out(c, wf_sum_out, c->d_wf_out, (size_t)n_out * c->n_ch * SSDR_NFFT * 2, out_is_device, kSyncHost));
     return SSDR_OK;
 } SSDR_UNGUARD
 
@@ -1296,39 +1342,17 @@ int ssdr_run_audio(ssdr_ctx *c, int16_t *pcm_out, float *rssi_out, int out_is_de
     if (!c) return SSDR_EINVAL;
     if (!c->have_input) return SSDR_ESTATE;
     HIP_TRY(hipSetDevice(c->device));
-    if (!c->concurrent) { int rcj = join_audio(c); if (rcj != SSDR_OK) return rcj; }      // the previous frame's state before this one
-    if (c->audio_frames < c->in_frames || c->flags_frames < c->in_frames) { int rcd = drain_audio(c); if (rcd != SSDR_OK) return rcd; }
-    if (c->audio_frames < c->in_frames) {
-        HIP_TRY(hipStreamSynchronize(c->stream));
-        if (c->d_pcm) { HIP_TRY(hipFree(c->d_pcm)); c->d_pcm = nullptr; }
-        if (c->d_rssi) { HIP_TRY(hipFree(c->d_rssi)); c->d_rssi = nullptr; }
-        c->audio_frames = 0;
-        HIP_TRY(hipMalloc(&c->d_pcm, (size_t)c->n_ch * c->in_frames * SSDR_FRAME * 2));
-        HIP_TRY(hipMalloc(&c->d_rssi, (size_t)c->n_ch * c->in_frames * sizeof(float)));
-        c->audio_frames = c->in_frames;
-    }
-    if (c->flags_frames < c->in_frames) {
-        HIP_TRY(hipStreamSynchronize(c->stream));
-        if (c->d_flags) { HIP_TRY(hipFree(c->d_flags)); c->d_flags = nullptr; }
-        c->flags_frames = 0;
-        HIP_TRY(hipMalloc(&c->d_flags, (size_t)c->n_ch * c->in_frames));
-        c->flags_frames = c->in_frames;
-    }
+    if (!c->concurrent) SSDR_TRY(join_audio(c));      // the previous frame's state before this one
+    if (c->audio_frames < c->in_frames || c->flags_frames < c->in_frames) SSDR_TRY(drain_audio(c));
+    SSDR_TRY(ensure_audio_out(c, c->in_frames));
+    SSDR_TRY(grow(c, c->d_flags, c->flags_frames, c->in_frames, c->n_ch));
     const size_t nb_mask_need = c->nb_on ? (size_t)c->n_ch * c->in_frames * 64 * c->decim : 0;     // one bit per input sample
     if (c->nb_mask_bytes < nb_mask_need) {
-        { int rcd = drain_audio(c); if (rcd != SSDR_OK) return rcd; }
-        HIP_TRY(hipStreamSynchronize(c->stream));
-        if (c->d_nb_mask) { HIP_TRY(hipFree(c->d_nb_mask)); c->d_nb_mask = nullptr; }
-        c->nb_mask_bytes = 0;
+        SSDR_TRY(drain_audio(c));
         c->nb_mask_valid = false;
-        HIP_TRY(hipMalloc(&c->d_nb_mask, nb_mask_need));
-        c->nb_mask_bytes = nb_mask_need;
+        SSDR_TRY(grow(c, c->d_nb_mask, c->nb_mask_bytes, nb_mask_need, 1));
     }
-    { int rca = adpcm_snd_alloc(c); if (rca != SSDR_OK) return rca; }
-    c->snd_adpcm_valid = false;
-    { int rcq = squelch_prepare(c); if (rcq != SSDR_OK) return rcq; }
-    c->sq_valid = false;
-    { int rce = deemp_prepare(c); if (rce != SSDR_OK) return rce; }
+    SSDR_TRY(audio_tail_prepare(c));
     SsdrAudioArgs a;
     a.iq = c->d_iq;
     a.ch_stride = (uint64_t)in_len(c, c->in_frames);
@@ -1348,19 +1372,14 @@ int ssdr_run_audio(ssdr_ctx *c, int16_t *pcm_out, float *rssi_out, int out_is_de
         const bool any_iq = c->sum_any_iq;
         if (any_iq && c->feed.empty()) {          // (the pipelined feed hands out PCM rows only: an IQ channel's row carries I)
             if (c->iq_out_frames < c->in_frames) {
-                { int rcd = drain_audio(c); if (rcd != SSDR_OK) return rcd; }
-                HIP_TRY(hipStreamSynchronize(c->stream));
-                if (c->d_iq_out) { HIP_TRY(hipFree(c->d_iq_out)); c->d_iq_out = nullptr; }
-                c->iq_out_frames = 0;
-                HIP_TRY(hipMalloc(&c->d_iq_out, (size_t)c->n_ch * c->in_frames * SSDR_FRAME * 4));
-                c->iq_out_frames = c->in_frames;
+                SSDR_TRY(drain_audio(c));
+                SSDR_TRY(grow(c, c->d_iq_out, c->iq_out_frames, c->in_frames, (size_t)c->n_ch * SSDR_FRAME * 4));
             }
             HIP_TRY(hipMemsetAsync(c->d_iq_out, 0, (size_t)c->n_ch * c->in_frames * SSDR_FRAME * 4, c->stream));   // rows of the other modes
             a.iq_out = c->d_iq_out;
             c->iq_out_valid = true;
         }
     }
-    int rc;
     hipStream_t s = c->stream;
     if (c->concurrent) {
         // the audio kernel only depends on the input batch (and on its own previous launch): run it beside the
@@ -1369,7 +1388,7 @@ int ssdr_run_audio(ssdr_ctx *c, int16_t *pcm_out, float *rssi_out, int out_is_de
         HIP_TRY(hipEventRecord(c->ev_in, c->stream));          // everything queued so far, incl. the input copy/synth
         HIP_TRY(hipStreamWaitEvent(s, c->ev_in, 0));
     }
-    { int rcl = ensure_chan_list(c, s); if (rcl != SSDR_OK) return rcl; }
+    SSDR_TRY(ensure_chan_list(c, s));
     c->audio_started = true;
     c->audio_run_frames = c->in_frames;
     c->nb_mask_valid = false;
@@ -1384,7 +1403,7 @@ int ssdr_run_audio(ssdr_ctx *c, int16_t *pcm_out, float *rssi_out, int out_is_de
         const uint64_t pairs = (c->n_ch + 1) / 2;
         const uint64_t need = (pairs + SSDR_WF_BLOCK / 64 - 1) / (SSDR_WF_BLOCK / 64);
         const uint32_t grid = (uint32_t)(need < c->fused_grid ? need : c->fused_grid);
-        if ((rc = timed_begin(c, s)) != SSDR_OK) return rc;
+        SSDR_TRY(timed_begin(c, s));
         if (c->fuse_ws_next) {
             const uint64_t need_g = ((uint64_t)c->n_ch + SSDR_WS_AUDIO_WAVES - 1) / SSDR_WS_AUDIO_WAVES;
             const uint32_t grid_g = (uint32_t)(need_g < c->ws_grid ? need_g : c->ws_grid);
@@ -1392,21 +1411,18 @@ int ssdr_run_audio(ssdr_ctx *c, int16_t *pcm_out, float *rssi_out, int out_is_de
             c->ws_ticket += (uint32_t)pairs + (grid_g ? grid_g : 1) * (SSDR_WS_AUDIO_WAVES / 2);     // (wraps as the device word does)
         } else if (c->exact_bins) HIP_TRY(ssdr_launch_fused_exact_am(fa, c->d_tw64, s));
         else HIP_TRY(ssdr_launch_fused_am(fa, grid ? grid : 1, s));
-        if ((rc = timed_end(c, SSDR_K_FUSED, s)) != SSDR_OK) return rc;
+        SSDR_TRY(timed_end(c, SSDR_K_FUSED, s));
         if (fa.wf.tail)          // hop 512: only now may the carried half-line (the kernel's line 0 read it) become this batch's last one
             HIP_TRY(hipMemcpy2DAsync(c->d_wf_tail, (SSDR_NFFT / 2) * 4, fa.wf.iq + (size_t)(fa.wf.n_lines - 1) * SSDR_FRAME,
                                      fa.wf.ch_stride * 4, (SSDR_NFFT / 2) * 4, c->n_ch, hipMemcpyDeviceToDevice, s));
-        if ((rc = squelch_launch(c, s)) != SSDR_OK) return rc;            // squelch, de-emphasis, then the encoders, behind the one-read kernel
-        if ((rc = deemp_launch(c, s)) != SSDR_OK) return rc;
-        if ((rc = adpcm_snd_launch(c, s)) != SSDR_OK) return rc;
-        if ((rc = adpcm_wf_launch(c, s, fa.wf.n_avg)) != SSDR_OK) return rc;
-        return SSDR_OK;
+        SSDR_TRY(audio_tail_launch(c, s));         // behind the one-read kernel, and then the W/F encoder
+        return adpcm_wf_launch(c, s, fa.wf.n_avg);
     }
     // one kernel per non-empty path: the first on the stream itself, the others beside it on their own streams
     // (fork and join by events); the stage is timed between two events on `s`
     if (c->decim > 1 && (c->path_n[SSDR_PATH_DELAY4] || c->path_n[SSDR_PATH_AM_RAW] || c->nb_n[SSDR_PATH_DELAY4] || c->nb_n[SSDR_PATH_AM_RAW]))
         return SSDR_ESTATE;                   // the decimating kernel is the general path: no channel may be compiled for a shift path
-    if ((rc = timed_begin(c, s)) != SSDR_OK) return rc;
+    SSDR_TRY(timed_begin(c, s));
     if (c->decim > 1) {                       // ONE kernel over all channels (it takes no channel list)
         a.chan_list = c->d_chan_list;
         a.list_n = c->n_ch;
@@ -1447,7 +1463,7 @@ int ssdr_run_audio(ssdr_ctx *c, int16_t *pcm_out, float *rssi_out, int out_is_de
         for (int i = 0; i < n_side; i++)
             HIP_TRY(hipStreamWaitEvent(s, i < SSDR_PATH_COUNT - 1 ? c->ev_path[i] : c->ev_nb[i - (SSDR_PATH_COUNT - 1)], 0));
     }
-    if ((rc = timed_end(c, SSDR_K_AUDIO, s)) != SSDR_OK) return rc;
+    SSDR_TRY(timed_end(c, SSDR_K_AUDIO, s));
     if (c->nb_on) {
         c->nb_mask_valid = true;
         c->nb_mask_frames = c->in_frames;
@@ -1458,9 +1474,7 @@ int ssdr_run_audio(ssdr_ctx *c, int16_t *pcm_out, float *rssi_out, int out_is_de
             c->nb_mask_gen = c->nb_gen;
         }
     }
-    if ((rc = squelch_launch(c, s)) != SSDR_OK) return rc;
-    if ((rc = deemp_launch(c, s)) != SSDR_OK) return rc;
-    if ((rc = adpcm_snd_launch(c, s)) != SSDR_OK) return rc;
+    SSDR_TRY(audio_tail_launch(c, s));
     const hipMemcpyKind kind = out_is_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
     if (pcm_out) HIP_TRY(hipMemcpyAsync(pcm_out, c->d_pcm, (size_t)c->n_ch * c->in_frames * SSDR_FRAME * 2, kind, s));
     if (rssi_out) HIP_TRY(hipMemcpyAsync(rssi_out, c->d_rssi, (size_t)c->n_ch * c->in_frames * sizeof(float), kind, s));
@@ -1590,11 +1604,8 @@ int ssdr_audio_iq(ssdr_ctx *c, int16_t *iq_out, int out_is_device) SSDR_GUARD
     if (!c || !iq_out) return SSDR_EINVAL;
     if (!c->iq_out_valid || !c->d_iq_out || c->audio_run_frames == 0) return SSDR_ESTATE;
     HIP_TRY(hipSetDevice(c->device));
-    { int rcj = join_audio(c); if (rcj != SSDR_OK) return rcj; }
-    HIP_TRY(hipMemcpyAsync(iq_out, c->d_iq_out, (size_t)c->n_ch * c->audio_run_frames * SSDR_FRAME * 4,
-                           out_is_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, c->stream));
-    if (!out_is_device) HIP_TRY(hipStreamSynchronize(c->stream));
-    return SSDR_OK;
+    SSDR_TRY(join_audio(c));
+    return copy_out(c, iq_out, c->d_iq_out, (size_t)c->n_ch * c->audio_run_frames * SSDR_FRAME * 4, out_is_device, kSyncHost);
 } SSDR_UNGUARD
 
 int ssdr_audio_flags(ssdr_ctx *c, uint8_t *flags_out, int out_is_device) SSDR_GUARD
@@ -1602,11 +1613,8 @@ int ssdr_audio_flags(ssdr_ctx *c, uint8_t *flags_out, int out_is_device) SSDR_GU
     if (!c || !flags_out) return SSDR_EINVAL;
     if (!c->d_flags || c->audio_run_frames == 0 || c->flags_frames < c->audio_run_frames) return SSDR_ESTATE;
     HIP_TRY(hipSetDevice(c->device));
-    { int rcj = join_audio(c); if (rcj != SSDR_OK) return rcj; }
-    HIP_TRY(hipMemcpyAsync(flags_out, c->d_flags, (size_t)c->n_ch * c->audio_run_frames,
-                           out_is_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, c->stream));
-    if (!out_is_device) HIP_TRY(hipStreamSynchronize(c->stream));
-    return SSDR_OK;
+    SSDR_TRY(join_audio(c));
+    return copy_out(c, flags_out, c->d_flags, (size_t)c->n_ch * c->audio_run_frames, out_is_device, kSyncHost);
 } SSDR_UNGUARD
 
 // ---- impulse noise blanker ---------------------------------------------------------------------------------------------
@@ -1630,7 +1638,7 @@ static int nb_upload(ssdr_ctx *c, uint32_t first, uint32_t count)
         if (th && ssdr_nb_gate_samples(gate_us, c->decim, c->kiwi_rate, &q[i].gate) == SSDR_OK) q[i].thresh = th;
         else q[i].gate = 0;
     }
-    { int rcj = join_audio(c); if (rcj != SSDR_OK) return rcj; }
+    SSDR_TRY(join_audio(c));
     HIP_TRY(hipMemcpyAsync(c->d_nb + first, q.data(), count * sizeof(SsdrNbChan), hipMemcpyHostToDevice, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
     return SSDR_OK;
@@ -1652,7 +1660,7 @@ int ssdr_set_noise_blanker(ssdr_ctx *c, uint32_t first, uint32_t count, const ui
             if (!c->nb_stream[i]) HIP_TRY(hipStreamCreateWithFlags(&c->nb_stream[i], hipStreamNonBlocking));
             if (!c->ev_nb[i]) HIP_TRY(hipEventCreateWithFlags(&c->ev_nb[i], hipEventDisableTiming));
         }
-        { int rcj = join_audio(c); if (rcj != SSDR_OK) return rcj; }
+        SSDR_TRY(join_audio(c));
         SsdrNbChan *d = nullptr;
         HIP_TRY(hipMalloc(&d, (size_t)c->n_ch * sizeof(SsdrNbChan)));
         c->d_nb = d;
@@ -1676,10 +1684,9 @@ int ssdr_audio_nb_mask(ssdr_ctx *c, uint8_t *mask_out, int out_is_device) SSDR_G
     if (!c || !mask_out) return SSDR_EINVAL;
     if (!c->nb_on || !c->nb_mask_valid || !c->d_nb_mask) return SSDR_ESTATE;
     HIP_TRY(hipSetDevice(c->device));
-    { int rcj = join_audio(c); if (rcj != SSDR_OK) return rcj; }
+    SSDR_TRY(join_audio(c));
     const size_t row = (size_t)c->nb_mask_frames * 64 * c->nb_mask_decim;
-    const hipMemcpyKind kind = out_is_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
-    HIP_TRY(hipMemcpyAsync(mask_out, c->d_nb_mask, (size_t)c->n_ch * row, kind, c->stream));
+    SSDR_TRY(copy_out(c, mask_out, c->d_nb_mask, (size_t)c->n_ch * row, out_is_device, kSyncLater));
     // the rows of channels that did not blank hold nothing of this run: zeros, a run of such channels at a time
     for (uint32_t ch = 0; ch < c->n_ch;) {
         if (c->nb_mask_on[ch]) { ch++; continue; }
@@ -1762,7 +1769,7 @@ int ssdr_feed_open(ssdr_ctx *c, uint32_t n_frames, uint32_t depth, uint32_t flag
     if (c->comp_snd_n || c->comp_wf_n || c->sq_set_n || c->de_set_n) return SSDR_ESTATE;   // no wire compression, squelch or de-emphasis in the slot pipeline      // the feed's slots are sized for un-zoomed 12 kHz IQ
     HIP_TRY(hipSetDevice(c->device));
     const bool post = (flags & SSDR_FEED_POST) != 0;
-    if (post) { int rcp = ensure_play(c); if (rcp != SSDR_OK) return rcp; }
+    if (post) SSDR_TRY(ensure_play(c));
     struct Undo { ssdr_ctx *c; bool armed; ~Undo() { if (armed) (void)ssdr_feed_close(c); } } undo{c, true};   // an error or an exception below: no half-open feed
     c->feed_post = post;
     if (post && c->feed_dbchan.size() != c->n_ch) {          // the reference's initial display state (utils_supersdr.py:599-603, 921, 945)
@@ -1860,10 +1867,9 @@ static int feed_submit_impl(ssdr_ctx *c, const void *host_in)
         w.ch_stride = (uint64_t)nf * SSDR_FRAME;
         w.rssi = s.d_wire_rssi;
         w.gps = nullptr;
-        int rcw;
-        if ((rcw = timed_begin(c)) != SSDR_OK) return rcw;
+        SSDR_TRY(timed_begin(c));
         HIP_TRY(ssdr_launch_iqwire(w, c->stream));
-        if ((rcw = timed_end(c, SSDR_K_WIRE)) != SSDR_OK) return rcw;
+        SSDR_TRY(timed_end(c, SSDR_K_WIRE));
     }
     // run the two kernels on this slot's buffers: the ctx's own batch pointers are parked meanwhile
     const uint32_t *k_iq = c->d_iq; const uint32_t k_frames = c->in_frames; const bool k_have = c->have_input;
@@ -1889,11 +1895,10 @@ static int feed_submit_impl(ssdr_ctx *c, const void *host_in)
             SsdrDb2colArgs d;
             d.wf = s.d_wf; d.n_ch = c->n_ch; d.n_lines = lines; d.n_avg = c->n_avg; d.chans = s.d_dbchan; d.color = s.d_color;
             d.sel = c->d_post_sel; d.n_sel = c->n_post;
-            int r2;
-            if ((r2 = timed_begin(c)) != SSDR_OK) return r2;
+            SSDR_TRY(timed_begin(c));
             HIP_TRY(ssdr_launch_db2col(d, c->stream));
-            if ((r2 = timed_end(c, SSDR_K_DB2COL)) != SSDR_OK) return r2;
-            if (c->d_wfdata) { r2 = wfdata_feed(c, s.d_color, lines); if (r2 != SSDR_OK) return r2; }
+            SSDR_TRY(timed_end(c, SSDR_K_DB2COL));
+            if (c->d_wfdata) SSDR_TRY(wfdata_feed(c, s.d_color, lines));
         }
         memcpy(s.h_playchan, c->feed_playchan.data(), (size_t)c->n_post * sizeof(ssdr_play_chan));
         HIP_TRY(hipMemcpyAsync(c->d_play, s.h_playchan, (size_t)c->n_post * sizeof(ssdr_play_chan), hipMemcpyHostToDevice, c->stream));
@@ -1905,11 +1910,10 @@ static int feed_submit_impl(ssdr_ctx *c, const void *host_in)
             HIP_TRY(hipMemcpyAsync(c->d_play_hist_alt, c->d_play_hist, (size_t)c->n_ch * 8 * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
         pa.out = s.d_play; pa.rs_taps = c->d_play_rs_taps; pa.mono = c->recording ? s.d_mono : nullptr;
         s.has_mono = c->recording;
-        int r3;
-        if ((r3 = timed_begin(c)) != SSDR_OK) return r3;
+        SSDR_TRY(timed_begin(c));
         HIP_TRY(c->kiwi_rate != SSDR_RATE ? ssdr_launch_play_rs(pa, c->stream) : ssdr_launch_play(pa, c->stream));
         if (c->kiwi_rate == SSDR_RATE) std::swap(c->d_play_hist, c->d_play_hist_alt);
-        if ((r3 = timed_end(c, SSDR_K_PLAY)) != SSDR_OK) return r3;
+        SSDR_TRY(timed_end(c, SSDR_K_PLAY));
         return SSDR_OK;
     }();
     c->d_iq = k_iq; c->in_frames = k_frames; c->have_input = k_have;
@@ -2064,7 +2068,7 @@ int ssdr_copy_from_device(ssdr_ctx *c, void *host_dst, const void *device_src, u
 {
     if (!c || !host_dst || !device_src) return SSDR_EINVAL;
     HIP_TRY(hipSetDevice(c->device));
-    { int rcj = join_audio(c); if (rcj != SSDR_OK) return rcj; }
+    SSDR_TRY(join_audio(c));
     HIP_TRY(hipMemcpyAsync(host_dst, device_src, bytes, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
     return SSDR_OK;
@@ -2074,7 +2078,7 @@ int ssdr_audio_device(ssdr_ctx *c, int16_t **pcm, float **rssi) SSDR_GUARD
 {
     if (!c) return SSDR_EINVAL;
     HIP_TRY(hipSetDevice(c->device));
-    { int rcj = join_audio(c); if (rcj != SSDR_OK) return rcj; }       // a consumer ordered behind the ctx stream sees the audio stage too
+    SSDR_TRY(join_audio(c));       // a consumer ordered behind the ctx stream sees the audio stage too
     if (pcm) *pcm = c->d_pcm;
     if (rssi) *rssi = c->d_rssi;
     return SSDR_OK;
@@ -2084,7 +2088,7 @@ int ssdr_get_consts(ssdr_ctx *c, uint32_t first, uint32_t count, ssdr_chan_const
 {
     if (!c || (uint64_t)first + count > c->n_ch) return SSDR_EINVAL;
     HIP_TRY(hipSetDevice(c->device));
-    { int rcj = join_audio(c); if (rcj != SSDR_OK) return rcj; }
+    SSDR_TRY(join_audio(c));
     if (consts) HIP_TRY(hipMemcpyAsync(consts, c->d_consts + first, count * sizeof(ssdr_chan_consts), hipMemcpyDeviceToHost, c->stream));
     if (taps) HIP_TRY(hipMemcpyAsync(taps, c->d_taps + (size_t)first * SSDR_NTAP_MAX, (size_t)count * SSDR_NTAP_MAX * 4, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
@@ -2095,7 +2099,7 @@ int ssdr_get_state(ssdr_ctx *c, uint32_t first, uint32_t count, ssdr_chan_state 
 {
     if (!c || (uint64_t)first + count > c->n_ch) return SSDR_EINVAL;
     HIP_TRY(hipSetDevice(c->device));
-    { int rcj = join_audio(c); if (rcj != SSDR_OK) return rcj; }
+    SSDR_TRY(join_audio(c));
     if (state) HIP_TRY(hipMemcpyAsync(state, c->d_state + first, count * sizeof(ssdr_chan_state), hipMemcpyDeviceToHost, c->stream));
     if (hist) HIP_TRY(hipMemcpyAsync(hist, c->d_hist + (size_t)first * SSDR_HIST, (size_t)count * SSDR_HIST * 4, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
@@ -2106,7 +2110,7 @@ int ssdr_set_state(ssdr_ctx *c, uint32_t first, uint32_t count, const ssdr_chan_
 {
     if (!c || (uint64_t)first + count > c->n_ch) return SSDR_EINVAL;
     HIP_TRY(hipSetDevice(c->device));
-    { int rcj = join_audio(c); if (rcj != SSDR_OK) return rcj; }
+    SSDR_TRY(join_audio(c));
     if (state) {
         HIP_TRY(hipMemcpyAsync(c->d_state + first, state, count * sizeof(ssdr_chan_state), hipMemcpyHostToDevice, c->stream));
         c->audio_started = true;             // a restored stream is live: ssdr_set_params must not re-seed its state
@@ -2143,7 +2147,7 @@ int ssdr_checkpoint_save(ssdr_ctx *c, void *blob) SSDR_GUARD
 {
     if (!c || !blob) return SSDR_EINVAL;
     HIP_TRY(hipSetDevice(c->device));
-    { int rcj = join_audio(c); if (rcj != SSDR_OK) return rcj; }
+    SSDR_TRY(join_audio(c));
     const size_t n = c->n_ch;
     if (c->zoom > 1) return SSDR_ESTATE;                     // the zoomed waterfall stream (phase, history, centres) is not part of the blob
     if (c->nb_on) return SSDR_ESTATE;                        // nor is the noise blanker's state
@@ -2202,8 +2206,8 @@ int ssdr_checkpoint_load(ssdr_ctx *c, const void *blob, uint64_t bytes) SSDR_GUA
         play_hist.assign(q, q + n * 8);
     }
     HIP_TRY(hipSetDevice(c->device));
-    { int rch = ssdr_set_hop(c, h.hop); if (rch != SSDR_OK) return rch; }
-    { int rcj = join_audio(c); if (rcj != SSDR_OK) return rcj; }
+    SSDR_TRY(ssdr_set_hop(c, h.hop));
+    SSDR_TRY(join_audio(c));
     const char *p = static_cast<const char *>(blob) + sizeof h;
     const hipMemcpyKind h2d = hipMemcpyHostToDevice;
     memcpy(c->h_consts.data(), kc.data(), n * sizeof(ssdr_chan_consts));
@@ -2282,7 +2286,7 @@ int ssdr_set_post_channels(ssdr_ctx *c, const uint32_t *channels, uint32_t count
         HIP_TRY(hipStreamSynchronize(c->stream));             // `channels` is the caller's
         c->n_post = count;
     } else {
-        if (c->d_post_sel) { HIP_TRY(hipStreamSynchronize(c->stream)); HIP_TRY(hipFree(c->d_post_sel)); c->d_post_sel = nullptr; }
+        SSDR_TRY(release(c, c->d_post_sel));
         c->n_post = c->n_ch;
     }
     // the device copy of wf_data holds other channels' rows now: it starts over (kiwi_waterfall.__init__'s np.zeros, utils_supersdr.py:692)
@@ -2302,11 +2306,7 @@ int ssdr_run_db2col(ssdr_ctx *c, ssdr_db2col_chan *chans, float *color_out, int 
     const uint32_t lines = c->wf_lines_ready;
     if (!c->d_db2col) HIP_TRY(hipMalloc(&c->d_db2col, (size_t)c->n_ch * sizeof(ssdr_db2col_chan)));
     if (lines == 0) return SSDR_OK;
-    if (c->color_lines < lines) {
-        if (c->d_color) { HIP_TRY(hipStreamSynchronize(c->stream)); HIP_TRY(hipFree(c->d_color)); c->d_color = nullptr; c->color_lines = 0; }
-        HIP_TRY(hipMalloc(&c->d_color, (size_t)lines * c->n_ch * SSDR_NFFT * sizeof(float)));
-        c->color_lines = lines;
-    }
+    SSDR_TRY(grow(c, c->d_color, c->color_lines, lines, (size_t)c->n_ch * SSDR_NFFT * sizeof(float)));
     if (c->n_post == 0) return SSDR_OK;                       // an empty selection: nobody is looking
     HIP_TRY(hipMemcpyAsync(c->d_db2col, chans, (size_t)c->n_post * sizeof(ssdr_db2col_chan), hipMemcpyHostToDevice, c->stream));
     SsdrDb2colArgs a;
@@ -2318,15 +2318,12 @@ int ssdr_run_db2col(ssdr_ctx *c, ssdr_db2col_chan *chans, float *color_out, int 
     a.color = c->d_color;
     a.sel = c->d_post_sel;
     a.n_sel = c->n_post;
-    int rc;
-    if ((rc = timed_begin(c)) != SSDR_OK) return rc;
+    SSDR_TRY(timed_begin(c));
     HIP_TRY(ssdr_launch_db2col(a, c->stream));
-    if ((rc = timed_end(c, SSDR_K_DB2COL)) != SSDR_OK) return rc;
-    if (c->d_wfdata) { int rcw = wfdata_feed(c, c->d_color, lines); if (rcw != SSDR_OK) return rcw; }
+    SSDR_TRY(timed_end(c, SSDR_K_DB2COL));
+    if (c->d_wfdata) SSDR_TRY(wfdata_feed(c, c->d_color, lines));
     HIP_TRY(hipMemcpyAsync(chans, c->d_db2col, (size_t)c->n_post * sizeof(ssdr_db2col_chan), hipMemcpyDeviceToHost, c->stream));
-    if (color_out)
-        HIP_TRY(hipMemcpyAsync(color_out, c->d_color, (size_t)lines * c->n_post * SSDR_NFFT * sizeof(float),
-                               out_is_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, c->stream));
+    if (color_out) SSDR_TRY(copy_out(c, color_out, c->d_color, (size_t)lines * c->n_post * SSDR_NFFT * sizeof(float), out_is_device, kSyncLater));
     HIP_TRY(hipStreamSynchronize(c->stream));
     return SSDR_OK;
 } SSDR_UNGUARD
@@ -2351,10 +2348,9 @@ int ssdr_db2col_line(ssdr_ctx *c, const int16_t *wf_sum, uint32_t n_avg, ssdr_db
     a.color = c->d_color1;
     a.sel = nullptr;
     a.n_sel = 1;
-    int rc;
-    if ((rc = timed_begin(c)) != SSDR_OK) return rc;
+    SSDR_TRY(timed_begin(c));
     HIP_TRY(ssdr_launch_db2col(a, c->stream));
-    if ((rc = timed_end(c, SSDR_K_DB2COL)) != SSDR_OK) return rc;
+    SSDR_TRY(timed_end(c, SSDR_K_DB2COL));
     HIP_TRY(hipMemcpyAsync(chan, c->d_dbchan1, sizeof(ssdr_db2col_chan), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipMemcpyAsync(color_out, c->d_color1, SSDR_NFFT * sizeof(float), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
@@ -2365,7 +2361,7 @@ int ssdr_output_checksum(ssdr_ctx *c, uint64_t sums[3]) SSDR_GUARD
 {
     if (!c || !sums) return SSDR_EINVAL;
     HIP_TRY(hipSetDevice(c->device));
-    { int rcj = join_audio(c); if (rcj != SSDR_OK) return rcj; }
+    SSDR_TRY(join_audio(c));
     HIP_TRY(hipMemsetAsync(c->d_scratch, 0, 24, c->stream));
     if (c->d_wf_out && c->wf_lines_ready)
         HIP_TRY(ssdr_launch_checksum(c->d_wf_out, (uint64_t)c->wf_lines_ready * c->n_ch * (SSDR_NFFT / 2), c->d_scratch, c->stream));
@@ -2384,9 +2380,8 @@ int ssdr_set_wfdata_rows(ssdr_ctx *c, uint32_t rows) SSDR_GUARD
 {
     if (!c || rows > 4096) return SSDR_EINVAL;
     HIP_TRY(hipSetDevice(c->device));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    if (c->d_wfdata) { HIP_TRY(hipFree(c->d_wfdata)); c->d_wfdata = nullptr; }
-    if (c->d_wfpend) { HIP_TRY(hipFree(c->d_wfpend)); c->d_wfpend = nullptr; }
+    SSDR_TRY(release(c, c->d_wfdata));
+    SSDR_TRY(release(c, c->d_wfpend));
     c->wfdata_rows = rows;
     c->wfdata_head = 0;
     c->wfdata_seen = c->wfpend_first = 0;
@@ -2394,7 +2389,7 @@ int ssdr_set_wfdata_rows(ssdr_ctx *c, uint32_t rows) SSDR_GUARD
     if (rows) {
         const size_t line = (size_t)c->n_ch * SSDR_NFFT * sizeof(float);
         if (hipMalloc(&c->d_wfdata, rows * line) != hipSuccess || hipMalloc(&c->d_wfpend, 3 * line) != hipSuccess) {
-            if (c->d_wfdata) (void)hipFree(c->d_wfdata);
+            (void)release(c, c->d_wfdata);
             c->d_wfdata = c->d_wfpend = nullptr;
             c->wfdata_rows = 0;
             return SSDR_ENOMEM;
@@ -2414,16 +2409,11 @@ int ssdr_push_color_lines(ssdr_ctx *c, const float *color, uint32_t lines, int c
     const size_t n = (size_t)lines * c->n_post * SSDR_NFFT;
     const float *src = color;
     if (!color_is_device) {
-        if (c->color_lines < lines) {
-            if (c->d_color) { HIP_TRY(hipStreamSynchronize(c->stream)); HIP_TRY(hipFree(c->d_color)); c->d_color = nullptr; c->color_lines = 0; }
-            HIP_TRY(hipMalloc(&c->d_color, n * sizeof(float)));
-            c->color_lines = lines;
-        }
+        SSDR_TRY(grow(c, c->d_color, c->color_lines, lines, (size_t)c->n_post * SSDR_NFFT * sizeof(float)));     // (lines of n_post channels)
         HIP_TRY(hipMemcpyAsync(c->d_color, color, n * sizeof(float), hipMemcpyHostToDevice, c->stream));
         src = c->d_color;
     }
-    int rc = wfdata_feed(c, src, lines);
-    if (rc != SSDR_OK) return rc;
+    SSDR_TRY(wfdata_feed(c, src, lines));
     HIP_TRY(hipStreamSynchronize(c->stream));
     return SSDR_OK;
 } SSDR_UNGUARD
@@ -2464,13 +2454,11 @@ int ssdr_run_trace(ssdr_ctx *c, uint32_t t_avg, uint32_t spectrum_height, double
     a.spectrum_height = spectrum_height;
     a.trace = c->d_trace;
     a.y = c->d_trace_y;
-    int rc;
-    if ((rc = timed_begin(c)) != SSDR_OK) return rc;
+    SSDR_TRY(timed_begin(c));
     HIP_TRY(ssdr_launch_trace(a, c->stream));
-    if ((rc = timed_end(c, SSDR_K_TRACE)) != SSDR_OK) return rc;
-    const hipMemcpyKind kind = out_is_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
-    if (trace_out) HIP_TRY(hipMemcpyAsync(trace_out, c->d_trace, n * sizeof(double), kind, c->stream));
-    if (y_out) HIP_TRY(hipMemcpyAsync(y_out, c->d_trace_y, n * sizeof(int32_t), kind, c->stream));
+    SSDR_TRY(timed_end(c, SSDR_K_TRACE));
+    if (trace_out) SSDR_TRY(copy_out(c, trace_out, c->d_trace, n * sizeof(double), out_is_device, kSyncLater));
+    if (y_out) SSDR_TRY(copy_out(c, y_out, c->d_trace_y, n * sizeof(int32_t), out_is_device, kSyncLater));
     HIP_TRY(hipStreamSynchronize(c->stream));
     return SSDR_OK;
 } SSDR_UNGUARD
@@ -2480,7 +2468,7 @@ int ssdr_run_smeter(ssdr_ctx *c, ssdr_smeter_chan *chans, const double *rssi_in,
     if (!c || !chans || !(fps > 0.0)) return SSDR_EINVAL;
     if (!rssi_in && (!c->d_rssi || c->audio_frames == 0 || c->audio_run_frames == 0)) return SSDR_ESTATE;
     HIP_TRY(hipSetDevice(c->device));
-    { int rcj = join_audio(c); if (rcj != SSDR_OK) return rcj; }
+    SSDR_TRY(join_audio(c));
     if (!c->d_smeter) {
         HIP_TRY(hipMalloc(&c->d_smeter, (size_t)c->n_ch * sizeof(ssdr_smeter_chan)));
         HIP_TRY(hipMalloc(&c->d_smeter_in, (size_t)c->n_ch * sizeof(double)));
@@ -2494,10 +2482,9 @@ int ssdr_run_smeter(ssdr_ctx *c, ssdr_smeter_chan *chans, const double *rssi_in,
     a.n_ch = c->n_ch;
     a.n_frames = c->audio_run_frames;
     a.fps = fps;
-    int rc;
-    if ((rc = timed_begin(c)) != SSDR_OK) return rc;
+    SSDR_TRY(timed_begin(c));
     HIP_TRY(ssdr_launch_smeter(a, c->stream));
-    if ((rc = timed_end(c, SSDR_K_SMETER)) != SSDR_OK) return rc;
+    SSDR_TRY(timed_end(c, SSDR_K_SMETER));
     HIP_TRY(hipMemcpyAsync(chans, c->d_smeter, (size_t)c->n_ch * sizeof(ssdr_smeter_chan), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
     return SSDR_OK;
@@ -2541,21 +2528,14 @@ int ssdr_run_playbuffer(ssdr_ctx *c, const ssdr_play_chan *chans, int16_t *out, 
     if (!c || !chans) return SSDR_EINVAL;
     if (!c->d_pcm || c->audio_run_frames == 0 || c->audio_frames < c->audio_run_frames) return SSDR_ESTATE;
     HIP_TRY(hipSetDevice(c->device));
-    { int rcj = join_audio(c); if (rcj != SSDR_OK) return rcj; }
+    SSDR_TRY(join_audio(c));
     const uint32_t nf = c->audio_run_frames;
     const bool wide = c->kiwi_rate != SSDR_RATE;                  // SAMPLE_RATIO % 1 != 0 (:1125)
     const size_t per_frame = wide ? (size_t)SSDR_RS_OUT_PER_FRAME : 2048;
-    { int rcp = ensure_play(c); if (rcp != SSDR_OK) return rcp; }
-    if (c->play_frames < nf) {          // sized for the longer (x4) form, either path fits
-        if (c->d_play_out) { HIP_TRY(hipStreamSynchronize(c->stream)); HIP_TRY(hipFree(c->d_play_out)); c->d_play_out = nullptr; c->play_frames = 0; }
-        HIP_TRY(hipMalloc(&c->d_play_out, (size_t)c->n_ch * nf * 2048 * 2 * sizeof(int16_t)));
-        c->play_frames = nf;
-    }
-    if (c->recording && c->play_mono_frames < nf) {
-        if (c->d_play_mono) { HIP_TRY(hipStreamSynchronize(c->stream)); HIP_TRY(hipFree(c->d_play_mono)); c->d_play_mono = nullptr; c->play_mono_frames = 0; }
-        HIP_TRY(hipMalloc(&c->d_play_mono, (size_t)c->n_ch * nf * 2048 * sizeof(int16_t)));
-        c->play_mono_frames = nf;
-    }
+    SSDR_TRY(ensure_play(c));
+    // (sized for the longer (x4) form, either path fits)
+    SSDR_TRY(grow(c, c->d_play_out, c->play_frames, nf, (size_t)c->n_ch * 2048 * 2 * sizeof(int16_t)));
+    if (c->recording) SSDR_TRY(grow(c, c->d_play_mono, c->play_mono_frames, nf, (size_t)c->n_ch * 2048 * sizeof(int16_t)));
     if (c->n_post == 0) { c->play_run_frames = 0; return SSDR_OK; }
     HIP_TRY(hipMemcpyAsync(c->d_play, chans, (size_t)c->n_post * sizeof(ssdr_play_chan), hipMemcpyHostToDevice, c->stream));
     if (c->d_post_sel && !wide)          // the channels outside the selection keep their history
@@ -2575,14 +2555,11 @@ int ssdr_run_playbuffer(ssdr_ctx *c, const ssdr_play_chan *chans, int16_t *out, 
     a.mono = c->recording ? c->d_play_mono : nullptr;
     c->play_run_frames = c->recording ? nf : 0;
     c->play_run_len = (uint32_t)per_frame;
-    int rc;
-    if ((rc = timed_begin(c)) != SSDR_OK) return rc;
+    SSDR_TRY(timed_begin(c));
     HIP_TRY(wide ? ssdr_launch_play_rs(a, c->stream) : ssdr_launch_play(a, c->stream));
     if (!wide) std::swap(c->d_play_hist, c->d_play_hist_alt);            // (the 64/27 branch carries no history)
-    if ((rc = timed_end(c, SSDR_K_PLAY)) != SSDR_OK) return rc;
-    if (out)
-        HIP_TRY(hipMemcpyAsync(out, c->d_play_out, (size_t)c->n_post * nf * per_frame * 2 * sizeof(int16_t),
-                               out_is_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, c->stream));
+    SSDR_TRY(timed_end(c, SSDR_K_PLAY));
+    if (out) SSDR_TRY(copy_out(c, out, c->d_play_out, (size_t)c->n_post * nf * per_frame * 2 * sizeof(int16_t), out_is_device, kSyncLater));
     HIP_TRY(hipStreamSynchronize(c->stream));
     return SSDR_OK;
 } SSDR_UNGUARD
@@ -2600,10 +2577,7 @@ int ssdr_playbuffer_mono(ssdr_ctx *c, int16_t *mono_out, int out_is_device) SSDR
     if (!c || !mono_out) return SSDR_EINVAL;
     if (!c->d_play_mono || c->play_run_frames == 0) return SSDR_ESTATE;       // the last ssdr_run_playbuffer did not record
     HIP_TRY(hipSetDevice(c->device));
-    HIP_TRY(hipMemcpyAsync(mono_out, c->d_play_mono, (size_t)c->n_post * c->play_run_frames * c->play_run_len * sizeof(int16_t),
-                           out_is_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    return SSDR_OK;
+    return copy_out(c, mono_out, c->d_play_mono, (size_t)c->n_post * c->play_run_frames * c->play_run_len * sizeof(int16_t), out_is_device, kSyncAlways);
 } SSDR_UNGUARD
 
 int ssdr_push_iq_wire(ssdr_ctx *c, const uint8_t *bodies, uint32_t n_frames, float *rssi_out) SSDR_GUARD
@@ -2611,13 +2585,11 @@ int ssdr_push_iq_wire(ssdr_ctx *c, const uint8_t *bodies, uint32_t n_frames, flo
     if (!c || !bodies || n_frames == 0) return SSDR_EINVAL;
     if (c->decim != 1) return SSDR_ESTATE;                       // SND bodies carry 512 IQ samples at 12 kHz
     HIP_TRY(hipSetDevice(c->device));
-    int rc = ensure_input(c, n_frames);
-    if (rc != SSDR_OK) return rc;
-    if (c->wire_frames < n_frames) {
-        HIP_TRY(hipStreamSynchronize(c->stream));
-        if (c->d_wire) { HIP_TRY(hipFree(c->d_wire)); c->d_wire = nullptr; }
-        if (c->d_wire_rssi) { HIP_TRY(hipFree(c->d_wire_rssi)); c->d_wire_rssi = nullptr; }
-        if (c->d_wire_gps) { HIP_TRY(hipFree(c->d_wire_gps)); c->d_wire_gps = nullptr; }
+    SSDR_TRY(ensure_input(c, n_frames));
+    if (c->wire_frames < n_frames) {                         // three buffers under one capacity
+        SSDR_TRY(release(c, c->d_wire));
+        SSDR_TRY(release(c, c->d_wire_rssi));
+        SSDR_TRY(release(c, c->d_wire_gps));
         c->wire_frames = 0;
         HIP_TRY(hipMalloc(&c->d_wire, (size_t)c->n_ch * n_frames * SSDR_WIRE_BODY + 16));   // (the unpack kernel reads whole dwords)
         HIP_TRY(hipMalloc(&c->d_wire_rssi, (size_t)c->n_ch * n_frames * sizeof(float)));
@@ -2634,9 +2606,9 @@ int ssdr_push_iq_wire(ssdr_ctx *c, const uint8_t *bodies, uint32_t n_frames, flo
     a.rssi = c->d_wire_rssi;
     a.gps = c->d_wire_gps;
     c->wire_run_frames = n_frames;
-    if ((rc = timed_begin(c)) != SSDR_OK) return rc;
+    SSDR_TRY(timed_begin(c));
     HIP_TRY(ssdr_launch_iqwire(a, c->stream));
-    if ((rc = timed_end(c, SSDR_K_WIRE)) != SSDR_OK) return rc;
+    SSDR_TRY(timed_end(c, SSDR_K_WIRE));
     if (rssi_out)
         HIP_TRY(hipMemcpyAsync(rssi_out, c->d_wire_rssi, (size_t)c->n_ch * n_frames * sizeof(float), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
@@ -2732,7 +2704,7 @@ int ssdr_set_compression(ssdr_ctx *c, uint32_t first, uint32_t count, const uint
         c->h_comp_snd.assign(c->n_ch, 0);
         c->h_comp_wf.assign(c->n_ch, 0);
         c->h_comp_list.assign(2 * (size_t)c->n_ch, 0u);
-        { int rcj = join_audio(c); if (rcj != SSDR_OK) return rcj; }
+        SSDR_TRY(join_audio(c));
         int32_t *st = nullptr;
         HIP_TRY(hipMalloc(&st, (size_t)c->n_ch * 8));
         c->d_adpcm_state = st;
@@ -2765,15 +2737,13 @@ int ssdr_set_compression(ssdr_ctx *c, uint32_t first, uint32_t count, const uint
         if (c->h_comp_snd[ch]) c->h_comp_list[ns++] = ch;
         if (c->h_comp_wf[ch]) c->h_comp_list[c->n_ch + nw++] = ch;
     }
-    { int rcj = join_audio(c); if (rcj != SSDR_OK) return rcj; }     // an encoder in flight reads the lists and the state
-    HIP_TRY(hipMemcpyAsync(c->d_comp_list, c->h_comp_list.data(), 2 * (size_t)c->n_ch * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
-    for (size_t i = 0; i < fresh.size();) {                 // (index, prev) = (0, 0), a run of consecutive channels at a time
-        size_t j = i + 1;
-        while (j < fresh.size() && fresh[j] == fresh[j - 1] + 1) j++;
-        HIP_TRY(hipMemsetAsync(c->d_adpcm_state + 2 * (size_t)fresh[i], 0, (j - i) * 8, c->stream));
-        i = j;
-    }
-    HIP_TRY(hipStreamSynchronize(c->stream));
+    SSDR_TRY(join_audio(c));     // an encoder in flight reads the lists and the state
+    // (index, prev) = (0, 0), a run of consecutive channels at a time
+    SSDR_TRY(for_each_run(fresh.data(), fresh.size(), [&](size_t i, size_t n) -> int {
+        HIP_TRY(hipMemsetAsync(c->d_adpcm_state + 2 * (size_t)fresh[i], 0, n * 8, c->stream));
+        return SSDR_OK;
+    }));
+    SSDR_TRY(upload_list(c, c->d_comp_list, c->h_comp_list.data(), 2 * (size_t)c->n_ch));
     c->comp_snd_n = ns;
     c->comp_wf_n = nw;
     if (snd_changed) c->snd_adpcm_valid = false;           // the rows of the last run were another selection's
@@ -2795,11 +2765,8 @@ int ssdr_audio_adpcm(ssdr_ctx *c, uint8_t *out, int out_is_device) SSDR_GUARD
     if (!c || !out) return SSDR_EINVAL;
     if (!c->comp_snd_n || !c->snd_adpcm_valid) return SSDR_ESTATE;
     HIP_TRY(hipSetDevice(c->device));
-    { int rcj = join_audio(c); if (rcj != SSDR_OK) return rcj; }
-    const size_t bytes = (size_t)c->comp_snd_n * c->snd_adpcm_frames * (SSDR_FRAME / 2);
-    HIP_TRY(hipMemcpyAsync(out, c->d_snd_adpcm, bytes, out_is_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    return SSDR_OK;
+    SSDR_TRY(join_audio(c));
+    return copy_out(c, out, c->d_snd_adpcm, (size_t)c->comp_snd_n * c->snd_adpcm_frames * (SSDR_FRAME / 2), out_is_device, kSyncAlways);
 } SSDR_UNGUARD
 
 int ssdr_wf_adpcm(ssdr_ctx *c, uint8_t *out, uint32_t *lines, int out_is_device) SSDR_GUARD
@@ -2809,10 +2776,7 @@ int ssdr_wf_adpcm(ssdr_ctx *c, uint8_t *out, uint32_t *lines, int out_is_device)
     *lines = c->wf_adpcm_lines;
     if (!out || !c->wf_adpcm_lines) return SSDR_OK;
     HIP_TRY(hipSetDevice(c->device));
-    const size_t bytes = (size_t)c->wf_adpcm_lines * c->comp_wf_n * SSDR_ADPCM_WF_BYTES;
-    HIP_TRY(hipMemcpyAsync(out, c->d_wf_adpcm, bytes, out_is_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    return SSDR_OK;
+    return copy_out(c, out, c->d_wf_adpcm, (size_t)c->wf_adpcm_lines * c->comp_wf_n * SSDR_ADPCM_WF_BYTES, out_is_device, kSyncAlways);
 } SSDR_UNGUARD
 
 int ssdr_squelch_tail_frames(double tail_s, uint32_t kiwi_rate, uint32_t *frames) SSDR_GUARD
@@ -2835,7 +2799,7 @@ int ssdr_set_squelch(ssdr_ctx *c, uint32_t first, uint32_t count, const ssdr_squ
     bool any = false;
     for (uint32_t i = 0; i < count; i++) any = any || p[i].fm_level || p[i].rssi_level;
     if (!c->d_sq && any) {                                  // the first nonzero level: state and list
-        { int rcj = join_audio(c); if (rcj != SSDR_OK) return rcj; }
+        SSDR_TRY(join_audio(c));
         SsdrSquelchChan *d = nullptr;
         HIP_TRY(hipMalloc(&d, (size_t)c->n_ch * sizeof(SsdrSquelchChan)));
         c->d_sq = d;
@@ -2845,7 +2809,7 @@ int ssdr_set_squelch(ssdr_ctx *c, uint32_t first, uint32_t count, const ssdr_squ
             c->d_sq_list = l;
         }
         if (c->h_sq.empty()) c->h_sq.assign(c->n_ch, ssdr_squelch_params{0u, 0u, 0u, 0u});
-        { int rcu = squelch_upload(c, 0, c->n_ch); if (rcu != SSDR_OK) return rcu; }     // every other channel: as set so far, fresh
+        SSDR_TRY(squelch_upload(c, 0, c->n_ch));     // every other channel: as set so far, fresh
     }
     if (c->h_sq.empty()) c->h_sq.assign(c->n_ch, ssdr_squelch_params{0u, 0u, 0u, 0u});
     uint32_t set_n = c->sq_set_n;
@@ -2872,18 +2836,15 @@ int ssdr_audio_squelch(ssdr_ctx *c, uint8_t *closed_out, int out_is_device) SSDR
     if (!c || !closed_out) return SSDR_EINVAL;
     if (c->sq_dirty || !c->sq_n || !c->sq_valid) return SSDR_ESTATE;       // (a change of settings or modes since the run: not that run's)
     HIP_TRY(hipSetDevice(c->device));
-    { int rcj = join_audio(c); if (rcj != SSDR_OK) return rcj; }
+    SSDR_TRY(join_audio(c));
     const size_t row = c->sq_frames;
     // the rows of the listed channels, a run of consecutive channels at a time; every other row is zero
     if (out_is_device) {
         HIP_TRY(hipMemsetAsync(closed_out, 0, (size_t)c->n_ch * row, c->stream));
-        for (uint32_t i = 0; i < c->sq_n;) {
-            uint32_t j = i + 1;
-            while (j < c->sq_n && c->h_sq_list[j] == c->h_sq_list[j - 1] + 1) j++;
-            HIP_TRY(hipMemcpyAsync(closed_out + (size_t)c->h_sq_list[i] * row, c->d_sq_closed + (size_t)i * row, (size_t)(j - i) * row,
-                                   hipMemcpyDeviceToDevice, c->stream));
-            i = j;
-        }
+        SSDR_TRY(for_each_run(c->h_sq_list.data(), c->sq_n, [&](size_t i, size_t n) -> int {
+            HIP_TRY(hipMemcpyAsync(closed_out + (size_t)c->h_sq_list[i] * row, c->d_sq_closed + i * row, n * row, hipMemcpyDeviceToDevice, c->stream));
+            return SSDR_OK;
+        }));
         HIP_TRY(hipStreamSynchronize(c->stream));
         return SSDR_OK;
     }
@@ -2913,7 +2874,7 @@ int ssdr_set_deemphasis(ssdr_ctx *c, uint32_t first, uint32_t count, const ssdr_
     bool any = false;
     for (uint32_t i = 0; i < count; i++) any = any || p[i].am || p[i].nfm;
     if (!c->d_de_state && any) {                            // the first nonzero setting: state and list
-        { int rcj = join_audio(c); if (rcj != SSDR_OK) return rcj; }
+        SSDR_TRY(join_audio(c));
         if (!c->d_de_list) {
             uint32_t *l = nullptr;
             HIP_TRY(hipMalloc(&l, (size_t)2 * c->n_ch * sizeof(uint32_t)));
@@ -2922,7 +2883,7 @@ int ssdr_set_deemphasis(ssdr_ctx *c, uint32_t first, uint32_t count, const ssdr_
         int32_t *d = nullptr;
         HIP_TRY(hipMalloc(&d, (size_t)c->n_ch * sizeof(int32_t)));
         c->d_de_state = d;
-        { int rcr = deemp_reset(c, 0, c->n_ch); if (rcr != SSDR_OK) return rcr; }
+        SSDR_TRY(deemp_reset(c, 0, c->n_ch));
     }
     if (c->h_de.empty()) c->h_de.assign(c->n_ch, ssdr_deemp_params{0u, 0u});
     uint32_t set_n = c->de_set_n;
@@ -2949,7 +2910,7 @@ int ssdr_get_deemp_state(ssdr_ctx *c, uint32_t first, uint32_t count, int32_t *S
     if (!count) return SSDR_OK;
     if (!c->d_de_state) { memset(S, 0, (size_t)count * sizeof(int32_t)); return SSDR_OK; }
     HIP_TRY(hipSetDevice(c->device));
-    { int rcj = join_audio(c); if (rcj != SSDR_OK) return rcj; }
+    SSDR_TRY(join_audio(c));
     HIP_TRY(hipMemcpyAsync(S, c->d_de_state + first, (size_t)count * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
     return SSDR_OK;
@@ -2959,8 +2920,7 @@ int ssdr_deemphasis_stats(ssdr_ctx *c, float *total_ms, uint32_t *launches, int 
 {
     if (!c) return SSDR_EINVAL;
     HIP_TRY(hipSetDevice(c->device));
-    int rc = resolve_pending(c);
-    if (rc != SSDR_OK) return rc;
+    SSDR_TRY(resolve_pending(c));
     if (total_ms) *total_ms = c->de_ms;
     if (launches) *launches = c->de_launches;
     if (reset) { c->de_ms = 0.0f; c->de_launches = 0; }
@@ -2971,11 +2931,7 @@ int ssdr_set_wf_lines(ssdr_ctx *c, const int16_t *wf_sum, uint32_t lines) SSDR_G
 {
     if (!c || !wf_sum || lines == 0) return SSDR_EINVAL;
     HIP_TRY(hipSetDevice(c->device));
-    if (c->wf_out_lines < lines) {
-        if (c->d_wf_out) { HIP_TRY(hipStreamSynchronize(c->stream)); HIP_TRY(hipFree(c->d_wf_out)); c->d_wf_out = nullptr; c->wf_out_lines = 0; }
-        HIP_TRY(hipMalloc(&c->d_wf_out, (size_t)lines * c->n_ch * SSDR_NFFT * 2));
-        c->wf_out_lines = lines;
-    }
+    SSDR_TRY(ensure_wf_out(c, lines));
     HIP_TRY(hipMemcpyAsync(c->d_wf_out, wf_sum, (size_t)lines * c->n_ch * SSDR_NFFT * 2, hipMemcpyHostToDevice, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
     c->wf_lines_ready = lines;
@@ -2986,16 +2942,8 @@ int ssdr_set_pcm(ssdr_ctx *c, const int16_t *pcm, uint32_t n_frames) SSDR_GUARD
 {
     if (!c || !pcm || n_frames == 0) return SSDR_EINVAL;
     HIP_TRY(hipSetDevice(c->device));
-    { int rcd = drain_audio(c); if (rcd != SSDR_OK) return rcd; }
-    if (c->audio_frames < n_frames) {
-        HIP_TRY(hipStreamSynchronize(c->stream));
-        if (c->d_pcm) { HIP_TRY(hipFree(c->d_pcm)); c->d_pcm = nullptr; }
-        if (c->d_rssi) { HIP_TRY(hipFree(c->d_rssi)); c->d_rssi = nullptr; }
-        c->audio_frames = 0;
-        HIP_TRY(hipMalloc(&c->d_pcm, (size_t)c->n_ch * n_frames * SSDR_FRAME * 2));
-        HIP_TRY(hipMalloc(&c->d_rssi, (size_t)c->n_ch * n_frames * sizeof(float)));
-        c->audio_frames = n_frames;
-    }
+    SSDR_TRY(drain_audio(c));
+    SSDR_TRY(ensure_audio_out(c, n_frames));
     HIP_TRY(hipMemcpyAsync(c->d_pcm, pcm, (size_t)c->n_ch * n_frames * SSDR_FRAME * 2, hipMemcpyHostToDevice, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
     c->audio_run_frames = n_frames;          // the input batch (d_iq / in_frames / have_input) is not touched

@@ -2084,7 +2084,8 @@ def test_waterfall_zoom_bit_exact_vs_twin_and_oracle(S, twin, Z, hop, n_avg, dec
 def test_contexts_release_their_device_memory(S):
     """ssdr_destroy gives back everything a ctx took, whatever it was used for: contexts that each touch every lazily
     allocated buffer (pipelined feed with post-processing, zoom, exact bins, hop 512, decimation, wf_data ring, trace,
-    playbuffer at both rates, wire input, pinned slots) are opened and closed in a loop; the device's free memory (hipMemGetInfo)
+    playbuffer at both rates, wire input, pinned slots, blanker, wire compression, squelch, de-emphasis, IQ mode) are opened and
+    closed in a loop; the device's free memory (hipMemGetInfo)
     does not drift."""
     import ctypes
     from supersdr_amd._lib import Db2colChan, PlayChan
@@ -2101,15 +2102,28 @@ def test_contexts_release_their_device_memory(S):
     def one_life(k):
         with S.SsdrEngine(n_ch) as eng:
             ps, _ = mixed_params(S, n_ch)
+            ps[5] = S.default_params("iq")
             eng.set_params(0, ps)
             if k % 3 == 1:
                 eng.set_hop(512)
             eng.set_averaging(1 + k % 3)
             eng.set_exact_bins(k % 2 == 1)
+            # the stages around the demodulator, each on a few channels: blanker, SND and W/F compression (byte lines when k % 3 == 0),
+            # squelch on an AM (0) and an NBFM (3) channel, de-emphasis on an AM channel; channel 5 in IQ mode
+            eng.set_noise_blanker(0, [100] * 4, [20] * 4)
+            eng.set_compression([1, 2, 3, 5], snd=True, wf=True)
+            eng.set_squelch(0, [(0, 0, 30, 4), (0, 0, 0, 0), (0, 0, 0, 0), (30, 1000, 0, 4)])
+            eng.set_deemphasis(0, [(1, 0)])
             eng.push_iq(iq)
             eng.run_chain()
             wf = eng.run_wf()
             eng.run_audio()
+            assert eng.audio_nb_mask().shape[0] == n_ch and len(eng.audio_adpcm()) == 4 and eng.audio_squelch().shape == (n_ch, 4)
+            assert eng.wf_adpcm().shape[:2] == (len(wf) if k % 3 == 0 else 0, 4) and eng.audio_iq().shape[0] == n_ch
+            eng.set_noise_blanker(0, [0] * 4, [0] * 4)            # (the feed below refuses to open beside these stages)
+            eng.set_compression([1, 2, 3, 5], snd=False, wf=False)
+            eng.set_squelch(0, [(0, 0, 0, 0)] * 4)
+            eng.set_deemphasis(0, [(0, 0)])
             eng.set_wfdata_rows(16)
             if len(wf):
                 eng.run_db2col([Db2colChan(zoom=0, auto_scale=1, low_clip_db=-120.0, high_clip_db=-60.0, dynamic_range=40.0)] * n_ch, len(wf))
