@@ -42,6 +42,29 @@ static int ssdr_caught(bool nomem) noexcept
     catch (const std::bad_alloc &) { return ssdr_caught(true); }   \
     catch (...) { return ssdr_caught(false); }
 
+// One batch: its input, and its results with their capacities and extents.  The ctx owns the one of ssdr_push_iq / ssdr_run_*
+// (`own`: what every getter and "the last run" reads); a slot of the pipelined feed forms one from its buffers.  The stages take
+// the batch they work on as a parameter.
+struct Batch {
+    const uint32_t *d_iq = nullptr;
+    uint32_t in_frames = 0;
+    bool have_input = false;
+    int16_t *d_wf_out = nullptr;
+    size_t wf_out_lines = 0;
+    uint32_t wf_lines_ready = 0;
+    int16_t *d_pcm = nullptr;
+    float *d_rssi = nullptr;
+    size_t audio_frames = 0;                  // capacity of d_pcm / d_rssi
+    uint32_t audio_run_frames = 0;            // frames the last audio run (or ssdr_set_pcm) produced: their extent and stride
+    uint8_t *d_flags = nullptr;               // ADC-overflow flag per frame of the last audio run
+    size_t flags_frames = 0;
+};
+// What ssdr_run_chain decides for a batch (chain_plan), handed to the two stages
+struct ChainPlan {
+    int one_read;                             // 0: a kernel per stage; 1: the fused AM kernel, 2: the wave-specialised one do both on one read of the input
+    bool beside;                              // the audio stage runs on stream2, beside the waterfall kernel
+};
+
 struct ssdr_ctx {
     int device = 0;
     uint32_t n_ch = 0;
@@ -84,12 +107,9 @@ struct ssdr_ctx {
     hipStream_t path_stream[SSDR_PATH_COUNT - 1] = {};  // the audio kernels of different paths run side by side
     hipEvent_t ev_fork = nullptr, ev_path[SSDR_PATH_COUNT - 1] = {};
     int fused_enabled = 1;                              // ssdr_set_fused: 0 never, 1 at hop 1024 (default), 2 at hop 512 as well, 3 + the wave-specialised kernel
-    bool fuse_ws_next = false;                          // ... and that kernel is ssdr_chain_ws_kernel (any mix of audio paths)
     uint32_t ws_grid = 0;
     uint32_t am_floor = 0, ws_floor = 0;                // ssdr_set_chain_floors: fewest channels for which ssdr_run_chain's default takes a one-read kernel
     bool overlap_enabled = true;                        // ssdr_set_overlap: un-fused ssdr_run_chain batches run the audio stage beside the waterfall kernel
-    bool fuse_next = false;                             // ssdr_run_chain: run_wf parks its arguments, run_audio launches the fused kernel
-    SsdrWfArgs fused_wf;
     uint32_t fused_grid = 0;
     bool audio_serial = false;                          // measurement: one path kernel after the other on one stream
     int16_t *d_wf_acc[2] = {nullptr, nullptr};          // ping-pong: carry-in / carry-out of partial groups
@@ -97,24 +117,13 @@ struct ssdr_ctx {
     // input batch
     uint32_t *d_iq_own = nullptr;
     size_t iq_own_frames = 0;
-    const uint32_t *d_iq = nullptr;
-    uint32_t in_frames = 0;
-    bool have_input = false;
+    Batch own;                               // the batch of ssdr_push_iq / ssdr_run_* and its results
     bool audio_started = false;              // an audio kernel has run since create / full reset: set_params leaves the state alone
     uint64_t synth_sample0 = 0;
-    // outputs
-    int16_t *d_wf_out = nullptr;
-    size_t wf_out_lines = 0;
-    uint32_t wf_lines_ready = 0;
-    int16_t *d_pcm = nullptr;
-    float *d_rssi = nullptr;
-    size_t audio_frames = 0;
+    // outputs that are the ctx's, whichever batch ran
     uint32_t *d_iq_out = nullptr;             // [n_ch][n_frames*512] I | Q << 16 of the channels in SSDR_MODE_IQ (allocated when one exists)
     size_t iq_out_frames = 0;
     bool iq_out_valid = false;
-    uint8_t *d_flags = nullptr;               // ADC-overflow flag per frame of the last audio run
-    size_t flags_frames = 0;
-    uint32_t audio_run_frames = 0;            // frames the last audio run (or ssdr_set_pcm) produced: extent and stride of d_pcm / d_rssi
     // pipelined host feed (ssdr_feed_*): slots of pinned host memory + their own device buffers
     struct FeedSlot {
         void *h_in = nullptr;                            // int16 IQ, or SND bodies in wire mode
@@ -261,7 +270,7 @@ static void free_owned(ssdr_ctx *c)
         c->d_zoom_taps, c->d_zoom_dphi, c->d_zoom_phase, c->d_zoom_hist, c->d_zoom_out,                               // zoom stage
         c->d_consts, c->d_taps, c->d_state, c->d_hist, c->d_chan_list, c->d_ws_list, c->d_wf_acc[0], c->d_wf_acc[1],  // per-channel
         c->d_iq_own,                                                                                                  // input batch
-        c->d_wf_out, c->d_pcm, c->d_rssi, c->d_iq_out, c->d_flags,                                                    // outputs
+        c->own.d_wf_out, c->own.d_pcm, c->own.d_rssi, c->d_iq_out, c->own.d_flags,                                    // outputs
         c->d_line1, c->d_dbchan1, c->d_color1,                                                                        // pipelined host feed
         c->d_scratch,                                                                                                 // measurement
         c->d_post_sel, c->d_db2col, c->d_color, c->d_play, c->d_play_taps, c->d_play_hist, c->d_play_rs_taps, c->d_play_hist_alt,
@@ -701,7 +710,7 @@ int ssdr_set_decimation(ssdr_ctx *c, uint32_t decim) SSDR_GUARD
     c->decim = decim;
     int rc = ssdr_set_params(c, 0, c->n_ch, all.data());
     if (rc == SSDR_OK) {
-        c->have_input = false;                                    // a batch pushed at the old rate has the wrong extent
+        c->own.have_input = false;                                // a batch pushed at the old rate has the wrong extent
         rc = ssdr_reset_state(c, 0, c->n_ch);                     // phases and histories of the old rate mean nothing now
         if (rc == SSDR_OK) rc = zoom_restart(c, 0, c->n_ch);
     }
@@ -968,37 +977,36 @@ static int ensure_input(ssdr_ctx *c, uint32_t n_frames)
     return grow(c, c->d_iq_own, c->iq_own_frames, (size_t)n_frames * c->decim, (size_t)c->n_ch * SSDR_FRAME * 4);
 }
 // room for the results of an audio run of n_frames frames: PCM and RSSI under one capacity (the caller drains the audio first)
-static int ensure_audio_out(ssdr_ctx *c, uint32_t n_frames)
+static int ensure_audio_out(ssdr_ctx *c, Batch &b, uint32_t n_frames)
 {
-    if (c->audio_frames >= n_frames) return SSDR_OK;
-    SSDR_TRY(release(c, c->d_pcm));
-    SSDR_TRY(release(c, c->d_rssi));
-    c->audio_frames = 0;
-    HIP_TRY(hipMalloc(&c->d_pcm, (size_t)c->n_ch * n_frames * SSDR_FRAME * 2));
-    HIP_TRY(hipMalloc(&c->d_rssi, (size_t)c->n_ch * n_frames * sizeof(float)));
-    c->audio_frames = n_frames;
+    if (b.audio_frames >= n_frames) return SSDR_OK;
+    SSDR_TRY(release(c, b.d_pcm));
+    SSDR_TRY(release(c, b.d_rssi));
+    b.audio_frames = 0;
+    HIP_TRY(hipMalloc(&b.d_pcm, (size_t)c->n_ch * n_frames * SSDR_FRAME * 2));
+    HIP_TRY(hipMalloc(&b.d_rssi, (size_t)c->n_ch * n_frames * sizeof(float)));
+    b.audio_frames = n_frames;
     return SSDR_OK;
 }
 // ... and for `lines` output lines of the waterfall stage
-static int ensure_wf_out(ssdr_ctx *c, uint32_t lines)
+static int ensure_wf_out(ssdr_ctx *c, Batch &b, uint32_t lines)
 {
-    return grow(c, c->d_wf_out, c->wf_out_lines, lines, (size_t)c->n_ch * SSDR_NFFT * 2);
+    return grow(c, b.d_wf_out, b.wf_out_lines, lines, (size_t)c->n_ch * SSDR_NFFT * 2);
 }
+
+// the ctx's own batch takes `n_frames` frames of input at `d_iq`
+static void own_input(ssdr_ctx *c, const uint32_t *d_iq, uint32_t n_frames) { c->own.d_iq = d_iq; c->own.in_frames = n_frames; c->own.have_input = true; }
 
 int ssdr_push_iq(ssdr_ctx *c, const int16_t *iq, uint32_t n_frames, int is_device) SSDR_GUARD
 {
     if (!c || !iq || n_frames == 0) return SSDR_EINVAL;
     HIP_TRY(hipSetDevice(c->device));
     SSDR_TRY(join_audio(c));
-    if (is_device) {
-        c->d_iq = reinterpret_cast<const uint32_t *>(iq);
-    } else {
+    if (!is_device) {
         SSDR_TRY(ensure_input(c, n_frames));
         HIP_TRY(hipMemcpyAsync(c->d_iq_own, iq, (size_t)c->n_ch * in_len(c, n_frames) * 4, hipMemcpyHostToDevice, c->stream));
-        c->d_iq = c->d_iq_own;
     }
-    c->in_frames = n_frames;
-    c->have_input = true;
+    own_input(c, is_device ? reinterpret_cast<const uint32_t *>(iq) : c->d_iq_own, n_frames);
     return SSDR_OK;
 } SSDR_UNGUARD
 
@@ -1019,31 +1027,29 @@ int ssdr_synth_iq(ssdr_ctx *c, uint32_t n_frames, uint32_t seed, uint32_t first_
     HIP_TRY(ssdr_launch_synth(a, c->stream));
     SSDR_TRY(timed_end(c, SSDR_K_SYNTH));
     c->synth_sample0 += a.n_samples;
-    c->d_iq = c->d_iq_own;
-    c->in_frames = n_frames;
-    c->have_input = true;
+    own_input(c, c->d_iq_own, n_frames);
     return SSDR_OK;
 } SSDR_UNGUARD
 
 int ssdr_read_input(ssdr_ctx *c, uint32_t first, uint32_t count, int16_t *iq_out) SSDR_GUARD
 {
     if (!c || !iq_out || (uint64_t)first + count > c->n_ch) return SSDR_EINVAL;
-    if (!c->have_input) return SSDR_ESTATE;
+    if (!c->own.have_input) return SSDR_ESTATE;
     HIP_TRY(hipSetDevice(c->device));
-    const size_t per_ch = in_len(c, c->in_frames);
-    HIP_TRY(hipMemcpyAsync(iq_out, c->d_iq + (size_t)first * per_ch, (size_t)count * per_ch * 4, hipMemcpyDeviceToHost, c->stream));
+    const size_t per_ch = in_len(c, c->own.in_frames);
+    HIP_TRY(hipMemcpyAsync(iq_out, c->own.d_iq + (size_t)first * per_ch, (size_t)count * per_ch * 4, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
     return SSDR_OK;
 } SSDR_UNGUARD
 
 // The shape rules of a waterfall batch, checked before ANY stage of a call is launched (ssdr_run_chain runs its audio stage first
 // when the stages go side by side: a batch the waterfall stage would refuse must not have advanced the audio state by then).
-static int validate_wf_batch(const ssdr_ctx *c)
+static int validate_wf_batch(const ssdr_ctx *c, const Batch &b)
 {
     const bool hop512 = c->hop == SSDR_NFFT / 2;
     const bool zoomed = c->zoom > 1;
-    if (zoomed && (c->fuse_next || (c->in_frames * c->decim) % c->zoom)) return SSDR_EINVAL;
-    const uint32_t halves = c->in_frames * c->decim / c->zoom;       // 512-sample half-lines the batch yields (of the zoomed stream)
+    if (zoomed && (b.in_frames * c->decim) % c->zoom) return SSDR_EINVAL;     // (no one-read kernel is ever planned for a zoomed batch)
+    const uint32_t halves = b.in_frames * c->decim / c->zoom;         // 512-sample half-lines the batch yields (of the zoomed stream)
     if (!hop512 && (halves & 1u)) return SSDR_EINVAL;                // a batch must hold a whole number of lines
     if (zoomed && halves == 0) return SSDR_EINVAL;
     return SSDR_OK;
@@ -1051,33 +1057,33 @@ static int validate_wf_batch(const ssdr_ctx *c)
 
 // ---- IMA-ADPCM wire compression: the encoder behind the stages (ssdr_set_compression) -------------------------------------
 // room for the SND payloads of an audio run of the current batch
-static int adpcm_snd_alloc(ssdr_ctx *c)
+static int adpcm_snd_alloc(ssdr_ctx *c, const Batch &b)
 {
-    const size_t need = (size_t)c->comp_snd_n * c->in_frames * (SSDR_FRAME / 2);
+    const size_t need = (size_t)c->comp_snd_n * b.in_frames * (SSDR_FRAME / 2);
     if (c->snd_adpcm_bytes >= need) return SSDR_OK;
     SSDR_TRY(drain_audio(c));
     c->snd_adpcm_valid = false;
     return grow(c, c->d_snd_adpcm, c->snd_adpcm_bytes, need, 1);
 }
 // the SND payloads of the audio stage just queued on `s` (its PCM), behind it on the same stream: the state advances once per batch
-static int adpcm_snd_launch(ssdr_ctx *c, hipStream_t s)
+static int adpcm_snd_launch(ssdr_ctx *c, const Batch &b, hipStream_t s)
 {
     if (!c->comp_snd_n) return SSDR_OK;
     SsdrAdpcmArgs e;
-    e.src = c->d_pcm;
-    e.row_stride = (uint64_t)c->in_frames * SSDR_FRAME;
+    e.src = b.d_pcm;
+    e.row_stride = (uint64_t)b.in_frames * SSDR_FRAME;
     e.line_stride = 0;
     e.list = c->d_comp_list;
     e.n_sel = c->comp_snd_n;
     e.n_lines = 1;
-    e.n_samples = c->in_frames * SSDR_FRAME;
+    e.n_samples = b.in_frames * SSDR_FRAME;
     e.consts = c->d_consts;
     e.state = c->d_adpcm_state;
     e.out = c->d_snd_adpcm;
-    e.out_stride = (uint64_t)c->in_frames * (SSDR_FRAME / 2);
+    e.out_stride = (uint64_t)b.in_frames * (SSDR_FRAME / 2);
     SSDR_TRY(timed_launch(c, SSDR_K_ADPCM, s, [&]() -> int { HIP_TRY(ssdr_launch_adpcm_enc(e, s)); return SSDR_OK; }));
     c->snd_adpcm_valid = true;
-    c->snd_adpcm_frames = c->in_frames;
+    c->snd_adpcm_frames = b.in_frames;
     return SSDR_OK;
 }
 // room for the W/F payloads of `lines` byte lines (the encoder only ever runs on the main stream)
@@ -1089,13 +1095,13 @@ static int adpcm_wf_alloc(ssdr_ctx *c, uint32_t lines)
     return grow(c, c->d_wf_adpcm, c->wf_adpcm_bytes, need, 1);
 }
 // the W/F payloads of the lines the waterfall stage just queued on `s`: only byte lines (N = 1) go on the wire
-static int adpcm_wf_launch(ssdr_ctx *c, hipStream_t s, uint32_t n_avg)
+static int adpcm_wf_launch(ssdr_ctx *c, const Batch &b, hipStream_t s, uint32_t n_avg)
 {
     if (!c->comp_wf_n) return SSDR_OK;
-    const uint32_t lines = n_avg == 1 ? c->wf_lines_ready : 0;
+    const uint32_t lines = n_avg == 1 ? b.wf_lines_ready : 0;
     if (lines) {
         SsdrAdpcmArgs e;
-        e.src = c->d_wf_out;
+        e.src = b.d_wf_out;
         e.row_stride = SSDR_NFFT;
         e.line_stride = (uint64_t)c->n_ch * SSDR_NFFT;
         e.list = c->d_comp_list + c->n_ch;
@@ -1152,24 +1158,24 @@ static int squelch_refresh(ssdr_ctx *c)
     return SSDR_OK;
 }
 // the list up to date, and room for the closed flags of an audio run of the current batch
-static int squelch_prepare(ssdr_ctx *c)
+static int squelch_prepare(ssdr_ctx *c, const Batch &b)
 {
     if (!c->sq_set_n && !c->sq_dirty) return SSDR_OK;
     SSDR_TRY(squelch_refresh(c));
-    const size_t need = (size_t)c->sq_n * c->in_frames;
+    const size_t need = (size_t)c->sq_n * b.in_frames;
     if (c->sq_closed_bytes >= need) return SSDR_OK;
     SSDR_TRY(drain_audio(c));
     c->sq_valid = false;
     return grow(c, c->d_sq_closed, c->sq_closed_bytes, need, 1);
 }
 // squelch the PCM of the audio stage just queued on `s`, behind it on the same stream: the state advances once per batch
-static int squelch_launch(ssdr_ctx *c, hipStream_t s)
+static int squelch_launch(ssdr_ctx *c, const Batch &b, hipStream_t s)
 {
     if (!c->sq_n) return SSDR_OK;
     SsdrSquelchArgs q;
-    q.pcm = c->d_pcm;
-    q.rssi = c->d_rssi;
-    q.n_frames = c->in_frames;
+    q.pcm = b.d_pcm;
+    q.rssi = b.d_rssi;
+    q.n_frames = b.in_frames;
     q.list = c->d_sq_list;
     q.list_n = c->sq_n;
     q.consts = c->d_consts;
@@ -1177,7 +1183,7 @@ static int squelch_launch(ssdr_ctx *c, hipStream_t s)
     q.closed = c->d_sq_closed;
     SSDR_TRY(timed_launch(c, SSDR_K_SQUELCH, s, [&]() -> int { HIP_TRY(ssdr_launch_squelch(q, s)); return SSDR_OK; }));
     c->sq_valid = true;
-    c->sq_frames = c->in_frames;
+    c->sq_frames = b.in_frames;
     return SSDR_OK;
 }
 
@@ -1223,12 +1229,12 @@ static int deemp_prepare(ssdr_ctx *c)
     return SSDR_OK;
 }
 // filter the PCM of the audio stage (and squelch) just queued on `s`, behind them on the same stream
-static int deemp_launch(ssdr_ctx *c, hipStream_t s)
+static int deemp_launch(ssdr_ctx *c, const Batch &b, hipStream_t s)
 {
     if (!c->de_n) return SSDR_OK;
     SsdrDeempArgs q;
-    q.pcm = c->d_pcm;
-    q.n_samples = c->in_frames * SSDR_FRAME;
+    q.pcm = b.d_pcm;
+    q.n_samples = b.in_frames * SSDR_FRAME;
     q.list = c->d_de_list;
     q.coef = c->d_de_list + c->n_ch;
     q.list_n = c->de_n;
@@ -1240,38 +1246,38 @@ static int deemp_launch(ssdr_ctx *c, hipStream_t s)
 
 // ---- the tail of the audio stage: squelch, de-emphasis, SND encoder -- one order, whichever kernel did the stage's work ---------
 // lists and room, before anything of the run is launched
-static int audio_tail_prepare(ssdr_ctx *c)
+static int audio_tail_prepare(ssdr_ctx *c, const Batch &b)
 {
-    SSDR_TRY(adpcm_snd_alloc(c));
+    SSDR_TRY(adpcm_snd_alloc(c, b));
     c->snd_adpcm_valid = false;
-    SSDR_TRY(squelch_prepare(c));
+    SSDR_TRY(squelch_prepare(c, b));
     c->sq_valid = false;
     return deemp_prepare(c);
 }
 // behind the kernel that wrote the PCM, on its stream `s`
-static int audio_tail_launch(ssdr_ctx *c, hipStream_t s)
+static int audio_tail_launch(ssdr_ctx *c, const Batch &b, hipStream_t s)
 {
-    SSDR_TRY(squelch_launch(c, s));
-    SSDR_TRY(deemp_launch(c, s));
-    return adpcm_snd_launch(c, s);
+    SSDR_TRY(squelch_launch(c, b, s));
+    SSDR_TRY(deemp_launch(c, b, s));
+    return adpcm_snd_launch(c, b, s);
 }
 
-int ssdr_run_wf(ssdr_ctx *c, int16_t *wf_sum_out, uint32_t *lines_ready, int out_is_device) SSDR_GUARD
+// The waterfall stage of batch `b` on the main stream.  Under a plan with a one-read kernel it does the stage's bookkeeping only and
+// hands its kernel arguments on in `*one_read`: the audio stage launches the kernel that does both stages' work.
+static int wf_stage(ssdr_ctx *c, Batch &b, ChainPlan plan, SsdrWfArgs *one_read, uint32_t *lines_ready)
 {
-    if (!c) return SSDR_EINVAL;
-    if (!c->have_input) return SSDR_ESTATE;
     const bool hop512 = c->hop == SSDR_NFFT / 2;
     const bool zoomed = c->zoom > 1;
-    SSDR_TRY(validate_wf_batch(c));
-    const uint32_t halves = c->in_frames * c->decim / c->zoom;
+    SSDR_TRY(validate_wf_batch(c, b));
+    const uint32_t halves = b.in_frames * c->decim / c->zoom;
     HIP_TRY(hipSetDevice(c->device));
-    const uint32_t *wf_src = c->d_iq;                                // what the waterfall kernel reads: the input, or the zoomed stream
-    uint64_t wf_stride = (uint64_t)in_len(c, c->in_frames);
+    const uint32_t *wf_src = b.d_iq;                                 // what the waterfall kernel reads: the input, or the zoomed stream
+    uint64_t wf_stride = (uint64_t)in_len(c, b.in_frames);
     if (zoomed) {
-        const uint32_t n_in = (uint32_t)in_len(c, c->in_frames), n_out = n_in / c->zoom;
+        const uint32_t n_in = (uint32_t)in_len(c, b.in_frames), n_out = n_in / c->zoom;
         SSDR_TRY(grow(c, c->d_zoom_out, c->zoom_out_samples, n_out, (size_t)c->n_ch * 4));
         SsdrZoomArgs z;
-        z.iq = c->d_iq; z.ch_stride = wf_stride; z.n_ch = c->n_ch; z.n_in = n_in; z.zoom = c->zoom; z.ntap = c->zoom_ntap;
+        z.iq = b.d_iq; z.ch_stride = wf_stride; z.n_ch = c->n_ch; z.n_in = n_in; z.zoom = c->zoom; z.ntap = c->zoom_ntap;
         z.taps = c->d_zoom_taps; z.dphi = c->d_zoom_dphi; z.phase = c->d_zoom_phase; z.hist = c->d_zoom_hist; z.out = c->d_zoom_out;
         SSDR_TRY(timed_begin(c));
         HIP_TRY(ssdr_launch_zoom(z, c->stream));
@@ -1284,7 +1290,7 @@ int ssdr_run_wf(ssdr_ctx *c, int16_t *wf_sum_out, uint32_t *lines_ready, int out
     const uint32_t total = c->wf_phase + n_lines;
     const uint32_t n_out = total / c->n_avg;
     const uint32_t n_groups = (total + c->n_avg - 1) / c->n_avg;
-    SSDR_TRY(ensure_wf_out(c, n_out));
+    SSDR_TRY(ensure_wf_out(c, b, n_out));
     if (c->comp_wf_n && c->n_avg == 1) SSDR_TRY(adpcm_wf_alloc(c, n_out));
     c->wf_adpcm_valid = false;
     SsdrWfArgs a;
@@ -1297,7 +1303,7 @@ int ssdr_run_wf(ssdr_ctx *c, int16_t *wf_sum_out, uint32_t *lines_ready, int out
     a.phase = c->wf_phase;
     a.n_groups = n_groups;
     a.grp_run = 1;
-    a.out = c->d_wf_out;
+    a.out = b.d_wf_out;
     a.acc_in = c->d_wf_acc[c->wf_acc_cur];
     a.acc_out = c->d_wf_acc[c->wf_acc_cur ^ 1];
     a.consts = c->d_consts;
@@ -1305,7 +1311,7 @@ int ssdr_run_wf(ssdr_ctx *c, int16_t *wf_sum_out, uint32_t *lines_ready, int out
     a.tw_stage = c->d_tw;
     a.lut = c->d_lut;
     uint64_t items = (uint64_t)((c->n_ch + 1) / 2) * n_groups;
-    const uint32_t wf_grid = c->concurrent ? c->wf_grid_1 : c->wf_grid;
+    const uint32_t wf_grid = plan.beside ? c->wf_grid_1 : c->wf_grid;
     if (hop512 && n_groups) {
         // a wave works through a run of consecutive groups of its channel pair, so the half-line two lines share is read
         // again by the wave that fetched it one line earlier; runs as long as still leave every resident wave ~8 items
@@ -1317,84 +1323,99 @@ int ssdr_run_wf(ssdr_ctx *c, int16_t *wf_sum_out, uint32_t *lines_ready, int out
     }
     const uint64_t need = (items + SSDR_WF_BLOCK / 64 - 1) / (SSDR_WF_BLOCK / 64);
     const uint32_t grid = (uint32_t)(need < wf_grid ? need : wf_grid);
-    if (c->fuse_next) {                      // the fused superframe kernel does this stage's work: ssdr_run_audio launches it
-        c->fused_wf = a;
+    if (plan.one_read) {                     // that kernel does this stage's work: the audio stage launches it
+        *one_read = a;
     } else {
         SSDR_TRY(timed_begin(c));
         if (c->exact_bins) HIP_TRY(ssdr_launch_wf_exact(a, c->d_tw64, c->stream));
         else HIP_TRY(ssdr_launch_wf(a, grid ? grid : 1, c->stream));
         SSDR_TRY(timed_end(c, SSDR_K_WF));
     }
-    if (hop512 && !c->fuse_next) // the batch's last half-line is the next batch's first: [n_ch] rows of 2 KB out of the input
+    if (hop512 && !plan.one_read) // the batch's last half-line is the next batch's first: [n_ch] rows of 2 KB out of the input
         HIP_TRY(hipMemcpy2DAsync(c->d_wf_tail, (SSDR_NFFT / 2) * 4, wf_src + (size_t)(halves - 1) * SSDR_FRAME,
                                  wf_stride * 4, (SSDR_NFFT / 2) * 4, c->n_ch, hipMemcpyDeviceToDevice, c->stream));
     c->wf_phase = total % c->n_avg;
     if (c->wf_phase) c->wf_acc_cur ^= 1;             // a partial group was written to acc_out
-    c->wf_lines_ready = n_out;
+    b.wf_lines_ready = n_out;
     if (lines_ready) *lines_ready = n_out;
-    if (!c->fuse_next) SSDR_TRY(adpcm_wf_launch(c, c->stream, c->n_avg));   // (fused: ssdr_run_audio)
-    if (wf_sum_out && n_out) SSDR_TRY(copy_out(c, wf_sum_out, c->d_wf_out, (size_t)n_out * c->n_ch * SSDR_NFFT * 2, out_is_device, kSyncHost));
+    if (!plan.one_read) SSDR_TRY(adpcm_wf_launch(c, b, c->stream, c->n_avg));   // (one-read: the audio stage)
     return SSDR_OK;
-} SSDR_UNGUARD
+}
 
-int ssdr_run_audio(ssdr_ctx *c, int16_t *pcm_out, float *rssi_out, int out_is_device) SSDR_GUARD
+int ssdr_run_wf(ssdr_ctx *c, int16_t *wf_sum_out, uint32_t *lines_ready, int out_is_device) SSDR_GUARD
 {
     if (!c) return SSDR_EINVAL;
-    if (!c->have_input) return SSDR_ESTATE;
+    if (!c->own.have_input) return SSDR_ESTATE;
+    Batch &b = c->own;
+    SSDR_TRY(wf_stage(c, b, ChainPlan{0, c->concurrent}, nullptr, lines_ready));
+    if (!wf_sum_out || !b.wf_lines_ready) return SSDR_OK;
+    return copy_out(c, wf_sum_out, b.d_wf_out, (size_t)b.wf_lines_ready * c->n_ch * SSDR_NFFT * 2, out_is_device, kSyncHost);
+} SSDR_UNGUARD
+
+// the stream the audio stage runs on under a plan; and, once all the call puts there is queued, the mark that later work on the
+// main stream (next input, playbuffer) follows
+static hipStream_t audio_stream(const ssdr_ctx *c, ChainPlan plan) { return plan.beside ? c->stream2 : c->stream; }
+static int audio_queued(ssdr_ctx *c, ChainPlan plan)
+{
+    if (plan.beside) { HIP_TRY(hipEventRecord(c->ev_a, c->stream2)); c->audio_pending = true; }
+    return SSDR_OK;
+}
+// The audio stage of batch `b` with its tail; under a plan with a one-read kernel that kernel, on the waterfall stage's arguments `wf`.
+static int audio_stage(ssdr_ctx *c, Batch &b, ChainPlan plan, const SsdrWfArgs *wf)
+{
     HIP_TRY(hipSetDevice(c->device));
-    if (!c->concurrent) SSDR_TRY(join_audio(c));      // the previous frame's state before this one
-    if (c->audio_frames < c->in_frames || c->flags_frames < c->in_frames) SSDR_TRY(drain_audio(c));
-    SSDR_TRY(ensure_audio_out(c, c->in_frames));
-    SSDR_TRY(grow(c, c->d_flags, c->flags_frames, c->in_frames, c->n_ch));
-    const size_t nb_mask_need = c->nb_on ? (size_t)c->n_ch * c->in_frames * 64 * c->decim : 0;     // one bit per input sample
+    if (!plan.beside) SSDR_TRY(join_audio(c));        // the previous frame's state before this one
+    if (b.audio_frames < b.in_frames || b.flags_frames < b.in_frames) SSDR_TRY(drain_audio(c));
+    SSDR_TRY(ensure_audio_out(c, b, b.in_frames));
+    SSDR_TRY(grow(c, b.d_flags, b.flags_frames, b.in_frames, c->n_ch));
+    const size_t nb_mask_need = c->nb_on ? (size_t)c->n_ch * b.in_frames * 64 * c->decim : 0;     // one bit per input sample
     if (c->nb_mask_bytes < nb_mask_need) {
         SSDR_TRY(drain_audio(c));
         c->nb_mask_valid = false;
         SSDR_TRY(grow(c, c->d_nb_mask, c->nb_mask_bytes, nb_mask_need, 1));
     }
-    SSDR_TRY(audio_tail_prepare(c));
+    SSDR_TRY(audio_tail_prepare(c, b));
     SsdrAudioArgs a;
-    a.iq = c->d_iq;
-    a.ch_stride = (uint64_t)in_len(c, c->in_frames);
+    a.iq = b.d_iq;
+    a.ch_stride = (uint64_t)in_len(c, b.in_frames);
     a.n_ch = c->n_ch;
-    a.n_frames = c->in_frames;
+    a.n_frames = b.in_frames;
     a.consts = c->d_consts;
     a.taps = c->d_taps;
     a.state = c->d_state;
     a.hist = c->d_hist;
-    a.pcm = c->d_pcm;
-    a.rssi = c->d_rssi;
-    a.flags = c->d_flags;
+    a.pcm = b.d_pcm;
+    a.rssi = b.d_rssi;
+    a.flags = b.d_flags;
     a.iq_out = nullptr;
     c->iq_out_valid = false;
     {
         chan_summary(c);
         const bool any_iq = c->sum_any_iq;
         if (any_iq && c->feed.empty()) {          // (the pipelined feed hands out PCM rows only: an IQ channel's row carries I)
-            if (c->iq_out_frames < c->in_frames) {
+            if (c->iq_out_frames < b.in_frames) {
                 SSDR_TRY(drain_audio(c));
-                SSDR_TRY(grow(c, c->d_iq_out, c->iq_out_frames, c->in_frames, (size_t)c->n_ch * SSDR_FRAME * 4));
+                SSDR_TRY(grow(c, c->d_iq_out, c->iq_out_frames, b.in_frames, (size_t)c->n_ch * SSDR_FRAME * 4));
             }
-            HIP_TRY(hipMemsetAsync(c->d_iq_out, 0, (size_t)c->n_ch * c->in_frames * SSDR_FRAME * 4, c->stream));   // rows of the other modes
+            HIP_TRY(hipMemsetAsync(c->d_iq_out, 0, (size_t)c->n_ch * b.in_frames * SSDR_FRAME * 4, c->stream));   // rows of the other modes
             a.iq_out = c->d_iq_out;
             c->iq_out_valid = true;
         }
     }
-    hipStream_t s = c->stream;
-    if (c->concurrent) {
+    const hipStream_t s = audio_stream(c, plan);
+    if (plan.beside) {
         // the audio kernel only depends on the input batch (and on its own previous launch): run it beside the
         // waterfall kernel on a second stream so that its waves fill the issue slots the waterfall leaves idle
-        s = c->stream2;
         HIP_TRY(hipEventRecord(c->ev_in, c->stream));          // everything queued so far, incl. the input copy/synth
         HIP_TRY(hipStreamWaitEvent(s, c->ev_in, 0));
     }
     SSDR_TRY(ensure_chan_list(c, s));
     c->audio_started = true;
-    c->audio_run_frames = c->in_frames;
+    b.audio_run_frames = b.in_frames;
     c->nb_mask_valid = false;
-    if (c->fuse_next) {                      // waterfall + full-band AM audio in one kernel: one read of the input
+    if (plan.one_read) {                     // waterfall + audio in one kernel: one read of the input
         SsdrFusedArgs fa;
-        fa.wf = c->fused_wf;
+        fa.wf = *wf;
         fa.au = a;
         fa.au.chan_list = c->d_ws_list;        // (the wave-specialised kernel draws pairs from its own list of all channels)
         fa.au.list_n = c->n_ch;
@@ -1404,7 +1425,7 @@ int ssdr_run_audio(ssdr_ctx *c, int16_t *pcm_out, float *rssi_out, int out_is_de
         const uint64_t need = (pairs + SSDR_WF_BLOCK / 64 - 1) / (SSDR_WF_BLOCK / 64);
         const uint32_t grid = (uint32_t)(need < c->fused_grid ? need : c->fused_grid);
         SSDR_TRY(timed_begin(c, s));
-        if (c->fuse_ws_next) {
+        if (plan.one_read == 2) {
             const uint64_t need_g = ((uint64_t)c->n_ch + SSDR_WS_AUDIO_WAVES - 1) / SSDR_WS_AUDIO_WAVES;
             const uint32_t grid_g = (uint32_t)(need_g < c->ws_grid ? need_g : c->ws_grid);
             HIP_TRY(ssdr_launch_chain_ws(fa, grid_g ? grid_g : 1, s));
@@ -1415,8 +1436,8 @@ int ssdr_run_audio(ssdr_ctx *c, int16_t *pcm_out, float *rssi_out, int out_is_de
         if (fa.wf.tail)          // hop 512: only now may the carried half-line (the kernel's line 0 read it) become this batch's last one
             HIP_TRY(hipMemcpy2DAsync(c->d_wf_tail, (SSDR_NFFT / 2) * 4, fa.wf.iq + (size_t)(fa.wf.n_lines - 1) * SSDR_FRAME,
                                      fa.wf.ch_stride * 4, (SSDR_NFFT / 2) * 4, c->n_ch, hipMemcpyDeviceToDevice, s));
-        SSDR_TRY(audio_tail_launch(c, s));         // behind the one-read kernel, and then the W/F encoder
-        return adpcm_wf_launch(c, s, fa.wf.n_avg);
+        SSDR_TRY(audio_tail_launch(c, b, s));      // behind the one-read kernel, and then the W/F encoder
+        return adpcm_wf_launch(c, b, s, fa.wf.n_avg);
     }
     // one kernel per non-empty path: the first on the stream itself, the others beside it on their own streams
     // (fork and join by events); the stage is timed between two events on `s`
@@ -1466,7 +1487,7 @@ int ssdr_run_audio(ssdr_ctx *c, int16_t *pcm_out, float *rssi_out, int out_is_de
     SSDR_TRY(timed_end(c, SSDR_K_AUDIO, s));
     if (c->nb_on) {
         c->nb_mask_valid = true;
-        c->nb_mask_frames = c->in_frames;
+        c->nb_mask_frames = b.in_frames;
         c->nb_mask_decim = c->decim;
         if (c->nb_mask_gen != c->nb_gen) {
             c->nb_mask_on.resize(c->n_ch);
@@ -1474,23 +1495,28 @@ int ssdr_run_audio(ssdr_ctx *c, int16_t *pcm_out, float *rssi_out, int out_is_de
             c->nb_mask_gen = c->nb_gen;
         }
     }
-    SSDR_TRY(audio_tail_launch(c, s));
-    const hipMemcpyKind kind = out_is_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
-    if (pcm_out) HIP_TRY(hipMemcpyAsync(pcm_out, c->d_pcm, (size_t)c->n_ch * c->in_frames * SSDR_FRAME * 2, kind, s));
-    if (rssi_out) HIP_TRY(hipMemcpyAsync(rssi_out, c->d_rssi, (size_t)c->n_ch * c->in_frames * sizeof(float), kind, s));
-    if ((pcm_out || rssi_out) && !out_is_device) HIP_TRY(hipStreamSynchronize(s));
-    if (c->concurrent) {                                       // later work on the main stream (next input, playbuffer) follows the audio
-        HIP_TRY(hipEventRecord(c->ev_a, s));
-        c->audio_pending = true;
-    }
-    return SSDR_OK;
-} SSDR_UNGUARD
+    return audio_tail_launch(c, b, s);
+}
 
-int ssdr_run_chain(ssdr_ctx *c, uint32_t *lines_ready, int *fused) SSDR_GUARD
+int ssdr_run_audio(ssdr_ctx *c, int16_t *pcm_out, float *rssi_out, int out_is_device) SSDR_GUARD
 {
     if (!c) return SSDR_EINVAL;
-    if (!c->have_input) return SSDR_ESTATE;
-    chan_summary(c);
+    if (!c->own.have_input) return SSDR_ESTATE;
+    const ChainPlan plan = {0, c->concurrent};
+    Batch &b = c->own;
+    SSDR_TRY(audio_stage(c, b, plan, nullptr));
+    const hipStream_t s = audio_stream(c, plan);
+    const hipMemcpyKind kind = out_is_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
+    if (pcm_out) HIP_TRY(hipMemcpyAsync(pcm_out, b.d_pcm, (size_t)c->n_ch * b.in_frames * SSDR_FRAME * 2, kind, s));
+    if (rssi_out) HIP_TRY(hipMemcpyAsync(rssi_out, b.d_rssi, (size_t)c->n_ch * b.in_frames * sizeof(float), kind, s));
+    if ((pcm_out || rssi_out) && !out_is_device) HIP_TRY(hipStreamSynchronize(s));
+    return audio_queued(c, plan);
+} SSDR_UNGUARD
+
+// What ssdr_run_chain does with batch `b`: which one-read kernel, if any, and whether the audio stage runs beside the waterfall
+// kernel.  Reads the ctx (its channel summary up to date: chan_summary) and the batch; writes nothing.
+static ChainPlan chain_plan(const ssdr_ctx *c, const Batch &b)
+{
     const uint32_t n_am = c->sum_paths[SSDR_PATH_AM_RAW];
     // the fused kernel covers the metric's configuration: every channel on the full-band AM path, N = 1, 12 kHz IQ, either line
     // rate (hop 1024, or hop 512 = the reference's 23 lines/s); from eight frames per call on (a wave sets a channel pair's
@@ -1499,8 +1525,8 @@ int ssdr_run_chain(ssdr_ctx *c, uint32_t *lines_ready, int *fused) SSDR_GUARD
     // (N > 1 and hop 512 are opt-in, ssdr_set_fused(ctx, 2): there the two stages side by side are faster)
     // (with float64 bins: the float64 counterpart, ssdr_fused_exact_am_kernel -- hop 1024 and N = 1 only)
     // (no one-read kernel takes a channel that blanks: ssdr_set_noise_blanker)
-    const bool eligible = c->nb_on == 0 && n_am == c->n_ch && c->decim == 1 && (hop512 || !(c->in_frames & 1u)) &&
-                          c->in_frames >= 8 &&
+    const bool eligible = c->nb_on == 0 && n_am == c->n_ch && c->decim == 1 && (hop512 || !(b.in_frames & 1u)) &&
+                          b.in_frames >= 8 &&
                           !c->concurrent && c->fused_grid != 0 && c->fused_enabled >= ((hop512 || c->n_avg > 1) ? 2 : 1) && c->zoom == 1 &&
                           (c->fused_enabled >= 2 || c->n_ch >= c->am_floor) &&
                           (!c->exact_bins || (!hop512 && c->n_avg == 1));
@@ -1508,15 +1534,27 @@ int ssdr_run_chain(ssdr_ctx *c, uint32_t *lines_ready, int *fused) SSDR_GUARD
     // read of the input.  By default where it is also the faster way (profiles/r06_ab_chain_ws.txt): when every channel runs the general path
     // (a filter to apply: the stages side by side are bound by the board's power cap there, and the second read of the input is energy);
     // for every batch it can take with ssdr_set_fused(ctx, 3) (full-band channels among them: 1 % slower than side by side, 39 % less HBM traffic)
-    const bool ws_can = c->nb_on == 0 && c->ws_grid != 0 && c->decim == 1 && !hop512 && !(c->in_frames & 1u) && !c->concurrent && c->zoom == 1 && !c->exact_bins;
+    const bool ws_can = c->nb_on == 0 && c->ws_grid != 0 && c->decim == 1 && !hop512 && !(b.in_frames & 1u) && !c->concurrent && c->zoom == 1 && !c->exact_bins;
     const bool eligible_ws = !eligible && ws_can &&
-                             (c->fused_enabled >= 3 || (c->fused_enabled >= 1 && c->sum_paths[SSDR_PATH_GENERAL] == c->n_ch && c->in_frames >= 8 &&
+                             (c->fused_enabled >= 3 || (c->fused_enabled >= 1 && c->sum_paths[SSDR_PATH_GENERAL] == c->n_ch && b.in_frames >= 8 &&
                                                         c->n_ch >= c->ws_floor));
-    if (fused) *fused = eligible ? 1 : (eligible_ws ? 2 : 0);
-    c->fuse_next = eligible || eligible_ws;
-    c->fuse_ws_next = eligible_ws;
-    {   // both stages or neither: what ssdr_run_wf and ssdr_run_audio would refuse is refused before either is launched
-        int rcv = validate_wf_batch(c);
+    const int one_read = eligible ? 1 : (eligible_ws ? 2 : 0);
+    // Everything else: the two stages side by side -- the audio stage on a second stream beside the waterfall kernel (one workgroup
+    // per CU then), each filling the issue slots the other leaves: +2.7 % on configs[3], +9 % on the full chain at hop 512
+    // (profiles/r04_ab_overlap.txt; there it beats the one-read kernel too, which is why that one is opt-in at hop 512)
+    // (not with the float64 waterfall kernel: it fills the CUs' LDS by itself, and beside it the audio stage only gets in the way:
+    //  3.61 ms one after the other, 3.75 ms side by side)
+    const bool overlap = !one_read && c->overlap_enabled && !c->concurrent && !c->exact_bins;
+    return ChainPlan{one_read, overlap || c->concurrent};         // (ssdr_set_concurrent: beside as well, the waterfall stage first)
+}
+
+static int run_chain(ssdr_ctx *c, Batch &b, uint32_t *lines_ready, int *fused)
+{
+    chan_summary(c);
+    const ChainPlan plan = chain_plan(c, b);
+    if (fused) *fused = plan.one_read;
+    {   // both stages or neither: what either stage would refuse is refused before one is launched
+        int rcv = validate_wf_batch(c, b);
         if (rcv == SSDR_OK && c->decim > 1) {
             chan_summary(c);
             if (c->sum_paths[SSDR_PATH_DELAY4] || c->sum_paths[SSDR_PATH_AM_RAW]) rcv = SSDR_ESTATE;
@@ -1525,40 +1563,35 @@ int ssdr_run_chain(ssdr_ctx *c, uint32_t *lines_ready, int *fused) SSDR_GUARD
             rcv = [&]() -> int { HIP_TRY(hipSetDevice(c->device)); return join_audio(c); }();
             if (rcv == SSDR_OK) rcv = ensure_chan_list(c, c->stream);
         }
-        if (rcv != SSDR_OK) { c->fuse_next = false; c->fuse_ws_next = false; if (fused) *fused = 0; return rcv; }
+        if (rcv != SSDR_OK) { if (fused) *fused = 0; return rcv; }
     }
-    // Everything else: the two stages side by side -- the audio stage on a second stream beside the waterfall kernel (one workgroup
-    // per CU then), each filling the issue slots the other leaves: +2.7 % on configs[3], +9 % on the full chain at hop 512
-    // (profiles/r04_ab_overlap.txt; there it beats the one-read kernel too, which is why that one is opt-in at hop 512)
-    // (not with the float64 waterfall kernel: it fills the CUs' LDS by itself, and beside it the audio stage only gets in the way:
-    //  3.61 ms one after the other, 3.75 ms side by side)
-    const bool overlap = !c->fuse_next && c->overlap_enabled && !c->concurrent && !c->exact_bins;
-    int rc;
-    if (overlap) {
+    if (plan.beside && !c->concurrent) {
         // the audio stage first: its stream waits for what is queued so far (the input), not for the waterfall kernel that follows
-        c->concurrent = true;
-        rc = ssdr_run_audio(c, nullptr, nullptr, 0);
-        if (rc == SSDR_OK) rc = ssdr_run_wf(c, nullptr, lines_ready, 0);
-        c->concurrent = false;                       // (audio_pending stays set: whoever needs the results or the input joins first)
-        if (rc == SSDR_OK && c->stream != c->own_stream) rc = join_audio(c);     // a caller's stream (ssdr_set_stream): what they order behind it covers both stages
-    } else {
-        // a one-read kernel: ssdr_run_wf only does the waterfall stage's bookkeeping and parks its arguments, ssdr_run_audio launches.  Should the
-        // launch fail, the bookkeeping goes back to where it stood: both stages or neither
-        const uint32_t phase0 = c->wf_phase, ready0 = c->wf_lines_ready;
-        const int acc0 = c->wf_acc_cur;
-        const bool one_read = c->fuse_next;
-        rc = ssdr_run_wf(c, nullptr, lines_ready, 0);
-        if (rc == SSDR_OK) {
-            rc = ssdr_run_audio(c, nullptr, nullptr, 0);
-            if (rc != SSDR_OK && one_read) {
-                c->wf_phase = phase0; c->wf_lines_ready = ready0; c->wf_acc_cur = acc0;
-                if (lines_ready) *lines_ready = 0;
-            }
-        }
+        SSDR_TRY(audio_stage(c, b, plan, nullptr));
+        SSDR_TRY(audio_queued(c, plan));             // (audio_pending stays set: whoever needs the results or the input joins first)
+        SSDR_TRY(wf_stage(c, b, plan, nullptr, lines_ready));
+        return c->stream != c->own_stream ? join_audio(c) : SSDR_OK;     // a caller's stream (ssdr_set_stream): what they order behind it covers both stages
     }
-    c->fuse_next = false;
-    c->fuse_ws_next = false;
-    return rc;
+    // a one-read kernel: the waterfall stage only does its bookkeeping and hands `wf` to the audio stage, which launches.  Should the
+    // launch fail, by a code or an exception, the bookkeeping goes back to where it stood: both stages or neither
+    struct Undo {
+        ssdr_ctx *c; Batch &b; uint32_t *lines; uint32_t phase, ready; int acc; bool armed;
+        ~Undo() { if (armed) { c->wf_phase = phase; b.wf_lines_ready = ready; c->wf_acc_cur = acc; if (lines) *lines = 0; } }
+    } undo{c, b, lines_ready, c->wf_phase, b.wf_lines_ready, c->wf_acc_cur, false};
+    SsdrWfArgs wf;
+    SSDR_TRY(wf_stage(c, b, plan, &wf, lines_ready));
+    undo.armed = plan.one_read != 0;
+    SSDR_TRY(audio_stage(c, b, plan, &wf));
+    SSDR_TRY(audio_queued(c, plan));
+    undo.armed = false;
+    return SSDR_OK;
+}
+
+int ssdr_run_chain(ssdr_ctx *c, uint32_t *lines_ready, int *fused) SSDR_GUARD
+{
+    if (!c) return SSDR_EINVAL;
+    if (!c->own.have_input) return SSDR_ESTATE;
+    return run_chain(c, c->own, lines_ready, fused);
 } SSDR_UNGUARD
 
 int ssdr_set_fused(ssdr_ctx *c, int on) SSDR_GUARD
@@ -1602,19 +1635,19 @@ int ssdr_audio_paths(ssdr_ctx *c, uint32_t counts[3]) SSDR_GUARD
 int ssdr_audio_iq(ssdr_ctx *c, int16_t *iq_out, int out_is_device) SSDR_GUARD
 {
     if (!c || !iq_out) return SSDR_EINVAL;
-    if (!c->iq_out_valid || !c->d_iq_out || c->audio_run_frames == 0) return SSDR_ESTATE;
+    if (!c->iq_out_valid || !c->d_iq_out || c->own.audio_run_frames == 0) return SSDR_ESTATE;
     HIP_TRY(hipSetDevice(c->device));
     SSDR_TRY(join_audio(c));
-    return copy_out(c, iq_out, c->d_iq_out, (size_t)c->n_ch * c->audio_run_frames * SSDR_FRAME * 4, out_is_device, kSyncHost);
+    return copy_out(c, iq_out, c->d_iq_out, (size_t)c->n_ch * c->own.audio_run_frames * SSDR_FRAME * 4, out_is_device, kSyncHost);
 } SSDR_UNGUARD
 
 int ssdr_audio_flags(ssdr_ctx *c, uint8_t *flags_out, int out_is_device) SSDR_GUARD
 {
     if (!c || !flags_out) return SSDR_EINVAL;
-    if (!c->d_flags || c->audio_run_frames == 0 || c->flags_frames < c->audio_run_frames) return SSDR_ESTATE;
+    if (!c->own.d_flags || c->own.audio_run_frames == 0 || c->own.flags_frames < c->own.audio_run_frames) return SSDR_ESTATE;
     HIP_TRY(hipSetDevice(c->device));
     SSDR_TRY(join_audio(c));
-    return copy_out(c, flags_out, c->d_flags, (size_t)c->n_ch * c->audio_run_frames, out_is_device, kSyncHost);
+    return copy_out(c, flags_out, c->own.d_flags, (size_t)c->n_ch * c->own.audio_run_frames, out_is_device, kSyncHost);
 } SSDR_UNGUARD
 
 // ---- impulse noise blanker ---------------------------------------------------------------------------------------------
@@ -1728,6 +1761,35 @@ static int ensure_play(ssdr_ctx *c)
 }
 
 static int wfdata_feed(ssdr_ctx *c, const float *color, uint32_t lines);
+
+// ---- the post kernels' launches, one each for the entry points and the feed's post step (buffers, uploads, read-backs, syncs: theirs)
+// spectrum_db2col of `lines` lines at `wf` under the display state at `chans`, the colours to `color`: of the ctx's channels (its
+// selection, and its wf_data fed where there is one), or -- `single` -- of one line that is nobody's
+static int db2col_launch(ssdr_ctx *c, const int16_t *wf, uint32_t lines, uint32_t n_avg, ssdr_db2col_chan *chans, float *color, bool single = false)
+{
+    SsdrDb2colArgs a;
+    a.wf = wf; a.n_lines = lines; a.n_avg = n_avg; a.chans = chans; a.color = color;
+    a.n_ch = single ? 1 : c->n_ch; a.sel = single ? nullptr : c->d_post_sel; a.n_sel = single ? 1 : c->n_post;
+    SSDR_TRY(timed_begin(c));
+    HIP_TRY(ssdr_launch_db2col(a, c->stream));
+    SSDR_TRY(timed_end(c, SSDR_K_DB2COL));
+    if (c->d_wfdata && !single) SSDR_TRY(wfdata_feed(c, color, lines));
+    return SSDR_OK;
+}
+// play_buffer of the `nf` frames of PCM at `pcm` under the settings uploaded to d_play, to `out` (and `mono`, unless null)
+static int play_launch(ssdr_ctx *c, const int16_t *pcm, uint32_t nf, int16_t *out, int16_t *mono)
+{
+    const bool wide = c->kiwi_rate != SSDR_RATE;                  // SAMPLE_RATIO % 1 != 0 (:1125)
+    if (c->d_post_sel && !wide)          // the channels outside the selection keep their history
+        HIP_TRY(hipMemcpyAsync(c->d_play_hist_alt, c->d_play_hist, (size_t)c->n_ch * 8 * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
+    SsdrPlayArgs a;
+    a.pcm = pcm; a.n_ch = c->n_ch; a.n_frames = nf; a.chans = c->d_play; a.taps = c->d_play_taps; a.rs_taps = c->d_play_rs_taps;
+    a.hist = c->d_play_hist; a.hist_out = c->d_play_hist_alt; a.sel = c->d_post_sel; a.n_sel = c->n_post; a.out = out; a.mono = mono;
+    SSDR_TRY(timed_begin(c));
+    HIP_TRY(wide ? ssdr_launch_play_rs(a, c->stream) : ssdr_launch_play(a, c->stream));
+    if (!wide) std::swap(c->d_play_hist, c->d_play_hist_alt);            // (the 64/27 branch carries no history)
+    return timed_end(c, SSDR_K_PLAY);
+}
 
 // ---- pipelined host feed ------------------------------------------------------------------------------------
 // Three streams: host->device copy of batch k+1, the two kernels of batch k, device->host copy of batch k-1.
@@ -1871,56 +1933,29 @@ static int feed_submit_impl(ssdr_ctx *c, const void *host_in)
         HIP_TRY(ssdr_launch_iqwire(w, c->stream));
         SSDR_TRY(timed_end(c, SSDR_K_WIRE));
     }
-    // run the two kernels on this slot's buffers: the ctx's own batch pointers are parked meanwhile
-    const uint32_t *k_iq = c->d_iq; const uint32_t k_frames = c->in_frames; const bool k_have = c->have_input;
-    int16_t *k_wf = c->d_wf_out; const size_t k_wf_lines = c->wf_out_lines; const uint32_t k_ready = c->wf_lines_ready;
-    int16_t *k_pcm = c->d_pcm; float *k_rssi = c->d_rssi; const size_t k_af = c->audio_frames; const uint32_t k_arf = c->audio_run_frames;
-    uint8_t *k_flags = c->d_flags; const size_t k_ff = c->flags_frames;
-    c->d_iq = s.d_in; c->in_frames = nf; c->have_input = true;
-    c->d_wf_out = s.d_wf; c->wf_out_lines = c->hop == SSDR_NFFT / 2 ? nf : nf / 2;
-    c->d_pcm = s.d_pcm; c->d_rssi = s.d_rssi; c->audio_frames = nf;
-    c->d_flags = s.d_flags; c->flags_frames = nf;
+    // the two stages on this slot's buffers: its batch (the ctx's own is not touched)
+    Batch b;
+    b.d_iq = s.d_in; b.in_frames = nf; b.have_input = true;
+    b.d_wf_out = s.d_wf; b.wf_out_lines = c->hop == SSDR_NFFT / 2 ? nf : nf / 2;
+    b.d_pcm = s.d_pcm; b.d_rssi = s.d_rssi; b.audio_frames = nf;
+    b.d_flags = s.d_flags; b.flags_frames = nf;
     uint32_t lines = 0;
     s.n_avg = c->n_avg;
-    int rc = ssdr_run_chain(c, &lines, nullptr);           // the fused superframe kernel where the batch allows it
-    if (rc == SSDR_OK) rc = join_audio(c);                  // (or the two stages side by side: what follows reads both results)
-    if (rc == SSDR_OK && c->feed_post) rc = [&]() -> int {
+    SSDR_TRY(run_chain(c, b, &lines, nullptr));            // the fused superframe kernel where the batch allows it
+    SSDR_TRY(join_audio(c));                                // (or the two stages side by side: what follows reads both results)
+    if (c->feed_post) { s.n_post = c->n_post; s.has_mono = c->n_post && c->recording; }
+    if (c->feed_post && c->n_post) {
         // spectrum_db2col of this batch's lines and play_buffer of its frames, on the slot's buffers, in batch order
-        s.n_post = c->n_post;
-        s.has_mono = false;
-        if (c->n_post == 0) return SSDR_OK;                  // ssdr_set_post_channels with an empty list: nobody is looking
+        // (not with an empty list from ssdr_set_post_channels: nobody is looking)
         if (lines) {
             memcpy(s.h_dbchan, c->feed_dbchan.data(), (size_t)c->n_post * sizeof(ssdr_db2col_chan));
             HIP_TRY(hipMemcpyAsync(s.d_dbchan, s.h_dbchan, (size_t)c->n_post * sizeof(ssdr_db2col_chan), hipMemcpyHostToDevice, c->stream));
-            SsdrDb2colArgs d;
-            d.wf = s.d_wf; d.n_ch = c->n_ch; d.n_lines = lines; d.n_avg = c->n_avg; d.chans = s.d_dbchan; d.color = s.d_color;
-            d.sel = c->d_post_sel; d.n_sel = c->n_post;
-            SSDR_TRY(timed_begin(c));
-            HIP_TRY(ssdr_launch_db2col(d, c->stream));
-            SSDR_TRY(timed_end(c, SSDR_K_DB2COL));
-            if (c->d_wfdata) SSDR_TRY(wfdata_feed(c, s.d_color, lines));
+            SSDR_TRY(db2col_launch(c, s.d_wf, lines, c->n_avg, s.d_dbchan, s.d_color));
         }
         memcpy(s.h_playchan, c->feed_playchan.data(), (size_t)c->n_post * sizeof(ssdr_play_chan));
         HIP_TRY(hipMemcpyAsync(c->d_play, s.h_playchan, (size_t)c->n_post * sizeof(ssdr_play_chan), hipMemcpyHostToDevice, c->stream));
-        SsdrPlayArgs pa;
-        pa.pcm = s.d_pcm; pa.n_ch = c->n_ch; pa.n_frames = nf; pa.chans = c->d_play; pa.taps = c->d_play_taps; pa.hist = c->d_play_hist;
-        pa.hist_out = c->d_play_hist_alt; pa.sel = c->d_post_sel; pa.n_sel = c->n_post;
-        s.n_post = c->n_post;
-        if (c->d_post_sel && c->kiwi_rate == SSDR_RATE)      // the channels outside the selection keep their history
-            HIP_TRY(hipMemcpyAsync(c->d_play_hist_alt, c->d_play_hist, (size_t)c->n_ch * 8 * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
-        pa.out = s.d_play; pa.rs_taps = c->d_play_rs_taps; pa.mono = c->recording ? s.d_mono : nullptr;
-        s.has_mono = c->recording;
-        SSDR_TRY(timed_begin(c));
-        HIP_TRY(c->kiwi_rate != SSDR_RATE ? ssdr_launch_play_rs(pa, c->stream) : ssdr_launch_play(pa, c->stream));
-        if (c->kiwi_rate == SSDR_RATE) std::swap(c->d_play_hist, c->d_play_hist_alt);
-        SSDR_TRY(timed_end(c, SSDR_K_PLAY));
-        return SSDR_OK;
-    }();
-    c->d_iq = k_iq; c->in_frames = k_frames; c->have_input = k_have;
-    c->d_wf_out = k_wf; c->wf_out_lines = k_wf_lines; c->wf_lines_ready = k_ready;
-    c->d_pcm = k_pcm; c->d_rssi = k_rssi; c->audio_frames = k_af; c->audio_run_frames = k_arf;
-    c->d_flags = k_flags; c->flags_frames = k_ff;
-    if (rc != SSDR_OK) return rc;
+        SSDR_TRY(play_launch(c, s.d_pcm, nf, s.d_play, c->recording ? s.d_mono : nullptr));
+    }
     s.lines = lines;
     // what goes back: every channel's rows, or (SSDR_FEED_LAZY_OUT) the selected channels' rows gathered into compact ones
     const int16_t *o_wf = s.d_wf, *o_pcm = s.d_pcm;
@@ -2059,8 +2094,8 @@ int ssdr_feed_collect_lazy(ssdr_ctx *c, uint32_t *n_sel, int16_t **d_wf_sum, int
 int ssdr_wf_device(ssdr_ctx *c, int16_t **ptr, uint32_t *lines) SSDR_GUARD
 {
     if (!c || !ptr) return SSDR_EINVAL;
-    *ptr = c->d_wf_out;
-    if (lines) *lines = c->wf_lines_ready;
+    *ptr = c->own.d_wf_out;
+    if (lines) *lines = c->own.wf_lines_ready;
     return SSDR_OK;
 } SSDR_UNGUARD
 
@@ -2079,8 +2114,8 @@ int ssdr_audio_device(ssdr_ctx *c, int16_t **pcm, float **rssi) SSDR_GUARD
     if (!c) return SSDR_EINVAL;
     HIP_TRY(hipSetDevice(c->device));
     SSDR_TRY(join_audio(c));       // a consumer ordered behind the ctx stream sees the audio stage too
-    if (pcm) *pcm = c->d_pcm;
-    if (rssi) *rssi = c->d_rssi;
+    if (pcm) *pcm = c->own.d_pcm;
+    if (rssi) *rssi = c->own.d_rssi;
     return SSDR_OK;
 } SSDR_UNGUARD
 
@@ -2221,7 +2256,7 @@ int ssdr_checkpoint_load(ssdr_ctx *c, const void *blob, uint64_t bytes) SSDR_GUA
         HIP_TRY(hipMemcpyAsync(c->d_wf_tail, p + n * 8 * sizeof(double), n * (SSDR_NFFT / 2) * 4, h2d, c->stream));
     memcpy(c->h_params.data(), p + n * 8 * sizeof(double) + n * (SSDR_NFFT / 2) * 4, n * sizeof(ssdr_chan_params));
     c->decim = h.decim;
-    c->have_input = false;                                  // a batch pushed before the load belongs to the old streams
+    c->own.have_input = false;                              // a batch pushed before the load belongs to the old streams
     HIP_TRY(hipStreamSynchronize(c->stream));
     c->n_avg = h.n_avg;
     c->wf_phase = h.wf_phase;
@@ -2301,27 +2336,15 @@ int ssdr_set_post_channels(ssdr_ctx *c, const uint32_t *channels, uint32_t count
 int ssdr_run_db2col(ssdr_ctx *c, ssdr_db2col_chan *chans, float *color_out, int out_is_device) SSDR_GUARD
 {
     if (!c || !chans) return SSDR_EINVAL;
-    if (!c->d_wf_out && c->wf_lines_ready) return SSDR_ESTATE;
+    if (!c->own.d_wf_out && c->own.wf_lines_ready) return SSDR_ESTATE;
     HIP_TRY(hipSetDevice(c->device));
-    const uint32_t lines = c->wf_lines_ready;
+    const uint32_t lines = c->own.wf_lines_ready;
     if (!c->d_db2col) HIP_TRY(hipMalloc(&c->d_db2col, (size_t)c->n_ch * sizeof(ssdr_db2col_chan)));
     if (lines == 0) return SSDR_OK;
     SSDR_TRY(grow(c, c->d_color, c->color_lines, lines, (size_t)c->n_ch * SSDR_NFFT * sizeof(float)));
     if (c->n_post == 0) return SSDR_OK;                       // an empty selection: nobody is looking
     HIP_TRY(hipMemcpyAsync(c->d_db2col, chans, (size_t)c->n_post * sizeof(ssdr_db2col_chan), hipMemcpyHostToDevice, c->stream));
-    SsdrDb2colArgs a;
-    a.wf = c->d_wf_out;
-    a.n_ch = c->n_ch;
-    a.n_lines = lines;
-    a.n_avg = c->n_avg;
-    a.chans = c->d_db2col;
-    a.color = c->d_color;
-    a.sel = c->d_post_sel;
-    a.n_sel = c->n_post;
-    SSDR_TRY(timed_begin(c));
-    HIP_TRY(ssdr_launch_db2col(a, c->stream));
-    SSDR_TRY(timed_end(c, SSDR_K_DB2COL));
-    if (c->d_wfdata) SSDR_TRY(wfdata_feed(c, c->d_color, lines));
+    SSDR_TRY(db2col_launch(c, c->own.d_wf_out, lines, c->n_avg, c->d_db2col, c->d_color));
     HIP_TRY(hipMemcpyAsync(chans, c->d_db2col, (size_t)c->n_post * sizeof(ssdr_db2col_chan), hipMemcpyDeviceToHost, c->stream));
     if (color_out) SSDR_TRY(copy_out(c, color_out, c->d_color, (size_t)lines * c->n_post * SSDR_NFFT * sizeof(float), out_is_device, kSyncLater));
     HIP_TRY(hipStreamSynchronize(c->stream));
@@ -2339,18 +2362,7 @@ int ssdr_db2col_line(ssdr_ctx *c, const int16_t *wf_sum, uint32_t n_avg, ssdr_db
     }
     HIP_TRY(hipMemcpyAsync(c->d_line1, wf_sum, SSDR_NFFT * sizeof(int16_t), hipMemcpyHostToDevice, c->stream));
     HIP_TRY(hipMemcpyAsync(c->d_dbchan1, chan, sizeof(ssdr_db2col_chan), hipMemcpyHostToDevice, c->stream));
-    SsdrDb2colArgs a;
-    a.wf = c->d_line1;
-    a.n_ch = 1;
-    a.n_lines = 1;
-    a.n_avg = n_avg;
-    a.chans = c->d_dbchan1;
-    a.color = c->d_color1;
-    a.sel = nullptr;
-    a.n_sel = 1;
-    SSDR_TRY(timed_begin(c));
-    HIP_TRY(ssdr_launch_db2col(a, c->stream));
-    SSDR_TRY(timed_end(c, SSDR_K_DB2COL));
+    SSDR_TRY(db2col_launch(c, c->d_line1, 1, n_avg, c->d_dbchan1, c->d_color1, true));
     HIP_TRY(hipMemcpyAsync(chan, c->d_dbchan1, sizeof(ssdr_db2col_chan), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipMemcpyAsync(color_out, c->d_color1, SSDR_NFFT * sizeof(float), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
@@ -2363,11 +2375,12 @@ int ssdr_output_checksum(ssdr_ctx *c, uint64_t sums[3]) SSDR_GUARD
     HIP_TRY(hipSetDevice(c->device));
     SSDR_TRY(join_audio(c));
     HIP_TRY(hipMemsetAsync(c->d_scratch, 0, 24, c->stream));
-    if (c->d_wf_out && c->wf_lines_ready)
-        HIP_TRY(ssdr_launch_checksum(c->d_wf_out, (uint64_t)c->wf_lines_ready * c->n_ch * (SSDR_NFFT / 2), c->d_scratch, c->stream));
-    if (c->d_pcm && c->audio_run_frames) {
-        HIP_TRY(ssdr_launch_checksum(c->d_pcm, (uint64_t)c->n_ch * c->audio_run_frames * (SSDR_FRAME / 2), c->d_scratch + 1, c->stream));
-        HIP_TRY(ssdr_launch_checksum(c->d_rssi, (uint64_t)c->n_ch * c->audio_run_frames, c->d_scratch + 2, c->stream));
+    const Batch &b = c->own;
+    if (b.d_wf_out && b.wf_lines_ready)
+        HIP_TRY(ssdr_launch_checksum(b.d_wf_out, (uint64_t)b.wf_lines_ready * c->n_ch * (SSDR_NFFT / 2), c->d_scratch, c->stream));
+    if (b.d_pcm && b.audio_run_frames) {
+        HIP_TRY(ssdr_launch_checksum(b.d_pcm, (uint64_t)c->n_ch * b.audio_run_frames * (SSDR_FRAME / 2), c->d_scratch + 1, c->stream));
+        HIP_TRY(ssdr_launch_checksum(b.d_rssi, (uint64_t)c->n_ch * b.audio_run_frames, c->d_scratch + 2, c->stream));
     }
     unsigned long long v[3] = {0, 0, 0};
     HIP_TRY(hipMemcpyAsync(v, c->d_scratch, 24, hipMemcpyDeviceToHost, c->stream));
@@ -2466,7 +2479,7 @@ int ssdr_run_trace(ssdr_ctx *c, uint32_t t_avg, uint32_t spectrum_height, double
 int ssdr_run_smeter(ssdr_ctx *c, ssdr_smeter_chan *chans, const double *rssi_in, double fps) SSDR_GUARD
 {
     if (!c || !chans || !(fps > 0.0)) return SSDR_EINVAL;
-    if (!rssi_in && (!c->d_rssi || c->audio_frames == 0 || c->audio_run_frames == 0)) return SSDR_ESTATE;
+    if (!rssi_in && (!c->own.d_rssi || c->own.audio_frames == 0 || c->own.audio_run_frames == 0)) return SSDR_ESTATE;
     HIP_TRY(hipSetDevice(c->device));
     SSDR_TRY(join_audio(c));
     if (!c->d_smeter) {
@@ -2477,10 +2490,10 @@ int ssdr_run_smeter(ssdr_ctx *c, ssdr_smeter_chan *chans, const double *rssi_in,
     if (rssi_in) HIP_TRY(hipMemcpyAsync(c->d_smeter_in, rssi_in, (size_t)c->n_ch * sizeof(double), hipMemcpyHostToDevice, c->stream));
     SsdrSmeterArgs a;
     a.chans = c->d_smeter;
-    a.rssi = c->d_rssi;
+    a.rssi = c->own.d_rssi;
     a.rssi_in = rssi_in ? c->d_smeter_in : nullptr;
     a.n_ch = c->n_ch;
-    a.n_frames = c->audio_run_frames;
+    a.n_frames = c->own.audio_run_frames;
     a.fps = fps;
     SSDR_TRY(timed_begin(c));
     HIP_TRY(ssdr_launch_smeter(a, c->stream));
@@ -2504,7 +2517,7 @@ int ssdr_set_kiwi_rate(ssdr_ctx *c, uint32_t kiwi_rate) SSDR_GUARD
     c->de_dirty = true;                                           // the de-emphasis coefficients are the rate's
     int rc = ssdr_set_params(c, 0, c->n_ch, all.data());
     if (rc == SSDR_OK) {
-        c->have_input = false;
+        c->own.have_input = false;
         rc = ssdr_reset_state(c, 0, c->n_ch);
         if (rc == SSDR_OK) rc = zoom_restart(c, 0, c->n_ch);
     }
@@ -2526,39 +2539,20 @@ int ssdr_playbuffer_frame_len(ssdr_ctx *c, uint32_t *samples_per_frame) SSDR_GUA
 int ssdr_run_playbuffer(ssdr_ctx *c, const ssdr_play_chan *chans, int16_t *out, int out_is_device) SSDR_GUARD
 {
     if (!c || !chans) return SSDR_EINVAL;
-    if (!c->d_pcm || c->audio_run_frames == 0 || c->audio_frames < c->audio_run_frames) return SSDR_ESTATE;
+    if (!c->own.d_pcm || c->own.audio_run_frames == 0 || c->own.audio_frames < c->own.audio_run_frames) return SSDR_ESTATE;
     HIP_TRY(hipSetDevice(c->device));
     SSDR_TRY(join_audio(c));
-    const uint32_t nf = c->audio_run_frames;
-    const bool wide = c->kiwi_rate != SSDR_RATE;                  // SAMPLE_RATIO % 1 != 0 (:1125)
-    const size_t per_frame = wide ? (size_t)SSDR_RS_OUT_PER_FRAME : 2048;
+    const uint32_t nf = c->own.audio_run_frames;
+    const size_t per_frame = c->kiwi_rate != SSDR_RATE ? (size_t)SSDR_RS_OUT_PER_FRAME : 2048;
     SSDR_TRY(ensure_play(c));
     // (sized for the longer (x4) form, either path fits)
     SSDR_TRY(grow(c, c->d_play_out, c->play_frames, nf, (size_t)c->n_ch * 2048 * 2 * sizeof(int16_t)));
     if (c->recording) SSDR_TRY(grow(c, c->d_play_mono, c->play_mono_frames, nf, (size_t)c->n_ch * 2048 * sizeof(int16_t)));
     if (c->n_post == 0) { c->play_run_frames = 0; return SSDR_OK; }
     HIP_TRY(hipMemcpyAsync(c->d_play, chans, (size_t)c->n_post * sizeof(ssdr_play_chan), hipMemcpyHostToDevice, c->stream));
-    if (c->d_post_sel && !wide)          // the channels outside the selection keep their history
-        HIP_TRY(hipMemcpyAsync(c->d_play_hist_alt, c->d_play_hist, (size_t)c->n_ch * 8 * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
-    SsdrPlayArgs a;
-    a.pcm = c->d_pcm;
-    a.n_ch = c->n_ch;
-    a.n_frames = nf;
-    a.chans = c->d_play;
-    a.taps = c->d_play_taps;
-    a.hist = c->d_play_hist;
-    a.hist_out = c->d_play_hist_alt;
-    a.sel = c->d_post_sel;
-    a.n_sel = c->n_post;
-    a.out = c->d_play_out;
-    a.rs_taps = c->d_play_rs_taps;
-    a.mono = c->recording ? c->d_play_mono : nullptr;
     c->play_run_frames = c->recording ? nf : 0;
     c->play_run_len = (uint32_t)per_frame;
-    SSDR_TRY(timed_begin(c));
-    HIP_TRY(wide ? ssdr_launch_play_rs(a, c->stream) : ssdr_launch_play(a, c->stream));
-    if (!wide) std::swap(c->d_play_hist, c->d_play_hist_alt);            // (the 64/27 branch carries no history)
-    SSDR_TRY(timed_end(c, SSDR_K_PLAY));
+    SSDR_TRY(play_launch(c, c->own.d_pcm, nf, c->d_play_out, c->recording ? c->d_play_mono : nullptr));
     if (out) SSDR_TRY(copy_out(c, out, c->d_play_out, (size_t)c->n_post * nf * per_frame * 2 * sizeof(int16_t), out_is_device, kSyncLater));
     HIP_TRY(hipStreamSynchronize(c->stream));
     return SSDR_OK;
@@ -2612,9 +2606,7 @@ int ssdr_push_iq_wire(ssdr_ctx *c, const uint8_t *bodies, uint32_t n_frames, flo
     if (rssi_out)
         HIP_TRY(hipMemcpyAsync(rssi_out, c->d_wire_rssi, (size_t)c->n_ch * n_frames * sizeof(float), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
-    c->d_iq = c->d_iq_own;
-    c->in_frames = n_frames;
-    c->have_input = true;
+    own_input(c, c->d_iq_own, n_frames);
     return SSDR_OK;
 } SSDR_UNGUARD
 
@@ -2931,10 +2923,10 @@ int ssdr_set_wf_lines(ssdr_ctx *c, const int16_t *wf_sum, uint32_t lines) SSDR_G
 {
     if (!c || !wf_sum || lines == 0) return SSDR_EINVAL;
     HIP_TRY(hipSetDevice(c->device));
-    SSDR_TRY(ensure_wf_out(c, lines));
-    HIP_TRY(hipMemcpyAsync(c->d_wf_out, wf_sum, (size_t)lines * c->n_ch * SSDR_NFFT * 2, hipMemcpyHostToDevice, c->stream));
+    SSDR_TRY(ensure_wf_out(c, c->own, lines));
+    HIP_TRY(hipMemcpyAsync(c->own.d_wf_out, wf_sum, (size_t)lines * c->n_ch * SSDR_NFFT * 2, hipMemcpyHostToDevice, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
-    c->wf_lines_ready = lines;
+    c->own.wf_lines_ready = lines;
     return SSDR_OK;
 } SSDR_UNGUARD
 
@@ -2943,10 +2935,10 @@ int ssdr_set_pcm(ssdr_ctx *c, const int16_t *pcm, uint32_t n_frames) SSDR_GUARD
     if (!c || !pcm || n_frames == 0) return SSDR_EINVAL;
     HIP_TRY(hipSetDevice(c->device));
     SSDR_TRY(drain_audio(c));
-    SSDR_TRY(ensure_audio_out(c, n_frames));
-    HIP_TRY(hipMemcpyAsync(c->d_pcm, pcm, (size_t)c->n_ch * n_frames * SSDR_FRAME * 2, hipMemcpyHostToDevice, c->stream));
+    SSDR_TRY(ensure_audio_out(c, c->own, n_frames));
+    HIP_TRY(hipMemcpyAsync(c->own.d_pcm, pcm, (size_t)c->n_ch * n_frames * SSDR_FRAME * 2, hipMemcpyHostToDevice, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
-    c->audio_run_frames = n_frames;          // the input batch (d_iq / in_frames / have_input) is not touched
+    c->own.audio_run_frames = n_frames;      // the input batch (d_iq / in_frames / have_input) is not touched
     return SSDR_OK;
 } SSDR_UNGUARD
 

@@ -8,7 +8,7 @@
 //   harness <libssdr.so> cpu      entry points that need no GPU, every library allocation failing
 //   harness <libssdr.so> gpu      fault-injection sweep: for every scenario, fail allocation 1, 2, 3, ... until the call runs
 //                                 through; each time the call must RETURN (SSDR_ENOMEM), the ctx must stay usable and a
-//                                 re-run of the scenario without faults must give SSDR_OK
+//                                 re-run of the scenario without faults must give SSDR_OK; then the two scenarios of run_after_failures
 // Prints one line per scenario and "PASS" / "FAIL"; exit code 0 / 1.  A crossed C boundary would be std::terminate = SIGABRT.
 #include "../include/ssdr.h"
 #include <cstdio>
@@ -56,6 +56,7 @@ SYM(ssdr_checkpoint_load); SYM(ssdr_set_post_channels); SYM(ssdr_set_decimation)
 SYM(ssdr_set_wf_zoom); SYM(ssdr_set_exact_bins); SYM(ssdr_feed_open); SYM(ssdr_feed_close); SYM(ssdr_output_checksum);
 SYM(ssdr_set_wfdata_rows); SYM(ssdr_strerror); SYM(ssdr_version); SYM(ssdr_last_hip_error); SYM(ssdr_set_wf_center);
 SYM(ssdr_run_db2col); SYM(ssdr_run_playbuffer); SYM(ssdr_set_averaging); SYM(ssdr_set_hop);
+SYM(ssdr_set_chain_floors); SYM(ssdr_feed_slot); SYM(ssdr_feed_submit); SYM(ssdr_feed_collect);
 
 static int g_bad = 0;
 #define CHECK(cond, ...) do { if (!(cond)) { printf("  FAILED: " __VA_ARGS__); printf("\n"); g_bad++; } } while (0)
@@ -108,6 +109,90 @@ static int run_cpu()
     g_fail_at = 0;
     printf("cpu: ctx-free entry points under failing allocations: %s\n", g_bad ? "FAIL" : "ok");
     return g_bad;
+}
+
+// What a failed call leaves behind, seen by the calls that follow it (not by a re-run of the same call).  Two contexts of default
+// AM channels with no channel-count floor, so that an 8-frame ssdr_run_chain takes the one-read kernel: `c` meets the failures,
+// `ctl` sees the same input and the same calls that succeed, never a failure.
+static void run_after_failures()
+{
+    ssdr_ctx *c = nullptr, *ctl = nullptr;
+    CHECK(p_ssdr_create(0, N_CH, SSDR_NFFT, SSDR_FRAME, &c) == SSDR_OK && p_ssdr_create(0, N_CH, SSDR_NFFT, SSDR_FRAME, &ctl) == SSDR_OK, "create");
+    if (!c || !ctl) return;
+    ssdr_chan_params am;
+    p_ssdr_default_params(SSDR_MODE_AM, &am);
+    const std::vector<ssdr_chan_params> params(N_CH, am);
+    for (ssdr_ctx *x : {c, ctl}) CHECK(p_ssdr_set_chain_floors(x, 0, 0) == SSDR_OK, "set_chain_floors");
+    uint64_t own[3] = {0, 0, 0};
+    // (1) no plan survives a failed ssdr_run_chain: ssdr_set_params makes the channel list dirty, the chain fails at allocation k; then
+    // ssdr_run_wf alone and ssdr_run_audio alone run their own kernels on the same input and give what they give on `ctl`
+    for (long k = 1;; k++) {
+        int rc = SSDR_OK;
+        for (ssdr_ctx *x : {c, ctl}) {
+            if (rc == SSDR_OK) rc = p_ssdr_reset_state(x, 0, N_CH);           // both streams (and the synthesiser) start over
+            if (rc == SSDR_OK) rc = p_ssdr_set_params(x, 0, N_CH, params.data());
+            if (rc == SSDR_OK) rc = p_ssdr_synth_iq(x, N_FRAMES, 31, 0);
+        }
+        CHECK(rc == SSDR_OK, "run_chain, then the stages alone: setting up %d (%s)", rc, p_ssdr_last_hip_error());
+        uint32_t lines = 0; int fused = -1;
+        g_seen = 0; g_thrown = 0; g_fail_at = k;
+        rc = p_ssdr_run_chain(c, &lines, &fused);
+        g_fail_at = 0;
+        if (g_thrown == 0) {
+            CHECK(rc == SSDR_OK && fused == 1 && lines, "undisturbed ssdr_run_chain: %d, fused %d, %u lines (the one-read kernel was meant)", rc, fused, lines);
+            printf("%-28s %ld allocation(s) failed in turn, the stages alone then ran as on an untouched ctx\n", "run_chain, then run_wf/audio", k - 1);
+            break;
+        }
+        CHECK(rc == SSDR_ENOMEM, "ssdr_run_chain: allocation %ld failed, the call returned %d", k, rc);
+        uint64_t sums[2][3] = {{0, 0, 0}, {1, 1, 1}};
+        int i = 0;
+        for (ssdr_ctx *x : {c, ctl}) {
+            uint32_t n = 0;
+            rc = p_ssdr_run_wf(x, nullptr, &n, 0);
+            CHECK(rc == SSDR_OK && n, "after allocation %ld: ssdr_run_wf alone returns %d with %u lines", k, rc, n);
+            rc = p_ssdr_run_audio(x, nullptr, nullptr, 0);
+            CHECK(rc == SSDR_OK, "after allocation %ld: ssdr_run_audio alone returns %d (%s)", k, rc, p_ssdr_last_hip_error());
+            if (rc == SSDR_OK) rc = p_ssdr_sync(x);
+            if (rc == SSDR_OK) rc = p_ssdr_output_checksum(x, sums[i++]);
+            CHECK(rc == SSDR_OK, "after allocation %ld: sync / checksum %d", k, rc);
+        }
+        CHECK(memcmp(sums[0], sums[1], sizeof sums[0]) == 0, "after allocation %ld: the stages alone give other results than on the control ctx", k);
+        if (k > 64) { CHECK(false, "ssdr_run_chain: more than 64 allocations in one call?"); break; }
+    }
+    // (2) a failed ssdr_feed_submit leaves the ctx's own batch (the chain's, above) alone: an open feed of 2 frames, depth 2
+    CHECK(p_ssdr_sync(c) == SSDR_OK && p_ssdr_output_checksum(c, own) == SSDR_OK, "own batch");
+    CHECK(p_ssdr_feed_open(c, 2, 2, 0) == SSDR_OK, "feed_open (%s)", p_ssdr_last_hip_error());
+    bool taken = false;
+    for (long k = 1;; k++) {
+        void *slot = nullptr;
+        int rc = p_ssdr_set_params(c, 0, N_CH, params.data());                // the submit rebuilds the channel list (host vectors)
+        if (rc == SSDR_OK && !taken) rc = p_ssdr_feed_slot(c, &slot);
+        CHECK(rc == SSDR_OK, "feed_slot %d", rc);
+        if (slot) { taken = true; for (size_t i = 0; i < (size_t)N_CH * 2 * SSDR_FRAME * 2; i++) ((int16_t *)slot)[i] = (int16_t)((i * 2654435761u) >> 20); }
+        g_seen = 0; g_thrown = 0; g_fail_at = k;
+        rc = p_ssdr_feed_submit(c);
+        g_fail_at = 0;
+        const bool failed = g_thrown != 0;
+        if (failed) {
+            CHECK(rc == SSDR_ENOMEM, "ssdr_feed_submit: allocation %ld failed, the call returned %d", k, rc);
+            uint64_t now[3] = {1, 1, 1};
+            CHECK(p_ssdr_output_checksum(c, now) == SSDR_OK && memcmp(now, own, sizeof own) == 0, "after allocation %ld of ssdr_feed_submit the own batch reads differently", k);
+            rc = p_ssdr_feed_submit(c);                                       // the slot is still the caller's: the same submit goes through
+        }
+        CHECK(rc == SSDR_OK, "ssdr_feed_submit%s: %d (%s)", failed ? " after a failure" : "", rc, p_ssdr_last_hip_error());
+        if (rc == SSDR_OK) { taken = false; CHECK(p_ssdr_feed_collect(c, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr) == SSDR_OK, "feed_collect"); }
+        if (!failed || k > 64) {
+            CHECK(!failed, "ssdr_feed_submit: more than 64 allocations in one call?");
+            printf("%-28s %ld allocation(s) failed in turn, the own batch untouched\n", "ssdr_feed_submit", k - 1);
+            break;
+        }
+    }
+    uint64_t now[3] = {1, 1, 1};
+    CHECK(p_ssdr_output_checksum(c, now) == SSDR_OK && memcmp(now, own, sizeof own) == 0, "the own batch reads differently after the feed's batches");
+    CHECK(p_ssdr_feed_close(c) == SSDR_OK, "feed_close");
+    CHECK(p_ssdr_output_checksum(c, now) == SSDR_OK && memcmp(now, own, sizeof own) == 0, "the own batch reads differently after ssdr_feed_close");
+    p_ssdr_destroy(c);
+    p_ssdr_destroy(ctl);
 }
 
 static int run_gpu()
@@ -204,6 +289,7 @@ static int run_gpu()
     }
     CHECK(memcmp(s1, s2, sizeof s1) == 0, "two fresh runs of the same input disagree after the sweeps");
     p_ssdr_destroy(c);
+    run_after_failures();
     return g_bad;
 }
 
@@ -223,6 +309,7 @@ int main(int argc, char **argv)
     LOAD(ssdr_set_wf_zoom); LOAD(ssdr_set_exact_bins); LOAD(ssdr_feed_open); LOAD(ssdr_feed_close); LOAD(ssdr_output_checksum);
     LOAD(ssdr_set_wfdata_rows); LOAD(ssdr_strerror); LOAD(ssdr_version); LOAD(ssdr_last_hip_error); LOAD(ssdr_set_wf_center);
     LOAD(ssdr_run_db2col); LOAD(ssdr_run_playbuffer); LOAD(ssdr_set_averaging); LOAD(ssdr_set_hop);
+    LOAD(ssdr_set_chain_floors); LOAD(ssdr_feed_slot); LOAD(ssdr_feed_submit); LOAD(ssdr_feed_collect);
     const int bad = strcmp(argv[2], "gpu") == 0 ? run_gpu() : run_cpu();
     printf(bad ? "FAIL\n" : "PASS\n");
     return bad ? 1 : 0;

@@ -519,6 +519,60 @@ def test_pipelined_feed_equals_push_and_run(S):
             assert np.array_equal(got[b][k], want[b][k]), (b, k)
 
 
+def test_the_own_batch_survives_the_pipelined_feed(S):
+    """The feed's slots are batches of their own: what ssdr_push_iq / ssdr_run_chain left in the ctx (lines, PCM, RSSI, ADC flags)
+    reads back unchanged while a post-processing feed is open, after its batches and after its close; run_db2col / run_playbuffer
+    still work on it, and the next push_iq + run_chain continues the streams -- all as on an engine that ran the same batches
+    through push_iq / run_chain and never opened a feed (mixed modes: several audio paths, the stages side by side)."""
+    from supersdr_amd._lib import Db2colChan, PlayChan
+    n_ch, own_nf, nf = 6, 4, 2
+    iq = O.synth_iq(n_ch, (2 * own_nf + 3 * nf) * 512, seed=93)
+    first, last = iq[:, :own_nf * 512], iq[:, (own_nf + 3 * nf) * 512:]
+    fed = [iq[:, (own_nf + k * nf) * 512:(own_nf + (k + 1) * nf) * 512] for k in range(3)]
+    ps, _ = mixed_params(S, n_ch)
+    play = [PlayChan(100.0, 0.0)] * n_ch                         # the feed's initial play_buffer settings (ssdr_feed_open)
+
+    def db():
+        return [Db2colChan(zoom=c, auto_scale=1, low_clip_db=-120.0, high_clip_db=-60.0, dynamic_range=40.0) for c in range(n_ch)]
+
+    def own(eng, lines):
+        return (eng.fetch_wf(lines), *eng.fetch_audio(), eng.audio_flags(), eng.output_checksum())
+
+    def same(a, b):
+        return all(np.array_equal(x, y) for x, y in zip(a[:4], b[:4])) and a[4] == b[4]
+
+    with S.SsdrEngine(n_ch) as eng, S.SsdrEngine(n_ch) as plain:
+        for e in (eng, plain):
+            e.set_params(0, ps)
+            e.push_iq(first)
+            lines, fused = e.run_chain()
+            assert lines == own_nf // 2 and fused == 0
+        rec = own(eng, lines)
+        assert same(own(plain, lines), rec)
+        eng.feed_open(nf, depth=2, post=True)
+        for k in range(3):
+            eng.feed_slot()[:] = fed[k]
+            eng.feed_submit()
+            wf_k, pcm_k, _ = eng.feed_collect()
+            plain.push_iq(fed[k])                                # the same batch, its play_buffer with it: the carried state matches
+            assert plain.run_chain() == (nf // 2, 0)
+            plain.run_playbuffer(play)
+            assert np.array_equal(wf_k, plain.fetch_wf(nf // 2)) and np.array_equal(pcm_k, plain.fetch_audio()[0])
+        assert same(own(eng, lines), rec)
+        eng.feed_close()
+        assert same(own(eng, lines), rec)
+        plain.set_wf_lines(rec[0])                               # its own batch: the first one's results again
+        plain.set_pcm(rec[1])
+        assert np.array_equal(eng.run_playbuffer(play), plain.run_playbuffer(play))
+        da, db_ = db(), db()
+        assert np.array_equal(eng.run_db2col(da, lines), plain.run_db2col(db_, lines))
+        assert all(bytes(x) == bytes(y) for x, y in zip(da, db_))
+        for e in (eng, plain):
+            e.push_iq(last)
+            assert e.run_chain() == (own_nf // 2, 0)
+        assert same(own(eng, lines), own(plain, lines))
+
+
 def test_pipelined_feed_through_the_fused_kernel_equals_the_two_kernels(S):
     """The feed runs its batches through ssdr_run_chain: with every channel on the full-band AM path, N = 1 and 8-frame batches
     that is the fused superframe kernel.  Its waterfall lines, PCM, RSSI and ADC flags, batch after batch with the state
