@@ -445,6 +445,52 @@ int ssdr_get_deemp_state(ssdr_ctx *ctx, uint32_t first, uint32_t count, int32_t 
  * launch; launches made with profiling off count, and add no time). */
 int ssdr_deemphasis_stats(ssdr_ctx *ctx, float *total_ms, uint32_t *launches, int reset);
 
+/* -- waterfall views: a zoom per listener ("SET zoom=%d start=%d" on every UP / DOWN key, utils_supersdr.py:741, 815-845).
+ * ssdr_set_wf_zoom zooms every channel of the ctx, takes the full-span line away from everybody and wants whole zoomed lines per
+ * batch.  A VIEW is a zoom stage of its own for one channel, beside the un-zoomed waterfall, for the few channels somebody looks
+ * at; the list of views can be replaced while the streams run.  A view of channel c at zoom Z and centre offset_hz computes, bit for
+ * bit, the zoomed stream the ctx-wide stage gives that channel (same NCO, same taps, same rounding: oracle/ssdr_oracle.py:zoom_taps,
+ * twin_zoom) -- only the cutting into lines differs, because a view carries what is left over from call to call:
+ *   every ssdr_run_wf and every path of ssdr_run_chain (*fused = 0, 1, 2) advances each view by the batch's raw input for its channel:
+ *   n_in = n_frames * 512 * D samples become n_in / Z zoomed int16 I,Q samples, appended to what the view carried;
+ *   hop 1024: a line for every full 1024 zoomed samples, the remainder (at most 1023) is carried;
+ *   hop 512:  a line per 512 new zoomed samples, covering those and the 512 before them (silence before the first, as after
+ *             ssdr_create); the remainder (at most 511) is carried.
+ * Any frame count is taken and a view may yield no line in a call.  (At hop 1024 the full-span stage still cannot split a line: a
+ * batch of an odd number of 512-sample halves -- SSDR_EINVAL without views -- is taken by ssdr_run_wf while a view is set, for the
+ * views alone: *lines_ready = 0 and the full-span stream does not see that batch.  ssdr_run_chain keeps refusing it.)
+ * View lines are single byte lines (N = 1) of the fp32 waterfall stage, int16 [1024] in 0..255 with the channel's wf_cal_db,
+ * whatever ssdr_set_averaging and ssdr_set_exact_bins say.  They are NOT ADPCM-encoded (ssdr_set_compression covers the full-span
+ * lines only).  The un-zoomed waterfall of all channels, its averaging groups and its W/F payloads are untouched.
+ * Kernels: ssdr_wf_view.hip (zoom for a compact list of views with a zoom each, then the shipped waterfall kernel on the views'
+ * streams, then a gather); with no view set nothing is launched, and before the first view nothing is allocated.  No SSDR_K_* slot:
+ * ssdr_wf_view_stats is the stage's own.  Cost: not timed yet (tools/wf_view_probe.py).
+ * While any view is set ssdr_feed_open and ssdr_checkpoint_save / _load return SSDR_ESTATE; while a pipelined feed is open
+ * ssdr_set_wf_views with count > 0 returns SSDR_ESTATE; views and ssdr_set_wf_zoom > 1 exclude each other (whichever comes second
+ * returns SSDR_ESTATE).  ssdr_set_hop, ssdr_set_decimation and ssdr_set_kiwi_rate restart every view (the last two recompute the
+ * NCO steps from offset_hz); ssdr_reset_state restarts the views of the channels it names. */
+#define SSDR_WF_VIEWS_MAX 256
+typedef struct ssdr_wf_view {
+    uint32_t channel;
+    uint32_t zoom;          /* 2, 4 or 8 (1 = no view: leave the channel out) */
+    double offset_hz;       /* zoom centre, Hz from the IQ band's centre: the range of ssdr_set_wf_center at the current input rate */
+} ssdr_wf_view;             /* 16 B */
+/* Replaces the whole list: channels ascending and unique, count <= SSDR_WF_VIEWS_MAX; (NULL, 0) removes every view.  Anything else
+ * is SSDR_EINVAL, and then nothing changes.  A view whose (channel, zoom, offset_hz) is in the old list keeps its stream (phase, raw
+ * history, carried samples); a new or changed one starts from silence.  No other view's stream is restarted or waited for beyond
+ * the upload of the list. */
+int ssdr_set_wf_views(ssdr_ctx *ctx, const ssdr_wf_view *views, uint32_t count);
+int ssdr_get_wf_views(ssdr_ctx *ctx, ssdr_wf_view *views /* may be NULL */, uint32_t *count);
+/* The view lines of the last run: lines_out int16 [*total_lines][1024], the views' lines one view after the other in list order
+ * (may be NULL: counts only); lines_per_view uint32 [count].  SSDR_ESTATE if no view is set, or there has been no run with the
+ * list as it is. */
+int ssdr_wf_view_lines(ssdr_ctx *ctx, int16_t *lines_out, uint32_t *lines_per_view, uint32_t *total_lines, int out_is_device);
+/* The zoomed samples view `view_index` produced in the last run (tests): iq_out int16 [n_in / Z][2] (host memory), *samples = n_in / Z */
+int ssdr_read_wf_view(ssdr_ctx *ctx, uint32_t view_index, int16_t *iq_out, uint32_t *samples);
+/* The view stage's runs since the last reset (one per batch while a view is set), and with ssdr_set_profiling on their summed time
+ * (one HIP-event pair around the stage's kernels; runs made with profiling off count, and add no time). */
+int ssdr_wf_view_stats(ssdr_ctx *ctx, float *total_ms, uint32_t *launches, int reset);
+
 /* -- pipelined host feed: the path a live ingest takes (KiwiSDRStream._process_iq_samples -> batches, kiwi/client.py:493)
  *
  * ssdr_push_iq + ssdr_run_* from pageable host memory serialise copy-in, kernels and copy-out.  The feed keeps `depth`

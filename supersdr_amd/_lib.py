@@ -76,6 +76,15 @@ class DeempParams(C.Structure):
 
 
 assert C.sizeof(DeempParams) == 8
+WF_VIEWS_MAX = 256          # SSDR_WF_VIEWS_MAX
+
+
+class WfView(C.Structure):
+    """ssdr_wf_view: one waterfall view -- channel, zoom (2, 4, 8), zoom centre in Hz from the IQ band's centre"""
+    _fields_ = [("channel", C.c_uint32), ("zoom", C.c_uint32), ("offset_hz", C.c_double)]
+
+
+assert C.sizeof(WfView) == 16
 assert C.sizeof(ChanConsts) == 64 and C.sizeof(ChanState) == 64 and C.sizeof(ChanParams) == 88
 assert C.sizeof(Db2colChan) == 48 and C.sizeof(PlayChan) == 16
 WIRE_BODY = 17 + FRAME * 4
@@ -140,6 +149,11 @@ _SIGS = {
     "ssdr_deemp_coeff": (C.c_int, [C.c_uint32, C.c_uint32, C.POINTER(C.c_uint32)]),
     "ssdr_get_deemp_state": (C.c_int, [_P, C.c_uint32, C.c_uint32, C.POINTER(C.c_int32)]),
     "ssdr_deemphasis_stats": (C.c_int, [_P, C.POINTER(C.c_float), C.POINTER(C.c_uint32), C.c_int]),
+    "ssdr_set_wf_views": (C.c_int, [_P, C.POINTER(WfView), C.c_uint32]),
+    "ssdr_get_wf_views": (C.c_int, [_P, C.POINTER(WfView), C.POINTER(C.c_uint32)]),
+    "ssdr_wf_view_lines": (C.c_int, [_P, _P, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.c_int]),
+    "ssdr_read_wf_view": (C.c_int, [_P, C.c_uint32, _P, C.POINTER(C.c_uint32)]),
+    "ssdr_wf_view_stats": (C.c_int, [_P, C.POINTER(C.c_float), C.POINTER(C.c_uint32), C.c_int]),
     "ssdr_feed_open": (C.c_int, [_P, C.c_uint32, C.c_uint32, C.c_uint32]),
     "ssdr_feed_slot": (C.c_int, [_P, C.POINTER(_P)]),
     "ssdr_feed_submit": (C.c_int, [_P]),

@@ -258,6 +258,26 @@ struct ssdr_ctx {
     uint32_t *d_de_list = nullptr;                      // [2 n_ch], as h_de_list
     float de_ms = 0.0f;                                 // the kernel's own timing (not an SSDR_K_* slot): ssdr_deemphasis_stats
     uint32_t de_launches = 0;
+    // waterfall views (ssdr_set_wf_views): device memory at the first view; with no view set nothing is launched
+    std::vector<ssdr_wf_view> h_wv;                     // the list as set, channels ascending
+    std::vector<uint32_t> h_wv_carry;                   // [views] zoomed samples each view carries (mirror of SsdrWfView::carry_n)
+    std::vector<uint32_t> h_wv_run_carry, h_wv_run_lines;   // of the last run: where each view's new samples begin in its row; its lines
+    uint32_t wv_run_n_in = 0, wv_run_total = 0;         // that run's input samples per channel; its lines over all views
+    uint64_t wv_run_stride = 0;
+    bool wv_run_valid = false;                          // there has been a run with the list as it is
+    int wv_set = 0;                                     // which of the two sets of state arrays is the current one (a new list is built in the other)
+    SsdrWfView *d_wv[2] = {nullptr, nullptr};           // [SSDR_WF_VIEWS_MAX]
+    uint32_t *d_wv_hist[2] = {nullptr, nullptr}, *d_wv_carry[2] = {nullptr, nullptr}, *d_wv_tail[2] = {nullptr, nullptr};
+    float *d_wv_taps = nullptr;                         // [3][256] the taps of Z = 2, 4, 8
+    ssdr_chan_consts *d_wv_consts = nullptr;            // [SSDR_WF_VIEWS_MAX] the views' channels' constants (wf_cal_lin), compact
+    bool wv_consts_dirty = true;
+    int16_t *d_wv_acc = nullptr;                        // [2][SSDR_WF_VIEWS_MAX][1024] the waterfall kernel's partial sums (N = 1: never used)
+    uint32_t *d_wv_stream = nullptr;                    // [views][stride] carried + new zoomed samples of the last run
+    size_t wv_stream_dwords = 0;
+    int16_t *d_wv_wf = nullptr, *d_wv_lines = nullptr;  // the waterfall kernel's [max lines][views][1024]; the compact [total][1024]
+    size_t wv_wf_rows = 0, wv_lines_rows = 0;
+    float wv_ms = 0.0f;                                 // the stage's own timing: ssdr_wf_view_stats
+    uint32_t wv_launches = 0;
 };
 // Every device buffer a ctx owns (the feed slots' own: ssdr_feed_close) -- what ssdr_destroy frees.  One line per section of the
 // struct above, in its order: a new `d_` member joins its section's line HERE, and tests/test_gpu_parity.py's
@@ -280,6 +300,8 @@ static void free_owned(ssdr_ctx *c)
         c->d_comp_list, c->d_adpcm_state, c->d_snd_adpcm, c->d_wf_adpcm,                                              // wire compression
         c->d_sq, c->d_sq_list, c->d_sq_closed,                                                                        // squelch
         c->d_de_state, c->d_de_list,                                                                                  // de-emphasis
+        c->d_wv[0], c->d_wv[1], c->d_wv_hist[0], c->d_wv_hist[1], c->d_wv_carry[0], c->d_wv_carry[1], c->d_wv_tail[0], c->d_wv_tail[1],
+        c->d_wv_taps, c->d_wv_consts, c->d_wv_acc, c->d_wv_stream, c->d_wv_wf, c->d_wv_lines,                         // waterfall views
     };
     for (void *p : owned)
         if (p) (void)hipFree(p);
@@ -293,6 +315,7 @@ static int get_event(ssdr_ctx *c, hipEvent_t *e)
 }
 // HIP events on the stream the kernel is launched on, bracketing exactly one launch.
 constexpr int kTimedDeemp = SSDR_K_COUNT;               // `which` of the de-emphasis kernel: timed beside the SSDR_K_* slots, not in them
+constexpr int kTimedWfView = SSDR_K_COUNT + 1;          // ... and of the waterfall views' stage
 static int timed_begin(ssdr_ctx *c, hipStream_t s = nullptr)
 {
     if (!s) s = c->stream;
@@ -325,6 +348,7 @@ static int resolve_pending(ssdr_ctx *c)
         HIP_TRY(hipEventSynchronize(p.e1));
         HIP_TRY(hipEventElapsedTime(&ms, p.e0, p.e1));
         if (p.which == kTimedDeemp) c->de_ms += ms;          // (its launches are counted where they are made)
+        else if (p.which == kTimedWfView) c->wv_ms += ms;
         else if (p.which >= 0) { c->k_ms[p.which] += ms; c->k_n[p.which] += 1; c->last_ms = ms; }
         c->free_events.push_back(p.e0);
         c->free_events.push_back(p.e1);
@@ -506,6 +530,7 @@ static int zoom_restart(ssdr_ctx *c, uint32_t first, uint32_t count, bool restar
 static int nb_upload(ssdr_ctx *c, uint32_t first, uint32_t count);
 static int squelch_upload(ssdr_ctx *c, uint32_t first, uint32_t count);
 static int deemp_reset(ssdr_ctx *c, uint32_t first, uint32_t count);
+static int wfview_restart(ssdr_ctx *c, uint32_t first, uint32_t count);
 
 int ssdr_reset_state(ssdr_ctx *c, uint32_t first, uint32_t count) SSDR_GUARD
 {
@@ -533,6 +558,7 @@ int ssdr_reset_state(ssdr_ctx *c, uint32_t first, uint32_t count) SSDR_GUARD
     SSDR_TRY(nb_upload(c, first, count));      // the blanker starts over (its gate at the current rate)
     SSDR_TRY(squelch_upload(c, first, count)); // and the squelch
     SSDR_TRY(deemp_reset(c, first, count));    // and the de-emphasis
+    SSDR_TRY(wfview_restart(c, first, count)); // and the views of these channels
     return zoom_restart(c, first, count, false);         // the zoomed streams of these channels start over as well
 } SSDR_UNGUARD
 
@@ -561,6 +587,7 @@ int ssdr_set_params(ssdr_ctx *c, uint32_t first, uint32_t count, const ssdr_chan
     for (uint32_t i = 0; i < count; i++) c->h_consts[first + i] = k[i];
     c->chan_list_dirty = true;
     c->summary_dirty = true;
+    c->wv_consts_dirty = true;               // (a view draws its lines with its channel's wf_cal_db)
     SSDR_TRY(join_audio(c));
     // their squelch state only, a run of consecutive channels at a time
     SSDR_TRY(for_each_run(sq_reset.data(), sq_reset.size(), [&](size_t i, size_t n) { return squelch_upload(c, sq_reset[i], (uint32_t)n); }));
@@ -735,21 +762,24 @@ int ssdr_set_hop(ssdr_ctx *c, uint32_t hop) SSDR_GUARD
     }
     c->hop = hop;
     c->wf_phase = 0;                                          // a change of framing restarts the averaging group
-    return SSDR_OK;
+    return wfview_restart(c, 0, c->n_ch);                     // ... and every view: its carried samples were cut for the old hop
 } SSDR_UNGUARD
 
+// a zoom centre as an NCO step at the input rate fs_in
+static uint32_t zoom_dphi(double offset_hz, double fs_in)
+{
+    const double x = std::nearbyint(offset_hz / fs_in * 4294967296.0);
+    long long v = (long long)x % 4294967296ll;
+    if (v < 0) v += 4294967296ll;
+    return (uint32_t)v;
+}
 // the zoom centres as NCO steps at the current input rate; the zoom streams restart (phase, history, averaging group)
 static int zoom_restart(ssdr_ctx *c, uint32_t first, uint32_t count, bool restart_group)
 {
     if (c->zoom <= 1 || !c->d_zoom_dphi || !count) return SSDR_OK;
     const double fs_in = (double)c->kiwi_rate * c->decim;
     std::vector<uint32_t> dphi(count);
-    for (uint32_t i = 0; i < count; i++) {
-        const double x = std::nearbyint(c->h_zoom_offset[first + i] / fs_in * 4294967296.0);
-        long long v = (long long)x % 4294967296ll;
-        if (v < 0) v += 4294967296ll;
-        dphi[i] = (uint32_t)v;
-    }
+    for (uint32_t i = 0; i < count; i++) dphi[i] = zoom_dphi(c->h_zoom_offset[first + i], fs_in);
     HIP_TRY(hipMemcpyAsync(c->d_zoom_dphi + first, dphi.data(), count * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
     HIP_TRY(hipMemsetAsync(c->d_zoom_phase + first, 0, count * sizeof(uint32_t), c->stream));
     HIP_TRY(hipMemsetAsync(c->d_zoom_hist + (size_t)first * SSDR_ZOOM_HIST, 0, (size_t)count * SSDR_ZOOM_HIST * 4, c->stream));
@@ -764,6 +794,7 @@ int ssdr_set_wf_zoom(ssdr_ctx *c, uint32_t zoom) SSDR_GUARD
 {
     if (!c || (zoom != 1 && zoom != 2 && zoom != 4 && zoom != 8)) return SSDR_EINVAL;
     if (!c->feed.empty()) return SSDR_ESTATE;              // the feed's slots are sized for un-zoomed lines
+    if (zoom > 1 && !c->h_wv.empty()) return SSDR_ESTATE;   // views and the ctx-wide zoom exclude each other: whichever comes second
     HIP_TRY(hipSetDevice(c->device));
     if (zoom > 1 && !c->d_zoom_dphi) {
         HIP_TRY(hipMalloc(&c->d_zoom_taps, (SSDR_ZOOM_TAPS_MAX + 1) * sizeof(float)));
@@ -1262,6 +1293,123 @@ static int audio_tail_launch(ssdr_ctx *c, const Batch &b, hipStream_t s)
     return adpcm_snd_launch(c, b, s);
 }
 
+// ---- waterfall views: a per-channel zoom stage beside the waterfall stage (ssdr_set_wf_views) ---------------------------------
+// the state arrays (two sets: a new list is built in the other one, so that a view that stays keeps its stream) and the tap tables
+static int wfview_alloc(ssdr_ctx *c)
+{
+    if (c->d_wv_taps) return SSDR_OK;
+    float hf[3][SSDR_ZOOM_TAPS_MAX + 1] = {};
+    for (int zi = 0; zi < 3; zi++) {         // the ctx-wide stage's taps (ssdr_set_wf_zoom), one table per Z
+        const int Z = 2 << zi, n = 32 * Z - 1;
+        double h[SSDR_ZOOM_TAPS_MAX + 1];
+        if (ssdr_design_lowpass_exact(1.0 / (2.0 * Z), 1.0, n, h) != n) return SSDR_EINVAL;
+        for (int i = 0; i < n; i++) hf[zi][i] = (float)h[i];
+    }
+    for (int i = 0; i < 2; i++) {
+        if (!c->d_wv[i]) HIP_TRY(hipMalloc(&c->d_wv[i], SSDR_WF_VIEWS_MAX * sizeof(SsdrWfView)));
+        if (!c->d_wv_hist[i]) HIP_TRY(hipMalloc(&c->d_wv_hist[i], (size_t)SSDR_WF_VIEWS_MAX * SSDR_ZOOM_HIST * 4));
+        if (!c->d_wv_carry[i]) HIP_TRY(hipMalloc(&c->d_wv_carry[i], (size_t)SSDR_WF_VIEWS_MAX * SSDR_NFFT * 4));
+        if (!c->d_wv_tail[i]) HIP_TRY(hipMalloc(&c->d_wv_tail[i], (size_t)SSDR_WF_VIEWS_MAX * (SSDR_NFFT / 2) * 4));
+    }
+    if (!c->d_wv_consts) HIP_TRY(hipMalloc(&c->d_wv_consts, SSDR_WF_VIEWS_MAX * sizeof(ssdr_chan_consts)));
+    if (!c->d_wv_acc) HIP_TRY(hipMalloc(&c->d_wv_acc, (size_t)2 * SSDR_WF_VIEWS_MAX * SSDR_NFFT * 2));
+    float *t = nullptr;
+    HIP_TRY(hipMalloc(&t, sizeof hf));
+    c->d_wv_taps = t;
+    HIP_TRY(hipMemcpy(c->d_wv_taps, hf, sizeof hf, hipMemcpyHostToDevice));
+    return SSDR_OK;
+}
+static SsdrWfView wfview_fresh(const ssdr_ctx *c, const ssdr_wf_view &v)
+{
+    SsdrWfView d = {};
+    d.channel = v.channel;
+    d.zoom = v.zoom;
+    d.dphi = zoom_dphi(v.offset_hz, (double)c->kiwi_rate * c->decim);
+    return d;
+}
+// view j of set `set` from silence (queued on the main stream; the caller waits): phase 0, no history, nothing carried
+static int wfview_silence(ssdr_ctx *c, int set, uint32_t j, const SsdrWfView *fresh)
+{
+    HIP_TRY(hipMemcpyAsync(c->d_wv[set] + j, fresh, sizeof *fresh, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemsetAsync(c->d_wv_hist[set] + (size_t)j * SSDR_ZOOM_HIST, 0, SSDR_ZOOM_HIST * 4, c->stream));
+    HIP_TRY(hipMemsetAsync(c->d_wv_tail[set] + (size_t)j * (SSDR_NFFT / 2), 0, (SSDR_NFFT / 2) * 4, c->stream));
+    return SSDR_OK;
+}
+// the views of channels [first, first + count) start over, their NCO steps at the current input rate
+static int wfview_restart(ssdr_ctx *c, uint32_t first, uint32_t count)
+{
+    if (c->h_wv.empty() || !count) return SSDR_OK;
+    std::vector<SsdrWfView> fresh(c->h_wv.size());
+    bool any = false;
+    for (size_t j = 0; j < c->h_wv.size(); j++) {
+        const uint32_t ch = c->h_wv[j].channel;
+        if (ch < first || ch - first >= count) continue;
+        fresh[j] = wfview_fresh(c, c->h_wv[j]);
+        SSDR_TRY(wfview_silence(c, c->wv_set, (uint32_t)j, &fresh[j]));
+        c->h_wv_carry[j] = 0;
+        any = true;
+    }
+    if (!any) return SSDR_OK;
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    c->wv_run_valid = false;
+    return SSDR_OK;
+}
+// Every view advanced by the batch's input for its channel, on the main stream: zoom kernel, the waterfall kernel on the views'
+// streams, finish kernel (ssdr_wf_view.hip).  Timed as one stage with its own event pair; not an SSDR_K_* slot.
+static int wfview_stage(ssdr_ctx *c, const Batch &b)
+{
+    const uint32_t nv = (uint32_t)c->h_wv.size();
+    if (!nv) return SSDR_OK;
+    const uint32_t n_in = (uint32_t)in_len(c, b.in_frames);
+    const uint64_t stride = (uint64_t)2 * SSDR_NFFT + n_in / 2;          // carried (< 1024) + new (<= n_in / 2), and a line to spare
+    uint32_t max_lines = 0, total = 0;
+    std::vector<uint32_t> lines(nv);
+    for (uint32_t j = 0; j < nv; j++) {
+        lines[j] = (c->h_wv_carry[j] + n_in / c->h_wv[j].zoom) / c->hop;
+        max_lines = std::max(max_lines, lines[j]);
+        total += lines[j];
+    }
+    c->wv_run_valid = false;
+    SSDR_TRY(grow(c, c->d_wv_stream, c->wv_stream_dwords, (size_t)nv * stride, 4));
+    SSDR_TRY(grow(c, c->d_wv_wf, c->wv_wf_rows, (size_t)std::max(max_lines, 1u) * nv, SSDR_NFFT * 2));
+    SSDR_TRY(grow(c, c->d_wv_lines, c->wv_lines_rows, std::max(total, 1u), SSDR_NFFT * 2));
+    if (c->wv_consts_dirty) {
+        std::vector<ssdr_chan_consts> k(nv);
+        for (uint32_t j = 0; j < nv; j++) k[j] = c->h_consts[c->h_wv[j].channel];
+        HIP_TRY(hipMemcpyAsync(c->d_wv_consts, k.data(), nv * sizeof(ssdr_chan_consts), hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(hipStreamSynchronize(c->stream));
+        c->wv_consts_dirty = false;
+    }
+    const int set = c->wv_set;
+    SsdrWfViewArgs a;
+    a.iq = b.d_iq; a.ch_stride = n_in; a.n_in = n_in; a.n_views = nv; a.hop = c->hop;
+    a.views = c->d_wv[set]; a.taps = c->d_wv_taps; a.hist = c->d_wv_hist[set]; a.carry = c->d_wv_carry[set]; a.tail = c->d_wv_tail[set];
+    a.stream = c->d_wv_stream; a.stream_stride = stride; a.wf_lines = c->d_wv_wf; a.lines_out = c->d_wv_lines;
+    SsdrWfArgs w;                            // the views as the channels of a small ctx: byte lines (N = 1), fp32 bins
+    w.iq = c->d_wv_stream; w.ch_stride = stride; w.n_ch = nv; w.n_lines = max_lines;
+    w.tail = c->hop == SSDR_NFFT / 2 ? c->d_wv_tail[set] : nullptr;
+    w.n_avg = 1; w.phase = 0; w.n_groups = max_lines; w.grp_run = 1;
+    w.out = c->d_wv_wf; w.acc_in = c->d_wv_acc; w.acc_out = c->d_wv_acc + (size_t)SSDR_WF_VIEWS_MAX * SSDR_NFFT;
+    w.consts = c->d_wv_consts; w.win = c->d_win; w.tw_stage = c->d_tw; w.lut = c->d_lut;
+    const uint64_t need = ((uint64_t)((nv + 1) / 2) * max_lines + SSDR_WF_BLOCK / 64 - 1) / (SSDR_WF_BLOCK / 64);
+    const uint32_t grid = (uint32_t)std::min<uint64_t>(std::max<uint64_t>(need, 1), c->wf_grid ? c->wf_grid : 1);
+    SSDR_TRY(timed_launch(c, kTimedWfView, c->stream, [&]() -> int {
+        HIP_TRY(ssdr_launch_wf_view_zoom(a, c->stream));
+        if (max_lines) HIP_TRY(ssdr_launch_wf(w, grid, c->stream));
+        HIP_TRY(ssdr_launch_wf_view_finish(a, c->stream));
+        return SSDR_OK;
+    }));
+    c->wv_launches++;
+    c->h_wv_run_carry = c->h_wv_carry;
+    for (uint32_t j = 0; j < nv; j++) c->h_wv_carry[j] = c->h_wv_carry[j] + n_in / c->h_wv[j].zoom - lines[j] * c->hop;
+    c->h_wv_run_lines = lines;
+    c->wv_run_n_in = n_in;
+    c->wv_run_total = total;
+    c->wv_run_stride = stride;
+    c->wv_run_valid = true;
+    return SSDR_OK;
+}
+
 // The waterfall stage of batch `b` on the main stream.  Under a plan with a one-read kernel it does the stage's bookkeeping only and
 // hands its kernel arguments on in `*one_read`: the audio stage launches the kernel that does both stages' work.
 static int wf_stage(ssdr_ctx *c, Batch &b, ChainPlan plan, SsdrWfArgs *one_read, uint32_t *lines_ready)
@@ -1339,6 +1487,7 @@ static int wf_stage(ssdr_ctx *c, Batch &b, ChainPlan plan, SsdrWfArgs *one_read,
     b.wf_lines_ready = n_out;
     if (lines_ready) *lines_ready = n_out;
     if (!plan.one_read) SSDR_TRY(adpcm_wf_launch(c, b, c->stream, c->n_avg));   // (one-read: the audio stage)
+    if (!plan.one_read) SSDR_TRY(wfview_stage(c, b));                          // (one-read: run_chain, once that kernel is launched)
     return SSDR_OK;
 }
 
@@ -1347,6 +1496,16 @@ int ssdr_run_wf(ssdr_ctx *c, int16_t *wf_sum_out, uint32_t *lines_ready, int out
     if (!c) return SSDR_EINVAL;
     if (!c->own.have_input) return SSDR_ESTATE;
     Batch &b = c->own;
+    if (!c->h_wv.empty() && c->zoom == 1 && c->hop == SSDR_NFFT && ((b.in_frames * c->decim) & 1u)) {
+        // half a full-span line over: the views, which carry their samples from call to call, take the batch; the full-span stage
+        // cannot split a line and sits this call out (no lines, its stream does not see the batch)
+        HIP_TRY(hipSetDevice(c->device));
+        SSDR_TRY(wfview_stage(c, b));
+        b.wf_lines_ready = 0;
+        c->wf_adpcm_valid = false;
+        if (lines_ready) *lines_ready = 0;
+        return SSDR_OK;
+    }
     SSDR_TRY(wf_stage(c, b, ChainPlan{0, c->concurrent}, nullptr, lines_ready));
     if (!wf_sum_out || !b.wf_lines_ready) return SSDR_OK;
     return copy_out(c, wf_sum_out, b.d_wf_out, (size_t)b.wf_lines_ready * c->n_ch * SSDR_NFFT * 2, out_is_device, kSyncHost);
@@ -1584,7 +1743,7 @@ static int run_chain(ssdr_ctx *c, Batch &b, uint32_t *lines_ready, int *fused)
     SSDR_TRY(audio_stage(c, b, plan, &wf));
     SSDR_TRY(audio_queued(c, plan));
     undo.armed = false;
-    return SSDR_OK;
+    return plan.one_read ? wfview_stage(c, b) : SSDR_OK;     // (the views read the input alone: on the main stream in every case)
 }
 
 int ssdr_run_chain(ssdr_ctx *c, uint32_t *lines_ready, int *fused) SSDR_GUARD
@@ -1828,7 +1987,7 @@ int ssdr_feed_open(ssdr_ctx *c, uint32_t n_frames, uint32_t depth, uint32_t flag
 {
     if (!c || n_frames == 0 || (n_frames & 1u) || depth < 2 || depth > 16 || (flags & ~(uint32_t)(SSDR_FEED_WIRE | SSDR_FEED_POST | SSDR_FEED_LAZY_OUT))) return SSDR_EINVAL;
     if (!c->feed.empty() || c->concurrent || c->decim != 1 || c->zoom != 1) return SSDR_ESTATE;
-    if (c->comp_snd_n || c->comp_wf_n || c->sq_set_n || c->de_set_n) return SSDR_ESTATE;   // no wire compression, squelch or de-emphasis in the slot pipeline      // the feed's slots are sized for un-zoomed 12 kHz IQ
+    if (c->comp_snd_n || c->comp_wf_n || c->sq_set_n || c->de_set_n || !c->h_wv.empty()) return SSDR_ESTATE;   // no wire compression, squelch, de-emphasis or waterfall view in the slot pipeline      // the feed's slots are sized for un-zoomed 12 kHz IQ
     HIP_TRY(hipSetDevice(c->device));
     const bool post = (flags & SSDR_FEED_POST) != 0;
     if (post) SSDR_TRY(ensure_play(c));
@@ -2189,6 +2348,7 @@ int ssdr_checkpoint_save(ssdr_ctx *c, void *blob) SSDR_GUARD
     if (c->comp_snd_n || c->comp_wf_n) return SSDR_ESTATE;   // nor the wire encoders'
     if (c->sq_set_n) return SSDR_ESTATE;                     // nor the squelch's
     if (c->de_set_n) return SSDR_ESTATE;                     // nor the de-emphasis's
+    if (!c->h_wv.empty()) return SSDR_ESTATE;                // nor the waterfall views' streams
     SsdrCkptHeader h = {kCkptMagic, kCkptVersion, c->n_ch, c->n_avg, c->wf_phase, c->audio_started ? 1u : 0u, c->kiwi_rate,
                         c->d_play_hist ? 1u : 0u, c->synth_sample0, c->hop, c->decim};
     char *p = static_cast<char *>(blob);
@@ -2233,7 +2393,7 @@ int ssdr_checkpoint_load(ssdr_ctx *c, const void *blob, uint64_t bytes) SSDR_GUA
     std::vector<float> ktaps(n * SSDR_NTAP_MAX);
     for (size_t i = 0; i < n; i++)
         if (ssdr_compile_params_host(&prm[i], &kc[i], ktaps.data() + i * SSDR_NTAP_MAX, h.decim, h.kiwi_rate) != SSDR_OK) return SSDR_EINVAL;
-    if (!c->feed.empty() || c->zoom > 1 || c->nb_on || c->comp_snd_n || c->comp_wf_n || c->sq_set_n || c->de_set_n) return SSDR_ESTATE;
+    if (!c->feed.empty() || c->zoom > 1 || c->nb_on || c->comp_snd_n || c->comp_wf_n || c->sq_set_n || c->de_set_n || !c->h_wv.empty()) return SSDR_ESTATE;
     std::vector<double> play_hist;                          // play_buffer state that arrives before its buffers exist: applied at first use
     if (h.has_play && !c->d_play_hist) {
         const double *q = reinterpret_cast<const double *>(static_cast<const char *>(blob) + sizeof h + n * (sizeof(ssdr_chan_consts) +
@@ -2916,6 +3076,97 @@ int ssdr_deemphasis_stats(ssdr_ctx *c, float *total_ms, uint32_t *launches, int 
     if (total_ms) *total_ms = c->de_ms;
     if (launches) *launches = c->de_launches;
     if (reset) { c->de_ms = 0.0f; c->de_launches = 0; }
+    return SSDR_OK;
+} SSDR_UNGUARD
+
+int ssdr_set_wf_views(ssdr_ctx *c, const ssdr_wf_view *views, uint32_t count) SSDR_GUARD
+{
+    if (!c || count > SSDR_WF_VIEWS_MAX || (count && !views)) return SSDR_EINVAL;
+    const double half = 0.5 * (double)c->kiwi_rate * c->decim;
+    for (uint32_t i = 0; i < count; i++) {                  // all or nothing: every view is checked before the list is touched
+        const ssdr_wf_view &v = views[i];
+        if (v.channel >= c->n_ch || (i && v.channel <= views[i - 1].channel)) return SSDR_EINVAL;
+        if (v.zoom != 2 && v.zoom != 4 && v.zoom != 8) return SSDR_EINVAL;
+        if (!(std::fabs(v.offset_hz) <= half)) return SSDR_EINVAL;
+    }
+    if (count && (!c->feed.empty() || c->zoom > 1)) return SSDR_ESTATE;
+    c->wv_run_valid = false;
+    if (!count) {                                           // (the state arrays stay for the next list)
+        c->h_wv.clear();
+        c->h_wv_carry.clear();
+        return SSDR_OK;
+    }
+    HIP_TRY(hipSetDevice(c->device));
+    SSDR_TRY(wfview_alloc(c));
+    // the new list is built in the other set of state arrays: a view that stays is copied there with all it carries, device to
+    // device behind whatever run is queued; a new or changed one starts from silence.  Nobody's stream waits for anybody else's.
+    const int from = c->wv_set, to = from ^ 1;
+    std::vector<SsdrWfView> fresh(count);
+    std::vector<uint32_t> carry(count, 0u);
+    size_t i = 0;
+    for (uint32_t j = 0; j < count; j++) {
+        while (i < c->h_wv.size() && c->h_wv[i].channel < views[j].channel) i++;
+        const bool stays = i < c->h_wv.size() && c->h_wv[i].channel == views[j].channel && c->h_wv[i].zoom == views[j].zoom &&
+                           c->h_wv[i].offset_hz == views[j].offset_hz;
+        if (stays) {
+            const hipMemcpyKind d2d = hipMemcpyDeviceToDevice;
+            HIP_TRY(hipMemcpyAsync(c->d_wv[to] + j, c->d_wv[from] + i, sizeof(SsdrWfView), d2d, c->stream));
+            HIP_TRY(hipMemcpyAsync(c->d_wv_hist[to] + (size_t)j * SSDR_ZOOM_HIST, c->d_wv_hist[from] + i * SSDR_ZOOM_HIST, SSDR_ZOOM_HIST * 4, d2d, c->stream));
+            HIP_TRY(hipMemcpyAsync(c->d_wv_carry[to] + (size_t)j * SSDR_NFFT, c->d_wv_carry[from] + i * SSDR_NFFT, SSDR_NFFT * 4, d2d, c->stream));
+            HIP_TRY(hipMemcpyAsync(c->d_wv_tail[to] + (size_t)j * (SSDR_NFFT / 2), c->d_wv_tail[from] + i * (SSDR_NFFT / 2), (SSDR_NFFT / 2) * 4, d2d, c->stream));
+            carry[j] = c->h_wv_carry[i];
+        } else {
+            fresh[j] = wfview_fresh(c, views[j]);
+            SSDR_TRY(wfview_silence(c, to, j, &fresh[j]));
+        }
+    }
+    HIP_TRY(hipStreamSynchronize(c->stream));               // (`fresh` is host memory)
+    c->h_wv.assign(views, views + count);
+    c->h_wv_carry = carry;
+    c->wv_set = to;
+    c->wv_consts_dirty = true;
+    return SSDR_OK;
+} SSDR_UNGUARD
+
+int ssdr_get_wf_views(ssdr_ctx *c, ssdr_wf_view *views, uint32_t *count) SSDR_GUARD
+{
+    if (!c || !count) return SSDR_EINVAL;
+    *count = (uint32_t)c->h_wv.size();
+    if (views) std::copy(c->h_wv.begin(), c->h_wv.end(), views);
+    return SSDR_OK;
+} SSDR_UNGUARD
+
+int ssdr_wf_view_lines(ssdr_ctx *c, int16_t *lines_out, uint32_t *lines_per_view, uint32_t *total_lines, int out_is_device) SSDR_GUARD
+{
+    if (!c) return SSDR_EINVAL;
+    if (c->h_wv.empty() || !c->wv_run_valid) return SSDR_ESTATE;
+    if (lines_per_view) std::copy(c->h_wv_run_lines.begin(), c->h_wv_run_lines.end(), lines_per_view);
+    if (total_lines) *total_lines = c->wv_run_total;
+    if (!lines_out || !c->wv_run_total) return SSDR_OK;
+    HIP_TRY(hipSetDevice(c->device));
+    return copy_out(c, lines_out, c->d_wv_lines, (size_t)c->wv_run_total * SSDR_NFFT * 2, out_is_device, kSyncHost);
+} SSDR_UNGUARD
+
+int ssdr_read_wf_view(ssdr_ctx *c, uint32_t view_index, int16_t *iq_out, uint32_t *samples) SSDR_GUARD
+{
+    if (!c) return SSDR_EINVAL;
+    if (c->h_wv.empty() || !c->wv_run_valid) return SSDR_ESTATE;
+    if (view_index >= c->h_wv.size()) return SSDR_EINVAL;
+    const uint32_t n = c->wv_run_n_in / c->h_wv[view_index].zoom;
+    if (samples) *samples = n;
+    if (!iq_out) return SSDR_OK;
+    HIP_TRY(hipSetDevice(c->device));
+    return copy_out(c, iq_out, c->d_wv_stream + (size_t)view_index * c->wv_run_stride + c->h_wv_run_carry[view_index], (size_t)n * 4, 0, kSyncHost);
+} SSDR_UNGUARD
+
+int ssdr_wf_view_stats(ssdr_ctx *c, float *total_ms, uint32_t *launches, int reset) SSDR_GUARD
+{
+    if (!c) return SSDR_EINVAL;
+    HIP_TRY(hipSetDevice(c->device));
+    SSDR_TRY(resolve_pending(c));
+    if (total_ms) *total_ms = c->wv_ms;
+    if (launches) *launches = c->wv_launches;
+    if (reset) { c->wv_ms = 0.0f; c->wv_launches = 0; }
     return SSDR_OK;
 } SSDR_UNGUARD
 

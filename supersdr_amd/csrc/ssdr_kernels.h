@@ -210,6 +210,27 @@ struct SsdrZoomArgs {
     uint32_t *out;                           // [n_ch][n_in / zoom] I | Q << 16
 };
 hipError_t ssdr_launch_zoom(const SsdrZoomArgs &a, hipStream_t stream);
+// waterfall views (ssdr_wf_view.hip, ssdr_set_wf_views): the zoom stage for a compact list of views, a zoom per view.  One view's
+// carried state: the phase of the next call's first sample, the zoomed samples carried towards its next line; and, from one kernel
+// of a call to the next, its line count and where its lines go in the compact output.  32 B.
+struct SsdrWfView { uint32_t channel, zoom, dphi, phase, carry_n, lines, line_off, pad; };
+struct SsdrWfViewArgs {
+    const uint32_t *iq;                      // [n_ch][ch_stride] input dwords of the batch
+    uint64_t ch_stride;
+    uint32_t n_in;                           // input samples per channel in this call (a multiple of 512)
+    uint32_t n_views, hop;                   // hop 1024 or 512: zoomed samples between a view's lines
+    SsdrWfView *views;                       // [n_views] in/out
+    const float *taps;                       // [3][SSDR_ZOOM_TAPS_MAX + 1] the taps of Z = 2, 4, 8, zero behind each table's 32 Z - 1
+    uint32_t *hist;                          // [n_views][SSDR_ZOOM_HIST] in/out: the raw samples before the call's first
+    uint32_t *carry;                         // [n_views][1024] in/out: carry_n zoomed samples I | Q << 16, oldest first
+    uint32_t *tail;                          // [n_views][512] in/out, hop 512: the half-line before the carried samples
+    uint32_t *stream;                        // [n_views][stream_stride] the carried samples, then this call's n_in / Z: what the lines are cut from
+    uint64_t stream_stride;                  // >= 1024 + n_in / 2
+    const int16_t *wf_lines;                 // [max lines][n_views][1024] the waterfall kernel's lines of `stream` (finish kernel)
+    int16_t *lines_out;                      // [total lines][1024] every view's own lines, in view order (finish kernel)
+};
+hipError_t ssdr_launch_wf_view_zoom(const SsdrWfViewArgs &a, hipStream_t stream);
+hipError_t ssdr_launch_wf_view_finish(const SsdrWfViewArgs &a, hipStream_t stream);
 struct SsdrFusedArgs { SsdrWfArgs wf; SsdrAudioArgs au; uint32_t *ticket; uint32_t ticket_base; };
 // ticket: ssdr_chain_ws_kernel's pair counter; it stands at ticket_base at launch and is never reset: every trio draws its pairs and one ticket
 // beyond the last pair, so a launch of `grid` workgroups leaves it at ticket_base + pairs + grid * SSDR_WS_AUDIO_WAVES / 2 (ssdr_api.cpp)

@@ -405,6 +405,50 @@ class SsdrEngine:
         check(lib.ssdr_deemphasis_stats(self._ctx, C.byref(ms), C.byref(n), 1 if reset else 0), "ssdr_deemphasis_stats")
         return ms.value, n.value
 
+    def set_wf_views(self, views):
+        """The waterfall views, replacing the whole list: a sequence of (channel, zoom, offset_hz), channels ascending and unique, zoom
+        2, 4 or 8, offset_hz the zoom centre from the IQ band's centre; at most 256; an empty sequence removes them all.  A view that
+        was in the old list with the same three values keeps its stream, any other starts from silence.  A value that does not fit
+        the struct raises ValueError before the library is called; a list the library refuses raises SsdrError (SSDR_EINVAL / SSDR_ESTATE).
+        Either way nothing changes."""
+        rows = [(int(ch), int(z), float(off)) for ch, z, off in views]
+        if any(not 0 <= ch < 2 ** 32 or not 0 <= z < 2 ** 32 for ch, z, _ in rows):
+            raise ValueError("waterfall views %r: out of range" % (views,))
+        arr = (L.WfView * max(len(rows), 1))(*[L.WfView(*r) for r in rows])
+        check(lib.ssdr_set_wf_views(self._ctx, arr if rows else None, len(rows)), "ssdr_set_wf_views")
+
+    def wf_views(self):
+        """-> [(channel, zoom, offset_hz), ...] the views as set"""
+        n = C.c_uint32(0)
+        arr = (L.WfView * L.WF_VIEWS_MAX)()
+        check(lib.ssdr_get_wf_views(self._ctx, arr, C.byref(n)), "ssdr_get_wf_views")
+        return [(v.channel, v.zoom, v.offset_hz) for v in arr[:n.value]]
+
+    def wf_view_lines(self):
+        """-> [int16 [k_i, 1024], ...]: the byte lines (N = 1) each view produced in the last run_wf / run_chain, in list order"""
+        n_views = len(self.wf_views())
+        per, total = (C.c_uint32 * max(n_views, 1))(), C.c_uint32(0)
+        check(lib.ssdr_wf_view_lines(self._ctx, None, per, C.byref(total), 0), "ssdr_wf_view_lines")
+        out = np.empty((total.value, L.NFFT), np.int16)
+        if total.value:
+            check(lib.ssdr_wf_view_lines(self._ctx, out.ctypes.data, per, C.byref(total), 0), "ssdr_wf_view_lines")
+        cuts = np.cumsum([0] + list(per[:n_views]))
+        return [out[cuts[i]:cuts[i + 1]] for i in range(n_views)]
+
+    def read_wf_view(self, index):
+        """-> int16 [n, 2]: the zoomed I,Q samples view `index` produced in the last run"""
+        n = C.c_uint32(0)
+        check(lib.ssdr_read_wf_view(self._ctx, int(index), None, C.byref(n)), "ssdr_read_wf_view")
+        out = np.empty((n.value, 2), np.int16)
+        check(lib.ssdr_read_wf_view(self._ctx, int(index), out.ctypes.data, C.byref(n)), "ssdr_read_wf_view")
+        return out
+
+    def wf_view_stats(self, reset=False):
+        """-> (total_ms, runs) of the view stage since the last reset (the time only with set_profiling on)"""
+        ms, n = C.c_float(), C.c_uint32()
+        check(lib.ssdr_wf_view_stats(self._ctx, C.byref(ms), C.byref(n), 1 if reset else 0), "ssdr_wf_view_stats")
+        return ms.value, n.value
+
     def audio_iq(self):
         """-> int16 [n_ch, n_frames*512, 2]: I,Q of the channels in "iq" mode for the last run_audio (rows of other modes: 0)"""
         out = np.empty((self.n_ch, self.audio_frames * L.FRAME, 2), np.int16)

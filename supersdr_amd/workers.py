@@ -91,9 +91,11 @@ class SuperframeResult:
     With wire compression on some channels (IQHub.set_compression): snd_adpcm uint8 [n, frames*256] / wf_adpcm uint8 [lines, n, 517],
     a row per channel of snd_adpcm_channels / wf_adpcm_channels (None: no channel compresses).
     With a squelch acting on some channel (IQHub.set_squelch): squelched uint8 [n_ch, frames], 1 where the frame was zeroed (None: no
-    channel squelches)."""
+    channel squelches).
+    With waterfall views (IQHub.set_wf_view): view_channels lists the channels that have one, ascending, and view_lines holds for each
+    an int16 [k, 1024] of the k byte lines (N = 1) its view produced in this run, k >= 0 (both None: no view is set)."""
     __slots__ = ("seq", "wf", "n_avg", "color", "chans", "pcm", "rssi", "flags", "play", "mono", "iq", "wire_rssi", "post_channels", "out_channels",
-                 "snd_adpcm", "wf_adpcm", "snd_adpcm_channels", "wf_adpcm_channels", "squelched")
+                 "snd_adpcm", "wf_adpcm", "snd_adpcm_channels", "wf_adpcm_channels", "squelched", "view_lines", "view_channels")
 
     def __init__(self, **kw):
         for k in self.__slots__:
@@ -275,6 +277,8 @@ class IQHub:
         self._deemp = {}                             # channel -> (am, nfm), for the channels that were given any
         self._sq_act = set()                         # channels whose setting acts in their current mode (the engine squelches them)
         self._comp_snd, self._comp_wf = [], []       # channels with "SET compression=1" / "SET wf_comp=1", sorted (the engine's row order)
+        self._views = {}                             # channel -> (zoom, offset_hz): the waterfall views (set_wf_view)
+        self._wf_listeners = {}                      # channel -> W/F streams open on it (the last one to close takes the view with it)
         self._want_n = np.ones(self.n_ch, np.int32)  # averaging_n asked for by each channel's waterfall client
         self._want_all = {1: self.n_ch}              # N -> channels that want it (all channels / channels with a client)
         self._want_cli = {}
@@ -319,6 +323,7 @@ class IQHub:
         with self._lock:
             if wf and self.wf_queue._q.pop(c, None) is not None:
                 self._wf_att.remove(c)
+                self._drop_wf_view(c)                # nobody is left to look at it
             if snd and self.snd_queue._q.pop(c, None) is not None:
                 self._snd_att.remove(c)
             n_q = (c in self.wf_queue._q) + (c in self.snd_queue._q)
@@ -495,6 +500,57 @@ class IQHub:
         """zoom centre of one channel, Hz from the centre of its IQ band (restarts that channel's zoomed stream)"""
         with self._lock:
             self.engine.set_wf_center(channel, [float(offset_hz)])
+
+    def wf_view(self, channel):
+        """-> (zoom, offset_hz) of the channel's waterfall view, or None: the channel gets the full-span lines"""
+        with self._lock:
+            return self._views.get(int(channel))
+
+    def set_wf_view(self, channel, zoom, offset_hz=0.0):
+        """The waterfall view of one channel (ssdr_set_wf_views): its wf_queue then carries the lines of a span 1 / zoom of the IQ band
+        around offset_hz (Hz from the band's centre) instead of the full-span line -- 0..k single lines (N = 1) per superframe, one
+        per 1024 zoomed samples (per 512 at hop 512).  zoom 2, 4 or 8; zoom 1 removes the view.  The other channels see no
+        difference, and the views of other channels keep their streams.  A changed view starts from silence.  ValueError out of
+        range, on the pipelined hub and on a hub built with zoom > 1 (before the engine is touched), and then nothing changes."""
+        c = int(channel)
+        if not 0 <= c < self.n_ch:
+            raise IndexError("channel %d of %d" % (c, self.n_ch))
+        if self.pipeline:
+            raise ValueError("a waterfall view needs the synchronous hub (the pipelined feed does not run the views)")
+        if self.zoom != 1:
+            raise ValueError("a waterfall view needs a hub built with zoom=1 (views and the hub-wide zoom exclude each other)")
+        if isinstance(zoom, bool) or int(zoom) != zoom or int(zoom) not in (1, 2, 4, 8):
+            raise ValueError("waterfall view zoom %r: 1 (no view), 2, 4 or 8" % (zoom,))
+        off = float(offset_hz)
+        if not abs(off) <= self.kiwi_rate / 2.0:         # (NaN fails as well)
+            raise ValueError("waterfall view centre %r Hz is outside the +-%g Hz IQ band" % (offset_hz, self.kiwi_rate / 2.0))
+        with self._lock:
+            new = dict(self._views)
+            if int(zoom) == 1:
+                new.pop(c, None)
+            else:
+                new[c] = (int(zoom), off)
+            if new == self._views:
+                return
+            if not hasattr(self.engine, "set_wf_views"):
+                raise ValueError("this engine has no waterfall views (set_wf_views)")
+            self.engine.set_wf_views([(ch,) + new[ch] for ch in sorted(new)])      # refused by the library: the old list stays
+            self._views = new
+
+    def _drop_wf_view(self, c):
+        if c in self._views:
+            self.set_wf_view(c, 1)
+
+    def _wf_listener_changed(self, channel, step):
+        """a W/F stream opened (+1) or closed (-1) on the channel: the last one to close removes the channel's view"""
+        c = int(channel)
+        with self._lock:
+            n = self._wf_listeners.get(c, 0) + step
+            if n > 0:
+                self._wf_listeners[c] = n
+            else:
+                self._wf_listeners.pop(c, None)
+                self._drop_wf_view(c)
 
     def set_averaging(self, n, channel=None):
         """channel=None: every channel wants N (one receiver, or a caller that owns the whole hub)."""
@@ -698,6 +754,8 @@ class IQHub:
         wf = eng.run_wf()                             # [lines, n_ch, 1024]
         wf_sel = list(self._comp_wf) if self._comp_wf else None
         wf_adpcm = eng.wf_adpcm() if wf_sel else None                           # [lines, n_wf, 517] ("SET wf_comp=1")
+        view_ch = sorted(self._views) if self._views else None
+        view_lines = eng.wf_view_lines() if view_ch else None                   # per view [k, 1024], k >= 0 (set_wf_view)
         color = chans = None
         if self.gpu_post and (self._n_wf_clients or self._n_snd_clients):
             self._sync_display_state()
@@ -720,7 +778,7 @@ class IQHub:
         self._hand_out(SuperframeResult(seq=self.superframes, wf=wf, n_avg=n_avg, color=color, chans=chans, pcm=pcm, rssi=rssi,
                                         flags=flags, play=play, mono=mono, iq=iqo, wire_rssi=wire_rssi, post_channels=self._post_sel,
                                         snd_adpcm=snd_adpcm, wf_adpcm=wf_adpcm, snd_adpcm_channels=snd_sel, wf_adpcm_channels=wf_sel,
-                                        squelched=closed))
+                                        squelched=closed, view_lines=view_lines, view_channels=view_ch))
 
     def _hand_out(self, r):
         self.last = r
@@ -731,8 +789,15 @@ class IQHub:
         opos = None if r.out_channels is None else (pos if r.out_channels is r.post_channels else {c: i for i, c in enumerate(r.out_channels)})
         wpos = {} if r.wf_adpcm is None or not len(r.wf_adpcm) else {c: i for i, c in enumerate(r.wf_adpcm_channels)}
         spos = {} if r.snd_adpcm is None else {c: i for i, c in enumerate(r.snd_adpcm_channels)}
+        vpos = {} if not r.view_channels else {c: i for i, c in enumerate(r.view_channels)}
         for c in self._wf_att:
             q = self.wf_queue._q[c]
+            if c in vpos:                                    # a channel with a view gets the view's lines, not the full-span one
+                for line in r.view_lines[vpos[c]]:
+                    # single lines of a receiver's own cadence: their colours as for a client that bins for itself (ssdr_db2col_line)
+                    post = self.db2col_line(c, line, 1) if self.gpu_post and self.wf_clients[c] is not None else None
+                    _put_drop_oldest(q, (line.copy(), 1, post))
+                continue
             pc = c if pos is None else pos.get(c)
             oc = c if opos is None else opos.get(c)          # row of the channel's line (lazy_out: attached after the batch left -> not in it)
             if oc is None:
@@ -934,7 +999,10 @@ class GpuStream:
     only if it was produced with the flag on: frames queued before the switch still go out raw, the race a real link has too.  A
     frame the hub's drop-oldest queue drops desynchronises the client's SND decoder, as a frame lost on a real link would.
     close_connection turns a flag this stream turned on off again, so the next connection starts from (0, 0).
-    "SET zoom=%d start=%d" (:741, 839) is remembered (`zoom`, `start`); the rest (auth, keepalive, ...)
+    "SET zoom=%d start=%d" (:741, 839) is remembered (`zoom`, `start`) and nothing else: how a span of 30 MHz / 2^zoom maps onto the
+    channel's 12 kHz IQ band is undefined, so it does not move the channel's waterfall view -- that is
+    WaterfallSeams.set_iq_view / IQHub.set_wf_view, in the band's own terms.  The last W/F stream of a channel to close takes the
+    channel's view with it.  The rest (auth, keepalive, ...)
     has no meaning without a server and is accepted.  A modulation without a demodulator here, or a frequency outside
     the channel's IQ band, raises ValueError instead of being demodulated as something else.  "SET mod=iq" selects the
     channel's filtered baseband itself (SSDR_MODE_IQ): its SND frames then carry I,Q pairs behind a GNSS stamp.
@@ -954,6 +1022,8 @@ class GpuStream:
         self._greeting = deque()
         if hasattr(hub, "attach"):                   # this channel has a listener now: its results are queued from here on
             hub.attach(self.channel, wf=(kind != "SND"), snd=(kind == "SND"))
+        if kind != "SND" and hasattr(hub, "_wf_listener_changed"):
+            hub._wf_listener_changed(self.channel, +1)
         if kind == "SND":
             rate = int(getattr(hub, "kiwi_rate", L.RATE))
             # every server announces its rate first; the reference takes KIWI_RATE, KIWI_RATE_TRUE, SAMPLE_RATIO from it (:988-994)
@@ -1083,6 +1153,8 @@ class GpuStream:
         if self._deemp_on and not self.closed:       # ... and with the de-emphasis off
             self._deemp_on = False
             self.hub.set_deemphasis(self.channel, am=0, nfm=0)
+        if self.kind != "SND" and not self.closed and hasattr(self.hub, "_wf_listener_changed"):
+            self.hub._wf_listener_changed(self.channel, -1)      # the last one to look takes the channel's view with it
         self.closed = True
 
 
@@ -1199,7 +1271,17 @@ class WaterfallSeams:
         self.hub.set_wf_center(self.channel, (float(khz) - self.iq_center_khz) * 1000.0)
         self.iq_zoom_center_khz = float(khz)
 
+    def set_iq_view(self, zoom, khz=None):
+        """this listener's own waterfall zoom (IQHub.set_wf_view): zoom 2, 4 or 8 around khz, an absolute frequency inside the channel's
+        IQ band (default: its centre); zoom 1: the full span again.  Works while the streams run and leaves every other channel
+        alone; iq_bin_to_khz / iq_khz_to_bin follow.  ValueError out of range, and then nothing changes."""
+        khz = self.iq_center_khz if khz is None else float(khz)
+        self.hub.set_wf_view(self.channel, zoom, (khz - self.iq_center_khz) * 1000.0)
+
     def _iq_axis(self):
+        view = self.hub.wf_view(self.channel) if hasattr(self.hub, "wf_view") else None
+        if view is not None:                             # the axis of the lines this channel's queue carries now
+            return self.iq_center_khz + view[1] / 1000.0, getattr(self.hub, "iq_span_khz", IQ_SPAN_KHZ) / view[0]
         span = getattr(self.hub, "iq_span_khz", IQ_SPAN_KHZ) / getattr(self.hub, "zoom", 1)
         return getattr(self, "iq_zoom_center_khz", self.iq_center_khz), span
 
