@@ -104,6 +104,7 @@ struct ssdr_ctx {
     bool summary_dirty = true;                          // path counts / any channel in IQ mode: recounted after the constants change
     uint32_t sum_paths[SSDR_PATH_COUNT] = {0, 0, 0};
     bool sum_any_iq = false;
+    uint32_t sum_hang = 0;                              // channels whose AGC hangs (hang_frames != 0): which fused AM kernel runs
     hipStream_t path_stream[SSDR_PATH_COUNT - 1] = {};  // the audio kernels of different paths run side by side
     hipEvent_t ev_fork = nullptr, ev_path[SSDR_PATH_COUNT - 1] = {};
     int fused_enabled = 1;                              // ssdr_set_fused: 0 never, 1 at hop 1024 (default), 2 at hop 512 as well, 3 + the wave-specialised kernel
@@ -940,10 +941,12 @@ static void chan_summary(ssdr_ctx *c)
     if (!c->summary_dirty) return;
     for (int p = 0; p < SSDR_PATH_COUNT; p++) c->sum_paths[p] = 0;
     c->sum_any_iq = false;
+    c->sum_hang = 0;
     for (uint32_t ch = 0; ch < c->n_ch; ch++) {
         const int path = ssdr_audio_path(c->h_consts[ch]);
         c->sum_paths[path]++;
         c->sum_any_iq = c->sum_any_iq || c->h_consts[ch].mode == SSDR_MODE_IQ;
+        c->sum_hang += c->h_consts[ch].hang_frames != 0;
     }
     c->summary_dirty = false;
 }
@@ -1590,7 +1593,7 @@ static int audio_stage(ssdr_ctx *c, Batch &b, ChainPlan plan, const SsdrWfArgs *
             HIP_TRY(ssdr_launch_chain_ws(fa, grid_g ? grid_g : 1, s));
             c->ws_ticket += (uint32_t)pairs + (grid_g ? grid_g : 1) * (SSDR_WS_AUDIO_WAVES / 2);     // (wraps as the device word does)
         } else if (c->exact_bins) HIP_TRY(ssdr_launch_fused_exact_am(fa, c->d_tw64, s));
-        else HIP_TRY(ssdr_launch_fused_am(fa, grid ? grid : 1, s));
+        else HIP_TRY(ssdr_launch_fused_am(fa, grid ? grid : 1, s, c->sum_hang != 0));
         SSDR_TRY(timed_end(c, SSDR_K_FUSED, s));
         if (fa.wf.tail)          // hop 512: only now may the carried half-line (the kernel's line 0 read it) become this batch's last one
             HIP_TRY(hipMemcpy2DAsync(c->d_wf_tail, (SSDR_NFFT / 2) * 4, fa.wf.iq + (size_t)(fa.wf.n_lines - 1) * SSDR_FRAME,

@@ -299,6 +299,52 @@ SSDR_DEV float agc_pack_store(const float (&p)[8], const float (&aud)[8], int l,
     return g;
 }
 
+// The fused AM kernel's frame tail (ssdr_wf.hip:ssdr_fused_am_kernel): agc_pack_store's arithmetic, operation for operation, with the
+// block's peak `pm` always the caller's and the hang a compile-time matter.  HANG == false: no channel of the launch hangs (K == 0
+// everywhere, the reference's default) -- the hang memory does not exist here, nothing tests K.  HANG == true: agc_pack_store as it
+// is, K == 0 channels among hanging ones included.
+template <bool HANG> struct AgcHang { float m[8]; };         // a channel's hang memory (ssdr_chan_state.agc_m) ...
+template <> struct AgcHang<false> {};                        // ... or nothing at all
+
+template <bool HANG>
+SSDR_DEV void agc_pack_store_fused(const float (&aud)[8], int l, const AgcK &k, float &agc_d, AgcHang<HANG> &hang, int16_t *dst, float pm)
+{
+    const float al = ssdr_log2p(pm);
+    const float fl = (float)l;
+    const float d8 = k.d8;
+    float e;
+    auto no_hang = [&] {
+        const float P = scan_max(fmaf(fl, d8, al));
+        e = vmax(fmaf(-fl, d8, P), fmaf(-(fl + 1.0f), d8, agc_d));
+        agc_d = lane63(e);
+    };
+    if constexpr (!HANG) {
+        no_hang();
+    } else if (k.K == 0) {
+        no_hang();
+    } else {
+        float (&agc_m)[8] = hang.m;
+        const float P = scan_max(al);
+        float maxM = agc_m[0], mK = agc_m[0];
+#pragma unroll
+        for (int i = 1; i < 8; i++)
+            if ((uint32_t)i < k.K) { maxM = fmaxf(maxM, agc_m[i]); mK = agc_m[i]; }
+        e = vmax(vmax(P, maxM), fmaf(-(fl + 1.0f), d8, agc_d));
+        agc_d = fmaxf(fmaf(-64.0f, d8, agc_d), mK);
+#pragma unroll
+        for (int i = 7; i > 0; i--) agc_m[i] = agc_m[i - 1];
+        agc_m[0] = lane63(P);
+    }
+    const float g = ssdr_exp2p(fmaf(k.c1, vmax(e, k.knee), k.c0));
+    u32x4 w;
+#pragma unroll
+    for (int j = 0; j < 8; j += 2) {
+        const int i0 = __float2int_rn(aud[j] * g), i1 = __float2int_rn(aud[j + 1] * g);
+        w[j >> 1] = __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_pk_i16(i0, i1));
+    }
+    SSDR_NT_STORE(w, reinterpret_cast<u32x4 *>(dst));
+}
+
 // SSDR_MODE_IQ: the lane's eight filtered samples times the AGC gain as I | Q << 16 (round-half-even, saturating), 32 B per lane
 SSDR_DEV void iq_pack_store(const float (&yr)[8], const float (&yi)[8], float g, uint32_t *dst)
 {

@@ -149,7 +149,11 @@ __global__ __launch_bounds__(SSDR_WF_BLOCK, SSDR_WF_WAVES_PER_EU) void ssdr_wf_k
 // it one step earlier, and only that read is left to the L2: plain load, everything else streams) followed by the new one.
 // AVG (round 4): time binning N > 1 -- the wave owns its channel pair for the whole call, so the N-line sums stay in 16 registers
 // per lane across the lines of a group (carry in / out of partial groups as in ssdr_wf_kernel<true, .>).
-template <bool HOP, bool AVG = false>
+// HANG: whether any channel of the launch has an AGC hang (hang_frames != 0; the host counts them when the parameters change).  The
+// reference's default is none, and then the hang memory agc_m[8] is no part of the audio phase: it is neither fetched from the state
+// record, nor parked in the pad column, nor tested against K frame by frame, and the record keeps the words it had (what the K == 0
+// branch of agc_pack_store leaves as well).  HANG == true handles every mix of hanging and non-hanging channels.
+template <bool HOP, bool AVG = false, bool HANG = true>
 __global__ __launch_bounds__(SSDR_WF_BLOCK, SSDR_WF_WAVES_PER_EU) void ssdr_fused_am_kernel(SsdrFusedArgs fa)
 {
     __shared__ __attribute__((aligned(16))) unsigned char smem[LDS_TOTAL];
@@ -181,16 +185,19 @@ __global__ __launch_bounds__(SSDR_WF_BLOCK, SSDR_WF_WAVES_PER_EU) void ssdr_fuse
         uint32_t flag_keep[2] = {0u, 0u};
         // (rows 16..31 of the pad column: the line staging reuses the first 2 KB of the buffer)
         auto pad = [&](int c, int i) -> float & { return xch_wave[c * XCH_FLOATS + 33 * (i + 16) + 32]; };
+        constexpr int PAD_TAIL = HANG ? 10 : 2;            // rows: dc, agc_d, (HANG: agc_m[8],) the four tail powers
         if (lane < 2) {
             const uint32_t cc = min(2 * pair + (uint32_t)lane, a.n_ch - 1);
             const ssdr_chan_state st = u.state[cc];
             pad(lane, 0) = st.dc;
             pad(lane, 1) = st.agc_d;
+            if (HANG) {
 #pragma unroll
-            for (int i = 0; i < 8; i++) pad(lane, 2 + i) = st.agc_m[i];
+                for (int i = 0; i < 8; i++) pad(lane, 2 + i) = st.agc_m[i];
+            }
             const uint4 t = *reinterpret_cast<const uint4 *>(u.hist + (size_t)cc * SSDR_HIST + SSDR_HIST - 4);
-            pad(lane, 10) = __uint_as_float(iq_power(t.x)); pad(lane, 11) = __uint_as_float(iq_power(t.y));
-            pad(lane, 12) = __uint_as_float(iq_power(t.z)); pad(lane, 13) = __uint_as_float(iq_power(t.w));
+            pad(lane, PAD_TAIL) = __uint_as_float(iq_power(t.x)); pad(lane, PAD_TAIL + 1) = __uint_as_float(iq_power(t.y));
+            pad(lane, PAD_TAIL + 2) = __uint_as_float(iq_power(t.z)); pad(lane, PAD_TAIL + 3) = __uint_as_float(iq_power(t.w));
         }
         wave_lds_sync();
 
@@ -203,15 +210,18 @@ __global__ __launch_bounds__(SSDR_WF_BLOCK, SSDR_WF_WAVES_PER_EU) void ssdr_fuse
         constexpr int FRAMES_PER_LINE = HOP ? 1 : 2;
         for (uint32_t line = 0; line < a.n_lines; line++, src += LINE_STEP) {
             // ---- the carried state out of its resting place (the powers below overwrite it)
-            float dc[2], agc_d[2], agc_m[2][8];
+            float dc[2], agc_d[2];
+            AgcHang<HANG> hang[2];
             uint32_t tail_q[2][4];
 #pragma unroll
             for (int c = 0; c < 2; c++) {
                 dc[c] = pad(c, 0); agc_d[c] = pad(c, 1);
+                if constexpr (HANG) {
 #pragma unroll
-                for (int i = 0; i < 8; i++) agc_m[c][i] = pad(c, 2 + i);
+                    for (int i = 0; i < 8; i++) hang[c].m[i] = pad(c, 2 + i);
+                }
 #pragma unroll
-                for (int i = 0; i < 4; i++) tail_q[c][i] = __float_as_uint(pad(c, 10 + i));
+                for (int i = 0; i < 4; i++) tail_q[c][i] = __float_as_uint(pad(c, PAD_TAIL + i));
             }
             wave_lds_sync();
             // ---- audio, phase 1: the line's raw samples into the (still unused) transpose buffer, in natural order.  Nobody needs them
@@ -279,7 +289,7 @@ __global__ __launch_bounds__(SSDR_WF_BLOCK, SSDR_WF_WAVES_PER_EU) void ssdr_fuse
                                       tail_q[c][2] >= 0x3FFF0001u || tail_q[c][3] >= 0x3FFF0001u;
                     const bool clip = trig ? wave_any(raw_clipped(rw)) : false;    // the exact check, only then
                     demod_am<true>(p, dc[c], aud);
-                    agc_pack_store(p, aud, lane, agc_c, agc_d[c], agc_m[c], u.pcm + ((uint64_t)cc * n_frames + frame) * SSDR_FRAME + 8 * lane, pmx);
+                    agc_pack_store_fused<HANG>(aud, lane, agc_c, agc_d[c], hang[c], u.pcm + ((uint64_t)cc * n_frames + frame) * SSDR_FRAME + 8 * lane, pmx);
                     rssi_flag_step(p, clip, frame, n_frames, lane, cal_c, rssi_sum[c], flag_keep[c],
                                    u.rssi + (uint64_t)cc * n_frames, u.flags + (uint64_t)cc * n_frames);
                 }
@@ -299,10 +309,12 @@ __global__ __launch_bounds__(SSDR_WF_BLOCK, SSDR_WF_WAVES_PER_EU) void ssdr_fuse
                 for (int c = 0; c < 2; c++) {
                     if (lane != c) continue;
                     pad(c, 0) = dc[c]; pad(c, 1) = agc_d[c];
+                    if constexpr (HANG) {
 #pragma unroll
-                    for (int i = 0; i < 8; i++) pad(c, 2 + i) = agc_m[c][i];
+                        for (int i = 0; i < 8; i++) pad(c, 2 + i) = hang[c].m[i];
+                    }
 #pragma unroll
-                    for (int i = 0; i < 4; i++) pad(c, 10 + i) = __uint_as_float(tail_q[c][i]);
+                    for (int i = 0; i < 4; i++) pad(c, PAD_TAIL + i) = __uint_as_float(tail_q[c][i]);
                 }
             }
             wave_lds_sync();
@@ -381,8 +393,10 @@ __global__ __launch_bounds__(SSDR_WF_BLOCK, SSDR_WF_WAVES_PER_EU) void ssdr_fuse
                 st.phi1 += (uint32_t)(SSDR_FRAME * n_frames) * kc.dphi1;
                 st.phi2 += (uint32_t)(SSDR_FRAME * n_frames) * kc.dphi2;
                 st.dc = pad(c, 0); st.agc_d = pad(c, 1);
+                if (HANG) {                                    // (else: the words the record came with)
 #pragma unroll
-                for (int i = 0; i < 8; i++) st.agc_m[i] = pad(c, 2 + i);
+                    for (int i = 0; i < 8; i++) st.agc_m[i] = pad(c, 2 + i);
+                }
                 if (lane == 0) u.state[cc] = st;
             }
         }
@@ -432,27 +446,44 @@ hipError_t ssdr_launch_wf(const SsdrWfArgs &a, uint32_t grid, hipStream_t stream
     return hipGetLastError();
 }
 
-hipError_t ssdr_launch_fused_am(const SsdrFusedArgs &a, uint32_t grid, hipStream_t stream)
+template <bool HANG>
+static void launch_fused_am(const SsdrFusedArgs &a, uint32_t grid, hipStream_t stream)
 {
     if (a.wf.n_avg > 1) {
-        if (a.wf.tail) hipLaunchKernelGGL((ssdr_fused_am_kernel<true, true>), dim3(grid), dim3(SSDR_WF_BLOCK), 0, stream, a);
-        else hipLaunchKernelGGL((ssdr_fused_am_kernel<false, true>), dim3(grid), dim3(SSDR_WF_BLOCK), 0, stream, a);
+        if (a.wf.tail) hipLaunchKernelGGL((ssdr_fused_am_kernel<true, true, HANG>), dim3(grid), dim3(SSDR_WF_BLOCK), 0, stream, a);
+        else hipLaunchKernelGGL((ssdr_fused_am_kernel<false, true, HANG>), dim3(grid), dim3(SSDR_WF_BLOCK), 0, stream, a);
     } else {
-        if (a.wf.tail) hipLaunchKernelGGL((ssdr_fused_am_kernel<true, false>), dim3(grid), dim3(SSDR_WF_BLOCK), 0, stream, a);
-        else hipLaunchKernelGGL((ssdr_fused_am_kernel<false, false>), dim3(grid), dim3(SSDR_WF_BLOCK), 0, stream, a);
+        if (a.wf.tail) hipLaunchKernelGGL((ssdr_fused_am_kernel<true, false, HANG>), dim3(grid), dim3(SSDR_WF_BLOCK), 0, stream, a);
+        else hipLaunchKernelGGL((ssdr_fused_am_kernel<false, false, HANG>), dim3(grid), dim3(SSDR_WF_BLOCK), 0, stream, a);
     }
+}
+
+// any_hang: whether a channel has hang_frames != 0 (the host's count of them, taken when the parameters change)
+hipError_t ssdr_launch_fused_am(const SsdrFusedArgs &a, uint32_t grid, hipStream_t stream, bool any_hang)
+{
+    if (any_hang) launch_fused_am<true>(a, grid, stream);
+    else launch_fused_am<false>(a, grid, stream);
     return hipGetLastError();
 }
 
-hipError_t ssdr_fused_blocks_per_cu(int *blocks)
+template <bool HANG>
+static hipError_t fused_blocks_per_cu(int *blocks)
 {
     int b[4] = {0, 0, 0, 0};
-    hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&b[0], ssdr_fused_am_kernel<false, false>, SSDR_WF_BLOCK, 0);
-    if (e == hipSuccess) e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&b[1], ssdr_fused_am_kernel<true, false>, SSDR_WF_BLOCK, 0);
-    if (e == hipSuccess) e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&b[2], ssdr_fused_am_kernel<false, true>, SSDR_WF_BLOCK, 0);
-    if (e == hipSuccess) e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&b[3], ssdr_fused_am_kernel<true, true>, SSDR_WF_BLOCK, 0);
-    *blocks = b[0];
-    for (int i = 1; i < 4; i++) *blocks = b[i] < *blocks ? b[i] : *blocks;
+    hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&b[0], ssdr_fused_am_kernel<false, false, HANG>, SSDR_WF_BLOCK, 0);
+    if (e == hipSuccess) e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&b[1], ssdr_fused_am_kernel<true, false, HANG>, SSDR_WF_BLOCK, 0);
+    if (e == hipSuccess) e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&b[2], ssdr_fused_am_kernel<false, true, HANG>, SSDR_WF_BLOCK, 0);
+    if (e == hipSuccess) e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&b[3], ssdr_fused_am_kernel<true, true, HANG>, SSDR_WF_BLOCK, 0);
+    for (int i = 0; i < 4; i++) *blocks = b[i] < *blocks ? b[i] : *blocks;
+    return e;
+}
+
+// workgroups of the fused kernel that are resident per CU (min over all eight instances)
+hipError_t ssdr_fused_blocks_per_cu(int *blocks)
+{
+    *blocks = 0x7fffffff;
+    hipError_t e = fused_blocks_per_cu<true>(blocks);
+    if (e == hipSuccess) e = fused_blocks_per_cu<false>(blocks);
     return e;
 }
 

@@ -9,8 +9,9 @@ FLAGS = "--offload-arch=gfx950 -O3 -std=c++17 -fPIC -ffp-contract=off -fno-fast-
 KERNELS = [("ssdr_wf.hip", "ssdr_wf_kernelILb0ELb0E", "ssdr_wf_kernel<false, false>"),
            ("ssdr_wf.hip", "ssdr_wf_kernelILb1ELb0E", "ssdr_wf_kernel<true, false>"),
            ("ssdr_wf.hip", "ssdr_wf_kernelILb0ELb1E", "ssdr_wf_kernel<false, true>"),
-           ("ssdr_wf.hip", "ssdr_fused_am_kernelILb0E", "ssdr_fused_am_kernel<false>  (hop 1024)"),
-           ("ssdr_wf.hip", "ssdr_fused_am_kernelILb1E", "ssdr_fused_am_kernel<true>   (hop 512)"),
+           ("ssdr_wf.hip", "ssdr_fused_am_kernelILb0ELb0ELb0E", "ssdr_fused_am_kernel<false, false, false>  (hop 1024, no channel hangs)"),
+           ("ssdr_wf.hip", "ssdr_fused_am_kernelILb0ELb0ELb1E", "ssdr_fused_am_kernel<false, false, true>   (hop 1024, with the hang memory)"),
+           ("ssdr_wf.hip", "ssdr_fused_am_kernelILb1ELb0ELb0E", "ssdr_fused_am_kernel<true, false, false>   (hop 512, no channel hangs)"),
            ("ssdr_audio.hip", "ssdr_audio_kernelILi0E", "ssdr_audio_kernel<0>  general: NCO -> FIR -> demodulator"),
            ("ssdr_audio.hip", "ssdr_audio_kernelILi1E", "ssdr_audio_kernel<1>  full-band lane shift"),
            ("ssdr_audio.hip", "ssdr_audio_kernelILi2E", "ssdr_audio_kernel<2>  full-band AM (no NCO, no FIR)"),
