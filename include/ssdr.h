@@ -345,21 +345,23 @@ int ssdr_adpcm_encode(ssdr_ctx *ctx, const int16_t *pcm, uint32_t n_streams, uin
  * zero and their state does not move.  A channel flagged for W/F has every byte line of ssdr_run_wf (N = 1) encoded from
  * (0, 0): the 1024 bytes as samples 0..255 and 10 samples repeating the last one, 517 bytes (the client decodes 1034 samples
  * and keeps 1024, :476-479).  With no flag set nothing is launched.  The encoder is timed as SSDR_K_ADPCM (with profiling on).
- * While any flag is set ssdr_feed_open and ssdr_checkpoint_save / _load return SSDR_ESTATE.  ssdr_reset_state leaves the
- * encoder state alone: it belongs to the link, not to the DSP. */
+ * While any flag is set ssdr_feed_open (without SSDR_FEED_LISTEN) and ssdr_checkpoint_save / _load return SSDR_ESTATE.
+ * ssdr_reset_state leaves the encoder state alone: it belongs to the link, not to the DSP. */
 /* Channels [first, first + count): snd_on / wf_on uint8 [count], 0 off, anything else on; either pointer may be NULL (that flag
  * stays as it is).  An SND flag going from 0 to 1 resets the channel's encoder state to (0, 0), where a new decoder starts;
- * setting one that is already on does not.  SSDR_ESTATE while a pipelined feed is open. */
+ * setting one that is already on does not.  SSDR_ESTATE while a pipelined feed is open, unless it was opened with
+ * SSDR_FEED_LISTEN: then the flags act on every batch submitted after the call and on none submitted before it. */
 int ssdr_set_compression(ssdr_ctx *ctx, uint32_t first, uint32_t count, const uint8_t *snd_on, const uint8_t *wf_on);
 /* The flagged channels, ascending (which: 0 SND, 1 W/F): *count of them; list (may be NULL) receives them.  The rows of
  * ssdr_audio_adpcm / ssdr_wf_adpcm are in this order. */
 int ssdr_compression_channels(ssdr_ctx *ctx, int which, uint32_t *list, uint32_t *count);
 /* The SND payloads of the last audio run: out uint8 [n_snd][n_frames * 256], a row per SND-flagged channel.  SSDR_ESTATE if no
- * SND flag is set, or there has been no audio run with the flags as they are. */
+ * SND flag is set, there has been no audio run with the flags as they are, or a feed with SSDR_FEED_LISTEN is open (its
+ * batches' payloads are the slots': ssdr_feed_collect_listen). */
 int ssdr_audio_adpcm(ssdr_ctx *ctx, uint8_t *out, int out_is_device);
 /* The W/F payloads of the last ssdr_run_wf: out uint8 [*lines][n_wf][517] (out may be NULL: *lines only).  *lines = 0 when that
- * run's N was not 1 (only byte lines go on the wire).  SSDR_ESTATE if no W/F flag is set, or there has been no ssdr_run_wf with the
- * flags as they are. */
+ * run's N was not 1 (only byte lines go on the wire).  SSDR_ESTATE if no W/F flag is set, there has been no ssdr_run_wf with the
+ * flags as they are, or a feed with SSDR_FEED_LISTEN is open (ssdr_feed_collect_listen). */
 int ssdr_wf_adpcm(ssdr_ctx *ctx, uint8_t *out, uint32_t *lines, int out_is_device);
 
 /* -- audio squelch: the KiwiSDR's "SET squelch=<v> max=<m>" (kiwi/client.py:255-256, the old server's SetSquelch(v, max)) and
@@ -384,7 +386,8 @@ int ssdr_wf_adpcm(ssdr_ctx *ctx, uint8_t *out, uint32_t *lines, int out_is_devic
  * before the first nonzero level nothing is allocated).
  * While any channel has a level above 0 in either setting (acting or not: a mode change could make it act) ssdr_feed_open and
  * ssdr_checkpoint_save / _load return SSDR_ESTATE, and while a pipelined feed is open ssdr_set_squelch returns SSDR_ESTATE: the
- * rule the noise blanker and the wire encoders follow. */
+ * rule the noise blanker and the wire encoders follow.  A feed opened with SSDR_FEED_LISTEN lifts both refusals of the feed (not
+ * the checkpoints'): ssdr_set_squelch then acts on every batch submitted after the call and on none submitted before it. */
 typedef struct ssdr_squelch_params {
     uint32_t fm_level;      /* "squelch=<v> max=<m>": v 0..99, 0 = off */
     uint32_t fm_max;        /* m 0..65535 */
@@ -397,8 +400,8 @@ typedef struct ssdr_squelch_params {
 int ssdr_set_squelch(ssdr_ctx *ctx, uint32_t first, uint32_t count, const ssdr_squelch_params *p);
 int ssdr_get_squelch(ssdr_ctx *ctx, uint32_t first, uint32_t count, ssdr_squelch_params *p);
 /* Which frames of the last audio run were zeroed: closed_out uint8 [n_ch][n_frames], 1 = closed.  Rows of channels whose acting
- * setting is off are zero.  SSDR_ESTATE if no channel squelches, or there has been no audio run with the settings (and modes) as
- * they are. */
+ * setting is off are zero.  SSDR_ESTATE if no channel squelches, there has been no audio run with the settings (and modes) as
+ * they are, or a feed with SSDR_FEED_LISTEN is open (ssdr_feed_collect_listen). */
 int ssdr_audio_squelch(ssdr_ctx *ctx, uint8_t *closed_out, int out_is_device);
 /* The tail of "param=<tail_s>" in frames (host only): round(tail_s * kiwi_rate / 512), halves up.  SSDR_EINVAL for a rate other
  * than 12000 / 20250, a negative or NaN tail_s, or more than 1024 frames. */
@@ -427,7 +430,9 @@ int ssdr_squelch_tail_frames(double tail_s, uint32_t kiwi_rate, uint32_t *frames
  * 1 % of them, 0.67 x and 0.60 x on BASELINE configs[3]'s mix (the squelch kernel: 0.18 x) -- bound by memory waits that the present
  * kernel no longer has; the present kernel has not been timed yet (tools/deemp_probe.py).
  * While any channel has a nonzero setting (acting or not: a mode change could make it act) ssdr_feed_open and
- * ssdr_checkpoint_save / _load return SSDR_ESTATE, and while a pipelined feed is open ssdr_set_deemphasis returns SSDR_ESTATE. */
+ * ssdr_checkpoint_save / _load return SSDR_ESTATE, and while a pipelined feed is open ssdr_set_deemphasis returns SSDR_ESTATE --
+ * the feed's two refusals unless it was opened with SSDR_FEED_LISTEN: then ssdr_set_deemphasis acts on every batch submitted after
+ * the call and on none submitted before it. */
 typedef struct ssdr_deemp_params {
     uint32_t am;            /* "de_emp=<n>" / "de_emp=<n> nfm=0": 0 off, 1 = 75 us, 2 = 50 us */
     uint32_t nfm;           /* "de_emp=<n> nfm=1": the same */
@@ -467,7 +472,8 @@ int ssdr_deemphasis_stats(ssdr_ctx *ctx, float *total_ms, uint32_t *launches, in
  * ssdr_wf_view_stats is the stage's own.  Cost beside a 65536-channel waterfall of 0.66 ms: 0.02 ms for 1 view, 0.11 ms for 256
  * at Z = 8 (profiles/wf_view_probe.txt).
  * While any view is set ssdr_feed_open and ssdr_checkpoint_save / _load return SSDR_ESTATE; while a pipelined feed is open
- * ssdr_set_wf_views with count > 0 returns SSDR_ESTATE; views and ssdr_set_wf_zoom > 1 exclude each other (whichever comes second
+ * ssdr_set_wf_views with count > 0 returns SSDR_ESTATE (a feed opened with SSDR_FEED_LISTEN lifts both refusals of the feed: the new
+ * list then acts on every batch submitted after the call); views and ssdr_set_wf_zoom > 1 exclude each other (whichever comes second
  * returns SSDR_ESTATE).  ssdr_set_hop, ssdr_set_decimation and ssdr_set_kiwi_rate restart every view (the last two recompute the
  * NCO steps from offset_hz); ssdr_reset_state restarts the views of the channels it names.  A view whose centre lies outside
  * the band after such a change of rate (9 kHz after D = 2 -> 1) keeps its offset_hz as set -- ssdr_get_wf_views reports it
@@ -485,10 +491,11 @@ typedef struct ssdr_wf_view {
 int ssdr_set_wf_views(ssdr_ctx *ctx, const ssdr_wf_view *views, uint32_t count);
 int ssdr_get_wf_views(ssdr_ctx *ctx, ssdr_wf_view *views /* may be NULL */, uint32_t *count);
 /* The view lines of the last run: lines_out int16 [*total_lines][1024], the views' lines one view after the other in list order
- * (may be NULL: counts only); lines_per_view uint32 [count].  SSDR_ESTATE if no view is set, or there has been no run with the
- * list as it is. */
+ * (may be NULL: counts only); lines_per_view uint32 [count].  SSDR_ESTATE if no view is set, there has been no run with the
+ * list as it is, or a feed with SSDR_FEED_LISTEN is open (ssdr_feed_collect_listen). */
 int ssdr_wf_view_lines(ssdr_ctx *ctx, int16_t *lines_out, uint32_t *lines_per_view, uint32_t *total_lines, int out_is_device);
-/* The zoomed samples view `view_index` produced in the last run (tests): iq_out int16 [n_in / Z][2] (host memory), *samples = n_in / Z */
+/* The zoomed samples view `view_index` produced in the last run (tests): iq_out int16 [n_in / Z][2] (host memory), *samples = n_in / Z.
+ * SSDR_ESTATE like ssdr_wf_view_lines. */
 int ssdr_read_wf_view(ssdr_ctx *ctx, uint32_t view_index, int16_t *iq_out, uint32_t *samples);
 /* The view stage's runs since the last reset (one per batch while a view is set), and with ssdr_set_profiling on their summed time
  * (one HIP-event pair around the stage's kernels; runs made with profiling off count, and add no time). */
@@ -540,6 +547,45 @@ int ssdr_wf_view_stats(ssdr_ctx *ctx, float *total_ms, uint32_t *launches, int r
 #define SSDR_FEED_LAZY_OUT 4u
 #define SSDR_FEED_LAZY_MAX 4096u
 int ssdr_feed_collect_lazy(ssdr_ctx *ctx, uint32_t *n_sel, int16_t **d_wf_sum, int16_t **d_pcm, float **d_rssi, uint8_t **d_flags);
+/* flags = SSDR_FEED_LISTEN (alone or with any of the others): the listener stages -- squelch, de-emphasis, wire compression, waterfall
+ * views -- run in the slot pipeline.  ssdr_feed_open then succeeds whatever of these the ctx carries (ssdr_set_concurrent, D != 1 and
+ * ssdr_set_wf_zoom > 1 still refuse, and so do the checkpoint calls), and ssdr_set_squelch, ssdr_set_deemphasis, ssdr_set_compression and
+ * ssdr_set_wf_views are accepted while the feed is open, with their state rules, argument checks and all-or-nothing behaviour
+ * unchanged.  A setter acts on every batch submitted after the call and on none submitted before it, in flight or not: it waits for
+ * the ctx's kernel streams, as ssdr_set_params does, never for the copies out.  Every slot owns a listener block in device and in
+ * pinned host memory, sized at ssdr_feed_open: closed flags for n_ch channels, each payload list for min(n_ch, SSDR_FEED_LAZY_MAX)
+ * channels, SSDR_WF_VIEWS_MAX views of the most lines n_frames can yield at the hop in force.  The stages of the slot's batch write
+ * there (the kernels and their arithmetic are those of ssdr_run_chain), and every non-empty part comes back with one copy behind the
+ * batch's kernels; an empty part costs no launch and no copy, so a listen feed with no listener setting costs what a plain one does.
+ * ssdr_feed_submit / _submit_from return SSDR_ESTATE, with nothing queued, while more than SSDR_FEED_LAZY_MAX channels compress on one
+ * of the two lists.  The PCM of ssdr_feed_collect (with SSDR_FEED_LAZY_OUT: the selection's rows, gathered behind the tail) and the
+ * play buffer of SSDR_FEED_POST are squelched and de-emphasised, as ssdr_run_audio's are.
+ * While such a feed is open ssdr_audio_squelch, ssdr_audio_adpcm, ssdr_wf_adpcm, ssdr_wf_view_lines and ssdr_read_wf_view return
+ * SSDR_ESTATE: the ctx's own buffers hold no batch of the feed.  ssdr_feed_close frees the blocks; settings and state stay, and the
+ * synchronous calls carry on from the state the feed left.
+ *   ssdr_feed_collect_listen(ctx, &out)    of the batch ssdr_feed_collect returned last: the four parts with the lists in force at
+ *                                          that batch's submit (host copies, latched per slot), rows in each stage's own list
+ *                                          order; pointers valid as long as ssdr_feed_collect's, NULL for an empty part.
+ *                                          SSDR_ESTATE before the first collect or on a feed without the flag */
+#define SSDR_FEED_LISTEN 8u
+typedef struct ssdr_feed_listen {
+    uint32_t sq_n;                      /* channels whose acting squelch setting was on */
+    uint32_t snd_n;                     /* SND-flagged channels */
+    uint32_t wf_n;                      /* W/F-flagged channels */
+    uint32_t wf_lines;                  /* lines of wf_adpcm: the batch's lines, 0 when its N was not 1 */
+    uint32_t view_n;                    /* views */
+    uint32_t view_total_lines;          /* their lines, summed */
+    const uint32_t *sq_channels;        /* [sq_n] ascending */
+    const uint8_t *sq_closed;           /* [sq_n][n_frames], 1 = closed */
+    const uint32_t *snd_channels;       /* [snd_n] ascending */
+    const uint8_t *snd_adpcm;           /* [snd_n][n_frames * 256] */
+    const uint32_t *wf_channels;        /* [wf_n] ascending */
+    const uint8_t *wf_adpcm;            /* [wf_lines][wf_n][517] */
+    const ssdr_wf_view *views;          /* [view_n] */
+    const uint32_t *lines_per_view;     /* [view_n] */
+    const int16_t *view_lines;          /* [view_total_lines][1024], one view after the other */
+} ssdr_feed_listen;                     /* 96 B */
+int ssdr_feed_collect_listen(ssdr_ctx *ctx, ssdr_feed_listen *out);
 int ssdr_feed_open(ssdr_ctx *ctx, uint32_t n_frames, uint32_t depth, uint32_t flags);
 int ssdr_feed_slot(ssdr_ctx *ctx, void **host_in);
 int ssdr_feed_submit(ssdr_ctx *ctx);

@@ -85,10 +85,25 @@ class WfView(C.Structure):
 
 
 assert C.sizeof(WfView) == 16
+
+
+class FeedListen(C.Structure):
+    """ssdr_feed_listen: the listener parts of a batch of a SSDR_FEED_LISTEN feed -- counts, the lists latched at its submit, and
+    pinned host pointers (NULL for an empty part)"""
+    _fields_ = [("sq_n", C.c_uint32), ("snd_n", C.c_uint32), ("wf_n", C.c_uint32), ("wf_lines", C.c_uint32),
+                ("view_n", C.c_uint32), ("view_total_lines", C.c_uint32),
+                ("sq_channels", C.POINTER(C.c_uint32)), ("sq_closed", C.POINTER(C.c_uint8)),
+                ("snd_channels", C.POINTER(C.c_uint32)), ("snd_adpcm", C.POINTER(C.c_uint8)),
+                ("wf_channels", C.POINTER(C.c_uint32)), ("wf_adpcm", C.POINTER(C.c_uint8)),
+                ("views", C.POINTER(WfView)), ("lines_per_view", C.POINTER(C.c_uint32)), ("view_lines", C.POINTER(C.c_int16))]
+
+
+assert C.sizeof(FeedListen) == 96
 assert C.sizeof(ChanConsts) == 64 and C.sizeof(ChanState) == 64 and C.sizeof(ChanParams) == 88
 assert C.sizeof(Db2colChan) == 48 and C.sizeof(PlayChan) == 16
 WIRE_BODY = 17 + FRAME * 4
 FEED_LAZY_MAX = 4096        # SSDR_FEED_LAZY_MAX (include/ssdr.h): rows a SSDR_FEED_LAZY_OUT feed copies back per batch
+FEED_WIRE, FEED_POST, FEED_LAZY_OUT, FEED_LISTEN = 1, 2, 4, 8      # SSDR_FEED_*: the flags of ssdr_feed_open
 
 _P = C.c_void_p
 _SIGS = {
@@ -164,6 +179,7 @@ _SIGS = {
                                     C.POINTER(_P), C.POINTER(C.c_uint32)]),
     "ssdr_feed_post": (C.c_int, [_P, C.POINTER(Db2colChan), C.POINTER(PlayChan)]),
     "ssdr_feed_collect_post": (C.c_int, [_P, C.POINTER(_P), C.POINTER(_P), C.POINTER(_P), C.POINTER(_P)]),
+    "ssdr_feed_collect_listen": (C.c_int, [_P, C.POINTER(FeedListen)]),
     "ssdr_feed_close": (C.c_int, [_P]),
     "ssdr_copy_from_device": (C.c_int, [_P, _P, _P, C.c_uint64]),
     "ssdr_wf_device": (C.c_int, [_P, C.POINTER(_P), C.POINTER(C.c_uint32)]),
@@ -198,6 +214,7 @@ _SIGS = {
     "ssdr_version": (C.c_char_p, []),
 }
 EXPORTS = tuple(_SIGS)
+_NEWER_THAN_AB_LIBS = ("ssdr_feed_collect_listen",)      # entry points a library named by SSDR_LIB_PATH (A/B builds only) may predate
 
 
 def _load():
@@ -207,6 +224,8 @@ def _load():
             "or `make -C supersdr_amd/csrc`.  There is no CPU fallback." % LIB_PATH)
     lib = C.CDLL(LIB_PATH)
     for name, (res, args) in _SIGS.items():
+        if name in _NEWER_THAN_AB_LIBS and os.environ.get("SSDR_LIB_PATH") and not hasattr(lib, name):
+            continue                     # an A/B library from before the entry point: whoever calls it gets the AttributeError
         fn = getattr(lib, name)          # AttributeError here == header/library mismatch
         fn.restype, fn.argtypes = res, args
     return lib

@@ -58,6 +58,12 @@ struct Batch {
     uint32_t audio_run_frames = 0;            // frames the last audio run (or ssdr_set_pcm) produced: their extent and stride
     uint8_t *d_flags = nullptr;               // ADC-overflow flag per frame of the last audio run
     size_t flags_frames = 0;
+    // a slot of a listen feed (SSDR_FEED_LISTEN): the listener stages write here, not into the ctx's own buffers (whose "valid" marks
+    // such a batch leaves down); the capacities are the slot's, fixed when the feed was opened
+    bool listen = false;
+    uint8_t *d_sq_closed = nullptr, *d_snd_adpcm = nullptr, *d_wf_adpcm = nullptr;
+    int16_t *d_wv_lines = nullptr;
+    size_t wv_lines_rows = 0;
 };
 // What ssdr_run_chain decides for a batch (chain_plan), handed to the two stages
 struct ChainPlan {
@@ -151,6 +157,12 @@ struct ssdr_ctx {
         float *d_sel_rssi = nullptr, *d_sel_wire_rssi = nullptr;
         uint8_t *d_sel_flags = nullptr;
         uint32_t n_sel = 0;
+        // SSDR_FEED_LISTEN: the listener block -- one device and one pinned host allocation, the four parts at the feed's offsets --
+        // and the lists in force at the batch's submit
+        uint8_t *d_listen = nullptr, *h_listen = nullptr;
+        std::vector<uint32_t> sq_list, snd_list, wf_list, wv_lines;
+        std::vector<ssdr_wf_view> wv;
+        uint32_t wf_adpcm_lines = 0, wv_total = 0;
     };
     std::vector<FeedSlot> feed;
     uint32_t feed_frames = 0, feed_head = 0, feed_tail = 0, feed_inflight = 0;
@@ -159,6 +171,8 @@ struct ssdr_ctx {
     bool feed_post = false;                              // SSDR_FEED_POST: db2col + play_buffer in the slot pipeline
     bool feed_lazy = false;                              // SSDR_FEED_LAZY_OUT: only the selected channels' results are copied back
     uint32_t feed_lazy_max = 0;                          // rows the compact buffers hold
+    bool feed_listen = false;                            // SSDR_FEED_LISTEN: the listener stages run in the slot pipeline
+    size_t listen_off[4] = {}, listen_wv_rows = 0;       // where closed flags, SND payloads, W/F payloads and view lines lie in a slot's block; the view lines it holds
     std::vector<ssdr_db2col_chan> feed_dbchan;           // display state for the next submits (ssdr_feed_post)
     std::vector<ssdr_play_chan> feed_playchan;
     int feed_last = -1;                                  // slot ssdr_feed_collect returned last
@@ -1093,6 +1107,7 @@ static int validate_wf_batch(const ssdr_ctx *c, const Batch &b)
 // room for the SND payloads of an audio run of the current batch
 static int adpcm_snd_alloc(ssdr_ctx *c, const Batch &b)
 {
+    if (b.listen) return SSDR_OK;            // (the slot's block has the room: feed_submit_impl checked)
     const size_t need = (size_t)c->comp_snd_n * b.in_frames * (SSDR_FRAME / 2);
     if (c->snd_adpcm_bytes >= need) return SSDR_OK;
     SSDR_TRY(drain_audio(c));
@@ -1113,10 +1128,10 @@ static int adpcm_snd_launch(ssdr_ctx *c, const Batch &b, hipStream_t s)
     e.n_samples = b.in_frames * SSDR_FRAME;
     e.consts = c->d_consts;
     e.state = c->d_adpcm_state;
-    e.out = c->d_snd_adpcm;
+    e.out = b.listen ? b.d_snd_adpcm : c->d_snd_adpcm;
     e.out_stride = (uint64_t)b.in_frames * (SSDR_FRAME / 2);
     SSDR_TRY(timed_launch(c, SSDR_K_ADPCM, s, [&]() -> int { HIP_TRY(ssdr_launch_adpcm_enc(e, s)); return SSDR_OK; }));
-    c->snd_adpcm_valid = true;
+    c->snd_adpcm_valid = !b.listen;
     c->snd_adpcm_frames = b.in_frames;
     return SSDR_OK;
 }
@@ -1144,11 +1159,11 @@ static int adpcm_wf_launch(ssdr_ctx *c, const Batch &b, hipStream_t s, uint32_t 
         e.n_samples = SSDR_NFFT;
         e.consts = nullptr;
         e.state = nullptr;
-        e.out = c->d_wf_adpcm;
+        e.out = b.listen ? b.d_wf_adpcm : c->d_wf_adpcm;
         e.out_stride = SSDR_ADPCM_WF_BYTES;
         SSDR_TRY(timed_launch(c, SSDR_K_ADPCM, s, [&]() -> int { HIP_TRY(ssdr_launch_adpcm_enc_wf(e, s)); return SSDR_OK; }));
     }
-    c->wf_adpcm_valid = true;
+    c->wf_adpcm_valid = !b.listen;
     c->wf_adpcm_lines = lines;
     return SSDR_OK;
 }
@@ -1197,7 +1212,7 @@ static int squelch_prepare(ssdr_ctx *c, const Batch &b)
     if (!c->sq_set_n && !c->sq_dirty) return SSDR_OK;
     SSDR_TRY(squelch_refresh(c));
     const size_t need = (size_t)c->sq_n * b.in_frames;
-    if (c->sq_closed_bytes >= need) return SSDR_OK;
+    if (b.listen || c->sq_closed_bytes >= need) return SSDR_OK;
     SSDR_TRY(drain_audio(c));
     c->sq_valid = false;
     return grow(c, c->d_sq_closed, c->sq_closed_bytes, need, 1);
@@ -1214,9 +1229,9 @@ static int squelch_launch(ssdr_ctx *c, const Batch &b, hipStream_t s)
     q.list_n = c->sq_n;
     q.consts = c->d_consts;
     q.chan = c->d_sq;
-    q.closed = c->d_sq_closed;
+    q.closed = b.listen ? b.d_sq_closed : c->d_sq_closed;
     SSDR_TRY(timed_launch(c, SSDR_K_SQUELCH, s, [&]() -> int { HIP_TRY(ssdr_launch_squelch(q, s)); return SSDR_OK; }));
-    c->sq_valid = true;
+    c->sq_valid = !b.listen;
     c->sq_frames = b.in_frames;
     return SSDR_OK;
 }
@@ -1375,7 +1390,8 @@ static int wfview_stage(ssdr_ctx *c, const Batch &b)
     c->wv_run_valid = false;
     SSDR_TRY(grow(c, c->d_wv_stream, c->wv_stream_dwords, (size_t)nv * stride, 4));
     SSDR_TRY(grow(c, c->d_wv_wf, c->wv_wf_rows, (size_t)std::max(max_lines, 1u) * nv, SSDR_NFFT * 2));
-    SSDR_TRY(grow(c, c->d_wv_lines, c->wv_lines_rows, std::max(total, 1u), SSDR_NFFT * 2));
+    if (b.listen && total > b.wv_lines_rows) return SSDR_ESTATE;         // (never: the slot holds the most lines its frames can yield)
+    if (!b.listen) SSDR_TRY(grow(c, c->d_wv_lines, c->wv_lines_rows, std::max(total, 1u), SSDR_NFFT * 2));
     if (c->wv_consts_dirty) {
         std::vector<ssdr_chan_consts> k(nv);
         for (uint32_t j = 0; j < nv; j++) k[j] = c->h_consts[c->h_wv[j].channel];
@@ -1387,7 +1403,7 @@ static int wfview_stage(ssdr_ctx *c, const Batch &b)
     SsdrWfViewArgs a;
     a.iq = b.d_iq; a.ch_stride = n_in; a.n_in = n_in; a.n_views = nv; a.hop = c->hop;
     a.views = c->d_wv[set]; a.taps = c->d_wv_taps; a.hist = c->d_wv_hist[set]; a.carry = c->d_wv_carry[set]; a.tail = c->d_wv_tail[set];
-    a.stream = c->d_wv_stream; a.stream_stride = stride; a.wf_lines = c->d_wv_wf; a.lines_out = c->d_wv_lines;
+    a.stream = c->d_wv_stream; a.stream_stride = stride; a.wf_lines = c->d_wv_wf; a.lines_out = b.listen ? b.d_wv_lines : c->d_wv_lines;
     SsdrWfArgs w;                            // the views as the channels of a small ctx: byte lines (N = 1), fp32 bins
     w.iq = c->d_wv_stream; w.ch_stride = stride; w.n_ch = nv; w.n_lines = max_lines;
     w.tail = c->hop == SSDR_NFFT / 2 ? c->d_wv_tail[set] : nullptr;
@@ -1409,7 +1425,7 @@ static int wfview_stage(ssdr_ctx *c, const Batch &b)
     c->wv_run_n_in = n_in;
     c->wv_run_total = total;
     c->wv_run_stride = stride;
-    c->wv_run_valid = true;
+    c->wv_run_valid = !b.listen;
     return SSDR_OK;
 }
 
@@ -1442,7 +1458,7 @@ static int wf_stage(ssdr_ctx *c, Batch &b, ChainPlan plan, SsdrWfArgs *one_read,
     const uint32_t n_out = total / c->n_avg;
     const uint32_t n_groups = (total + c->n_avg - 1) / c->n_avg;
     SSDR_TRY(ensure_wf_out(c, b, n_out));
-    if (c->comp_wf_n && c->n_avg == 1) SSDR_TRY(adpcm_wf_alloc(c, n_out));
+    if (c->comp_wf_n && c->n_avg == 1 && !b.listen) SSDR_TRY(adpcm_wf_alloc(c, n_out));
     c->wf_adpcm_valid = false;
     SsdrWfArgs a;
     a.iq = wf_src;
@@ -1967,10 +1983,10 @@ int ssdr_feed_close(ssdr_ctx *c) SSDR_GUARD
     if (c->feed_s_in) (void)hipStreamSynchronize(c->feed_s_in);
     if (c->feed_s_out) (void)hipStreamSynchronize(c->feed_s_out);
     for (auto &s : c->feed) {
-        void *hp[] = {s.h_in, s.h_wf, s.h_pcm, s.h_rssi, s.h_wire_rssi, s.h_flags, s.h_color, s.h_dbchan, s.h_playchan, s.h_play, s.h_mono};
+        void *hp[] = {s.h_in, s.h_wf, s.h_pcm, s.h_rssi, s.h_wire_rssi, s.h_flags, s.h_color, s.h_dbchan, s.h_playchan, s.h_play, s.h_mono, s.h_listen};
         for (void *p : hp) if (p) (void)hipHostFree(p);
         void *dp[] = {s.d_in, s.d_wf, s.d_pcm, s.d_rssi, s.d_wire, s.d_wire_rssi, s.d_flags, s.d_color, s.d_dbchan, s.d_play, s.d_mono,
-                      s.d_sel_wf, s.d_sel_pcm, s.d_sel_rssi, s.d_sel_wire_rssi, s.d_sel_flags};
+                      s.d_sel_wf, s.d_sel_pcm, s.d_sel_rssi, s.d_sel_wire_rssi, s.d_sel_flags, s.d_listen};
         for (void *p : dp) if (p) (void)hipFree(p);
         hipEvent_t ev[] = {s.ev_in, s.ev_run, s.ev_out};
         for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e);
@@ -1982,15 +1998,19 @@ int ssdr_feed_close(ssdr_ctx *c) SSDR_GUARD
     c->feed_taken = false;
     c->feed_post = false;
     c->feed_lazy = false;
+    c->feed_listen = false;
     c->feed_last = -1;
     return SSDR_OK;
 } SSDR_UNGUARD
 
 int ssdr_feed_open(ssdr_ctx *c, uint32_t n_frames, uint32_t depth, uint32_t flags) SSDR_GUARD
 {
-    if (!c || n_frames == 0 || (n_frames & 1u) || depth < 2 || depth > 16 || (flags & ~(uint32_t)(SSDR_FEED_WIRE | SSDR_FEED_POST | SSDR_FEED_LAZY_OUT))) return SSDR_EINVAL;
+    if (!c || n_frames == 0 || (n_frames & 1u) || depth < 2 || depth > 16 || (flags & ~(uint32_t)(SSDR_FEED_WIRE | SSDR_FEED_POST | SSDR_FEED_LAZY_OUT | SSDR_FEED_LISTEN))) return SSDR_EINVAL;
+    // the feed's slots are sized for un-zoomed 12 kHz IQ
     if (!c->feed.empty() || c->concurrent || c->decim != 1 || c->zoom != 1) return SSDR_ESTATE;
-    if (c->comp_snd_n || c->comp_wf_n || c->sq_set_n || c->de_set_n || !c->h_wv.empty()) return SSDR_ESTATE;   // no wire compression, squelch, de-emphasis or waterfall view in the slot pipeline      // the feed's slots are sized for un-zoomed 12 kHz IQ
+    // no wire compression, squelch, de-emphasis or waterfall view in the slot pipeline, unless it was opened for them
+    const bool listen = (flags & SSDR_FEED_LISTEN) != 0;
+    if (!listen && (c->comp_snd_n || c->comp_wf_n || c->sq_set_n || c->de_set_n || !c->h_wv.empty())) return SSDR_ESTATE;
     HIP_TRY(hipSetDevice(c->device));
     const bool post = (flags & SSDR_FEED_POST) != 0;
     if (post) SSDR_TRY(ensure_play(c));
@@ -2016,8 +2036,20 @@ int ssdr_feed_open(ssdr_ctx *c, uint32_t n_frames, uint32_t depth, uint32_t flag
     c->feed_lazy = lazy;
     c->feed_lazy_max = c->n_ch < SSDR_FEED_LAZY_MAX ? c->n_ch : SSDR_FEED_LAZY_MAX;
     const size_t out_ch = lazy ? c->feed_lazy_max : c->n_ch;
+    // SSDR_FEED_LISTEN: a slot's listener block -- closed flags [n_ch][n_frames] | SND payloads [lazy_max][n_frames * 256] | W/F payloads
+    // [lines][lazy_max][517] | view lines [SSDR_WF_VIEWS_MAX * most lines of a view][1024]: a view carries less than a hop and gains at
+    // most n_frames * 512 / 2 samples per batch
+    size_t listen_b = 0;
+    if (listen) {
+        const size_t wf_lines = c->hop == SSDR_NFFT / 2 ? n_frames : n_frames / 2;
+        c->listen_wv_rows = (size_t)SSDR_WF_VIEWS_MAX * ((c->hop - 1 + (size_t)n_frames * SSDR_FRAME / 2) / c->hop);
+        const size_t part_b[4] = {(size_t)c->n_ch * n_frames, (size_t)c->feed_lazy_max * n_frames * (SSDR_FRAME / 2),
+                                  wf_lines * c->feed_lazy_max * SSDR_ADPCM_WF_BYTES, c->listen_wv_rows * SSDR_NFFT * 2};
+        for (int i = 0; i < 4; i++) { c->listen_off[i] = listen_b; listen_b += (part_b[i] + 255) / 256 * 256; }
+    }
     const size_t h_wf_b = wf_b / c->n_ch * out_ch, h_pcm_b = pcm_b / c->n_ch * out_ch, h_rssi_b = rssi_b / c->n_ch * out_ch, h_flags_b = out_ch * n_frames;
     c->feed.resize(depth);
+    c->feed_listen = listen;                 // (once there are slots: ssdr_feed_close takes the mark down with them)
     bool ok = hipStreamCreateWithFlags(&c->feed_s_in, hipStreamNonBlocking) == hipSuccess &&
               hipStreamCreateWithFlags(&c->feed_s_out, hipStreamNonBlocking) == hipSuccess;
     for (auto &s : c->feed) {
@@ -2049,6 +2081,7 @@ int ssdr_feed_open(ssdr_ctx *c, uint32_t n_frames, uint32_t depth, uint32_t flag
             ok = ok && hipHostMalloc(reinterpret_cast<void **>(&s.h_play), play_b, hipHostMallocDefault) == hipSuccess;
             ok = ok && hipHostMalloc(reinterpret_cast<void **>(&s.h_mono), play_b / 2, hipHostMallocDefault) == hipSuccess;
         }
+        if (listen) ok = ok && hipMalloc(&s.d_listen, listen_b) == hipSuccess && hipHostMalloc(reinterpret_cast<void **>(&s.h_listen), listen_b, hipHostMallocDefault) == hipSuccess;
         ok = ok && hipEventCreateWithFlags(&s.ev_in, hipEventDisableTiming) == hipSuccess;
         ok = ok && hipEventCreateWithFlags(&s.ev_run, hipEventDisableTiming) == hipSuccess;
         ok = ok && hipEventCreateWithFlags(&s.ev_out, hipEventDisableTiming) == hipSuccess;
@@ -2076,6 +2109,7 @@ static int feed_submit_impl(ssdr_ctx *c, const void *host_in)
     auto &s = c->feed[c->feed_head];
     const uint32_t nf = c->feed_frames;
     if (c->feed_lazy && (c->d_post_sel ? c->n_post : c->n_ch) > c->feed_lazy_max) return SSDR_ESTATE;     // more listeners than the compact rows hold
+    if (c->feed_listen && (c->comp_snd_n > c->feed_lazy_max || c->comp_wf_n > c->feed_lazy_max)) return SSDR_ESTATE;   // ... or than the slot's payload rows
     if (c->feed_wire)
         HIP_TRY(hipMemcpyAsync(s.d_wire, host_in, (size_t)c->n_ch * nf * SSDR_WIRE_BODY, hipMemcpyHostToDevice, c->feed_s_in));
     else
@@ -2101,10 +2135,26 @@ static int feed_submit_impl(ssdr_ctx *c, const void *host_in)
     b.d_wf_out = s.d_wf; b.wf_out_lines = c->hop == SSDR_NFFT / 2 ? nf : nf / 2;
     b.d_pcm = s.d_pcm; b.d_rssi = s.d_rssi; b.audio_frames = nf;
     b.d_flags = s.d_flags; b.flags_frames = nf;
+    if (c->feed_listen) {                                   // the listener stages write into the slot's block and nowhere else
+        b.listen = true;
+        b.d_sq_closed = s.d_listen + c->listen_off[0]; b.d_snd_adpcm = s.d_listen + c->listen_off[1]; b.d_wf_adpcm = s.d_listen + c->listen_off[2];
+        b.d_wv_lines = reinterpret_cast<int16_t *>(s.d_listen + c->listen_off[3]); b.wv_lines_rows = c->listen_wv_rows;
+    }
     uint32_t lines = 0;
     s.n_avg = c->n_avg;
     SSDR_TRY(run_chain(c, b, &lines, nullptr));            // the fused superframe kernel where the batch allows it
     SSDR_TRY(join_audio(c));                                // (or the two stages side by side: what follows reads both results)
+    if (c->feed_listen) {                                   // the lists this batch ran with: a setter changes the ctx's, not these
+        s.sq_list.assign(c->h_sq_list.begin(), c->h_sq_list.begin() + c->sq_n);
+        s.snd_list.assign(c->h_comp_list.begin(), c->h_comp_list.begin() + c->comp_snd_n);
+        s.wf_list.clear();
+        if (c->comp_wf_n) s.wf_list.assign(c->h_comp_list.begin() + c->n_ch, c->h_comp_list.begin() + c->n_ch + c->comp_wf_n);
+        s.wf_adpcm_lines = c->comp_wf_n && s.n_avg == 1 ? lines : 0;
+        s.wv = c->h_wv;
+        s.wv_lines.clear();
+        if (!s.wv.empty()) s.wv_lines = c->h_wv_run_lines;
+        s.wv_total = s.wv.empty() ? 0 : c->wv_run_total;
+    }
     if (c->feed_post) { s.n_post = c->n_post; s.has_mono = c->n_post && c->recording; }
     if (c->feed_post && c->n_post) {
         // spectrum_db2col of this batch's lines and play_buffer of its frames, on the slot's buffers, in batch order
@@ -2157,6 +2207,13 @@ static int feed_submit_impl(ssdr_ctx *c, const void *host_in)
             if (s.has_mono)
                 HIP_TRY(hipMemcpyAsync(s.h_mono, s.d_mono, (size_t)c->n_post * nf * per_frame * sizeof(int16_t), hipMemcpyDeviceToHost, c->feed_s_out));
         }
+    }
+    if (c->feed_listen) {                                   // one copy per non-empty part
+        const size_t part_b[4] = {s.sq_list.size() * nf, s.snd_list.size() * nf * (SSDR_FRAME / 2),
+                                  (size_t)s.wf_adpcm_lines * s.wf_list.size() * SSDR_ADPCM_WF_BYTES, (size_t)s.wv_total * SSDR_NFFT * 2};
+        for (int i = 0; i < 4; i++)
+            if (part_b[i])
+                HIP_TRY(hipMemcpyAsync(s.h_listen + c->listen_off[i], s.d_listen + c->listen_off[i], part_b[i], hipMemcpyDeviceToHost, c->feed_s_out));
     }
     HIP_TRY(hipEventRecord(s.ev_out, c->feed_s_out));
     c->feed_head = (c->feed_head + 1) % (uint32_t)c->feed.size();
@@ -2237,6 +2294,29 @@ int ssdr_feed_collect(ssdr_ctx *c, int16_t **wf_sum, uint32_t *lines, int16_t **
     c->feed_last = (int)c->feed_tail;
     c->feed_tail = (c->feed_tail + 1) % (uint32_t)c->feed.size();
     c->feed_inflight--;
+    return SSDR_OK;
+} SSDR_UNGUARD
+
+int ssdr_feed_collect_listen(ssdr_ctx *c, ssdr_feed_listen *out) SSDR_GUARD
+{
+    if (!c || !out) return SSDR_EINVAL;
+    if (c->feed.empty() || !c->feed_listen || c->feed_last < 0) return SSDR_ESTATE;
+    const auto &s = c->feed[c->feed_last];
+    memset(out, 0, sizeof *out);
+    out->sq_n = (uint32_t)s.sq_list.size();
+    out->snd_n = (uint32_t)s.snd_list.size();
+    out->wf_n = (uint32_t)s.wf_list.size();
+    out->wf_lines = s.wf_adpcm_lines;
+    out->view_n = (uint32_t)s.wv.size();
+    out->view_total_lines = s.wv_total;
+    if (out->sq_n) { out->sq_channels = s.sq_list.data(); out->sq_closed = s.h_listen + c->listen_off[0]; }
+    if (out->snd_n) { out->snd_channels = s.snd_list.data(); out->snd_adpcm = s.h_listen + c->listen_off[1]; }
+    if (out->wf_n) { out->wf_channels = s.wf_list.data(); if (out->wf_lines) out->wf_adpcm = s.h_listen + c->listen_off[2]; }
+    if (out->view_n) {
+        out->views = s.wv.data();
+        out->lines_per_view = s.wv_lines.data();
+        if (out->view_total_lines) out->view_lines = reinterpret_cast<const int16_t *>(s.h_listen + c->listen_off[3]);
+    }
     return SSDR_OK;
 } SSDR_UNGUARD
 
@@ -2852,7 +2932,7 @@ int ssdr_adpcm_encode(ssdr_ctx *c, const int16_t *pcm, uint32_t n_streams, uint3
 int ssdr_set_compression(ssdr_ctx *c, uint32_t first, uint32_t count, const uint8_t *snd_on, const uint8_t *wf_on) SSDR_GUARD
 {
     if (!c || (uint64_t)first + count > c->n_ch) return SSDR_EINVAL;
-    if (!c->feed.empty()) return SSDR_ESTATE;
+    if (!c->feed.empty() && !c->feed_listen) return SSDR_ESTATE;
     if (!count || (!snd_on && !wf_on)) return SSDR_OK;
     HIP_TRY(hipSetDevice(c->device));
     if (!c->d_comp_list) {                                  // first use: flags, channel lists, encoder state
@@ -2918,7 +2998,7 @@ int ssdr_compression_channels(ssdr_ctx *c, int which, uint32_t *list, uint32_t *
 int ssdr_audio_adpcm(ssdr_ctx *c, uint8_t *out, int out_is_device) SSDR_GUARD
 {
     if (!c || !out) return SSDR_EINVAL;
-    if (!c->comp_snd_n || !c->snd_adpcm_valid) return SSDR_ESTATE;
+    if (c->feed_listen || !c->comp_snd_n || !c->snd_adpcm_valid) return SSDR_ESTATE;     // (a listen feed's payloads are its slots')
     HIP_TRY(hipSetDevice(c->device));
     SSDR_TRY(join_audio(c));
     return copy_out(c, out, c->d_snd_adpcm, (size_t)c->comp_snd_n * c->snd_adpcm_frames * (SSDR_FRAME / 2), out_is_device, kSyncAlways);
@@ -2927,7 +3007,7 @@ int ssdr_audio_adpcm(ssdr_ctx *c, uint8_t *out, int out_is_device) SSDR_GUARD
 int ssdr_wf_adpcm(ssdr_ctx *c, uint8_t *out, uint32_t *lines, int out_is_device) SSDR_GUARD
 {
     if (!c || !lines) return SSDR_EINVAL;
-    if (!c->comp_wf_n || !c->wf_adpcm_valid) return SSDR_ESTATE;
+    if (c->feed_listen || !c->comp_wf_n || !c->wf_adpcm_valid) return SSDR_ESTATE;
     *lines = c->wf_adpcm_lines;
     if (!out || !c->wf_adpcm_lines) return SSDR_OK;
     HIP_TRY(hipSetDevice(c->device));
@@ -2948,7 +3028,7 @@ int ssdr_set_squelch(ssdr_ctx *c, uint32_t first, uint32_t count, const ssdr_squ
     if (!c || (uint64_t)first + count > c->n_ch || (count && !p)) return SSDR_EINVAL;
     for (uint32_t i = 0; i < count; i++)                    // all or nothing: every channel is checked before any is changed
         if (p[i].fm_level > 99 || p[i].fm_max > 65535 || p[i].rssi_level > 99 || p[i].tail_frames > 1024) return SSDR_EINVAL;
-    if (!c->feed.empty()) return SSDR_ESTATE;
+    if (!c->feed.empty() && !c->feed_listen) return SSDR_ESTATE;
     if (!count) return SSDR_OK;
     HIP_TRY(hipSetDevice(c->device));
     bool any = false;
@@ -2989,7 +3069,7 @@ int ssdr_get_squelch(ssdr_ctx *c, uint32_t first, uint32_t count, ssdr_squelch_p
 int ssdr_audio_squelch(ssdr_ctx *c, uint8_t *closed_out, int out_is_device) SSDR_GUARD
 {
     if (!c || !closed_out) return SSDR_EINVAL;
-    if (c->sq_dirty || !c->sq_n || !c->sq_valid) return SSDR_ESTATE;       // (a change of settings or modes since the run: not that run's)
+    if (c->feed_listen || c->sq_dirty || !c->sq_n || !c->sq_valid) return SSDR_ESTATE;       // (a change of settings or modes since the run: not that run's; a listen feed's flags are its slots')
     HIP_TRY(hipSetDevice(c->device));
     SSDR_TRY(join_audio(c));
     const size_t row = c->sq_frames;
@@ -3023,7 +3103,7 @@ int ssdr_set_deemphasis(ssdr_ctx *c, uint32_t first, uint32_t count, const ssdr_
     if (!c || (uint64_t)first + count > c->n_ch || (count && !p)) return SSDR_EINVAL;
     for (uint32_t i = 0; i < count; i++)                    // all or nothing: every channel is checked before any is changed
         if (p[i].am > 2 || p[i].nfm > 2) return SSDR_EINVAL;
-    if (!c->feed.empty()) return SSDR_ESTATE;
+    if (!c->feed.empty() && !c->feed_listen) return SSDR_ESTATE;
     if (!count) return SSDR_OK;
     HIP_TRY(hipSetDevice(c->device));
     bool any = false;
@@ -3092,7 +3172,7 @@ int ssdr_set_wf_views(ssdr_ctx *c, const ssdr_wf_view *views, uint32_t count) SS
         if (v.zoom != 2 && v.zoom != 4 && v.zoom != 8) return SSDR_EINVAL;
         if (!(std::fabs(v.offset_hz) <= half)) return SSDR_EINVAL;
     }
-    if (count && (!c->feed.empty() || c->zoom > 1)) return SSDR_ESTATE;
+    if (count && ((!c->feed.empty() && !c->feed_listen) || c->zoom > 1)) return SSDR_ESTATE;
     c->wv_run_valid = false;
     if (!count) {                                           // (the state arrays stay for the next list)
         c->h_wv.clear();
@@ -3142,7 +3222,7 @@ int ssdr_get_wf_views(ssdr_ctx *c, ssdr_wf_view *views, uint32_t *count) SSDR_GU
 int ssdr_wf_view_lines(ssdr_ctx *c, int16_t *lines_out, uint32_t *lines_per_view, uint32_t *total_lines, int out_is_device) SSDR_GUARD
 {
     if (!c) return SSDR_EINVAL;
-    if (c->h_wv.empty() || !c->wv_run_valid) return SSDR_ESTATE;
+    if (c->feed_listen || c->h_wv.empty() || !c->wv_run_valid) return SSDR_ESTATE;
     if (lines_per_view) std::copy(c->h_wv_run_lines.begin(), c->h_wv_run_lines.end(), lines_per_view);
     if (total_lines) *total_lines = c->wv_run_total;
     if (!lines_out || !c->wv_run_total) return SSDR_OK;
@@ -3153,7 +3233,7 @@ int ssdr_wf_view_lines(ssdr_ctx *c, int16_t *lines_out, uint32_t *lines_per_view
 int ssdr_read_wf_view(ssdr_ctx *c, uint32_t view_index, int16_t *iq_out, uint32_t *samples) SSDR_GUARD
 {
     if (!c) return SSDR_EINVAL;
-    if (c->h_wv.empty() || !c->wv_run_valid) return SSDR_ESTATE;
+    if (c->feed_listen || c->h_wv.empty() || !c->wv_run_valid) return SSDR_ESTATE;
     if (view_index >= c->h_wv.size()) return SSDR_EINVAL;
     const uint32_t n = c->wv_run_n_in / c->h_wv[view_index].zoom;
     if (samples) *samples = n;

@@ -485,13 +485,17 @@ class SsdrEngine:
         return out
 
     # ---- pipelined host feed (copy-in / kernels / copy-out of consecutive batches overlap)
-    def feed_open(self, n_frames, depth=3, wire=False, post=False, lazy_out=False):
+    def feed_open(self, n_frames, depth=3, wire=False, post=False, lazy_out=False, listen=False):
         """wire=True: slots take SND bodies uint8 [n_ch, n_frames, 2065] (kiwi/client.py:443-454), unpacked on the device.
         post=True: every batch also goes through spectrum_db2col / play_buffer on the device (feed_post, feed_collect_post).
         lazy_out=True (SSDR_FEED_LAZY_OUT): only the channels of set_post_channels come back to the host -- feed_collect's arrays then
         have one row per SELECTED channel (the selection in force at the batch's submit); every channel's results stay on the
-        device (feed_device)."""
-        check(lib.ssdr_feed_open(self._ctx, int(n_frames), int(depth), (1 if wire else 0) | (2 if post else 0) | (4 if lazy_out else 0)), "ssdr_feed_open")
+        device (feed_device).
+        listen=True (SSDR_FEED_LISTEN): squelch, de-emphasis, wire compression and waterfall views run in the slot pipeline; their setters
+        are accepted while the feed is open and act on the batches submitted after the call; feed_collect_listen hands out a batch's
+        closed flags, payloads and view lines."""
+        flags = (L.FEED_WIRE if wire else 0) | (L.FEED_POST if post else 0) | (L.FEED_LAZY_OUT if lazy_out else 0) | (L.FEED_LISTEN if listen else 0)
+        check(lib.ssdr_feed_open(self._ctx, int(n_frames), int(depth), flags), "ssdr_feed_open")
         self._feed_frames, self._feed_wire, self._feed_post = int(n_frames), bool(wire), bool(post)
         self._feed_lazy = bool(lazy_out)
         self._feed_lines = 0
@@ -601,6 +605,29 @@ class SsdrEngine:
         n_sel, a, b, c, d = C.c_uint32(), C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_void_p()
         check(lib.ssdr_feed_collect_lazy(self._ctx, C.byref(n_sel), C.byref(a), C.byref(b), C.byref(c), C.byref(d)), "ssdr_feed_collect_lazy")
         return {"wf": a.value, "pcm": b.value, "rssi": c.value, "flags": d.value, "rows": int(n_sel.value), "lines": self._feed_lines}
+
+    def feed_collect_listen(self):
+        """of the batch feed_collect returned last, on a listen feed -> dict of the four listener parts, each with the list in force
+        at that batch's submit and its rows in that order, as views of pinned memory (valid as long as feed_collect's arrays):
+        sq_channels uint32 [k], sq_closed uint8 [k, n_frames]; snd_channels, snd_adpcm uint8 [k, n_frames*256]; wf_channels, wf_adpcm
+        uint8 [lines, k, 517] (no lines when the batch's N was not 1); views [(channel, zoom, offset_hz)], view_lines [int16 [k_i, 1024]]"""
+        o = L.FeedListen()
+        check(lib.ssdr_feed_collect_listen(self._ctx, C.byref(o)), "ssdr_feed_collect_listen")
+        nf = self._feed_frames
+
+        def view(ptr, dtype, shape):
+            n = int(np.prod(shape))
+            return np.ctypeslib.as_array(ptr, shape=(n,)).reshape(shape) if n else np.zeros(shape, dtype)
+
+        per = [int(v) for v in o.lines_per_view[:o.view_n]]
+        lines = view(o.view_lines, np.int16, (o.view_total_lines, L.NFFT))
+        cuts = np.cumsum([0] + per)
+        return {"sq_channels": np.array(o.sq_channels[:o.sq_n], np.uint32), "sq_closed": view(o.sq_closed, np.uint8, (o.sq_n, nf)),
+                "snd_channels": np.array(o.snd_channels[:o.snd_n], np.uint32),
+                "snd_adpcm": view(o.snd_adpcm, np.uint8, (o.snd_n, nf * L.FRAME // 2)),
+                "wf_channels": np.array(o.wf_channels[:o.wf_n], np.uint32), "wf_adpcm": view(o.wf_adpcm, np.uint8, (o.wf_lines, o.wf_n, 517)),
+                "views": [(v.channel, v.zoom, v.offset_hz) for v in o.views[:o.view_n]],
+                "view_lines": [lines[cuts[i]:cuts[i + 1]] for i in range(o.view_n)]}
 
     def feed_close(self):
         check(lib.ssdr_feed_close(self._ctx), "ssdr_feed_close")

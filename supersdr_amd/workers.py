@@ -91,11 +91,13 @@ class SuperframeResult:
     With wire compression on some channels (IQHub.set_compression): snd_adpcm uint8 [n, frames*256] / wf_adpcm uint8 [lines, n, 517],
     a row per channel of snd_adpcm_channels / wf_adpcm_channels (None: no channel compresses).
     With a squelch acting on some channel (IQHub.set_squelch): squelched uint8 [n_ch, frames], 1 where the frame was zeroed (None: no
-    channel squelches).
+    channel squelches).  On a pipelined listen hub squelched has a row per channel of squelched_channels (the channels whose squelch
+    acted at the batch's submit) instead of one per channel; squelched_channels None: one per channel.
     With waterfall views (IQHub.set_wf_view): view_channels lists the channels that have one, ascending, and view_lines holds for each
     an int16 [k, 1024] of the k byte lines (N = 1) its view produced in this run, k >= 0 (both None: no view is set)."""
     __slots__ = ("seq", "wf", "n_avg", "color", "chans", "pcm", "rssi", "flags", "play", "mono", "iq", "wire_rssi", "post_channels", "out_channels",
-                 "snd_adpcm", "wf_adpcm", "snd_adpcm_channels", "wf_adpcm_channels", "squelched", "view_lines", "view_channels")
+                 "snd_adpcm", "wf_adpcm", "snd_adpcm_channels", "wf_adpcm_channels", "squelched", "view_lines", "view_channels",
+                 "squelched_channels")
 
     def __init__(self, **kw):
         for k in self.__slots__:
@@ -167,6 +169,9 @@ class IQHub:
     overlapped, the copy-in straight from the hub's (pinned) slot (ssdr_feed_submit_from); with gpu_post the slot pipeline
     also runs spectrum_db2col and play_buffer (SSDR_FEED_POST) with the display state latched at submit.  Results arrive
     `depth - 1` superframes late (flush() drains) and are bit-identical to the synchronous hub's.
+    listen=True (with pipeline=True; SSDR_FEED_LISTEN) runs the listener stages in the slot pipeline: set_squelch, set_deemphasis,
+    set_compression and set_wf_view then work as on the synchronous hub, on the superframes submitted after the call, and
+    Frame.squelched, Frame.adpcm, a line's .adpcm and a view's lines reach the queues `depth - 1` superframes late with everything else.
     `batch_superframes=K` runs K superframes per GPU call (K lines + 2K audio frames per channel and call): latency for
     launch efficiency at very large channel counts.  `exact_bins=True`: the waterfall stage in float64 (ssdr_set_exact_bins).  `copy_threads=T` splits feed_block's copy of a large block over T threads (default: up to 8 on hubs of 8192+ receivers).
     """
@@ -175,7 +180,7 @@ class IQHub:
 
     def __init__(self, n_channels, device=0, engine=None, max_queue=64, gpu_post=True, kiwi_rate=12000, trace_rows=0,
                  backlog_superframes=8, stall_superframes=4, pipeline=False, depth=3, hop=1024, zoom=1, lazy=None,
-                 batch_superframes=1, wire=False, copy_threads=None, exact_bins=False, lazy_out=False):
+                 batch_superframes=1, wire=False, copy_threads=None, exact_bins=False, lazy_out=False, listen=False):
         self.n_ch = int(n_channels)
         # argument combinations that cannot work are refused BEFORE an engine (a GPU context) exists
         self._lazy = (self.n_ch > self.LAZY_ABOVE) if lazy is None else bool(lazy)
@@ -183,6 +188,8 @@ class IQHub:
             raise ValueError("zoom needs the synchronous hub (the pipelined feed's slots hold un-zoomed lines)")
         if lazy_out and not (pipeline and self._lazy):
             raise ValueError("lazy_out needs the pipelined feed and a lazy hub (pipeline=True, lazy=True)")
+        if listen and not pipeline:
+            raise ValueError("listen needs the pipelined feed (pipeline=True): the synchronous hub runs the listener stages as it is")
         self.engine = engine if engine is not None else SsdrEngine(self.n_ch, device)
         # waterfall zoom ("SET zoom=", utils_supersdr.py:741, 839): the lines then span 1/zoom of the IQ band around each
         # channel's zoom centre (set_wf_center) and one line needs `zoom` superframes: the hub batches that many per GPU run
@@ -211,6 +218,7 @@ class IQHub:
             self.engine.set_wfdata_rows(self.trace_rows)
         self._smeter = None
         self.pipeline = bool(pipeline)
+        self._listen = bool(listen)                  # the pipelined feed runs squelch, de-emphasis, wire compression and views (SSDR_FEED_LISTEN)
         self._inflight, self._depth = 0, int(depth)
         self.wire = bool(wire)                       # slots hold SND bodies (kiwi/client.py:443-454), unpacked on the device
         # feed_block's one copy, split over a few threads when the block is large (NumPy copies outside the GIL): a single core moves
@@ -288,7 +296,7 @@ class IQHub:
         self.superframes = 0
         if self.pipeline:
             self.engine.feed_open(2 * self.zoom * self.batch_superframes, self._depth, post=self.gpu_post, **({"wire": True} if self.wire else {}),
-                                  **({"lazy_out": True} if self._lazy_out else {}))
+                                  **({"lazy_out": True} if self._lazy_out else {}), **({"listen": True} if self._listen else {}))
         if not self._lazy:
             for c in range(self.n_ch):
                 self.attach(c, wf=True, snd=True)
@@ -420,7 +428,7 @@ class IQHub:
         "SET squelch=<v> param=<tail_s>", the RSSI squelch of every other mode but iq (v dB over the noise floor 0..99, 0 = off; the
         tail in frames 0..1024).  ValueError out of range, and then nothing changes.  The setting is stored here and handed to the
         engine when the engine has set_squelch; a setting that would act in the channel's current mode on an engine without it,
-        or any level above 0 on the pipelined hub (the feed does not run the squelch), is a ValueError.  Resets the channel's
+        or any level above 0 on a pipelined hub built without listen=True (its feed does not run the squelch), is a ValueError.  Resets the channel's
         squelch state."""
         c = int(channel)
         if not 0 <= c < self.n_ch:
@@ -430,7 +438,7 @@ class IQHub:
             new = tuple(int(o if v is None else v) for o, v in zip(old, (fm_level, fm_max, rssi_level, tail_frames)))
             check_squelch(*new)
             acts = _squelch_acts(new, self.params(c).mode)
-            if self.pipeline:
+            if self.pipeline and not self._listen:
                 if new[0] or new[2]:
                     raise ValueError("squelch needs the synchronous hub (the pipelined feed does not run it)")
             elif hasattr(self.engine, "set_squelch"):
@@ -449,7 +457,7 @@ class IQHub:
         """The audio de-emphasis of one channel (ssdr_set_deemphasis); None leaves a value as it is.  am: "SET de_emp=<n>", the filter
         that acts while the channel is in AM; nfm: "SET de_emp=<n> nfm=1", the one that acts in NBFM; each 0 = off, 1 = 75 us,
         2 = 50 us.  ValueError out of range, and then nothing changes.  A nonzero setting on an engine without set_deemphasis, or on
-        the pipelined hub (the feed does not run the filter), is a ValueError.  Resets the channel's filter state."""
+        a pipelined hub built without listen=True (its feed does not run the filter), is a ValueError.  Resets the channel's filter state."""
         c = int(channel)
         if not 0 <= c < self.n_ch:
             raise IndexError("channel %d of %d" % (c, self.n_ch))
@@ -457,7 +465,7 @@ class IQHub:
         with self._lock:
             old = self._deemp.get(c, (0, 0))
             new = tuple(int(o if v is None else v) for o, v in zip(old, (am, nfm)))
-            if self.pipeline:
+            if self.pipeline and not self._listen:
                 if new[0] or new[1]:
                     raise ValueError("de-emphasis needs the synchronous hub (the pipelined feed does not run it)")
             elif hasattr(self.engine, "set_deemphasis"):
@@ -476,8 +484,8 @@ class IQHub:
         """"SET compression=" (snd) / "SET wf_comp=" (wf) of one channel: True / False, None leaves that flag as it is.  Frames and
         lines produced from the next superframe on carry their ADPCM payload (Frame.adpcm, WfLine.adpcm).  Turning SND compression on
         restarts the channel's encoder at (0, 0), where a new client's decoder starts; a request that changes nothing does not reach
-        the engine.  The pipelined hub refuses (ValueError) before the engine is touched."""
-        if self.pipeline:
+        the engine.  A pipelined hub built without listen=True refuses (ValueError) before the engine is touched."""
+        if self.pipeline and not self._listen:
             raise ValueError("wire compression needs the synchronous hub (the pipelined feed does not run the encoder)")
         import bisect
         c = int(channel)
@@ -511,11 +519,12 @@ class IQHub:
         around offset_hz (Hz from the band's centre) instead of the full-span line -- 0..k single lines (N = 1) per superframe, one
         per 1024 zoomed samples (per 512 at hop 512).  zoom 2, 4 or 8; zoom 1 removes the view.  The other channels see no
         difference, and the views of other channels keep their streams.  A changed view starts from silence.  ValueError out of
-        range, on the pipelined hub and on a hub built with zoom > 1 (before the engine is touched), and then nothing changes."""
+        range, on a pipelined hub built without listen=True and on a hub built with zoom > 1 (before the engine is touched), and then
+        nothing changes."""
         c = int(channel)
         if not 0 <= c < self.n_ch:
             raise IndexError("channel %d of %d" % (c, self.n_ch))
-        if self.pipeline:
+        if self.pipeline and not self._listen:
             raise ValueError("a waterfall view needs the synchronous hub (the pipelined feed does not run the views)")
         if self.zoom != 1:
             raise ValueError("a waterfall view needs a hub built with zoom=1 (views and the hub-wide zoom exclude each other)")
@@ -790,6 +799,7 @@ class IQHub:
         wpos = {} if r.wf_adpcm is None or not len(r.wf_adpcm) else {c: i for i, c in enumerate(r.wf_adpcm_channels)}
         spos = {} if r.snd_adpcm is None else {c: i for i, c in enumerate(r.snd_adpcm_channels)}
         vpos = {} if not r.view_channels else {c: i for i, c in enumerate(r.view_channels)}
+        qpos = None if r.squelched_channels is None else {c: i for i, c in enumerate(r.squelched_channels)}     # None: a row per channel
         for c in self._wf_att:
             q = self.wf_queue._q[c]
             if c in vpos:                                    # a channel with a view gets the view's lines, not the full-span one
@@ -831,8 +841,10 @@ class IQHub:
                     r.iq[c, f * L.FRAME:(f + 1) * L.FRAME].copy() if iq_mode else None)
                 if sc is not None:
                     fr.adpcm = r.snd_adpcm[sc, f * (L.FRAME // 2):(f + 1) * (L.FRAME // 2)].tobytes()
-                if r.squelched is not None and r.squelched[c, f]:
-                    fr.squelched = True
+                if r.squelched is not None:
+                    qc = c if qpos is None else qpos.get(c)
+                    if qc is not None and r.squelched[qc, f]:
+                        fr.squelched = True
                 _put_drop_oldest(q, fr)
 
     def _run_pipelined(self, batch):
@@ -870,9 +882,20 @@ class IQHub:
                 color = None
             if not self._n_snd_clients:
                 play = mono = None
+        listen = {}
+        if self._listen:                              # the listener parts, with the lists the batch was submitted under
+            li = eng.feed_collect_listen()
+            if len(li["snd_channels"]):
+                listen.update(snd_adpcm=li["snd_adpcm"], snd_adpcm_channels=[int(c) for c in li["snd_channels"]])
+            if len(li["wf_channels"]):
+                listen.update(wf_adpcm=li["wf_adpcm"], wf_adpcm_channels=[int(c) for c in li["wf_channels"]])
+            if len(li["sq_channels"]):
+                listen.update(squelched=li["sq_closed"], squelched_channels=[int(c) for c in li["sq_channels"]])
+            if li["views"]:
+                listen.update(view_lines=li["view_lines"], view_channels=[int(v[0]) for v in li["views"]])
         self._hand_out(SuperframeResult(seq=self.superframes - self._inflight, wf=wf, n_avg=n_avg, color=color, chans=chans, pcm=pcm,
                                         rssi=rssi, flags=flags, play=play, mono=mono, wire_rssi=got[3] if len(got) > 3 else None,
-                                        post_channels=sel, out_channels=sel if self._lazy_out else None))
+                                        post_channels=sel, out_channels=sel if self._lazy_out else None, **listen))
 
     def flush(self):
         """pipeline mode: wait for the superframes still in flight and hand their results out"""
