@@ -552,7 +552,7 @@ int ssdr_feed_collect_lazy(ssdr_ctx *ctx, uint32_t *n_sel, int16_t **d_wf_sum, i
  * ssdr_set_wf_zoom > 1 still refuse, and so do the checkpoint calls), and ssdr_set_squelch, ssdr_set_deemphasis, ssdr_set_compression and
  * ssdr_set_wf_views are accepted while the feed is open, with their state rules, argument checks and all-or-nothing behaviour
  * unchanged.  A setter acts on every batch submitted after the call and on none submitted before it, in flight or not: it waits for
- * the ctx's kernel streams, as ssdr_set_params does, never for the copies out.  Every slot owns a listener block in device and in
+ * the ctx's kernel streams, as ssdr_set_params does, never for the copies out.  Every slot holds four listener parts in device and in
  * pinned host memory, sized at ssdr_feed_open: closed flags for n_ch channels, each payload list for min(n_ch, SSDR_FEED_LAZY_MAX)
  * channels, SSDR_WF_VIEWS_MAX views of the most lines n_frames can yield at the hop in force.  The stages of the slot's batch write
  * there (the kernels and their arithmetic are those of ssdr_run_chain), and every non-empty part comes back with one copy behind the
@@ -561,8 +561,8 @@ int ssdr_feed_collect_lazy(ssdr_ctx *ctx, uint32_t *n_sel, int16_t **d_wf_sum, i
  * of the two lists.  The PCM of ssdr_feed_collect (with SSDR_FEED_LAZY_OUT: the selection's rows, gathered behind the tail) and the
  * play buffer of SSDR_FEED_POST are squelched and de-emphasised, as ssdr_run_audio's are.
  * While such a feed is open ssdr_audio_squelch, ssdr_audio_adpcm, ssdr_wf_adpcm, ssdr_wf_view_lines and ssdr_read_wf_view return
- * SSDR_ESTATE: the ctx's own buffers hold no batch of the feed.  ssdr_feed_close frees the blocks; settings and state stay, and the
- * synchronous calls carry on from the state the feed left.
+ * SSDR_ESTATE, and after its close until a synchronous run: the ctx's own buffers hold no batch of the feed.  ssdr_feed_close frees
+ * the slots; settings and state stay, and the synchronous calls carry on from the state the feed left.
  *   ssdr_feed_collect_listen(ctx, &out)    of the batch ssdr_feed_collect returned last: the four parts with the lists in force at
  *                                          that batch's submit (host copies, latched per slot), rows in each stage's own list
  *                                          order; pointers valid as long as ssdr_feed_collect's, NULL for an empty part.

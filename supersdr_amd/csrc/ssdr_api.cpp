@@ -9,6 +9,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <new>
+#include <type_traits>
 #include <utility>
 #include <vector>
 
@@ -42,10 +43,12 @@ static int ssdr_caught(bool nomem) noexcept
     catch (const std::bad_alloc &) { return ssdr_caught(true); }   \
     catch (...) { return ssdr_caught(false); }
 
-// One batch: its input, and its results with their capacities and extents.  The ctx owns the one of ssdr_push_iq / ssdr_run_*
-// (`own`: what every getter and "the last run" reads); a slot of the pipelined feed forms one from its buffers.  The stages take
-// the batch they work on as a parameter.
+// One batch: its input, and its results -- the listener stages' among them -- with their capacities, "valid" marks and extents.
+// The ctx owns the one of ssdr_push_iq / ssdr_run_* (`own`: what every getter and "the last run" reads; its buffers grow on demand);
+// a slot of the pipelined feed holds one whose buffers are parts of the slot's device block (`borrowed`).  The stages take the batch
+// they work on as a parameter and never ask whose it is.
 struct Batch {
+    bool borrowed = false;                    // the buffers are somebody else's memory and the capacities final: never freed or grown from here
     const uint32_t *d_iq = nullptr;
     uint32_t in_frames = 0;
     bool have_input = false;
@@ -58,12 +61,12 @@ struct Batch {
     uint32_t audio_run_frames = 0;            // frames the last audio run (or ssdr_set_pcm) produced: their extent and stride
     uint8_t *d_flags = nullptr;               // ADC-overflow flag per frame of the last audio run
     size_t flags_frames = 0;
-    // a slot of a listen feed (SSDR_FEED_LISTEN): the listener stages write here, not into the ctx's own buffers (whose "valid" marks
-    // such a batch leaves down); the capacities are the slot's, fixed when the feed was opened
-    bool listen = false;
-    uint8_t *d_sq_closed = nullptr, *d_snd_adpcm = nullptr, *d_wf_adpcm = nullptr;
-    int16_t *d_wv_lines = nullptr;
-    size_t wv_lines_rows = 0;
+    // the listener stages' results: buffer, capacity, "there has been a run with the settings as they are", extent of that run
+    uint8_t *d_sq_closed = nullptr; size_t sq_closed_bytes = 0; bool sq_valid = false; uint32_t sq_frames = 0;                 // [sq_n][frames] squelch closed flags
+    uint8_t *d_snd_adpcm = nullptr; size_t snd_adpcm_bytes = 0; bool snd_adpcm_valid = false; uint32_t snd_adpcm_frames = 0;   // [comp_snd_n][frames * 256] SND payloads
+    uint8_t *d_wf_adpcm = nullptr; size_t wf_adpcm_bytes = 0; bool wf_adpcm_valid = false; uint32_t wf_adpcm_lines = 0;        // [lines][comp_wf_n][517] W/F payloads
+    int16_t *d_wv_lines = nullptr; size_t wv_lines_rows = 0;      // [total][1024] the views' lines, compact (their validity: ssdr_ctx::wv_run_valid)
+    std::vector<uint32_t> wv_run_lines; uint32_t wv_run_total = 0;        // [views] lines of each view; their total
 };
 // What ssdr_run_chain decides for a batch (chain_plan), handed to the two stages
 struct ChainPlan {
@@ -131,20 +134,21 @@ struct ssdr_ctx {
     uint32_t *d_iq_out = nullptr;             // [n_ch][n_frames*512] I | Q << 16 of the channels in SSDR_MODE_IQ (allocated when one exists)
     size_t iq_out_frames = 0;
     bool iq_out_valid = false;
-    // pipelined host feed (ssdr_feed_*): slots of pinned host memory + their own device buffers
+    // pipelined host feed (ssdr_feed_*): a slot is one batch, one device block and one pinned host block; every pointer below and
+    // every buffer of `b` is a part of one of the two (feed_slot_layout), set at ssdr_feed_open and null where its flag is not set
     struct FeedSlot {
+        uint8_t *d_block = nullptr, *h_block = nullptr;  // the slot's two allocations
+        Batch b;                                         // input and results of the batch in this slot (borrowed: parts of d_block)
         void *h_in = nullptr;                            // int16 IQ, or SND bodies in wire mode
         int16_t *h_wf = nullptr, *h_pcm = nullptr;
-        float *h_rssi = nullptr, *h_wire_rssi = nullptr;
-        uint8_t *d_wire = nullptr;
-        float *d_wire_rssi = nullptr;
-        uint32_t *d_in = nullptr;
-        int16_t *d_wf = nullptr, *d_pcm = nullptr;
-        float *d_rssi = nullptr;
+        float *h_rssi = nullptr;
+        uint8_t *h_flags = nullptr;                      // ADC-overflow flag per frame of this batch
         hipEvent_t ev_in = nullptr, ev_run = nullptr, ev_out = nullptr;
         uint32_t lines = 0;
         uint32_t n_avg = 1;                              // averaging N in force when the batch was submitted
-        uint8_t *d_flags = nullptr, *h_flags = nullptr;  // ADC-overflow flag per frame of this batch
+        // SSDR_FEED_WIRE: the bodies as they came, the RSSI of their headers
+        uint8_t *d_wire = nullptr;
+        float *d_wire_rssi = nullptr, *h_wire_rssi = nullptr;
         // SSDR_FEED_POST: spectrum_db2col / play_buffer of this batch
         float *d_color = nullptr, *h_color = nullptr;
         ssdr_db2col_chan *d_dbchan = nullptr, *h_dbchan = nullptr;
@@ -152,17 +156,16 @@ struct ssdr_ctx {
         int16_t *d_play = nullptr, *h_play = nullptr, *d_mono = nullptr, *h_mono = nullptr;
         bool has_mono = false;
         uint32_t n_post = 0;                             // channels the batch was post-processed for (ssdr_set_post_channels at submit)
-        // SSDR_FEED_LAZY_OUT: compact rows of the selected channels (what is copied back); the whole-batch d_wf / d_pcm / ... stay on the device
+        // SSDR_FEED_LAZY_OUT: compact rows of the selected channels (what is copied back); the whole-batch results of `b` stay on the device
         int16_t *d_sel_wf = nullptr, *d_sel_pcm = nullptr;
         float *d_sel_rssi = nullptr, *d_sel_wire_rssi = nullptr;
         uint8_t *d_sel_flags = nullptr;
         uint32_t n_sel = 0;
-        // SSDR_FEED_LISTEN: the listener block -- one device and one pinned host allocation, the four parts at the feed's offsets --
-        // and the lists in force at the batch's submit
-        uint8_t *d_listen = nullptr, *h_listen = nullptr;
-        std::vector<uint32_t> sq_list, snd_list, wf_list, wv_lines;
+        // SSDR_FEED_LISTEN: where the listener results of `b` arrive on the host, and the lists in force at the batch's submit
+        uint8_t *h_sq_closed = nullptr, *h_snd_adpcm = nullptr, *h_wf_adpcm = nullptr;
+        int16_t *h_wv_lines = nullptr;
+        std::vector<uint32_t> sq_list, snd_list, wf_list;
         std::vector<ssdr_wf_view> wv;
-        uint32_t wf_adpcm_lines = 0, wv_total = 0;
     };
     std::vector<FeedSlot> feed;
     uint32_t feed_frames = 0, feed_head = 0, feed_tail = 0, feed_inflight = 0;
@@ -172,7 +175,6 @@ struct ssdr_ctx {
     bool feed_lazy = false;                              // SSDR_FEED_LAZY_OUT: only the selected channels' results are copied back
     uint32_t feed_lazy_max = 0;                          // rows the compact buffers hold
     bool feed_listen = false;                            // SSDR_FEED_LISTEN: the listener stages run in the slot pipeline
-    size_t listen_off[4] = {}, listen_wv_rows = 0;       // where closed flags, SND payloads, W/F payloads and view lines lie in a slot's block; the view lines it holds
     std::vector<ssdr_db2col_chan> feed_dbchan;           // display state for the next submits (ssdr_feed_post)
     std::vector<ssdr_play_chan> feed_playchan;
     int feed_last = -1;                                  // slot ssdr_feed_collect returned last
@@ -241,14 +243,6 @@ struct ssdr_ctx {
     uint32_t comp_snd_n = 0, comp_wf_n = 0;
     uint32_t *d_comp_list = nullptr;
     int32_t *d_adpcm_state = nullptr;                   // [n_ch][2] the SND encoder's (index, prev): the link's, not the DSP's
-    uint8_t *d_snd_adpcm = nullptr;                     // [comp_snd_n][n_frames * 256] of the last audio run
-    size_t snd_adpcm_bytes = 0;
-    bool snd_adpcm_valid = false;
-    uint32_t snd_adpcm_frames = 0;
-    uint8_t *d_wf_adpcm = nullptr;                      // [lines][comp_wf_n][517] of the last ssdr_run_wf
-    size_t wf_adpcm_bytes = 0;
-    bool wf_adpcm_valid = false;
-    uint32_t wf_adpcm_lines = 0;
     // audio squelch (ssdr_set_squelch): host settings at its first call, device memory at the first nonzero level; with no
     // channel squelching nothing is launched
     std::vector<ssdr_squelch_params> h_sq;              // [n_ch] as set
@@ -258,10 +252,6 @@ struct ssdr_ctx {
     bool sq_dirty = false;                              // settings or modes changed since the list was made
     SsdrSquelchChan *d_sq = nullptr;                    // [n_ch] settings + carried state
     uint32_t *d_sq_list = nullptr;                      // [n_ch]
-    uint8_t *d_sq_closed = nullptr;                     // [sq_n][n_frames] of the last audio run
-    size_t sq_closed_bytes = 0;
-    bool sq_valid = false;
-    uint32_t sq_frames = 0;
     // audio de-emphasis (ssdr_set_deemphasis): host settings at its first call, device memory at the first nonzero setting; with
     // no acting channel nothing is launched
     std::vector<ssdr_deemp_params> h_de;                // [n_ch] as set
@@ -276,10 +266,11 @@ struct ssdr_ctx {
     // waterfall views (ssdr_set_wf_views): device memory at the first view; with no view set nothing is launched
     std::vector<ssdr_wf_view> h_wv;                     // the list as set, channels ascending
     std::vector<uint32_t> h_wv_carry;                   // [views] zoomed samples each view carries (mirror of SsdrWfView::carry_n)
-    std::vector<uint32_t> h_wv_run_carry, h_wv_run_lines;   // of the last run: where each view's new samples begin in its row; its lines
-    uint32_t wv_run_n_in = 0, wv_run_total = 0;         // that run's input samples per channel; its lines over all views
+    // the last run's record in the scratch below, which any batch overwrites (its lines are the batch's: Batch::d_wv_lines)
+    std::vector<uint32_t> h_wv_run_carry;               // where each view's new samples begin in its row
+    uint32_t wv_run_n_in = 0;                           // that run's input samples per channel
     uint64_t wv_run_stride = 0;
-    bool wv_run_valid = false;                          // there has been a run with the list as it is
+    bool wv_run_valid = false;                          // the last run was the ctx's own batch's, with the list as it is
     int wv_set = 0;                                     // which of the two sets of state arrays is the current one (a new list is built in the other)
     SsdrWfView *d_wv[2] = {nullptr, nullptr};           // [SSDR_WF_VIEWS_MAX]
     uint32_t *d_wv_hist[2] = {nullptr, nullptr}, *d_wv_carry[2] = {nullptr, nullptr}, *d_wv_tail[2] = {nullptr, nullptr};
@@ -289,13 +280,13 @@ struct ssdr_ctx {
     int16_t *d_wv_acc = nullptr;                        // [2][SSDR_WF_VIEWS_MAX][1024] the waterfall kernel's partial sums (N = 1: never used)
     uint32_t *d_wv_stream = nullptr;                    // [views][stride] carried + new zoomed samples of the last run
     size_t wv_stream_dwords = 0;
-    int16_t *d_wv_wf = nullptr, *d_wv_lines = nullptr;  // the waterfall kernel's [max lines][views][1024]; the compact [total][1024]
-    size_t wv_wf_rows = 0, wv_lines_rows = 0;
+    int16_t *d_wv_wf = nullptr;                         // the waterfall kernel's [max lines][views][1024]
+    size_t wv_wf_rows = 0;
     float wv_ms = 0.0f;                                 // the stage's own timing: ssdr_wf_view_stats
     uint32_t wv_launches = 0;
 };
-// Every device buffer a ctx owns (the feed slots' own: ssdr_feed_close) -- what ssdr_destroy frees.  One line per section of the
-// struct above, in its order: a new `d_` member joins its section's line HERE, and tests/test_gpu_parity.py's
+// Every device buffer a ctx owns (a feed slot's block: ssdr_feed_close) -- what ssdr_destroy frees.  One line per section of the
+// struct above, in its order (the own batch's buffers where `own` stands): a new `d_` member joins its section's line HERE, and tests/test_gpu_parity.py's
 // test_contexts_release_their_device_memory gets a call that allocates it.
 static void free_owned(ssdr_ctx *c)
 {
@@ -304,19 +295,20 @@ static void free_owned(ssdr_ctx *c)
         c->d_win, c->d_thr, c->d_tw64, c->d_tw, c->d_lut,                                                             // tables
         c->d_zoom_taps, c->d_zoom_dphi, c->d_zoom_phase, c->d_zoom_hist, c->d_zoom_out,                               // zoom stage
         c->d_consts, c->d_taps, c->d_state, c->d_hist, c->d_chan_list, c->d_ws_list, c->d_wf_acc[0], c->d_wf_acc[1],  // per-channel
-        c->d_iq_own,                                                                                                  // input batch
-        c->own.d_wf_out, c->own.d_pcm, c->own.d_rssi, c->d_iq_out, c->own.d_flags,                                    // outputs
+        c->d_iq_own, c->own.d_wf_out, c->own.d_pcm, c->own.d_rssi, c->own.d_flags,                                    // input batch, and its results
+        c->own.d_sq_closed, c->own.d_snd_adpcm, c->own.d_wf_adpcm, c->own.d_wv_lines,                                 // ... the listener stages' among them
+        c->d_iq_out,                                                                                                  // outputs that are the ctx's
         c->d_line1, c->d_dbchan1, c->d_color1,                                                                        // pipelined host feed
         c->d_scratch,                                                                                                 // measurement
         c->d_post_sel, c->d_db2col, c->d_color, c->d_play, c->d_play_taps, c->d_play_hist, c->d_play_rs_taps, c->d_play_hist_alt,
         c->d_wfdata, c->d_wfpend, c->d_trace, c->d_trace_y, c->d_smeter, c->d_smeter_in, c->d_play_out, c->d_play_mono,
         c->d_wire, c->d_wire_rssi, c->d_wire_gps,                                                                     // post-processing
         c->d_nb, c->d_nb_mask,                                                                                        // noise blanker
-        c->d_comp_list, c->d_adpcm_state, c->d_snd_adpcm, c->d_wf_adpcm,                                              // wire compression
-        c->d_sq, c->d_sq_list, c->d_sq_closed,                                                                        // squelch
+        c->d_comp_list, c->d_adpcm_state,                                                                             // wire compression
+        c->d_sq, c->d_sq_list,                                                                                        // squelch
         c->d_de_state, c->d_de_list,                                                                                  // de-emphasis
         c->d_wv[0], c->d_wv[1], c->d_wv_hist[0], c->d_wv_hist[1], c->d_wv_carry[0], c->d_wv_carry[1], c->d_wv_tail[0], c->d_wv_tail[1],
-        c->d_wv_taps, c->d_wv_consts, c->d_wv_acc, c->d_wv_stream, c->d_wv_wf, c->d_wv_lines,                         // waterfall views
+        c->d_wv_taps, c->d_wv_consts, c->d_wv_acc, c->d_wv_stream, c->d_wv_wf,                                        // waterfall views
     };
     for (void *p : owned)
         if (p) (void)hipFree(p);
@@ -414,6 +406,12 @@ template <class T> static int grow(ssdr_ctx *c, T *&ptr, size_t &cap, size_t nee
     HIP_TRY(hipMalloc(&ptr, need * unit_bytes));
     cap = need;
     return SSDR_OK;
+}
+// ... in a buffer of batch `b`: a borrowed one has the room it was given, and what it points to is not an allocation to free
+template <class T> static int grow(ssdr_ctx *c, const Batch &b, T *&ptr, size_t &cap, size_t need, size_t unit_bytes)
+{
+    if (cap >= need) return SSDR_OK;
+    return b.borrowed ? SSDR_ESTATE : grow(c, ptr, cap, need, unit_bytes);
 }
 // a result on the main stream to the caller's buffer, host or device.  Each getter keeps its own rule for when the call waits.
 enum CopySync { kSyncHost /* only for a host destination */, kSyncAlways, kSyncLater /* the caller does, behind more copies */ };
@@ -606,7 +604,7 @@ int ssdr_set_params(ssdr_ctx *c, uint32_t first, uint32_t count, const ssdr_chan
     SSDR_TRY(join_audio(c));
     // their squelch state only, a run of consecutive channels at a time
     SSDR_TRY(for_each_run(sq_reset.data(), sq_reset.size(), [&](size_t i, size_t n) { return squelch_upload(c, sq_reset[i], (uint32_t)n); }));
-    if (!sq_reset.empty()) { c->sq_dirty = true; c->sq_valid = false; }
+    if (!sq_reset.empty()) { c->sq_dirty = true; c->own.sq_valid = false; }
     SSDR_TRY(for_each_run(de_reset.data(), de_reset.size(), [&](size_t i, size_t n) { return deemp_reset(c, de_reset[i], (uint32_t)n); }));
     if (!de_reset.empty()) c->de_dirty = true;
     HIP_TRY(hipMemcpyAsync(c->d_consts + first, k.data(), count * sizeof(ssdr_chan_consts), hipMemcpyHostToDevice, c->stream));
@@ -1028,6 +1026,7 @@ static int ensure_input(ssdr_ctx *c, uint32_t n_frames)
 static int ensure_audio_out(ssdr_ctx *c, Batch &b, uint32_t n_frames)
 {
     if (b.audio_frames >= n_frames) return SSDR_OK;
+    if (b.borrowed) return SSDR_ESTATE;
     SSDR_TRY(release(c, b.d_pcm));
     SSDR_TRY(release(c, b.d_rssi));
     b.audio_frames = 0;
@@ -1039,7 +1038,7 @@ static int ensure_audio_out(ssdr_ctx *c, Batch &b, uint32_t n_frames)
 // ... and for `lines` output lines of the waterfall stage
 static int ensure_wf_out(ssdr_ctx *c, Batch &b, uint32_t lines)
 {
-    return grow(c, b.d_wf_out, b.wf_out_lines, lines, (size_t)c->n_ch * SSDR_NFFT * 2);
+    return grow(c, b, b.d_wf_out, b.wf_out_lines, lines, (size_t)c->n_ch * SSDR_NFFT * 2);
 }
 
 // the ctx's own batch takes `n_frames` frames of input at `d_iq`
@@ -1105,17 +1104,16 @@ static int validate_wf_batch(const ssdr_ctx *c, const Batch &b)
 
 // ---- IMA-ADPCM wire compression: the encoder behind the stages (ssdr_set_compression) -------------------------------------
 // room for the SND payloads of an audio run of the current batch
-static int adpcm_snd_alloc(ssdr_ctx *c, const Batch &b)
+static int adpcm_snd_alloc(ssdr_ctx *c, Batch &b)
 {
-    if (b.listen) return SSDR_OK;            // (the slot's block has the room: feed_submit_impl checked)
     const size_t need = (size_t)c->comp_snd_n * b.in_frames * (SSDR_FRAME / 2);
-    if (c->snd_adpcm_bytes >= need) return SSDR_OK;
+    if (b.snd_adpcm_bytes >= need) return SSDR_OK;
     SSDR_TRY(drain_audio(c));
-    c->snd_adpcm_valid = false;
-    return grow(c, c->d_snd_adpcm, c->snd_adpcm_bytes, need, 1);
+    b.snd_adpcm_valid = false;
+    return grow(c, b, b.d_snd_adpcm, b.snd_adpcm_bytes, need, 1);
 }
 // the SND payloads of the audio stage just queued on `s` (its PCM), behind it on the same stream: the state advances once per batch
-static int adpcm_snd_launch(ssdr_ctx *c, const Batch &b, hipStream_t s)
+static int adpcm_snd_launch(ssdr_ctx *c, Batch &b, hipStream_t s)
 {
     if (!c->comp_snd_n) return SSDR_OK;
     SsdrAdpcmArgs e;
@@ -1128,23 +1126,23 @@ static int adpcm_snd_launch(ssdr_ctx *c, const Batch &b, hipStream_t s)
     e.n_samples = b.in_frames * SSDR_FRAME;
     e.consts = c->d_consts;
     e.state = c->d_adpcm_state;
-    e.out = b.listen ? b.d_snd_adpcm : c->d_snd_adpcm;
+    e.out = b.d_snd_adpcm;
     e.out_stride = (uint64_t)b.in_frames * (SSDR_FRAME / 2);
     SSDR_TRY(timed_launch(c, SSDR_K_ADPCM, s, [&]() -> int { HIP_TRY(ssdr_launch_adpcm_enc(e, s)); return SSDR_OK; }));
-    c->snd_adpcm_valid = !b.listen;
-    c->snd_adpcm_frames = b.in_frames;
+    b.snd_adpcm_valid = true;
+    b.snd_adpcm_frames = b.in_frames;
     return SSDR_OK;
 }
 // room for the W/F payloads of `lines` byte lines (the encoder only ever runs on the main stream)
-static int adpcm_wf_alloc(ssdr_ctx *c, uint32_t lines)
+static int adpcm_wf_alloc(ssdr_ctx *c, Batch &b, uint32_t lines)
 {
     const size_t need = (size_t)c->comp_wf_n * lines * SSDR_ADPCM_WF_BYTES;
-    if (c->wf_adpcm_bytes >= need) return SSDR_OK;
-    c->wf_adpcm_valid = false;
-    return grow(c, c->d_wf_adpcm, c->wf_adpcm_bytes, need, 1);
+    if (b.wf_adpcm_bytes >= need) return SSDR_OK;
+    b.wf_adpcm_valid = false;
+    return grow(c, b, b.d_wf_adpcm, b.wf_adpcm_bytes, need, 1);
 }
 // the W/F payloads of the lines the waterfall stage just queued on `s`: only byte lines (N = 1) go on the wire
-static int adpcm_wf_launch(ssdr_ctx *c, const Batch &b, hipStream_t s, uint32_t n_avg)
+static int adpcm_wf_launch(ssdr_ctx *c, Batch &b, hipStream_t s, uint32_t n_avg)
 {
     if (!c->comp_wf_n) return SSDR_OK;
     const uint32_t lines = n_avg == 1 ? b.wf_lines_ready : 0;
@@ -1159,12 +1157,12 @@ static int adpcm_wf_launch(ssdr_ctx *c, const Batch &b, hipStream_t s, uint32_t 
         e.n_samples = SSDR_NFFT;
         e.consts = nullptr;
         e.state = nullptr;
-        e.out = b.listen ? b.d_wf_adpcm : c->d_wf_adpcm;
+        e.out = b.d_wf_adpcm;
         e.out_stride = SSDR_ADPCM_WF_BYTES;
         SSDR_TRY(timed_launch(c, SSDR_K_ADPCM, s, [&]() -> int { HIP_TRY(ssdr_launch_adpcm_enc_wf(e, s)); return SSDR_OK; }));
     }
-    c->wf_adpcm_valid = !b.listen;
-    c->wf_adpcm_lines = lines;
+    b.wf_adpcm_valid = true;
+    b.wf_adpcm_lines = lines;
     return SSDR_OK;
 }
 
@@ -1203,22 +1201,22 @@ static int squelch_refresh(ssdr_ctx *c)
     SSDR_TRY(upload_list(c, c->d_sq_list, c->h_sq_list.data(), n));
     c->sq_n = n;
     c->sq_dirty = false;
-    c->sq_valid = false;
+    c->own.sq_valid = false;
     return SSDR_OK;
 }
 // the list up to date, and room for the closed flags of an audio run of the current batch
-static int squelch_prepare(ssdr_ctx *c, const Batch &b)
+static int squelch_prepare(ssdr_ctx *c, Batch &b)
 {
     if (!c->sq_set_n && !c->sq_dirty) return SSDR_OK;
     SSDR_TRY(squelch_refresh(c));
     const size_t need = (size_t)c->sq_n * b.in_frames;
-    if (b.listen || c->sq_closed_bytes >= need) return SSDR_OK;
+    if (b.sq_closed_bytes >= need) return SSDR_OK;
     SSDR_TRY(drain_audio(c));
-    c->sq_valid = false;
-    return grow(c, c->d_sq_closed, c->sq_closed_bytes, need, 1);
+    b.sq_valid = false;
+    return grow(c, b, b.d_sq_closed, b.sq_closed_bytes, need, 1);
 }
 // squelch the PCM of the audio stage just queued on `s`, behind it on the same stream: the state advances once per batch
-static int squelch_launch(ssdr_ctx *c, const Batch &b, hipStream_t s)
+static int squelch_launch(ssdr_ctx *c, Batch &b, hipStream_t s)
 {
     if (!c->sq_n) return SSDR_OK;
     SsdrSquelchArgs q;
@@ -1229,10 +1227,10 @@ static int squelch_launch(ssdr_ctx *c, const Batch &b, hipStream_t s)
     q.list_n = c->sq_n;
     q.consts = c->d_consts;
     q.chan = c->d_sq;
-    q.closed = b.listen ? b.d_sq_closed : c->d_sq_closed;
+    q.closed = b.d_sq_closed;
     SSDR_TRY(timed_launch(c, SSDR_K_SQUELCH, s, [&]() -> int { HIP_TRY(ssdr_launch_squelch(q, s)); return SSDR_OK; }));
-    c->sq_valid = !b.listen;
-    c->sq_frames = b.in_frames;
+    b.sq_valid = true;
+    b.sq_frames = b.in_frames;
     return SSDR_OK;
 }
 
@@ -1295,16 +1293,16 @@ static int deemp_launch(ssdr_ctx *c, const Batch &b, hipStream_t s)
 
 // ---- the tail of the audio stage: squelch, de-emphasis, SND encoder -- one order, whichever kernel did the stage's work ---------
 // lists and room, before anything of the run is launched
-static int audio_tail_prepare(ssdr_ctx *c, const Batch &b)
+static int audio_tail_prepare(ssdr_ctx *c, Batch &b)
 {
     SSDR_TRY(adpcm_snd_alloc(c, b));
-    c->snd_adpcm_valid = false;
+    b.snd_adpcm_valid = false;
     SSDR_TRY(squelch_prepare(c, b));
-    c->sq_valid = false;
+    b.sq_valid = false;
     return deemp_prepare(c);
 }
 // behind the kernel that wrote the PCM, on its stream `s`
-static int audio_tail_launch(ssdr_ctx *c, const Batch &b, hipStream_t s)
+static int audio_tail_launch(ssdr_ctx *c, Batch &b, hipStream_t s)
 {
     SSDR_TRY(squelch_launch(c, b, s));
     SSDR_TRY(deemp_launch(c, b, s));
@@ -1374,7 +1372,7 @@ static int wfview_restart(ssdr_ctx *c, uint32_t first, uint32_t count)
 }
 // Every view advanced by the batch's input for its channel, on the main stream: zoom kernel, the waterfall kernel on the views'
 // streams, finish kernel (ssdr_wf_view.hip).  Timed as one stage with its own event pair; not an SSDR_K_* slot.
-static int wfview_stage(ssdr_ctx *c, const Batch &b)
+static int wfview_stage(ssdr_ctx *c, Batch &b)
 {
     const uint32_t nv = (uint32_t)c->h_wv.size();
     if (!nv) return SSDR_OK;
@@ -1390,8 +1388,7 @@ static int wfview_stage(ssdr_ctx *c, const Batch &b)
     c->wv_run_valid = false;
     SSDR_TRY(grow(c, c->d_wv_stream, c->wv_stream_dwords, (size_t)nv * stride, 4));
     SSDR_TRY(grow(c, c->d_wv_wf, c->wv_wf_rows, (size_t)std::max(max_lines, 1u) * nv, SSDR_NFFT * 2));
-    if (b.listen && total > b.wv_lines_rows) return SSDR_ESTATE;         // (never: the slot holds the most lines its frames can yield)
-    if (!b.listen) SSDR_TRY(grow(c, c->d_wv_lines, c->wv_lines_rows, std::max(total, 1u), SSDR_NFFT * 2));
+    SSDR_TRY(grow(c, b, b.d_wv_lines, b.wv_lines_rows, std::max(total, 1u), SSDR_NFFT * 2));
     if (c->wv_consts_dirty) {
         std::vector<ssdr_chan_consts> k(nv);
         for (uint32_t j = 0; j < nv; j++) k[j] = c->h_consts[c->h_wv[j].channel];
@@ -1403,7 +1400,7 @@ static int wfview_stage(ssdr_ctx *c, const Batch &b)
     SsdrWfViewArgs a;
     a.iq = b.d_iq; a.ch_stride = n_in; a.n_in = n_in; a.n_views = nv; a.hop = c->hop;
     a.views = c->d_wv[set]; a.taps = c->d_wv_taps; a.hist = c->d_wv_hist[set]; a.carry = c->d_wv_carry[set]; a.tail = c->d_wv_tail[set];
-    a.stream = c->d_wv_stream; a.stream_stride = stride; a.wf_lines = c->d_wv_wf; a.lines_out = b.listen ? b.d_wv_lines : c->d_wv_lines;
+    a.stream = c->d_wv_stream; a.stream_stride = stride; a.wf_lines = c->d_wv_wf; a.lines_out = b.d_wv_lines;
     SsdrWfArgs w;                            // the views as the channels of a small ctx: byte lines (N = 1), fp32 bins
     w.iq = c->d_wv_stream; w.ch_stride = stride; w.n_ch = nv; w.n_lines = max_lines;
     w.tail = c->hop == SSDR_NFFT / 2 ? c->d_wv_tail[set] : nullptr;
@@ -1421,11 +1418,11 @@ static int wfview_stage(ssdr_ctx *c, const Batch &b)
     c->wv_launches++;
     c->h_wv_run_carry = c->h_wv_carry;
     for (uint32_t j = 0; j < nv; j++) c->h_wv_carry[j] = c->h_wv_carry[j] + n_in / c->h_wv[j].zoom - lines[j] * c->hop;
-    c->h_wv_run_lines = lines;
+    b.wv_run_lines = lines;
+    b.wv_run_total = total;
     c->wv_run_n_in = n_in;
-    c->wv_run_total = total;
     c->wv_run_stride = stride;
-    c->wv_run_valid = !b.listen;
+    c->wv_run_valid = &b == &c->own;         // (the scratch holds this run: ssdr_read_wf_view reads it for the ctx's own batch only)
     return SSDR_OK;
 }
 
@@ -1458,8 +1455,8 @@ static int wf_stage(ssdr_ctx *c, Batch &b, ChainPlan plan, SsdrWfArgs *one_read,
     const uint32_t n_out = total / c->n_avg;
     const uint32_t n_groups = (total + c->n_avg - 1) / c->n_avg;
     SSDR_TRY(ensure_wf_out(c, b, n_out));
-    if (c->comp_wf_n && c->n_avg == 1 && !b.listen) SSDR_TRY(adpcm_wf_alloc(c, n_out));
-    c->wf_adpcm_valid = false;
+    if (c->comp_wf_n && c->n_avg == 1) SSDR_TRY(adpcm_wf_alloc(c, b, n_out));
+    b.wf_adpcm_valid = false;
     SsdrWfArgs a;
     a.iq = wf_src;
     a.ch_stride = wf_stride;
@@ -1521,7 +1518,7 @@ int ssdr_run_wf(ssdr_ctx *c, int16_t *wf_sum_out, uint32_t *lines_ready, int out
         HIP_TRY(hipSetDevice(c->device));
         SSDR_TRY(wfview_stage(c, b));
         b.wf_lines_ready = 0;
-        c->wf_adpcm_valid = false;
+        b.wf_adpcm_valid = false;
         if (lines_ready) *lines_ready = 0;
         return SSDR_OK;
     }
@@ -1545,7 +1542,7 @@ static int audio_stage(ssdr_ctx *c, Batch &b, ChainPlan plan, const SsdrWfArgs *
     if (!plan.beside) SSDR_TRY(join_audio(c));        // the previous frame's state before this one
     if (b.audio_frames < b.in_frames || b.flags_frames < b.in_frames) SSDR_TRY(drain_audio(c));
     SSDR_TRY(ensure_audio_out(c, b, b.in_frames));
-    SSDR_TRY(grow(c, b.d_flags, b.flags_frames, b.in_frames, c->n_ch));
+    SSDR_TRY(grow(c, b, b.d_flags, b.flags_frames, b.in_frames, c->n_ch));
     const size_t nb_mask_need = c->nb_on ? (size_t)c->n_ch * b.in_frames * 64 * c->decim : 0;     // one bit per input sample
     if (c->nb_mask_bytes < nb_mask_need) {
         SSDR_TRY(drain_audio(c));
@@ -1973,6 +1970,59 @@ static int play_launch(ssdr_ctx *c, const int16_t *pcm, uint32_t nf, int16_t *ou
 // Three streams: host->device copy of batch k+1, the two kernels of batch k, device->host copy of batch k-1.
 // The kernels stay on the ctx stream, in batch order, so the per-channel state and the waterfall's partial sums
 // carry from batch to batch exactly as with ssdr_push_iq / ssdr_run_*.
+//
+// A slot's memory, written once: every buffer with its size and the flag it depends on, as the parts of the slot's device block
+// and of its pinned host block, each part at a multiple of 256 bytes.  The sizes of the two blocks come back in *d_bytes and *h_bytes
+// (a slot without blocks: ssdr_feed_open asks for them first); in a slot with its blocks every pointer is set, the batch's with
+// their capacities, and a part whose flag is down stays null.
+static void feed_slot_layout(const ssdr_ctx *c, uint32_t nf, uint32_t flags, ssdr_ctx::FeedSlot &s, size_t *d_bytes, size_t *h_bytes)
+{
+    size_t d_off = 0, h_off = 0;
+    const auto part = [](uint8_t *base, size_t &off, auto *&ptr, size_t bytes, bool on) {
+        if (on && base) ptr = reinterpret_cast<std::remove_reference_t<decltype(ptr)>>(base + off);
+        if (on) off += (bytes + 255) / 256 * 256;
+    };
+    const auto dev = [&](auto *&ptr, size_t bytes, bool on = true) { part(s.d_block, d_off, ptr, bytes, on); };
+    const auto host = [&](auto *&ptr, size_t bytes, bool on = true) { part(s.h_block, h_off, ptr, bytes, on); };
+    const auto both = [&](auto *&d, auto *&h, size_t bytes, bool on) { dev(d, bytes, on); host(h, bytes, on); };
+    const bool wire = (flags & SSDR_FEED_WIRE) != 0, post = (flags & SSDR_FEED_POST) != 0;
+    const bool lazy = (flags & SSDR_FEED_LAZY_OUT) != 0, listen = (flags & SSDR_FEED_LISTEN) != 0;
+    const size_t n_ch = c->n_ch, wf_lines = c->hop == SSDR_NFFT / 2 ? nf : nf / 2;
+    Batch &b = s.b;
+    b.borrowed = b.have_input = true;
+    b.in_frames = nf; b.wf_out_lines = wf_lines; b.audio_frames = b.flags_frames = nf;
+    // the batch: input and the two stages' results of every channel
+    const size_t in_b = n_ch * nf * SSDR_FRAME * 4, wire_b = n_ch * nf * SSDR_WIRE_BODY;
+    const size_t wf_b = wf_lines * n_ch * SSDR_NFFT * 2, pcm_b = n_ch * nf * SSDR_FRAME * 2, rssi_b = n_ch * nf * sizeof(float), flags_b = n_ch * nf;
+    dev(b.d_iq, in_b); dev(b.d_wf_out, wf_b); dev(b.d_pcm, pcm_b); dev(b.d_rssi, rssi_b); dev(b.d_flags, flags_b);
+    // SSDR_FEED_WIRE: the bodies (the unpack kernel reads whole dwords: 16 bytes to spare) and their headers' RSSI
+    dev(s.d_wire, wire_b + 16, wire); dev(s.d_wire_rssi, rssi_b, wire);
+    // what comes back to the host: every channel's rows, or -- SSDR_FEED_LAZY_OUT -- rows for the listeners, gathered on the device
+    const size_t out_ch = lazy ? c->feed_lazy_max : n_ch;
+    const size_t o_wf_b = wf_b / n_ch * out_ch, o_pcm_b = pcm_b / n_ch * out_ch, o_rssi_b = rssi_b / n_ch * out_ch, o_flags_b = out_ch * nf;
+    host(s.h_in, wire ? wire_b : in_b);
+    dev(s.d_sel_wf, o_wf_b, lazy); host(s.h_wf, o_wf_b);
+    dev(s.d_sel_pcm, o_pcm_b, lazy); host(s.h_pcm, o_pcm_b);
+    dev(s.d_sel_rssi, o_rssi_b, lazy); host(s.h_rssi, o_rssi_b);
+    dev(s.d_sel_flags, o_flags_b, lazy); host(s.h_flags, o_flags_b);
+    dev(s.d_sel_wire_rssi, o_rssi_b, lazy && wire); host(s.h_wire_rssi, o_rssi_b, wire);
+    // SSDR_FEED_POST: colours (a float per bin), display state, play_buffer output sized for the x4 form (either rate fits)
+    const size_t play_b = n_ch * nf * 2048 * 2 * sizeof(int16_t);
+    both(s.d_color, s.h_color, wf_b * 2, post); both(s.d_dbchan, s.h_dbchan, n_ch * sizeof(ssdr_db2col_chan), post);
+    both(s.d_play, s.h_play, play_b, post); both(s.d_mono, s.h_mono, play_b / 2, post);
+    host(s.h_playchan, n_ch * sizeof(ssdr_play_chan), post);
+    // SSDR_FEED_LISTEN: closed flags [n_ch][nf] | SND payloads [lazy_max][nf * 256] | W/F payloads [lines][lazy_max][517] | view
+    // lines [SSDR_WF_VIEWS_MAX * most lines of a view][1024]: a view carries less than a hop and gains at most nf * 512 / 2 samples
+    // per batch
+    const size_t wv_rows = (size_t)SSDR_WF_VIEWS_MAX * ((c->hop - 1 + (size_t)nf * SSDR_FRAME / 2) / c->hop);
+    const size_t sq_b = n_ch * nf, snd_b = (size_t)c->feed_lazy_max * nf * (SSDR_FRAME / 2), wfa_b = wf_lines * c->feed_lazy_max * SSDR_ADPCM_WF_BYTES;
+    if (listen) { b.sq_closed_bytes = sq_b; b.snd_adpcm_bytes = snd_b; b.wf_adpcm_bytes = wfa_b; b.wv_lines_rows = wv_rows; }
+    both(b.d_sq_closed, s.h_sq_closed, sq_b, listen); both(b.d_snd_adpcm, s.h_snd_adpcm, snd_b, listen);
+    both(b.d_wf_adpcm, s.h_wf_adpcm, wfa_b, listen); both(b.d_wv_lines, s.h_wv_lines, wv_rows * SSDR_NFFT * 2, listen);
+    if (d_bytes) *d_bytes = d_off;
+    if (h_bytes) *h_bytes = h_off;
+}
+
 int ssdr_feed_close(ssdr_ctx *c) SSDR_GUARD
 {
     if (!c) return SSDR_EINVAL;
@@ -1983,11 +2033,8 @@ int ssdr_feed_close(ssdr_ctx *c) SSDR_GUARD
     if (c->feed_s_in) (void)hipStreamSynchronize(c->feed_s_in);
     if (c->feed_s_out) (void)hipStreamSynchronize(c->feed_s_out);
     for (auto &s : c->feed) {
-        void *hp[] = {s.h_in, s.h_wf, s.h_pcm, s.h_rssi, s.h_wire_rssi, s.h_flags, s.h_color, s.h_dbchan, s.h_playchan, s.h_play, s.h_mono, s.h_listen};
-        for (void *p : hp) if (p) (void)hipHostFree(p);
-        void *dp[] = {s.d_in, s.d_wf, s.d_pcm, s.d_rssi, s.d_wire, s.d_wire_rssi, s.d_flags, s.d_color, s.d_dbchan, s.d_play, s.d_mono,
-                      s.d_sel_wf, s.d_sel_pcm, s.d_sel_rssi, s.d_sel_wire_rssi, s.d_sel_flags, s.d_listen};
-        for (void *p : dp) if (p) (void)hipFree(p);
+        if (s.h_block) (void)hipHostFree(s.h_block);
+        if (s.d_block) (void)hipFree(s.d_block);
         hipEvent_t ev[] = {s.ev_in, s.ev_run, s.ev_out};
         for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e);
     }
@@ -2024,64 +2071,22 @@ int ssdr_feed_open(ssdr_ctx *c, uint32_t n_frames, uint32_t depth, uint32_t flag
         ssdr_play_chan pc = {100.0, 0.0};
         c->feed_playchan.assign(c->n_ch, pc);
     }
-    const size_t in_b = (size_t)c->n_ch * n_frames * SSDR_FRAME * 4;
-    const size_t wire_b = (size_t)c->n_ch * n_frames * SSDR_WIRE_BODY;
-    const bool wire = (flags & SSDR_FEED_WIRE) != 0;
-    c->feed_wire = wire;
-    const size_t wf_b = (size_t)(c->hop == SSDR_NFFT / 2 ? n_frames : n_frames / 2) * c->n_ch * SSDR_NFFT * 2;
-    const size_t pcm_b = (size_t)c->n_ch * n_frames * SSDR_FRAME * 2;
-    const size_t rssi_b = (size_t)c->n_ch * n_frames * sizeof(float);
-    // SSDR_FEED_LAZY_OUT: what comes back to the host is sized for the listeners, not for the receivers
-    const bool lazy = (flags & SSDR_FEED_LAZY_OUT) != 0;
-    c->feed_lazy = lazy;
+    c->feed_wire = (flags & SSDR_FEED_WIRE) != 0;
+    c->feed_lazy = (flags & SSDR_FEED_LAZY_OUT) != 0;
     c->feed_lazy_max = c->n_ch < SSDR_FEED_LAZY_MAX ? c->n_ch : SSDR_FEED_LAZY_MAX;
-    const size_t out_ch = lazy ? c->feed_lazy_max : c->n_ch;
-    // SSDR_FEED_LISTEN: a slot's listener block -- closed flags [n_ch][n_frames] | SND payloads [lazy_max][n_frames * 256] | W/F payloads
-    // [lines][lazy_max][517] | view lines [SSDR_WF_VIEWS_MAX * most lines of a view][1024]: a view carries less than a hop and gains at
-    // most n_frames * 512 / 2 samples per batch
-    size_t listen_b = 0;
-    if (listen) {
-        const size_t wf_lines = c->hop == SSDR_NFFT / 2 ? n_frames : n_frames / 2;
-        c->listen_wv_rows = (size_t)SSDR_WF_VIEWS_MAX * ((c->hop - 1 + (size_t)n_frames * SSDR_FRAME / 2) / c->hop);
-        const size_t part_b[4] = {(size_t)c->n_ch * n_frames, (size_t)c->feed_lazy_max * n_frames * (SSDR_FRAME / 2),
-                                  wf_lines * c->feed_lazy_max * SSDR_ADPCM_WF_BYTES, c->listen_wv_rows * SSDR_NFFT * 2};
-        for (int i = 0; i < 4; i++) { c->listen_off[i] = listen_b; listen_b += (part_b[i] + 255) / 256 * 256; }
-    }
-    const size_t h_wf_b = wf_b / c->n_ch * out_ch, h_pcm_b = pcm_b / c->n_ch * out_ch, h_rssi_b = rssi_b / c->n_ch * out_ch, h_flags_b = out_ch * n_frames;
+    size_t d_bytes = 0, h_bytes = 0;
+    { ssdr_ctx::FeedSlot none; feed_slot_layout(c, n_frames, flags, none, &d_bytes, &h_bytes); }      // (no blocks: only the sizes)
     c->feed.resize(depth);
     c->feed_listen = listen;                 // (once there are slots: ssdr_feed_close takes the mark down with them)
+    // the ctx's own listener results are from before the feed, and the streams go on in the slots: no getter hands them out again,
+    // after the close either, until a synchronous run has made new ones
+    if (listen) c->own.sq_valid = c->own.snd_adpcm_valid = c->own.wf_adpcm_valid = c->wv_run_valid = false;
     bool ok = hipStreamCreateWithFlags(&c->feed_s_in, hipStreamNonBlocking) == hipSuccess &&
               hipStreamCreateWithFlags(&c->feed_s_out, hipStreamNonBlocking) == hipSuccess;
     for (auto &s : c->feed) {
-        ok = ok && hipHostMalloc(&s.h_in, wire ? wire_b : in_b, hipHostMallocDefault) == hipSuccess;
-        if (wire) {
-            ok = ok && hipHostMalloc(reinterpret_cast<void **>(&s.h_wire_rssi), h_rssi_b, hipHostMallocDefault) == hipSuccess;
-            ok = ok && hipMalloc(&s.d_wire, wire_b + 16) == hipSuccess /* the unpack kernel reads whole dwords */ && hipMalloc(&s.d_wire_rssi, rssi_b) == hipSuccess;
-        }
-        ok = ok && hipHostMalloc(reinterpret_cast<void **>(&s.h_wf), h_wf_b, hipHostMallocDefault) == hipSuccess;
-        ok = ok && hipHostMalloc(reinterpret_cast<void **>(&s.h_pcm), h_pcm_b, hipHostMallocDefault) == hipSuccess;
-        ok = ok && hipHostMalloc(reinterpret_cast<void **>(&s.h_rssi), h_rssi_b, hipHostMallocDefault) == hipSuccess;
-        if (lazy) {
-            ok = ok && hipMalloc(&s.d_sel_wf, h_wf_b) == hipSuccess && hipMalloc(&s.d_sel_pcm, h_pcm_b) == hipSuccess;
-            ok = ok && hipMalloc(&s.d_sel_rssi, h_rssi_b) == hipSuccess && hipMalloc(&s.d_sel_flags, h_flags_b) == hipSuccess;
-            if (wire) ok = ok && hipMalloc(&s.d_sel_wire_rssi, h_rssi_b) == hipSuccess;
-        }
-        ok = ok && hipMalloc(&s.d_in, in_b) == hipSuccess && hipMalloc(&s.d_wf, wf_b) == hipSuccess;
-        ok = ok && hipMalloc(&s.d_pcm, pcm_b) == hipSuccess && hipMalloc(&s.d_rssi, rssi_b) == hipSuccess;
-        ok = ok && hipMalloc(&s.d_flags, (size_t)c->n_ch * n_frames) == hipSuccess;
-        ok = ok && hipHostMalloc(reinterpret_cast<void **>(&s.h_flags), h_flags_b, hipHostMallocDefault) == hipSuccess;
-        if (post) {
-            const size_t color_b = wf_b * 2, db_b = (size_t)c->n_ch * sizeof(ssdr_db2col_chan);
-            const size_t play_b = (size_t)c->n_ch * n_frames * 2048 * 2 * sizeof(int16_t);       // sized for the x4 form, either rate fits
-            ok = ok && hipMalloc(&s.d_color, color_b) == hipSuccess && hipMalloc(&s.d_dbchan, db_b) == hipSuccess;
-            ok = ok && hipMalloc(&s.d_play, play_b) == hipSuccess && hipMalloc(&s.d_mono, play_b / 2) == hipSuccess;
-            ok = ok && hipHostMalloc(reinterpret_cast<void **>(&s.h_color), color_b, hipHostMallocDefault) == hipSuccess;
-            ok = ok && hipHostMalloc(reinterpret_cast<void **>(&s.h_dbchan), db_b, hipHostMallocDefault) == hipSuccess;
-            ok = ok && hipHostMalloc(reinterpret_cast<void **>(&s.h_playchan), (size_t)c->n_ch * sizeof(ssdr_play_chan), hipHostMallocDefault) == hipSuccess;
-            ok = ok && hipHostMalloc(reinterpret_cast<void **>(&s.h_play), play_b, hipHostMallocDefault) == hipSuccess;
-            ok = ok && hipHostMalloc(reinterpret_cast<void **>(&s.h_mono), play_b / 2, hipHostMallocDefault) == hipSuccess;
-        }
-        if (listen) ok = ok && hipMalloc(&s.d_listen, listen_b) == hipSuccess && hipHostMalloc(reinterpret_cast<void **>(&s.h_listen), listen_b, hipHostMallocDefault) == hipSuccess;
+        ok = ok && hipMalloc(&s.d_block, d_bytes) == hipSuccess;
+        ok = ok && hipHostMalloc(reinterpret_cast<void **>(&s.h_block), h_bytes, hipHostMallocDefault) == hipSuccess;
+        if (ok) feed_slot_layout(c, n_frames, flags, s, nullptr, nullptr);
         ok = ok && hipEventCreateWithFlags(&s.ev_in, hipEventDisableTiming) == hipSuccess;
         ok = ok && hipEventCreateWithFlags(&s.ev_run, hipEventDisableTiming) == hipSuccess;
         ok = ok && hipEventCreateWithFlags(&s.ev_out, hipEventDisableTiming) == hipSuccess;
@@ -2107,13 +2112,15 @@ static int feed_submit_impl(ssdr_ctx *c, const void *host_in)
 {
     HIP_TRY(hipSetDevice(c->device));
     auto &s = c->feed[c->feed_head];
+    Batch &b = s.b;                                         // the slot's batch (the ctx's own is not touched)
+    uint32_t *const d_in = const_cast<uint32_t *>(b.d_iq);  // (the slot's memory: the copy or the unpack kernel fills what the stages read)
     const uint32_t nf = c->feed_frames;
     if (c->feed_lazy && (c->d_post_sel ? c->n_post : c->n_ch) > c->feed_lazy_max) return SSDR_ESTATE;     // more listeners than the compact rows hold
     if (c->feed_listen && (c->comp_snd_n > c->feed_lazy_max || c->comp_wf_n > c->feed_lazy_max)) return SSDR_ESTATE;   // ... or than the slot's payload rows
     if (c->feed_wire)
         HIP_TRY(hipMemcpyAsync(s.d_wire, host_in, (size_t)c->n_ch * nf * SSDR_WIRE_BODY, hipMemcpyHostToDevice, c->feed_s_in));
     else
-        HIP_TRY(hipMemcpyAsync(s.d_in, host_in, (size_t)c->n_ch * nf * SSDR_FRAME * 4, hipMemcpyHostToDevice, c->feed_s_in));
+        HIP_TRY(hipMemcpyAsync(d_in, host_in, (size_t)c->n_ch * nf * SSDR_FRAME * 4, hipMemcpyHostToDevice, c->feed_s_in));
     HIP_TRY(hipEventRecord(s.ev_in, c->feed_s_in));
     HIP_TRY(hipStreamWaitEvent(c->stream, s.ev_in, 0));
     if (c->feed_wire) {                                  // header strip + big-endian -> little-endian on the device
@@ -2121,7 +2128,7 @@ static int feed_submit_impl(ssdr_ctx *c, const void *host_in)
         w.bodies = s.d_wire;
         w.n_ch = c->n_ch;
         w.n_frames = nf;
-        w.iq = s.d_in;
+        w.iq = d_in;
         w.ch_stride = (uint64_t)nf * SSDR_FRAME;
         w.rssi = s.d_wire_rssi;
         w.gps = nullptr;
@@ -2129,17 +2136,9 @@ static int feed_submit_impl(ssdr_ctx *c, const void *host_in)
         HIP_TRY(ssdr_launch_iqwire(w, c->stream));
         SSDR_TRY(timed_end(c, SSDR_K_WIRE));
     }
-    // the two stages on this slot's buffers: its batch (the ctx's own is not touched)
-    Batch b;
-    b.d_iq = s.d_in; b.in_frames = nf; b.have_input = true;
-    b.d_wf_out = s.d_wf; b.wf_out_lines = c->hop == SSDR_NFFT / 2 ? nf : nf / 2;
-    b.d_pcm = s.d_pcm; b.d_rssi = s.d_rssi; b.audio_frames = nf;
-    b.d_flags = s.d_flags; b.flags_frames = nf;
-    if (c->feed_listen) {                                   // the listener stages write into the slot's block and nowhere else
-        b.listen = true;
-        b.d_sq_closed = s.d_listen + c->listen_off[0]; b.d_snd_adpcm = s.d_listen + c->listen_off[1]; b.d_wf_adpcm = s.d_listen + c->listen_off[2];
-        b.d_wv_lines = reinterpret_cast<int16_t *>(s.d_listen + c->listen_off[3]); b.wv_lines_rows = c->listen_wv_rows;
-    }
+    // the two stages on the slot's batch: nothing of the batch it held before
+    b.wf_lines_ready = b.audio_run_frames = b.wf_adpcm_lines = b.wv_run_total = 0;
+    b.wv_run_lines.clear();
     uint32_t lines = 0;
     s.n_avg = c->n_avg;
     SSDR_TRY(run_chain(c, b, &lines, nullptr));            // the fused superframe kernel where the batch allows it
@@ -2149,11 +2148,7 @@ static int feed_submit_impl(ssdr_ctx *c, const void *host_in)
         s.snd_list.assign(c->h_comp_list.begin(), c->h_comp_list.begin() + c->comp_snd_n);
         s.wf_list.clear();
         if (c->comp_wf_n) s.wf_list.assign(c->h_comp_list.begin() + c->n_ch, c->h_comp_list.begin() + c->n_ch + c->comp_wf_n);
-        s.wf_adpcm_lines = c->comp_wf_n && s.n_avg == 1 ? lines : 0;
         s.wv = c->h_wv;
-        s.wv_lines.clear();
-        if (!s.wv.empty()) s.wv_lines = c->h_wv_run_lines;
-        s.wv_total = s.wv.empty() ? 0 : c->wv_run_total;
     }
     if (c->feed_post) { s.n_post = c->n_post; s.has_mono = c->n_post && c->recording; }
     if (c->feed_post && c->n_post) {
@@ -2162,22 +2157,22 @@ static int feed_submit_impl(ssdr_ctx *c, const void *host_in)
         if (lines) {
             memcpy(s.h_dbchan, c->feed_dbchan.data(), (size_t)c->n_post * sizeof(ssdr_db2col_chan));
             HIP_TRY(hipMemcpyAsync(s.d_dbchan, s.h_dbchan, (size_t)c->n_post * sizeof(ssdr_db2col_chan), hipMemcpyHostToDevice, c->stream));
-            SSDR_TRY(db2col_launch(c, s.d_wf, lines, c->n_avg, s.d_dbchan, s.d_color));
+            SSDR_TRY(db2col_launch(c, b.d_wf_out, lines, c->n_avg, s.d_dbchan, s.d_color));
         }
         memcpy(s.h_playchan, c->feed_playchan.data(), (size_t)c->n_post * sizeof(ssdr_play_chan));
         HIP_TRY(hipMemcpyAsync(c->d_play, s.h_playchan, (size_t)c->n_post * sizeof(ssdr_play_chan), hipMemcpyHostToDevice, c->stream));
-        SSDR_TRY(play_launch(c, s.d_pcm, nf, s.d_play, c->recording ? s.d_mono : nullptr));
+        SSDR_TRY(play_launch(c, b.d_pcm, nf, s.d_play, c->recording ? s.d_mono : nullptr));
     }
     s.lines = lines;
     // what goes back: every channel's rows, or (SSDR_FEED_LAZY_OUT) the selected channels' rows gathered into compact ones
-    const int16_t *o_wf = s.d_wf, *o_pcm = s.d_pcm;
-    const float *o_rssi = s.d_rssi, *o_wire_rssi = s.d_wire_rssi;
-    const uint8_t *o_flags = s.d_flags;
+    const int16_t *o_wf = b.d_wf_out, *o_pcm = b.d_pcm;
+    const float *o_rssi = b.d_rssi, *o_wire_rssi = s.d_wire_rssi;
+    const uint8_t *o_flags = b.d_flags;
     size_t o_ch = c->n_ch;
     s.n_sel = c->n_ch;
     if (c->feed_lazy) {
         SsdrGatherArgs g;
-        g.wf = s.d_wf; g.pcm = s.d_pcm; g.rssi = s.d_rssi; g.flags = s.d_flags; g.wire_rssi = c->feed_wire ? s.d_wire_rssi : nullptr;
+        g.wf = b.d_wf_out; g.pcm = b.d_pcm; g.rssi = b.d_rssi; g.flags = b.d_flags; g.wire_rssi = c->feed_wire ? s.d_wire_rssi : nullptr;
         g.wf_out = s.d_sel_wf; g.pcm_out = s.d_sel_pcm; g.rssi_out = s.d_sel_rssi; g.flags_out = s.d_sel_flags; g.wire_rssi_out = s.d_sel_wire_rssi;
         g.sel = c->d_post_sel; g.n_sel = c->d_post_sel ? c->n_post : c->n_ch; g.n_ch = c->n_ch; g.n_lines = lines; g.n_frames = nf;
         HIP_TRY(ssdr_launch_gather(g, c->stream));
@@ -2209,11 +2204,12 @@ static int feed_submit_impl(ssdr_ctx *c, const void *host_in)
         }
     }
     if (c->feed_listen) {                                   // one copy per non-empty part
-        const size_t part_b[4] = {s.sq_list.size() * nf, s.snd_list.size() * nf * (SSDR_FRAME / 2),
-                                  (size_t)s.wf_adpcm_lines * s.wf_list.size() * SSDR_ADPCM_WF_BYTES, (size_t)s.wv_total * SSDR_NFFT * 2};
-        for (int i = 0; i < 4; i++)
-            if (part_b[i])
-                HIP_TRY(hipMemcpyAsync(s.h_listen + c->listen_off[i], s.d_listen + c->listen_off[i], part_b[i], hipMemcpyDeviceToHost, c->feed_s_out));
+        const struct { void *h; const void *d; size_t bytes; } part[4] = {
+            {s.h_sq_closed, b.d_sq_closed, s.sq_list.size() * nf}, {s.h_snd_adpcm, b.d_snd_adpcm, s.snd_list.size() * nf * (SSDR_FRAME / 2)},
+            {s.h_wf_adpcm, b.d_wf_adpcm, (size_t)b.wf_adpcm_lines * s.wf_list.size() * SSDR_ADPCM_WF_BYTES},
+            {s.h_wv_lines, b.d_wv_lines, (size_t)b.wv_run_total * SSDR_NFFT * 2}};
+        for (const auto &p : part)
+            if (p.bytes) HIP_TRY(hipMemcpyAsync(p.h, p.d, p.bytes, hipMemcpyDeviceToHost, c->feed_s_out));
     }
     HIP_TRY(hipEventRecord(s.ev_out, c->feed_s_out));
     c->feed_head = (c->feed_head + 1) % (uint32_t)c->feed.size();
@@ -2306,16 +2302,16 @@ int ssdr_feed_collect_listen(ssdr_ctx *c, ssdr_feed_listen *out) SSDR_GUARD
     out->sq_n = (uint32_t)s.sq_list.size();
     out->snd_n = (uint32_t)s.snd_list.size();
     out->wf_n = (uint32_t)s.wf_list.size();
-    out->wf_lines = s.wf_adpcm_lines;
+    out->wf_lines = s.b.wf_adpcm_lines;
     out->view_n = (uint32_t)s.wv.size();
-    out->view_total_lines = s.wv_total;
-    if (out->sq_n) { out->sq_channels = s.sq_list.data(); out->sq_closed = s.h_listen + c->listen_off[0]; }
-    if (out->snd_n) { out->snd_channels = s.snd_list.data(); out->snd_adpcm = s.h_listen + c->listen_off[1]; }
-    if (out->wf_n) { out->wf_channels = s.wf_list.data(); if (out->wf_lines) out->wf_adpcm = s.h_listen + c->listen_off[2]; }
+    out->view_total_lines = s.b.wv_run_total;
+    if (out->sq_n) { out->sq_channels = s.sq_list.data(); out->sq_closed = s.h_sq_closed; }
+    if (out->snd_n) { out->snd_channels = s.snd_list.data(); out->snd_adpcm = s.h_snd_adpcm; }
+    if (out->wf_n) { out->wf_channels = s.wf_list.data(); if (out->wf_lines) out->wf_adpcm = s.h_wf_adpcm; }
     if (out->view_n) {
         out->views = s.wv.data();
-        out->lines_per_view = s.wv_lines.data();
-        if (out->view_total_lines) out->view_lines = reinterpret_cast<const int16_t *>(s.h_listen + c->listen_off[3]);
+        out->lines_per_view = s.b.wv_run_lines.data();
+        if (out->view_total_lines) out->view_lines = s.h_wv_lines;
     }
     return SSDR_OK;
 } SSDR_UNGUARD
@@ -2326,10 +2322,10 @@ int ssdr_feed_collect_lazy(ssdr_ctx *c, uint32_t *n_sel, int16_t **d_wf_sum, int
     if (c->feed.empty() || c->feed_last < 0) return SSDR_ESTATE;
     auto &s = c->feed[c->feed_last];
     if (n_sel) *n_sel = s.n_sel;
-    if (d_wf_sum) *d_wf_sum = s.d_wf;
-    if (d_pcm) *d_pcm = s.d_pcm;
-    if (d_rssi) *d_rssi = s.d_rssi;
-    if (d_flags) *d_flags = s.d_flags;
+    if (d_wf_sum) *d_wf_sum = s.b.d_wf_out;
+    if (d_pcm) *d_pcm = s.b.d_pcm;
+    if (d_rssi) *d_rssi = s.b.d_rssi;
+    if (d_flags) *d_flags = s.b.d_flags;
     return SSDR_OK;
 } SSDR_UNGUARD
 
@@ -2981,8 +2977,8 @@ int ssdr_set_compression(ssdr_ctx *c, uint32_t first, uint32_t count, const uint
     SSDR_TRY(upload_list(c, c->d_comp_list, c->h_comp_list.data(), 2 * (size_t)c->n_ch));
     c->comp_snd_n = ns;
     c->comp_wf_n = nw;
-    if (snd_changed) c->snd_adpcm_valid = false;           // the rows of the last run were another selection's
-    if (wf_changed) c->wf_adpcm_valid = false;
+    if (snd_changed) c->own.snd_adpcm_valid = false;       // the rows of the last run were another selection's
+    if (wf_changed) c->own.wf_adpcm_valid = false;
     return SSDR_OK;
 } SSDR_UNGUARD
 
@@ -2998,20 +2994,20 @@ int ssdr_compression_channels(ssdr_ctx *c, int which, uint32_t *list, uint32_t *
 int ssdr_audio_adpcm(ssdr_ctx *c, uint8_t *out, int out_is_device) SSDR_GUARD
 {
     if (!c || !out) return SSDR_EINVAL;
-    if (c->feed_listen || !c->comp_snd_n || !c->snd_adpcm_valid) return SSDR_ESTATE;     // (a listen feed's payloads are its slots')
+    if (c->feed_listen || !c->comp_snd_n || !c->own.snd_adpcm_valid) return SSDR_ESTATE;     // (a listen feed's payloads are its slots')
     HIP_TRY(hipSetDevice(c->device));
     SSDR_TRY(join_audio(c));
-    return copy_out(c, out, c->d_snd_adpcm, (size_t)c->comp_snd_n * c->snd_adpcm_frames * (SSDR_FRAME / 2), out_is_device, kSyncAlways);
+    return copy_out(c, out, c->own.d_snd_adpcm, (size_t)c->comp_snd_n * c->own.snd_adpcm_frames * (SSDR_FRAME / 2), out_is_device, kSyncAlways);
 } SSDR_UNGUARD
 
 int ssdr_wf_adpcm(ssdr_ctx *c, uint8_t *out, uint32_t *lines, int out_is_device) SSDR_GUARD
 {
     if (!c || !lines) return SSDR_EINVAL;
-    if (c->feed_listen || !c->comp_wf_n || !c->wf_adpcm_valid) return SSDR_ESTATE;
-    *lines = c->wf_adpcm_lines;
-    if (!out || !c->wf_adpcm_lines) return SSDR_OK;
+    if (c->feed_listen || !c->comp_wf_n || !c->own.wf_adpcm_valid) return SSDR_ESTATE;
+    *lines = c->own.wf_adpcm_lines;
+    if (!out || !c->own.wf_adpcm_lines) return SSDR_OK;
     HIP_TRY(hipSetDevice(c->device));
-    return copy_out(c, out, c->d_wf_adpcm, (size_t)c->wf_adpcm_lines * c->comp_wf_n * SSDR_ADPCM_WF_BYTES, out_is_device, kSyncAlways);
+    return copy_out(c, out, c->own.d_wf_adpcm, (size_t)c->own.wf_adpcm_lines * c->comp_wf_n * SSDR_ADPCM_WF_BYTES, out_is_device, kSyncAlways);
 } SSDR_UNGUARD
 
 int ssdr_squelch_tail_frames(double tail_s, uint32_t kiwi_rate, uint32_t *frames) SSDR_GUARD
@@ -3055,7 +3051,7 @@ int ssdr_set_squelch(ssdr_ctx *c, uint32_t first, uint32_t count, const ssdr_squ
     }
     c->sq_set_n = set_n;
     c->sq_dirty = true;
-    c->sq_valid = false;
+    c->own.sq_valid = false;
     return squelch_upload(c, first, count);
 } SSDR_UNGUARD
 
@@ -3069,22 +3065,22 @@ int ssdr_get_squelch(ssdr_ctx *c, uint32_t first, uint32_t count, ssdr_squelch_p
 int ssdr_audio_squelch(ssdr_ctx *c, uint8_t *closed_out, int out_is_device) SSDR_GUARD
 {
     if (!c || !closed_out) return SSDR_EINVAL;
-    if (c->feed_listen || c->sq_dirty || !c->sq_n || !c->sq_valid) return SSDR_ESTATE;       // (a change of settings or modes since the run: not that run's; a listen feed's flags are its slots')
+    if (c->feed_listen || c->sq_dirty || !c->sq_n || !c->own.sq_valid) return SSDR_ESTATE;       // (a change of settings or modes since the run: not that run's; a listen feed's flags are its slots')
     HIP_TRY(hipSetDevice(c->device));
     SSDR_TRY(join_audio(c));
-    const size_t row = c->sq_frames;
+    const size_t row = c->own.sq_frames;
     // the rows of the listed channels, a run of consecutive channels at a time; every other row is zero
     if (out_is_device) {
         HIP_TRY(hipMemsetAsync(closed_out, 0, (size_t)c->n_ch * row, c->stream));
         SSDR_TRY(for_each_run(c->h_sq_list.data(), c->sq_n, [&](size_t i, size_t n) -> int {
-            HIP_TRY(hipMemcpyAsync(closed_out + (size_t)c->h_sq_list[i] * row, c->d_sq_closed + i * row, n * row, hipMemcpyDeviceToDevice, c->stream));
+            HIP_TRY(hipMemcpyAsync(closed_out + (size_t)c->h_sq_list[i] * row, c->own.d_sq_closed + i * row, n * row, hipMemcpyDeviceToDevice, c->stream));
             return SSDR_OK;
         }));
         HIP_TRY(hipStreamSynchronize(c->stream));
         return SSDR_OK;
     }
     std::vector<uint8_t> rows((size_t)c->sq_n * row);
-    HIP_TRY(hipMemcpyAsync(rows.data(), c->d_sq_closed, rows.size(), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(rows.data(), c->own.d_sq_closed, rows.size(), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
     memset(closed_out, 0, (size_t)c->n_ch * row);
     for (uint32_t i = 0; i < c->sq_n; i++) memcpy(closed_out + (size_t)c->h_sq_list[i] * row, rows.data() + (size_t)i * row, row);
@@ -3223,11 +3219,11 @@ int ssdr_wf_view_lines(ssdr_ctx *c, int16_t *lines_out, uint32_t *lines_per_view
 {
     if (!c) return SSDR_EINVAL;
     if (c->feed_listen || c->h_wv.empty() || !c->wv_run_valid) return SSDR_ESTATE;
-    if (lines_per_view) std::copy(c->h_wv_run_lines.begin(), c->h_wv_run_lines.end(), lines_per_view);
-    if (total_lines) *total_lines = c->wv_run_total;
-    if (!lines_out || !c->wv_run_total) return SSDR_OK;
+    if (lines_per_view) std::copy(c->own.wv_run_lines.begin(), c->own.wv_run_lines.end(), lines_per_view);
+    if (total_lines) *total_lines = c->own.wv_run_total;
+    if (!lines_out || !c->own.wv_run_total) return SSDR_OK;
     HIP_TRY(hipSetDevice(c->device));
-    return copy_out(c, lines_out, c->d_wv_lines, (size_t)c->wv_run_total * SSDR_NFFT * 2, out_is_device, kSyncHost);
+    return copy_out(c, lines_out, c->own.d_wv_lines, (size_t)c->own.wv_run_total * SSDR_NFFT * 2, out_is_device, kSyncHost);
 } SSDR_UNGUARD
 
 int ssdr_read_wf_view(ssdr_ctx *c, uint32_t view_index, int16_t *iq_out, uint32_t *samples) SSDR_GUARD

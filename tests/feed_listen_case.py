@@ -3,6 +3,8 @@ feed and through the synchronous calls and holds the two to each other bit for b
 through the fp32 twin, squelch_ref and the views' closed form and proves that the case exercises the stages -- both squelching
 channels have open and closed frames, the Z = 8 view has a batch with no line and a batch with one.  NumPy only; nothing here
 touches a GPU."""
+import struct
+
 import numpy as np
 
 import stage_cases as SC
@@ -68,3 +70,17 @@ def apply_late(eng):
         eng.set_squelch(c, [q])
     eng.set_wf_views(VIEWS_LATE)
     eng.set_compression(SND_OFF_LATE, snd=False)
+
+
+def wire_bodies(batch, first_frame=0):
+    """the batch int16 [n_ch, n_frames * 512, 2] as SND bodies (17-byte header, big-endian IQ), built as tests/test_gpu_parity.py's
+    test_pipelined_feed_wire_mode builds them -> (uint8 [n_ch, n_frames, 2065], the headers' RSSI in dBm float64 [n_ch, n_frames])"""
+    n_ch, nf = batch.shape[0], batch.shape[1] // 512
+    bodies, dbm = np.empty((n_ch, nf, 2065), np.uint8), np.empty((n_ch, nf))
+    for c in range(n_ch):
+        for f in range(nf):
+            word = 500 + 10 * c + f
+            hdr = struct.pack("<BI", 0, first_frame + f) + struct.pack(">H", word) + struct.pack("<BBII", 1, 0, 2, 3)
+            bodies[c, f] = np.frombuffer(hdr + batch[c, f * 512:(f + 1) * 512].astype(">i2").tobytes(), np.uint8)
+            dbm[c, f] = 0.1 * word - 127
+    return bodies, dbm

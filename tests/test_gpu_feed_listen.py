@@ -4,7 +4,11 @@ Two ctxs of 8 channels get the same 7 batches of 4 frames (tests/feed_listen_cas
 tests/test_feed_listen_inputs.py).  A goes through ssdr_feed_submit_from / ssdr_feed_collect / ssdr_feed_collect_listen at depth 3, B
 through ssdr_push_iq / ssdr_run_chain and the ctx-owned getters.  Midway, with two batches in flight on A, a squelch goes on for a plain
 channel, one view is dropped and another added, and one compression flag goes off -- on B between the same two batches.  The batches
-in flight must come back as submitted, and their lists as latched."""
+in flight must come back as submitted, and their lists as latched.
+
+The mode "all" opens the feed with all four flags (WIRE | POST | LAZY_OUT | LISTEN), the one combination in which every part of a
+slot's two blocks exists: the batches go in as SND bodies through ssdr_feed_slot / ssdr_feed_submit, the post step and the rows that
+come back are the selection's, and the headers' RSSI comes back beside them."""
 import os
 import sys
 
@@ -82,16 +86,21 @@ def _compare(k, got, listen, ref, sel, play):
         assert np.array_equal(play, ref["play"]), k
 
 
-@pytest.mark.parametrize("mode", ["plain", "lazy_out", "post"])
+@pytest.mark.parametrize("mode", ["plain", "lazy_out", "post", "all"])
 @pytest.mark.parametrize("plan", list(PLANS))
 @pytest.mark.parametrize("hop", [1024, 512])
 def test_a_listen_feed_is_the_synchronous_path_bit_for_bit(S, case_batches, hop, plan, mode):
     from supersdr_amd._lib import PlayChan
-    sel = F.SEL if mode == "lazy_out" else None
-    play = [PlayChan(100.0 - 7 * c, 0.25 * (c % 5) - 0.5) for c in range(F.N_CH)] if mode == "post" else None
+    wire = mode == "all"
+    sel = F.SEL if mode in ("lazy_out", "all") else None
+    play = [PlayChan(100.0 - 7 * c, 0.25 * (c % 5) - 0.5) for c in range(F.N_CH)] if mode in ("post", "all") else None
+    if mode == "all":
+        play = [play[c] for c in sel]                                 # the post step works on the selection: on both ctxs
     # B first: the synchronous ctx, the changes in front of batch CHANGE_AT
     refs = []
     with _engine(S, hop, plan) as b:
+        if mode == "all":
+            b.set_post_channels(sel)
         for k, batch in enumerate(case_batches):
             if k == F.CHANGE_AT:
                 F.apply_late(b)
@@ -111,16 +120,20 @@ def test_a_listen_feed_is_the_synchronous_path_bit_for_bit(S, case_batches, hop,
     with _engine(S, hop, plan) as a:
         if sel is not None:
             a.set_post_channels(sel)
-        a.feed_open(F.N_FRAMES, depth=F.DEPTH, lazy_out=sel is not None, post=play is not None, listen=True)
+        a.feed_open(F.N_FRAMES, depth=F.DEPTH, wire=wire, lazy_out=sel is not None, post=play is not None, listen=True)
         if play is not None:
             a.feed_post(play=play)
-        pinned = [a.host_alloc(case_batches[0].shape, np.int16) for _ in range(F.DEPTH)]
+        pinned = [a.host_alloc(case_batches[0].shape, np.int16) for _ in range(F.DEPTH)] if not wire else None
         done = 0
 
         def collect():
             nonlocal done
-            got = a.feed_collect()
-            got = tuple(np.array(g) for g in got) + (np.array(a.feed_flags),)
+            got = [np.array(g) for g in a.feed_collect()]
+            if wire:
+                # the headers' RSSI of the selection's rows: 0.1 * word - 127 in fp32 (rounding of 0.1f, of the product and of the
+                # difference near 77: under 2e-5 together; the bound of test_pipelined_feed_wire_mode)
+                assert np.abs(got.pop() - F.wire_bodies(case_batches[done])[1][sel]).max() < 1e-4, done
+            got = tuple(got) + (np.array(a.feed_flags),)
             pl = a.feed_collect_post()[2] if play is not None else None
             _compare(done, got, a.feed_collect_listen(), refs[done], sel, pl)
             done += 1
@@ -130,8 +143,12 @@ def test_a_listen_feed_is_the_synchronous_path_bit_for_bit(S, case_batches, hop,
                 collect()
             if k == F.CHANGE_AT:                                      # batches CHANGE_AT - 2 and CHANGE_AT - 1 are in flight
                 F.apply_late(a)
-            pinned[k % F.DEPTH][...] = batch
-            a.feed_submit_from(pinned[k % F.DEPTH])
+            if wire:
+                a.feed_slot()[...] = F.wire_bodies(batch, k * F.N_FRAMES)[0]
+                a.feed_submit()
+            else:
+                pinned[k % F.DEPTH][...] = batch
+                a.feed_submit_from(pinned[k % F.DEPTH])
         while done < F.N_BATCHES:
             collect()
         a.feed_close()

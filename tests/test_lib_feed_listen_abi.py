@@ -186,3 +186,151 @@ def test_after_the_close_a_synchronous_run_continues_the_same_streams(S):
             assert a._lines == b._lines and np.array_equal(a.fetch_wf(a._lines), b.fetch_wf(b._lines))
             for x, y in zip(_listener_results(a), _listener_results(b)):
                 assert x.shape == y.shape and np.array_equal(x, y), k
+
+
+N_CH = 4
+VIEW = (1, 2, 100.0)
+
+
+def _listeners(eng, on=True):
+    """a squelch, SND and W/F compression and one view, or none of them"""
+    eng.set_squelch(0, [(0, 0, 10 if on else 0, 1 if on else 0)])
+    eng.set_compression([0, 2], snd=on)
+    eng.set_compression(3, wf=on)
+    eng.set_wf_views([VIEW] if on else [])
+
+
+def _engine(S, hop=1024):
+    eng = S.SsdrEngine(N_CH)
+    eng.set_params(0, [S.default_params("am")] * N_CH)
+    eng.set_hop(hop)
+    _listeners(eng)
+    return eng
+
+
+def _getter_codes(eng):
+    """the return codes of the five ctx-owned getters"""
+    from supersdr_amd import _lib as L
+    ctx, lib, n = eng._ctx, L.lib, C.c_uint32()
+    buf = np.zeros(1 << 16, np.uint8)
+    return [lib.ssdr_audio_squelch(ctx, buf.ctypes.data, 0), lib.ssdr_audio_adpcm(ctx, buf.ctypes.data, 0),
+            lib.ssdr_wf_adpcm(ctx, None, C.byref(n), 0), lib.ssdr_wf_view_lines(ctx, None, None, C.byref(n), 0),
+            lib.ssdr_read_wf_view(ctx, 0, None, C.byref(n))]
+
+
+@pytest.mark.gpu
+def test_results_from_before_the_feed_do_not_resurface(S):
+    from supersdr_amd import _lib as L
+    iq = np.random.default_rng(11).integers(-3000, 3000, (3, N_CH, 2 * 512, 2)).astype(np.int16)
+    with _engine(S) as a, _engine(S) as b:
+        for eng in (a, b):
+            eng.push_iq(iq[0])
+            eng.run_chain()
+        assert _getter_codes(a) == [L.OK] * 5
+        a.feed_open(2, depth=2, listen=True)
+        a.feed_submit_from(iq[1])
+        a.feed_collect()
+        a.feed_close()
+        assert _getter_codes(a) == [L.ESTATE] * 5                   # not the results of batch 0 again
+        b.push_iq(iq[1])                                            # B: the same batch, synchronously
+        b.run_chain()
+        for eng in (a, b):
+            eng.push_iq(iq[2])
+            eng._lines, _ = eng.run_chain()
+        assert _getter_codes(a) == [L.OK] * 5
+        assert a._lines == b._lines and np.array_equal(a.fetch_wf(a._lines), b.fetch_wf(b._lines))
+        for x, y in zip(_listener_results(a), _listener_results(b)):
+            assert x.shape == y.shape and np.array_equal(x, y)
+
+
+@pytest.mark.gpu
+def test_every_pointer_of_a_slot_is_a_part_of_its_own(S):
+    """all four flags: every part of a slot's two blocks exists.  Every pointer the entry points hand out is a multiple of 256, and
+    the byte ranges the returned counts imply are disjoint, within a slot and between the two slots (host arithmetic only)"""
+    iq = np.random.default_rng(12).integers(-3000, 3000, (2, N_CH, 2 * 512, 2)).astype(np.int16)
+    with _engine(S, hop=512) as eng:                                # (hop 512: the view has a line in either batch)
+        eng.set_post_channels([0, 2])
+        eng.set_recording(True)                                     # (the mono block too)
+        eng.feed_open(2, depth=2, wire=True, post=True, lazy_out=True, listen=True)
+        ranges = []                                                 # (slot, name, address, bytes)
+
+        def add(slot, name, x):
+            if isinstance(x, np.ndarray):
+                assert x.nbytes, name
+                ranges.append((slot, name, x.ctypes.data, x.nbytes))
+            else:
+                ranges.append((slot, name, C.addressof(x), C.sizeof(x)))
+
+        for k in range(2):
+            slot = eng.feed_slot()
+            add(k, "in", slot)
+            slot[...] = F.wire_bodies(iq[k], 2 * k)[0]
+            eng.feed_submit()
+        for k in range(2):
+            for name, x in zip(("wf", "pcm", "rssi", "wire_rssi"), eng.feed_collect()):
+                assert x.shape[0 if name != "wf" else 1] == 2, name
+                add(k, name, x)
+            add(k, "flags", eng.feed_flags)
+            for name, x in zip(("color", "dbchan", "play", "mono"), eng.feed_collect_post()):
+                add(k, name, x)
+            got = eng.feed_collect_listen()
+            assert [len(v) for v in got["view_lines"]] == [1]
+            for name in ("sq_closed", "snd_adpcm", "wf_adpcm"):
+                add(k, name, got[name])
+            add(k, "view_lines", got["view_lines"][0])
+            dev = eng.feed_device()
+            assert dev["rows"] == 2 and dev["lines"] == 2
+            for name, n in (("wf", 2 * N_CH * 1024 * 2), ("pcm", N_CH * 2 * 512 * 2), ("rssi", N_CH * 2 * 4), ("flags", N_CH * 2)):
+                ranges.append((k, "d_" + name, dev[name], n))
+        eng.feed_close()
+    assert len(ranges) == 2 * 18
+    for slot, name, addr, n in ranges:
+        assert addr and addr % 256 == 0, (slot, name)
+    ranges.sort(key=lambda r: r[2])
+    for lo, hi in zip(ranges, ranges[1:]):
+        assert lo[2] + lo[3] <= hi[2], (lo[:2], hi[:2])
+
+
+@pytest.mark.gpu
+def test_open_close_and_reopen_with_other_flags_and_sizes(S):
+    """flags 15 at 2 frames, flags 0 at 4 frames, flags 8 at 2 frames, a batch through each: the third feed is a fresh ctx's first
+    (which got the first two batches synchronously, so that the streams it carries are the same)"""
+    from supersdr_amd import _lib as L
+    iq = np.random.default_rng(13).integers(-3000, 3000, (N_CH, 8 * 512, 2)).astype(np.int16)
+    b0, b1, b2 = (np.ascontiguousarray(x) for x in (iq[:, :1024], iq[:, 1024:3072], iq[:, 3072:]))
+
+    def third(eng):
+        eng.feed_open(2, depth=2, listen=True)
+        eng.feed_submit_from(b2)
+        got = [np.array(g) for g in eng.feed_collect()] + [np.array(eng.feed_flags)]
+        listen = eng.feed_collect_listen()
+        got += [np.array(listen[k]) for k in ("sq_channels", "sq_closed", "snd_channels", "snd_adpcm", "wf_channels", "wf_adpcm")]
+        got += [np.array(v) for v in listen["view_lines"]]
+        eng.feed_close()
+        return got
+
+    with _engine(S, hop=512) as a, _engine(S, hop=512) as b:       # (hop 512: the restarted view has a line in the third feed's batch)
+        a.feed_open(2, depth=2, wire=True, post=True, lazy_out=True, listen=True)
+        a.feed_slot()[...] = F.wire_bodies(b0)[0]
+        a.feed_submit()
+        a.feed_collect()
+        a.feed_close()
+        _listeners(a, on=False)                                     # (a plain feed opens with no listener setting)
+        a.feed_open(4, depth=2)
+        a.feed_submit_from(b1)
+        a.feed_collect()
+        a.feed_close()
+        _listeners(a)
+        got_a = third(a)
+        assert L.lib.ssdr_feed_collect_listen(a._ctx, C.byref(L.FeedListen())) == L.ESTATE
+        b.push_iq(b0)
+        b.run_chain()
+        _listeners(b, on=False)
+        b.push_iq(b1)
+        b.run_chain()
+        _listeners(b)
+        got_b = third(b)
+    assert len(got_a) == len(got_b) == 11
+    assert [len(got_a[i]) for i in (4, 6, 8)] == [1, 2, 1] and got_a[10].shape == (1, 1024)     # every listener part is there
+    for x, y in zip(got_a, got_b):
+        assert x.shape == y.shape and np.array_equal(x, y)
