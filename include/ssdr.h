@@ -501,6 +501,61 @@ int ssdr_read_wf_view(ssdr_ctx *ctx, uint32_t view_index, int16_t *iq_out, uint3
  * (one HIP-event pair around the stage's kernels; runs made with profiling off count, and add no time). */
 int ssdr_wf_view_stats(ssdr_ctx *ctx, float *total_ms, uint32_t *launches, int reset);
 
+/* -- sub-receivers: further demodulators on a channel's IQ (the reference's SUB RX, key Y: utils_supersdr.py:90; supersdr.py:624-629
+ *    builds a second kiwi_sound with subrx_=True, its own mode, passband and frequency, next to the main receiver)
+ *
+ * A channel has one audio chain (ssdr_set_params).  A SUB-RECEIVER is a further chain -- NCO, channel filter, demodulator, AGC, int16
+ * PCM, RSSI, ADC-overflow flag -- on the raw IQ of one channel, with parameters and carried state of its own, for the few channels
+ * on which somebody listens to a second signal; the list can be replaced while the streams run.  Sub-receiver j on channel c with
+ * parameters P produces, bit for bit, the PCM, RSSI, flags and carried state (ssdr_chan_state, raw history) of a channel of a ctx
+ * that is fed channel c's IQ and holds P: no new arithmetic (oracle/ssdr_oracle.py:audio_chain, oracle/ssdr_twin.c, the shipped
+ * audio kernels).  It sees the input as it came: the channel's noise blanker does not act on it and it has none of its own; nor
+ * squelch, de-emphasis, ADPCM or SSDR_MODE_IQ.
+ *   every ssdr_run_audio and every path of ssdr_run_chain (*fused = 0, 1, 2) advances every sub-receiver by the batch;
+ *   which kernel the channels get (chain_plan) does not depend on the list, and their results, state and timing are untouched.
+ * Kernels: ssdr_audio.hip, ssdr_audio_sub_kernel (12 kHz: one launch, a wave per sub-receiver, all three frame paths) and
+ * ssdr_audio_sub_dec_kernel<D> -- the channels' own chain functions reading the parent's input row -- on the audio stage's stream
+ * behind the channels' kernels and in front of squelch / de-emphasis / SND encoder; every call that waits for the audio stage waits
+ * for them.  With no sub-receiver set nothing is launched, and before the first one nothing is allocated.  No SSDR_K_* slot:
+ * ssdr_subrx_stats is the stage's own.  Cost beside a 65536-channel general-path audio stage of 1.32 ms at 16 frames per call: 0.05 ms
+ * for 1 to 256 sub-receivers -- one wave's latency over its frames, not arithmetic (profiles/subrx_probe.txt).
+ * While any sub-receiver is set ssdr_feed_open (with or without SSDR_FEED_LISTEN) and ssdr_checkpoint_save / _load return
+ * SSDR_ESTATE; while a pipelined feed is open ssdr_set_subrx with count > 0 returns SSDR_ESTATE.  ssdr_reset_state restarts the
+ * sub-receivers of the channels it names; ssdr_set_kiwi_rate and ssdr_set_decimation recompile and restart all of them, and return
+ * SSDR_EINVAL with nothing changed if a sub-receiver's parameters do not compile at the new setting; ssdr_set_params on the parent
+ * channel does not touch them. */
+#define SSDR_SUBRX_MAX 256
+typedef struct ssdr_subrx {
+    uint32_t id;            /* the caller's name for it: what makes a sub-receiver "the same one" across lists */
+    uint32_t channel;       /* whose IQ it listens to */
+    ssdr_chan_params params;
+} ssdr_subrx;               /* 96 B */
+/* Replaces the whole list: id ascending and unique, count <= SSDR_SUBRX_MAX; (NULL, 0) removes every sub-receiver.  SSDR_EINVAL,
+ * and then nothing changes: a list out of order, a channel outside the ctx, parameters ssdr_set_params would refuse at the current
+ * rate and decimation, SSDR_MODE_IQ (a sub-receiver has no I,Q output), at D > 1 parameters that compile to a shift path.  Result
+ * rows are in list order.  A sub-receiver whose (id, channel) is in the old list keeps its stream -- NCO phases, raw history, DC
+ * estimate, AGC envelope and hang memory, discriminator memory, play_buffer history -- and takes new parameters the way
+ * ssdr_set_params does: state kept, the envelope to the new knee only while that sub-receiver has not run yet.  A new one (a new id,
+ * or an old id on another channel) starts in the state ssdr_reset_state leaves a channel holding those parameters.  Nobody's stream
+ * restarts or waits for somebody else's change beyond the upload of the list. */
+int ssdr_set_subrx(ssdr_ctx *ctx, const ssdr_subrx *subs, uint32_t count);
+int ssdr_get_subrx(ssdr_ctx *ctx, ssdr_subrx *subs /* may be NULL */, uint32_t *count);
+/* The sub-receivers' results of the last audio run, rows in list order (each pointer may be NULL): pcm int16 [count][n_frames * 512],
+ * rssi float [count][n_frames], flags uint8 [count][n_frames].  SSDR_ESTATE if no sub-receiver is set or there has been no audio run
+ * with the list as it is (a parameter change of a kept sub-receiver does not invalidate a run). */
+int ssdr_subrx_audio(ssdr_ctx *ctx, int16_t *pcm, float *rssi, uint8_t *flags, int out_is_device);
+/* Carried state and compiled constants of rows [first_row, first_row + count) of the list, as ssdr_get_state / ssdr_get_consts. */
+int ssdr_get_subrx_state(ssdr_ctx *ctx, uint32_t first_row, uint32_t count, ssdr_chan_state *state, int16_t *hist /* may be NULL */);
+int ssdr_get_subrx_consts(ssdr_ctx *ctx, uint32_t first_row, uint32_t count, ssdr_chan_consts *consts, float *taps /* may be NULL */);
+/* play_buffer of the sub-receivers' PCM rows of the last audio run, as if they were the channels of a small ctx: the shipped kernels
+ * of ssdr_run_playbuffer at either rate, on a history array of the sub-receivers' own (a kept sub-receiver keeps its history across a
+ * list change).  chans [count]; out int16 [count][n_frames * ssdr_playbuffer_frame_len][2].  No recording block.  SSDR_ESTATE like
+ * ssdr_subrx_audio. */
+int ssdr_run_subrx_playbuffer(ssdr_ctx *ctx, const ssdr_play_chan *chans, int16_t *out, int out_is_device);
+/* The sub-receiver stage's runs since the last reset (one per batch while a sub-receiver is set), and with ssdr_set_profiling on
+ * their summed time (one HIP-event pair around the stage's kernel; runs made with profiling off count, and add no time). */
+int ssdr_subrx_stats(ssdr_ctx *ctx, float *total_ms, uint32_t *launches, int reset);
+
 /* -- pipelined host feed: the path a live ingest takes (KiwiSDRStream._process_iq_samples -> batches, kiwi/client.py:493)
  *
  * ssdr_push_iq + ssdr_run_* from pageable host memory serialise copy-in, kernels and copy-out.  The feed keeps `depth`

@@ -85,6 +85,15 @@ class WfView(C.Structure):
 
 
 assert C.sizeof(WfView) == 16
+SUBRX_MAX = 256             # SSDR_SUBRX_MAX
+
+
+class SubRx(C.Structure):
+    """ssdr_subrx: one sub-receiver -- the caller's id for it, the channel whose IQ it listens to, its own parameters"""
+    _fields_ = [("id", C.c_uint32), ("channel", C.c_uint32), ("params", ChanParams)]
+
+
+assert C.sizeof(SubRx) == 96
 
 
 class FeedListen(C.Structure):
@@ -169,6 +178,13 @@ _SIGS = {
     "ssdr_wf_view_lines": (C.c_int, [_P, _P, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.c_int]),
     "ssdr_read_wf_view": (C.c_int, [_P, C.c_uint32, _P, C.POINTER(C.c_uint32)]),
     "ssdr_wf_view_stats": (C.c_int, [_P, C.POINTER(C.c_float), C.POINTER(C.c_uint32), C.c_int]),
+    "ssdr_set_subrx": (C.c_int, [_P, C.POINTER(SubRx), C.c_uint32]),
+    "ssdr_get_subrx": (C.c_int, [_P, C.POINTER(SubRx), C.POINTER(C.c_uint32)]),
+    "ssdr_subrx_audio": (C.c_int, [_P, _P, _P, _P, C.c_int]),
+    "ssdr_get_subrx_state": (C.c_int, [_P, C.c_uint32, C.c_uint32, _P, _P]),
+    "ssdr_get_subrx_consts": (C.c_int, [_P, C.c_uint32, C.c_uint32, _P, _P]),
+    "ssdr_run_subrx_playbuffer": (C.c_int, [_P, C.POINTER(PlayChan), _P, C.c_int]),
+    "ssdr_subrx_stats": (C.c_int, [_P, C.POINTER(C.c_float), C.POINTER(C.c_uint32), C.c_int]),
     "ssdr_feed_open": (C.c_int, [_P, C.c_uint32, C.c_uint32, C.c_uint32]),
     "ssdr_feed_slot": (C.c_int, [_P, C.POINTER(_P)]),
     "ssdr_feed_submit": (C.c_int, [_P]),
@@ -214,7 +230,8 @@ _SIGS = {
     "ssdr_version": (C.c_char_p, []),
 }
 EXPORTS = tuple(_SIGS)
-_NEWER_THAN_AB_LIBS = ("ssdr_feed_collect_listen",)      # entry points a library named by SSDR_LIB_PATH (A/B builds only) may predate
+_NEWER_THAN_AB_LIBS = ("ssdr_feed_collect_listen", "ssdr_set_subrx", "ssdr_get_subrx", "ssdr_subrx_audio", "ssdr_get_subrx_state",
+                       "ssdr_get_subrx_consts", "ssdr_run_subrx_playbuffer", "ssdr_subrx_stats")      # entry points a library named by SSDR_LIB_PATH (A/B builds only) may predate
 
 
 def _load():

@@ -67,6 +67,11 @@ struct Batch {
     uint8_t *d_wf_adpcm = nullptr; size_t wf_adpcm_bytes = 0; bool wf_adpcm_valid = false; uint32_t wf_adpcm_lines = 0;        // [lines][comp_wf_n][517] W/F payloads
     int16_t *d_wv_lines = nullptr; size_t wv_lines_rows = 0;      // [total][1024] the views' lines, compact (their validity: ssdr_ctx::wv_run_valid)
     std::vector<uint32_t> wv_run_lines; uint32_t wv_run_total = 0;        // [views] lines of each view; their total
+    // the sub-receivers' results, rows in list order (their validity: ssdr_ctx::sub_run_valid): buffers, capacities in rows * frames
+    int16_t *d_sub_pcm = nullptr; size_t sub_pcm_cap = 0;         // [rows][frames * 512]
+    float *d_sub_rssi = nullptr; size_t sub_rssi_cap = 0;         // [rows][frames]
+    uint8_t *d_sub_flags = nullptr; size_t sub_flags_cap = 0;     // [rows][frames]
+    uint32_t sub_run_rows = 0, sub_run_frames = 0;                // extent of the last run
 };
 // What ssdr_run_chain decides for a batch (chain_plan), handed to the two stages
 struct ChainPlan {
@@ -284,6 +289,24 @@ struct ssdr_ctx {
     size_t wv_wf_rows = 0;
     float wv_ms = 0.0f;                                 // the stage's own timing: ssdr_wf_view_stats
     uint32_t wv_launches = 0;
+    // sub-receivers (ssdr_set_subrx): device memory at the first one; with none set nothing is launched
+    std::vector<ssdr_subrx> h_sub;                      // the list as set, ids ascending
+    std::vector<ssdr_chan_consts> h_sub_consts;         // [rows] mirror of d_sub_consts
+    std::vector<uint8_t> h_sub_started;                 // [rows] the sub-receiver has run since it was created or restarted
+    bool sub_run_valid = false;                         // the last audio run was the ctx's own batch's, with the list as it is
+    int sub_set = 0;                                    // which of the two sets of state arrays is the current one (as wv_set)
+    ssdr_chan_state *d_sub_state[2] = {nullptr, nullptr};       // [SSDR_SUBRX_MAX]
+    uint32_t *d_sub_hist[2] = {nullptr, nullptr};       // [SSDR_SUBRX_MAX][SSDR_HIST]
+    double *d_sub_phist[2] = {nullptr, nullptr};        // [SSDR_SUBRX_MAX][8] play_buffer history (ssdr_run_subrx_playbuffer)
+    double *d_sub_phist_alt = nullptr;                  // the kernel reads the current set's and writes this one; swapped after every launch
+    ssdr_chan_consts *d_sub_consts = nullptr;           // [SSDR_SUBRX_MAX] compiled from the list's parameters
+    float *d_sub_taps = nullptr;                        // [SSDR_SUBRX_MAX][SSDR_NTAP_MAX]
+    uint32_t *d_sub_parent = nullptr;                   // [SSDR_SUBRX_MAX] the row of the input each one reads
+    ssdr_play_chan *d_sub_play = nullptr;               // [SSDR_SUBRX_MAX]
+    int16_t *d_sub_play_out = nullptr;
+    size_t sub_play_cap = 0;                            // rows * frames d_sub_play_out holds
+    float sub_ms = 0.0f;                                // the stage's own timing: ssdr_subrx_stats
+    uint32_t sub_launches = 0;
 };
 // Every device buffer a ctx owns (a feed slot's block: ssdr_feed_close) -- what ssdr_destroy frees.  One line per section of the
 // struct above, in its order (the own batch's buffers where `own` stands): a new `d_` member joins its section's line HERE, and tests/test_gpu_parity.py's
@@ -309,6 +332,9 @@ static void free_owned(ssdr_ctx *c)
         c->d_de_state, c->d_de_list,                                                                                  // de-emphasis
         c->d_wv[0], c->d_wv[1], c->d_wv_hist[0], c->d_wv_hist[1], c->d_wv_carry[0], c->d_wv_carry[1], c->d_wv_tail[0], c->d_wv_tail[1],
         c->d_wv_taps, c->d_wv_consts, c->d_wv_acc, c->d_wv_stream, c->d_wv_wf,                                        // waterfall views
+        c->own.d_sub_pcm, c->own.d_sub_rssi, c->own.d_sub_flags,                                                      // sub-receivers: the own batch's results,
+        c->d_sub_state[0], c->d_sub_state[1], c->d_sub_hist[0], c->d_sub_hist[1], c->d_sub_phist[0], c->d_sub_phist[1], c->d_sub_phist_alt,
+        c->d_sub_consts, c->d_sub_taps, c->d_sub_parent, c->d_sub_play, c->d_sub_play_out,                            // ... state, constants, play_buffer
     };
     for (void *p : owned)
         if (p) (void)hipFree(p);
@@ -323,6 +349,7 @@ static int get_event(ssdr_ctx *c, hipEvent_t *e)
 // HIP events on the stream the kernel is launched on, bracketing exactly one launch.
 constexpr int kTimedDeemp = SSDR_K_COUNT;               // `which` of the de-emphasis kernel: timed beside the SSDR_K_* slots, not in them
 constexpr int kTimedWfView = SSDR_K_COUNT + 1;          // ... and of the waterfall views' stage
+constexpr int kTimedSubRx = SSDR_K_COUNT + 2;           // ... and of the sub-receivers'
 static int timed_begin(ssdr_ctx *c, hipStream_t s = nullptr)
 {
     if (!s) s = c->stream;
@@ -356,6 +383,7 @@ static int resolve_pending(ssdr_ctx *c)
         HIP_TRY(hipEventElapsedTime(&ms, p.e0, p.e1));
         if (p.which == kTimedDeemp) c->de_ms += ms;          // (its launches are counted where they are made)
         else if (p.which == kTimedWfView) c->wv_ms += ms;
+        else if (p.which == kTimedSubRx) c->sub_ms += ms;
         else if (p.which >= 0) { c->k_ms[p.which] += ms; c->k_n[p.which] += 1; c->last_ms = ms; }
         c->free_events.push_back(p.e0);
         c->free_events.push_back(p.e1);
@@ -544,6 +572,10 @@ static int nb_upload(ssdr_ctx *c, uint32_t first, uint32_t count);
 static int squelch_upload(ssdr_ctx *c, uint32_t first, uint32_t count);
 static int deemp_reset(ssdr_ctx *c, uint32_t first, uint32_t count);
 static int wfview_restart(ssdr_ctx *c, uint32_t first, uint32_t count);
+static int subrx_restart(ssdr_ctx *c, uint32_t first, uint32_t count);
+static int subrx_compile(const ssdr_ctx *c, const ssdr_subrx *subs, uint32_t count, uint32_t decim, uint32_t rate,
+                         std::vector<ssdr_chan_consts> &k, std::vector<float> &taps);
+static int subrx_install(ssdr_ctx *c, const std::vector<ssdr_chan_consts> &k, const std::vector<float> &taps);
 
 int ssdr_reset_state(ssdr_ctx *c, uint32_t first, uint32_t count) SSDR_GUARD
 {
@@ -572,6 +604,7 @@ int ssdr_reset_state(ssdr_ctx *c, uint32_t first, uint32_t count) SSDR_GUARD
     SSDR_TRY(squelch_upload(c, first, count)); // and the squelch
     SSDR_TRY(deemp_reset(c, first, count));    // and the de-emphasis
     SSDR_TRY(wfview_restart(c, first, count)); // and the views of these channels
+    SSDR_TRY(subrx_restart(c, first, count));  // and their sub-receivers
     return zoom_restart(c, first, count, false);         // the zoomed streams of these channels start over as well
 } SSDR_UNGUARD
 
@@ -745,6 +778,9 @@ int ssdr_set_decimation(ssdr_ctx *c, uint32_t decim) SSDR_GUARD
     if (!c->feed.empty()) return SSDR_ESTATE;
     if (decim == c->decim) return SSDR_OK;
     HIP_TRY(hipSetDevice(c->device));
+    std::vector<ssdr_chan_consts> sub_k;                          // the sub-receivers at the new rate, before anything changes
+    std::vector<float> sub_taps;
+    SSDR_TRY(subrx_compile(c, c->h_sub.data(), (uint32_t)c->h_sub.size(), decim, c->kiwi_rate, sub_k, sub_taps));
     std::vector<ssdr_chan_params> all = c->h_params;              // recompile every channel for the new input rate
     const uint32_t keep = c->decim;
     c->decim = decim;
@@ -753,6 +789,7 @@ int ssdr_set_decimation(ssdr_ctx *c, uint32_t decim) SSDR_GUARD
         c->own.have_input = false;                                // a batch pushed at the old rate has the wrong extent
         rc = ssdr_reset_state(c, 0, c->n_ch);                     // phases and histories of the old rate mean nothing now
         if (rc == SSDR_OK) rc = zoom_restart(c, 0, c->n_ch);
+        if (rc == SSDR_OK) rc = subrx_install(c, sub_k, sub_taps);
     }
     if (rc != SSDR_OK) {                                          // all or nothing: back to the old rate, streams restarted
         c->decim = keep;
@@ -1527,6 +1564,125 @@ int ssdr_run_wf(ssdr_ctx *c, int16_t *wf_sum_out, uint32_t *lines_ready, int out
     return copy_out(c, wf_sum_out, b.d_wf_out, (size_t)b.wf_lines_ready * c->n_ch * SSDR_NFFT * 2, out_is_device, kSyncHost);
 } SSDR_UNGUARD
 
+// ---- sub-receivers: further audio chains on a channel's IQ (ssdr_set_subrx) --------------------------------------------------------
+// the list's parameters compiled at a decimation and rate: SSDR_EINVAL for what ssdr_set_subrx refuses, and nothing is touched
+static int subrx_compile(const ssdr_ctx *c, const ssdr_subrx *subs, uint32_t count, uint32_t decim, uint32_t rate,
+                         std::vector<ssdr_chan_consts> &k, std::vector<float> &taps)
+{
+    k.resize(count);
+    taps.assign((size_t)count * SSDR_NTAP_MAX, 0.0f);
+    for (uint32_t j = 0; j < count; j++) {
+        if (subs[j].channel >= c->n_ch || (j && subs[j].id <= subs[j - 1].id)) return SSDR_EINVAL;
+        if (subs[j].params.mode == SSDR_MODE_IQ) return SSDR_EINVAL;            // a sub-receiver has no I,Q output
+        SSDR_TRY(ssdr_compile_params_host(&subs[j].params, &k[j], taps.data() + (size_t)j * SSDR_NTAP_MAX, decim, rate));
+        if (decim > 1 && ssdr_audio_path(k[j]) != SSDR_PATH_GENERAL) return SSDR_EINVAL;    // the decimating kernel is the general path (audio_stage)
+    }
+    return SSDR_OK;
+}
+// the state arrays (two sets: a new list is built in the other one, so that a sub-receiver that stays keeps its stream), constants, parents
+static int subrx_alloc(ssdr_ctx *c)
+{
+    for (int i = 0; i < 2; i++) {
+        if (!c->d_sub_state[i]) HIP_TRY(hipMalloc(&c->d_sub_state[i], SSDR_SUBRX_MAX * sizeof(ssdr_chan_state)));
+        if (!c->d_sub_hist[i]) HIP_TRY(hipMalloc(&c->d_sub_hist[i], (size_t)SSDR_SUBRX_MAX * SSDR_HIST * 4));
+        if (!c->d_sub_phist[i]) HIP_TRY(hipMalloc(&c->d_sub_phist[i], (size_t)SSDR_SUBRX_MAX * 8 * sizeof(double)));
+    }
+    if (!c->d_sub_phist_alt) HIP_TRY(hipMalloc(&c->d_sub_phist_alt, (size_t)SSDR_SUBRX_MAX * 8 * sizeof(double)));
+    if (!c->d_sub_consts) HIP_TRY(hipMalloc(&c->d_sub_consts, SSDR_SUBRX_MAX * sizeof(ssdr_chan_consts)));
+    if (!c->d_sub_taps) HIP_TRY(hipMalloc(&c->d_sub_taps, (size_t)SSDR_SUBRX_MAX * SSDR_NTAP_MAX * sizeof(float)));
+    if (!c->d_sub_parent) HIP_TRY(hipMalloc(&c->d_sub_parent, SSDR_SUBRX_MAX * sizeof(uint32_t)));
+    if (!c->d_sub_play) HIP_TRY(hipMalloc(&c->d_sub_play, SSDR_SUBRX_MAX * sizeof(ssdr_play_chan)));
+    return SSDR_OK;
+}
+static ssdr_chan_state subrx_fresh(const ssdr_chan_consts &k)
+{
+    ssdr_chan_state st;
+    memset(&st, 0, sizeof st);
+    st.agc_d = k.agc_knee;                   // as ssdr_reset_state: the envelope starts at the knee
+    for (int j = 0; j < 8; j++) st.agc_m[j] = -1000.0f;
+    return st;
+}
+// row j of set `set` as ssdr_reset_state leaves a channel (queued on the main stream; the caller waits: *fresh is host memory)
+static int subrx_silence(ssdr_ctx *c, int set, uint32_t j, const ssdr_chan_state *fresh)
+{
+    HIP_TRY(hipMemcpyAsync(c->d_sub_state[set] + j, fresh, sizeof *fresh, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemsetAsync(c->d_sub_hist[set] + (size_t)j * SSDR_HIST, 0, SSDR_HIST * 4, c->stream));
+    HIP_TRY(hipMemsetAsync(c->d_sub_phist[set] + (size_t)j * 8, 0, 8 * sizeof(double), c->stream));
+    return SSDR_OK;
+}
+// the sub-receivers of channels [first, first + count) start over
+static int subrx_restart(ssdr_ctx *c, uint32_t first, uint32_t count)
+{
+    if (c->h_sub.empty() || !count) return SSDR_OK;
+    SSDR_TRY(join_audio(c));
+    std::vector<ssdr_chan_state> fresh(c->h_sub.size());
+    bool any = false;
+    for (size_t j = 0; j < c->h_sub.size(); j++) {
+        const uint32_t ch = c->h_sub[j].channel;
+        if (ch < first || ch - first >= count) continue;
+        fresh[j] = subrx_fresh(c->h_sub_consts[j]);
+        SSDR_TRY(subrx_silence(c, c->sub_set, (uint32_t)j, &fresh[j]));
+        c->h_sub_started[j] = 0;
+        any = true;
+    }
+    if (any) HIP_TRY(hipStreamSynchronize(c->stream));
+    return SSDR_OK;
+}
+// constants and taps of the whole list to the device, behind what is queued; there when the call returns
+static int subrx_upload_consts(ssdr_ctx *c, const std::vector<ssdr_chan_consts> &k, const std::vector<float> &taps)
+{
+    if (k.empty()) return SSDR_OK;
+    SSDR_TRY(join_audio(c));
+    HIP_TRY(hipMemcpyAsync(c->d_sub_consts, k.data(), k.size() * sizeof(ssdr_chan_consts), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(c->d_sub_taps, taps.data(), taps.size() * sizeof(float), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return SSDR_OK;
+}
+// the list recompiled for a new rate or decimation (subrx_compile): every sub-receiver takes its constants and starts over
+static int subrx_install(ssdr_ctx *c, const std::vector<ssdr_chan_consts> &k, const std::vector<float> &taps)
+{
+    if (c->h_sub.empty()) return SSDR_OK;
+    SSDR_TRY(subrx_upload_consts(c, k, taps));
+    c->h_sub_consts = k;
+    c->sub_run_valid = false;
+    return subrx_restart(c, 0, c->n_ch);
+}
+// room for the results of the run, before anything of it is launched
+static int subrx_prepare(ssdr_ctx *c, Batch &b)
+{
+    const size_t n = c->h_sub.size();
+    if (!n) return SSDR_OK;
+    c->sub_run_valid = false;
+    const size_t need = n * b.in_frames;
+    if (b.sub_pcm_cap < need || b.sub_rssi_cap < need || b.sub_flags_cap < need) SSDR_TRY(drain_audio(c));
+    SSDR_TRY(grow(c, b, b.d_sub_pcm, b.sub_pcm_cap, need, SSDR_FRAME * sizeof(int16_t)));
+    SSDR_TRY(grow(c, b, b.d_sub_rssi, b.sub_rssi_cap, need, sizeof(float)));
+    return grow(c, b, b.d_sub_flags, b.sub_flags_cap, need, 1);
+}
+// Every sub-receiver advanced by the batch, on the audio stage's stream `s` behind the channels' kernels: one launch.  Timed with its
+// own event pair; not an SSDR_K_* slot.  `au`: the audio stage's arguments (the input and its extent).
+static int subrx_launch(ssdr_ctx *c, Batch &b, const SsdrAudioArgs &au, hipStream_t s)
+{
+    const uint32_t n = (uint32_t)c->h_sub.size();
+    if (!n) return SSDR_OK;
+    SsdrSubArgs a;
+    a.au = au;
+    a.au.n_ch = n;
+    a.au.consts = c->d_sub_consts; a.au.taps = c->d_sub_taps;
+    a.au.state = c->d_sub_state[c->sub_set]; a.au.hist = c->d_sub_hist[c->sub_set];
+    a.au.pcm = b.d_sub_pcm; a.au.rssi = b.d_sub_rssi; a.au.flags = b.d_sub_flags;
+    a.au.iq_out = nullptr;
+    a.au.chan_list = nullptr; a.au.list_n = n;
+    a.parent = c->d_sub_parent;
+    SSDR_TRY(timed_launch(c, kTimedSubRx, s, [&]() -> int { HIP_TRY(ssdr_launch_audio_sub(a, c->decim, s)); return SSDR_OK; }));
+    c->sub_launches++;
+    std::fill(c->h_sub_started.begin(), c->h_sub_started.end(), (uint8_t)1);
+    b.sub_run_rows = n;
+    b.sub_run_frames = b.in_frames;
+    c->sub_run_valid = &b == &c->own;
+    return SSDR_OK;
+}
+
 // the stream the audio stage runs on under a plan; and, once all the call puts there is queued, the mark that later work on the
 // main stream (next input, playbuffer) follows
 static hipStream_t audio_stream(const ssdr_ctx *c, ChainPlan plan) { return plan.beside ? c->stream2 : c->stream; }
@@ -1550,6 +1706,7 @@ static int audio_stage(ssdr_ctx *c, Batch &b, ChainPlan plan, const SsdrWfArgs *
         SSDR_TRY(grow(c, c->d_nb_mask, c->nb_mask_bytes, nb_mask_need, 1));
     }
     SSDR_TRY(audio_tail_prepare(c, b));
+    SSDR_TRY(subrx_prepare(c, b));
     SsdrAudioArgs a;
     a.iq = b.d_iq;
     a.ch_stride = (uint64_t)in_len(c, b.in_frames);
@@ -1611,7 +1768,8 @@ static int audio_stage(ssdr_ctx *c, Batch &b, ChainPlan plan, const SsdrWfArgs *
         if (fa.wf.tail)          // hop 512: only now may the carried half-line (the kernel's line 0 read it) become this batch's last one
             HIP_TRY(hipMemcpy2DAsync(c->d_wf_tail, (SSDR_NFFT / 2) * 4, fa.wf.iq + (size_t)(fa.wf.n_lines - 1) * SSDR_FRAME,
                                      fa.wf.ch_stride * 4, (SSDR_NFFT / 2) * 4, c->n_ch, hipMemcpyDeviceToDevice, s));
-        SSDR_TRY(audio_tail_launch(c, b, s));      // behind the one-read kernel, and then the W/F encoder
+        SSDR_TRY(subrx_launch(c, b, a, s));        // behind the one-read kernel: the sub-receivers, the tail, and then the W/F encoder
+        SSDR_TRY(audio_tail_launch(c, b, s));
         return adpcm_wf_launch(c, b, s, fa.wf.n_avg);
     }
     // one kernel per non-empty path: the first on the stream itself, the others beside it on their own streams
@@ -1670,6 +1828,7 @@ static int audio_stage(ssdr_ctx *c, Batch &b, ChainPlan plan, const SsdrWfArgs *
             c->nb_mask_gen = c->nb_gen;
         }
     }
+    SSDR_TRY(subrx_launch(c, b, a, s));
     return audio_tail_launch(c, b, s);
 }
 
@@ -2057,6 +2216,7 @@ int ssdr_feed_open(ssdr_ctx *c, uint32_t n_frames, uint32_t depth, uint32_t flag
     if (!c->feed.empty() || c->concurrent || c->decim != 1 || c->zoom != 1) return SSDR_ESTATE;
     // no wire compression, squelch, de-emphasis or waterfall view in the slot pipeline, unless it was opened for them
     const bool listen = (flags & SSDR_FEED_LISTEN) != 0;
+    if (!c->h_sub.empty()) return SSDR_ESTATE;               // nor a sub-receiver, whatever it was opened for
     if (!listen && (c->comp_snd_n || c->comp_wf_n || c->sq_set_n || c->de_set_n || !c->h_wv.empty())) return SSDR_ESTATE;
     HIP_TRY(hipSetDevice(c->device));
     const bool post = (flags & SSDR_FEED_POST) != 0;
@@ -2428,6 +2588,7 @@ int ssdr_checkpoint_save(ssdr_ctx *c, void *blob) SSDR_GUARD
     if (c->sq_set_n) return SSDR_ESTATE;                     // nor the squelch's
     if (c->de_set_n) return SSDR_ESTATE;                     // nor the de-emphasis's
     if (!c->h_wv.empty()) return SSDR_ESTATE;                // nor the waterfall views' streams
+    if (!c->h_sub.empty()) return SSDR_ESTATE;               // nor the sub-receivers'
     SsdrCkptHeader h = {kCkptMagic, kCkptVersion, c->n_ch, c->n_avg, c->wf_phase, c->audio_started ? 1u : 0u, c->kiwi_rate,
                         c->d_play_hist ? 1u : 0u, c->synth_sample0, c->hop, c->decim};
     char *p = static_cast<char *>(blob);
@@ -2472,7 +2633,7 @@ int ssdr_checkpoint_load(ssdr_ctx *c, const void *blob, uint64_t bytes) SSDR_GUA
     std::vector<float> ktaps(n * SSDR_NTAP_MAX);
     for (size_t i = 0; i < n; i++)
         if (ssdr_compile_params_host(&prm[i], &kc[i], ktaps.data() + i * SSDR_NTAP_MAX, h.decim, h.kiwi_rate) != SSDR_OK) return SSDR_EINVAL;
-    if (!c->feed.empty() || c->zoom > 1 || c->nb_on || c->comp_snd_n || c->comp_wf_n || c->sq_set_n || c->de_set_n || !c->h_wv.empty()) return SSDR_ESTATE;
+    if (!c->feed.empty() || c->zoom > 1 || c->nb_on || c->comp_snd_n || c->comp_wf_n || c->sq_set_n || c->de_set_n || !c->h_wv.empty() || !c->h_sub.empty()) return SSDR_ESTATE;
     std::vector<double> play_hist;                          // play_buffer state that arrives before its buffers exist: applied at first use
     if (h.has_play && !c->d_play_hist) {
         const double *q = reinterpret_cast<const double *>(static_cast<const char *>(blob) + sizeof h + n * (sizeof(ssdr_chan_consts) +
@@ -2750,6 +2911,9 @@ int ssdr_set_kiwi_rate(ssdr_ctx *c, uint32_t kiwi_rate) SSDR_GUARD
     HIP_TRY(hipSetDevice(c->device));
     // the rate of the play-back stage AND of the IQ the channels receive: every channel's constants (NCO steps, filter,
     // AGC time constants, NBFM scale) are compiled for it, and streams of the old rate mean nothing at the new one
+    std::vector<ssdr_chan_consts> sub_k;                          // the sub-receivers at the new rate, before anything changes
+    std::vector<float> sub_taps;
+    SSDR_TRY(subrx_compile(c, c->h_sub.data(), (uint32_t)c->h_sub.size(), c->decim, kiwi_rate, sub_k, sub_taps));
     std::vector<ssdr_chan_params> all = c->h_params;
     const uint32_t keep = c->kiwi_rate;
     c->kiwi_rate = kiwi_rate;
@@ -2759,6 +2923,7 @@ int ssdr_set_kiwi_rate(ssdr_ctx *c, uint32_t kiwi_rate) SSDR_GUARD
         c->own.have_input = false;
         rc = ssdr_reset_state(c, 0, c->n_ch);
         if (rc == SSDR_OK) rc = zoom_restart(c, 0, c->n_ch);
+        if (rc == SSDR_OK) rc = subrx_install(c, sub_k, sub_taps);
     }
     if (rc != SSDR_OK) {                                          // all or nothing, as ssdr_set_decimation
         c->kiwi_rate = keep;
@@ -3246,6 +3411,138 @@ int ssdr_wf_view_stats(ssdr_ctx *c, float *total_ms, uint32_t *launches, int res
     if (total_ms) *total_ms = c->wv_ms;
     if (launches) *launches = c->wv_launches;
     if (reset) { c->wv_ms = 0.0f; c->wv_launches = 0; }
+    return SSDR_OK;
+} SSDR_UNGUARD
+
+int ssdr_set_subrx(ssdr_ctx *c, const ssdr_subrx *subs, uint32_t count) SSDR_GUARD
+{
+    if (!c || count > SSDR_SUBRX_MAX || (count && !subs)) return SSDR_EINVAL;
+    std::vector<ssdr_chan_consts> k;                        // all or nothing: every sub-receiver is checked before the list is touched
+    std::vector<float> taps;
+    SSDR_TRY(subrx_compile(c, subs, count, c->decim, c->kiwi_rate, k, taps));
+    if (count && !c->feed.empty()) return SSDR_ESTATE;
+    if (!count) {                                           // (the state arrays stay for the next list)
+        c->h_sub.clear();
+        c->h_sub_consts.clear();
+        c->h_sub_started.clear();
+        c->sub_run_valid = false;
+        return SSDR_OK;
+    }
+    HIP_TRY(hipSetDevice(c->device));
+    SSDR_TRY(subrx_alloc(c));
+    SSDR_TRY(join_audio(c));                                // what is queued beside the main stream reads the current set and the constants
+    // the new list is built in the other set of state arrays: a sub-receiver that stays is copied there with all it carries, device
+    // to device behind whatever run is queued; a new one starts as after ssdr_reset_state.  Nobody's stream waits for anybody else's.
+    const int from = c->sub_set, to = from ^ 1;
+    std::vector<ssdr_chan_state> fresh(count);
+    std::vector<uint8_t> started(count, 0);
+    std::vector<uint32_t> parent(count);
+    bool same_rows = c->h_sub.size() == count;
+    size_t i = 0;
+    for (uint32_t j = 0; j < count; j++) {
+        parent[j] = subs[j].channel;
+        while (i < c->h_sub.size() && c->h_sub[i].id < subs[j].id) i++;
+        const bool stays = i < c->h_sub.size() && c->h_sub[i].id == subs[j].id && c->h_sub[i].channel == subs[j].channel;
+        same_rows = same_rows && stays && i == j;
+        if (stays && c->h_sub_started[i]) {
+            const hipMemcpyKind d2d = hipMemcpyDeviceToDevice;
+            HIP_TRY(hipMemcpyAsync(c->d_sub_state[to] + j, c->d_sub_state[from] + i, sizeof(ssdr_chan_state), d2d, c->stream));
+            HIP_TRY(hipMemcpyAsync(c->d_sub_hist[to] + (size_t)j * SSDR_HIST, c->d_sub_hist[from] + i * SSDR_HIST, SSDR_HIST * 4, d2d, c->stream));
+            HIP_TRY(hipMemcpyAsync(c->d_sub_phist[to] + (size_t)j * 8, c->d_sub_phist[from] + i * 8, 8 * sizeof(double), d2d, c->stream));
+            started[j] = 1;
+        } else {                                            // new, or kept but not run yet: it starts at ITS knee (ssdr_set_params)
+            fresh[j] = subrx_fresh(k[j]);
+            SSDR_TRY(subrx_silence(c, to, j, &fresh[j]));
+        }
+    }
+    HIP_TRY(hipMemcpyAsync(c->d_sub_parent, parent.data(), count * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
+    SSDR_TRY(subrx_upload_consts(c, k, taps));              // (waits: `fresh` and `parent` are host memory)
+    c->h_sub.assign(subs, subs + count);
+    c->h_sub_consts = k;
+    c->h_sub_started = started;
+    c->sub_set = to;
+    if (!same_rows) c->sub_run_valid = false;               // (new parameters of the same rows leave the last run's results what they were)
+    return SSDR_OK;
+} SSDR_UNGUARD
+
+int ssdr_get_subrx(ssdr_ctx *c, ssdr_subrx *subs, uint32_t *count) SSDR_GUARD
+{
+    if (!c || !count) return SSDR_EINVAL;
+    *count = (uint32_t)c->h_sub.size();
+    if (subs) std::copy(c->h_sub.begin(), c->h_sub.end(), subs);
+    return SSDR_OK;
+} SSDR_UNGUARD
+
+int ssdr_subrx_audio(ssdr_ctx *c, int16_t *pcm, float *rssi, uint8_t *flags, int out_is_device) SSDR_GUARD
+{
+    if (!c) return SSDR_EINVAL;
+    if (c->h_sub.empty() || !c->sub_run_valid) return SSDR_ESTATE;
+    HIP_TRY(hipSetDevice(c->device));
+    SSDR_TRY(join_audio(c));
+    const Batch &b = c->own;
+    const size_t n = (size_t)b.sub_run_rows * b.sub_run_frames;
+    if (pcm) SSDR_TRY(copy_out(c, pcm, b.d_sub_pcm, n * SSDR_FRAME * sizeof(int16_t), out_is_device, kSyncLater));
+    if (rssi) SSDR_TRY(copy_out(c, rssi, b.d_sub_rssi, n * sizeof(float), out_is_device, kSyncLater));
+    if (flags) SSDR_TRY(copy_out(c, flags, b.d_sub_flags, n, out_is_device, kSyncLater));
+    if (!out_is_device) HIP_TRY(hipStreamSynchronize(c->stream));
+    return SSDR_OK;
+} SSDR_UNGUARD
+
+int ssdr_get_subrx_state(ssdr_ctx *c, uint32_t first_row, uint32_t count, ssdr_chan_state *state, int16_t *hist) SSDR_GUARD
+{
+    if (!c || (uint64_t)first_row + count > c->h_sub.size()) return SSDR_EINVAL;
+    if (!count) return SSDR_OK;
+    HIP_TRY(hipSetDevice(c->device));
+    SSDR_TRY(join_audio(c));
+    const int set = c->sub_set;
+    if (state) HIP_TRY(hipMemcpyAsync(state, c->d_sub_state[set] + first_row, count * sizeof(ssdr_chan_state), hipMemcpyDeviceToHost, c->stream));
+    if (hist) HIP_TRY(hipMemcpyAsync(hist, c->d_sub_hist[set] + (size_t)first_row * SSDR_HIST, (size_t)count * SSDR_HIST * 4, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return SSDR_OK;
+} SSDR_UNGUARD
+
+int ssdr_get_subrx_consts(ssdr_ctx *c, uint32_t first_row, uint32_t count, ssdr_chan_consts *consts, float *taps) SSDR_GUARD
+{
+    if (!c || (uint64_t)first_row + count > c->h_sub.size()) return SSDR_EINVAL;
+    if (!count) return SSDR_OK;
+    HIP_TRY(hipSetDevice(c->device));
+    SSDR_TRY(join_audio(c));
+    if (consts) HIP_TRY(hipMemcpyAsync(consts, c->d_sub_consts + first_row, count * sizeof(ssdr_chan_consts), hipMemcpyDeviceToHost, c->stream));
+    if (taps) HIP_TRY(hipMemcpyAsync(taps, c->d_sub_taps + (size_t)first_row * SSDR_NTAP_MAX, (size_t)count * SSDR_NTAP_MAX * 4, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return SSDR_OK;
+} SSDR_UNGUARD
+
+int ssdr_run_subrx_playbuffer(ssdr_ctx *c, const ssdr_play_chan *chans, int16_t *out, int out_is_device) SSDR_GUARD
+{
+    if (!c || !chans) return SSDR_EINVAL;
+    if (c->h_sub.empty() || !c->sub_run_valid) return SSDR_ESTATE;
+    HIP_TRY(hipSetDevice(c->device));
+    SSDR_TRY(join_audio(c));
+    const uint32_t n = c->own.sub_run_rows, nf = c->own.sub_run_frames;
+    const bool wide = c->kiwi_rate != SSDR_RATE;
+    const size_t per_frame = wide ? (size_t)SSDR_RS_OUT_PER_FRAME : 2048;
+    SSDR_TRY(ensure_play(c));                                 // (the tap tables are the ctx's)
+    SSDR_TRY(grow(c, c->d_sub_play_out, c->sub_play_cap, (size_t)n * nf, (size_t)2048 * 2 * sizeof(int16_t)));
+    HIP_TRY(hipMemcpyAsync(c->d_sub_play, chans, (size_t)n * sizeof(ssdr_play_chan), hipMemcpyHostToDevice, c->stream));
+    SsdrPlayArgs a;                                           // the sub-receivers as the channels of a small ctx
+    a.pcm = c->own.d_sub_pcm; a.n_ch = n; a.n_frames = nf; a.chans = c->d_sub_play; a.taps = c->d_play_taps; a.rs_taps = c->d_play_rs_taps;
+    a.hist = c->d_sub_phist[c->sub_set]; a.hist_out = c->d_sub_phist_alt; a.sel = nullptr; a.n_sel = n; a.out = c->d_sub_play_out; a.mono = nullptr;
+    HIP_TRY(wide ? ssdr_launch_play_rs(a, c->stream) : ssdr_launch_play(a, c->stream));
+    if (!wide) std::swap(c->d_sub_phist[c->sub_set], c->d_sub_phist_alt);          // (the 64/27 branch carries no history)
+    if (out) SSDR_TRY(copy_out(c, out, c->d_sub_play_out, (size_t)n * nf * per_frame * 2 * sizeof(int16_t), out_is_device, kSyncLater));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return SSDR_OK;
+} SSDR_UNGUARD
+
+int ssdr_subrx_stats(ssdr_ctx *c, float *total_ms, uint32_t *launches, int reset) SSDR_GUARD
+{
+    if (!c) return SSDR_EINVAL;
+    HIP_TRY(hipSetDevice(c->device));
+    SSDR_TRY(resolve_pending(c));
+    if (total_ms) *total_ms = c->sub_ms;
+    if (launches) *launches = c->sub_launches;
+    if (reset) { c->sub_ms = 0.0f; c->sub_launches = 0; }
     return SSDR_OK;
 } SSDR_UNGUARD
 

@@ -51,10 +51,11 @@ __host__ __device__ constexpr int dec_streams_per_phase(int D) { return dec_phas
 // registers, then those take the same two regions -- and every stream's history (its last HOCT_S octets) lives in a small area of
 // its own, copied in front of the stream when its phase begins and refreshed by the lanes that hold the frame's tail when they file
 // it.  Same sums in the same order: stream 0 first, taps ascending.
-// BLANK: the noise blanker on the lane's 8 D raw inputs right after the loads, as in channel_frames.
-template <int D, bool BLANK = false>
+// BLANK: the noise blanker on the lane's 8 D raw inputs right after the loads, as in channel_frames.  Row: as in channel_frames.
+template <int D, bool BLANK = false, typename Row = OwnRow>
 SSDR_DEV void channel_frames_dec(const SsdrAudioArgs &a, const uint32_t ch, const int l, const ssdr_chan_consts &kc,
-                                 float2 *s_z, float2 *s_h, float *s_taps, SsdrNbChan *nb = nullptr, uint8_t *nb_mask = nullptr)
+                                 float2 *s_z, float2 *s_h, float *s_taps, SsdrNbChan *nb = nullptr, uint8_t *nb_mask = nullptr,
+                                 const Row &in_row = Row())
 {
     constexpr int SLOTS = SSDR_NTAP_MAX / D;             // tap slots per stream
     constexpr int HOCT_S = SSDR_HIST / D / 8;            // history octets per stream
@@ -109,7 +110,7 @@ SSDR_DEV void channel_frames_dec(const SsdrAudioArgs &a, const uint32_t ch, cons
         }
     }
 
-    const uint32_t *src = a.iq + (uint64_t)ch * a.ch_stride + NB * l;
+    const uint32_t *src = in_row(a, ch) + NB * l;
     int16_t *dst = a.pcm + (uint64_t)ch * a.n_frames * SSDR_FRAME + 8 * l;
     float *rssi_row = a.rssi + (uint64_t)ch * a.n_frames;
     uint8_t *flag_row = a.flags + (uint64_t)ch * a.n_frames;
@@ -357,6 +358,40 @@ __global__ __launch_bounds__(SSDR_AUDIO_BLOCK) __attribute__((amdgpu_waves_per_e
                                       a.mask + (uint64_t)ch * a.au.n_frames * 64);
 }
 
+// Sub-receivers (ssdr_set_subrx): further audio chains on the raw IQ of a channel that has its own.  Wave r IS channel_frames /
+// channel_frames_dec on row r of the sub-receivers' own arrays (a.au: constants, taps, state, history, PCM, RSSI, flags); only the
+// input row is the parent's, parent[r] (validated on the host), read once per wave.  The list is short (SSDR_SUBRX_MAX waves at most:
+// occupancy decides nothing, launches decide everything), so at 12 kHz ONE kernel takes all three frame paths, switching on the
+// wave-uniform path of the row's constants: the general path's LDS, the largest path's registers.
+__global__ __launch_bounds__(SSDR_AUDIO_BLOCK) __attribute__((amdgpu_waves_per_eu(1, 4))) void ssdr_audio_sub_kernel(SsdrSubArgs a)
+{
+    __shared__ __attribute__((aligned(16))) float2 s_z[NOCT * OCT];
+    __shared__ __attribute__((aligned(16))) float s_taps[SSDR_NTAP_MAX + 8];
+    const int l = threadIdx.x;
+    const uint32_t r = blockIdx.x;
+    if (r >= a.au.list_n) return;
+    const RowAt in_row = {a.au.iq + (uint64_t)a.parent[r] * a.au.ch_stride};
+    const ssdr_chan_consts kc = a.au.consts[r];
+    const int path = ssdr_audio_path(kc);                // wave-uniform
+    if (path == SSDR_PATH_GENERAL) channel_frames<PATH_GENERAL, NoTap, false, RowAt>(a.au, r, l, kc, s_z, s_taps, NoTap(), nullptr, nullptr, in_row);
+    else if (path == SSDR_PATH_DELAY4) channel_frames<PATH_DELAY4, NoTap, false, RowAt>(a.au, r, l, kc, s_z, s_taps, NoTap(), nullptr, nullptr, in_row);
+    else channel_frames<PATH_AM_RAW, NoTap, false, RowAt>(a.au, r, l, kc, s_z, s_taps, NoTap(), nullptr, nullptr, in_row);
+}
+
+template <int D>
+__global__ __launch_bounds__(SSDR_AUDIO_BLOCK) __attribute__((amdgpu_waves_per_eu(dec_phased(D) ? 3 : 1, 8))) void ssdr_audio_sub_dec_kernel(SsdrSubArgs a)
+{
+    constexpr int HOCT_S = SSDR_HIST / D / 8;
+    __shared__ __attribute__((aligned(16))) float2 s_z[dec_streams_per_phase(D) * (HOCT_S + 64) * OCT];
+    __shared__ __attribute__((aligned(16))) float2 s_h[dec_phased(D) ? D * HOCT_S * OCT : 1];
+    __shared__ __attribute__((aligned(16))) float s_taps[SSDR_NTAP_MAX + 8];
+    const int l = threadIdx.x;
+    const uint32_t r = blockIdx.x;
+    if (r >= a.au.list_n) return;
+    channel_frames_dec<D, false, RowAt>(a.au, r, l, a.au.consts[r], s_z, s_h, s_taps, nullptr, nullptr,
+                                        RowAt{a.au.iq + (uint64_t)a.parent[r] * a.au.ch_stride});
+}
+
 // ---------------------------------------------------------------- synthetic IQ (bench input)
 SSDR_DEV uint32_t fmix32(uint32_t h)
 {
@@ -485,6 +520,17 @@ hipError_t ssdr_launch_audio_dec_nb(const SsdrNbArgs &a, uint32_t decim, hipStre
     if (!a.au.list_n) return hipSuccess;
     if (decim == 2) hipLaunchKernelGGL(ssdr_audio_dec_nb_kernel<2>, dim3(a.au.list_n), dim3(SSDR_AUDIO_BLOCK), 0, stream, a);
     else if (decim == 4) hipLaunchKernelGGL(ssdr_audio_dec_nb_kernel<4>, dim3(a.au.list_n), dim3(SSDR_AUDIO_BLOCK), 0, stream, a);
+    else return hipErrorInvalidValue;
+    return hipGetLastError();
+}
+
+hipError_t ssdr_launch_audio_sub(const SsdrSubArgs &a, uint32_t decim, hipStream_t stream)
+{
+    if (!a.au.list_n) return hipSuccess;
+    const dim3 grid(a.au.list_n), block(SSDR_AUDIO_BLOCK);
+    if (decim == 1) hipLaunchKernelGGL(ssdr_audio_sub_kernel, grid, block, 0, stream, a);
+    else if (decim == 2) hipLaunchKernelGGL(ssdr_audio_sub_dec_kernel<2>, grid, block, 0, stream, a);
+    else if (decim == 4) hipLaunchKernelGGL(ssdr_audio_sub_dec_kernel<4>, grid, block, 0, stream, a);
     else return hipErrorInvalidValue;
     return hipGetLastError();
 }

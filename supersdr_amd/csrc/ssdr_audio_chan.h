@@ -21,6 +21,15 @@ struct NoTap {
     SSDR_DEV void operator()(uint32_t, const u32x4 &, const u32x4 &) const {}
 };
 
+// the Row policy of channel_frames / channel_frames_dec: where channel `ch` reads its frames from
+struct OwnRow {
+    SSDR_DEV const uint32_t *operator()(const SsdrAudioArgs &a, uint32_t ch) const { return a.iq + (uint64_t)ch * a.ch_stride; }
+};
+struct RowAt {
+    const uint32_t *row;
+    SSDR_DEV const uint32_t *operator()(const SsdrAudioArgs &, uint32_t) const { return row; }
+};
+
 enum { PATH_GENERAL = SSDR_PATH_GENERAL, PATH_DELAY4 = SSDR_PATH_DELAY4, PATH_AM_RAW = SSDR_PATH_AM_RAW };
 
 // One receiver channel, all frames of the call.
@@ -33,9 +42,12 @@ enum { PATH_GENERAL = SSDR_PATH_GENERAL, PATH_DELAY4 = SSDR_PATH_DELAY4, PATH_AM
 // BLANK: the impulse noise blanker (nb_frame) zeroes samples right after the loads; the tap, the ADC-overflow flag and nb_mask see
 // the input as it came, everything else -- the NCO, the filter, the FIR history in HBM -- the blanked samples.  nb: the channel's
 // blanker state, nb_mask: its mask row.  A separate instantiation: the kernels without it are the same code as before it existed.
-template <int PATH, typename Tap = NoTap, bool BLANK = false>
+// Row: where the frames are read from -- row `ch` of a.iq (OwnRow), or another row of it while constants, state and results are
+// row `ch` of arrays of their own (RowAt: a sub-receiver on its parent channel's IQ, ssdr_audio_sub_kernel).
+template <int PATH, typename Tap = NoTap, bool BLANK = false, typename Row = OwnRow>
 SSDR_DEV void channel_frames(const SsdrAudioArgs &a, const uint32_t ch, const int l, const ssdr_chan_consts &kc,
-                             float2 *s_z, float *s_taps, const Tap &tap = Tap(), SsdrNbChan *nb = nullptr, uint8_t *nb_mask = nullptr)
+                             float2 *s_z, float *s_taps, const Tap &tap = Tap(), SsdrNbChan *nb = nullptr, uint8_t *nb_mask = nullptr,
+                             const Row &in_row = Row())
 {
     const uint32_t mode = kc.mode;
     const uint32_t tap_groups = kc.tap_groups;           // fma(0, z, acc) == acc exactly: all-zero 4-tap groups are skipped
@@ -99,7 +111,7 @@ SSDR_DEV void channel_frames(const SsdrAudioArgs &a, const uint32_t ch, const in
         }
     }
 
-    const uint32_t *src = a.iq + (uint64_t)ch * a.ch_stride + 8 * l;
+    const uint32_t *src = in_row(a, ch) + 8 * l;
     int16_t *dst = a.pcm + (uint64_t)ch * a.n_frames * SSDR_FRAME + 8 * l;
     float *rssi_row = a.rssi + (uint64_t)ch * a.n_frames;
     uint8_t *flag_row = a.flags + (uint64_t)ch * a.n_frames;

@@ -61,9 +61,12 @@ struct SsdrNbChan { uint32_t gate, thresh, s1, s2, left, pad[3]; };
 // the audio kernels with the blanker instantiated (ssdr_audio_nb_kernel / ssdr_audio_dec_nb_kernel): the chain's arguments, the
 // blanker state [n_ch] and the blank mask [n_ch][n_frames * 64 D] (bit i of byte j: sample 8 j + i of the channel's input)
 struct SsdrNbArgs { SsdrAudioArgs au; SsdrNbChan *nb; uint8_t *mask; };
+// the audio kernels over a list of sub-receivers (ssdr_audio_sub_kernel / ssdr_audio_sub_dec_kernel, ssdr_set_subrx): row r of the
+// chain's arguments -- constants, taps, state, history, PCM, RSSI, flags, all [list_n] -- reads row parent[r] of au.iq
+struct SsdrSubArgs { SsdrAudioArgs au; const uint32_t *parent; };
 // frame paths of the audio kernel (ssdr_audio.hip): chosen per channel from its compiled constants
 enum { SSDR_PATH_GENERAL = 0, SSDR_PATH_DELAY4 = 1, SSDR_PATH_AM_RAW = 2, SSDR_PATH_COUNT = 3 };
-static inline int ssdr_audio_path(const ssdr_chan_consts &k)
+__host__ __device__ static inline int ssdr_audio_path(const ssdr_chan_consts &k)
 {
     if (!(k.fir_flags & SSDR_FIR_DELAY4) || k.mode == SSDR_MODE_IQ) return SSDR_PATH_GENERAL;
     return k.mode == SSDR_MODE_AM ? SSDR_PATH_AM_RAW : SSDR_PATH_DELAY4;
@@ -255,6 +258,7 @@ hipError_t ssdr_launch_audio(const SsdrAudioArgs &a, int path, hipStream_t strea
 hipError_t ssdr_launch_audio_dec(const SsdrAudioArgs &a, uint32_t decim, hipStream_t stream);
 hipError_t ssdr_launch_audio_nb(const SsdrNbArgs &a, int path, hipStream_t stream);            // the channels of a.au.chan_list
 hipError_t ssdr_launch_audio_dec_nb(const SsdrNbArgs &a, uint32_t decim, hipStream_t stream);
+hipError_t ssdr_launch_audio_sub(const SsdrSubArgs &a, uint32_t decim, hipStream_t stream);   // every row of the list, any path (decim 1) or D = 2 / 4
 hipError_t ssdr_launch_synth(const SsdrSynthArgs &a, hipStream_t stream);
 hipError_t ssdr_launch_sqrt_selftest(unsigned long long *mismatch, hipStream_t stream);
 hipError_t ssdr_launch_sqrt_values(const float *in, float *out_scaled, float *out_int, uint32_t n, hipStream_t stream);

@@ -449,6 +449,78 @@ class SsdrEngine:
         check(lib.ssdr_wf_view_stats(self._ctx, C.byref(ms), C.byref(n), 1 if reset else 0), "ssdr_wf_view_stats")
         return ms.value, n.value
 
+    def set_subrx(self, subs):
+        """The sub-receivers, replacing the whole list: a sequence of (id, channel, ChanParams), ids ascending and unique, at most 256;
+        an empty sequence removes them all.  A sub-receiver whose (id, channel) was in the old list keeps its stream and takes the new
+        parameters as set_params would; any other starts as after reset_state.  A value that does not fit the struct raises ValueError
+        before the library is called; a list the library refuses raises SsdrError (SSDR_EINVAL / SSDR_ESTATE).  Either way nothing
+        changes."""
+        rows = [(int(i), int(ch), p) for i, ch, p in subs]
+        if any(not 0 <= i < 2 ** 32 or not 0 <= ch < 2 ** 32 or not isinstance(p, ChanParams) for i, ch, p in rows):
+            raise ValueError("sub-receivers %r: out of range" % (subs,))
+        arr = (L.SubRx * max(len(rows), 1))(*[L.SubRx(*r) for r in rows])
+        check(lib.ssdr_set_subrx(self._ctx, arr if rows else None, len(rows)), "ssdr_set_subrx")
+
+    def get_subrx(self):
+        """-> [(id, channel, ChanParams), ...] the sub-receivers as set"""
+        n = C.c_uint32(0)
+        arr = (L.SubRx * L.SUBRX_MAX)()
+        check(lib.ssdr_get_subrx(self._ctx, arr, C.byref(n)), "ssdr_get_subrx")
+        out = []
+        for v in arr[:n.value]:
+            p = ChanParams()
+            C.memmove(C.byref(p), C.byref(v.params), C.sizeof(ChanParams))
+            out.append((v.id, v.channel, p))
+        return out
+
+    def _subrx_count(self):
+        n = C.c_uint32(0)
+        check(lib.ssdr_get_subrx(self._ctx, None, C.byref(n)), "ssdr_get_subrx")
+        return n.value
+
+    def subrx_audio(self):
+        """-> (pcm int16 [n_sub, n_frames*512], rssi float32 [n_sub, n_frames], flags uint8 [n_sub, n_frames]) of the last run_audio /
+        run_chain, rows in list order"""
+        n, nf = self._subrx_count(), self.audio_frames
+        pcm = np.empty((n, nf * L.FRAME), np.int16)
+        rssi = np.empty((n, nf), np.float32)
+        flags = np.empty((n, nf), np.uint8)
+        check(lib.ssdr_subrx_audio(self._ctx, pcm.ctypes.data, rssi.ctypes.data, flags.ctypes.data, 0), "ssdr_subrx_audio")
+        return pcm, rssi, flags
+
+    def subrx_state(self, first=0, count=None):
+        """-> (state, hist) of rows [first, first + count) of the list, as get_state"""
+        count = self._subrx_count() - first if count is None else int(count)
+        st = np.empty(count, STATE_DTYPE)
+        hist = np.empty((count, L.HIST, 2), np.int16)
+        check(lib.ssdr_get_subrx_state(self._ctx, int(first), count, st.ctypes.data, hist.ctypes.data), "ssdr_get_subrx_state")
+        return st, hist
+
+    def subrx_consts(self, first=0, count=None):
+        """-> (consts, taps) of rows [first, first + count) of the list, as get_consts"""
+        count = self._subrx_count() - first if count is None else int(count)
+        k = np.empty(count, CONSTS_DTYPE)
+        taps = np.empty((count, L.NTAP_MAX), np.float32)
+        check(lib.ssdr_get_subrx_consts(self._ctx, int(first), count, k.ctypes.data, taps.ctypes.data), "ssdr_get_subrx_consts")
+        return k, taps
+
+    def run_subrx_playbuffer(self, chans):
+        """play_buffer for the sub-receivers' frames of the last run -> int16 [n_sub, n_frames*L, 2], L = playbuffer_frame_len().
+        chans: list of PlayChan, one per sub-receiver in list order, or a ctypes array."""
+        n = self._subrx_count()
+        arr = chans if isinstance(chans, C.Array) else (PlayChan * max(n, 1))(*chans)
+        if len(arr) < n:
+            raise ValueError("run_subrx_playbuffer: %d settings for %d sub-receivers" % (len(arr), n))
+        out = np.empty((n, self.audio_frames * self.playbuffer_frame_len(), 2), np.int16)
+        check(lib.ssdr_run_subrx_playbuffer(self._ctx, arr, out.ctypes.data, 0), "ssdr_run_subrx_playbuffer")
+        return out
+
+    def subrx_stats(self, reset=False):
+        """-> (total_ms, runs) of the sub-receiver stage since the last reset (the time only with set_profiling on)"""
+        ms, n = C.c_float(), C.c_uint32()
+        check(lib.ssdr_subrx_stats(self._ctx, C.byref(ms), C.byref(n), 1 if reset else 0), "ssdr_subrx_stats")
+        return ms.value, n.value
+
     def audio_iq(self):
         """-> int16 [n_ch, n_frames*512, 2]: I,Q of the channels in "iq" mode for the last run_audio (rows of other modes: 0)"""
         out = np.empty((self.n_ch, self.audio_frames * L.FRAME, 2), np.int16)

@@ -94,10 +94,13 @@ class SuperframeResult:
     channel squelches).  On a pipelined listen hub squelched has a row per channel of squelched_channels (the channels whose squelch
     acted at the batch's submit) instead of one per channel; squelched_channels None: one per channel.
     With waterfall views (IQHub.set_wf_view): view_channels lists the channels that have one, ascending, and view_lines holds for each
-    an int16 [k, 1024] of the k byte lines (N = 1) its view produced in this run, k >= 0 (both None: no view is set)."""
+    an int16 [k, 1024] of the k byte lines (N = 1) its view produced in this run, k >= 0 (both None: no view is set).
+    With sub-receivers (IQHub.open_sub): sub_ids lists them, ascending, and sub_pcm int16 [n, frames*512], sub_rssi float32 [n, frames],
+    sub_flags uint8 [n, frames] and, with gpu_post and a worker on one of them, sub_play int16 [n, frames*L, 2] have a row for each
+    (all None: no sub-receiver is open)."""
     __slots__ = ("seq", "wf", "n_avg", "color", "chans", "pcm", "rssi", "flags", "play", "mono", "iq", "wire_rssi", "post_channels", "out_channels",
                  "snd_adpcm", "wf_adpcm", "snd_adpcm_channels", "wf_adpcm_channels", "squelched", "view_lines", "view_channels",
-                 "squelched_channels")
+                 "squelched_channels", "sub_ids", "sub_pcm", "sub_rssi", "sub_flags", "sub_play")
 
     def __init__(self, **kw):
         for k in self.__slots__:
@@ -154,6 +157,7 @@ class IQHub:
     channels -- those with a kiwi_waterfall / kiwi_sound / GpuStream on them (or attach()):
         wf_queue[c]  : (int16[1024] sum of N byte lines, N, db2col result or None)
         snd_queue[c] : Frame (int16[512] pcm + rssi, ADC-overflow flag, 48 kHz blocks) per audio frame
+        sub_queue[sid] : Frame per audio frame of sub-receiver `sid` (open_sub: a further demodulator on a channel's IQ)
     `lazy=None` attaches every channel at start on hubs of up to 1024 channels (a receiver UI) and none above that.
 
     A receiver that stalls or reconnects (KiwiWorker sleeps 5-15 s on its retry paths, kiwi/worker.py:58, 66) does not
@@ -287,6 +291,10 @@ class IQHub:
         self._comp_snd, self._comp_wf = [], []       # channels with "SET compression=1" / "SET wf_comp=1", sorted (the engine's row order)
         self._views = {}                             # channel -> (zoom, offset_hz): the waterfall views (set_wf_view)
         self._wf_listeners = {}                      # channel -> W/F streams open on it (the last one to close takes the view with it)
+        self._subs = {}                              # sid -> (channel, ChanParams): the sub-receivers (open_sub), the engine's rows in sid order
+        self._next_sid = 1
+        self.sub_queue = {}                          # sid -> bounded queue of Frame
+        self.sub_clients = {}                        # sid -> the kiwi_sound on it (volume / balance for its play_buffer), or None
         self._want_n = np.ones(self.n_ch, np.int32)  # averaging_n asked for by each channel's waterfall client
         self._want_all = {1: self.n_ch}              # N -> channels that want it (all channels / channels with a client)
         self._want_cli = {}
@@ -546,6 +554,71 @@ class IQHub:
             self.engine.set_wf_views([(ch,) + new[ch] for ch in sorted(new)])      # refused by the library: the old list stays
             self._views = new
 
+    # ---- sub-receivers: further demodulators on a channel's IQ (the reference's SUB RX, supersdr.py:624-629; ssdr_set_subrx)
+    def sub_params(self, sid):
+        """-> (channel, ChanParams) of sub-receiver `sid`"""
+        with self._lock:
+            return self._subs[int(sid)]
+
+    def _set_subs(self, new):
+        """the whole list to the engine, ids ascending; refused by the library: the old list stays"""
+        self.engine.set_subrx([(sid,) + new[sid] for sid in sorted(new)])
+        self._subs = new
+
+    @staticmethod
+    def _check_sub_params(p):
+        if p.mode == L.MODE_IQ:
+            raise ValueError("mod=iq on a sub-receiver: a sub-receiver has no I,Q output")
+
+    def open_sub(self, channel, params=None):
+        """A sub-receiver on `channel`: a further audio chain (NCO, filter, demodulator, AGC) on the channel's raw IQ with parameters
+        of its own, beside the channel's own demodulator, which does not notice.  -> sid, the hub's name for it: its frames arrive
+        in sub_queue[sid], set_sub_params(sid, p) retunes it (state kept, like set_params), close_sub(sid) ends it.  The other
+        sub-receivers keep their streams.  ValueError on a pipelined hub (before the engine is touched), beyond 256 of them (SSDR_SUBRX_MAX), for
+        mod=iq and for parameters the library refuses; then nothing changes."""
+        c = int(channel)
+        if not 0 <= c < self.n_ch:
+            raise IndexError("channel %d of %d" % (c, self.n_ch))
+        if self.pipeline:
+            raise ValueError("a sub-receiver needs the synchronous hub (the pipelined feed does not run sub-receivers)")
+        p = _copy_params(params if params is not None else self._default_params)
+        self._check_sub_params(p)
+        with self._lock:
+            if len(self._subs) >= L.SUBRX_MAX:
+                raise ValueError("a hub runs at most %d sub-receivers (SSDR_SUBRX_MAX)" % L.SUBRX_MAX)
+            if not hasattr(self.engine, "set_subrx"):
+                raise ValueError("this engine has no sub-receivers (set_subrx)")
+            sid = self._next_sid
+            new = dict(self._subs)
+            new[sid] = (c, p)
+            try:
+                self._set_subs(new)
+            except L.SsdrError as e:
+                raise ValueError("sub-receiver on channel %d refused: %s" % (c, e))
+            self._next_sid += 1
+            self.sub_queue[sid] = queue.Queue(2 * self._max_queue)
+            self.sub_clients[sid] = None
+            return sid
+
+    def set_sub_params(self, sid, p):
+        sid = int(sid)
+        self._check_sub_params(p)
+        with self._lock:
+            new = dict(self._subs)
+            new[sid] = (self._subs[sid][0], _copy_params(p))       # KeyError: no such sub-receiver
+            self._set_subs(new)                      # raises for parameters the library refuses; the old ones stay
+
+    def close_sub(self, sid):
+        sid = int(sid)
+        with self._lock:
+            if sid not in self._subs:
+                return                               # closing twice counts once
+            new = dict(self._subs)
+            del new[sid]
+            self._set_subs(new)
+            self.sub_queue.pop(sid, None)
+            self.sub_clients.pop(sid, None)
+
     def _drop_wf_view(self, c):
         if c in self._views:
             self.set_wf_view(c, 1)
@@ -783,8 +856,17 @@ class IQHub:
             play = eng.run_playbuffer(self._play_arr)
             if rec:
                 mono = eng.playbuffer_mono()
+        sub_ids = sub_pcm = sub_rssi = sub_flags = sub_play = None
+        if self._subs:
+            sub_ids = sorted(self._subs)
+            sub_pcm, sub_rssi, sub_flags = eng.subrx_audio()                    # [n_sub, frames*512], [n_sub, frames] x 2 (open_sub)
+            clients = [self.sub_clients.get(sid) for sid in sub_ids]
+            if self.gpu_post and any(s is not None for s in clients):
+                sub_play = eng.run_subrx_playbuffer([PlayChan(100.0, 0.0) if s is None else PlayChan(float(s.volume), float(s.audio_balance))
+                                                     for s in clients])
         self.superframes += 1
         self._hand_out(SuperframeResult(seq=self.superframes, wf=wf, n_avg=n_avg, color=color, chans=chans, pcm=pcm, rssi=rssi,
+                                        sub_ids=sub_ids, sub_pcm=sub_pcm, sub_rssi=sub_rssi, sub_flags=sub_flags, sub_play=sub_play,
                                         flags=flags, play=play, mono=mono, iq=iqo, wire_rssi=wire_rssi, post_channels=self._post_sel,
                                         snd_adpcm=snd_adpcm, wf_adpcm=wf_adpcm, snd_adpcm_channels=snd_sel, wf_adpcm_channels=wf_sel,
                                         squelched=closed, view_lines=view_lines, view_channels=view_ch))
@@ -846,6 +928,14 @@ class IQHub:
                     if qc is not None and r.squelched[qc, f]:
                         fr.squelched = True
                 _put_drop_oldest(q, fr)
+        for i, sid in enumerate(r.sub_ids or ()):
+            q = self.sub_queue.get(sid)
+            if q is None:
+                continue
+            for f in range(r.sub_pcm.shape[1] // L.FRAME):
+                _put_drop_oldest(q, Frame.make(r.sub_pcm[i, f * L.FRAME:(f + 1) * L.FRAME], r.sub_rssi[i, f],
+                                               r.sub_play[i, f * P:(f + 1) * P].copy() if r.sub_play is not None else None, None,
+                                               r.sub_flags[i, f]))
 
     def _run_pipelined(self, batch):
         eng = self.engine
@@ -1030,12 +1120,25 @@ class GpuStream:
     the channel's IQ band, raises ValueError instead of being demodulated as something else.  "SET mod=iq" selects the
     channel's filtered baseband itself (SSDR_MODE_IQ): its SND frames then carry I,Q pairs behind a GNSS stamp.
 
+    sub=sid (an SND stream; IQHub.open_sub): the stream is that of a SUB-RECEIVER on the channel, not of the channel's own demodulator.
+    "SET mod= low_cut= high_cut= freq=" and "SET agc= ..." then go to IQHub.set_sub_params (with the same refusal of frequencies
+    outside the channel's IQ band, and of mod=iq), its frames come from hub.sub_queue[sid], and close_connection closes the
+    sub-receiver.  "SET compression=0" and everything without a meaning here are accepted as on any stream; "SET nb=", "SET squelch=",
+    "SET de_emp=" and "SET compression=1" raise ValueError naming the sub-receiver: they are the channel's, not built for
+    sub-receivers.
+
     receive_message(): server -> client frames, byte for byte in the wire format the reference parses
     (utils_supersdr.py:782-784, 1065-1074): first what the constructors wait for ("MSG audio_init audio_rate= sample_rate=",
     then one empty W/F resp. SND frame), after that one frame per GPU result of this channel."""
 
-    def __init__(self, hub, channel, kind, center_khz, timeout=5.0):
+    def __init__(self, hub, channel, kind, center_khz, timeout=5.0, sub=None):
         self.hub, self.channel, self.kind, self.center_khz, self.timeout = hub, int(channel), kind, float(center_khz), timeout
+        self.sub = None if sub is None else int(sub)
+        if self.sub is not None:
+            if kind != "SND":
+                raise ValueError("a sub-receiver has an SND stream only")
+            if hub.sub_params(self.sub)[0] != self.channel:
+                raise ValueError("sub-receiver %d listens to channel %d, not %d" % (self.sub, hub.sub_params(self.sub)[0], self.channel))
         self.zoom = self.start = None
         self.seq = 0
         self.closed = False
@@ -1043,7 +1146,7 @@ class GpuStream:
         self._squelch_on = False                     # ... and its squelch
         self._deemp_on = False                       # ... and its de-emphasis
         self._greeting = deque()
-        if hasattr(hub, "attach"):                   # this channel has a listener now: its results are queued from here on
+        if self.sub is None and hasattr(hub, "attach"):      # this channel has a listener now: its results are queued from here on
             hub.attach(self.channel, wf=(kind != "SND"), snd=(kind == "SND"))
         if kind != "SND" and hasattr(hub, "_wf_listener_changed"):
             hub._wf_listener_changed(self.channel, +1)
@@ -1063,14 +1166,24 @@ class GpuStream:
         if len(words) < 2 or words[0] != "SET":
             return
         kv = dict(w.split("=", 1) for w in words[1:] if "=" in w)
+        if self.sub is not None:
+            for key in ("nb", "squelch", "de_emp"):
+                if key in kv and "mod" not in kv and "agc" not in kv:
+                    raise ValueError("SET %s= on sub-receiver %d of channel %d: the %s is the channel's, there is none for sub-receivers"
+                                     % (key, self.sub, self.channel, {"nb": "noise blanker", "squelch": "squelch", "de_emp": "de-emphasis"}[key]))
+            if "compression" in kv and "mod" not in kv and "agc" not in kv and int(kv["compression"]) != 0:
+                raise ValueError("SET compression=1 on sub-receiver %d of channel %d: a sub-receiver's frames are not ADPCM-encoded"
+                                 % (self.sub, self.channel))
         if "mod" in kv:
             self._retune(kv)
         elif "agc" in kv:
-            p = self.hub.params(self.channel)
+            p = self._params()
             q = _copy_params(p, agc_on=int(kv["agc"]), agc_hang=int(kv.get("hang", 0)), agc_thresh=float(kv.get("thresh", -80)),
                              agc_slope=float(kv.get("slope", 0)), agc_decay=float(kv.get("decay", 4000)),
                              agc_man_gain=float(kv.get("manGain", 50)))
-            self.hub.set_params(self.channel, q)
+            self._set_params(q)
+        elif self.sub is not None:
+            pass                                     # (compression=0, zoom=, ...: nothing to do for a sub-receiver)
         elif "nb" in kv:
             if "th" not in kv:
                 raise ValueError("SET nb= without th=: %r" % (msg,))
@@ -1088,6 +1201,15 @@ class GpuStream:
                 self._set_compression(int(kv[key]) != 0)
         elif "zoom" in kv:
             self.zoom, self.start = int(kv["zoom"]), int(kv.get("start", 0))
+
+    def _params(self):
+        return self.hub.params(self.channel) if self.sub is None else self.hub.sub_params(self.sub)[1]
+
+    def _set_params(self, q):
+        if self.sub is None:
+            self.hub.set_params(self.channel, q)
+        else:
+            self.hub.set_sub_params(self.sub, q)
 
     def _set_squelch(self, kv, msg):
         """both spellings: "squelch=<v> max=<m>" (the NBFM noise squelch) and "squelch=<v> param=<tail_s>" (the RSSI squelch)"""
@@ -1134,10 +1256,10 @@ class GpuStream:
         if abs(f_shift) > rate / 2:
             raise ValueError("tuning %.3f kHz is outside the %g kHz IQ band around %.3f kHz that channel %d receives"
                              % (freq, rate / 1000.0, self.center_khz, self.channel))
-        p = self.hub.params(self.channel)
+        p = self._params()
         q = _copy_params(p, mode=L.MODE_BY_NAME[mode], f_shift_hz=f_shift, low_cut=float(kv.get("low_cut", p.low_cut)),
                          high_cut=float(kv.get("high_cut", p.high_cut)))
-        self.hub.set_params(self.channel, q)
+        self._set_params(q)
 
     # ---- server -> client
     def receive_message(self):
@@ -1146,6 +1268,9 @@ class GpuStream:
         if self.closed:
             return None
         try:
+            if self.sub is not None:
+                f = self.hub.sub_queue[self.sub].get(timeout=self.timeout)
+                return snd_frame(f, f.rssi, self._next_seq(), adc_overflow=f.adc_overflow)
             if self.kind == "SND":
                 f = self.hub.snd_queue[self.channel].get(timeout=self.timeout)
                 if f.iq_block is not None:           # the channel is in "SET mod=iq": I,Q pairs behind a GNSS stamp
@@ -1167,6 +1292,8 @@ class GpuStream:
         return self.seq
 
     def close_connection(self, *a, **k):
+        if self.sub is not None and not self.closed:
+            self.hub.close_sub(self.sub)             # the sub-receiver goes with its stream
         if self._comp_on and not self.closed:        # the next connection's decoder starts from (0, 0): so does its encoder
             self._comp_on = False
             self.hub.set_compression(self.channel, **{("snd" if self.kind == "SND" else "wf"): False})
@@ -1399,24 +1526,35 @@ class WaterfallSeams:
 
 
 class SoundSeams:
-    """In front of the maintainer's kiwi_sound: process_audio_stream, play_buffer and the constructor's socket part."""
+    """In front of the maintainer's kiwi_sound: process_audio_stream, play_buffer and the constructor's socket part.
+    sub=True: the object is a SUB-RECEIVER on `channel` (IQHub.open_sub) -- the reference's SUB RX, a second kiwi_sound beside the
+    main one (supersdr.py:624-629) -- instead of taking the channel's own demodulator; `sub_id` is the hub's name for it.  The
+    default keeps the channel's own demodulator, whatever subrx_ says (subrx_ goes to the maintainer's constructor either way)."""
     _ref_module = None
 
     def __init__(self, freq_, mode_, lc_, hc_, password_, kiwi_wf, buffer_len, volume_=100, host_=None, port_=None,
-                 subrx_=False, hub=None, channel=None, timeout=5.0):
+                 subrx_=False, hub=None, channel=None, timeout=5.0, sub=False):
         self.hub = hub if hub is not None else kiwi_wf.hub
         self.channel = kiwi_wf.channel if channel is None else int(channel)
         self._timeout = timeout
         self.center_khz = float(getattr(kiwi_wf, "iq_center_khz", kiwi_wf.freq))   # the IQ band's centre: tuning is relative to it
         self.error = None                                # set by play_buffer when it has to give up
         self.late_flag = False                           # (the reference creates it in run(); play_buffer reads it)
-        self._gpu_stream = GpuStream(self.hub, self.channel, "SND", self.center_khz, timeout)
-        if hasattr(self.hub, "snd_clients"):
+        self.sub_id = self.hub.open_sub(self.channel) if sub else None
+        self._gpu_stream = GpuStream(self.hub, self.channel, "SND", self.center_khz, timeout, **({} if self.sub_id is None else {"sub": self.sub_id}))
+        if self.sub_id is None and hasattr(self.hub, "snd_clients"):
             self.hub.snd_clients[self.channel] = None
-        with _server_is_the_gpu(self._ref_module, self._gpu_stream):
-            # the maintainer's constructor sends "SET mod= ..." and "SET agc= ..." itself (:975-980): the channel is tuned by it
-            super().__init__(freq_, mode_, lc_, hc_, password_, kiwi_wf, buffer_len, volume_, host_, port_, subrx_)
-        if hasattr(self.hub, "snd_clients"):
+        try:
+            with _server_is_the_gpu(self._ref_module, self._gpu_stream):
+                # the maintainer's constructor sends "SET mod= ..." and "SET agc= ..." itself (:975-980): the channel is tuned by it
+                super().__init__(freq_, mode_, lc_, hc_, password_, kiwi_wf, buffer_len, volume_, host_, port_, subrx_)
+        except Exception:
+            if self.sub_id is not None:              # a sub-receiver that could not be tuned does not stay behind
+                self.hub.close_sub(self.sub_id)
+            raise
+        if self.sub_id is not None:
+            self.hub.sub_clients[self.sub_id] = self
+        elif hasattr(self.hub, "snd_clients"):
             self.hub.snd_clients[self.channel] = self
 
     def close_connection(self):
@@ -1426,7 +1564,10 @@ class SoundSeams:
     # ---- seam: utils_supersdr.py:1044-1076
     def _next_frame(self):
         try:
-            return self.hub.snd_queue[self.channel].get(timeout=self._timeout)
+            q = self.hub.snd_queue[self.channel] if self.sub_id is None else self.hub.sub_queue.get(self.sub_id)
+            if q is None:                            # the sub-receiver was closed under the worker
+                raise queue.Empty
+            return q.get(timeout=self._timeout)
         except queue.Empty:
             self.terminate = True
             self.kiwi_wf.terminate = True
