@@ -556,6 +556,46 @@ int ssdr_run_subrx_playbuffer(ssdr_ctx *ctx, const ssdr_play_chan *chans, int16_
  * their summed time (one HIP-event pair around the stage's kernel; runs made with profiling off count, and add no time). */
 int ssdr_subrx_stats(ssdr_ctx *ctx, float *total_ms, uint32_t *launches, int reset);
 
+/* -- wideband channeliser: one wide IQ stream in, 1024 receiver rows out (the step the KiwiSDR's DDC does in front of everything
+ *    above: the source of the narrow-band rows that ssdr_push_iq expects somebody to have cut already)
+ *
+ * A polyphase filter bank of M = SSDR_CHAN_BRANCHES = 1024 branches.  R = M / O wideband samples per output sample, oversampling
+ * O = 1 or 2; the prototype h is real, L = P * M taps (1 <= P <= SSDR_CHAN_TAPS_PER_BRANCH_MAX), float32, the gain folded in.  For
+ * stream w, wideband sample x[i] (complex from int16 I,Q; x[i] = 0 before the first call) and absolute output index n:
+ *     v_k[n] = sum_{t=0}^{L-1} h[t] x[n R - t] exp(-j 2 pi k (n R - t) / M),      k = 0 .. M-1
+ * -- mixed down by k fs / M, low-passed by h, decimated by R.  Rows ascend in frequency like the waterfall's bins: row w * M + r
+ * of the ctx holds k = (r + M/2) mod M, centred (r - M/2) fs / M from the stream's centre.  The stored sample is
+ * (rint(Re v), rint(Im v)), round-half-even, saturated to int16 (tests/chan_ref.py is the definition; the kernel works in float32
+ * and lands within 1 LSB of it).  The channel rate O fs / M is what the ctx treats as D times the Kiwi rate; O and D are independent.
+ * State per stream: its last L wideband samples and the output index.  ssdr_set_decimation / ssdr_set_kiwi_rate / ssdr_set_hop /
+ * ssdr_reset_state describe the channels, not the wide stream, and leave that state alone.  With no channeliser set nothing is
+ * launched, and before the first one nothing is allocated.  While one is set ssdr_feed_open and ssdr_checkpoint_save / _load return
+ * SSDR_ESTATE; while a pipelined feed is open setting one returns SSDR_ESTATE.  No SSDR_K_* slot: ssdr_channelizer_stats is the
+ * stage's own (DESIGN.md section 17 has the kernel and its cost). */
+#define SSDR_CHAN_BRANCHES 1024
+#define SSDR_CHAN_TAPS_PER_BRANCH_MAX 16
+/* taps float [taps_per_branch * 1024].  SSDR_EINVAL, and then nothing changes: branches != 1024, oversample not 1 or 2,
+ * taps_per_branch outside 1 .. 16, n_streams * 1024 != the ctx's channels, taps NULL or not finite.  n_streams = 0 removes the
+ * channeliser (the other arguments are ignored).  Setting one -- again, too -- starts every stream from silence at output index 0. */
+int ssdr_set_channelizer(ssdr_ctx *ctx, uint32_t n_streams, uint32_t branches, uint32_t oversample, const float *taps,
+                         uint32_t taps_per_branch);
+/* n_streams = 0: none is set (the others are 0 then); taps may be NULL, as may every pointer but n_streams */
+int ssdr_get_channelizer(ssdr_ctx *ctx, uint32_t *n_streams, uint32_t *branches, uint32_t *oversample, float *taps,
+                         uint32_t *taps_per_branch);
+/* every stream back to silence and output index 0, as after ssdr_set_channelizer.  SSDR_ESTATE without a channeliser. */
+int ssdr_channelizer_reset(ssdr_ctx *ctx);
+/* The counterpart of ssdr_push_iq: iq int16 [n_streams][n_frames * 512 * D * R][2] (a device pointer must be 16-byte aligned)
+ * becomes the ctx's input batch of n_frames frames, n_frames * 512 * D samples in each of its rows.  After it ssdr_run_wf /
+ * ssdr_run_audio / ssdr_run_chain, ssdr_read_input, views, sub-receivers and listener stages behave exactly as after a ssdr_push_iq
+ * of the same rows.  SSDR_ESTATE without a channeliser. */
+int ssdr_push_wideband(ssdr_ctx *ctx, const int16_t *iq, uint32_t n_frames, int is_device);
+/* the carried state: hist int16 [n_streams][L][2] each stream's last L wideband samples, oldest first (may be NULL); the index of
+ * the next output sample (may be NULL).  SSDR_ESTATE without a channeliser. */
+int ssdr_get_channelizer_state(ssdr_ctx *ctx, int16_t *hist, uint64_t *out_index);
+/* The stage's runs since the last reset (one per ssdr_push_wideband), and with ssdr_set_profiling on their summed time (one
+ * HIP-event pair around the stage: the filter bank's kernel and the small one that rewrites the history rows). */
+int ssdr_channelizer_stats(ssdr_ctx *ctx, float *total_ms, uint32_t *launches, int reset);
+
 /* -- pipelined host feed: the path a live ingest takes (KiwiSDRStream._process_iq_samples -> batches, kiwi/client.py:493)
  *
  * ssdr_push_iq + ssdr_run_* from pageable host memory serialise copy-in, kernels and copy-out.  The feed keeps `depth`

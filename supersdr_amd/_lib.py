@@ -94,6 +94,7 @@ class SubRx(C.Structure):
 
 
 assert C.sizeof(SubRx) == 96
+CHAN_BRANCHES, CHAN_TAPS_PER_BRANCH_MAX = 1024, 16      # SSDR_CHAN_BRANCHES, SSDR_CHAN_TAPS_PER_BRANCH_MAX
 
 
 class FeedListen(C.Structure):
@@ -185,6 +186,12 @@ _SIGS = {
     "ssdr_get_subrx_consts": (C.c_int, [_P, C.c_uint32, C.c_uint32, _P, _P]),
     "ssdr_run_subrx_playbuffer": (C.c_int, [_P, C.POINTER(PlayChan), _P, C.c_int]),
     "ssdr_subrx_stats": (C.c_int, [_P, C.POINTER(C.c_float), C.POINTER(C.c_uint32), C.c_int]),
+    "ssdr_set_channelizer": (C.c_int, [_P, C.c_uint32, C.c_uint32, C.c_uint32, _P, C.c_uint32]),
+    "ssdr_get_channelizer": (C.c_int, [_P, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), _P, C.POINTER(C.c_uint32)]),
+    "ssdr_channelizer_reset": (C.c_int, [_P]),
+    "ssdr_push_wideband": (C.c_int, [_P, _P, C.c_uint32, C.c_int]),
+    "ssdr_get_channelizer_state": (C.c_int, [_P, _P, C.POINTER(C.c_uint64)]),
+    "ssdr_channelizer_stats": (C.c_int, [_P, C.POINTER(C.c_float), C.POINTER(C.c_uint32), C.c_int]),
     "ssdr_feed_open": (C.c_int, [_P, C.c_uint32, C.c_uint32, C.c_uint32]),
     "ssdr_feed_slot": (C.c_int, [_P, C.POINTER(_P)]),
     "ssdr_feed_submit": (C.c_int, [_P]),
@@ -231,7 +238,9 @@ _SIGS = {
 }
 EXPORTS = tuple(_SIGS)
 _NEWER_THAN_AB_LIBS = ("ssdr_feed_collect_listen", "ssdr_set_subrx", "ssdr_get_subrx", "ssdr_subrx_audio", "ssdr_get_subrx_state",
-                       "ssdr_get_subrx_consts", "ssdr_run_subrx_playbuffer", "ssdr_subrx_stats")      # entry points a library named by SSDR_LIB_PATH (A/B builds only) may predate
+                       "ssdr_get_subrx_consts", "ssdr_run_subrx_playbuffer", "ssdr_subrx_stats", "ssdr_set_channelizer",
+                       "ssdr_get_channelizer", "ssdr_channelizer_reset", "ssdr_push_wideband", "ssdr_get_channelizer_state",
+                       "ssdr_channelizer_stats")      # entry points a library named by SSDR_LIB_PATH (A/B builds only) may predate
 
 
 def _load():

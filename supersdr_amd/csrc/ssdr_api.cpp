@@ -307,6 +307,16 @@ struct ssdr_ctx {
     size_t sub_play_cap = 0;                            // rows * frames d_sub_play_out holds
     float sub_ms = 0.0f;                                // the stage's own timing: ssdr_subrx_stats
     uint32_t sub_launches = 0;
+    // wideband channeliser (ssdr_set_channelizer): device memory at the first one set; with none set nothing is launched
+    uint32_t chz_streams = 0, chz_over = 1, chz_p = 0;  // streams (0: none set), O, P
+    std::vector<float> h_chz_taps;                      // [P * 1024] the prototype as set
+    float *d_chz_taps = nullptr;                        // [16 * 1024]
+    uint32_t *d_chz_hist = nullptr;                     // [n_ch / 1024][16 * 1024] rows of L = P * 1024: each stream's last L wideband samples
+    uint32_t *d_chz_in = nullptr;                       // a host caller's wideband samples of the call
+    size_t chz_in_dwords = 0;
+    uint64_t chz_out_index = 0;                         // output instants since the streams last started from silence
+    float chz_ms = 0.0f;                                // the stage's own timing: ssdr_channelizer_stats
+    uint32_t chz_launches = 0;
 };
 // Every device buffer a ctx owns (a feed slot's block: ssdr_feed_close) -- what ssdr_destroy frees.  One line per section of the
 // struct above, in its order (the own batch's buffers where `own` stands): a new `d_` member joins its section's line HERE, and tests/test_gpu_parity.py's
@@ -335,6 +345,7 @@ static void free_owned(ssdr_ctx *c)
         c->own.d_sub_pcm, c->own.d_sub_rssi, c->own.d_sub_flags,                                                      // sub-receivers: the own batch's results,
         c->d_sub_state[0], c->d_sub_state[1], c->d_sub_hist[0], c->d_sub_hist[1], c->d_sub_phist[0], c->d_sub_phist[1], c->d_sub_phist_alt,
         c->d_sub_consts, c->d_sub_taps, c->d_sub_parent, c->d_sub_play, c->d_sub_play_out,                            // ... state, constants, play_buffer
+        c->d_chz_taps, c->d_chz_hist, c->d_chz_in,                                                                    // wideband channeliser
     };
     for (void *p : owned)
         if (p) (void)hipFree(p);
@@ -350,6 +361,7 @@ static int get_event(ssdr_ctx *c, hipEvent_t *e)
 constexpr int kTimedDeemp = SSDR_K_COUNT;               // `which` of the de-emphasis kernel: timed beside the SSDR_K_* slots, not in them
 constexpr int kTimedWfView = SSDR_K_COUNT + 1;          // ... and of the waterfall views' stage
 constexpr int kTimedSubRx = SSDR_K_COUNT + 2;           // ... and of the sub-receivers'
+constexpr int kTimedChan = SSDR_K_COUNT + 3;            // ... and of the wideband channeliser
 static int timed_begin(ssdr_ctx *c, hipStream_t s = nullptr)
 {
     if (!s) s = c->stream;
@@ -384,6 +396,7 @@ static int resolve_pending(ssdr_ctx *c)
         if (p.which == kTimedDeemp) c->de_ms += ms;          // (its launches are counted where they are made)
         else if (p.which == kTimedWfView) c->wv_ms += ms;
         else if (p.which == kTimedSubRx) c->sub_ms += ms;
+        else if (p.which == kTimedChan) c->chz_ms += ms;
         else if (p.which >= 0) { c->k_ms[p.which] += ms; c->k_n[p.which] += 1; c->last_ms = ms; }
         c->free_events.push_back(p.e0);
         c->free_events.push_back(p.e1);
@@ -2217,6 +2230,7 @@ int ssdr_feed_open(ssdr_ctx *c, uint32_t n_frames, uint32_t depth, uint32_t flag
     // no wire compression, squelch, de-emphasis or waterfall view in the slot pipeline, unless it was opened for them
     const bool listen = (flags & SSDR_FEED_LISTEN) != 0;
     if (!c->h_sub.empty()) return SSDR_ESTATE;               // nor a sub-receiver, whatever it was opened for
+    if (c->chz_streams) return SSDR_ESTATE;                  // nor a channeliser: it fills the ctx's own batch, not a slot
     if (!listen && (c->comp_snd_n || c->comp_wf_n || c->sq_set_n || c->de_set_n || !c->h_wv.empty())) return SSDR_ESTATE;
     HIP_TRY(hipSetDevice(c->device));
     const bool post = (flags & SSDR_FEED_POST) != 0;
@@ -2589,6 +2603,7 @@ int ssdr_checkpoint_save(ssdr_ctx *c, void *blob) SSDR_GUARD
     if (c->de_set_n) return SSDR_ESTATE;                     // nor the de-emphasis's
     if (!c->h_wv.empty()) return SSDR_ESTATE;                // nor the waterfall views' streams
     if (!c->h_sub.empty()) return SSDR_ESTATE;               // nor the sub-receivers'
+    if (c->chz_streams) return SSDR_ESTATE;                  // nor the channeliser's history
     SsdrCkptHeader h = {kCkptMagic, kCkptVersion, c->n_ch, c->n_avg, c->wf_phase, c->audio_started ? 1u : 0u, c->kiwi_rate,
                         c->d_play_hist ? 1u : 0u, c->synth_sample0, c->hop, c->decim};
     char *p = static_cast<char *>(blob);
@@ -2633,7 +2648,7 @@ int ssdr_checkpoint_load(ssdr_ctx *c, const void *blob, uint64_t bytes) SSDR_GUA
     std::vector<float> ktaps(n * SSDR_NTAP_MAX);
     for (size_t i = 0; i < n; i++)
         if (ssdr_compile_params_host(&prm[i], &kc[i], ktaps.data() + i * SSDR_NTAP_MAX, h.decim, h.kiwi_rate) != SSDR_OK) return SSDR_EINVAL;
-    if (!c->feed.empty() || c->zoom > 1 || c->nb_on || c->comp_snd_n || c->comp_wf_n || c->sq_set_n || c->de_set_n || !c->h_wv.empty() || !c->h_sub.empty()) return SSDR_ESTATE;
+    if (!c->feed.empty() || c->zoom > 1 || c->nb_on || c->comp_snd_n || c->comp_wf_n || c->sq_set_n || c->de_set_n || !c->h_wv.empty() || !c->h_sub.empty() || c->chz_streams) return SSDR_ESTATE;
     std::vector<double> play_hist;                          // play_buffer state that arrives before its buffers exist: applied at first use
     if (h.has_play && !c->d_play_hist) {
         const double *q = reinterpret_cast<const double *>(static_cast<const char *>(blob) + sizeof h + n * (sizeof(ssdr_chan_consts) +
@@ -3543,6 +3558,112 @@ int ssdr_subrx_stats(ssdr_ctx *c, float *total_ms, uint32_t *launches, int reset
     if (total_ms) *total_ms = c->sub_ms;
     if (launches) *launches = c->sub_launches;
     if (reset) { c->sub_ms = 0.0f; c->sub_launches = 0; }
+    return SSDR_OK;
+} SSDR_UNGUARD
+
+// ---- wideband channeliser: one IQ stream in, 1024 rows of the ctx's input out (ssdr_channelize.hip) ------------------------
+int ssdr_set_channelizer(ssdr_ctx *c, uint32_t n_streams, uint32_t branches, uint32_t oversample, const float *taps,
+                         uint32_t taps_per_branch) SSDR_GUARD
+{
+    if (!c) return SSDR_EINVAL;
+    if (n_streams == 0) { c->chz_streams = 0; return SSDR_OK; }         // (the buffers stay for the next one)
+    if (branches != SSDR_CHAN_BRANCHES || (oversample != 1 && oversample != 2) || taps_per_branch < 1 ||
+        taps_per_branch > SSDR_CHAN_TAPS_PER_BRANCH_MAX || (uint64_t)n_streams * SSDR_CHAN_BRANCHES != c->n_ch || !taps) return SSDR_EINVAL;
+    const size_t n_taps = (size_t)taps_per_branch * SSDR_CHAN_BRANCHES;
+    for (size_t i = 0; i < n_taps; i++)
+        if (!std::isfinite(taps[i])) return SSDR_EINVAL;
+    if (!c->feed.empty()) return SSDR_ESTATE;
+    HIP_TRY(hipSetDevice(c->device));
+    std::vector<float> h(taps, taps + n_taps);
+    constexpr size_t kMaxTaps = (size_t)SSDR_CHAN_TAPS_PER_BRANCH_MAX * SSDR_CHAN_BRANCHES;
+    if (!c->d_chz_taps) HIP_TRY(hipMalloc(&c->d_chz_taps, kMaxTaps * sizeof(float)));
+    if (!c->d_chz_hist) HIP_TRY(hipMalloc(&c->d_chz_hist, (size_t)n_streams * kMaxTaps * 4));
+    // behind a channeliser run in flight (the main stream's order); silence in every history row
+    HIP_TRY(hipMemcpyAsync(c->d_chz_taps, h.data(), n_taps * sizeof(float), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemsetAsync(c->d_chz_hist, 0, (size_t)n_streams * n_taps * 4, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));                           // (`h` is host memory)
+    c->h_chz_taps.swap(h);
+    c->chz_streams = n_streams; c->chz_over = oversample; c->chz_p = taps_per_branch;
+    c->chz_out_index = 0;
+    return SSDR_OK;
+} SSDR_UNGUARD
+
+int ssdr_get_channelizer(ssdr_ctx *c, uint32_t *n_streams, uint32_t *branches, uint32_t *oversample, float *taps,
+                         uint32_t *taps_per_branch) SSDR_GUARD
+{
+    if (!c || !n_streams) return SSDR_EINVAL;
+    *n_streams = c->chz_streams;
+    const bool set = c->chz_streams != 0;
+    if (branches) *branches = set ? SSDR_CHAN_BRANCHES : 0;
+    if (oversample) *oversample = set ? c->chz_over : 0;
+    if (taps_per_branch) *taps_per_branch = set ? c->chz_p : 0;
+    if (taps && set) std::copy(c->h_chz_taps.begin(), c->h_chz_taps.end(), taps);
+    return SSDR_OK;
+} SSDR_UNGUARD
+
+int ssdr_channelizer_reset(ssdr_ctx *c) SSDR_GUARD
+{
+    if (!c) return SSDR_EINVAL;
+    if (!c->chz_streams) return SSDR_ESTATE;
+    HIP_TRY(hipSetDevice(c->device));
+    HIP_TRY(hipMemsetAsync(c->d_chz_hist, 0, (size_t)c->chz_streams * c->chz_p * SSDR_CHAN_BRANCHES * 4, c->stream));
+    c->chz_out_index = 0;
+    return SSDR_OK;
+} SSDR_UNGUARD
+
+int ssdr_get_channelizer_state(ssdr_ctx *c, int16_t *hist, uint64_t *out_index) SSDR_GUARD
+{
+    if (!c) return SSDR_EINVAL;
+    if (!c->chz_streams) return SSDR_ESTATE;
+    HIP_TRY(hipSetDevice(c->device));
+    if (out_index) *out_index = c->chz_out_index;
+    if (hist) {
+        HIP_TRY(hipMemcpyAsync(hist, c->d_chz_hist, (size_t)c->chz_streams * c->chz_p * SSDR_CHAN_BRANCHES * 4, hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(hipStreamSynchronize(c->stream));
+    }
+    return SSDR_OK;
+} SSDR_UNGUARD
+
+int ssdr_push_wideband(ssdr_ctx *c, const int16_t *iq, uint32_t n_frames, int is_device) SSDR_GUARD
+{
+    if (!c || !iq || n_frames == 0) return SSDR_EINVAL;
+    if (!c->chz_streams) return SSDR_ESTATE;
+    const uint64_t n_out = in_len(c, n_frames);
+    const uint64_t n_in = n_out * (SSDR_CHAN_BRANCHES / c->chz_over);
+    if (n_in > 0x7FFFFFFFull || (is_device && (reinterpret_cast<uintptr_t>(iq) & 15u))) return SSDR_EINVAL;
+    HIP_TRY(hipSetDevice(c->device));
+    SSDR_TRY(join_audio(c));
+    if (!is_device) {
+        SSDR_TRY(grow(c, c->d_chz_in, c->chz_in_dwords, (size_t)c->chz_streams * n_in, 4));
+        HIP_TRY(hipMemcpyAsync(c->d_chz_in, iq, (size_t)c->chz_streams * n_in * 4, hipMemcpyHostToDevice, c->stream));
+    }
+    SSDR_TRY(ensure_input(c, n_frames));
+    SsdrChanArgs a;
+    a.in = is_device ? reinterpret_cast<const uint32_t *>(iq) : c->d_chz_in;
+    a.in_stride = n_in;
+    a.n_streams = c->chz_streams; a.n_in = (uint32_t)n_in; a.n_out = (uint32_t)n_out;
+    a.oversample = c->chz_over; a.n_taps = c->chz_p * SSDR_CHAN_BRANCHES;
+    a.taps = c->d_chz_taps;
+    a.hist = c->d_chz_hist;
+    a.out_index = c->chz_out_index;
+    a.out = c->d_iq_own;
+    a.out_stride = n_out;
+    a.tw_stage = c->d_tw;
+    SSDR_TRY(timed_launch(c, kTimedChan, c->stream, [&]() -> int { HIP_TRY(ssdr_launch_channelize(a, c->stream)); return SSDR_OK; }));
+    c->chz_launches++;
+    c->chz_out_index += n_out;
+    own_input(c, c->d_iq_own, n_frames);
+    return SSDR_OK;
+} SSDR_UNGUARD
+
+int ssdr_channelizer_stats(ssdr_ctx *c, float *total_ms, uint32_t *launches, int reset) SSDR_GUARD
+{
+    if (!c) return SSDR_EINVAL;
+    HIP_TRY(hipSetDevice(c->device));
+    SSDR_TRY(resolve_pending(c));
+    if (total_ms) *total_ms = c->chz_ms;
+    if (launches) *launches = c->chz_launches;
+    if (reset) { c->chz_ms = 0.0f; c->chz_launches = 0; }
     return SSDR_OK;
 } SSDR_UNGUARD
 

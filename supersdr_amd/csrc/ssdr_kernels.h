@@ -234,6 +234,21 @@ struct SsdrWfViewArgs {
 };
 hipError_t ssdr_launch_wf_view_zoom(const SsdrWfViewArgs &a, hipStream_t stream);
 hipError_t ssdr_launch_wf_view_finish(const SsdrWfViewArgs &a, hipStream_t stream);
+// wideband channeliser (ssdr_channelize.hip, ssdr_set_channelizer): stream w of `in` -> rows w * 1024 .. w * 1024 + 1023 of `out`
+#define SSDR_CHAN_RUN 16                     // consecutive output instants one workgroup owns: n_out is a multiple (of 512, in fact)
+struct SsdrChanArgs {
+    const uint32_t *in;                      // [n_streams][in_stride] wideband dwords I | Q << 16 of this call, 16-byte aligned rows
+    uint64_t in_stride;                      // dwords between streams (a multiple of 4)
+    uint32_t n_streams, n_in, n_out;         // n_in = n_out * 1024 / oversample samples per stream
+    uint32_t oversample, n_taps;             // O; L = P * 1024
+    const float *taps;                       // [n_taps] the prototype
+    uint32_t *hist;                          // [n_streams][n_taps] in/out: the samples before the call's first, oldest first
+    uint64_t out_index;                      // absolute index of the call's first output instant (the O = 2 sign)
+    uint32_t *out;                           // [n_streams * 1024][out_stride]
+    uint64_t out_stride;                     // dwords between rows (a multiple of 4)
+    const float2 *tw_stage;                  // [992]
+};
+hipError_t ssdr_launch_channelize(const SsdrChanArgs &a, hipStream_t stream);     // the filter bank, then the history rows
 struct SsdrFusedArgs { SsdrWfArgs wf; SsdrAudioArgs au; uint32_t *ticket; uint32_t ticket_base; };
 // ticket: ssdr_chain_ws_kernel's pair counter; it stands at ticket_base at launch and is never reset: every trio draws its pairs and one ticket
 // beyond the last pair, so a launch of `grid` workgroups leaves it at ticket_base + pairs + grid * SSDR_WS_AUDIO_WAVES / 2 (ssdr_api.cpp)

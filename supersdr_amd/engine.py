@@ -8,7 +8,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib as L
-from ._lib import SmeterChan, ChanParams, ChanConsts, ChanState, Db2colChan, PlayChan, check, lib
+from ._lib import SmeterChan, ChanParams, ChanConsts, ChanState, Db2colChan, PlayChan, SsdrError, check, lib
 
 CONSTS_DTYPE = np.dtype([("mode", "<u4"), ("ntap8", "<u4"), ("dphi1", "<u4"), ("dphi2", "<u4"),
                          ("wf_cal_lin", "<f4"), ("smeter_cal_db", "<f4"), ("agc_c0", "<f4"), ("agc_c1", "<f4"),
@@ -519,6 +519,69 @@ class SsdrEngine:
         """-> (total_ms, runs) of the sub-receiver stage since the last reset (the time only with set_profiling on)"""
         ms, n = C.c_float(), C.c_uint32()
         check(lib.ssdr_subrx_stats(self._ctx, C.byref(ms), C.byref(n), 1 if reset else 0), "ssdr_subrx_stats")
+        return ms.value, n.value
+
+    # ---- wideband channeliser: one wide IQ stream -> 1024 rows of the input batch
+    def set_channelizer(self, n_streams, oversample=1, taps=None, branches=L.CHAN_BRANCHES):
+        """A polyphase filter bank in front of the ctx: every wideband stream fills 1024 rows (n_streams * 1024 == n_ch).  taps:
+        float32 [P * 1024], 1 <= P <= 16, the prototype with the gain folded in (iqstream.Channelizer designs one).  Every stream
+        starts from silence.  n_streams = 0 removes it.  What the library refuses raises SsdrError and changes nothing."""
+        if not int(n_streams):
+            check(lib.ssdr_set_channelizer(self._ctx, 0, 0, 0, None, 0), "ssdr_set_channelizer")
+            return
+        t = np.ascontiguousarray(taps, dtype=np.float32).ravel()
+        if t.size == 0 or t.size % int(branches):
+            raise ValueError("taps: %d is no multiple of %d branches" % (t.size, int(branches)))
+        check(lib.ssdr_set_channelizer(self._ctx, int(n_streams), int(branches), int(oversample), t.ctypes.data, t.size // int(branches)),
+              "ssdr_set_channelizer")
+
+    def get_channelizer(self):
+        """-> None, or (n_streams, oversample, taps float32 [P * 1024])"""
+        n, m, o, p = C.c_uint32(), C.c_uint32(), C.c_uint32(), C.c_uint32()
+        check(lib.ssdr_get_channelizer(self._ctx, C.byref(n), C.byref(m), C.byref(o), None, C.byref(p)), "ssdr_get_channelizer")
+        if not n.value:
+            return None
+        taps = np.empty(m.value * p.value, np.float32)
+        check(lib.ssdr_get_channelizer(self._ctx, C.byref(n), None, None, taps.ctypes.data, None), "ssdr_get_channelizer")
+        return n.value, o.value, taps
+
+    def _wideband_per_frame(self):
+        ch = self.get_channelizer()
+        if ch is None:
+            raise SsdrError(L.ESTATE, "push_wideband")
+        return ch[0], L.FRAME * self.decim * (L.CHAN_BRANCHES // ch[1])
+
+    def push_wideband(self, iq):
+        """iq: int16 [n_streams, n_frames * 512 * D * R, 2] host array, R = 1024 / oversample; becomes the input batch of n_frames frames"""
+        n_streams, per_frame = self._wideband_per_frame()
+        iq = np.ascontiguousarray(iq, dtype=np.int16)
+        if iq.ndim != 3 or iq.shape[0] != n_streams or iq.shape[2] != 2 or iq.shape[1] == 0 or iq.shape[1] % per_frame:
+            raise ValueError("iq must be int16[n_streams=%d, k*%d, 2], got %r" % (n_streams, per_frame, iq.shape))
+        n_frames = iq.shape[1] // per_frame
+        check(lib.ssdr_push_wideband(self._ctx, iq.ctypes.data, n_frames, 0), "ssdr_push_wideband")
+        self.in_frames = n_frames
+        self.sync()             # the host buffer may be released by the caller after this returns
+
+    def push_wideband_device(self, dev_ptr, n_frames):
+        check(lib.ssdr_push_wideband(self._ctx, int(dev_ptr), int(n_frames), 1), "ssdr_push_wideband")
+        self.in_frames = int(n_frames)
+
+    def channelizer_reset(self):
+        check(lib.ssdr_channelizer_reset(self._ctx), "ssdr_channelizer_reset")
+
+    def channelizer_state(self):
+        """-> (hist int16 [n_streams, L, 2]: each stream's last L wideband samples, oldest first; index of the next output sample)"""
+        ch = self.get_channelizer()
+        if ch is None:
+            raise SsdrError(L.ESTATE, "channelizer_state")
+        hist, n = np.empty((ch[0], ch[2].size, 2), np.int16), C.c_uint64()
+        check(lib.ssdr_get_channelizer_state(self._ctx, hist.ctypes.data, C.byref(n)), "ssdr_get_channelizer_state")
+        return hist, n.value
+
+    def channelizer_stats(self, reset=False):
+        """-> (total_ms, runs) of the channeliser since the last reset (the time only with set_profiling on)"""
+        ms, n = C.c_float(), C.c_uint32()
+        check(lib.ssdr_channelizer_stats(self._ctx, C.byref(ms), C.byref(n), 1 if reset else 0), "ssdr_channelizer_stats")
         return ms.value, n.value
 
     def audio_iq(self):

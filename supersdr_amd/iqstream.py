@@ -6,6 +6,8 @@
                       class Recorder(IQBatcher, KiwiSDRStream): pass
                   and drive it with the reference's own KiwiWorker(args=(recorder, options, run_event))
                   (kiwi/worker.py:10-79) -- its connect / open / run loop and retry table need nothing from here.
+  Channelizer     the wideband side of the boundary: the prototype filter and the row <-> frequency map of the
+                  1024-branch filter bank (ssdr_set_channelizer) that cuts one wide IQ stream into receiver rows.
   iq_body_to_int16 / int16_to_wire   the SND IQ frame payload (kiwi/client.py:443-454) <-> the
                   little-endian int16 [n,2] layout the kernels read.
 """
@@ -75,6 +77,58 @@ def kiwi_iq_wav_time_axis(stamps, block_len, nominal_rate=12000.0):
         last = now
         primed += primed < 3
     return (np.stack(rows) if rows else np.zeros((0, block_len))), np.array(rates)
+
+
+class Channelizer:
+    """The wideband channeliser as its user sees it (ssdr_set_channelizer): M = 1024 rows per stream, `oversample` O = 1 or 2 (the
+    rows run at O * fs / 1024), a prototype low-pass of taps_per_branch * 1024 taps.
+
+    The default prototype is a Kaiser-windowed sinc (beta 8), cut off at half the row spacing -- the 6 dB point sits where two
+    neighbouring rows meet -- and normalised so that a carrier on a row's centre comes out with `gain` times its amplitude.  With
+    taps_per_branch = 1 the window is all there is (a plain windowed FFT bank); 8 and more give rows that are flat over most of their
+    spacing.  Pass `taps` to use another one (float32 [taps_per_branch * 1024], gain folded in)."""
+    BRANCHES = 1024
+
+    def __init__(self, oversample, taps_per_branch, gain=1.0, taps=None):
+        self.oversample, self.taps_per_branch, self.gain = int(oversample), int(taps_per_branch), float(gain)
+        if self.oversample not in (1, 2) or not 1 <= self.taps_per_branch <= 16:
+            raise ValueError("oversample 1 or 2, taps_per_branch 1..16")
+        n = self.taps_per_branch * self.BRANCHES
+        if taps is None:
+            t = np.arange(n) - (n - 1) / 2.0
+            h = np.sinc(t / self.BRANCHES) * np.kaiser(n, 8.0)
+            taps = h * (self.gain / h.sum())
+        self.taps = np.ascontiguousarray(taps, np.float32).ravel()
+        if self.taps.size != n or not np.isfinite(self.taps).all():
+            raise ValueError("taps: %d finite values" % n)
+
+    @property
+    def step(self):
+        """wideband samples per sample of a row"""
+        return self.BRANCHES // self.oversample
+
+    def row_rate(self, rate):
+        """sample rate of the rows for a wideband rate `rate`"""
+        return float(rate) * self.oversample / self.BRANCHES
+
+    def row_of(self, offset_hz, rate):
+        """a frequency `offset_hz` from the wide stream's centre (-rate / 2 <= offset_hz < rate / 2), sampled at `rate` -> (row within
+        the stream, residual Hz from that row's centre): the row whose centre is nearest, ties upwards.  Row 0 is centred on -rate / 2,
+        which is +rate / 2 as well: the top half row spacing of the band comes out in row 0 with a negative residual."""
+        rate = float(rate)
+        spacing = rate / self.BRANCHES
+        if not -rate / 2 <= offset_hz < rate / 2:
+            raise ValueError("%g Hz is outside a %g Hz wide stream" % (offset_hz, rate))
+        k = int(np.floor(float(offset_hz) / spacing + 0.5))              # -512 .. 512
+        return (k + self.BRANCHES // 2) % self.BRANCHES, float(offset_hz) - k * spacing
+
+    def offset_of(self, row, residual_hz, rate):
+        """the inverse of row_of, in [-rate / 2, rate / 2)"""
+        if not 0 <= int(row) < self.BRANCHES:
+            raise ValueError("row %r of %d" % (row, self.BRANCHES))
+        rate = float(rate)
+        f = (int(row) - self.BRANCHES // 2) * rate / self.BRANCHES + float(residual_hz)
+        return f + rate if f < -rate / 2 else f
 
 
 class IQBatcher:

@@ -829,9 +829,43 @@ class IQHub:
             self._recording = rec
         return rec
 
-    def _run_superframe(self, batch):
+    def set_channelizer(self, channelizer):
+        """a wideband channeliser in front of the hub (iqstream.Channelizer; None removes it): every 1024 channels are the rows of one
+        wide stream, fed by feed_wideband.  Synchronous sample hubs only; refused before the engine is touched."""
+        if channelizer is not None and (self.pipeline or self.wire):
+            raise ValueError("the channeliser needs the synchronous sample hub (it fills the engine's own batch, not a feed slot)")
+        if channelizer is not None and self.n_ch % channelizer.BRANCHES:
+            raise ValueError("%d channels are no whole number of %d-row streams" % (self.n_ch, channelizer.BRANCHES))
+        with self._lock:
+            if channelizer is None:
+                self.engine.set_channelizer(0)
+            else:
+                self.engine.set_channelizer(self.n_ch // channelizer.BRANCHES, channelizer.oversample, channelizer.taps)
+            self.channelizer = channelizer
+
+    def feed_wideband(self, block):
+        """one superframe of every wide stream: int16 [n_streams, superframe samples * 1024 / oversample, 2] -> one GPU run, as if the
+        rows the channeliser cuts from it had been fed channel by channel"""
+        if self.pipeline or self.wire:
+            raise ValueError("feed_wideband needs the synchronous sample hub")
+        ch = getattr(self, "channelizer", None)
+        if ch is None:
+            raise ValueError("no channeliser is set (set_channelizer)")
+        block = np.asarray(block, np.int16)
+        want = (self.n_ch // ch.BRANCHES, self._sf * ch.step, 2)
+        if block.shape != want:
+            raise ValueError("feed_wideband takes int16 %r (one superframe of every stream), got %r" % (want, block.shape))
+        with self._lock:
+            if self._gmax > self._base * self._U:
+                raise ValueError("channels have samples buffered from feed(): a hub is fed either way, not both")
+            self._run_superframe(block, wideband=True)
+
+    def _run_superframe(self, batch, wideband=False):
         eng = self.engine
-        wire_rssi = eng.push_iq_wire(batch) if self.wire else eng.push_iq(batch)
+        if wideband:
+            wire_rssi = eng.push_wideband(batch)        # (None: the rows carry no SND headers)
+        else:
+            wire_rssi = eng.push_iq_wire(batch) if self.wire else eng.push_iq(batch)
         n_avg = self.averaging_n
         wf = eng.run_wf()                             # [lines, n_ch, 1024]
         wf_sel = list(self._comp_wf) if self._comp_wf else None
