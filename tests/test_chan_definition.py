@@ -4,14 +4,19 @@ import numpy as np
 import pytest
 
 import chan_cases as K
+import chan_edge_cases as E
 import chan_ref as R
 
 M = 1024
 
 
-@pytest.mark.parametrize("P,O", [(4, 1), (8, 2), (1, 2)])
-def test_fast_form_equals_the_defining_sum(P, O):
-    h = K.proto(P, O, 2.0)
+@pytest.mark.parametrize("P,O,kind", [(4, 1, "sinc"), (8, 2, "sinc"), (1, 2, "sinc"), (3, 2, "random"), (5, 1, "decay")],
+                         ids=["4-1", "8-2", "1-2", "3-2-random", "5-1-decay"])
+def test_fast_form_equals_the_defining_sum(P, O, kind):
+    # the windowed sinc is symmetric: only the asymmetric prototypes (tests/chan_edge_cases.py) hold the two forms to each other
+    # where the orientation of h matters -- the fast form on h[::-1] is then far from the defining sum
+    h = {"sinc": lambda: K.proto(P, O, 2.0), "random": lambda: E.proto_random(P, seed=11), "decay": lambda: E.proto_decay(P)}[kind]()
+    assert np.allclose(h, h[::-1], atol=1e-9) == (kind == "sinc")
     iq = K.wideband(1, 24 * (M // O), seed=P * 10 + O)[0]
     v = R.ChanRef(h, O).push(iq)                        # [rows, 24]
     x = R.to_complex(iq)
@@ -20,6 +25,11 @@ def test_fast_form_equals_the_defining_sum(P, O):
         d = R.direct(h, x, O, n, k)
         f = v[(k + M // 2) % M, n]
         assert abs(d - f) <= 1e-9 * scale, (n, k, d, f)
+    if kind != "sinc":
+        back = R.ChanRef(h[::-1].copy(), O).push(iq)
+        # (reversed taps miss by far more than the two forms may differ: 1e5 times that allowance, and about a tenth of |v|)
+        d = R.direct(h, x, O, 20, 333)
+        assert abs(d - back[(333 + M // 2) % M, 20]) > max(1e-4 * scale, 0.1 * abs(d))
 
 
 @pytest.mark.parametrize("O", [1, 2])
