@@ -596,6 +596,61 @@ int ssdr_get_channelizer_state(ssdr_ctx *ctx, int16_t *hist, uint64_t *out_index
  * HIP-event pair around the stage: the filter bank's kernel and the small one that rewrites the history rows). */
 int ssdr_channelizer_stats(ssdr_ctx *ctx, float *total_ms, uint32_t *launches, int reset);
 
+/* -- wideband scopes: zoomable waterfalls of a channeliser's wide stream (the reference's kiwi_waterfall looks at the server's whole
+ *    band and zooms into it: SET zoom=%d start=%d / cf=, utils_supersdr.py:741, 815-845; span = band / 2^zoom, kiwi/client.py:277-280)
+ *
+ * With a channeliser set (n_streams, O, R = 1024 / O) the wide rate is F = 1024 * D * kiwi_rate / O.  A SCOPE is (stream w, zoom z
+ * in 0 .. SSDR_WB_SCOPE_ZOOM_MAX, offset_hz with |offset_hz| <= F / 2): a DDC on stream w, F / 2^z wide around offset_hz, drawn by
+ * the shipped waterfall stage.  With Z = 2^z, x[i] the wide samples at absolute index i = out_index * R (counted from the
+ * channeliser's start or reset; x[i] = 0 where the stream's kept history does not reach), dphi = round(offset_hz / F * 2^32):
+ *     zmix[i] = x[i] * conj(P(i * dphi mod 2^32))        the phase is absolute in the stream's index: nothing is carried
+ *     y[m]    = sum_k h[k] zmix[Z m - k]                  h = float32(design_lowpass(1 / (2 Z), 1, 32 Z - 1, 32 Z - 1)): the rule of
+ *                                                         the views' taps, continued to Z = 1 .. 1024 (ssdr_wb_scope_taps)
+ *     stored as (rint Re, rint Im), half-even, saturated to int16.                       tests/scope_ref.py is the definition.
+ * Lines are SNAPSHOTS at the cadence of a receiver's un-zoomed waterfall, at every zoom: with the ctx's hop a line period is
+ * T = hop * D * R wide samples, line l is complete when the stream reaches i = (l + 1) T, and it is the fp32 waterfall stage's byte
+ * line (N = 1, calibration 0 dB, int16 [1024] in 0..255, like a view's) of the 1024 outputs m = (l + 1) T / Z - 1024 .. (l + 1) T / Z - 1
+ * (where T / Z < 1024 the windows overlap).  A call of n_frames yields floor((n0 + n_frames * 512 * D) / (hop * D)) - floor(n0 / (hop * D))
+ * lines per scope, n0 the channeliser's output index before the call; any frame count is taken, and a line is computed in the call
+ * that completes it, with that call's dphi and hop.  The lines are a product of ssdr_push_wideband, on its stream, behind the filter
+ * bank -- not of ssdr_run_wf.
+ * State: a scope has none of its own; a line is a pure function of the stream's raw samples.  While a stream has at least one scope
+ * it keeps its last SSDR_WB_SCOPE_HIST wide samples (enough for a z = 10 line that ends one sample into a call).  The history of a
+ * stream that gets its first scope starts as silence; a scope added to a stream that already has one sees the kept past; a stream
+ * that loses its last scope drops its history.  ssdr_channelizer_reset zeroes the histories and keeps the list; ssdr_set_channelizer
+ * empties the list (setting one or removing it).  ssdr_set_hop, ssdr_set_decimation and ssdr_set_kiwi_rate restart nothing (the last
+ * two recompute dphi from offset_hz; a scope whose offset_hz no longer fits keeps it as set and aliases, as a view's does).  Replacing
+ * the list restarts nobody: the lines of a kept scope are bit-identical whether or not another was added, changed or removed.
+ * Kernels: ssdr_wb_scope.hip (the DDC for the needed outputs only, then the shipped waterfall kernel with every (scope, line) as a
+ * channel of one line, then the history rings); with no scope set nothing is launched, before the first scope nothing is allocated,
+ * and memory grows with the streams that have scopes, not with n_streams.  No SSDR_K_* slot: ssdr_wb_scope_stats is the stage's
+ * own (DESIGN.md section 18 has the kernel and its cost).  Feed and checkpoints already refuse while a channeliser is set. */
+#define SSDR_WB_SCOPES_MAX 64
+#define SSDR_WB_SCOPE_ZOOM_MAX 10
+#define SSDR_WB_SCOPE_HIST (1056 * 1024)
+typedef struct ssdr_wb_scope {
+    uint32_t stream;
+    uint32_t zoom;          /* z: the span is F / 2^z */
+    double offset_hz;       /* centre, Hz from the wide stream's centre */
+} ssdr_wb_scope;            /* 16 B */
+/* Replaces the whole list: any order, several per stream, count <= SSDR_WB_SCOPES_MAX; (NULL, 0) removes every scope.  SSDR_EINVAL,
+ * and then nothing changes: count > 64, a stream not below n_streams, zoom > 10, offset_hz not finite or |offset_hz| > F / 2, a NULL
+ * list with count > 0.  SSDR_ESTATE without a channeliser. */
+int ssdr_set_wb_scopes(ssdr_ctx *ctx, const ssdr_wb_scope *scopes, uint32_t count);
+int ssdr_get_wb_scopes(ssdr_ctx *ctx, ssdr_wb_scope *scopes /* may be NULL */, uint32_t *count);
+/* The scope lines of the last ssdr_push_wideband: lines_out int16 [*total][1024], the scopes' lines one scope after the other in
+ * list order (may be NULL: counts only); every scope has *lines_per_scope of them.  SSDR_ESTATE if no scope is set or there has
+ * been no ssdr_push_wideband with the list as it is. */
+int ssdr_wb_scope_lines(ssdr_ctx *ctx, int16_t *lines_out, uint32_t *lines_per_scope, uint32_t *total, int out_is_device);
+/* The outputs the lines of scope `index` were drawn from (tests): iq_out int16 [lines][1024][2] (host memory), *samples = lines * 1024.
+ * SSDR_ESTATE like ssdr_wb_scope_lines. */
+int ssdr_read_wb_scope(ssdr_ctx *ctx, uint32_t index, int16_t *iq_out, uint32_t *samples);
+/* host only: the 32 * 2^zoom - 1 taps of a zoom, as the device holds them.  SSDR_EINVAL: zoom > 10, out NULL. */
+int ssdr_wb_scope_taps(uint32_t zoom, float *out);
+/* The scope stage's runs since the last reset (one per ssdr_push_wideband while a scope is set), and with ssdr_set_profiling on
+ * their summed time (one HIP-event pair around the stage's kernels). */
+int ssdr_wb_scope_stats(ssdr_ctx *ctx, float *total_ms, uint32_t *launches, int reset);
+
 /* -- pipelined host feed: the path a live ingest takes (KiwiSDRStream._process_iq_samples -> batches, kiwi/client.py:493)
  *
  * ssdr_push_iq + ssdr_run_* from pageable host memory serialise copy-in, kernels and copy-out.  The feed keeps `depth`

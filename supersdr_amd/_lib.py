@@ -95,6 +95,15 @@ class SubRx(C.Structure):
 
 assert C.sizeof(SubRx) == 96
 CHAN_BRANCHES, CHAN_TAPS_PER_BRANCH_MAX = 1024, 16      # SSDR_CHAN_BRANCHES, SSDR_CHAN_TAPS_PER_BRANCH_MAX
+WB_SCOPES_MAX, WB_SCOPE_ZOOM_MAX, WB_SCOPE_HIST = 64, 10, 1056 * 1024      # SSDR_WB_SCOPES_MAX, SSDR_WB_SCOPE_ZOOM_MAX, SSDR_WB_SCOPE_HIST
+
+
+class WbScope(C.Structure):
+    """a wideband scope (ssdr_set_wb_scopes): the span is the wide rate / 2^zoom around offset_hz"""
+    _fields_ = [("stream", C.c_uint32), ("zoom", C.c_uint32), ("offset_hz", C.c_double)]
+
+
+assert C.sizeof(WbScope) == 16
 
 
 class FeedListen(C.Structure):
@@ -192,6 +201,12 @@ _SIGS = {
     "ssdr_push_wideband": (C.c_int, [_P, _P, C.c_uint32, C.c_int]),
     "ssdr_get_channelizer_state": (C.c_int, [_P, _P, C.POINTER(C.c_uint64)]),
     "ssdr_channelizer_stats": (C.c_int, [_P, C.POINTER(C.c_float), C.POINTER(C.c_uint32), C.c_int]),
+    "ssdr_set_wb_scopes": (C.c_int, [_P, C.POINTER(WbScope), C.c_uint32]),
+    "ssdr_get_wb_scopes": (C.c_int, [_P, C.POINTER(WbScope), C.POINTER(C.c_uint32)]),
+    "ssdr_wb_scope_lines": (C.c_int, [_P, _P, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.c_int]),
+    "ssdr_read_wb_scope": (C.c_int, [_P, C.c_uint32, _P, C.POINTER(C.c_uint32)]),
+    "ssdr_wb_scope_taps": (C.c_int, [C.c_uint32, _P]),
+    "ssdr_wb_scope_stats": (C.c_int, [_P, C.POINTER(C.c_float), C.POINTER(C.c_uint32), C.c_int]),
     "ssdr_feed_open": (C.c_int, [_P, C.c_uint32, C.c_uint32, C.c_uint32]),
     "ssdr_feed_slot": (C.c_int, [_P, C.POINTER(_P)]),
     "ssdr_feed_submit": (C.c_int, [_P]),
@@ -240,7 +255,8 @@ EXPORTS = tuple(_SIGS)
 _NEWER_THAN_AB_LIBS = ("ssdr_feed_collect_listen", "ssdr_set_subrx", "ssdr_get_subrx", "ssdr_subrx_audio", "ssdr_get_subrx_state",
                        "ssdr_get_subrx_consts", "ssdr_run_subrx_playbuffer", "ssdr_subrx_stats", "ssdr_set_channelizer",
                        "ssdr_get_channelizer", "ssdr_channelizer_reset", "ssdr_push_wideband", "ssdr_get_channelizer_state",
-                       "ssdr_channelizer_stats")      # entry points a library named by SSDR_LIB_PATH (A/B builds only) may predate
+                       "ssdr_channelizer_stats", "ssdr_set_wb_scopes", "ssdr_get_wb_scopes", "ssdr_wb_scope_lines", "ssdr_read_wb_scope",
+                       "ssdr_wb_scope_taps", "ssdr_wb_scope_stats")      # entry points a library named by SSDR_LIB_PATH (A/B builds only) may predate
 
 
 def _load():

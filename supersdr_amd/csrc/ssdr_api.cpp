@@ -317,6 +317,23 @@ struct ssdr_ctx {
     uint64_t chz_out_index = 0;                         // output instants since the streams last started from silence
     float chz_ms = 0.0f;                                // the stage's own timing: ssdr_channelizer_stats
     uint32_t chz_launches = 0;
+    // wideband scopes (ssdr_set_wb_scopes): device memory at the first scope; with none set nothing is launched
+    std::vector<ssdr_wb_scope> h_ws;                    // the list as set
+    std::vector<uint32_t> h_ws_streams;                 // the streams that have a scope, ascending: ring s of d_ws_hist follows h_ws_streams[s]
+    bool ws_dirty = false;                              // the device list (slots, NCO steps) is to be uploaded before the next run
+    bool ws_run_valid = false;                          // there has been an ssdr_push_wideband with the list as it is
+    uint32_t ws_run_lines = 0;                          // lines per scope of that run
+    float *d_ws_taps = nullptr;                         // the eleven tap tables, that of Z at 32 (Z - 1)
+    SsdrWbScope *d_ws_scopes = nullptr;                 // [SSDR_WB_SCOPES_MAX]
+    uint32_t *d_ws_slot_stream = nullptr;               // [SSDR_WB_SCOPES_MAX]
+    uint32_t *d_ws_hist = nullptr;                      // [scoped streams][SSDR_WB_SCOPE_HIST] rings of raw wide samples
+    uint32_t *d_ws_out = nullptr;                       // [scopes][lines][1024] the outputs the lines are drawn from
+    int16_t *d_ws_lines = nullptr;                      // [scopes][lines][1024] the lines
+    int16_t *d_ws_acc = nullptr;                        // [2][rows][1024] the waterfall kernel's partial sums (N = 1: never used)
+    ssdr_chan_consts *d_ws_consts = nullptr;            // [rows] calibration 0 dB
+    size_t ws_rows = 0;                                 // (scope, line) rows d_ws_out / d_ws_lines / d_ws_acc / d_ws_consts hold
+    float ws_ms = 0.0f;                                 // the stage's own timing: ssdr_wb_scope_stats
+    uint32_t ws_launches = 0;
 };
 // Every device buffer a ctx owns (a feed slot's block: ssdr_feed_close) -- what ssdr_destroy frees.  One line per section of the
 // struct above, in its order (the own batch's buffers where `own` stands): a new `d_` member joins its section's line HERE, and tests/test_gpu_parity.py's
@@ -346,6 +363,7 @@ static void free_owned(ssdr_ctx *c)
         c->d_sub_state[0], c->d_sub_state[1], c->d_sub_hist[0], c->d_sub_hist[1], c->d_sub_phist[0], c->d_sub_phist[1], c->d_sub_phist_alt,
         c->d_sub_consts, c->d_sub_taps, c->d_sub_parent, c->d_sub_play, c->d_sub_play_out,                            // ... state, constants, play_buffer
         c->d_chz_taps, c->d_chz_hist, c->d_chz_in,                                                                    // wideband channeliser
+        c->d_ws_taps, c->d_ws_scopes, c->d_ws_slot_stream, c->d_ws_hist, c->d_ws_out, c->d_ws_lines, c->d_ws_acc, c->d_ws_consts,   // wideband scopes
     };
     for (void *p : owned)
         if (p) (void)hipFree(p);
@@ -362,6 +380,7 @@ constexpr int kTimedDeemp = SSDR_K_COUNT;               // `which` of the de-emp
 constexpr int kTimedWfView = SSDR_K_COUNT + 1;          // ... and of the waterfall views' stage
 constexpr int kTimedSubRx = SSDR_K_COUNT + 2;           // ... and of the sub-receivers'
 constexpr int kTimedChan = SSDR_K_COUNT + 3;            // ... and of the wideband channeliser
+constexpr int kTimedScope = SSDR_K_COUNT + 4;           // ... and of the wideband scopes
 static int timed_begin(ssdr_ctx *c, hipStream_t s = nullptr)
 {
     if (!s) s = c->stream;
@@ -397,6 +416,7 @@ static int resolve_pending(ssdr_ctx *c)
         else if (p.which == kTimedWfView) c->wv_ms += ms;
         else if (p.which == kTimedSubRx) c->sub_ms += ms;
         else if (p.which == kTimedChan) c->chz_ms += ms;
+        else if (p.which == kTimedScope) c->ws_ms += ms;
         else if (p.which >= 0) { c->k_ms[p.which] += ms; c->k_n[p.which] += 1; c->last_ms = ms; }
         c->free_events.push_back(p.e0);
         c->free_events.push_back(p.e1);
@@ -797,6 +817,7 @@ int ssdr_set_decimation(ssdr_ctx *c, uint32_t decim) SSDR_GUARD
     std::vector<ssdr_chan_params> all = c->h_params;              // recompile every channel for the new input rate
     const uint32_t keep = c->decim;
     c->decim = decim;
+    c->ws_dirty = true;                                           // (the scopes' NCO steps are the wide rate's; nothing of theirs restarts)
     int rc = ssdr_set_params(c, 0, c->n_ch, all.data());
     if (rc == SSDR_OK) {
         c->own.have_input = false;                                // a batch pushed at the old rate has the wrong extent
@@ -2932,6 +2953,7 @@ int ssdr_set_kiwi_rate(ssdr_ctx *c, uint32_t kiwi_rate) SSDR_GUARD
     std::vector<ssdr_chan_params> all = c->h_params;
     const uint32_t keep = c->kiwi_rate;
     c->kiwi_rate = kiwi_rate;
+    c->ws_dirty = true;                                           // (the scopes' NCO steps, as ssdr_set_decimation)
     c->de_dirty = true;                                           // the de-emphasis coefficients are the rate's
     int rc = ssdr_set_params(c, 0, c->n_ch, all.data());
     if (rc == SSDR_OK) {
@@ -3561,12 +3583,109 @@ int ssdr_subrx_stats(ssdr_ctx *c, float *total_ms, uint32_t *launches, int reset
     return SSDR_OK;
 } SSDR_UNGUARD
 
+// ---- wideband scopes: DDCs on the channeliser's wide streams, drawn by the waterfall kernel (ssdr_wb_scope.hip) -----------------
+static double ws_wide_rate(const ssdr_ctx *c) { return (double)SSDR_CHAN_BRANCHES * c->decim * c->kiwi_rate / c->chz_over; }
+// the taps of zoom z: 32 Z - 1 floats of design_lowpass, and a zero
+static int ws_make_taps(uint32_t z, float *out)
+{
+    const int n = (32 << z) - 1;
+    std::vector<double> h((size_t)n + 1);
+    if (ssdr_design_lowpass_exact(1.0 / (2.0 * (double)(1u << z)), 1.0, n, h.data()) != n) return SSDR_EINVAL;
+    for (int i = 0; i < n; i++) out[i] = (float)h[i];
+    out[n] = 0.0f;
+    return SSDR_OK;
+}
+// no scope: the list and the histories go (the small tables stay for the next list)
+static int ws_clear(ssdr_ctx *c)
+{
+    c->h_ws.clear();
+    c->h_ws_streams.clear();
+    c->ws_run_valid = false;
+    return release(c, c->d_ws_hist);
+}
+// The scopes' stage of one ssdr_push_wideband, on the main stream behind the filter bank: `in` the call's wide samples, n0 the output
+// index before the call.  Timed as one stage with its own event pair; not an SSDR_K_* slot.
+static int ws_stage(ssdr_ctx *c, const uint32_t *in, uint64_t in_stride, uint32_t n_in, uint64_t n_out, uint64_t n0)
+{
+    const uint32_t ns = (uint32_t)c->h_ws.size();
+    if (!ns) return SSDR_OK;
+    const uint32_t step = SSDR_CHAN_BRANCHES / c->chz_over;            // R
+    const uint64_t per_line = (uint64_t)c->hop * c->decim;              // output instants between lines
+    const uint32_t lines = (uint32_t)((n0 + n_out) / per_line - n0 / per_line);
+    c->ws_run_valid = false;
+    if (c->ws_dirty) {
+        std::vector<SsdrWbScope> dev(ns);
+        for (uint32_t j = 0; j < ns; j++) {
+            const ssdr_wb_scope &v = c->h_ws[j];
+            const uint32_t slot = (uint32_t)(std::lower_bound(c->h_ws_streams.begin(), c->h_ws_streams.end(), v.stream) - c->h_ws_streams.begin());
+            dev[j] = SsdrWbScope{v.stream, slot, v.zoom, zoom_dphi(v.offset_hz, ws_wide_rate(c))};
+        }
+        HIP_TRY(hipMemcpyAsync(c->d_ws_scopes, dev.data(), ns * sizeof(SsdrWbScope), hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(hipMemcpyAsync(c->d_ws_slot_stream, c->h_ws_streams.data(), c->h_ws_streams.size() * 4, hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(hipStreamSynchronize(c->stream));                       // (`dev` is host memory)
+        c->ws_dirty = false;
+    }
+    const size_t rows = (size_t)ns * lines;
+    if (rows > c->ws_rows) {                                            // the four buffers share one capacity
+        SSDR_TRY(release(c, c->d_ws_out));
+        SSDR_TRY(release(c, c->d_ws_lines));
+        SSDR_TRY(release(c, c->d_ws_acc));
+        SSDR_TRY(release(c, c->d_ws_consts));
+        c->ws_rows = 0;
+        HIP_TRY(hipMalloc(&c->d_ws_out, rows * SSDR_NFFT * 4));
+        HIP_TRY(hipMalloc(&c->d_ws_lines, rows * SSDR_NFFT * 2));
+        HIP_TRY(hipMalloc(&c->d_ws_acc, 2 * rows * SSDR_NFFT * 2));
+        HIP_TRY(hipMalloc(&c->d_ws_consts, rows * sizeof(ssdr_chan_consts)));
+        ssdr_chan_consts k = {};
+        k.wf_cal_lin = 1.0f;
+        std::vector<ssdr_chan_consts> ks(rows, k);
+        HIP_TRY(hipMemcpy(c->d_ws_consts, ks.data(), rows * sizeof(ssdr_chan_consts), hipMemcpyHostToDevice));
+        c->ws_rows = rows;
+    }
+    SsdrWbScopeArgs a;
+    a.in = in; a.in_stride = in_stride; a.n_in = n_in;
+    a.scopes = c->d_ws_scopes; a.n_scopes = ns; a.n_lines = lines;
+    a.zoom_mask = 0;
+    for (const ssdr_wb_scope &v : c->h_ws) a.zoom_mask |= 1u << v.zoom;
+    a.i0 = n0 * step;
+    a.hist_pos = (uint32_t)(a.i0 % SSDR_WB_SCOPE_HIST);
+    a.first_end = (uint32_t)(((n0 / per_line + 1) * per_line - n0) * step);
+    a.period = (uint32_t)(per_line * step);
+    a.taps = c->d_ws_taps; a.hist = c->d_ws_hist; a.out = c->d_ws_out;
+    a.slot_stream = c->d_ws_slot_stream; a.n_slots = (uint32_t)c->h_ws_streams.size();
+    SsdrWfArgs w;                            // every (scope, line) as a channel of a small ctx with one line: byte lines (N = 1), fp32 bins
+    w.iq = c->d_ws_out; w.ch_stride = SSDR_NFFT; w.n_ch = (uint32_t)rows; w.n_lines = 1;
+    w.tail = nullptr;
+    w.n_avg = 1; w.phase = 0; w.n_groups = 1; w.grp_run = 1;
+    w.out = c->d_ws_lines; w.acc_in = c->d_ws_acc; w.acc_out = c->d_ws_acc + c->ws_rows * SSDR_NFFT;
+    w.consts = c->d_ws_consts; w.win = c->d_win; w.tw_stage = c->d_tw; w.lut = c->d_lut;
+    const uint64_t need = ((uint64_t)((rows + 1) / 2) + SSDR_WF_BLOCK / 64 - 1) / (SSDR_WF_BLOCK / 64);
+    const uint32_t grid = (uint32_t)std::min<uint64_t>(std::max<uint64_t>(need, 1), c->wf_grid ? c->wf_grid : 1);
+    SSDR_TRY(timed_launch(c, kTimedScope, c->stream, [&]() -> int {
+        if (lines) {
+            HIP_TRY(ssdr_launch_wb_scope(a, c->stream));
+            HIP_TRY(ssdr_launch_wf(w, grid, c->stream));
+        }
+        HIP_TRY(ssdr_launch_wb_scope_hist(a, c->stream));
+        return SSDR_OK;
+    }));
+    c->ws_launches++;
+    c->ws_run_lines = lines;
+    c->ws_run_valid = true;
+    return SSDR_OK;
+}
+
 // ---- wideband channeliser: one IQ stream in, 1024 rows of the ctx's input out (ssdr_channelize.hip) ------------------------
 int ssdr_set_channelizer(ssdr_ctx *c, uint32_t n_streams, uint32_t branches, uint32_t oversample, const float *taps,
                          uint32_t taps_per_branch) SSDR_GUARD
 {
     if (!c) return SSDR_EINVAL;
-    if (n_streams == 0) { c->chz_streams = 0; return SSDR_OK; }         // (the buffers stay for the next one)
+    if (n_streams == 0) {                                               // (the buffers stay for the next one)
+        HIP_TRY(hipSetDevice(c->device));
+        SSDR_TRY(ws_clear(c));                                          // the scopes go with their streams
+        c->chz_streams = 0;
+        return SSDR_OK;
+    }
     if (branches != SSDR_CHAN_BRANCHES || (oversample != 1 && oversample != 2) || taps_per_branch < 1 ||
         taps_per_branch > SSDR_CHAN_TAPS_PER_BRANCH_MAX || (uint64_t)n_streams * SSDR_CHAN_BRANCHES != c->n_ch || !taps) return SSDR_EINVAL;
     const size_t n_taps = (size_t)taps_per_branch * SSDR_CHAN_BRANCHES;
@@ -3574,6 +3693,7 @@ int ssdr_set_channelizer(ssdr_ctx *c, uint32_t n_streams, uint32_t branches, uin
         if (!std::isfinite(taps[i])) return SSDR_EINVAL;
     if (!c->feed.empty()) return SSDR_ESTATE;
     HIP_TRY(hipSetDevice(c->device));
+    SSDR_TRY(ws_clear(c));                                              // a new channeliser starts without scopes
     std::vector<float> h(taps, taps + n_taps);
     constexpr size_t kMaxTaps = (size_t)SSDR_CHAN_TAPS_PER_BRANCH_MAX * SSDR_CHAN_BRANCHES;
     if (!c->d_chz_taps) HIP_TRY(hipMalloc(&c->d_chz_taps, kMaxTaps * sizeof(float)));
@@ -3607,6 +3727,7 @@ int ssdr_channelizer_reset(ssdr_ctx *c) SSDR_GUARD
     if (!c->chz_streams) return SSDR_ESTATE;
     HIP_TRY(hipSetDevice(c->device));
     HIP_TRY(hipMemsetAsync(c->d_chz_hist, 0, (size_t)c->chz_streams * c->chz_p * SSDR_CHAN_BRANCHES * 4, c->stream));
+    if (c->d_ws_hist) HIP_TRY(hipMemsetAsync(c->d_ws_hist, 0, c->h_ws_streams.size() * SSDR_WB_SCOPE_HIST * 4, c->stream));   // the scopes' list stays
     c->chz_out_index = 0;
     return SSDR_OK;
 } SSDR_UNGUARD
@@ -3651,6 +3772,7 @@ int ssdr_push_wideband(ssdr_ctx *c, const int16_t *iq, uint32_t n_frames, int is
     a.tw_stage = c->d_tw;
     SSDR_TRY(timed_launch(c, kTimedChan, c->stream, [&]() -> int { HIP_TRY(ssdr_launch_channelize(a, c->stream)); return SSDR_OK; }));
     c->chz_launches++;
+    SSDR_TRY(ws_stage(c, a.in, a.in_stride, a.n_in, n_out, c->chz_out_index));
     c->chz_out_index += n_out;
     own_input(c, c->d_iq_own, n_frames);
     return SSDR_OK;
@@ -3664,6 +3786,111 @@ int ssdr_channelizer_stats(ssdr_ctx *c, float *total_ms, uint32_t *launches, int
     if (total_ms) *total_ms = c->chz_ms;
     if (launches) *launches = c->chz_launches;
     if (reset) { c->chz_ms = 0.0f; c->chz_launches = 0; }
+    return SSDR_OK;
+} SSDR_UNGUARD
+
+int ssdr_set_wb_scopes(ssdr_ctx *c, const ssdr_wb_scope *scopes, uint32_t count) SSDR_GUARD
+{
+    if (!c || count > SSDR_WB_SCOPES_MAX || (count && !scopes)) return SSDR_EINVAL;
+    if (!c->chz_streams) return SSDR_ESTATE;
+    const double half = 0.5 * ws_wide_rate(c);
+    for (uint32_t i = 0; i < count; i++) {                  // all or nothing: every scope is checked before the list is touched
+        const ssdr_wb_scope &v = scopes[i];
+        if (v.stream >= c->chz_streams || v.zoom > SSDR_WB_SCOPE_ZOOM_MAX) return SSDR_EINVAL;
+        if (!(std::fabs(v.offset_hz) <= half)) return SSDR_EINVAL;           // (a NaN fails the comparison)
+    }
+    HIP_TRY(hipSetDevice(c->device));
+    if (!count) return ws_clear(c);
+    if (!c->d_ws_taps) {                                    // the first scope: the eleven tap tables and the small lists
+        std::vector<float> t((size_t)32 * ((2u << SSDR_WB_SCOPE_ZOOM_MAX) - 1u));
+        for (uint32_t z = 0; z <= SSDR_WB_SCOPE_ZOOM_MAX; z++) SSDR_TRY(ws_make_taps(z, t.data() + 32u * ((1u << z) - 1u)));
+        float *d = nullptr;
+        HIP_TRY(hipMalloc(&d, t.size() * sizeof(float)));
+        c->d_ws_taps = d;
+        HIP_TRY(hipMemcpy(c->d_ws_taps, t.data(), t.size() * sizeof(float), hipMemcpyHostToDevice));
+    }
+    if (!c->d_ws_scopes) HIP_TRY(hipMalloc(&c->d_ws_scopes, SSDR_WB_SCOPES_MAX * sizeof(SsdrWbScope)));
+    if (!c->d_ws_slot_stream) HIP_TRY(hipMalloc(&c->d_ws_slot_stream, SSDR_WB_SCOPES_MAX * 4));
+    std::vector<uint32_t> streams;
+    for (uint32_t i = 0; i < count; i++) streams.push_back(scopes[i].stream);
+    std::sort(streams.begin(), streams.end());
+    streams.erase(std::unique(streams.begin(), streams.end()), streams.end());
+    if (streams != c->h_ws_streams) {
+        // the rings of the new set of streams: a stream that keeps a scope keeps its history (device to device, behind whatever run
+        // is queued), one that gets its first starts as silence, one that lost its last is not copied
+        uint32_t *fresh = nullptr;
+        HIP_TRY(hipMalloc(&fresh, streams.size() * (size_t)SSDR_WB_SCOPE_HIST * 4));
+        int rc = [&]() -> int {
+            for (size_t s = 0; s < streams.size(); s++) {
+                const auto old = std::lower_bound(c->h_ws_streams.begin(), c->h_ws_streams.end(), streams[s]);
+                uint32_t *dst = fresh + s * (size_t)SSDR_WB_SCOPE_HIST;
+                if (old != c->h_ws_streams.end() && *old == streams[s])
+                    HIP_TRY(hipMemcpyAsync(dst, c->d_ws_hist + (size_t)(old - c->h_ws_streams.begin()) * SSDR_WB_SCOPE_HIST, (size_t)SSDR_WB_SCOPE_HIST * 4,
+                                           hipMemcpyDeviceToDevice, c->stream));
+                else
+                    HIP_TRY(hipMemsetAsync(dst, 0, (size_t)SSDR_WB_SCOPE_HIST * 4, c->stream));
+            }
+            return release(c, c->d_ws_hist);                // (waits for the copies)
+        }();
+        if (rc != SSDR_OK) { (void)hipStreamSynchronize(c->stream); (void)hipFree(fresh); return rc; }
+        c->d_ws_hist = fresh;
+        c->h_ws_streams.swap(streams);
+    }
+    c->h_ws.assign(scopes, scopes + count);
+    c->ws_dirty = true;
+    c->ws_run_valid = false;
+    return SSDR_OK;
+} SSDR_UNGUARD
+
+int ssdr_get_wb_scopes(ssdr_ctx *c, ssdr_wb_scope *scopes, uint32_t *count) SSDR_GUARD
+{
+    if (!c || !count) return SSDR_EINVAL;
+    *count = (uint32_t)c->h_ws.size();
+    if (scopes) std::copy(c->h_ws.begin(), c->h_ws.end(), scopes);
+    return SSDR_OK;
+} SSDR_UNGUARD
+
+int ssdr_wb_scope_lines(ssdr_ctx *c, int16_t *lines_out, uint32_t *lines_per_scope, uint32_t *total, int out_is_device) SSDR_GUARD
+{
+    if (!c) return SSDR_EINVAL;
+    if (c->h_ws.empty() || !c->ws_run_valid) return SSDR_ESTATE;
+    const size_t all = c->h_ws.size() * (size_t)c->ws_run_lines;
+    if (lines_per_scope) *lines_per_scope = c->ws_run_lines;
+    if (total) *total = (uint32_t)all;
+    if (!lines_out || !all) return SSDR_OK;
+    HIP_TRY(hipSetDevice(c->device));
+    return copy_out(c, lines_out, c->d_ws_lines, all * SSDR_NFFT * 2, out_is_device, kSyncHost);
+} SSDR_UNGUARD
+
+int ssdr_read_wb_scope(ssdr_ctx *c, uint32_t index, int16_t *iq_out, uint32_t *samples) SSDR_GUARD
+{
+    if (!c) return SSDR_EINVAL;
+    if (c->h_ws.empty() || !c->ws_run_valid) return SSDR_ESTATE;
+    if (index >= c->h_ws.size()) return SSDR_EINVAL;
+    const size_t n = (size_t)c->ws_run_lines * SSDR_NFFT;
+    if (samples) *samples = (uint32_t)n;
+    if (!iq_out || !n) return SSDR_OK;
+    HIP_TRY(hipSetDevice(c->device));
+    return copy_out(c, iq_out, c->d_ws_out + index * n, n * 4, 0, kSyncHost);
+} SSDR_UNGUARD
+
+int ssdr_wb_scope_taps(uint32_t zoom, float *out) SSDR_GUARD
+{
+    if (zoom > SSDR_WB_SCOPE_ZOOM_MAX || !out) return SSDR_EINVAL;
+    std::vector<float> t((size_t)32 << zoom);
+    SSDR_TRY(ws_make_taps(zoom, t.data()));
+    std::copy(t.begin(), t.end() - 1, out);
+    return SSDR_OK;
+} SSDR_UNGUARD
+
+int ssdr_wb_scope_stats(ssdr_ctx *c, float *total_ms, uint32_t *launches, int reset) SSDR_GUARD
+{
+    if (!c) return SSDR_EINVAL;
+    HIP_TRY(hipSetDevice(c->device));
+    SSDR_TRY(resolve_pending(c));
+    if (total_ms) *total_ms = c->ws_ms;
+    if (launches) *launches = c->ws_launches;
+    if (reset) { c->ws_ms = 0.0f; c->ws_launches = 0; }
     return SSDR_OK;
 } SSDR_UNGUARD
 

@@ -249,6 +249,26 @@ struct SsdrChanArgs {
     const float2 *tw_stage;                  // [992]
 };
 hipError_t ssdr_launch_channelize(const SsdrChanArgs &a, hipStream_t stream);     // the filter bank, then the history rows
+// wideband scopes (ssdr_wb_scope.hip, ssdr_set_wb_scopes): decimating DDCs on the channeliser's wide streams, 1024 outputs per completed line
+struct SsdrWbScope { uint32_t stream, slot, zoom, dphi; };     // stream of the input, row of `hist`, z (Z = 2^z), NCO step at the wide rate.  16 B
+struct SsdrWbScopeArgs {
+    const uint32_t *in;                      // [n_streams][in_stride] the call's wideband dwords (the channeliser's input)
+    uint64_t in_stride;
+    uint32_t n_in;                           // samples per stream in this call (a multiple of 512 * 512)
+    const SsdrWbScope *scopes;               // [n_scopes]
+    uint32_t n_scopes, n_lines;              // lines completed in this call: the same for every scope
+    uint32_t zoom_mask;                      // bit z: a scope of the list has zoom z (sizes the grid)
+    uint64_t i0;                             // absolute index of the call's first sample
+    uint32_t hist_pos;                       // i0 mod SSDR_WB_SCOPE_HIST: the ring slot of the call's first sample
+    uint32_t first_end, period;              // the first line ends first_end samples into the call (1 .. n_in), the next ones `period` apart
+    const float *taps;                       // the eleven tables: that of Z at 32 (Z - 1), 32 Z floats, the last one zero
+    uint32_t *hist;                          // [n_slots][SSDR_WB_SCOPE_HIST] rings: the scoped streams' last samples before the call
+    uint32_t *out;                           // [n_scopes][n_lines][1024] I | Q << 16
+    const uint32_t *slot_stream;             // [n_slots] the stream each ring follows (history kernel)
+    uint32_t n_slots;
+};
+hipError_t ssdr_launch_wb_scope(const SsdrWbScopeArgs &a, hipStream_t stream);
+hipError_t ssdr_launch_wb_scope_hist(const SsdrWbScopeArgs &a, hipStream_t stream);
 struct SsdrFusedArgs { SsdrWfArgs wf; SsdrAudioArgs au; uint32_t *ticket; uint32_t ticket_base; };
 // ticket: ssdr_chain_ws_kernel's pair counter; it stands at ticket_base at launch and is never reset: every trio draws its pairs and one ticket
 // beyond the last pair, so a launch of `grid` workgroups leaves it at ticket_base + pairs + grid * SSDR_WS_AUDIO_WAVES / 2 (ssdr_api.cpp)

@@ -584,6 +584,50 @@ class SsdrEngine:
         check(lib.ssdr_channelizer_stats(self._ctx, C.byref(ms), C.byref(n), 1 if reset else 0), "ssdr_channelizer_stats")
         return ms.value, n.value
 
+    # ---- wideband scopes: zoomable waterfalls of the channeliser's wide streams
+    def set_wb_scopes(self, scopes):
+        """The wideband scopes, replacing the whole list: a sequence of (stream, zoom, offset_hz) in any order, several per stream
+        allowed, zoom 0 .. 10 (the span is the wide rate / 2^zoom), offset_hz the centre from the wide stream's centre; at most 64; an
+        empty sequence removes them all.  Nobody is restarted: a scope has no state of its own.  A value that does not fit the struct
+        raises ValueError before the library is called; a list the library refuses raises SsdrError (SSDR_EINVAL / SSDR_ESTATE).
+        Either way nothing changes."""
+        rows = [(int(w), int(z), float(off)) for w, z, off in scopes]
+        if any(not 0 <= w < 2 ** 32 or not 0 <= z < 2 ** 32 for w, z, _ in rows):
+            raise ValueError("wideband scopes %r: out of range" % (scopes,))
+        arr = (L.WbScope * max(len(rows), 1))(*[L.WbScope(*r) for r in rows])
+        check(lib.ssdr_set_wb_scopes(self._ctx, arr if rows else None, len(rows)), "ssdr_set_wb_scopes")
+
+    def wb_scopes(self):
+        """-> [(stream, zoom, offset_hz), ...] the scopes as set"""
+        n = C.c_uint32(0)
+        arr = (L.WbScope * L.WB_SCOPES_MAX)()
+        check(lib.ssdr_get_wb_scopes(self._ctx, arr, C.byref(n)), "ssdr_get_wb_scopes")
+        return [(v.stream, v.zoom, v.offset_hz) for v in arr[:n.value]]
+
+    def wb_scope_lines(self):
+        """-> int16 [scopes, k, 1024]: the byte lines (N = 1) every scope completed in the last push_wideband, in list order"""
+        per, total = C.c_uint32(0), C.c_uint32(0)
+        check(lib.ssdr_wb_scope_lines(self._ctx, None, C.byref(per), C.byref(total), 0), "ssdr_wb_scope_lines")
+        out = np.empty((total.value // per.value if per.value else len(self.wb_scopes()), per.value, L.NFFT), np.int16)
+        if total.value:
+            check(lib.ssdr_wb_scope_lines(self._ctx, out.ctypes.data, C.byref(per), C.byref(total), 0), "ssdr_wb_scope_lines")
+        return out
+
+    def read_wb_scope(self, index):
+        """-> int16 [k, 1024, 2]: the I,Q outputs the lines of scope `index` were drawn from in the last push_wideband"""
+        n = C.c_uint32(0)
+        check(lib.ssdr_read_wb_scope(self._ctx, int(index), None, C.byref(n)), "ssdr_read_wb_scope")
+        out = np.empty((n.value // L.NFFT, L.NFFT, 2), np.int16)
+        if n.value:
+            check(lib.ssdr_read_wb_scope(self._ctx, int(index), out.ctypes.data, C.byref(n)), "ssdr_read_wb_scope")
+        return out
+
+    def wb_scope_stats(self, reset=False):
+        """-> (total_ms, runs) of the scope stage since the last reset (the time only with set_profiling on)"""
+        ms, n = C.c_float(), C.c_uint32()
+        check(lib.ssdr_wb_scope_stats(self._ctx, C.byref(ms), C.byref(n), 1 if reset else 0), "ssdr_wb_scope_stats")
+        return ms.value, n.value
+
     def audio_iq(self):
         """-> int16 [n_ch, n_frames*512, 2]: I,Q of the channels in "iq" mode for the last run_audio (rows of other modes: 0)"""
         out = np.empty((self.n_ch, self.audio_frames * L.FRAME, 2), np.int16)

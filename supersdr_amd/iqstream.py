@@ -130,6 +130,32 @@ class Channelizer:
         f = (int(row) - self.BRANCHES // 2) * rate / self.BRANCHES + float(residual_hz)
         return f + rate if f < -rate / 2 else f
 
+    # the wideband scopes (ssdr_set_wb_scopes): zoom z shows rate / 2^z around a centre, z = 0 .. SCOPE_ZOOM_MAX
+    SCOPE_ZOOM_MAX = 10
+
+    def wide_rate(self, row_rate):
+        """the inverse of row_rate: the wide stream's sample rate for rows that run at `row_rate` (D * kiwi_rate)"""
+        return float(row_rate) * self.BRANCHES / self.oversample
+
+    def scope_span(self, zoom, rate):
+        """Hz a scope of `zoom` shows of a wide stream sampled at `rate`"""
+        if not 0 <= int(zoom) <= self.SCOPE_ZOOM_MAX:
+            raise ValueError("zoom %r outside 0..%d" % (zoom, self.SCOPE_ZOOM_MAX))
+        return float(rate) / (1 << int(zoom))
+
+    def scope_for(self, lo_hz, hi_hz, rate):
+        """-> (zoom, offset_hz): the deepest zoom whose span still covers [lo_hz, hi_hz] (offsets from the wide stream's centre), centred
+        on the interval but moved inwards where the span would reach past the band's edge"""
+        rate, lo, hi = float(rate), float(lo_hz), float(hi_hz)
+        if not -rate / 2 <= lo <= hi <= rate / 2:
+            raise ValueError("[%g, %g] Hz is not an interval of a %g Hz wide stream" % (lo, hi, rate))
+        zoom = 0
+        while zoom < self.SCOPE_ZOOM_MAX and rate / (2 << zoom) >= hi - lo:
+            zoom += 1
+        half = rate / (2 << zoom)
+        centre = min(max((lo + hi) / 2.0, -rate / 2 + half), rate / 2 - half)
+        return zoom, centre
+
 
 class IQBatcher:
     """Mixin: IQ frames -> IQHub.  `samples` arrives as the reference builds it (kiwi/client.py:

@@ -97,10 +97,12 @@ class SuperframeResult:
     an int16 [k, 1024] of the k byte lines (N = 1) its view produced in this run, k >= 0 (both None: no view is set).
     With sub-receivers (IQHub.open_sub): sub_ids lists them, ascending, and sub_pcm int16 [n, frames*512], sub_rssi float32 [n, frames],
     sub_flags uint8 [n, frames] and, with gpu_post and a worker on one of them, sub_play int16 [n, frames*L, 2] have a row for each
-    (all None: no sub-receiver is open)."""
+    (all None: no sub-receiver is open).
+    With wideband scopes (IQHub.open_scope): scope_ids lists them, ascending, and scope_lines int16 [n, k, 1024] holds the k byte lines
+    (N = 1) each completed in this feed_wideband, k >= 0 (both None: no scope is open)."""
     __slots__ = ("seq", "wf", "n_avg", "color", "chans", "pcm", "rssi", "flags", "play", "mono", "iq", "wire_rssi", "post_channels", "out_channels",
                  "snd_adpcm", "wf_adpcm", "snd_adpcm_channels", "wf_adpcm_channels", "squelched", "view_lines", "view_channels",
-                 "squelched_channels", "sub_ids", "sub_pcm", "sub_rssi", "sub_flags", "sub_play")
+                 "squelched_channels", "sub_ids", "sub_pcm", "sub_rssi", "sub_flags", "sub_play", "scope_ids", "scope_lines")
 
     def __init__(self, **kw):
         for k in self.__slots__:
@@ -158,6 +160,8 @@ class IQHub:
         wf_queue[c]  : (int16[1024] sum of N byte lines, N, db2col result or None)
         snd_queue[c] : Frame (int16[512] pcm + rssi, ADC-overflow flag, 48 kHz blocks) per audio frame
         sub_queue[sid] : Frame per audio frame of sub-receiver `sid` (open_sub: a further demodulator on a channel's IQ)
+        scope_queue[sid] : WfLine (int16[1024] byte line, N = 1) per line of wideband scope `sid` (open_scope: a zoomable waterfall of a
+                       channeliser's wide stream, fed by feed_wideband)
     `lazy=None` attaches every channel at start on hubs of up to 1024 channels (a receiver UI) and none above that.
 
     A receiver that stalls or reconnects (KiwiWorker sleeps 5-15 s on its retry paths, kiwi/worker.py:58, 66) does not
@@ -295,6 +299,10 @@ class IQHub:
         self._next_sid = 1
         self.sub_queue = {}                          # sid -> bounded queue of Frame
         self.sub_clients = {}                        # sid -> the kiwi_sound on it (volume / balance for its play_buffer), or None
+        self._scopes = {}                            # sid -> (stream, zoom, offset_hz): the wideband scopes (open_scope), the engine's list in sid order
+        self._next_scope = 1
+        self.scope_queue = {}                        # sid -> bounded queue of WfLine (N = 1), drop-oldest
+        self.scope_clients = {}                      # sid -> the kiwi_waterfall on it (its display state for ssdr_db2col_line), or None
         self._want_n = np.ones(self.n_ch, np.int32)  # averaging_n asked for by each channel's waterfall client
         self._want_all = {1: self.n_ch}              # N -> channels that want it (all channels / channels with a client)
         self._want_cli = {}
@@ -619,6 +627,73 @@ class IQHub:
             self.sub_queue.pop(sid, None)
             self.sub_clients.pop(sid, None)
 
+    # ---- wideband scopes: zoomable waterfalls of a channeliser's wide stream (the band scope of kiwi_waterfall; ssdr_set_wb_scopes)
+    def scope(self, sid):
+        """-> (stream, zoom, offset_hz) of scope `sid`"""
+        with self._lock:
+            return self._scopes[int(sid)]
+
+    def _require_scopes(self):
+        if self.pipeline or self.wire:
+            raise ValueError("a wideband scope needs the synchronous sample hub")
+        if getattr(self, "channelizer", None) is None:
+            raise ValueError("a wideband scope needs a channeliser (set_channelizer)")
+        if not hasattr(self.engine, "set_wb_scopes"):
+            raise ValueError("this engine has no wideband scopes (set_wb_scopes)")
+
+    def _set_scopes(self, new):
+        """the whole list to the engine, in sid order; refused by the library: the old list stays"""
+        try:
+            self.engine.set_wb_scopes([new[sid] for sid in sorted(new)])
+        except L.SsdrError as e:
+            raise ValueError("wideband scopes refused: %s" % e)
+        self._scopes = new
+
+    def open_scope(self, stream, zoom, offset_hz=0.0):
+        """A scope on wide stream `stream`: the wide rate / 2^zoom around offset_hz (Hz from the stream's centre), zoom 0 .. 10.  -> sid:
+        scope_queue[sid] receives a WfLine (N = 1) per line of every feed_wideband -- as many a second as a receiver's un-zoomed
+        waterfall, at every zoom; retune_scope(sid, zoom, offset_hz) moves it, close_scope(sid) ends it.  Nobody else is restarted,
+        and a scope on a stream that already has one shows the stream's past at once.  ValueError on a pipelined or wire hub and
+        without a channeliser (before the engine is touched), beyond 64 scopes and for what the library refuses; then nothing changes."""
+        self._require_scopes()
+        row = (int(stream), int(zoom), float(offset_hz))
+        with self._lock:
+            if len(self._scopes) >= L.WB_SCOPES_MAX:
+                raise ValueError("a hub runs at most %d wideband scopes (SSDR_WB_SCOPES_MAX)" % L.WB_SCOPES_MAX)
+            sid = self._next_scope
+            new = dict(self._scopes)
+            new[sid] = row
+            self._set_scopes(new)
+            self._next_scope += 1
+            self.scope_queue[sid] = queue.Queue(2 * self._max_queue)
+            self.scope_clients[sid] = None
+            return sid
+
+    def retune_scope(self, sid, zoom, offset_hz):
+        sid = int(sid)
+        with self._lock:
+            new = dict(self._scopes)
+            new[sid] = (self._scopes[sid][0], int(zoom), float(offset_hz))       # KeyError: no such scope
+            self._set_scopes(new)
+
+    def close_scope(self, sid):
+        sid = int(sid)
+        with self._lock:
+            if sid not in self._scopes:
+                return                               # closing twice counts once
+            new = dict(self._scopes)
+            del new[sid]
+            self._set_scopes(new)
+            self.scope_queue.pop(sid, None)
+            self.scope_clients.pop(sid, None)
+
+    def db2col_scope_line(self, sid, wf_sum, n):
+        """db2col_line for a scope's client: the display state is that of the kiwi_waterfall on the scope"""
+        with self._lock:
+            k = self._db2col_chan(self.scope_clients.get(int(sid)))
+            color = self.engine.db2col_line(wf_sum, n, k)
+            return (color, k.low_clip_db, k.high_clip_db, k.dynamic_range, k.wf_min_db, k.wf_max_db)
+
     def _drop_wf_view(self, c):
         if c in self._views:
             self.set_wf_view(c, 1)
@@ -842,6 +917,9 @@ class IQHub:
             else:
                 self.engine.set_channelizer(self.n_ch // channelizer.BRANCHES, channelizer.oversample, channelizer.taps)
             self.channelizer = channelizer
+            self._scopes = {}                        # the library emptied its list: every scope is closed
+            self.scope_queue.clear()
+            self.scope_clients.clear()
 
     def feed_wideband(self, block):
         """one superframe of every wide stream: int16 [n_streams, superframe samples * 1024 / oversample, 2] -> one GPU run, as if the
@@ -866,6 +944,8 @@ class IQHub:
             wire_rssi = eng.push_wideband(batch)        # (None: the rows carry no SND headers)
         else:
             wire_rssi = eng.push_iq_wire(batch) if self.wire else eng.push_iq(batch)
+        scope_ids = sorted(self._scopes) if wideband and self._scopes else None
+        scope_lines = eng.wb_scope_lines() if scope_ids else None               # [n, k, 1024], k >= 0 (open_scope)
         n_avg = self.averaging_n
         wf = eng.run_wf()                             # [lines, n_ch, 1024]
         wf_sel = list(self._comp_wf) if self._comp_wf else None
@@ -903,7 +983,8 @@ class IQHub:
                                         sub_ids=sub_ids, sub_pcm=sub_pcm, sub_rssi=sub_rssi, sub_flags=sub_flags, sub_play=sub_play,
                                         flags=flags, play=play, mono=mono, iq=iqo, wire_rssi=wire_rssi, post_channels=self._post_sel,
                                         snd_adpcm=snd_adpcm, wf_adpcm=wf_adpcm, snd_adpcm_channels=snd_sel, wf_adpcm_channels=wf_sel,
-                                        squelched=closed, view_lines=view_lines, view_channels=view_ch))
+                                        squelched=closed, view_lines=view_lines, view_channels=view_ch,
+                                        scope_ids=scope_ids, scope_lines=scope_lines))
 
     def _hand_out(self, r):
         self.last = r
@@ -970,6 +1051,13 @@ class IQHub:
                 _put_drop_oldest(q, Frame.make(r.sub_pcm[i, f * L.FRAME:(f + 1) * L.FRAME], r.sub_rssi[i, f],
                                                r.sub_play[i, f * P:(f + 1) * P].copy() if r.sub_play is not None else None, None,
                                                r.sub_flags[i, f]))
+
+        for i, sid in enumerate(r.scope_ids or ()):
+            q = self.scope_queue.get(sid)
+            if q is None:
+                continue
+            for line in r.scope_lines[i]:
+                _put_drop_oldest(q, line.copy().view(WfLine))
 
     def _run_pipelined(self, batch):
         eng = self.engine
@@ -1148,7 +1236,10 @@ class GpuStream:
     close_connection turns a flag this stream turned on off again, so the next connection starts from (0, 0).
     "SET zoom=%d start=%d" (:741, 839) is remembered (`zoom`, `start`) and nothing else: how a span of 30 MHz / 2^zoom maps onto the
     channel's 12 kHz IQ band is undefined, so it does not move the channel's waterfall view -- that is
-    WaterfallSeams.set_iq_view / IQHub.set_wf_view, in the band's own terms.  The last W/F stream of a channel to close takes the
+    WaterfallSeams.set_iq_view / IQHub.set_wf_view, in the band's own terms.  Nor does it move a wideband scope (scope=sid: the
+    stream carries the lines of IQHub.open_scope's scope and closes it with the connection): a span of 30 MHz / 2^zoom is not the
+    wide rate F / 2^z for a general F, so the two zoom ladders are not mapped onto each other; a scope is
+    moved in its own terms, by WaterfallSeams.set_scope / IQHub.retune_scope.  The last W/F stream of a channel to close takes the
     channel's view with it.  The rest (auth, keepalive, ...)
     has no meaning without a server and is accepted.  A modulation without a demodulator here, or a frequency outside
     the channel's IQ band, raises ValueError instead of being demodulated as something else.  "SET mod=iq" selects the
@@ -1165,9 +1256,14 @@ class GpuStream:
     (utils_supersdr.py:782-784, 1065-1074): first what the constructors wait for ("MSG audio_init audio_rate= sample_rate=",
     then one empty W/F resp. SND frame), after that one frame per GPU result of this channel."""
 
-    def __init__(self, hub, channel, kind, center_khz, timeout=5.0, sub=None):
+    def __init__(self, hub, channel, kind, center_khz, timeout=5.0, sub=None, scope=None):
         self.hub, self.channel, self.kind, self.center_khz, self.timeout = hub, int(channel), kind, float(center_khz), timeout
         self.sub = None if sub is None else int(sub)
+        self.scope = None if scope is None else int(scope)
+        if self.scope is not None:
+            if kind == "SND" or sub is not None:
+                raise ValueError("a wideband scope has a W/F stream only")
+            hub.scope(self.scope)                    # KeyError: no such scope
         if self.sub is not None:
             if kind != "SND":
                 raise ValueError("a sub-receiver has an SND stream only")
@@ -1180,9 +1276,9 @@ class GpuStream:
         self._squelch_on = False                     # ... and its squelch
         self._deemp_on = False                       # ... and its de-emphasis
         self._greeting = deque()
-        if self.sub is None and hasattr(hub, "attach"):      # this channel has a listener now: its results are queued from here on
+        if self.sub is None and self.scope is None and hasattr(hub, "attach"):      # this channel has a listener now: its results are queued from here on
             hub.attach(self.channel, wf=(kind != "SND"), snd=(kind == "SND"))
-        if kind != "SND" and hasattr(hub, "_wf_listener_changed"):
+        if kind != "SND" and self.scope is None and hasattr(hub, "_wf_listener_changed"):
             hub._wf_listener_changed(self.channel, +1)
         if kind == "SND":
             rate = int(getattr(hub, "kiwi_rate", L.RATE))
@@ -1312,6 +1408,8 @@ class GpuStream:
                 if getattr(f, "adpcm", None) is not None:      # produced with "SET compression=1"
                     return snd_adpcm_frame(f.adpcm, f.rssi, self._next_seq(), adc_overflow=f.adc_overflow)
                 return snd_frame(f, f.rssi, self._next_seq(), adc_overflow=f.adc_overflow)
+            if self.scope is not None:               # a wideband scope's lines: single byte lines, never compressed
+                return wf_frame(self.hub.scope_queue[self.scope].get(timeout=self.timeout), self._next_seq())
             while True:                              # a line summed for some client's N > 1 is not a wire line: skip it
                 line, n, _ = self.hub.wf_queue[self.channel].get(timeout=self.timeout)
                 if n == 1:
@@ -1328,6 +1426,8 @@ class GpuStream:
     def close_connection(self, *a, **k):
         if self.sub is not None and not self.closed:
             self.hub.close_sub(self.sub)             # the sub-receiver goes with its stream
+        if self.scope is not None and not self.closed:
+            self.hub.close_scope(self.scope)         # ... and so does the scope
         if self._comp_on and not self.closed:        # the next connection's decoder starts from (0, 0): so does its encoder
             self._comp_on = False
             self.hub.set_compression(self.channel, **{("snd" if self.kind == "SND" else "wf"): False})
@@ -1337,7 +1437,7 @@ class GpuStream:
         if self._deemp_on and not self.closed:       # ... and with the de-emphasis off
             self._deemp_on = False
             self.hub.set_deemphasis(self.channel, am=0, nfm=0)
-        if self.kind != "SND" and not self.closed and hasattr(self.hub, "_wf_listener_changed"):
+        if self.kind != "SND" and self.scope is None and not self.closed and hasattr(self.hub, "_wf_listener_changed"):
             self.hub._wf_listener_changed(self.channel, -1)      # the last one to look takes the channel's view with it
         self.closed = True
 
@@ -1429,25 +1529,41 @@ class WaterfallSeams:
     What the GPU waterfall shows is the channel's 12 kHz IQ band (IQ_SPAN_KHZ around `iq_center_khz`, bin 512 = centre,
     11.72 Hz per bin), not a zoomable 0-30 MHz span: there is no server-side DDC behind it.  The reference's zoom / span
     arithmetic keeps running because supersdr.py drives it, but it only labels the display; `iq_bin_to_khz` /
-    `iq_khz_to_bin` are the true axis of `spectrum` and `wf_data`, and `set_freq_zoom` does not retune anything."""
+    `iq_khz_to_bin` are the true axis of `spectrum` and `wf_data`, and `set_freq_zoom` does not retune anything.
+
+    scope=sid (IQHub.open_scope): the object shows a WIDEBAND SCOPE instead of a channel's band -- the band scope a SuperSDR user
+    looks at first.  `freq_` is then the wide stream's centre, the worker's lines come from hub.scope_queue[sid] (single lines: a
+    client with N > 1 bins them itself, and with gpu_post the colours come from ssdr_db2col_line with this object's display state),
+    set_scope(zoom, khz) retunes, the axis is the scope's centre and span, and close_connection closes the scope."""
     _ref_module = None                               # set by bind()
 
-    def __init__(self, host_, port_, pass_, zoom_, freq_, eibi, disp, hub=None, channel=0, timeout=5.0):
+    def __init__(self, host_, port_, pass_, zoom_, freq_, eibi, disp, hub=None, channel=0, timeout=5.0, scope=None):
         if hub is None:
             raise ValueError("the GPU-backed kiwi_waterfall needs an IQHub (there is no server-side FFT to fall back to)")
         self.hub, self.channel, self._timeout = hub, int(channel), timeout
-        self.iq_center_khz = float(freq_ if freq_ else 14200)        # centre of the IQ band this channel receives
+        self.scope_id = None if scope is None else int(scope)        # a wideband scope (IQHub.open_scope) instead of a channel's band
+        self.iq_center_khz = float(freq_ if freq_ else 14200)        # centre of the IQ band this channel receives (scope: of the wide stream)
         self._gpu_post = None
         self._own_binning = None                     # (sum int16[1024], lines) while binning single lines itself
-        self._gpu_stream = GpuStream(hub, channel, "W/F", self.iq_center_khz, timeout)
+        self._gpu_stream = GpuStream(hub, channel, "W/F", self.iq_center_khz, timeout, scope=self.scope_id)
         with _server_is_the_gpu(self._ref_module, self._gpu_stream):
             # the maintainer's constructor and its start_stream() (:719-745) run as they are: their handshake lands on the
             # stand-ins, their Stream(...) is the GPU stream, their "SET zoom= start=" ... commands go to send_message()
             super().__init__(host_, port_, pass_, zoom_, freq_, eibi, disp)
-        if hasattr(hub, "wf_clients"):
+        if self.scope_id is not None:
+            hub.scope_clients[self.scope_id] = self
+        elif hasattr(hub, "wf_clients"):
             hub.wf_clients[self.channel] = self
 
     # ---- the true frequency axis of the GPU waterfall
+    def set_scope(self, zoom, khz=None):
+        """a worker on a wideband scope (scope=sid): zoom 0 .. 10 around khz, an absolute frequency inside the wide stream (default: its
+        centre, `freq_`); iq_bin_to_khz / iq_khz_to_bin follow.  ValueError out of range, and then nothing changes."""
+        if self.scope_id is None:
+            raise ValueError("set_scope needs a kiwi_waterfall opened on a wideband scope (scope=sid)")
+        khz = self.iq_center_khz if khz is None else float(khz)
+        self.hub.retune_scope(self.scope_id, zoom, (khz - self.iq_center_khz) * 1000.0)
+
     def set_iq_zoom_center(self, khz):
         """centre of this channel's zoomed waterfall (hub built with zoom > 1), an absolute frequency inside its IQ band"""
         if getattr(self.hub, "zoom", 1) == 1:        # no zoom stage runs: the lines stay centred on iq_center_khz, and so must the axis
@@ -1463,6 +1579,10 @@ class WaterfallSeams:
         self.hub.set_wf_view(self.channel, zoom, (khz - self.iq_center_khz) * 1000.0)
 
     def _iq_axis(self):
+        if self.scope_id is not None:                    # the scope's centre and span: the wide rate / 2^zoom
+            _, zoom, off = self.hub.scope(self.scope_id)
+            ch = self.hub.channelizer
+            return self.iq_center_khz + off / 1000.0, ch.scope_span(zoom, ch.wide_rate(self.hub.kiwi_rate)) / 1000.0
         view = self.hub.wf_view(self.channel) if hasattr(self.hub, "wf_view") else None
         if view is not None:                             # the axis of the lines this channel's queue carries now
             return self.iq_center_khz + view[1] / 1000.0, getattr(self.hub, "iq_span_khz", IQ_SPAN_KHZ) / view[0]
@@ -1483,15 +1603,18 @@ class WaterfallSeams:
 
     def _next_line(self):
         try:
+            if self.scope_id is not None:                # single lines; their colours: this client's own db2col run (spectrum_db2col)
+                return self.hub.scope_queue[self.scope_id].get(timeout=self._timeout), 1, None
             return self.hub.wf_queue[self.channel].get(timeout=self._timeout)
-        except queue.Empty:
+        except (queue.Empty, KeyError):                  # (KeyError: the scope was closed under the worker)
             self.terminate = True
             return None
 
     # ---- seam: utils_supersdr.py:780-785
     def receive_spectrum(self):
         """Leaves self.spectrum = float32[WF_BINS] in byte units (dBm = byte - 255)."""
-        self.hub.set_averaging(1, self.channel)          # this client bins nothing; others keep their N
+        if self.scope_id is None:
+            self.hub.set_averaging(1, self.channel)      # this client bins nothing; others keep their N
         while not self.terminate:
             item = self._next_line()
             if item is None:
@@ -1499,13 +1622,16 @@ class WaterfallSeams:
             line, n, self._gpu_post = item
             if n == 1:                                   # lines summed for a previous N of this client are stale
                 self.spectrum = line.astype(np.float32)
+                if self.scope_id is not None:            # a scope's line comes without colours: converted like a line binned here
+                    self._own_binning = (np.asarray(line, np.int16), 1)
                 return
 
     def receive_binned_spectrum(self, n):
         """Time binning (utils_supersdr.py:881-886).  On the GPU when the hub's clients agree on N: one summed line per N
         input lines, float32(sum)/float32(N) bit-identical to the reference's np.mean over its deque.  When they disagree
         the hub delivers single lines and this client takes the reference's own mean of N of them."""
-        self.hub.set_averaging(n, self.channel)
+        if self.scope_id is None:                        # (a scope's lines are single lines: binned here)
+            self.hub.set_averaging(n, self.channel)
         single = deque([], n)
         while not self.terminate:
             item = self._next_line()
@@ -1529,7 +1655,8 @@ class WaterfallSeams:
     def spectrum_db2col(self):
         if self._gpu_post is None and self._own_binning is not None and getattr(self.hub, "gpu_post", False):
             wf_sum, n = self._own_binning                # a line this client binned itself: its own db2col run
-            self._gpu_post = self.hub.db2col_line(self.channel, wf_sum, n)
+            self._gpu_post = (self.hub.db2col_line(self.channel, wf_sum, n) if self.scope_id is None
+                              else self.hub.db2col_scope_line(self.scope_id, wf_sum, n))
         self._own_binning = None
         if self._gpu_post is not None:                   # computed by ssdr_run_db2col with this object's display state
             (self.wf_color, self.low_clip_db, self.high_clip_db, self.dynamic_range,
