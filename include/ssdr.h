@@ -651,6 +651,45 @@ int ssdr_wb_scope_taps(uint32_t zoom, float *out);
  * their summed time (one HIP-event pair around the stage's kernels). */
 int ssdr_wb_scope_stats(ssdr_ctx *ctx, float *total_ms, uint32_t *launches, int reset);
 
+/* -- scope detectors: AVERAGE, PEAK and MIN of a scope's line over every window of the line period (a band scope's detectors; the
+ *    KiwiSDR's "SET interp=", which the reference sends in kiwi_waterfall.start_stream)
+ *
+ * A SAMPLE line is a snapshot: the last 1024 DDC outputs before the line's end, 1024 Z of the T = hop * D * R wide samples of the
+ * period.  A detector looks at all of them.  With everything of the block above (stream, zoom z, Z = 2^z, dphi, h, y[m] stored as
+ * saturated half-even int16, line l complete at E = (l + 1) T, x[i] = 0 where the kept history does not reach):
+ *     S = min(T, SSDR_WB_SCOPE_SPAN)                  W = max(1, S / (1024 Z))       all powers of two
+ *     window v (0 = the newest) of line l: the stored outputs m = E / Z - 1024 (v + 1) .. E / Z - 1024 v - 1
+ *     P_v[b] = the waterfall stage's scaled power of window v (Hann, 1024-point FFT, |X|^2, calibration 0 dB)
+ *     SAMPLE byte(P_0)    AVERAGE byte((1 / W) sum_v P_v)    PEAK byte(max_v P_v)    MIN byte(min_v P_v)
+ * byte() the stage's 1-dB quantiser, bins in ascending frequency.  tests/scope_det_ref.py is the definition.  The windows do not
+ * overlap and end at the line's end.  Where T / Z <= 1024 (deep zooms) W = 1 and every detector is SAMPLE, bit for bit.  Where
+ * T > SSDR_WB_SCOPE_SPAN (D = 2 or 4 at O = 1) the detector covers the NEWEST 2^20 samples of the period, not all of it: the ring
+ * (SSDR_WB_SCOPE_HIST = 2^20 + the longest filter) is as it was.  A scope still has no state: a detector line is a pure function of
+ * the stream's raw samples, computed in the call that completes it with that call's dphi, hop and detector; so it does not depend
+ * on how the stream is cut into calls or on what else is in the list, and the first lines behind a stream's first scope combine
+ * windows of silence (power 0, byte 0) as defined.  AVERAGE sums float32 powers in an order fixed by W alone (ssdr_wb_scope_det.hip).
+ * The detectors are a parallel array in list order; ssdr_wb_scope stays 16 bytes.  ssdr_set_wb_scopes puts every scope of the new
+ * list on SAMPLE (a caller that never sets detectors sees what it saw before, and launches what it launched); a caller that keeps
+ * detectors sets them again behind every list change -- scopes are stateless, so that costs nothing.
+ * Kernels: ssdr_wb_scope_det.hip.  Scratch: at most SSDR_WB_DET_SCRATCH bytes (48 MiB: 8192 windows of outputs and their partial
+ * power rows; a (zoom, detector)'s lines are worked through in passes of that size), allocated at the first non-SAMPLE detector or
+ * the first ssdr_read_wb_scope_windows, independent of n_streams and of the list.  ssdr_wb_scope_stats covers the passes. */
+enum { SSDR_WB_DET_SAMPLE = 0, SSDR_WB_DET_AVERAGE = 1, SSDR_WB_DET_PEAK = 2, SSDR_WB_DET_MIN = 3 };
+#define SSDR_WB_SCOPE_SPAN (1024 * 1024)
+#define SSDR_WB_DET_SCRATCH (48u << 20)
+/* det[count], count the list's length.  SSDR_EINVAL, and then nothing changes: count not the list's, a value above 3, NULL with
+ * count > 0.  SSDR_ESTATE without a channeliser.  After it ssdr_wb_scope_lines / ssdr_read_wb_scope return SSDR_ESTATE until the
+ * next ssdr_push_wideband, as after a list change. */
+int ssdr_set_wb_scope_detectors(ssdr_ctx *ctx, const uint32_t *det, uint32_t count);
+int ssdr_get_wb_scope_detectors(ssdr_ctx *ctx, uint32_t *det /* may be NULL */, uint32_t *count);
+/* W of scope `index` at the current hop, D and O (whatever its detector).  SSDR_EINVAL: index not in the list. */
+int ssdr_wb_scope_windows(ssdr_ctx *ctx, uint32_t index, uint32_t *windows);
+/* The stored window outputs of the LAST line of the last ssdr_push_wideband for scope `index` (tests), newest window first:
+ * iq_out int16 [W][1024][2] (host memory; NULL: the count only), W as of that push; window 0 is that line's row of
+ * ssdr_read_wb_scope.  Recomputed from the stream's ring, so valid only if that push ended exactly on a line end: SSDR_ESTATE
+ * otherwise, where ssdr_wb_scope_lines would refuse, and after ssdr_channelizer_reset. */
+int ssdr_read_wb_scope_windows(ssdr_ctx *ctx, uint32_t index, int16_t *iq_out, uint32_t *windows);
+
 /* -- pipelined host feed: the path a live ingest takes (KiwiSDRStream._process_iq_samples -> batches, kiwi/client.py:493)
  *
  * ssdr_push_iq + ssdr_run_* from pageable host memory serialise copy-in, kernels and copy-out.  The feed keeps `depth`

@@ -96,6 +96,8 @@ class SubRx(C.Structure):
 assert C.sizeof(SubRx) == 96
 CHAN_BRANCHES, CHAN_TAPS_PER_BRANCH_MAX = 1024, 16      # SSDR_CHAN_BRANCHES, SSDR_CHAN_TAPS_PER_BRANCH_MAX
 WB_SCOPES_MAX, WB_SCOPE_ZOOM_MAX, WB_SCOPE_HIST = 64, 10, 1056 * 1024      # SSDR_WB_SCOPES_MAX, SSDR_WB_SCOPE_ZOOM_MAX, SSDR_WB_SCOPE_HIST
+WB_DET_SAMPLE, WB_DET_AVERAGE, WB_DET_PEAK, WB_DET_MIN = 0, 1, 2, 3          # SSDR_WB_DET_*
+WB_SCOPE_SPAN = 1024 * 1024                                                # SSDR_WB_SCOPE_SPAN
 
 
 class WbScope(C.Structure):
@@ -207,6 +209,10 @@ _SIGS = {
     "ssdr_read_wb_scope": (C.c_int, [_P, C.c_uint32, _P, C.POINTER(C.c_uint32)]),
     "ssdr_wb_scope_taps": (C.c_int, [C.c_uint32, _P]),
     "ssdr_wb_scope_stats": (C.c_int, [_P, C.POINTER(C.c_float), C.POINTER(C.c_uint32), C.c_int]),
+    "ssdr_set_wb_scope_detectors": (C.c_int, [_P, C.POINTER(C.c_uint32), C.c_uint32]),
+    "ssdr_get_wb_scope_detectors": (C.c_int, [_P, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
+    "ssdr_wb_scope_windows": (C.c_int, [_P, C.c_uint32, C.POINTER(C.c_uint32)]),
+    "ssdr_read_wb_scope_windows": (C.c_int, [_P, C.c_uint32, _P, C.POINTER(C.c_uint32)]),
     "ssdr_feed_open": (C.c_int, [_P, C.c_uint32, C.c_uint32, C.c_uint32]),
     "ssdr_feed_slot": (C.c_int, [_P, C.POINTER(_P)]),
     "ssdr_feed_submit": (C.c_int, [_P]),
@@ -256,7 +262,8 @@ _NEWER_THAN_AB_LIBS = ("ssdr_feed_collect_listen", "ssdr_set_subrx", "ssdr_get_s
                        "ssdr_get_subrx_consts", "ssdr_run_subrx_playbuffer", "ssdr_subrx_stats", "ssdr_set_channelizer",
                        "ssdr_get_channelizer", "ssdr_channelizer_reset", "ssdr_push_wideband", "ssdr_get_channelizer_state",
                        "ssdr_channelizer_stats", "ssdr_set_wb_scopes", "ssdr_get_wb_scopes", "ssdr_wb_scope_lines", "ssdr_read_wb_scope",
-                       "ssdr_wb_scope_taps", "ssdr_wb_scope_stats")      # entry points a library named by SSDR_LIB_PATH (A/B builds only) may predate
+                       "ssdr_wb_scope_taps", "ssdr_wb_scope_stats", "ssdr_set_wb_scope_detectors", "ssdr_get_wb_scope_detectors",
+                       "ssdr_wb_scope_windows", "ssdr_read_wb_scope_windows")      # entry points a library named by SSDR_LIB_PATH (A/B builds only) may predate
 
 
 def _load():

@@ -319,6 +319,12 @@ struct ssdr_ctx {
     uint32_t chz_launches = 0;
     // wideband scopes (ssdr_set_wb_scopes): device memory at the first scope; with none set nothing is launched
     std::vector<ssdr_wb_scope> h_ws;                    // the list as set
+    std::vector<uint32_t> h_ws_det;                     // the detectors, parallel to it (ssdr_set_wb_scope_detectors; a new list: all SAMPLE)
+    std::vector<uint32_t> ws_run_wlog;                  // log2 W of every scope in the last run
+    bool ws_win_valid = false;                          // that run ended on a line end and the rings still hold it (ssdr_read_wb_scope_windows)
+    uint64_t ws_run_end = 0;                            // the absolute wide index the last run ended at
+    uint32_t *d_wd_win = nullptr;                       // [SSDR_WB_DET_ROWS][1024] a detector pass's window outputs
+    float *d_wd_part = nullptr;                         // [SSDR_WB_DET_ROWS / 2][1024] its partial power rows
     std::vector<uint32_t> h_ws_streams;                 // the streams that have a scope, ascending: ring s of d_ws_hist follows h_ws_streams[s]
     bool ws_dirty = false;                              // the device list (slots, NCO steps) is to be uploaded before the next run
     bool ws_run_valid = false;                          // there has been an ssdr_push_wideband with the list as it is
@@ -364,6 +370,7 @@ static void free_owned(ssdr_ctx *c)
         c->d_sub_consts, c->d_sub_taps, c->d_sub_parent, c->d_sub_play, c->d_sub_play_out,                            // ... state, constants, play_buffer
         c->d_chz_taps, c->d_chz_hist, c->d_chz_in,                                                                    // wideband channeliser
         c->d_ws_taps, c->d_ws_scopes, c->d_ws_slot_stream, c->d_ws_hist, c->d_ws_out, c->d_ws_lines, c->d_ws_acc, c->d_ws_consts,   // wideband scopes
+        c->d_wd_win, c->d_wd_part,                                                                                    // ... their detectors' scratch
     };
     for (void *p : owned)
         if (p) (void)hipFree(p);
@@ -3599,9 +3606,53 @@ static int ws_make_taps(uint32_t z, float *out)
 static int ws_clear(ssdr_ctx *c)
 {
     c->h_ws.clear();
+    c->h_ws_det.clear();
     c->h_ws_streams.clear();
     c->ws_run_valid = false;
+    c->ws_win_valid = false;
     return release(c, c->d_ws_hist);
+}
+// log2 of W = max(1, min(T, SSDR_WB_SCOPE_SPAN) / (1024 Z)) at the ctx's hop, D and O: everything is a power of two
+static uint32_t ws_windows_log(const ssdr_ctx *c, uint32_t zoom)
+{
+    const uint64_t T = (uint64_t)c->hop * c->decim * (SSDR_CHAN_BRANCHES / c->chz_over);
+    const uint64_t S = std::min<uint64_t>(T, SSDR_WB_SCOPE_SPAN), per = (uint64_t)SSDR_NFFT << zoom;
+    uint32_t lg = 0;
+    while ((per << (lg + 1)) <= S) lg++;
+    return lg;
+}
+static int ws_det_scratch(ssdr_ctx *c)
+{
+    static_assert((size_t)SSDR_WB_DET_ROWS * SSDR_NFFT * 4 + (size_t)(SSDR_WB_DET_ROWS / 2) * SSDR_NFFT * 4 <= SSDR_WB_DET_SCRATCH, "the header's bound");
+    if (!c->d_wd_win) HIP_TRY(hipMalloc(&c->d_wd_win, (size_t)SSDR_WB_DET_ROWS * SSDR_NFFT * 4));
+    if (!c->d_wd_part) HIP_TRY(hipMalloc(&c->d_wd_part, (size_t)(SSDR_WB_DET_ROWS / 2) * SSDR_NFFT * sizeof(float)));
+    return SSDR_OK;
+}
+// The detector passes of a run: per (zoom, detector) with W > 1 the scopes in list order, their (scope, line) items cut into passes of
+// at most SSDR_WB_DET_ROWS windows; the passes rewrite those items' rows of d_ws_lines behind the shipped path (stream order)
+static int ws_det_passes(ssdr_ctx *c, const SsdrWbScopeArgs &a)
+{
+    for (uint32_t z = 0; z <= SSDR_WB_SCOPE_ZOOM_MAX; z++) {
+        const uint32_t w_log = ws_windows_log(c, z);
+        if (!w_log) continue;
+        for (uint32_t det = SSDR_WB_DET_AVERAGE; det <= SSDR_WB_DET_MIN; det++) {
+            SsdrWbDetArgs d = {};
+            d.s = a;
+            for (uint32_t j = 0; j < (uint32_t)c->h_ws.size(); j++)
+                if (c->h_ws[j].zoom == z && c->h_ws_det[j] == det) d.list[d.n_list++] = (uint8_t)j;
+            if (!d.n_list) continue;
+            d.zoom = z; d.det = det; d.w_log = w_log; d.c_log = std::min(w_log, 3u);
+            d.win = c->d_wd_win; d.part = c->d_wd_part; d.lines = c->d_ws_lines;
+            d.win_tab = c->d_win; d.tw_stage = c->d_tw; d.lut = c->d_lut;
+            const uint32_t items = d.n_list * a.n_lines, per_pass = SSDR_WB_DET_ROWS >> w_log;
+            for (d.item0 = 0; d.item0 < items; d.item0 += per_pass) {
+                d.n_items = std::min(per_pass, items - d.item0);
+                HIP_TRY(ssdr_launch_wb_scope_win(d, c->stream));
+                HIP_TRY(ssdr_launch_wb_scope_det(d, c->stream));
+            }
+        }
+    }
+    return SSDR_OK;
 }
 // The scopes' stage of one ssdr_push_wideband, on the main stream behind the filter bank: `in` the call's wide samples, n0 the output
 // index before the call.  Timed as one stage with its own event pair; not an SSDR_K_* slot.
@@ -3613,6 +3664,9 @@ static int ws_stage(ssdr_ctx *c, const uint32_t *in, uint64_t in_stride, uint32_
     const uint64_t per_line = (uint64_t)c->hop * c->decim;              // output instants between lines
     const uint32_t lines = (uint32_t)((n0 + n_out) / per_line - n0 / per_line);
     c->ws_run_valid = false;
+    c->ws_win_valid = false;
+    const bool any_det = std::any_of(c->h_ws_det.begin(), c->h_ws_det.end(), [](uint32_t v) { return v != SSDR_WB_DET_SAMPLE; });
+    if (any_det) SSDR_TRY(ws_det_scratch(c));
     if (c->ws_dirty) {
         std::vector<SsdrWbScope> dev(ns);
         for (uint32_t j = 0; j < ns; j++) {
@@ -3665,6 +3719,7 @@ static int ws_stage(ssdr_ctx *c, const uint32_t *in, uint64_t in_stride, uint32_
         if (lines) {
             HIP_TRY(ssdr_launch_wb_scope(a, c->stream));
             HIP_TRY(ssdr_launch_wf(w, grid, c->stream));
+            if (any_det) SSDR_TRY(ws_det_passes(c, a));
         }
         HIP_TRY(ssdr_launch_wb_scope_hist(a, c->stream));
         return SSDR_OK;
@@ -3672,6 +3727,10 @@ static int ws_stage(ssdr_ctx *c, const uint32_t *in, uint64_t in_stride, uint32_
     c->ws_launches++;
     c->ws_run_lines = lines;
     c->ws_run_valid = true;
+    c->ws_run_wlog.resize(ns);
+    for (uint32_t j = 0; j < ns; j++) c->ws_run_wlog[j] = ws_windows_log(c, c->h_ws[j].zoom);
+    c->ws_run_end = (n0 + n_out) * step;
+    c->ws_win_valid = (n0 + n_out) % per_line == 0;
     return SSDR_OK;
 }
 
@@ -3728,6 +3787,7 @@ int ssdr_channelizer_reset(ssdr_ctx *c) SSDR_GUARD
     HIP_TRY(hipSetDevice(c->device));
     HIP_TRY(hipMemsetAsync(c->d_chz_hist, 0, (size_t)c->chz_streams * c->chz_p * SSDR_CHAN_BRANCHES * 4, c->stream));
     if (c->d_ws_hist) HIP_TRY(hipMemsetAsync(c->d_ws_hist, 0, c->h_ws_streams.size() * SSDR_WB_SCOPE_HIST * 4, c->stream));   // the scopes' list stays
+    c->ws_win_valid = false;
     c->chz_out_index = 0;
     return SSDR_OK;
 } SSDR_UNGUARD
@@ -3837,9 +3897,65 @@ int ssdr_set_wb_scopes(ssdr_ctx *c, const ssdr_wb_scope *scopes, uint32_t count)
         c->h_ws_streams.swap(streams);
     }
     c->h_ws.assign(scopes, scopes + count);
+    c->h_ws_det.assign(count, SSDR_WB_DET_SAMPLE);
     c->ws_dirty = true;
     c->ws_run_valid = false;
+    c->ws_win_valid = false;
     return SSDR_OK;
+} SSDR_UNGUARD
+
+int ssdr_set_wb_scope_detectors(ssdr_ctx *c, const uint32_t *det, uint32_t count) SSDR_GUARD
+{
+    if (!c) return SSDR_EINVAL;
+    if (!c->chz_streams) return SSDR_ESTATE;
+    if (count != c->h_ws.size() || (count && !det)) return SSDR_EINVAL;
+    for (uint32_t i = 0; i < count; i++)
+        if (det[i] > SSDR_WB_DET_MIN) return SSDR_EINVAL;
+    c->h_ws_det.assign(det, det + count);
+    c->ws_run_valid = false;
+    c->ws_win_valid = false;
+    return SSDR_OK;
+} SSDR_UNGUARD
+
+int ssdr_get_wb_scope_detectors(ssdr_ctx *c, uint32_t *det, uint32_t *count) SSDR_GUARD
+{
+    if (!c || !count) return SSDR_EINVAL;
+    *count = (uint32_t)c->h_ws_det.size();
+    if (det) std::copy(c->h_ws_det.begin(), c->h_ws_det.end(), det);
+    return SSDR_OK;
+} SSDR_UNGUARD
+
+int ssdr_wb_scope_windows(ssdr_ctx *c, uint32_t index, uint32_t *windows) SSDR_GUARD
+{
+    if (!c || !windows || index >= c->h_ws.size()) return SSDR_EINVAL;
+    *windows = 1u << ws_windows_log(c, c->h_ws[index].zoom);
+    return SSDR_OK;
+} SSDR_UNGUARD
+
+int ssdr_read_wb_scope_windows(ssdr_ctx *c, uint32_t index, int16_t *iq_out, uint32_t *windows) SSDR_GUARD
+{
+    if (!c) return SSDR_EINVAL;
+    if (c->h_ws.empty() || !c->ws_run_valid || !c->ws_win_valid || !c->ws_run_lines) return SSDR_ESTATE;
+    if (index >= c->h_ws.size()) return SSDR_EINVAL;
+    const uint32_t w_log = c->ws_run_wlog[index];
+    if (windows) *windows = 1u << w_log;
+    if (!iq_out) return SSDR_OK;
+    HIP_TRY(hipSetDevice(c->device));
+    SSDR_TRY(ws_det_scratch(c));
+    // the device list is still that run's (it is uploaded by the next one); every window ends at or before the ring's newest sample
+    SsdrWbDetArgs d = {};
+    d.s.in = c->d_ws_hist; d.s.in_stride = 0; d.s.n_in = 0;      // (never read: rel < 0 everywhere)
+    d.s.scopes = c->d_ws_scopes; d.s.n_scopes = (uint32_t)c->h_ws.size(); d.s.n_lines = 1;
+    d.s.i0 = c->ws_run_end;
+    d.s.hist_pos = (uint32_t)(d.s.i0 % SSDR_WB_SCOPE_HIST);
+    d.s.first_end = 0; d.s.period = 0;
+    d.s.taps = c->d_ws_taps; d.s.hist = c->d_ws_hist;
+    d.list[0] = (uint8_t)index; d.n_list = 1;
+    d.zoom = c->h_ws[index].zoom; d.det = SSDR_WB_DET_PEAK; d.w_log = w_log; d.c_log = std::min(w_log, 3u);
+    d.item0 = 0; d.n_items = 1;
+    d.win = c->d_wd_win;
+    HIP_TRY(ssdr_launch_wb_scope_win(d, c->stream));
+    return copy_out(c, iq_out, c->d_wd_win, ((size_t)SSDR_NFFT << w_log) * 4, 0, kSyncHost);
 } SSDR_UNGUARD
 
 int ssdr_get_wb_scopes(ssdr_ctx *c, ssdr_wb_scope *scopes, uint32_t *count) SSDR_GUARD

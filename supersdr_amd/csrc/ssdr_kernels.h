@@ -267,7 +267,26 @@ struct SsdrWbScopeArgs {
     const uint32_t *slot_stream;             // [n_slots] the stream each ring follows (history kernel)
     uint32_t n_slots;
 };
+// scope detectors (ssdr_wb_scope_det.hip, ssdr_set_wb_scope_detectors): one PASS is the scopes of one zoom and one detector, items
+// (k, line) = item0 .. item0 + n_items - 1 of [n_list][s.n_lines] (k-major), each with W = 2^w_log windows; three kernels per pass:
+// the windows' DDC (ssdr_wb_scope.hip) -> win, a chain of 2^c_log consecutive windows per half-wave -> part, the tree and the byte
+#define SSDR_WB_DET_ROWS 8192u               // windows a pass holds at once: win is 32 MiB, part at most 16 MiB (chains of >= 2)
+struct SsdrWbDetArgs {
+    SsdrWbScopeArgs s;                       // the call (s.out is not used)
+    uint8_t list[SSDR_WB_SCOPES_MAX];        // [n_list] the scopes of the pass, in list order
+    uint32_t n_list, zoom, det;              // SSDR_WB_DET_AVERAGE / PEAK / MIN
+    uint32_t w_log, c_log;                   // W = 2^w_log >= 2; chain length 2^c_log = min(W, 8)
+    uint32_t item0, n_items;                 // n_items * W <= SSDR_WB_DET_ROWS
+    uint32_t *win;                           // [n_items][W][1024] I | Q << 16, window 0 the newest
+    float *part;                             // [n_items][W >> c_log][1024] combined scaled powers, bin order
+    int16_t *lines;                          // [s.n_scopes][s.n_lines][1024] the stage's lines: the pass rewrites its items' rows
+    const float *win_tab;                    // [513], [992], [SSDR_LUT_N]: the waterfall stage's tables
+    const float2 *tw_stage;
+    const uint32_t *lut;
+};
 hipError_t ssdr_launch_wb_scope(const SsdrWbScopeArgs &a, hipStream_t stream);
+hipError_t ssdr_launch_wb_scope_win(const SsdrWbDetArgs &d, hipStream_t stream);
+hipError_t ssdr_launch_wb_scope_det(const SsdrWbDetArgs &d, hipStream_t stream);      // the chains, then the tree and the quantiser
 hipError_t ssdr_launch_wb_scope_hist(const SsdrWbScopeArgs &a, hipStream_t stream);
 struct SsdrFusedArgs { SsdrWfArgs wf; SsdrAudioArgs au; uint32_t *ticket; uint32_t ticket_base; };
 // ticket: ssdr_chain_ws_kernel's pair counter; it stands at ticket_base at launch and is never reset: every trio draws its pairs and one ticket

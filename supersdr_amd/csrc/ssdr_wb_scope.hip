@@ -38,6 +38,10 @@
 // the call's last min(n_in, H) samples to their slots (16-byte pieces: a call begins and ends on a multiple of 512 * 512 samples
 // and H is a multiple of 4, so a piece never straddles the wrap).
 // No atomics, no scratch, vector stores only (profiles/scope_isa_spills.txt).
+// Detectors (ssdr_wb_scope_det.hip) need the same 1024 outputs in front of ends that lie before the line's: the body is the device
+// function sc_outputs, ssdr_wb_scope_kernel calls it for (scope, line) as before (its code did not change: profiles/
+// scope_det_isa_spills.txt) and ssdr_wb_scope_win_kernel for (item, window) -- an end at or before the call's first sample reads the ring
+// alone (rel < 0 everywhere; the oldest sample of the oldest window lies SSDR_WB_SCOPE_SPAN + 32 Z - 1 < H before the line's end).
 #include "ssdr_math.h"
 #include "ssdr_kernels.h"
 
@@ -60,12 +64,12 @@ SSDR_DEV void sc_step(float (&ar)[32], float (&ai)[32], const float (&ht)[32], f
     }
 }
 
-__global__ __launch_bounds__(SC_BLOCK) void ssdr_wb_scope_kernel(SsdrWbScopeArgs a)
+// the 1024 outputs in front of the end e_rel (relative to the call's first sample; <= 0 for a window that ends in the ring) of one
+// scope into row `item` of out_rows: the whole of steps 1 .. 3 of the order.  Both kernels below are this body and nothing else.
+template <typename End>
+SSDR_DEV void sc_outputs(const SsdrWbScopeArgs &a, const uint32_t scope, End end_of, uint32_t *out_rows, const uint32_t item, float2 *s_part)
 {
-    __shared__ float2 s_part[SC_PART];
     const uint32_t t = threadIdx.x;
-    const uint32_t item = blockIdx.x;                                                // (scope, line): the long axis of the grid
-    const uint32_t scope = item / a.n_lines, line = item - scope * a.n_lines;
     const SsdrWbScope sc = a.scopes[scope];
     const uint32_t z = sc.zoom, Z = 1u << z;
     const uint32_t ch_log = z <= 4u ? 5u : 7u, CH = 1u << ch_log, n_chunks = SSDR_NFFT >> ch_log;
@@ -84,7 +88,7 @@ __global__ __launch_bounds__(SC_BLOCK) void ssdr_wb_scope_kernel(SsdrWbScopeArgs
     const uint32_t *in = a.in + (uint64_t)sc.stream * a.in_stride;
     const uint32_t *hist = a.hist + (uint64_t)sc.slot * SSDR_WB_SCOPE_HIST;
     const float *taps = a.taps + 32u * (Z - 1u);                                     // the table of this Z: 32 Z floats, the last one zero
-    const int32_t e_rel = (int32_t)(a.first_end + line * a.period);                  // the line's end, relative to the call's first sample: 1 .. n_in
+    const int32_t e_rel = end_of();                                                  // the end, relative to the call's first sample
     const uint32_t i0 = (uint32_t)a.i0;                                              // the phase is 2^32-periodic in the absolute index
 
     for (uint32_t j = 0; j < n_j; j++) {
@@ -127,7 +131,7 @@ __global__ __launch_bounds__(SC_BLOCK) void ssdr_wb_scope_kernel(SsdrWbScopeArgs
     }
     __syncthreads();
     // step 3 of the order, rounding, and the line's dwords: consecutive threads, consecutive outputs
-    uint32_t *out = a.out + (uint64_t)item * SSDR_NFFT + blockIdx.y * outs;
+    uint32_t *out = out_rows + (uint64_t)item * SSDR_NFFT + blockIdx.y * outs;
     for (uint32_t o = t; o < outs; o += SC_BLOCK) {
         const auto wave_sum = [&](uint32_t w) {                                       // t_w: the sum over j ascending
             float2 acc = s_part[w * outs + o];
@@ -146,6 +150,28 @@ __global__ __launch_bounds__(SC_BLOCK) void ssdr_wb_scope_kernel(SsdrWbScopeArgs
         const int ir = __float2int_rn(y.x), ii = __float2int_rn(y.y);                // saturating conversions, then saturating pack
         out[o] = __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_pk_i16(ir, ii));
     }
+}
+
+__global__ __launch_bounds__(SC_BLOCK) void ssdr_wb_scope_kernel(SsdrWbScopeArgs a)
+{
+    __shared__ float2 s_part[SC_PART];
+    const uint32_t item = blockIdx.x;                                                // (scope, line): the long axis of the grid
+    const uint32_t scope = item / a.n_lines, line = item - scope * a.n_lines;
+    // the line's end, relative to the call's first sample: 1 .. n_in
+    sc_outputs(a, scope, [&]() { return (int32_t)(a.first_end + line * a.period); }, a.out, item, s_part);
+}
+
+// the window axis (ssdr_wb_scope_det.hip has the detector): row = (item of the pass, window v), v = 0 the newest; window v of a
+// line ends 1024 Z v samples before the line does -- for older windows before the call's first sample, in the ring
+__global__ __launch_bounds__(SC_BLOCK) void ssdr_wb_scope_win_kernel(SsdrWbDetArgs d)
+{
+    __shared__ float2 s_part[SC_PART];
+    const uint32_t row = blockIdx.x;
+    const uint32_t it = d.item0 + (row >> d.w_log), v = row & ((1u << d.w_log) - 1u);
+    const uint32_t k = it / d.s.n_lines, line = it - k * d.s.n_lines;
+    const uint32_t scope = d.list[k];
+    if (d.s.scopes[scope].zoom != d.zoom) return;                                    // (uniform; the host builds a pass from one zoom)
+    sc_outputs(d.s, scope, [&]() { return (int32_t)(d.s.first_end + line * d.s.period) - (int32_t)(v << (10u + d.zoom)); }, d.win, row, s_part);
 }
 
 // the call's last min(n_in, H) samples of every scoped stream into its ring: the second launch (see the header)
@@ -176,6 +202,24 @@ hipError_t ssdr_launch_wb_scope(const SsdrWbScopeArgs &a, hipStream_t stream)
         if (n_chunks / per_wg > wgs) wgs = n_chunks / per_wg;
     }
     hipLaunchKernelGGL(ssdr_wb_scope_kernel, dim3(a.n_scopes * a.n_lines, wgs), dim3(SC_BLOCK), 0, stream, a);
+    return hipGetLastError();
+}
+
+// one pass of the detectors' DDC: every window of the pass's items (one zoom: the grid's second axis is exact)
+hipError_t ssdr_launch_wb_scope_win(const SsdrWbDetArgs &d, hipStream_t stream)
+{
+    const uint32_t z = d.zoom;
+    if (!d.n_items) return hipSuccess;
+    if (z > SSDR_WB_SCOPE_ZOOM_MAX || d.w_log + 10u + z > 20u || !d.n_list || d.n_list > SSDR_WB_SCOPES_MAX || !d.s.n_lines ||
+        (uint64_t)d.item0 + d.n_items > (uint64_t)d.n_list * d.s.n_lines || ((uint64_t)d.n_items << d.w_log) > SSDR_WB_DET_ROWS ||
+        d.s.first_end > d.s.n_in || (uint64_t)d.s.first_end + (uint64_t)(d.s.n_lines - 1u) * d.s.period > d.s.n_in ||
+        d.s.hist_pos >= SSDR_WB_SCOPE_HIST || !d.s.hist || !d.win)
+        return hipErrorInvalidValue;
+    for (uint32_t k = 0; k < d.n_list; k++)
+        if (d.list[k] >= d.s.n_scopes) return hipErrorInvalidValue;
+    const uint32_t ch_log = z <= 4u ? 5u : 7u, zw_log = z < 8u ? z : 8u;
+    const uint32_t n_chunks = SSDR_NFFT >> ch_log, per_wg = (256u >> zw_log) < n_chunks ? (256u >> zw_log) : n_chunks;
+    hipLaunchKernelGGL(ssdr_wb_scope_win_kernel, dim3(d.n_items << d.w_log, n_chunks / per_wg), dim3(SC_BLOCK), 0, stream, d);
     return hipGetLastError();
 }
 

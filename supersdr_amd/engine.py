@@ -622,6 +622,38 @@ class SsdrEngine:
             check(lib.ssdr_read_wb_scope(self._ctx, int(index), out.ctypes.data, C.byref(n)), "ssdr_read_wb_scope")
         return out
 
+    def set_wb_scope_detectors(self, detectors):
+        """The scopes' detectors, one per scope in list order: 0 sample, 1 average, 2 peak, 3 min (L.WB_DET_*) over the windows of
+        the line period.  set_wb_scopes puts every scope back on sample, so set them again behind every list change.  A length
+        other than the list's or a value above 3 raises SsdrError (SSDR_EINVAL) and nothing changes."""
+        vals = [int(v) for v in detectors]
+        if any(not 0 <= v < 2 ** 32 for v in vals):
+            raise ValueError("scope detectors %r: out of range" % (detectors,))
+        arr = (C.c_uint32 * max(len(vals), 1))(*vals)
+        check(lib.ssdr_set_wb_scope_detectors(self._ctx, arr if vals else None, len(vals)), "ssdr_set_wb_scope_detectors")
+
+    def wb_scope_detectors(self):
+        """-> [detector, ...] in list order"""
+        n = C.c_uint32(0)
+        arr = (C.c_uint32 * L.WB_SCOPES_MAX)()
+        check(lib.ssdr_get_wb_scope_detectors(self._ctx, arr, C.byref(n)), "ssdr_get_wb_scope_detectors")
+        return list(arr[:n.value])
+
+    def wb_scope_windows(self, index):
+        """-> W: the windows a line of scope `index` has at the current hop, D and O"""
+        n = C.c_uint32(0)
+        check(lib.ssdr_wb_scope_windows(self._ctx, int(index), C.byref(n)), "ssdr_wb_scope_windows")
+        return n.value
+
+    def read_wb_scope_windows(self, index):
+        """-> int16 [W, 1024, 2]: the stored outputs of every window of the last line of the last push_wideband, newest first
+        (tests; valid when that push ended on a line end)"""
+        n = C.c_uint32(0)
+        check(lib.ssdr_read_wb_scope_windows(self._ctx, int(index), None, C.byref(n)), "ssdr_read_wb_scope_windows")
+        out = np.empty((n.value, L.NFFT, 2), np.int16)
+        check(lib.ssdr_read_wb_scope_windows(self._ctx, int(index), out.ctypes.data, C.byref(n)), "ssdr_read_wb_scope_windows")
+        return out
+
     def wb_scope_stats(self, reset=False):
         """-> (total_ms, runs) of the scope stage since the last reset (the time only with set_profiling on)"""
         ms, n = C.c_float(), C.c_uint32()

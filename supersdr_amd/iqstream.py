@@ -143,6 +143,17 @@ class Channelizer:
             raise ValueError("zoom %r outside 0..%d" % (zoom, self.SCOPE_ZOOM_MAX))
         return float(rate) / (1 << int(zoom))
 
+    SCOPE_SPAN = 1024 * 1024                        # SSDR_WB_SCOPE_SPAN: the wide samples of a line period a detector looks at
+
+    def scope_windows(self, zoom, hop=1024, D=1):
+        """W: the windows (of 1024 outputs, not overlapping, ending at the line's end) a scope detector combines per line, for the
+        ctx's hop (1024 or 512) and decimation D: max(1, min(hop * D * step, SCOPE_SPAN) / (1024 * 2^zoom)) -- ssdr_wb_scope_windows"""
+        if not 0 <= int(zoom) <= self.SCOPE_ZOOM_MAX:
+            raise ValueError("zoom %r outside 0..%d" % (zoom, self.SCOPE_ZOOM_MAX))
+        if int(hop) not in (512, 1024) or int(D) not in (1, 2, 4):
+            raise ValueError("hop %r / D %r" % (hop, D))
+        return max(1, min(int(hop) * int(D) * self.step, self.SCOPE_SPAN) // (1024 << int(zoom)))
+
     def scope_for(self, lo_hz, hi_hz, rate):
         """-> (zoom, offset_hz): the deepest zoom whose span still covers [lo_hz, hi_hz] (offsets from the wide stream's centre), centred
         on the interval but moved inwards where the span would reach past the band's edge"""

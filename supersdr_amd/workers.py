@@ -42,6 +42,30 @@ from . import _lib as L
 from ._lib import Db2colChan, PlayChan
 from .engine import SsdrEngine, check_deemphasis, check_noise_blanker, check_squelch, default_params
 
+# the wideband scopes' detectors (ssdr_set_wb_scope_detectors): name -> SSDR_WB_DET_*
+SCOPE_DETECTORS = {"sample": L.WB_DET_SAMPLE, "average": L.WB_DET_AVERAGE, "peak": L.WB_DET_PEAK, "min": L.WB_DET_MIN}
+# "SET interp=n" on a scope's stream: the Kiwi's n % 10 (0 max, 1 min, 2 last, 3 drop, 4 cma) -> the detector.  The Kiwi applies these
+# across the FFT bins of one pixel; here they act across the windows of a line period, and the mapping is this project's
+_KIWI_INTERP = {0: "peak", 1: "min", 2: "sample", 3: "sample", 4: "average"}
+
+
+def check_scope_detector(name):
+    """-> the name, or ValueError"""
+    if not isinstance(name, str) or name not in SCOPE_DETECTORS:
+        raise ValueError("scope detector %r: one of %s" % (name, ", ".join(sorted(SCOPE_DETECTORS))))
+    return name
+
+
+def kiwi_interp_detector(value):
+    """the detector of "SET interp=<value>": value % 10 names it, the tens digit (CIC compensation) is ignored"""
+    try:
+        n = int(value)
+    except (TypeError, ValueError):
+        raise ValueError("SET interp=%r: not a number" % (value,))
+    if n < 0 or n % 10 not in _KIWI_INTERP:
+        raise ValueError("SET interp=%r: %d is none of the Kiwi's modes 0 (max), 1 (min), 2 (last), 3 (drop), 4 (cma)" % (value, n % 10 if n >= 0 else n))
+    return _KIWI_INTERP[n % 10]
+
 IQ_SPAN_KHZ = L.RATE / 1000.0          # what one channel's GPU waterfall covers: the IQ band around its centre (12 kHz; hub.iq_span_khz)
 
 
@@ -300,6 +324,7 @@ class IQHub:
         self.sub_queue = {}                          # sid -> bounded queue of Frame
         self.sub_clients = {}                        # sid -> the kiwi_sound on it (volume / balance for its play_buffer), or None
         self._scopes = {}                            # sid -> (stream, zoom, offset_hz): the wideband scopes (open_scope), the engine's list in sid order
+        self._scope_det = {}                         # sid -> "sample" | "average" | "peak" | "min": the scopes' detectors (set_scope_detector)
         self._next_scope = 1
         self.scope_queue = {}                        # sid -> bounded queue of WfLine (N = 1), drop-oldest
         self.scope_clients = {}                      # sid -> the kiwi_waterfall on it (its display state for ssdr_db2col_line), or None
@@ -641,20 +666,54 @@ class IQHub:
         if not hasattr(self.engine, "set_wb_scopes"):
             raise ValueError("this engine has no wideband scopes (set_wb_scopes)")
 
-    def _set_scopes(self, new):
-        """the whole list to the engine, in sid order; refused by the library: the old list stays"""
+    def _set_scopes(self, new, det=None):
+        """the whole list to the engine, in sid order, and then the detectors (the library puts a new list on sample; all on sample:
+        nothing to send); refused by the library: the old list and the old detectors stay"""
+        det = {sid: (self._scope_det if det is None else det).get(sid, "sample") for sid in new}
+        order = sorted(new)
+        codes = [SCOPE_DETECTORS[det[sid]] for sid in order]
+        if any(codes) and not hasattr(self.engine, "set_wb_scope_detectors"):
+            raise ValueError("this engine has no scope detectors (set_wb_scope_detectors)")
         try:
-            self.engine.set_wb_scopes([new[sid] for sid in sorted(new)])
+            self.engine.set_wb_scopes([new[sid] for sid in order])
         except L.SsdrError as e:
             raise ValueError("wideband scopes refused: %s" % e)
-        self._scopes = new
+        try:
+            if any(codes):
+                self.engine.set_wb_scope_detectors(codes)
+        except L.SsdrError as e:                     # back to what was: the list, then its detectors
+            old = sorted(self._scopes)
+            self.engine.set_wb_scopes([self._scopes[sid] for sid in old])
+            if any(self._scope_det.get(sid, "sample") != "sample" for sid in old):
+                self.engine.set_wb_scope_detectors([SCOPE_DETECTORS[self._scope_det.get(sid, "sample")] for sid in old])
+            raise ValueError("scope detectors refused: %s" % e)
+        self._scopes, self._scope_det = new, det
 
-    def open_scope(self, stream, zoom, offset_hz=0.0):
+    def scope_detector(self, sid):
+        """-> "sample" | "average" | "peak" | "min" of scope `sid`"""
+        with self._lock:
+            self._scopes[int(sid)]                   # KeyError: no such scope
+            return self._scope_det.get(int(sid), "sample")
+
+    def set_scope_detector(self, sid, detector):
+        """The detector of scope `sid` over the windows of a line period (ssdr_set_wb_scope_detectors): "sample" (the last 1024 outputs
+        before the line's end: a snapshot), "average", "peak" or "min" of the power over every window of the period.  Nobody is
+        restarted.  Another name is a ValueError before the engine is touched."""
+        sid, name = int(sid), check_scope_detector(detector)
+        with self._lock:
+            self._scopes[sid]                        # KeyError: no such scope
+            det = dict(self._scope_det)
+            det[sid] = name
+            self._set_scopes(dict(self._scopes), det)
+
+    def open_scope(self, stream, zoom, offset_hz=0.0, detector="sample"):
         """A scope on wide stream `stream`: the wide rate / 2^zoom around offset_hz (Hz from the stream's centre), zoom 0 .. 10.  -> sid:
         scope_queue[sid] receives a WfLine (N = 1) per line of every feed_wideband -- as many a second as a receiver's un-zoomed
         waterfall, at every zoom; retune_scope(sid, zoom, offset_hz) moves it, close_scope(sid) ends it.  Nobody else is restarted,
-        and a scope on a stream that already has one shows the stream's past at once.  ValueError on a pipelined or wire hub and
+        and a scope on a stream that already has one shows the stream's past at once.  detector: "sample" (a snapshot at the line's
+        end), "average", "peak" or "min" over every window of the line period (set_scope_detector).  ValueError on a pipelined or wire hub and
         without a channeliser (before the engine is touched), beyond 64 scopes and for what the library refuses; then nothing changes."""
+        name = check_scope_detector(detector)                # (before the engine is touched)
         self._require_scopes()
         row = (int(stream), int(zoom), float(offset_hz))
         with self._lock:
@@ -663,18 +722,25 @@ class IQHub:
             sid = self._next_scope
             new = dict(self._scopes)
             new[sid] = row
-            self._set_scopes(new)
+            det = dict(self._scope_det)
+            det[sid] = name
+            self._set_scopes(new, det)
             self._next_scope += 1
             self.scope_queue[sid] = queue.Queue(2 * self._max_queue)
             self.scope_clients[sid] = None
             return sid
 
-    def retune_scope(self, sid, zoom, offset_hz):
+    def retune_scope(self, sid, zoom, offset_hz, detector=None):
+        """moves scope `sid`; detector None keeps its detector"""
         sid = int(sid)
+        name = None if detector is None else check_scope_detector(detector)
         with self._lock:
             new = dict(self._scopes)
             new[sid] = (self._scopes[sid][0], int(zoom), float(offset_hz))       # KeyError: no such scope
-            self._set_scopes(new)
+            det = dict(self._scope_det)
+            if name is not None:
+                det[sid] = name
+            self._set_scopes(new, det)
 
     def close_scope(self, sid):
         sid = int(sid)
@@ -683,7 +749,9 @@ class IQHub:
                 return                               # closing twice counts once
             new = dict(self._scopes)
             del new[sid]
-            self._set_scopes(new)
+            det = dict(self._scope_det)
+            det.pop(sid, None)
+            self._set_scopes(new, det)
             self.scope_queue.pop(sid, None)
             self.scope_clients.pop(sid, None)
 
@@ -918,6 +986,7 @@ class IQHub:
                 self.engine.set_channelizer(self.n_ch // channelizer.BRANCHES, channelizer.oversample, channelizer.taps)
             self.channelizer = channelizer
             self._scopes = {}                        # the library emptied its list: every scope is closed
+            self._scope_det = {}
             self.scope_queue.clear()
             self.scope_clients.clear()
 
@@ -1239,7 +1308,11 @@ class GpuStream:
     WaterfallSeams.set_iq_view / IQHub.set_wf_view, in the band's own terms.  Nor does it move a wideband scope (scope=sid: the
     stream carries the lines of IQHub.open_scope's scope and closes it with the connection): a span of 30 MHz / 2^zoom is not the
     wide rate F / 2^z for a general F, so the two zoom ladders are not mapped onto each other; a scope is
-    moved in its own terms, by WaterfallSeams.set_scope / IQHub.retune_scope.  The last W/F stream of a channel to close takes the
+    moved in its own terms, by WaterfallSeams.set_scope / IQHub.retune_scope.  "SET interp=%d" on a scope's stream selects the scope's
+    detector (kiwi_interp_detector: n % 10 = 0 peak, 1 min, 4 average, 2 and 3 sample; the tens digit, the Kiwi's CIC compensation, is
+    ignored; another value raises ValueError), so the reference's own "SET interp=13" (kiwi_waterfall.start_stream) leaves a scope on
+    sample.  The Kiwi applies these modes across the FFT bins that fall into one pixel; here they act across the windows of a line
+    period -- the mapping is this project's.  On a stream that is no scope, interp stays ignored.  The last W/F stream of a channel to close takes the
     channel's view with it.  The rest (auth, keepalive, ...)
     has no meaning without a server and is accepted.  A modulation without a demodulator here, or a frequency outside
     the channel's IQ band, raises ValueError instead of being demodulated as something else.  "SET mod=iq" selects the
@@ -1304,6 +1377,9 @@ class GpuStream:
             if "compression" in kv and "mod" not in kv and "agc" not in kv and int(kv["compression"]) != 0:
                 raise ValueError("SET compression=1 on sub-receiver %d of channel %d: a sub-receiver's frames are not ADPCM-encoded"
                                  % (self.sub, self.channel))
+        if self.scope is not None and "interp" in kv:
+            self.hub.set_scope_detector(self.scope, kiwi_interp_detector(kv["interp"]))
+            return
         if "mod" in kv:
             self._retune(kv)
         elif "agc" in kv:
@@ -1563,6 +1639,12 @@ class WaterfallSeams:
             raise ValueError("set_scope needs a kiwi_waterfall opened on a wideband scope (scope=sid)")
         khz = self.iq_center_khz if khz is None else float(khz)
         self.hub.retune_scope(self.scope_id, zoom, (khz - self.iq_center_khz) * 1000.0)
+
+    def set_scope_detector(self, name):
+        """a worker on a wideband scope (scope=sid): "sample", "average", "peak" or "min" over the windows of a line period"""
+        if self.scope_id is None:
+            raise ValueError("set_scope_detector needs a kiwi_waterfall opened on a wideband scope (scope=sid)")
+        self.hub.set_scope_detector(self.scope_id, name)
 
     def set_iq_zoom_center(self, khz):
         """centre of this channel's zoomed waterfall (hub built with zoom > 1), an absolute frequency inside its IQ band"""

@@ -8,7 +8,10 @@ interleaved rounds.  Without it the package's own channeliser stage with no scop
 The arithmetic of a line is 1024 outputs x (32 Z - 1) taps x 2 components of multiply-add; `x_arith` is the stage's time over that
 at the chip's fp32 FMA rate (256 CUs x 128 lanes x 2.4 GHz).  Every shape is warmed up before it is timed; interleaved repeats;
 medians and ranges.
-    timeout -k 10 900 python tools/scope_probe.py [repeats] [steps] [--before-lib PATH] >> profiles/scope_probe.txt"""
+`--detector NAME` (average, peak, min) puts every scope of every shape on that detector (ssdr_set_wb_scope_detectors): the stage then
+also runs the detector passes (every window of the line period: W = 1024 >> z windows per line here, 1 at z = 10), `windows` and
+the arithmetic count them; without it the scopes are on sample, which is what the parent commit runs.
+    timeout -k 10 900 python tools/scope_probe.py [repeats] [steps] [--before-lib PATH] [--detector NAME] >> profiles/scope_probe.txt"""
 import ctypes as C
 import json
 import os
@@ -87,13 +90,15 @@ def stats(v):
 def main():
     argv = sys.argv[1:]
     before_path = argv[argv.index("--before-lib") + 1] if "--before-lib" in argv else None
-    args = [a for a in argv if not a.startswith("--") and a != before_path]
+    det_name = argv[argv.index("--detector") + 1] if "--detector" in argv else None
+    det = {None: 0, "sample": 0, "average": 1, "peak": 2, "min": 3}[det_name]
+    args = [a for a in argv if not a.startswith("--") and a != before_path and a != det_name]
     repeats = int(args[0]) if len(args) > 0 else 6
     steps = int(args[1]) if len(args) > 1 else 5
     head = os.path.join(bench.ROOT, ".ssdr_head")
     taps = Channelizer(O, P, gain=2.0).taps
     lines = FRAMES * 512 // 1024
-    rec = {"probe": "scope_probe", "streams": STREAMS, "channels": N_CH, "frames": FRAMES, "lines_per_scope": lines, "P": P, "O": O,
+    rec = {"probe": "scope_probe", "detector": det_name or "sample", "streams": STREAMS, "channels": N_CH, "frames": FRAMES, "lines_per_scope": lines, "P": P, "O": O,
            "repeats": repeats, "steps": steps, "csrc_sha256": bench.csrc_sha256(),
            "git_commit": open(head).read().strip() if os.path.exists(head) else None,
            "yardstick": "parent commit's channeliser stage" if before_path else "this library's channeliser stage, no scope set (no --before-lib)"}
@@ -122,6 +127,8 @@ def main():
                 t[k]["ms"].append(ms)
             else:
                 eng.set_wb_scopes(shapes[k])
+                if det and shapes[k]:
+                    eng.set_wb_scope_detectors([det] * len(shapes[k]))
                 ms, cms, wall = run_own(eng, wide, steps)
                 t[k]["ms"].append(ms)
                 t[k]["chan_ms"].append(cms)
@@ -137,8 +144,9 @@ def main():
         out = {"scopes": len(scopes), "scope_ms": stats(t[k]["ms"]), "chan_ms": stats(t[k]["chan_ms"]), "step_ms": stats(t[k]["step_ms"])}
         if scopes:
             z = scopes[0][1]
-            fma = len(scopes) * lines * 1024 * (32 * (1 << z) - 1) * 2
-            out.update({"zoom": z, "x_yardstick": round(med / yard, 3), "fma": fma, "arith_ms": round(fma / FMA_PER_S * 1e3, 5),
+            windows = Channelizer(O, P).scope_windows(z, 1024, 1) if det else 1
+            fma = len(scopes) * lines * (windows + (1 if windows > 1 else 0)) * 1024 * (32 * (1 << z) - 1) * 2   # (window 0 is computed twice)
+            out.update({"zoom": z, "windows": windows, "x_yardstick": round(med / yard, 3), "fma": fma, "arith_ms": round(fma / FMA_PER_S * 1e3, 5),
                         "x_arith": round(med / (fma / FMA_PER_S * 1e3), 1)})
         rec[k] = out
     print(json.dumps(rec))
