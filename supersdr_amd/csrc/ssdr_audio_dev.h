@@ -391,6 +391,23 @@ SSDR_DEV bool raw_clipped(const uint32_t (&rw)[8])
     return c;
 }
 
+SSDR_DEV bool raw_clipped1(uint32_t rw)
+{
+    const int lo = (int16_t)(rw & 0xFFFFu), hi = (int32_t)rw >> 16;
+    return lo >= 32767 || lo <= -32767 || hi >= 32767 || hi <= -32767;
+}
+// The same for a lane that holds the frame's samples 8l-4 .. 8l+3 (the fused kernel's delayed read, ssdr_wf.hip) and one of the
+// frame's last four, `last`: lane 0's first four belong to the frame before and do not count.
+SSDR_DEV bool raw_clipped_delayed(const uint32_t (&rw)[8], uint32_t last, int l)
+{
+    bool head = false, c = raw_clipped1(last);
+#pragma unroll
+    for (int j = 0; j < 4; j++) head |= raw_clipped1(rw[j]);
+#pragma unroll
+    for (int j = 4; j < 8; j++) c |= raw_clipped1(rw[j]);
+    return c | (head & (l != 0));
+}
+
 // ---- impulse noise blanker (ssdr_set_noise_blanker; the definition is tests/nb_ref.py) ----------------
 // Integer scans across the lanes, the SSDR_SCAN6 steps: an exact sum and an exact max, so any order gives the same value.
 SSDR_DEV uint32_t scan_add_u(uint32_t x)

@@ -179,13 +179,21 @@ __global__ __launch_bounds__(SSDR_WF_BLOCK, SSDR_WF_WAVES_PER_EU) void ssdr_fuse
 
         // The audio chain's carried state of both channels (wave-uniform: 14 words per channel) does not stay in registers
         // across the FFT, which needs nearly all of them: between two audio phases it rests in the pad column of the wave's
-        // transpose buffer (index 33 i + 32, i >= 16: written by neither the transpose nor the line staging).  Only the two per-lane
+        // transpose buffer (index 33 i + 32, i >= 17: written by neither the transpose nor the line staging).  Only the two per-lane
         // keepers (RSSI sum, flag of frame f mod 64) stay in registers.
         float rssi_sum[2] = {0.0f, 0.0f};
         uint32_t flag_keep[2] = {0u, 0u};
-        // (rows 16..31 of the pad column: the line staging reuses the first 2 KB of the buffer)
-        auto pad = [&](int c, int i) -> float & { return xch_wave[c * XCH_FLOATS + 33 * (i + 16) + 32]; };
-        constexpr int PAD_TAIL = HANG ? 10 : 2;            // rows: dc, agc_d, (HANG: agc_m[8],) the four tail powers
+        // (rows 17..30 of the pad column: the line staging reuses the first 2 KB of the buffer; from row 17 on a channel's cells lie within
+        // 1 KB and one address register reaches them all through the two-address DS forms' offset fields)
+        auto pad = [&](int c, int i) -> float & { return xch_wave[c * XCH_FLOATS + 33 * (i + 17) + 32]; };
+        constexpr int PAD_TAIL = HANG ? 10 : 2;            // rows: dc, agc_d, (HANG: agc_m[8],) the four tail samples
+        // The AM chain's 4-sample delay.  Hop 1024 (PARKED): the line is parked 16 bytes into its region, behind the four raw samples
+        // that precede it (the history's last four, later the previous line's), so a lane reads its samples 8l-4 .. 8l+3 of a frame
+        // straight out of the LDS; across the FFT those four rest, raw, in the pad column.  Hop 512: the older half-line is the
+        // waterfall side's tail, not the audio history -- there the lanes' own eight powers are shifted across lanes as before and
+        // the pad column holds the four carried POWERS.
+        constexpr bool PARKED = !HOP;
+        constexpr int PARK = PARKED ? 4 : 0;               // floats in front of the parked line
         if (lane < 2) {
             const uint32_t cc = min(2 * pair + (uint32_t)lane, a.n_ch - 1);
             const ssdr_chan_state st = u.state[cc];
@@ -196,8 +204,13 @@ __global__ __launch_bounds__(SSDR_WF_BLOCK, SSDR_WF_WAVES_PER_EU) void ssdr_fuse
                 for (int i = 0; i < 8; i++) pad(lane, 2 + i) = st.agc_m[i];
             }
             const uint4 t = *reinterpret_cast<const uint4 *>(u.hist + (size_t)cc * SSDR_HIST + SSDR_HIST - 4);
-            pad(lane, PAD_TAIL) = __uint_as_float(iq_power(t.x)); pad(lane, PAD_TAIL + 1) = __uint_as_float(iq_power(t.y));
-            pad(lane, PAD_TAIL + 2) = __uint_as_float(iq_power(t.z)); pad(lane, PAD_TAIL + 3) = __uint_as_float(iq_power(t.w));
+            if constexpr (PARKED) {
+                pad(lane, PAD_TAIL) = __uint_as_float(t.x); pad(lane, PAD_TAIL + 1) = __uint_as_float(t.y);
+                pad(lane, PAD_TAIL + 2) = __uint_as_float(t.z); pad(lane, PAD_TAIL + 3) = __uint_as_float(t.w);
+            } else {
+                pad(lane, PAD_TAIL) = __uint_as_float(iq_power(t.x)); pad(lane, PAD_TAIL + 1) = __uint_as_float(iq_power(t.y));
+                pad(lane, PAD_TAIL + 2) = __uint_as_float(iq_power(t.z)); pad(lane, PAD_TAIL + 3) = __uint_as_float(iq_power(t.w));
+            }
         }
         wave_lds_sync();
 
@@ -220,8 +233,22 @@ __global__ __launch_bounds__(SSDR_WF_BLOCK, SSDR_WF_WAVES_PER_EU) void ssdr_fuse
 #pragma unroll
                     for (int i = 0; i < 8; i++) hang[c].m[i] = pad(c, 2 + i);
                 }
+                if constexpr (!PARKED) {
 #pragma unroll
-                for (int i = 0; i < 4; i++) tail_q[c][i] = __float_as_uint(pad(c, PAD_TAIL + i));
+                    for (int i = 0; i < 4; i++) tail_q[c][i] = __float_as_uint(pad(c, PAD_TAIL + i));
+                }
+            }
+            if constexpr (PARKED) {
+                u32x4 b[2];                                    // the four samples in front of the line: from rest to the head of the region
+#pragma unroll
+                for (int c = 0; c < 2; c++)
+#pragma unroll
+                    for (int i = 0; i < 4; i++) b[c][i] = __float_as_uint(pad(c, PAD_TAIL + i));
+                wave_lds_sync();                               // (all of the resting place is read before anything is written)
+                if (lane == 0) {
+#pragma unroll
+                    for (int c = 0; c < 2; c++) *reinterpret_cast<u32x4 *>(qbuf + c * XCH_FLOATS) = b[c];
+                }
             }
             wave_lds_sync();
             // ---- audio, phase 1: the line's raw samples into the (still unused) transpose buffer, in natural order.  Nobody needs them
@@ -229,8 +256,11 @@ __global__ __launch_bounds__(SSDR_WF_BLOCK, SSDR_WF_WAVES_PER_EU) void ssdr_fuse
             // channel at a time (8 load and 8 LDS store instructions per line pair instead of 32 and 16).  The audio chain reads them back
             // eight consecutive samples per lane, the FFT takes them out of the LDS in its own layout afterwards: one read from HBM
             // (streaming), none from the L2, and no 32 registers held across the audio chain.
+            // The lane's places in the parked line are formed once per line: frames and channels differ in the DS instructions' offset fields.
+            const uint32_t lw = opaque(lane);
+            uint32_t *q_park = qbuf + PARK + 4 * lw;                 // 16 bytes per lane and store
+            const uint32_t *q_lane = q_park - PARK + 4 * lw, *q_last = qbuf + (lw & 3u);    // 8 samples per lane; one of a frame's last four
             {
-                const uint32_t lw = opaque(lane);
                 u32x4 t[2][4];
 #pragma unroll
                 for (int c = 0; c < 2; c++) {
@@ -253,7 +283,7 @@ __global__ __launch_bounds__(SSDR_WF_BLOCK, SSDR_WF_WAVES_PER_EU) void ssdr_fuse
 #pragma unroll
                 for (int c = 0; c < 2; c++)
 #pragma unroll
-                    for (int i = 0; i < 4; i++) reinterpret_cast<u32x4 *>(qbuf + c * XCH_FLOATS)[64 * i + lw] = t[c][i];
+                    for (int i = 0; i < 4; i++) reinterpret_cast<u32x4 *>(q_park + c * XCH_FLOATS)[64 * i] = t[c][i];
                 SCHED_FENCE();
             }
             wave_lds_sync();
@@ -271,23 +301,41 @@ __global__ __launch_bounds__(SSDR_WF_BLOCK, SSDR_WF_WAVES_PER_EU) void ssdr_fuse
 #pragma unroll
                 for (int f = 0; f < FRAMES_PER_LINE; f++) {
                     const uint32_t frame = HOP ? line : 2 * line + f;               // hop 512: the new half of the line is the step's frame
-                    const u32x4 *qp = reinterpret_cast<const u32x4 *>(qbuf + c * XCH_FLOATS + SSDR_FRAME * (HOP ? 1 : f)) + 2 * opaque(lane);
+                    // PARKED: the region starts 4 samples ahead of the line, so these are the frame's samples 8l-4 .. 8l+3, delay included
+                    const int FBASE = c * XCH_FLOATS + SSDR_FRAME * (HOP ? 1 : f);
+                    const u32x4 *qp = reinterpret_cast<const u32x4 *>(q_lane + FBASE);
                     const u32x4 q0 = qp[0], q1 = qp[1];
                     const uint32_t rw[8] = {q0.x, q0.y, q0.z, q0.w, q1.x, q1.y, q1.z, q1.w};
-                    uint32_t qv[8], d[8];
-#pragma unroll
-                    for (int j = 0; j < 8; j++) qv[j] = iq_power(rw[j]);
+                    uint32_t d[8];
                     float p[8], aud[8];
+                    float pmx;                                                // the block's peak (also what the AGC takes as such)
+                    bool trig, clip;
+                    if constexpr (PARKED) {
+                        // the frame's last four samples, which no lane holds (they open the next frame's lane 0): lane i takes number i & 3
+                        const uint32_t last = q_last[FBASE + SSDR_FRAME];
 #pragma unroll
-                    for (int j = 0; j < 4; j++) { d[j] = from_prev_lane_u(tail_q[c][j], qv[4 + j]); d[4 + j] = qv[j]; }
+                        for (int j = 0; j < 8; j++) d[j] = iq_power(rw[j]);
 #pragma unroll
-                    for (int j = 0; j < 4; j++) tail_q[c][j] = lane63_u(qv[4 + j]);
+                        for (int j = 0; j < 8; j++) p[j] = (float)d[j];
+                        pmx = block_peak(p);
+                        // the cheap trigger, necessary for a clipped sample anywhere in -4 .. 511 of the frame
+                        trig = wave_any((pmx >= 1073676160.0f) | (iq_power(last) >= 0x3FFF0001u));
+                        clip = trig ? wave_any(raw_clipped_delayed(rw, last, lane)) : false;    // the exact check, only then: samples 0 .. 511
+                    } else {
+                        uint32_t qv[8];
 #pragma unroll
-                    for (int j = 0; j < 8; j++) p[j] = (float)d[j];
-                    const float pmx = block_peak(p);                          // (also what the AGC takes as the block's peak)
-                    const bool trig = wave_any(pmx >= 1073676160.0f) || tail_q[c][0] >= 0x3FFF0001u || tail_q[c][1] >= 0x3FFF0001u ||
-                                      tail_q[c][2] >= 0x3FFF0001u || tail_q[c][3] >= 0x3FFF0001u;
-                    const bool clip = trig ? wave_any(raw_clipped(rw)) : false;    // the exact check, only then
+                        for (int j = 0; j < 8; j++) qv[j] = iq_power(rw[j]);
+#pragma unroll
+                        for (int j = 0; j < 4; j++) { d[j] = from_prev_lane_u(tail_q[c][j], qv[4 + j]); d[4 + j] = qv[j]; }
+#pragma unroll
+                        for (int j = 0; j < 4; j++) tail_q[c][j] = lane63_u(qv[4 + j]);
+#pragma unroll
+                        for (int j = 0; j < 8; j++) p[j] = (float)d[j];
+                        pmx = block_peak(p);
+                        trig = wave_any(pmx >= 1073676160.0f) || tail_q[c][0] >= 0x3FFF0001u || tail_q[c][1] >= 0x3FFF0001u ||
+                               tail_q[c][2] >= 0x3FFF0001u || tail_q[c][3] >= 0x3FFF0001u;
+                        clip = trig ? wave_any(raw_clipped(rw)) : false;    // the exact check, only then
+                    }
                     demod_am<true>(p, dc[c], aud);
                     agc_pack_store_fused<HANG>(aud, lane, agc_c, agc_d[c], hang[c], u.pcm + ((uint64_t)cc * n_frames + frame) * SSDR_FRAME + 8 * lane, pmx);
                     rssi_flag_step(p, clip, frame, n_frames, lane, cal_c, rssi_sum[c], flag_keep[c],
@@ -301,7 +349,7 @@ __global__ __launch_bounds__(SSDR_WF_BLOCK, SSDR_WF_WAVES_PER_EU) void ssdr_fuse
             {
                 const uint32_t *q = qbuf + opaque(h) * XCH_FLOATS + opaque(l);
 #pragma unroll
-                for (int r = 0; r < 32; r++) raw[r] = q[32 * r];
+                for (int r = 0; r < 32; r++) raw[r] = q[PARK + 32 * r];
             }
             wave_lds_sync();
             if (lane < 2) {                                                    // ... and back to rest
@@ -313,8 +361,14 @@ __global__ __launch_bounds__(SSDR_WF_BLOCK, SSDR_WF_WAVES_PER_EU) void ssdr_fuse
 #pragma unroll
                         for (int i = 0; i < 8; i++) pad(c, 2 + i) = hang[c].m[i];
                     }
+                    if constexpr (PARKED) {                    // the line's last four samples, still where they were parked
+                        const u32x4 e = *reinterpret_cast<const u32x4 *>(qbuf + c * XCH_FLOATS + PARK + SSDR_NFFT - 4);
 #pragma unroll
-                    for (int i = 0; i < 4; i++) pad(c, PAD_TAIL + i) = __uint_as_float(tail_q[c][i]);
+                        for (int i = 0; i < 4; i++) pad(c, PAD_TAIL + i) = __uint_as_float(e[i]);
+                    } else {
+#pragma unroll
+                        for (int i = 0; i < 4; i++) pad(c, PAD_TAIL + i) = __uint_as_float(tail_q[c][i]);
+                    }
                 }
             }
             wave_lds_sync();
@@ -372,17 +426,28 @@ __global__ __launch_bounds__(SSDR_WF_BLOCK, SSDR_WF_WAVES_PER_EU) void ssdr_fuse
         if (a.n_lines) {
             // the discriminator memory an AM channel leaves behind: y[511] = z1[507] of the last frame, mixed as the twin does
             // (block 63 of the frame, element 3).  Sample 507 of that frame is the line's sample 1019 = raw[31] of lane 27.
+            // The three phasors per channel it takes have wave-uniform arguments: lane 3 c + k evaluates the k-th of channel c, all six in
+            // one pass through the polynomial.
+            uint32_t parg = 0;
+#pragma unroll
+            for (int c = 0; c < 2; c++) {
+                if ((uint32_t)c >= n_sub) continue;
+                const uint32_t cc = 2 * pair + c;
+                const uint32_t dphi1 = u.consts[cc].dphi1;
+                const uint32_t phi_last = u.state[cc].phi1 + (uint32_t)(SSDR_FRAME * (n_frames - 1)) * dphi1;
+                parg = lane == 3 * c ? phi_last : lane == 3 * c + 1 ? (uint32_t)(8 * 63) * dphi1 : lane == 3 * c + 2 ? dphi1 : parg;
+            }
+            float pcos, psin;
+            ssdr_phasor32(parg, pcos, psin);
 #pragma unroll
             for (int c = 0; c < 2; c++) {
                 if ((uint32_t)c >= n_sub) continue;
                 const uint32_t cc = 2 * pair + c;
                 const ssdr_chan_consts &kc = u.consts[cc];
                 ssdr_chan_state st = u.state[cc];
-                const uint32_t phi_last = st.phi1 + (uint32_t)(SSDR_FRAME * (n_frames - 1)) * kc.dphi1;
-                float fc, fs, qc, qs, bc, bs, cs, ss;
-                ssdr_phasor32(phi_last, fc, fs);
-                ssdr_phasor32((uint32_t)(8 * 63) * kc.dphi1, qc, qs);
-                ssdr_phasor32(kc.dphi1, cs, ss);
+                const float fc = lane_f(pcos, 3 * c), fs = lane_f(psin, 3 * c), qc = lane_f(pcos, 3 * c + 1), qs = lane_f(psin, 3 * c + 1);
+                const float cs = lane_f(pcos, 3 * c + 2), ss = lane_f(psin, 3 * c + 2);
+                float bc, bs;
                 phasor_mul(fc, fs, qc, qs, bc, bs);
 #pragma unroll
                 for (int j = 0; j < 3; j++) { const float cn = fmaf(bc, cs, -(bs * ss)), sn = fmaf(bs, cs, bc * ss); bc = cn; bs = sn; }

@@ -133,6 +133,18 @@ SSDR_DEV int opaque(int v)
     return v;
 }
 
+// The same for a whole LDS address.  A per-lane base plus compile-time offsets should be one address register and the DS
+// instructions' offset fields; but the compiler pulls the constant part of the base (LDS_XCH, a literal too large for the
+// two-address forms' 8-bit fields) out to the individual accesses and then builds one base register per instruction.  Laundered,
+// the base is a value it cannot look into: one register, the offsets ride in the instructions.
+SSDR_DEV float *opaque_lds(float *p)
+{
+    typedef __attribute__((address_space(3))) float lds_float;
+    uint32_t a = (uint32_t)(uintptr_t)(lds_float *)p;
+    asm volatile("" : "+v"(a));
+    return (float *)(lds_float *)(uintptr_t)a;
+}
+
 SSDR_DEV void wave_lds_sync()
 {
     // One wave owns its LDS region and DS instructions of a wave execute in order, so
@@ -296,14 +308,15 @@ SSDR_DEV void fft_line(f32x2 (&z)[32], const unsigned char *smem, float *xch_wav
     const int lx = opaque(l);
     float *xch = xch_wave + opaque(h) * XCH_FLOATS;
     const int g = __builtin_bitreverse32((uint32_t)lx) >> 27;
+    float *row = opaque_lds(xch + g * XPAD);       // the lane's row: one address register for the 32 writes of both passes
 #pragma unroll
-    for (int r = 0; r < 32; r++) xch[g * XPAD + r] = z[r].x;
+    for (int r = 0; r < 32; r++) row[r] = z[r].x;
     wave_lds_sync();
 #pragma unroll
     for (int j = 0; j < 32; j++) z[j].x = xch[j * XPAD + lx];
     wave_lds_sync();
 #pragma unroll
-    for (int r = 0; r < 32; r++) xch[g * XPAD + r] = z[r].y;
+    for (int r = 0; r < 32; r++) row[r] = z[r].y;
     wave_lds_sync();
 #pragma unroll
     for (int j = 0; j < 32; j++) z[j].y = xch[j * XPAD + lx];
