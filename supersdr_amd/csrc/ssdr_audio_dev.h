@@ -306,8 +306,19 @@ SSDR_DEV float agc_pack_store(const float (&p)[8], const float (&aud)[8], int l,
 template <bool HANG> struct AgcHang { float m[8]; };         // a channel's hang memory (ssdr_chan_state.agc_m) ...
 template <> struct AgcHang<false> {};                        // ... or nothing at all
 
+// The frame's 1 KB of PCM starts at `frame` (wave-uniform, a scalar register pair), the lane's 16 bytes lie `lane_bytes` behind it:
+// the store names both (scalar base, 32-bit lane offset) -- written out, because handed a sum the compiler forms it per lane in 64 bits
+// (an address laundered through an "s" operand included).  The compiler pads no hazard of an instruction it does not see: five wait
+// states in front, should a vector instruction (v_readfirstlane) have written the base, and two behind, before anything overwrites the
+// four data registers.  It does not count the store either; the kernel never waits for it (nothing reads PCM back), and an uncounted
+// store in the queue only makes the compiler's own vmcnt waits longer, never shorter (the queue retires in order).
+// `frame` MUST be wave-uniform: for a per-lane address the "s" operand would silently take one lane's value.
+#ifndef SSDR_PCM_STORE_FRONT_PAD
+#define SSDR_PCM_STORE_FRONT_PAD "s_nop 4\n\t"     // (an A/B build without it: -DSSDR_PCM_STORE_FRONT_PAD='""', profiles/fused_scan_ab.txt)
+#endif
 template <bool HANG>
-SSDR_DEV void agc_pack_store_fused(const float (&aud)[8], int l, const AgcK &k, float &agc_d, AgcHang<HANG> &hang, int16_t *dst, float pm)
+SSDR_DEV void agc_pack_store_fused(const float (&aud)[8], int l, const AgcK &k, float &agc_d, AgcHang<HANG> &hang, int16_t *frame,
+                                   uint32_t lane_bytes, float pm)
 {
     const float al = ssdr_log2p(pm);
     const float fl = (float)l;
@@ -342,7 +353,7 @@ SSDR_DEV void agc_pack_store_fused(const float (&aud)[8], int l, const AgcK &k, 
         const int i0 = __float2int_rn(aud[j] * g), i1 = __float2int_rn(aud[j + 1] * g);
         w[j >> 1] = __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_pk_i16(i0, i1));
     }
-    SSDR_NT_STORE(w, reinterpret_cast<u32x4 *>(dst));
+    asm volatile(SSDR_PCM_STORE_FRONT_PAD "global_store_dwordx4 %0, %1, %2 nt\n\ts_nop 1" : : "v"(lane_bytes), "v"(w), "s"(frame) : "memory");
 }
 
 // SSDR_MODE_IQ: the lane's eight filtered samples times the AGC gain as I | Q << 16 (round-half-even, saturating), 32 B per lane
@@ -378,6 +389,102 @@ SSDR_DEV void rssi_flag_step(const float (&p)[8], bool clip, uint32_t f, uint32_
 }
 
 SSDR_DEV bool wave_any(bool x) { return __builtin_amdgcn_ballot_w64(x) != 0ull; }
+SSDR_DEV uint32_t wave_count(bool x) { return (uint32_t)__builtin_popcountll(__builtin_amdgcn_ballot_w64(x)); }
+
+// ---- the fused AM kernel's forms of scan_affine, demod_am and rssi_flag_step (ssdr_wf.hip:ssdr_fused_am_kernel) ------------
+// demod_am starts every lane's map at A = DC_APOW[7], and scan_affine's steps update A from A alone: the A a lane holds in front of each
+// step, and Ae = the previous lane's A behind the last one, are the same 64 numbers per step in every frame of every channel.  The
+// kernel tabulates them once per workgroup with scan_affine's own multiplies (same controls, same masks: lanes without a source keep
+// their value), so they are bit for bit what scan_affine would compute, and the frames run the B half alone.
+struct DcScan { float a[6]; float ae; };       // a[k]: the lane's A in front of step k (a[0] = DC_APOW[7] everywhere); ae: Ae
+
+SSDR_DEV void scan_affine_consts(DcScan &t)
+{
+    constexpr float DC_APOW[8] = SSDR_DC_APOW_INIT;
+    float A = DC_APOW[7];
+    float after[6];
+    int k = 0;
+#define STEP(C, M) asm("s_nop 1\n\tv_mul_f32_dpp %0, %0, %0" SSDR_DPP(C, M) : "+v"(A)); after[k++] = A;
+    SSDR_SCAN6(STEP)
+#undef STEP
+    t.a[0] = DC_APOW[7];
+#pragma unroll
+    for (int i = 1; i < 6; i++) t.a[i] = after[i - 1];
+    t.ae = from_prev_lane(1.0f, after[5]);
+}
+// from_prev_lane(0.0f, x) without a register for the zero: bound_ctrl makes lane 0, which has no source, read 0
+SSDR_DEV float from_prev_lane_or_zero(float x)
+{
+    return __int_as_float(__builtin_amdgcn_update_dpp(__float_as_int(x), __float_as_int(x), 0x138, 0xF, 0xF, true));
+}
+// scan_affine's B half: B = fma(A, B_src, B) with the tabulated A of each step
+SSDR_DEV void scan_affine_b(float &B, const DcScan &t)
+{
+    int k = 0;
+#define STEP(C, M) asm("s_nop 1\n\tv_fmac_f32_dpp %0, %0, %1" SSDR_DPP(C, M) : "+v"(B) : "v"(t.a[k])); k++;
+    SSDR_SCAN6(STEP)
+#undef STEP
+}
+// demod_am<true> with the scan's constants handed in.  The recurrence's first step, fmaf(SSDR_DC_A, 0, SSDR_DC_AL * env[0]), is the
+// product itself: 0 + x = x unless x is -0, and env >= 0, SSDR_DC_AL > 0.
+SSDR_DEV void demod_am_tab(const float (&p)[8], float &dc, float (&aud)[8], const DcScan &t)
+{
+    constexpr float DC_APOW[8] = SSDR_DC_APOW_INIT;
+    float env[8], loc[8];
+    env[0] = ssdr_sqrt_rn_int(p[0]);
+    float s = SSDR_DC_AL * env[0];
+    loc[0] = s;
+#pragma unroll
+    for (int j = 1; j < 8; j++) {
+        env[j] = ssdr_sqrt_rn_int(p[j]);
+        s = fmaf(SSDR_DC_A, s, SSDR_DC_AL * env[j]);
+        loc[j] = s;
+    }
+    float Bsc = s;
+    scan_affine_b(Bsc, t);
+    const float Be = from_prev_lane_or_zero(Bsc);
+    const float carry = fmaf(t.ae, dc, Be);          // lane 0: identity map -> dc
+    float m = 0.0f;
+#pragma unroll
+    for (int j = 0; j < 8; j++) {
+        m = fmaf(DC_APOW[j], carry, loc[j]);
+        aud[j] = env[j] - m;
+    }
+    dc = lane63(m);
+}
+// v_writelane_b32 (value, lane, old).  Where clang has __builtin_amdgcn_writelane, that is used.  ROCm 7.2's hipcc (clang 22.0.0git,
+// roc-7.2.0) has the instruction's intrinsic but no builtin of that name: there it is declared by its IR name, which is the overloaded
+// intrinsic's mangled name in that LLVM (older ones spell it without ".i32"; a wrong name fails the build, not the result).  Either way the
+// compiler sees what it is: it puts the lane select into m0 and keeps the wait states.
+#if defined(__has_builtin) && __has_builtin(__builtin_amdgcn_writelane)
+SSDR_DEV int ssdr_writelane(int value, int lane, int old) { return __builtin_amdgcn_writelane(value, lane, old); }
+#else
+extern "C" __device__ int ssdr_writelane(int value, int lane, int old) __asm("llvm.amdgcn.writelane.i32");
+#endif
+
+// rssi_flag_step for a caller whose frame number, channel rows and clip flag are wave-uniform: the frame's total and flag (`clip`: 0 or 1)
+// go into lane f mod 64 of the keepers from the scalar side, and everything the rare flush needs -- the lane's place in the rows, the mask of the
+// kept frames -- is formed inside its branch from a laundered lane id (nothing of it can be hoisted into the ordinary frame).
+// rssi_row, flag_row: the channel's rows (wave-uniform); the stores take them as scalar base plus a 32-bit lane offset.
+SSDR_DEV void rssi_flag_step_uniform(const float (&p)[8], uint32_t clip, uint32_t f, uint32_t n_frames, int l, float cal,
+                                     float &rssi_sum, uint32_t &flag_keep, float *rssi_row, uint8_t *flag_row)
+{
+    float ps = p[0];
+#pragma unroll
+    for (int j = 1; j < 8; j++) ps = ps + p[j];
+    const float tot = lane63(scan_sum(ps));
+    rssi_sum = __int_as_float(ssdr_writelane(__float_as_int(tot), (int)(f & 63u), __float_as_int(rssi_sum)));
+    flag_keep = (uint32_t)ssdr_writelane((int)clip, (int)(f & 63u), (int)flag_keep);
+    if ((f & 63u) == 63u || f + 1 == n_frames) {
+        uint32_t lx = (uint32_t)l;
+        asm volatile("" : "+v"(lx));
+        if (lx <= (f & 63u)) {
+            char *r = reinterpret_cast<char *>(rssi_row + (f & ~63u));
+            *reinterpret_cast<float *>(r + (lx << 2)) = fmaf(ssdr_log2p(fmaxf(rssi_sum, 1e-20f)) - 39.0f, SSDR_DB_PER_LOG2, cal);
+            (flag_row + (f & ~63u))[lx] = (uint8_t)flag_keep;
+        }
+    }
+}
 
 // |component| >= 32767 for any of a lane's eight raw samples (the rare exact check behind the cheap triggers)
 SSDR_DEV bool raw_clipped(const uint32_t (&rw)[8])

@@ -35,6 +35,15 @@ namespace {
 constexpr int WAVES = SSDR_WF_BLOCK / 64;
 constexpr int LDS_TOTAL = LDS_XCH + WAVES * 2 * XCH_FLOATS * 4;
 static_assert(LDS_TOTAL <= 163840, "LDS budget");
+// The fused kernel's map: the same, and behind it the DC scan's constants (ssdr_audio_dev.h: DcScan; six rows of 64 floats, a[1..5]
+// and ae).  Everything in front keeps the address it has in the waterfall kernel.
+// The margin for two workgroups per CU is smaller than the 1504 B the assertion leaves: the LDS is allocated in blocks, and if those are
+// 1280 B, 81168 B take 81920 and two workgroups fill the CU exactly.  Whoever adds a byte to this map checks on the device that
+// ssdr_fused_blocks_per_cu still returns 2 (ssdr_create's default fused floor is 8192 channels then).
+constexpr int LDS_SCAN = LDS_TOTAL;
+constexpr int LDS_SCAN_BYTES = 6 * 64 * 4;
+constexpr int LDS_TOTAL_FUSED = LDS_SCAN + LDS_SCAN_BYTES;
+static_assert(LDS_SCAN % 4 == 0 && 2 * LDS_TOTAL_FUSED <= 163840, "two workgroups per CU");
 
 // AVG == false: averaging N == 1, every line is an output line (no accumulators at all).
 // HOP == true: lines overlap by half (hop 512 samples = 23.4 lines/s, the reference's waterfall rate, utils_supersdr.py:597):
@@ -133,6 +142,19 @@ __global__ __launch_bounds__(SSDR_WF_BLOCK, SSDR_WF_WAVES_PER_EU) void ssdr_wf_k
     }
 }
 
+// a wave-uniform global address plus the lane's 32-bit byte offset, as 16-byte words: the scalar-base form of the vector memory
+// instructions (no 64-bit add per lane)
+template <typename T>
+SSDR_DEV u32x4 *lane_at(T *base, uint32_t lane_bytes)
+{
+    return reinterpret_cast<u32x4 *>(reinterpret_cast<char *>(base) + lane_bytes);
+}
+template <typename T>
+SSDR_DEV const u32x4 *lane_at(const T *base, uint32_t lane_bytes)
+{
+    return reinterpret_cast<const u32x4 *>(reinterpret_cast<const char *>(base) + lane_bytes);
+}
+
 // ---------------------------------------------------------------------------------------------------------------
 // Fused superframe kernel for the metric's configuration (N = 1, hop 1024, every channel on the full-band AM path):
 // one read of a channel's 4 KB line feeds the FFT and both 512-sample audio frames.
@@ -153,13 +175,24 @@ __global__ __launch_bounds__(SSDR_WF_BLOCK, SSDR_WF_WAVES_PER_EU) void ssdr_wf_k
 // reference's default is none, and then the hang memory agc_m[8] is no part of the audio phase: it is neither fetched from the state
 // record, nor parked in the pad column, nor tested against K frame by frame, and the record keeps the words it had (what the K == 0
 // branch of agc_pack_store leaves as well).  HANG == true handles every mix of hanging and non-hanging channels.
+// What no data enters is not computed per frame: the A half of the DC block's affine scan is a table in the LDS (wave 0 fills it in front
+// of load_tables, the lanes read their six values once per line; ssdr_audio_dev.h: DcScan), the frame's RSSI total and overflow flag go
+// into their keeper lane from scalar registers, and every global address of the audio phase is a scalar base plus the lane's 16 l.
 template <bool HOP, bool AVG = false, bool HANG = true>
 __global__ __launch_bounds__(SSDR_WF_BLOCK, SSDR_WF_WAVES_PER_EU) void ssdr_fused_am_kernel(SsdrFusedArgs fa)
 {
-    __shared__ __attribute__((aligned(16))) unsigned char smem[LDS_TOTAL];
+    __shared__ __attribute__((aligned(16))) unsigned char smem[LDS_TOTAL_FUSED];
     const SsdrWfArgs &a = fa.wf;
     const SsdrAudioArgs &u = fa.au;
-    load_tables(smem, a.win, a.tw_stage, a.lut);
+    if (threadIdx.x < 64) {                                                  // the DC scan's constants, once per workgroup (wave 0)
+        DcScan t;
+        scan_affine_consts(t);
+        float *s_scan = reinterpret_cast<float *>(smem + LDS_SCAN) + threadIdx.x;
+#pragma unroll
+        for (int k = 1; k < 6; k++) s_scan[64 * (k - 1)] = t.a[k];
+        s_scan[64 * 5] = t.ae;
+    }
+    load_tables(smem, a.win, a.tw_stage, a.lut);                             // (ends in the kernel's only __syncthreads)
 
     const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int h = lane >> 5, l = lane & 31;
@@ -260,6 +293,8 @@ __global__ __launch_bounds__(SSDR_WF_BLOCK, SSDR_WF_WAVES_PER_EU) void ssdr_fuse
             const uint32_t lw = opaque(lane);
             uint32_t *q_park = qbuf + PARK + 4 * lw;                 // 16 bytes per lane and store
             const uint32_t *q_lane = q_park - PARK + 4 * lw, *q_last = qbuf + (lw & 3u);    // 8 samples per lane; one of a frame's last four
+            // ... and its 16 bytes of a 1 KB global access: the line's loads and the PCM stores are a scalar base plus this
+            const uint32_t lane16 = lw << 4;
             {
                 u32x4 t[2][4];
 #pragma unroll
@@ -271,12 +306,12 @@ __global__ __launch_bounds__(SSDR_WF_BLOCK, SSDR_WF_WAVES_PER_EU) void ssdr_fuse
                     if (HOP) {
                         const uint32_t *older = line ? row - SSDR_NFFT / 2 : a.tail + (uint64_t)cc * (SSDR_NFFT / 2);
 #pragma unroll
-                        for (int i = 0; i < 2; i++) t[c][i] = SSDR_NT_LOAD(reinterpret_cast<const u32x4 *>(older) + 64 * i + lw);   // its last use
+                        for (int i = 0; i < 2; i++) t[c][i] = SSDR_NT_LOAD(lane_at(older, lane16) + 64 * i);   // its last use
 #pragma unroll
-                        for (int i = 0; i < 2; i++) t[c][2 + i] = reinterpret_cast<const u32x4 *>(row)[64 * i + lw];      // read again one line later: L2
+                        for (int i = 0; i < 2; i++) t[c][2 + i] = lane_at(row, lane16)[64 * i];      // read again one line later: L2
                     } else {
 #pragma unroll
-                        for (int i = 0; i < 4; i++) t[c][i] = SSDR_NT_LOAD(reinterpret_cast<const u32x4 *>(row) + 64 * i + lw);
+                        for (int i = 0; i < 4; i++) t[c][i] = SSDR_NT_LOAD(lane_at(row, lane16) + 64 * i);
                     }
                 }
                 SCHED_FENCE();
@@ -287,6 +322,19 @@ __global__ __launch_bounds__(SSDR_WF_BLOCK, SSDR_WF_WAVES_PER_EU) void ssdr_fuse
                 SCHED_FENCE();
             }
             wave_lds_sync();
+            // the DC scan's constants: read once per line, held across its frames (the FFT is not live here)
+            DcScan dcs;
+            {
+                constexpr float DC_APOW[8] = SSDR_DC_APOW_INIT;
+                uint32_t scan_base = LDS_SCAN;                                  // (in a scalar register: the lane's address is one shift-and-add)
+                asm volatile("" : "+s"(scan_base));
+                const float *s_scan = reinterpret_cast<const float *>(smem + scan_base) + lw;
+                dcs.a[0] = DC_APOW[7];
+                asm volatile("" : "+v"(dcs.a[0]));                            // (one register for the line, not a literal move per frame)
+#pragma unroll
+                for (int k = 1; k < 6; k++) dcs.a[k] = s_scan[64 * (k - 1)];
+                dcs.ae = s_scan[64 * 5];
+            }
             // ---- audio, phase 2: channel A, then channel B, two frames each, all 64 lanes on one channel
             prio_latency_phase();                                             // (the call's first line; later ones arrive with it)
 #pragma unroll
@@ -309,7 +357,10 @@ __global__ __launch_bounds__(SSDR_WF_BLOCK, SSDR_WF_WAVES_PER_EU) void ssdr_fuse
                     uint32_t d[8];
                     float p[8], aud[8];
                     float pmx;                                                // the block's peak (also what the AGC takes as such)
-                    bool trig, clip;
+                    bool trig;
+                    // the frame's flag, 0 or 1, in a scalar register: (count of clipping lanes + 63) >> 6.  (Out of a bool, or out of
+                    // min(count, 1), which the compiler reads as one, it becomes a 0 / 1 per lane selected in either branch.)
+                    uint32_t clip;
                     if constexpr (PARKED) {
                         // the frame's last four samples, which no lane holds (they open the next frame's lane 0): lane i takes number i & 3
                         const uint32_t last = q_last[FBASE + SSDR_FRAME];
@@ -320,7 +371,7 @@ __global__ __launch_bounds__(SSDR_WF_BLOCK, SSDR_WF_WAVES_PER_EU) void ssdr_fuse
                         pmx = block_peak(p);
                         // the cheap trigger, necessary for a clipped sample anywhere in -4 .. 511 of the frame
                         trig = wave_any((pmx >= 1073676160.0f) | (iq_power(last) >= 0x3FFF0001u));
-                        clip = trig ? wave_any(raw_clipped_delayed(rw, last, lane)) : false;    // the exact check, only then: samples 0 .. 511
+                        clip = trig ? (wave_count(raw_clipped_delayed(rw, last, lane)) + 63u) >> 6 : 0u;    // the exact check, only then: samples 0 .. 511
                     } else {
                         uint32_t qv[8];
 #pragma unroll
@@ -334,12 +385,13 @@ __global__ __launch_bounds__(SSDR_WF_BLOCK, SSDR_WF_WAVES_PER_EU) void ssdr_fuse
                         pmx = block_peak(p);
                         trig = wave_any(pmx >= 1073676160.0f) || tail_q[c][0] >= 0x3FFF0001u || tail_q[c][1] >= 0x3FFF0001u ||
                                tail_q[c][2] >= 0x3FFF0001u || tail_q[c][3] >= 0x3FFF0001u;
-                        clip = trig ? wave_any(raw_clipped(rw)) : false;    // the exact check, only then
+                        clip = trig ? (wave_count(raw_clipped(rw)) + 63u) >> 6 : 0u;    // the exact check, only then
                     }
-                    demod_am<true>(p, dc[c], aud);
-                    agc_pack_store_fused<HANG>(aud, lane, agc_c, agc_d[c], hang[c], u.pcm + ((uint64_t)cc * n_frames + frame) * SSDR_FRAME + 8 * lane, pmx);
-                    rssi_flag_step(p, clip, frame, n_frames, lane, cal_c, rssi_sum[c], flag_keep[c],
-                                   u.rssi + (uint64_t)cc * n_frames, u.flags + (uint64_t)cc * n_frames);
+                    demod_am_tab(p, dc[c], aud, dcs);
+                    // (the frame's base is wave-uniform: cc comes through readfirstlane, frame and n_frames are the call's)
+                    agc_pack_store_fused<HANG>(aud, lane, agc_c, agc_d[c], hang[c], u.pcm + ((uint64_t)cc * n_frames + frame) * SSDR_FRAME, lane16, pmx);
+                    rssi_flag_step_uniform(p, clip, frame, n_frames, lane, cal_c, rssi_sum[c], flag_keep[c],
+                                           u.rssi + (uint64_t)cc * n_frames, u.flags + (uint64_t)cc * n_frames);
                 }
             }
             wave_lds_sync();
