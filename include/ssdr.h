@@ -54,7 +54,15 @@ enum {
 enum { SSDR_MODE_AM = 0, SSDR_MODE_LSB = 1, SSDR_MODE_USB = 2, SSDR_MODE_CW = 3, SSDR_MODE_NBFM = 4,
        /* "SET mod=iq" (kiwi/client.py:217-249, default passband +-5 kHz): no demodulator -- the channel's tuned, filtered and
         * gain-controlled complex baseband itself.  The PCM row of such a channel carries I; I,Q pairs: ssdr_audio_iq */
-       SSDR_MODE_IQ = 5 };
+       SSDR_MODE_IQ = 5,
+       /* "SET mod=sam|sal|sau": synchronous AM, one demodulator whose passband picks both sidebands or one.  On a KiwiSDR it is
+        * server-side DSP, so the reference has no code for it: tests/sam_ref.py is this project's definition.
+        * The constants compile by the SSB rule (f_bc = (lc + hc) / 2, fl = |hc - lc| / 2, dphi1 from f_shift + f_bc, dphi2 from f_bc;
+        * fir_flags 0), so the tuned carrier sits at 0 Hz behind the second NCO wherever the passband lies; a second-order PLL, updated
+        * once per AGC block of 8 samples, follows it; the audio is the in-phase part minus AM's one-pole DC estimate.  Filter, AGC,
+        * RSSI and flags are those of SSB with the same passband.  ssdr_get_sam_carrier reads the loop.  12 kHz / 20.25 kHz input only:
+        * with ssdr_set_decimation(D > 1) the mode is not available (SSDR_ESTATE, see ssdr_set_decimation). */
+       SSDR_MODE_SAM = 6 };
 
 /* Per-channel parameters: the reference's a13 parameter surface:
  *   "SET mod=%s low_cut=%d high_cut=%d freq=%.3f"              utils_supersdr.py:1028
@@ -96,7 +104,10 @@ typedef struct ssdr_chan_state {
     float dc, agc_d;
     float agc_m[8];
     float prev_re, prev_im;
-    uint32_t pad[2];
+    uint32_t pad[2];            /* SSDR_MODE_SAM: the carrier loop.  pad[0] = theta, the loop's phase as a 32-bit phase like phi1
+                                 * (radians = 2 pi pad[0] / 2^32, it wraps by itself); pad[1] = the bits of a float32, omega in radians
+                                 * per sample.  Both 0 after ssdr_reset_state and when ssdr_set_params moves a channel into the mode;
+                                 * channels of the other modes carry the two words through untouched. */
 } ssdr_chan_state;
 
 typedef struct ssdr_ctx ssdr_ctx;
@@ -113,7 +124,7 @@ void ssdr_destroy(ssdr_ctx *ctx);
  *    ssdr_set_params then also puts the channel's AGC envelope at its new knee (the initial
  *    state of ssdr_reset_state: full gain, no pop). */
 int ssdr_set_params(ssdr_ctx *ctx, uint32_t first, uint32_t count, const ssdr_chan_params *p);
-int ssdr_default_params(int mode, ssdr_chan_params *out);      /* reference defaults, utils:42-50,936-944 */
+int ssdr_default_params(int mode, ssdr_chan_params *out);      /* reference defaults, utils:42-50,936-944; SSDR_MODE_SAM: +-4900 Hz */
 int ssdr_reset_state(ssdr_ctx *ctx, uint32_t first, uint32_t count);
 /* kiwi_waterfall.averaging_n (utils_supersdr.py:616, 881-886; supersdr.py:376-385), 1..100 */
 int ssdr_set_averaging(ssdr_ctx *ctx, uint32_t n);
@@ -123,7 +134,9 @@ int ssdr_set_averaging(ssdr_ctx *ctx, uint32_t n);
  * rate; output y[m] = sum_k h[k] z[D m - k]) down to the 12 kHz the demodulators, the AGC and the PCM frames run at.
  * A frame is still what yields 512 PCM samples: ssdr_push_iq then takes int16 [n_ch][n_frames*512*D][2], f_shift_hz may
  * reach +-D*6000, and the waterfall draws its lines (1024 or 512 input samples apart) from the wide stream.  Changing D
- * recompiles every channel's parameters and resets the streams.  Not available on the pipelined feed / wire input. */
+ * recompiles every channel's parameters and resets the streams.  Not available on the pipelined feed / wire input.
+ * SSDR_MODE_SAM has no decimating front end: whichever comes second of a channel or sub-receiver in that mode (ssdr_set_params,
+ * ssdr_set_subrx) and D > 1 returns SSDR_ESTATE and changes nothing; ssdr_compile_params_decim / _rate return it for that pair too. */
 int ssdr_set_decimation(ssdr_ctx *ctx, uint32_t decim);
 int ssdr_compile_params_decim(const ssdr_chan_params *p, uint32_t decim, ssdr_chan_consts *consts, float *taps /*[128]*/);
 
@@ -547,6 +560,8 @@ int ssdr_subrx_audio(ssdr_ctx *ctx, int16_t *pcm, float *rssi, uint8_t *flags, i
 /* Carried state and compiled constants of rows [first_row, first_row + count) of the list, as ssdr_get_state / ssdr_get_consts. */
 int ssdr_get_subrx_state(ssdr_ctx *ctx, uint32_t first_row, uint32_t count, ssdr_chan_state *state, int16_t *hist /* may be NULL */);
 int ssdr_get_subrx_consts(ssdr_ctx *ctx, uint32_t first_row, uint32_t count, ssdr_chan_consts *consts, float *taps /* may be NULL */);
+/* ssdr_get_sam_carrier for rows [first_row, first_row + count) of the list */
+int ssdr_get_subrx_sam_carrier(ssdr_ctx *ctx, uint32_t first_row, uint32_t count, float *offset_hz, float *phase_rad /* may be NULL */);
 /* play_buffer of the sub-receivers' PCM rows of the last audio run, as if they were the channels of a small ctx: the shipped kernels
  * of ssdr_run_playbuffer at either rate, on a history array of the sub-receivers' own (a kept sub-receiver keeps its history across a
  * list change).  chans [count]; out int16 [count][n_frames * ssdr_playbuffer_frame_len][2].  No recording block.  SSDR_ESTATE like
@@ -830,6 +845,11 @@ int ssdr_compile_params(const ssdr_chan_params *p, ssdr_chan_consts *consts, flo
 int ssdr_get_consts(ssdr_ctx *ctx, uint32_t first, uint32_t count, ssdr_chan_consts *consts, float *taps);
 int ssdr_get_state(ssdr_ctx *ctx, uint32_t first, uint32_t count, ssdr_chan_state *state, int16_t *hist);
 int ssdr_set_state(ssdr_ctx *ctx, uint32_t first, uint32_t count, const ssdr_chan_state *state, const int16_t *hist);
+/* The carrier loop of the SSDR_MODE_SAM channels [first, first + count) as the last audio run left it: offset_hz float [count] =
+ * omega * rate / (2 pi), the carrier's offset from the tuned frequency as the loop reads it; phase_rad float [count] (may be NULL) =
+ * theta in [-pi, pi).  Both 0 for channels of other modes.  SSDR_EINVAL for a range outside the ctx or a NULL offset_hz.  Ordered
+ * behind the ctx's queued work, like ssdr_get_state. */
+int ssdr_get_sam_carrier(ssdr_ctx *ctx, uint32_t first, uint32_t count, float *offset_hz, float *phase_rad);
 /* Checkpoint: everything a ctx carries from one call to the next -- compiled channel constants and taps, NCO phases, FIR
  * history, DC / AGC / discriminator state, the waterfall's partial sums with their phase and N, the play_buffer
  * history -- as one blob of ssdr_checkpoint_size bytes (host memory).  Loading it into a ctx of the same channel count

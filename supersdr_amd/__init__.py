@@ -6,7 +6,7 @@ C-ABI in include/ssdr.h; the Python host goes in front of the reference's own ki
 kiwi_sound classes (supersdr_amd.workers: bind(), IQHub, GpuStream) and its kiwiclient hook
 (supersdr_amd.iqstream: IQBatcher).
 """
-from ._lib import (NFFT, FRAME, RATE, NTAP_MAX, HIST, MODE_AM, MODE_LSB, MODE_USB, MODE_CW, MODE_NBFM,
+from ._lib import (NFFT, FRAME, RATE, NTAP_MAX, HIST, MODE_AM, MODE_LSB, MODE_USB, MODE_CW, MODE_NBFM, MODE_SAM,
                    MODE_BY_NAME, ChanParams, SsdrError, LIB_PATH)
 from .engine import SsdrEngine, default_params, compile_params, table
 

@@ -11,8 +11,12 @@ LIB_PATH = os.environ.get("SSDR_LIB_PATH") or os.path.join(_HERE, "libssdr.so") 
 
 NFFT, FRAME, RATE, NTAP_MAX, HIST = 1024, 512, 12000, 128, 128
 OK, EINVAL, ENOMEM, EHIP, ENODEV, ESTATE = 0, -1, -2, -3, -4, -5
-MODE_AM, MODE_LSB, MODE_USB, MODE_CW, MODE_NBFM, MODE_IQ = range(6)
-MODE_BY_NAME = {"am": 0, "lsb": 1, "usb": 2, "cw": 3, "nbfm": 4, "nfm": 4, "iq": 5}
+MODE_AM, MODE_LSB, MODE_USB, MODE_CW, MODE_NBFM, MODE_IQ, MODE_SAM = range(7)
+# "sam", "sal", "sau": one demodulator (SSDR_MODE_SAM), the passband picks both sidebands or one
+MODE_BY_NAME = {"am": 0, "lsb": 1, "usb": 2, "cw": 3, "nbfm": 4, "nfm": 4, "iq": 5, "sam": 6, "sal": 6, "sau": 6}
+# Default passbands of the three names, Hz.  The KiwiSDR's own defaults as remembered; the reference has none for these modes, so
+# they are this project's choice.
+SAM_PASSBANDS = {"sam": (-4900.0, 4900.0), "sal": (-4900.0, 0.0), "sau": (0.0, 4900.0)}
 K_WF, K_AUDIO, K_SYNTH, K_DB2COL, K_PLAY, K_WIRE, K_TRACE, K_SMETER, K_FUSED, K_ZOOM, K_ADPCM, K_SQUELCH = range(12)
 T_WINDOW, T_TWIDDLE_RE, T_TWIDDLE_IM, T_DB_THRESH = range(4)
 
@@ -241,6 +245,8 @@ _SIGS = {
     "ssdr_get_consts": (C.c_int, [_P, C.c_uint32, C.c_uint32, _P, _P]),
     "ssdr_get_state": (C.c_int, [_P, C.c_uint32, C.c_uint32, _P, _P]),
     "ssdr_set_state": (C.c_int, [_P, C.c_uint32, C.c_uint32, _P, _P]),
+    "ssdr_get_sam_carrier": (C.c_int, [_P, C.c_uint32, C.c_uint32, _P, _P]),
+    "ssdr_get_subrx_sam_carrier": (C.c_int, [_P, C.c_uint32, C.c_uint32, _P, _P]),
     "ssdr_checkpoint_size": (C.c_int, [_P, C.POINTER(C.c_uint64)]),
     "ssdr_checkpoint_save": (C.c_int, [_P, _P]),
     "ssdr_checkpoint_load": (C.c_int, [_P, _P, C.c_uint64]),
@@ -263,7 +269,7 @@ _NEWER_THAN_AB_LIBS = ("ssdr_feed_collect_listen", "ssdr_set_subrx", "ssdr_get_s
                        "ssdr_get_channelizer", "ssdr_channelizer_reset", "ssdr_push_wideband", "ssdr_get_channelizer_state",
                        "ssdr_channelizer_stats", "ssdr_set_wb_scopes", "ssdr_get_wb_scopes", "ssdr_wb_scope_lines", "ssdr_read_wb_scope",
                        "ssdr_wb_scope_taps", "ssdr_wb_scope_stats", "ssdr_set_wb_scope_detectors", "ssdr_get_wb_scope_detectors",
-                       "ssdr_wb_scope_windows", "ssdr_read_wb_scope_windows")      # entry points a library named by SSDR_LIB_PATH (A/B builds only) may predate
+                       "ssdr_wb_scope_windows", "ssdr_read_wb_scope_windows", "ssdr_get_sam_carrier", "ssdr_get_subrx_sam_carrier")      # entry points a library named by SSDR_LIB_PATH (A/B builds only) may predate
 
 
 def _load():

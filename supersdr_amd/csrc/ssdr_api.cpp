@@ -5,6 +5,7 @@
 #include "ssdr_resample_taps.h"
 #include <algorithm>
 #include <cmath>
+#include <cstddef>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -113,14 +114,15 @@ struct ssdr_ctx {
     uint32_t *d_chan_list = nullptr;                    // channels sorted by audio frame path (ssdr_audio_path)
     uint32_t *d_ws_list = nullptr;                      // [n_ch] + 1 ticket word: the same channels as pairs, the paths interleaved (ssdr_chain_ws_kernel)
     uint32_t ws_ticket = 0;                             // where the ticket word stands (it only counts up: SsdrFusedArgs)
-    uint32_t path_off[SSDR_PATH_COUNT] = {}, path_n[SSDR_PATH_COUNT] = {};
+    uint32_t path_off[SSDR_GROUP_COUNT] = {}, path_n[SSDR_GROUP_COUNT] = {};     // by launch group: the three paths, then SSDR_GROUP_SAM
     bool chan_list_dirty = true;
     bool summary_dirty = true;                          // path counts / any channel in IQ mode: recounted after the constants change
     uint32_t sum_paths[SSDR_PATH_COUNT] = {0, 0, 0};
+    uint32_t sum_sam = 0;                               // channels in SSDR_MODE_SAM (counted among the general path's)
     bool sum_any_iq = false;
     uint32_t sum_hang = 0;                              // channels whose AGC hangs (hang_frames != 0): which fused AM kernel runs
-    hipStream_t path_stream[SSDR_PATH_COUNT - 1] = {};  // the audio kernels of different paths run side by side
-    hipEvent_t ev_fork = nullptr, ev_path[SSDR_PATH_COUNT - 1] = {};
+    hipStream_t path_stream[SSDR_GROUP_COUNT - 1] = {};  // the audio kernels of different paths run side by side
+    hipEvent_t ev_fork = nullptr, ev_path[SSDR_GROUP_COUNT - 1] = {};
     int fused_enabled = 1;                              // ssdr_set_fused: 0 never, 1 at hop 1024 (default), 2 at hop 512 as well, 3 + the wave-specialised kernel
     uint32_t ws_grid = 0;
     uint32_t am_floor = 0, ws_floor = 0;                // ssdr_set_chain_floors: fewest channels for which ssdr_run_chain's default takes a one-read kernel
@@ -233,9 +235,9 @@ struct ssdr_ctx {
     uint32_t nb_on = 0;                                 // channels whose blanker is on
     uint64_t nb_gen = 0;                                // counts the changes of which channels blank
     SsdrNbChan *d_nb = nullptr;                         // [n_ch] gate in samples, threshold, carried sums and samples left to blank
-    uint32_t nb_off[SSDR_PATH_COUNT] = {}, nb_n[SSDR_PATH_COUNT] = {};     // d_chan_list behind the paths' lists: the blanking channels by path
-    hipStream_t nb_stream[SSDR_PATH_COUNT] = {};        // their kernels beside the others (with path_stream: five side streams at most)
-    hipEvent_t ev_nb[SSDR_PATH_COUNT] = {};
+    uint32_t nb_off[SSDR_GROUP_COUNT] = {}, nb_n[SSDR_GROUP_COUNT] = {};     // d_chan_list behind the paths' lists: the blanking channels by path
+    hipStream_t nb_stream[SSDR_GROUP_COUNT] = {};       // their kernels beside the others (with path_stream: seven side streams at most)
+    hipEvent_t ev_nb[SSDR_GROUP_COUNT] = {};
     uint8_t *d_nb_mask = nullptr;                       // [n_ch][n_frames * 64 D] blank mask of the last audio run
     size_t nb_mask_bytes = 0;
     bool nb_mask_valid = false;                         // the last ssdr_run_audio ran the blanker
@@ -543,11 +545,11 @@ void ssdr_destroy(ssdr_ctx *c)
     if (c->ev_in) (void)hipEventDestroy(c->ev_in);
     if (c->ev_a) (void)hipEventDestroy(c->ev_a);
     if (c->ev_fork) (void)hipEventDestroy(c->ev_fork);
-    for (int i = 0; i < SSDR_PATH_COUNT - 1; i++) {
+    for (int i = 0; i < SSDR_GROUP_COUNT - 1; i++) {
         if (c->path_stream[i]) { (void)hipStreamSynchronize(c->path_stream[i]); (void)hipStreamDestroy(c->path_stream[i]); }
         if (c->ev_path[i]) (void)hipEventDestroy(c->ev_path[i]);
     }
-    for (int i = 0; i < SSDR_PATH_COUNT; i++) {
+    for (int i = 0; i < SSDR_GROUP_COUNT; i++) {
         if (c->nb_stream[i]) { (void)hipStreamSynchronize(c->nb_stream[i]); (void)hipStreamDestroy(c->nb_stream[i]); }
         if (c->ev_nb[i]) (void)hipEventDestroy(c->ev_nb[i]);
     }
@@ -557,7 +559,7 @@ void ssdr_destroy(ssdr_ctx *c)
 
 int ssdr_default_params(int mode, ssdr_chan_params *p) SSDR_GUARD
 {
-    if (!p || mode < SSDR_MODE_AM || mode > SSDR_MODE_IQ) return SSDR_EINVAL;
+    if (!p || mode < SSDR_MODE_AM || mode > SSDR_MODE_SAM) return SSDR_EINVAL;
     memset(p, 0, sizeof *p);
     p->mode = mode;
     p->agc_on = 1;                    // utils_supersdr.py:937
@@ -574,6 +576,7 @@ int ssdr_default_params(int mode, ssdr_chan_params *p) SSDR_GUARD
     case SSDR_MODE_USB: p->low_cut = 30.0; p->high_cut = 3000.0; break;
     case SSDR_MODE_CW: p->low_cut = 400.0; p->high_cut = 800.0; break;
     case SSDR_MODE_IQ: p->low_cut = -5000.0; p->high_cut = 5000.0; break;       // kiwi/client.py:244-246
+    case SSDR_MODE_SAM: p->low_cut = -4900.0; p->high_cut = 4900.0; break;      // not in the reference: this project's choice
     default: p->low_cut = -6000.0; p->high_cut = 6000.0; break;
     }
     return SSDR_OK;
@@ -616,6 +619,14 @@ static int subrx_restart(ssdr_ctx *c, uint32_t first, uint32_t count);
 static int subrx_compile(const ssdr_ctx *c, const ssdr_subrx *subs, uint32_t count, uint32_t decim, uint32_t rate,
                          std::vector<ssdr_chan_consts> &k, std::vector<float> &taps);
 static int subrx_install(ssdr_ctx *c, const std::vector<ssdr_chan_consts> &k, const std::vector<float> &taps);
+
+// the carrier loop (ssdr_chan_state.pad) of n consecutive state rows to 0, queued on the main stream
+static int sam_loop_zero(ssdr_ctx *c, ssdr_chan_state *d_rows, size_t n)
+{
+    HIP_TRY(hipMemset2DAsync(reinterpret_cast<char *>(d_rows) + offsetof(ssdr_chan_state, pad), sizeof(ssdr_chan_state), 0,
+                             sizeof(((ssdr_chan_state *)nullptr)->pad), n, c->stream));
+    return SSDR_OK;
+}
 
 int ssdr_reset_state(ssdr_ctx *c, uint32_t first, uint32_t count) SSDR_GUARD
 {
@@ -669,6 +680,9 @@ int ssdr_set_params(ssdr_ctx *c, uint32_t first, uint32_t count, const ssdr_chan
             const ssdr_deemp_params &q = c->h_de[first + i];
             if ((q.am || q.nfm) && c->h_consts[first + i].mode != k[i].mode) de_reset.push_back(first + i);
         }
+    std::vector<uint32_t> sam_start;                        // channels that move into synchronous AM: their carrier loop starts at 0
+    for (uint32_t i = 0; i < count; i++)
+        if (k[i].mode == SSDR_MODE_SAM && c->h_consts[first + i].mode != SSDR_MODE_SAM) sam_start.push_back(first + i);
     for (uint32_t i = 0; i < count; i++) c->h_params[first + i] = p[i];
     for (uint32_t i = 0; i < count; i++) c->h_consts[first + i] = k[i];
     c->chan_list_dirty = true;
@@ -680,6 +694,7 @@ int ssdr_set_params(ssdr_ctx *c, uint32_t first, uint32_t count, const ssdr_chan
     if (!sq_reset.empty()) { c->sq_dirty = true; c->own.sq_valid = false; }
     SSDR_TRY(for_each_run(de_reset.data(), de_reset.size(), [&](size_t i, size_t n) { return deemp_reset(c, de_reset[i], (uint32_t)n); }));
     if (!de_reset.empty()) c->de_dirty = true;
+    SSDR_TRY(for_each_run(sam_start.data(), sam_start.size(), [&](size_t i, size_t n) { return sam_loop_zero(c, c->d_state + sam_start[i], n); }));
     HIP_TRY(hipMemcpyAsync(c->d_consts + first, k.data(), count * sizeof(ssdr_chan_consts), hipMemcpyHostToDevice, c->stream));
     HIP_TRY(hipMemcpyAsync(c->d_taps + (size_t)first * SSDR_NTAP_MAX, taps.data(), taps.size() * sizeof(float),
                            hipMemcpyHostToDevice, c->stream));
@@ -734,7 +749,7 @@ int ssdr_create(int device_id, uint32_t n_channels, uint32_t nfft, uint32_t fram
         c->h_consts.resize(n_channels);
         c->h_params.resize(n_channels);
         HIP_TRY(hipEventCreateWithFlags(&c->ev_fork, hipEventDisableTiming));
-        for (int i = 0; i < SSDR_PATH_COUNT - 1; i++) {
+        for (int i = 0; i < SSDR_GROUP_COUNT - 1; i++) {
             HIP_TRY(hipStreamCreateWithFlags(&c->path_stream[i], hipStreamNonBlocking));
             HIP_TRY(hipEventCreateWithFlags(&c->ev_path[i], hipEventDisableTiming));
         }
@@ -817,6 +832,9 @@ int ssdr_set_decimation(ssdr_ctx *c, uint32_t decim) SSDR_GUARD
     if (!c || (decim != 1 && decim != 2 && decim != 4)) return SSDR_EINVAL;
     if (!c->feed.empty()) return SSDR_ESTATE;
     if (decim == c->decim) return SSDR_OK;
+    if (decim > 1)                                                // synchronous AM has no decimating front end: nothing changes
+        for (const ssdr_chan_params &q : c->h_params)
+            if (q.mode == SSDR_MODE_SAM) return SSDR_ESTATE;
     HIP_TRY(hipSetDevice(c->device));
     std::vector<ssdr_chan_consts> sub_k;                          // the sub-receivers at the new rate, before anything changes
     std::vector<float> sub_taps;
@@ -1032,11 +1050,13 @@ static void chan_summary(ssdr_ctx *c)
     for (int p = 0; p < SSDR_PATH_COUNT; p++) c->sum_paths[p] = 0;
     c->sum_any_iq = false;
     c->sum_hang = 0;
+    c->sum_sam = 0;
     for (uint32_t ch = 0; ch < c->n_ch; ch++) {
         const int path = ssdr_audio_path(c->h_consts[ch]);
         c->sum_paths[path]++;
         c->sum_any_iq = c->sum_any_iq || c->h_consts[ch].mode == SSDR_MODE_IQ;
         c->sum_hang += c->h_consts[ch].hang_frames != 0;
+        c->sum_sam += c->h_consts[ch].mode == SSDR_MODE_SAM;
     }
     c->summary_dirty = false;
 }
@@ -1048,13 +1068,13 @@ static int ensure_chan_list(ssdr_ctx *c, hipStream_t s)
     if (!c->chan_list_dirty) return SSDR_OK;
     std::vector<uint32_t> list(c->n_ch);
     // the paths' lists, then the lists of the channels that blank, by path (empty while no channel blanks: the list is the same)
-    uint32_t pos = 0, off[2 * SSDR_PATH_COUNT], cnt[2 * SSDR_PATH_COUNT];
-    for (int g = 0; g < 2 * SSDR_PATH_COUNT; g++) {
-        const int p = g % SSDR_PATH_COUNT;
-        const bool blank = g >= SSDR_PATH_COUNT;
+    uint32_t pos = 0, off[2 * SSDR_GROUP_COUNT], cnt[2 * SSDR_GROUP_COUNT];
+    for (int g = 0; g < 2 * SSDR_GROUP_COUNT; g++) {
+        const int p = g % SSDR_GROUP_COUNT;
+        const bool blank = g >= SSDR_GROUP_COUNT;
         off[g] = pos;
         for (uint32_t ch = 0; ch < c->n_ch; ch++)
-            if (ssdr_audio_path(c->h_consts[ch]) == p && (c->nb_on && c->h_nb_thresh[ch] != 0) == blank) list[pos++] = ch;
+            if (ssdr_audio_group(c->h_consts[ch]) == p && (c->nb_on && c->h_nb_thresh[ch] != 0) == blank) list[pos++] = ch;
         cnt[g] = pos - off[g];
     }
     HIP_TRY(hipMemcpyAsync(c->d_chan_list, list.data(), (size_t)c->n_ch * sizeof(uint32_t), hipMemcpyHostToDevice, s));
@@ -1083,9 +1103,9 @@ static int ensure_chan_list(ssdr_ctx *c, hipStream_t s)
     HIP_TRY(hipMemcpyAsync(c->d_ws_list, ws.data(), ((size_t)c->n_ch + 1) * sizeof(uint32_t), hipMemcpyHostToDevice, s));
     c->ws_ticket = 0;
     HIP_TRY(hipStreamSynchronize(s));    // `list` goes out of scope
-    for (int p = 0; p < SSDR_PATH_COUNT; p++) {
+    for (int p = 0; p < SSDR_GROUP_COUNT; p++) {
         c->path_off[p] = off[p]; c->path_n[p] = cnt[p];
-        c->nb_off[p] = off[SSDR_PATH_COUNT + p]; c->nb_n[p] = cnt[SSDR_PATH_COUNT + p];
+        c->nb_off[p] = off[SSDR_GROUP_COUNT + p]; c->nb_n[p] = cnt[SSDR_GROUP_COUNT + p];
     }
     c->chan_list_dirty = false;
     return SSDR_OK;
@@ -1321,7 +1341,7 @@ static uint32_t deemp_coeff(uint32_t setting, uint32_t kiwi_rate)
 }
 static inline uint32_t deemp_acting(const ssdr_deemp_params &q, uint32_t mode)
 {
-    return mode == SSDR_MODE_NBFM ? q.nfm : (mode == SSDR_MODE_AM ? q.am : 0u);
+    return mode == SSDR_MODE_NBFM ? q.nfm : (mode == SSDR_MODE_AM || mode == SSDR_MODE_SAM ? q.am : 0u);
 }
 // S of channels [first, first + count) back to 0
 static int deemp_reset(ssdr_ctx *c, uint32_t first, uint32_t count)
@@ -1715,7 +1735,13 @@ static int subrx_launch(ssdr_ctx *c, Batch &b, const SsdrAudioArgs &au, hipStrea
     a.au.iq_out = nullptr;
     a.au.chan_list = nullptr; a.au.list_n = n;
     a.parent = c->d_sub_parent;
-    SSDR_TRY(timed_launch(c, kTimedSubRx, s, [&]() -> int { HIP_TRY(ssdr_launch_audio_sub(a, c->decim, s)); return SSDR_OK; }));
+    bool any_sam = false;                                  // rows in synchronous AM run the mode's own instantiation beside the others'
+    for (const ssdr_chan_consts &k : c->h_sub_consts) any_sam = any_sam || k.mode == SSDR_MODE_SAM;
+    SSDR_TRY(timed_launch(c, kTimedSubRx, s, [&]() -> int {
+        HIP_TRY(ssdr_launch_audio_sub(a, c->decim, s));
+        if (any_sam) HIP_TRY(ssdr_launch_audio_sub_sam(a, s));
+        return SSDR_OK;
+    }));
     c->sub_launches++;
     std::fill(c->h_sub_started.begin(), c->h_sub_started.end(), (uint8_t)1);
     b.sub_run_rows = n;
@@ -1761,6 +1787,7 @@ static int audio_stage(ssdr_ctx *c, Batch &b, ChainPlan plan, const SsdrWfArgs *
     a.rssi = b.d_rssi;
     a.flags = b.d_flags;
     a.iq_out = nullptr;
+    a.rate = c->kiwi_rate;
     c->iq_out_valid = false;
     {
         chan_summary(c);
@@ -1801,7 +1828,7 @@ static int audio_stage(ssdr_ctx *c, Batch &b, ChainPlan plan, const SsdrWfArgs *
         if (plan.one_read == 2) {
             const uint64_t need_g = ((uint64_t)c->n_ch + SSDR_WS_AUDIO_WAVES - 1) / SSDR_WS_AUDIO_WAVES;
             const uint32_t grid_g = (uint32_t)(need_g < c->ws_grid ? need_g : c->ws_grid);
-            HIP_TRY(ssdr_launch_chain_ws(fa, grid_g ? grid_g : 1, s));
+            HIP_TRY(ssdr_launch_chain_ws(fa, grid_g ? grid_g : 1, s, c->sum_sam != 0));
             c->ws_ticket += (uint32_t)pairs + (grid_g ? grid_g : 1) * (SSDR_WS_AUDIO_WAVES / 2);     // (wraps as the device word does)
         } else if (c->exact_bins) HIP_TRY(ssdr_launch_fused_exact_am(fa, c->d_tw64, s));
         else HIP_TRY(ssdr_launch_fused_am(fa, grid ? grid : 1, s, c->sum_hang != 0));
@@ -1828,15 +1855,15 @@ static int audio_stage(ssdr_ctx *c, Batch &b, ChainPlan plan, const SsdrWfArgs *
             HIP_TRY(ssdr_launch_audio_dec(a, c->decim, s));
         }
     } else {
-        // launch groups: the three paths, then the three paths' channels that blank (their kernels' blanker twins)
+        // launch groups: the three paths and synchronous AM, then the same groups' channels that blank (their kernels' blanker twins)
         int n_paths = 0, n_side = 0;
-        for (int g = 0; g < 2 * SSDR_PATH_COUNT; g++) n_paths += (g < SSDR_PATH_COUNT ? c->path_n[g] : c->nb_n[g - SSDR_PATH_COUNT]) != 0;
+        for (int g = 0; g < 2 * SSDR_GROUP_COUNT; g++) n_paths += (g < SSDR_GROUP_COUNT ? c->path_n[g] : c->nb_n[g - SSDR_GROUP_COUNT]) != 0;
         const bool side = n_paths > 1 && !c->audio_serial;
         if (side) HIP_TRY(hipEventRecord(c->ev_fork, s));
         bool first = true;
-        for (int g = 0; g < 2 * SSDR_PATH_COUNT; g++) {
-            const int p = g % SSDR_PATH_COUNT;
-            const bool blank = g >= SSDR_PATH_COUNT;
+        for (int g = 0; g < 2 * SSDR_GROUP_COUNT; g++) {
+            const int p = g % SSDR_GROUP_COUNT;
+            const bool blank = g >= SSDR_GROUP_COUNT;
             const uint32_t n = blank ? c->nb_n[p] : c->path_n[p];
             if (!n) continue;
             a.chan_list = c->d_chan_list + (blank ? c->nb_off[p] : c->path_off[p]);
@@ -1845,9 +1872,9 @@ static int audio_stage(ssdr_ctx *c, Batch &b, ChainPlan plan, const SsdrWfArgs *
             if (first || !side) {
                 HIP_TRY(blank ? ssdr_launch_audio_nb(na, p, s) : ssdr_launch_audio(a, p, s));
             } else {
-                const bool own = n_side < SSDR_PATH_COUNT - 1;
-                hipStream_t ps = own ? c->path_stream[n_side] : c->nb_stream[n_side - (SSDR_PATH_COUNT - 1)];
-                hipEvent_t pe = own ? c->ev_path[n_side] : c->ev_nb[n_side - (SSDR_PATH_COUNT - 1)];
+                const bool own = n_side < SSDR_GROUP_COUNT - 1;
+                hipStream_t ps = own ? c->path_stream[n_side] : c->nb_stream[n_side - (SSDR_GROUP_COUNT - 1)];
+                hipEvent_t pe = own ? c->ev_path[n_side] : c->ev_nb[n_side - (SSDR_GROUP_COUNT - 1)];
                 HIP_TRY(hipStreamWaitEvent(ps, c->ev_fork, 0));
                 HIP_TRY(blank ? ssdr_launch_audio_nb(na, p, ps) : ssdr_launch_audio(a, p, ps));
                 HIP_TRY(hipEventRecord(pe, ps));
@@ -1856,7 +1883,7 @@ static int audio_stage(ssdr_ctx *c, Batch &b, ChainPlan plan, const SsdrWfArgs *
             first = false;
         }
         for (int i = 0; i < n_side; i++)
-            HIP_TRY(hipStreamWaitEvent(s, i < SSDR_PATH_COUNT - 1 ? c->ev_path[i] : c->ev_nb[i - (SSDR_PATH_COUNT - 1)], 0));
+            HIP_TRY(hipStreamWaitEvent(s, i < SSDR_GROUP_COUNT - 1 ? c->ev_path[i] : c->ev_nb[i - (SSDR_GROUP_COUNT - 1)], 0));
     }
     SSDR_TRY(timed_end(c, SSDR_K_AUDIO, s));
     if (c->nb_on) {
@@ -2064,7 +2091,7 @@ int ssdr_set_noise_blanker(ssdr_ctx *c, uint32_t first, uint32_t count, const ui
     if (!c->d_nb) {                                         // first use: state, side streams
         c->h_nb_gate_us.assign(c->n_ch, 0u);
         c->h_nb_thresh.assign(c->n_ch, 0u);
-        for (int i = 0; i < SSDR_PATH_COUNT; i++) {
+        for (int i = 0; i < SSDR_GROUP_COUNT; i++) {
             if (!c->nb_stream[i]) HIP_TRY(hipStreamCreateWithFlags(&c->nb_stream[i], hipStreamNonBlocking));
             if (!c->ev_nb[i]) HIP_TRY(hipEventCreateWithFlags(&c->ev_nb[i], hipEventDisableTiming));
         }
@@ -2579,6 +2606,32 @@ int ssdr_get_state(ssdr_ctx *c, uint32_t first, uint32_t count, ssdr_chan_state 
     if (hist) HIP_TRY(hipMemcpyAsync(hist, c->d_hist + (size_t)first * SSDR_HIST, (size_t)count * SSDR_HIST * 4, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
     return SSDR_OK;
+} SSDR_UNGUARD
+
+// ssdr_get_sam_carrier / ssdr_get_subrx_sam_carrier: the loop of `count` state rows whose constants are k[0 .. count)
+static int sam_carrier_read(ssdr_ctx *c, const ssdr_chan_state *d_rows, const ssdr_chan_consts *k, uint32_t count, float *offset_hz, float *phase_rad)
+{
+    if (!count) return SSDR_OK;
+    HIP_TRY(hipSetDevice(c->device));
+    SSDR_TRY(join_audio(c));
+    std::vector<ssdr_chan_state> st(count);
+    HIP_TRY(hipMemcpyAsync(st.data(), d_rows, count * sizeof(ssdr_chan_state), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    const double two_pi = 6.283185307179586476925;
+    for (uint32_t i = 0; i < count; i++) {
+        const bool sam = k[i].mode == SSDR_MODE_SAM;
+        float om;
+        memcpy(&om, &st[i].pad[1], sizeof om);
+        offset_hz[i] = sam ? (float)((double)om * c->kiwi_rate / two_pi) : 0.0f;
+        if (phase_rad) phase_rad[i] = sam ? (float)((double)(int32_t)st[i].pad[0] * (two_pi / 4294967296.0)) : 0.0f;
+    }
+    return SSDR_OK;
+}
+
+int ssdr_get_sam_carrier(ssdr_ctx *c, uint32_t first, uint32_t count, float *offset_hz, float *phase_rad) SSDR_GUARD
+{
+    if (!c || !offset_hz || (uint64_t)first + count > c->n_ch) return SSDR_EINVAL;
+    return sam_carrier_read(c, c->d_state + first, c->h_consts.data() + first, count, offset_hz, phase_rad);
 } SSDR_UNGUARD
 
 int ssdr_set_state(ssdr_ctx *c, uint32_t first, uint32_t count, const ssdr_chan_state *state, const int16_t *hist) SSDR_GUARD
@@ -3493,6 +3546,7 @@ int ssdr_set_subrx(ssdr_ctx *c, const ssdr_subrx *subs, uint32_t count) SSDR_GUA
             HIP_TRY(hipMemcpyAsync(c->d_sub_state[to] + j, c->d_sub_state[from] + i, sizeof(ssdr_chan_state), d2d, c->stream));
             HIP_TRY(hipMemcpyAsync(c->d_sub_hist[to] + (size_t)j * SSDR_HIST, c->d_sub_hist[from] + i * SSDR_HIST, SSDR_HIST * 4, d2d, c->stream));
             HIP_TRY(hipMemcpyAsync(c->d_sub_phist[to] + (size_t)j * 8, c->d_sub_phist[from] + i * 8, 8 * sizeof(double), d2d, c->stream));
+            if (k[j].mode == SSDR_MODE_SAM && c->h_sub_consts[i].mode != SSDR_MODE_SAM) SSDR_TRY(sam_loop_zero(c, c->d_sub_state[to] + j, 1));
             started[j] = 1;
         } else {                                            // new, or kept but not run yet: it starts at ITS knee (ssdr_set_params)
             fresh[j] = subrx_fresh(k[j]);
@@ -3543,6 +3597,13 @@ int ssdr_get_subrx_state(ssdr_ctx *c, uint32_t first_row, uint32_t count, ssdr_c
     if (hist) HIP_TRY(hipMemcpyAsync(hist, c->d_sub_hist[set] + (size_t)first_row * SSDR_HIST, (size_t)count * SSDR_HIST * 4, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
     return SSDR_OK;
+} SSDR_UNGUARD
+
+int ssdr_get_subrx_sam_carrier(ssdr_ctx *c, uint32_t first_row, uint32_t count, float *offset_hz, float *phase_rad) SSDR_GUARD
+{
+    if (!c || !offset_hz || (uint64_t)first_row + count > c->h_sub.size()) return SSDR_EINVAL;
+    if (!count) return SSDR_OK;
+    return sam_carrier_read(c, c->d_sub_state[c->sub_set] + first_row, c->h_sub_consts.data() + first_row, count, offset_hz, phase_rad);
 } SSDR_UNGUARD
 
 int ssdr_get_subrx_consts(ssdr_ctx *c, uint32_t first_row, uint32_t count, ssdr_chan_consts *consts, float *taps) SSDR_GUARD

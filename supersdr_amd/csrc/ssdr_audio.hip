@@ -358,6 +358,21 @@ __global__ __launch_bounds__(SSDR_AUDIO_BLOCK) __attribute__((amdgpu_waves_per_e
                                       a.mask + (uint64_t)ch * a.au.n_frames * 64);
 }
 
+// Synchronous AM (SSDR_MODE_SAM): the general path with the carrier loop compiled in, over the list of the channels in that mode
+// (SSDR_GROUP_SAM) -- an instantiation of its own, so that the kernels above are what they were before the mode existed.  BLANK: its
+// noise-blanker twin.  The twin is held to three waves per SIMD: at four (128 registers) the loop on top of the blanker spills.
+template <bool BLANK>
+__global__ __launch_bounds__(SSDR_AUDIO_BLOCK) __attribute__((amdgpu_waves_per_eu(BLANK ? 3 : SSDR_AUDIO_WAVES, 8))) void ssdr_audio_sam_kernel(SsdrNbArgs a)
+{
+    __shared__ __attribute__((aligned(16))) float2 s_z[NOCT * OCT];
+    __shared__ __attribute__((aligned(16))) float s_taps[SSDR_NTAP_MAX + 8];
+    const int l = threadIdx.x;
+    if (blockIdx.x >= a.au.list_n) return;
+    const uint32_t ch = a.au.chan_list[blockIdx.x];
+    channel_frames<PATH_GENERAL, NoTap, BLANK, OwnRow, true>(a.au, ch, l, a.au.consts[ch], s_z, s_taps, NoTap(), a.nb,
+                                                             BLANK ? a.mask + (uint64_t)ch * a.au.n_frames * 64 : nullptr);
+}
+
 // Sub-receivers (ssdr_set_subrx): further audio chains on the raw IQ of a channel that has its own.  Wave r IS channel_frames /
 // channel_frames_dec on row r of the sub-receivers' own arrays (a.au: constants, taps, state, history, PCM, RSSI, flags); only the
 // input row is the parent's, parent[r] (validated on the host), read once per wave.  The list is short (SSDR_SUBRX_MAX waves at most:
@@ -372,10 +387,25 @@ __global__ __launch_bounds__(SSDR_AUDIO_BLOCK) __attribute__((amdgpu_waves_per_e
     if (r >= a.au.list_n) return;
     const RowAt in_row = {a.au.iq + (uint64_t)a.parent[r] * a.au.ch_stride};
     const ssdr_chan_consts kc = a.au.consts[r];
+    if (kc.mode == SSDR_MODE_SAM) return;                // ssdr_audio_sub_sam_kernel's row
     const int path = ssdr_audio_path(kc);                // wave-uniform
     if (path == SSDR_PATH_GENERAL) channel_frames<PATH_GENERAL, NoTap, false, RowAt>(a.au, r, l, kc, s_z, s_taps, NoTap(), nullptr, nullptr, in_row);
     else if (path == SSDR_PATH_DELAY4) channel_frames<PATH_DELAY4, NoTap, false, RowAt>(a.au, r, l, kc, s_z, s_taps, NoTap(), nullptr, nullptr, in_row);
     else channel_frames<PATH_AM_RAW, NoTap, false, RowAt>(a.au, r, l, kc, s_z, s_taps, NoTap(), nullptr, nullptr, in_row);
+}
+
+// the list's rows in SSDR_MODE_SAM (12 kHz / 20.25 kHz only: the mode has no decimating front end); every other row is the kernel's above
+__global__ __launch_bounds__(SSDR_AUDIO_BLOCK) __attribute__((amdgpu_waves_per_eu(1, 4))) void ssdr_audio_sub_sam_kernel(SsdrSubArgs a)
+{
+    __shared__ __attribute__((aligned(16))) float2 s_z[NOCT * OCT];
+    __shared__ __attribute__((aligned(16))) float s_taps[SSDR_NTAP_MAX + 8];
+    const int l = threadIdx.x;
+    const uint32_t r = blockIdx.x;
+    if (r >= a.au.list_n) return;
+    const ssdr_chan_consts kc = a.au.consts[r];
+    if (kc.mode != SSDR_MODE_SAM) return;
+    channel_frames<PATH_GENERAL, NoTap, false, RowAt, true>(a.au, r, l, kc, s_z, s_taps, NoTap(), nullptr, nullptr,
+                                                            RowAt{a.au.iq + (uint64_t)a.parent[r] * a.au.ch_stride});
 }
 
 template <int D>
@@ -489,6 +519,7 @@ hipError_t ssdr_launch_audio(const SsdrAudioArgs &a, int path, hipStream_t strea
     case SSDR_PATH_GENERAL: hipLaunchKernelGGL(ssdr_audio_kernel<PATH_GENERAL>, dim3(a.list_n), dim3(SSDR_AUDIO_BLOCK), 0, stream, a); break;
     case SSDR_PATH_DELAY4: hipLaunchKernelGGL(ssdr_audio_kernel<PATH_DELAY4>, dim3(a.list_n), dim3(SSDR_AUDIO_BLOCK), 0, stream, a); break;
     case SSDR_PATH_AM_RAW: hipLaunchKernelGGL(ssdr_audio_kernel<PATH_AM_RAW>, dim3(a.list_n), dim3(SSDR_AUDIO_BLOCK), 0, stream, a); break;
+    case SSDR_GROUP_SAM: hipLaunchKernelGGL(ssdr_audio_sam_kernel<false>, dim3(a.list_n), dim3(SSDR_AUDIO_BLOCK), 0, stream, SsdrNbArgs{a, nullptr, nullptr}); break;
     default: return hipErrorInvalidValue;
     }
     return hipGetLastError();
@@ -510,6 +541,7 @@ hipError_t ssdr_launch_audio_nb(const SsdrNbArgs &a, int path, hipStream_t strea
     case SSDR_PATH_GENERAL: hipLaunchKernelGGL(ssdr_audio_nb_kernel<PATH_GENERAL>, grid, block, 0, stream, a); break;
     case SSDR_PATH_DELAY4: hipLaunchKernelGGL(ssdr_audio_nb_kernel<PATH_DELAY4>, grid, block, 0, stream, a); break;
     case SSDR_PATH_AM_RAW: hipLaunchKernelGGL(ssdr_audio_nb_kernel<PATH_AM_RAW>, grid, block, 0, stream, a); break;
+    case SSDR_GROUP_SAM: hipLaunchKernelGGL(ssdr_audio_sam_kernel<true>, grid, block, 0, stream, a); break;
     default: return hipErrorInvalidValue;
     }
     return hipGetLastError();
@@ -532,6 +564,13 @@ hipError_t ssdr_launch_audio_sub(const SsdrSubArgs &a, uint32_t decim, hipStream
     else if (decim == 2) hipLaunchKernelGGL(ssdr_audio_sub_dec_kernel<2>, grid, block, 0, stream, a);
     else if (decim == 4) hipLaunchKernelGGL(ssdr_audio_sub_dec_kernel<4>, grid, block, 0, stream, a);
     else return hipErrorInvalidValue;
+    return hipGetLastError();
+}
+
+hipError_t ssdr_launch_audio_sub_sam(const SsdrSubArgs &a, hipStream_t stream)
+{
+    if (!a.au.list_n) return hipSuccess;
+    hipLaunchKernelGGL(ssdr_audio_sub_sam_kernel, dim3(a.au.list_n), dim3(SSDR_AUDIO_BLOCK), 0, stream, a);
     return hipGetLastError();
 }
 

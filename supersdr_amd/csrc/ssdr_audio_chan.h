@@ -44,7 +44,9 @@ enum { PATH_GENERAL = SSDR_PATH_GENERAL, PATH_DELAY4 = SSDR_PATH_DELAY4, PATH_AM
 // blanker state, nb_mask: its mask row.  A separate instantiation: the kernels without it are the same code as before it existed.
 // Row: where the frames are read from -- row `ch` of a.iq (OwnRow), or another row of it while constants, state and results are
 // row `ch` of arrays of their own (RowAt: a sub-receiver on its parent channel's IQ, ssdr_audio_sub_kernel).
-template <int PATH, typename Tap = NoTap, bool BLANK = false, typename Row = OwnRow>
+// SAM: the instantiation knows SSDR_MODE_SAM (general path only; demod_sam).  Without it the mode's code does not exist, and a
+// channel in that mode must not reach the instantiation (ssdr_audio_group).
+template <int PATH, typename Tap = NoTap, bool BLANK = false, typename Row = OwnRow, bool SAM = false>
 SSDR_DEV void channel_frames(const SsdrAudioArgs &a, const uint32_t ch, const int l, const ssdr_chan_consts &kc,
                              float2 *s_z, float *s_taps, const Tap &tap = Tap(), SsdrNbChan *nb = nullptr, uint8_t *nb_mask = nullptr,
                              const Row &in_row = Row())
@@ -134,7 +136,7 @@ SSDR_DEV void channel_frames(const SsdrAudioArgs &a, const uint32_t ch, const in
     for (uint32_t f = 0; f < a.n_frames; f++, src += SSDR_FRAME, dst += SSDR_FRAME) {
         if ((f & 63u) == 0) {                               // the next 64 frames' phasors, one per lane
             if constexpr (PATH != PATH_AM_RAW) nco_frame_table(n1, phi1, l);
-            if constexpr (PATH != PATH_AM_RAW) if (mode >= SSDR_MODE_LSB && mode <= SSDR_MODE_CW) nco_frame_table(n2, phi2, l);
+            if constexpr (PATH != PATH_AM_RAW) if ((mode >= SSDR_MODE_LSB && mode <= SSDR_MODE_CW) || (SAM && mode == SSDR_MODE_SAM)) nco_frame_table(n2, phi2, l);
         }
         if constexpr (Tap::PREFETCH) {
             raw0 = nxt0;
@@ -250,6 +252,15 @@ SSDR_DEV void channel_frames(const SsdrAudioArgs &a, const uint32_t ch, const in
                 demod_ssb(yr, yi, b2c, b2s, cs2, ss2, aud);
             }
             else if (mode == SSDR_MODE_NBFM) demod_fm(yr, yi, prev_re, prev_im, kc.kfm, aud);
+            else if (SAM && mode == SSDR_MODE_SAM) {        // the carrier loop lives in the state's two spare words (ssdr.h)
+                if constexpr (SAM) {
+                    float b2c, b2s, om = __uint_as_float(st.pad[1]);
+                    nco_block(n2, f, b2c, b2s);
+                    demod_sam(yr, yi, b2c, b2s, cs2, ss2, l, a.rate == SSDR_RATE_WIDE ? sam_consts(SSDR_RATE_WIDE) : sam_consts(SSDR_RATE),
+                              st.pad[0], om, dc, aud);
+                    st.pad[1] = __float_as_uint(om);
+                }
+            }
             else {                                          // SSDR_MODE_IQ: no demodulator, the PCM row carries I
 #pragma unroll
                 for (int j = 0; j < 8; j++) aud[j] = yr[j];

@@ -255,6 +255,78 @@ SSDR_DEV void demod_fm(const float (&yr)[8], const float (&yi)[8], float prev_re
     }
 }
 
+// Synchronous AM (SSDR_MODE_SAM; the definition is tests/sam_ref.py).  The loop's constants depend on the
+// ctx's rate alone: T_u = 8 / rate, alpha = 2 zeta w_N T_u, beta = w_N^2 T_u / rate, w_max = 2 pi 500 / rate; w_N = 250 rad/s, zeta = 1.
+// theta is a 32-bit phase (it wraps by itself and feeds ssdr_phasor32), omega a float in radians per sample; a phase step is formed in
+// units of 2 pi / 2^32 as two separately rounded integers, 8 omega and alpha e, because their sum may pass half a turn.
+struct SamK { float alpha_u, beta, wmax, eight_u; };
+constexpr double SAM_WN = 250.0, SAM_ZETA = 1.0, SAM_PULL_HZ = 500.0, SAM_PI = 3.14159265358979323846;
+constexpr double SAM_U_PER_RAD = 4294967296.0 / (2.0 * SAM_PI);
+constexpr SamK sam_consts(double rate)
+{
+    return {(float)(2.0 * SAM_ZETA * SAM_WN * 8.0 / rate * SAM_U_PER_RAD), (float)(SAM_WN * SAM_WN * 8.0 / rate / rate),
+            (float)(2.0 * SAM_PI * SAM_PULL_HZ / rate), (float)(8.0 * SAM_U_PER_RAD)};
+}
+SSDR_DEV uint32_t sam_phase_u(float rad_times_scale) { return (uint32_t)__float2int_rn(rad_times_scale); }
+
+// v = y e^{+j phi2} puts the tuned carrier at 0 Hz (demod_ssb's second NCO); u[n] = v[n] e^{-j omega0 n} takes the loop's frequency at
+// the frame's start out of the lane's eight samples -- one rotation chain for both, block phasor (c, s) and step S2 conj(W) -- and
+// T = sum u is the lane's block sum, in parallel.  The 64-step chain then runs on wave-uniform values: lane b's T, one phasor of theta,
+// one arctangent, the two updates; lane b keeps theta_b.  After it every lane rotates its eight u by its own theta_b, and AM's DC scan
+// (demod_am's recurrence and its affine scan across the lanes, on I instead of the envelope) gives the audio.
+SSDR_DEV void demod_sam(const float (&yr)[8], const float (&yi)[8], float c, float s, float cs2, float ss2, int l, const SamK &k,
+                        uint32_t &theta, float &omega, float &dc, float (&aud)[8])
+{
+    constexpr float DC_APOW[8] = SSDR_DC_APOW_INIT;
+    float wc, ws, cs, ss;
+    ssdr_phasor32(sam_phase_u(omega * (float)SAM_U_PER_RAD), wc, ws);
+    phasor_mul(cs2, ss2, wc, -ws, cs, ss);
+    float ur[8], ui[8];
+    float tr = 0.0f, ti = 0.0f;
+#pragma unroll
+    for (int j = 0; j < 8; j++) {
+        ur[j] = fmaf(yr[j], c, -(yi[j] * s));        // y * (c + j s)
+        ui[j] = fmaf(yi[j], c, yr[j] * s);
+        tr = tr + ur[j];
+        ti = ti + ui[j];
+        const float cn = fmaf(c, cs, -(s * ss)), sn = fmaf(s, cs, c * ss);
+        c = cn; s = sn;
+    }
+    uint32_t th = theta, th_lane = 0;
+    float om = omega;
+#pragma unroll 1
+    for (uint32_t b = 0; b < 64; b++) {
+        const float Tr = lane_f(tr, b), Ti = lane_f(ti, b);
+        float pc, ps;
+        ssdr_phasor32(th, pc, ps);
+        const float e = ssdr_atan2p(fmaf(Ti, pc, -(Tr * ps)), fmaf(Tr, pc, Ti * ps));       // angle of T e^{-j theta}; 0 for T = 0
+        th_lane = (uint32_t)l == b ? th : th_lane;
+        th += sam_phase_u(om * k.eight_u) + sam_phase_u(e * k.alpha_u);
+        om = __builtin_amdgcn_fmed3f(fmaf(k.beta, e, om), -k.wmax, k.wmax);
+    }
+    theta = th;
+    omega = om;
+    float pc, ps, I[8], loc[8];
+    ssdr_phasor32(th_lane, pc, ps);
+    float m = 0.0f;
+#pragma unroll
+    for (int j = 0; j < 8; j++) {
+        I[j] = fmaf(ur[j], pc, ui[j] * ps);          // Re{u e^{-j theta_b}}
+        m = fmaf(SSDR_DC_A, m, SSDR_DC_AL * I[j]);
+        loc[j] = m;
+    }
+    float Asc = DC_APOW[7], Bsc = m;
+    scan_affine(Asc, Bsc);
+    const float Ae = from_prev_lane(1.0f, Asc), Be = from_prev_lane(0.0f, Bsc);
+    const float carry = fmaf(Ae, dc, Be);
+#pragma unroll
+    for (int j = 0; j < 8; j++) {
+        m = fmaf(DC_APOW[j], carry, loc[j]);
+        aud[j] = I[j] - m;
+    }
+    dc = lane63(m);
+}
+
 SSDR_DEV float block_peak(const float (&p)[8])
 {
     return vmax3(vmax3(vmax3(p[0], p[1], p[2]), p[3], p[4]), vmax3(p[5], p[6], p[7]), SSDR_P_FLOOR);

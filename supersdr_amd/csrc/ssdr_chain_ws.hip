@@ -35,6 +35,7 @@
 // instruction, HBM traffic 1.02 x the fused budget; +2 % against the two stages side by side where every channel filters, a tie on
 // all-SSB, -0.6 ... -1.5 % with full-band channels in the batch: both schedules sit at the board's power cap and spend the same joules.
 // ssdr_run_chain takes it by default where every channel runs the general path, from 32 768 channels on (ssdr_api.cpp).
+#include <algorithm>
 #include "ssdr_math.h"
 #include "ssdr_kernels.h"
 #include "ssdr_audio_dev.h"
@@ -107,7 +108,9 @@ SSDR_DEV int dev_audio_path(const ssdr_chan_consts &k)          // ssdr_kernels.
     return k.mode == SSDR_MODE_AM ? PATH_AM_RAW : PATH_DELAY4;
 }
 
-template <bool AVG>
+// SAM: the audio waves' general path knows SSDR_MODE_SAM (ssdr_audio_chan.h).  The carrier loop costs the kernel six registers and
+// 0.4 % on a batch without the mode, so batches without a SAM channel keep the kernel that does not know it (ssdr_launch_chain_ws).
+template <bool AVG, bool SAM>
 __global__ __launch_bounds__(SSDR_WS_BLOCK) void ssdr_chain_ws_kernel(SsdrFusedArgs fa)
 {
     __shared__ __attribute__((aligned(16))) unsigned char smem[LDS_TOTAL];
@@ -142,7 +145,7 @@ __global__ __launch_bounds__(SSDR_WS_BLOCK) void ssdr_chain_ws_kernel(SsdrFusedA
             const ssdr_chan_consts &kc = u.consts[ch];
             const RingTap tap = {smem + LDS_RING + wave * RING_BYTES, prod + wave, cons + wave, k0, lane};
             const int path = __builtin_amdgcn_readfirstlane(dev_audio_path(kc));
-            if (path == PATH_GENERAL) channel_frames<PATH_GENERAL>(u, ch, lane, kc, s_z, s_taps, tap);
+            if (path == PATH_GENERAL) channel_frames<PATH_GENERAL, RingTap, false, OwnRow, SAM>(u, ch, lane, kc, s_z, s_taps, tap);
             else if (path == PATH_DELAY4) channel_frames<PATH_DELAY4>(u, ch, lane, kc, s_z, s_taps, tap);
             else channel_frames<PATH_AM_RAW>(u, ch, lane, kc, s_z, s_taps, tap);
             lds_sync();                                          // (the next channel's prologue writes the work area again)
@@ -244,18 +247,24 @@ __global__ __launch_bounds__(SSDR_WS_BLOCK) void ssdr_chain_ws_kernel(SsdrFusedA
 
 } // namespace
 
-hipError_t ssdr_launch_chain_ws(const SsdrFusedArgs &a, uint32_t grid, hipStream_t stream)
+hipError_t ssdr_launch_chain_ws(const SsdrFusedArgs &a, uint32_t grid, hipStream_t stream, bool any_sam)
 {
-    if (a.wf.n_avg > 1) hipLaunchKernelGGL((ssdr_chain_ws_kernel<true>), dim3(grid), dim3(SSDR_WS_BLOCK), 0, stream, a);
-    else hipLaunchKernelGGL((ssdr_chain_ws_kernel<false>), dim3(grid), dim3(SSDR_WS_BLOCK), 0, stream, a);
+    const dim3 g(grid), b(SSDR_WS_BLOCK);
+    if (any_sam) {
+        if (a.wf.n_avg > 1) hipLaunchKernelGGL((ssdr_chain_ws_kernel<true, true>), g, b, 0, stream, a);
+        else hipLaunchKernelGGL((ssdr_chain_ws_kernel<false, true>), g, b, 0, stream, a);
+    } else if (a.wf.n_avg > 1) hipLaunchKernelGGL((ssdr_chain_ws_kernel<true, false>), g, b, 0, stream, a);
+    else hipLaunchKernelGGL((ssdr_chain_ws_kernel<false, false>), g, b, 0, stream, a);
     return hipGetLastError();
 }
 
 hipError_t ssdr_chain_ws_blocks_per_cu(int *blocks)
 {
-    int b0 = 0, b1 = 0;
-    hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&b0, ssdr_chain_ws_kernel<false>, SSDR_WS_BLOCK, 0);
-    if (e == hipSuccess) e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&b1, ssdr_chain_ws_kernel<true>, SSDR_WS_BLOCK, 0);
-    *blocks = b0 < b1 ? b0 : b1;
+    int b0 = 0, b1 = 0, b2 = 0, b3 = 0;
+    hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&b0, ssdr_chain_ws_kernel<false, false>, SSDR_WS_BLOCK, 0);
+    if (e == hipSuccess) e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&b1, ssdr_chain_ws_kernel<true, false>, SSDR_WS_BLOCK, 0);
+    if (e == hipSuccess) e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&b2, ssdr_chain_ws_kernel<false, true>, SSDR_WS_BLOCK, 0);
+    if (e == hipSuccess) e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&b3, ssdr_chain_ws_kernel<true, true>, SSDR_WS_BLOCK, 0);
+    *blocks = std::min(std::min(b0, b1), std::min(b2, b3));
     return e;
 }

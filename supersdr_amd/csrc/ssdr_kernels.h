@@ -54,6 +54,7 @@ struct SsdrAudioArgs {
     uint32_t *iq_out;                        // [n_ch][n_frames*512] I | Q << 16 of channels in SSDR_MODE_IQ, or null
     const uint32_t *chan_list;               // channels of this launch (one frame path), list_n of them
     uint32_t list_n;
+    uint32_t rate;                           // the ctx's rate, 12000 or 20250 (ssdr_set_kiwi_rate): SSDR_MODE_SAM's loop constants
 };
 // the impulse noise blanker of one channel (ssdr_set_noise_blanker): gate in input samples and threshold (both 0: off), the
 // unblanked frame sums S_{f-1}, S_{f-2} and the samples still to blank at the start of the next frame.  32 B.
@@ -64,13 +65,18 @@ struct SsdrNbArgs { SsdrAudioArgs au; SsdrNbChan *nb; uint8_t *mask; };
 // the audio kernels over a list of sub-receivers (ssdr_audio_sub_kernel / ssdr_audio_sub_dec_kernel, ssdr_set_subrx): row r of the
 // chain's arguments -- constants, taps, state, history, PCM, RSSI, flags, all [list_n] -- reads row parent[r] of au.iq
 struct SsdrSubArgs { SsdrAudioArgs au; const uint32_t *parent; };
-// frame paths of the audio kernel (ssdr_audio.hip): chosen per channel from its compiled constants
+// frame paths of the audio kernel (ssdr_audio.hip): chosen per channel from its compiled constants (SSDR_MODE_SAM compiles with
+// fir_flags 0: always the general path)
 enum { SSDR_PATH_GENERAL = 0, SSDR_PATH_DELAY4 = 1, SSDR_PATH_AM_RAW = 2, SSDR_PATH_COUNT = 3 };
+// launch groups of the stand-alone audio kernels: the three paths, and the general path's channels in SSDR_MODE_SAM, which run an
+// instantiation of their own (the carrier loop costs registers: the shipped instantiations stay what they were without it)
+enum { SSDR_GROUP_SAM = SSDR_PATH_COUNT, SSDR_GROUP_COUNT = SSDR_PATH_COUNT + 1 };
 __host__ __device__ static inline int ssdr_audio_path(const ssdr_chan_consts &k)
 {
     if (!(k.fir_flags & SSDR_FIR_DELAY4) || k.mode == SSDR_MODE_IQ) return SSDR_PATH_GENERAL;
     return k.mode == SSDR_MODE_AM ? SSDR_PATH_AM_RAW : SSDR_PATH_DELAY4;
 }
+static inline int ssdr_audio_group(const ssdr_chan_consts &k) { return k.mode == SSDR_MODE_SAM ? SSDR_GROUP_SAM : ssdr_audio_path(k); }
 
 struct SsdrSynthArgs {
     uint32_t *iq;
@@ -297,7 +303,7 @@ struct SsdrFusedArgs { SsdrWfArgs wf; SsdrAudioArgs au; uint32_t *ticket; uint32
 // tools/experiments/ssdr_chain_ws_knobs.patch.)
 #define SSDR_WS_AUDIO_WAVES 8
 #define SSDR_WS_BLOCK (64 * (SSDR_WS_AUDIO_WAVES + SSDR_WS_AUDIO_WAVES / 2))
-hipError_t ssdr_launch_chain_ws(const SsdrFusedArgs &a, uint32_t grid, hipStream_t stream);
+hipError_t ssdr_launch_chain_ws(const SsdrFusedArgs &a, uint32_t grid, hipStream_t stream, bool any_sam);   // any_sam: a channel in SSDR_MODE_SAM
 hipError_t ssdr_chain_ws_blocks_per_cu(int *blocks);
 hipError_t ssdr_launch_fused_am(const SsdrFusedArgs &a, uint32_t grid, hipStream_t stream, bool any_hang);   // any_hang: a channel with hang_frames != 0
 hipError_t ssdr_fused_blocks_per_cu(int *blocks);
@@ -308,11 +314,12 @@ hipError_t ssdr_launch_wf(const SsdrWfArgs &a, uint32_t grid, hipStream_t stream
 #define SSDR_TW64_N 752
 hipError_t ssdr_launch_wf_exact(const SsdrWfArgs &a, const double2 *tw, hipStream_t stream);   // ssdr_wf_exact.hip; chooses grid and a.grp_run itself
 hipError_t ssdr_wf_blocks_per_cu(int *blocks);
-hipError_t ssdr_launch_audio(const SsdrAudioArgs &a, int path, hipStream_t stream);
+hipError_t ssdr_launch_audio(const SsdrAudioArgs &a, int path, hipStream_t stream);                // path: a launch group, SSDR_GROUP_SAM included
 hipError_t ssdr_launch_audio_dec(const SsdrAudioArgs &a, uint32_t decim, hipStream_t stream);
 hipError_t ssdr_launch_audio_nb(const SsdrNbArgs &a, int path, hipStream_t stream);            // the channels of a.au.chan_list
 hipError_t ssdr_launch_audio_dec_nb(const SsdrNbArgs &a, uint32_t decim, hipStream_t stream);
 hipError_t ssdr_launch_audio_sub(const SsdrSubArgs &a, uint32_t decim, hipStream_t stream);   // every row of the list, any path (decim 1) or D = 2 / 4
+hipError_t ssdr_launch_audio_sub_sam(const SsdrSubArgs &a, hipStream_t stream);               // the list's SSDR_MODE_SAM rows, which the kernel above leaves alone
 hipError_t ssdr_launch_synth(const SsdrSynthArgs &a, hipStream_t stream);
 hipError_t ssdr_launch_sqrt_selftest(unsigned long long *mismatch, hipStream_t stream);
 hipError_t ssdr_launch_sqrt_values(const float *in, float *out_scaled, float *out_int, uint32_t n, hipStream_t stream);

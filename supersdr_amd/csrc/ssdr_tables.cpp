@@ -148,9 +148,11 @@ static uint32_t dphi_at(double f_hz, double fs)
 int ssdr_compile_params_host(const ssdr_chan_params *p, ssdr_chan_consts *c, float *taps, uint32_t decim, uint32_t rate_hz)
 {
     if (!p || !c || !taps) return SSDR_EINVAL;
-    if (p->mode < SSDR_MODE_AM || p->mode > SSDR_MODE_IQ) return SSDR_EINVAL;
+    if (p->mode < SSDR_MODE_AM || p->mode > SSDR_MODE_SAM) return SSDR_EINVAL;
     if (decim != 1 && decim != 2 && decim != 4) return SSDR_EINVAL;
     if (rate_hz != SSDR_RATE && rate_hz != SSDR_RATE_WIDE) return SSDR_EINVAL;
+    const bool sam = p->mode == SSDR_MODE_SAM;
+    if (sam && decim > 1) return SSDR_ESTATE;               // synchronous AM has no decimating front end (ssdr.h: ssdr_set_decimation)
     const double rate = (double)rate_hz;
     const double fs_in = rate * decim;
     // the tuning offset must lie inside the IQ band: beyond +-fs/2 the NCO step wraps mod 2^32 and the channel would
@@ -160,7 +162,7 @@ int ssdr_compile_params_host(const ssdr_chan_params *p, ssdr_chan_consts *c, flo
     if (!(std::fabs(p->wf_cal_db) <= 200.0)) return SSDR_EINVAL;
     std::memset(c, 0, sizeof *c);
     double f_bc, fl;
-    if (p->mode >= SSDR_MODE_LSB && p->mode <= SSDR_MODE_CW) {
+    if ((p->mode >= SSDR_MODE_LSB && p->mode <= SSDR_MODE_CW) || sam) {     // sam / sal / sau: the SSB rule, whichever sidebands the passband holds
         f_bc = 0.5 * (p->low_cut + p->high_cut);
         fl = 0.5 * std::fabs(p->high_cut - p->low_cut);
     } else {
@@ -197,7 +199,7 @@ int ssdr_compile_params_host(const ssdr_chan_params *p, ssdr_chan_consts *c, flo
     {
         int nz = 0;
         for (int i = 0; i < ntap; i++) nz += (taps[i] != 0.0f);
-        c->fir_flags = (nz == 1 && ntap > 4 && taps[4] == 1.0f && p->mode != SSDR_MODE_IQ) ? SSDR_FIR_DELAY4 : 0u;
+        c->fir_flags = (nz == 1 && ntap > 4 && taps[4] == 1.0f && p->mode != SSDR_MODE_IQ && !sam) ? SSDR_FIR_DELAY4 : 0u;
     }
     c->dphi1 = dphi_at(p->f_shift_hz + f_bc, fs_in);            // the mixer runs at the input rate,
     c->dphi2 = dphi_of(f_bc, rate);                             // the SSB re-mixer at the output rate

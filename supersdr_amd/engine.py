@@ -20,10 +20,13 @@ assert CONSTS_DTYPE.itemsize == 64 and STATE_DTYPE.itemsize == 64
 
 
 def default_params(mode="am", **over):
-    """Reference defaults for a receiver in `mode` (utils_supersdr.py:42-50, 936-944)."""
+    """Reference defaults for a receiver in `mode` (utils_supersdr.py:42-50, 936-944).  "sam", "sal" and "sau" are one mode with
+    three default passbands (L.SAM_PASSBANDS)."""
     p = ChanParams()
     m = L.MODE_BY_NAME[mode.lower()] if isinstance(mode, str) else int(mode)
     check(lib.ssdr_default_params(m, C.byref(p)), "ssdr_default_params")
+    if isinstance(mode, str) and mode.lower() in L.SAM_PASSBANDS:
+        p.low_cut, p.high_cut = L.SAM_PASSBANDS[mode.lower()]
     for k, v in over.items():
         if not hasattr(p, k):
             raise AttributeError("ssdr_chan_params has no field %r" % k)
@@ -495,6 +498,13 @@ class SsdrEngine:
         hist = np.empty((count, L.HIST, 2), np.int16)
         check(lib.ssdr_get_subrx_state(self._ctx, int(first), count, st.ctypes.data, hist.ctypes.data), "ssdr_get_subrx_state")
         return st, hist
+
+    def subrx_sam_carrier(self, first=0, count=None):
+        """-> (offset_hz, phase_rad) float32 arrays of rows [first, first + count) of the list, as sam_carrier"""
+        count = self._subrx_count() - first if count is None else int(count)
+        hz, ph = np.zeros(count, np.float32), np.zeros(count, np.float32)
+        check(lib.ssdr_get_subrx_sam_carrier(self._ctx, int(first), count, hz.ctypes.data, ph.ctypes.data), "ssdr_get_subrx_sam_carrier")
+        return hz, ph
 
     def subrx_consts(self, first=0, count=None):
         """-> (consts, taps) of rows [first, first + count) of the list, as get_consts"""
@@ -1052,6 +1062,14 @@ class SsdrEngine:
         hist = np.empty((count, L.HIST, 2), np.int16)
         check(lib.ssdr_get_state(self._ctx, int(first), count, st.ctypes.data, hist.ctypes.data), "ssdr_get_state")
         return st, hist
+
+    def sam_carrier(self, first=0, count=None):
+        """-> (offset_hz, phase_rad) float32 arrays: the carrier loop of the synchronous-AM channels [first, first + count) after the
+        last run -- the carrier's offset from the tuned frequency and the loop's phase in [-pi, pi); 0 for channels of other modes"""
+        count = self.n_ch - first if count is None else int(count)
+        hz, ph = np.zeros(count, np.float32), np.zeros(count, np.float32)
+        check(lib.ssdr_get_sam_carrier(self._ctx, int(first), count, hz.ctypes.data, ph.ctypes.data), "ssdr_get_sam_carrier")
+        return hz, ph
 
     def set_state(self, first, state, hist):
         state = np.ascontiguousarray(state, STATE_DTYPE)

@@ -441,6 +441,8 @@ class IQHub:
     def set_params(self, channel, p):
         if self.pipeline and p.mode == L.MODE_IQ:    # the feed's slots hand out PCM rows only (an IQ channel's row carries I)
             raise ValueError("mod=iq needs the synchronous hub: the pipelined feed does not return I,Q pairs")
+        if p.mode == L.MODE_SAM and not hasattr(self.engine, "sam_carrier"):      # (an engine from before the mode, the fp32 twin's double)
+            raise ValueError("synchronous AM (sam, sal, sau) has no demodulator on this engine (no sam_carrier)")
         with self._lock:
             sq = self._squelch.get(int(channel))
             acts = sq is not None and _squelch_acts(sq, p.mode)
@@ -450,6 +452,23 @@ class IQHub:
             self._n_iq_mode += (p.mode == L.MODE_IQ) - (self.params(channel).mode == L.MODE_IQ)
             self._params[int(channel)] = p
             (self._sq_act.add if acts else self._sq_act.discard)(int(channel))
+
+    def sam_carrier(self, channel=None, sub=None):
+        """-> (offset_hz, phase_rad) of the carrier loop of a channel in synchronous AM (sam / sal / sau) after the last block, or of
+        sub-receiver `sub`: the carrier's offset from the tuned frequency as the loop reads it, and the loop's phase in [-pi, pi).
+        (0.0, 0.0) in any other mode (ssdr_get_sam_carrier)."""
+        if (channel is None) == (sub is None):
+            raise ValueError("sam_carrier takes a channel or a sub-receiver id")
+        with self._lock:
+            if sub is not None:
+                row = sorted(self._subs).index(int(sub))           # ValueError: no such sub-receiver
+                hz, ph = self.engine.subrx_sam_carrier(row, 1)
+            else:
+                c = int(channel)
+                if not 0 <= c < self.n_ch:
+                    raise IndexError("channel %d of %d" % (c, self.n_ch))
+                hz, ph = self.engine.sam_carrier(c, 1)
+        return float(hz[0]), float(ph[0])
 
     def set_noise_blanker(self, channel, gate_us, thresh):
         """"SET nb=<gate_us> th=<thresh>" of one channel (ssdr_set_noise_blanker; either 0 = off): resets the channel's blanker state,
@@ -598,10 +617,11 @@ class IQHub:
         self.engine.set_subrx([(sid,) + new[sid] for sid in sorted(new)])
         self._subs = new
 
-    @staticmethod
-    def _check_sub_params(p):
+    def _check_sub_params(self, p):
         if p.mode == L.MODE_IQ:
             raise ValueError("mod=iq on a sub-receiver: a sub-receiver has no I,Q output")
+        if p.mode == L.MODE_SAM and not hasattr(self.engine, "subrx_sam_carrier"):
+            raise ValueError("synchronous AM (sam, sal, sau) has no demodulator on this engine's sub-receivers (no subrx_sam_carrier)")
 
     def open_sub(self, channel, params=None):
         """A sub-receiver on `channel`: a further audio chain (NCO, filter, demodulator, AGC) on the channel's raw IQ with parameters
@@ -1454,8 +1474,8 @@ class GpuStream:
 
     def _retune(self, kv):
         mode = kv["mod"].lower()
-        if mode not in L.MODE_BY_NAME:               # "SET mod=sam", "drm", ... have no demodulator here: say so
-            raise ValueError("radio_mode %r has no demodulator on the GPU path (am, lsb, usb, cw, nbfm, iq)" % (kv["mod"],))
+        if mode not in L.MODE_BY_NAME:               # "SET mod=drm", "qam", ... have no demodulator here: say so
+            raise ValueError("radio_mode %r has no demodulator on the GPU path (am, lsb, usb, cw, nbfm, iq, sam, sal, sau)" % (kv["mod"],))
         freq = float(kv.get("freq", self.center_khz))
         f_shift = (freq - self.center_khz) * 1000.0
         rate = float(getattr(self.hub, "kiwi_rate", L.RATE))

@@ -4,6 +4,8 @@ would see a live receiver: IQ blocks -> IQHub (ssdr_push_iq, both kernels, db2co
 kiwi_sound -> a 48 kHz stereo .wav of what PortAudio would have played and the waterfall rows as .npy.
 
     python tools/replay_iq_wav.py rec.wav --mode usb --tune-khz 0.0 --audio out.wav --waterfall wf.npy [--averaging 3]
+
+--mode sam | sal | sau: synchronous AM on both sidebands, the lower or the upper one.
 """
 import argparse
 import os
@@ -44,7 +46,8 @@ def replay(wav, mode="AM", tune_khz=0.0, averaging=1, volume=100, zoom=10, cente
     blocks, _ = read_kiwi_iq_wav(wav)
     hub = IQHub(1, device=device)
     wf = kiwi_waterfall("replay", 0, "", zoom, center_khz, _Eibi(), _Disp(), hub=hub, channel=0, timeout=0.05)
-    lc, hc = {"AM": (-6000, 6000), "USB": (30, 3000), "LSB": (-3000, -30), "CW": (400, 800), "NBFM": (-6000, 6000)}[mode.upper()]
+    lc, hc = {"AM": (-6000, 6000), "USB": (30, 3000), "LSB": (-3000, -30), "CW": (400, 800), "NBFM": (-6000, 6000),
+              "SAM": (-4900, 4900), "SAL": (-4900, 0), "SAU": (0, 4900)}[mode.upper()]      # synchronous AM: supersdr_amd._lib.SAM_PASSBANDS
     snd = kiwi_sound(center_khz + tune_khz, mode.upper(), lc, hc, "", wf, 8, volume_=volume)
     wf.averaging_n = averaging
     hub.set_averaging(averaging)
@@ -71,7 +74,7 @@ def replay(wav, mode="AM", tune_khz=0.0, averaging=1, volume=100, zoom=10, cente
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("wav")
-    ap.add_argument("--mode", default="am", choices=["am", "usb", "lsb", "cw", "nbfm"])
+    ap.add_argument("--mode", default="am", choices=["am", "usb", "lsb", "cw", "nbfm", "sam", "sal", "sau"])
     ap.add_argument("--tune-khz", type=float, default=0.0, help="receiver frequency relative to the recording's centre")
     ap.add_argument("--averaging", type=int, default=1)
     ap.add_argument("--volume", type=int, default=100)
