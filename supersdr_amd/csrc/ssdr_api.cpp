@@ -16,13 +16,16 @@
 
 static thread_local char g_hip_err[256] = "";
 
+// a HIP call that must succeed: on an error its text and the runtime's message go to the thread's buffer and the code comes back
+__attribute__((noinline, cold)) static int ssdr_hip_failed(const char *expr, hipError_t e) noexcept
+{
+    snprintf(g_hip_err, sizeof g_hip_err, "%s: %s", expr, hipGetErrorString(e));
+    return e == hipErrorOutOfMemory ? SSDR_ENOMEM : SSDR_EHIP;
+}
 #define HIP_TRY(expr)                                                                   \
     do {                                                                                \
         hipError_t e_ = (expr);                                                         \
-        if (e_ != hipSuccess) {                                                         \
-            snprintf(g_hip_err, sizeof g_hip_err, "%s: %s", #expr, hipGetErrorString(e_)); \
-            return e_ == hipErrorOutOfMemory ? SSDR_ENOMEM : SSDR_EHIP;                 \
-        }                                                                               \
+        if (e_ != hipSuccess) return ssdr_hip_failed(#expr, e_);                        \
     } while (0)
 // ... and a code of ours: evaluated once, handed on unless it is SSDR_OK
 #define SSDR_TRY(expr)                                                                  \
@@ -79,6 +82,14 @@ struct ChainPlan {
     int one_read;                             // 0: a kernel per stage; 1: the fused AM kernel, 2: the wave-specialised one do both on one read of the input
     bool beside;                              // the audio stage runs on stream2, beside the waterfall kernel
 };
+
+// `which` of the stages that are timed beside the SSDR_K_* slots, not in them: each has a stats entry point of its own
+constexpr int kTimedDeemp = SSDR_K_COUNT;               // the de-emphasis kernel (ssdr_deemphasis_stats)
+constexpr int kTimedWfView = SSDR_K_COUNT + 1;          // the waterfall views' stage (ssdr_wf_view_stats)
+constexpr int kTimedSubRx = SSDR_K_COUNT + 2;           // the sub-receivers' (ssdr_subrx_stats)
+constexpr int kTimedChan = SSDR_K_COUNT + 3;            // the wideband channeliser (ssdr_channelizer_stats)
+constexpr int kTimedScope = SSDR_K_COUNT + 4;           // the wideband scopes (ssdr_wb_scope_stats)
+constexpr int kTimedCount = SSDR_K_COUNT + 5;
 
 struct ssdr_ctx {
     int device = 0;
@@ -198,6 +209,8 @@ struct ssdr_ctx {
     float k_ms[SSDR_K_COUNT] = {};
     uint32_t k_n[SSDR_K_COUNT] = {};
     float last_ms = 0.0f;
+    // the stages that are timed beside the SSDR_K_* slots, by `which - SSDR_K_COUNT` (kTimed* above): stage_launch, stage_stats
+    struct { float ms = 0.0f; uint32_t launches = 0; } stage[kTimedCount - SSDR_K_COUNT];
     uint32_t wf_grid = 0, wf_grid_1 = 0;
     unsigned long long *d_scratch = nullptr;
     // post-processing
@@ -268,8 +281,6 @@ struct ssdr_ctx {
     bool de_dirty = false;                              // settings, modes or the rate changed since the list was made
     int32_t *d_de_state = nullptr;                      // [n_ch] S
     uint32_t *d_de_list = nullptr;                      // [2 n_ch], as h_de_list
-    float de_ms = 0.0f;                                 // the kernel's own timing (not an SSDR_K_* slot): ssdr_deemphasis_stats
-    uint32_t de_launches = 0;
     // waterfall views (ssdr_set_wf_views): device memory at the first view; with no view set nothing is launched
     std::vector<ssdr_wf_view> h_wv;                     // the list as set, channels ascending
     std::vector<uint32_t> h_wv_carry;                   // [views] zoomed samples each view carries (mirror of SsdrWfView::carry_n)
@@ -289,8 +300,6 @@ struct ssdr_ctx {
     size_t wv_stream_dwords = 0;
     int16_t *d_wv_wf = nullptr;                         // the waterfall kernel's [max lines][views][1024]
     size_t wv_wf_rows = 0;
-    float wv_ms = 0.0f;                                 // the stage's own timing: ssdr_wf_view_stats
-    uint32_t wv_launches = 0;
     // sub-receivers (ssdr_set_subrx): device memory at the first one; with none set nothing is launched
     std::vector<ssdr_subrx> h_sub;                      // the list as set, ids ascending
     std::vector<ssdr_chan_consts> h_sub_consts;         // [rows] mirror of d_sub_consts
@@ -307,8 +316,6 @@ struct ssdr_ctx {
     ssdr_play_chan *d_sub_play = nullptr;               // [SSDR_SUBRX_MAX]
     int16_t *d_sub_play_out = nullptr;
     size_t sub_play_cap = 0;                            // rows * frames d_sub_play_out holds
-    float sub_ms = 0.0f;                                // the stage's own timing: ssdr_subrx_stats
-    uint32_t sub_launches = 0;
     // wideband channeliser (ssdr_set_channelizer): device memory at the first one set; with none set nothing is launched
     uint32_t chz_streams = 0, chz_over = 1, chz_p = 0;  // streams (0: none set), O, P
     std::vector<float> h_chz_taps;                      // [P * 1024] the prototype as set
@@ -317,8 +324,6 @@ struct ssdr_ctx {
     uint32_t *d_chz_in = nullptr;                       // a host caller's wideband samples of the call
     size_t chz_in_dwords = 0;
     uint64_t chz_out_index = 0;                         // output instants since the streams last started from silence
-    float chz_ms = 0.0f;                                // the stage's own timing: ssdr_channelizer_stats
-    uint32_t chz_launches = 0;
     // wideband scopes (ssdr_set_wb_scopes): device memory at the first scope; with none set nothing is launched
     std::vector<ssdr_wb_scope> h_ws;                    // the list as set
     std::vector<uint32_t> h_ws_det;                     // the detectors, parallel to it (ssdr_set_wb_scope_detectors; a new list: all SAMPLE)
@@ -340,8 +345,6 @@ struct ssdr_ctx {
     int16_t *d_ws_acc = nullptr;                        // [2][rows][1024] the waterfall kernel's partial sums (N = 1: never used)
     ssdr_chan_consts *d_ws_consts = nullptr;            // [rows] calibration 0 dB
     size_t ws_rows = 0;                                 // (scope, line) rows d_ws_out / d_ws_lines / d_ws_acc / d_ws_consts hold
-    float ws_ms = 0.0f;                                 // the stage's own timing: ssdr_wb_scope_stats
-    uint32_t ws_launches = 0;
 };
 // Every device buffer a ctx owns (a feed slot's block: ssdr_feed_close) -- what ssdr_destroy frees.  One line per section of the
 // struct above, in its order (the own batch's buffers where `own` stands): a new `d_` member joins its section's line HERE, and tests/test_gpu_parity.py's
@@ -385,11 +388,6 @@ static int get_event(ssdr_ctx *c, hipEvent_t *e)
     return SSDR_OK;
 }
 // HIP events on the stream the kernel is launched on, bracketing exactly one launch.
-constexpr int kTimedDeemp = SSDR_K_COUNT;               // `which` of the de-emphasis kernel: timed beside the SSDR_K_* slots, not in them
-constexpr int kTimedWfView = SSDR_K_COUNT + 1;          // ... and of the waterfall views' stage
-constexpr int kTimedSubRx = SSDR_K_COUNT + 2;           // ... and of the sub-receivers'
-constexpr int kTimedChan = SSDR_K_COUNT + 3;            // ... and of the wideband channeliser
-constexpr int kTimedScope = SSDR_K_COUNT + 4;           // ... and of the wideband scopes
 static int timed_begin(ssdr_ctx *c, hipStream_t s = nullptr)
 {
     if (!s) s = c->stream;
@@ -421,11 +419,7 @@ static int resolve_pending(ssdr_ctx *c)
         float ms = 0.0f;
         HIP_TRY(hipEventSynchronize(p.e1));
         HIP_TRY(hipEventElapsedTime(&ms, p.e0, p.e1));
-        if (p.which == kTimedDeemp) c->de_ms += ms;          // (its launches are counted where they are made)
-        else if (p.which == kTimedWfView) c->wv_ms += ms;
-        else if (p.which == kTimedSubRx) c->sub_ms += ms;
-        else if (p.which == kTimedChan) c->chz_ms += ms;
-        else if (p.which == kTimedScope) c->ws_ms += ms;
+        if (p.which >= SSDR_K_COUNT) c->stage[p.which - SSDR_K_COUNT].ms += ms;     // (a stage's launches are counted where they are made: stage_launch)
         else if (p.which >= 0) { c->k_ms[p.which] += ms; c->k_n[p.which] += 1; c->last_ms = ms; }
         c->free_events.push_back(p.e0);
         c->free_events.push_back(p.e1);
@@ -440,6 +434,25 @@ template <class F> static int timed_launch(ssdr_ctx *c, int which, hipStream_t s
     if (c->profiling) SSDR_TRY(timed_begin(c, s));
     SSDR_TRY(launch());
     if (c->profiling) SSDR_TRY(timed_end(c, which, s));
+    return SSDR_OK;
+}
+// ... of a stage with a kTimed* id: a launch that was made is counted, profiling or not; its time is kept only with profiling on
+template <class F> static int stage_launch(ssdr_ctx *c, int which, hipStream_t s, F launch)
+{
+    SSDR_TRY(timed_launch(c, which, s, launch));
+    c->stage[which - SSDR_K_COUNT].launches++;
+    return SSDR_OK;
+}
+// behind the five ssdr_*_stats entry points of those stages
+static int stage_stats(ssdr_ctx *c, int which, float *total_ms, uint32_t *launches, int reset)
+{
+    if (!c) return SSDR_EINVAL;
+    HIP_TRY(hipSetDevice(c->device));
+    SSDR_TRY(resolve_pending(c));
+    auto &t = c->stage[which - SSDR_K_COUNT];
+    if (total_ms) *total_ms = t.ms;
+    if (launches) *launches = t.launches;
+    if (reset) { t.ms = 0.0f; t.launches = 0; }
     return SSDR_OK;
 }
 
@@ -510,6 +523,97 @@ static int upload_list(ssdr_ctx *c, uint32_t *d_dst, const uint32_t *h_src, size
     HIP_TRY(hipMemcpyAsync(d_dst, h_src, n * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
     return SSDR_OK;
+}
+// a list as set, behind ssdr_get_wf_views / _subrx / _wb_scopes / _wb_scope_detectors: the count, and the entries unless `out` is null
+template <class T> static int get_list(ssdr_ctx *c, std::vector<T> ssdr_ctx::*list, T *out, uint32_t *count)
+{
+    if (!c || !count) return SSDR_EINVAL;
+    const std::vector<T> &v = c->*list;
+    *count = (uint32_t)v.size();
+    if (out) std::copy(v.begin(), v.end(), out);
+    return SSDR_OK;
+}
+
+// a channel state as after a reset: all zero, but the envelope starts at the knee (full gain, no pop)
+static ssdr_chan_state fresh_state(const ssdr_chan_consts &k)
+{
+    ssdr_chan_state st;
+    memset(&st, 0, sizeof st);
+    st.agc_d = k.agc_knee;
+    for (int j = 0; j < 8; j++) st.agc_m[j] = -1000.0f;
+    return st;
+}
+// The taps of a zoom by Z, 32 Z - 1 floats to `out` (the caller pads its table with zeros): the reference's tap formula
+// (utils_supersdr.py:334-344) with the cut-off at the zoomed stream's Nyquist frequency, fl / fs = 1 / (2 Z) -- the transition takes
+// the outer ~17 % of the span on either side at every Z.  One design for the ctx-wide stage, the views and the wideband scopes.
+static int zoom_taps(uint32_t Z, float *out)
+{
+    const int n = (int)(32 * Z - 1);
+    std::vector<double> h((size_t)n + 1);
+    if (ssdr_design_lowpass_exact(1.0 / (2.0 * (double)Z), 1.0, n, h.data()) != n) return SSDR_EINVAL;
+    for (int i = 0; i < n; i++) out[i] = (float)h[i];
+    return SSDR_OK;
+}
+// the waterfall kernel's grid for `items` (channel pair, group run) items, a wave each: what they need, within the resident grid
+static uint32_t wf_grid_for(uint64_t items, uint32_t wf_grid)
+{
+    const uint64_t need = (items + SSDR_WF_BLOCK / 64 - 1) / (SSDR_WF_BLOCK / 64);
+    return (uint32_t)std::min<uint64_t>(std::max<uint64_t>(need, 1), wf_grid ? wf_grid : 1);
+}
+// `n_rows` rows of `stride` samples as the channels of a small ctx for the waterfall kernel: n_lines byte lines each (N = 1, phase 0),
+// fp32 bins, to `out`; `acc` the two sets of partial sums of acc_rows rows the kernel asks for (N = 1: never used)
+static SsdrWfArgs wf_rows_args(const ssdr_ctx *c, const uint32_t *rows, uint64_t stride, uint32_t n_rows, uint32_t n_lines, const uint32_t *tail,
+                               int16_t *out, int16_t *acc, size_t acc_rows, const ssdr_chan_consts *consts)
+{
+    SsdrWfArgs w;
+    w.iq = rows; w.ch_stride = stride; w.n_ch = n_rows; w.n_lines = n_lines;
+    w.tail = tail;
+    w.n_avg = 1; w.phase = 0; w.n_groups = n_lines; w.grp_run = 1;
+    w.out = out; w.acc_in = acc; w.acc_out = acc + acc_rows * SSDR_NFFT;
+    w.consts = consts; w.win = c->d_win; w.tw_stage = c->d_tw; w.lut = c->d_lut;
+    return w;
+}
+
+// what the entry points below call across the sections of this file, further down
+static int zoom_restart(ssdr_ctx *c, uint32_t first, uint32_t count, bool restart_group = true);
+static int nb_upload(ssdr_ctx *c, uint32_t first, uint32_t count);
+static int squelch_upload(ssdr_ctx *c, uint32_t first, uint32_t count);
+static int deemp_reset(ssdr_ctx *c, uint32_t first, uint32_t count);
+static int wfview_restart(ssdr_ctx *c, uint32_t first, uint32_t count);
+static int subrx_restart(ssdr_ctx *c, uint32_t first, uint32_t count);
+static int subrx_compile(const ssdr_ctx *c, const ssdr_subrx *subs, uint32_t count, uint32_t decim, uint32_t rate,
+                         std::vector<ssdr_chan_consts> &k, std::vector<float> &taps);
+static int subrx_install(ssdr_ctx *c, const std::vector<ssdr_chan_consts> &k, const std::vector<float> &taps);
+
+// ssdr_set_decimation / ssdr_set_kiwi_rate, once their own checks have passed: the IQ arrives at decim * kiwi_rate from now on.
+// Every channel's constants (NCO steps, filter, AGC time constants, NBFM scale) are compiled for that rate, and streams of the old
+// one mean nothing at the new: all or nothing, every stream restarted.
+static int change_input_rate(ssdr_ctx *c, uint32_t decim, uint32_t kiwi_rate)
+{
+    HIP_TRY(hipSetDevice(c->device));
+    std::vector<ssdr_chan_consts> sub_k;                          // the sub-receivers at the new rate, before anything changes
+    std::vector<float> sub_taps;
+    SSDR_TRY(subrx_compile(c, c->h_sub.data(), (uint32_t)c->h_sub.size(), decim, kiwi_rate, sub_k, sub_taps));
+    std::vector<ssdr_chan_params> all = c->h_params;              // recompile every channel for the new input rate
+    const uint32_t keep_decim = c->decim, keep_rate = c->kiwi_rate;
+    c->decim = decim;
+    c->kiwi_rate = kiwi_rate;
+    c->ws_dirty = true;                                           // (the scopes' NCO steps are the wide rate's; nothing of theirs restarts)
+    if (kiwi_rate != keep_rate) c->de_dirty = true;               // the de-emphasis coefficients are the rate's
+    int rc = ssdr_set_params(c, 0, c->n_ch, all.data());
+    if (rc == SSDR_OK) {
+        c->own.have_input = false;                                // a batch pushed at the old rate has the wrong extent
+        rc = ssdr_reset_state(c, 0, c->n_ch);                     // phases and histories of the old rate mean nothing now
+        if (rc == SSDR_OK) rc = zoom_restart(c, 0, c->n_ch);
+        if (rc == SSDR_OK) rc = subrx_install(c, sub_k, sub_taps);
+    }
+    if (rc != SSDR_OK) {                                          // all or nothing: back to the old rate, streams restarted
+        c->decim = keep_decim;
+        c->kiwi_rate = keep_rate;
+        (void)ssdr_set_params(c, 0, c->n_ch, all.data());
+        (void)ssdr_reset_state(c, 0, c->n_ch);
+    }
+    return rc;
 }
 
 extern "C" {
@@ -610,16 +714,6 @@ int ssdr_table(int which, float *out, uint32_t n) SSDR_GUARD
     }
 } SSDR_UNGUARD
 
-static int zoom_restart(ssdr_ctx *c, uint32_t first, uint32_t count, bool restart_group = true);
-static int nb_upload(ssdr_ctx *c, uint32_t first, uint32_t count);
-static int squelch_upload(ssdr_ctx *c, uint32_t first, uint32_t count);
-static int deemp_reset(ssdr_ctx *c, uint32_t first, uint32_t count);
-static int wfview_restart(ssdr_ctx *c, uint32_t first, uint32_t count);
-static int subrx_restart(ssdr_ctx *c, uint32_t first, uint32_t count);
-static int subrx_compile(const ssdr_ctx *c, const ssdr_subrx *subs, uint32_t count, uint32_t decim, uint32_t rate,
-                         std::vector<ssdr_chan_consts> &k, std::vector<float> &taps);
-static int subrx_install(ssdr_ctx *c, const std::vector<ssdr_chan_consts> &k, const std::vector<float> &taps);
-
 // the carrier loop (ssdr_chan_state.pad) of n consecutive state rows to 0, queued on the main stream
 static int sam_loop_zero(ssdr_ctx *c, ssdr_chan_state *d_rows, size_t n)
 {
@@ -635,14 +729,9 @@ int ssdr_reset_state(ssdr_ctx *c, uint32_t first, uint32_t count) SSDR_GUARD
     HIP_TRY(hipSetDevice(c->device));
     SSDR_TRY(join_audio(c));
     std::vector<ssdr_chan_consts> k(count);
-    HIP_TRY(hipMemcpyAsync(k.data(), c->d_consts + first, count * sizeof(ssdr_chan_consts), hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
+    SSDR_TRY(copy_out(c, k.data(), c->d_consts + first, count * sizeof(ssdr_chan_consts), 0, kSyncHost));
     std::vector<ssdr_chan_state> st(count);
-    for (uint32_t i = 0; i < count; i++) {
-        memset(&st[i], 0, sizeof st[i]);
-        st[i].agc_d = k[i].agc_knee;          // envelope starts at the knee: full gain, no pop
-        for (int j = 0; j < 8; j++) st[i].agc_m[j] = -1000.0f;
-    }
+    for (uint32_t i = 0; i < count; i++) st[i] = fresh_state(k[i]);
     HIP_TRY(hipMemcpyAsync(c->d_state + first, st.data(), count * sizeof(ssdr_chan_state), hipMemcpyHostToDevice, c->stream));
     HIP_TRY(hipMemsetAsync(c->d_hist + (size_t)first * SSDR_HIST, 0, (size_t)count * SSDR_HIST * 4, c->stream));
     for (int i = 0; i < 2; i++)
@@ -701,11 +790,7 @@ int ssdr_set_params(ssdr_ctx *c, uint32_t first, uint32_t count, const ssdr_chan
     std::vector<ssdr_chan_state> st;
     if (!c->audio_started) {                 // a channel that has not produced audio yet starts at ITS knee (full gain, no pop)
         st.resize(count);
-        for (uint32_t i = 0; i < count; i++) {
-            memset(&st[i], 0, sizeof st[i]);
-            st[i].agc_d = k[i].agc_knee;
-            for (int j = 0; j < 8; j++) st[i].agc_m[j] = -1000.0f;
-        }
+        for (uint32_t i = 0; i < count; i++) st[i] = fresh_state(k[i]);
         HIP_TRY(hipMemcpyAsync(c->d_state + first, st.data(), count * sizeof(ssdr_chan_state), hipMemcpyHostToDevice, c->stream));
     }
     HIP_TRY(hipStreamSynchronize(c->stream));
@@ -835,27 +920,7 @@ int ssdr_set_decimation(ssdr_ctx *c, uint32_t decim) SSDR_GUARD
     if (decim > 1)                                                // synchronous AM has no decimating front end: nothing changes
         for (const ssdr_chan_params &q : c->h_params)
             if (q.mode == SSDR_MODE_SAM) return SSDR_ESTATE;
-    HIP_TRY(hipSetDevice(c->device));
-    std::vector<ssdr_chan_consts> sub_k;                          // the sub-receivers at the new rate, before anything changes
-    std::vector<float> sub_taps;
-    SSDR_TRY(subrx_compile(c, c->h_sub.data(), (uint32_t)c->h_sub.size(), decim, c->kiwi_rate, sub_k, sub_taps));
-    std::vector<ssdr_chan_params> all = c->h_params;              // recompile every channel for the new input rate
-    const uint32_t keep = c->decim;
-    c->decim = decim;
-    c->ws_dirty = true;                                           // (the scopes' NCO steps are the wide rate's; nothing of theirs restarts)
-    int rc = ssdr_set_params(c, 0, c->n_ch, all.data());
-    if (rc == SSDR_OK) {
-        c->own.have_input = false;                                // a batch pushed at the old rate has the wrong extent
-        rc = ssdr_reset_state(c, 0, c->n_ch);                     // phases and histories of the old rate mean nothing now
-        if (rc == SSDR_OK) rc = zoom_restart(c, 0, c->n_ch);
-        if (rc == SSDR_OK) rc = subrx_install(c, sub_k, sub_taps);
-    }
-    if (rc != SSDR_OK) {                                          // all or nothing: back to the old rate, streams restarted
-        c->decim = keep;
-        (void)ssdr_set_params(c, 0, c->n_ch, all.data());
-        (void)ssdr_reset_state(c, 0, c->n_ch);
-    }
-    return rc;
+    return change_input_rate(c, decim, c->kiwi_rate);
 } SSDR_UNGUARD
 
 int ssdr_set_hop(ssdr_ctx *c, uint32_t hop) SSDR_GUARD
@@ -920,14 +985,9 @@ int ssdr_set_wf_zoom(ssdr_ctx *c, uint32_t zoom) SSDR_GUARD
         HIP_TRY(hipStreamSynchronize(c->stream));
     }
     if (zoom > 1) {
-        // the reference's tap formula (utils_supersdr.py:334-344) with the cut-off at the zoomed stream's Nyquist frequency,
-        // fl / fs = 1 / (2 Z), and 32 Z - 1 taps: the transition takes the outer ~17 % of the span on either side at every Z
-        double h[SSDR_ZOOM_TAPS_MAX + 1];
-        const int n = (int)(32 * zoom - 1);
-        if (ssdr_design_lowpass_exact(1.0 / (2.0 * zoom), 1.0, n, h) != n) return SSDR_EINVAL;
         float hf[SSDR_ZOOM_TAPS_MAX + 1] = {};
-        for (int i = 0; i < n; i++) hf[i] = (float)h[i];
-        c->zoom_ntap = (uint32_t)n;
+        SSDR_TRY(zoom_taps(zoom, hf));
+        c->zoom_ntap = 32 * zoom - 1;
         HIP_TRY(hipMemcpy(c->d_zoom_taps, hf, sizeof hf, hipMemcpyHostToDevice));
         return zoom_restart(c, 0, c->n_ch);
     }
@@ -953,10 +1013,7 @@ int ssdr_read_zoom(ssdr_ctx *c, uint32_t first, uint32_t count, int16_t *iq_out,
     if (samples_per_channel) *samples_per_channel = c->zoom_run_samples;
     if (!iq_out) return SSDR_OK;
     HIP_TRY(hipSetDevice(c->device));
-    HIP_TRY(hipMemcpyAsync(iq_out, c->d_zoom_out + (size_t)first * c->zoom_run_samples, (size_t)count * c->zoom_run_samples * 4,
-                           hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    return SSDR_OK;
+    return copy_out(c, iq_out, c->d_zoom_out + (size_t)first * c->zoom_run_samples, (size_t)count * c->zoom_run_samples * 4, 0, kSyncHost);
 } SSDR_UNGUARD
 
 int ssdr_set_exact_bins(ssdr_ctx *c, int on) SSDR_GUARD
@@ -1182,9 +1239,7 @@ int ssdr_read_input(ssdr_ctx *c, uint32_t first, uint32_t count, int16_t *iq_out
     if (!c->own.have_input) return SSDR_ESTATE;
     HIP_TRY(hipSetDevice(c->device));
     const size_t per_ch = in_len(c, c->own.in_frames);
-    HIP_TRY(hipMemcpyAsync(iq_out, c->own.d_iq + (size_t)first * per_ch, (size_t)count * per_ch * 4, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    return SSDR_OK;
+    return copy_out(c, iq_out, c->own.d_iq + (size_t)first * per_ch, (size_t)count * per_ch * 4, 0, kSyncHost);
 } SSDR_UNGUARD
 
 // The shape rules of a waterfall batch, checked before ANY stage of a call is launched (ssdr_run_chain runs its audio stage first
@@ -1384,9 +1439,7 @@ static int deemp_launch(ssdr_ctx *c, const Batch &b, hipStream_t s)
     q.coef = c->d_de_list + c->n_ch;
     q.list_n = c->de_n;
     q.state = c->d_de_state;
-    SSDR_TRY(timed_launch(c, kTimedDeemp, s, [&]() -> int { HIP_TRY(ssdr_launch_deemp(q, s)); return SSDR_OK; }));
-    c->de_launches++;
-    return SSDR_OK;
+    return stage_launch(c, kTimedDeemp, s, [&]() -> int { HIP_TRY(ssdr_launch_deemp(q, s)); return SSDR_OK; });
 }
 
 // ---- the tail of the audio stage: squelch, de-emphasis, SND encoder -- one order, whichever kernel did the stage's work ---------
@@ -1413,12 +1466,7 @@ static int wfview_alloc(ssdr_ctx *c)
 {
     if (c->d_wv_taps) return SSDR_OK;
     float hf[3][SSDR_ZOOM_TAPS_MAX + 1] = {};
-    for (int zi = 0; zi < 3; zi++) {         // the ctx-wide stage's taps (ssdr_set_wf_zoom), one table per Z
-        const int Z = 2 << zi, n = 32 * Z - 1;
-        double h[SSDR_ZOOM_TAPS_MAX + 1];
-        if (ssdr_design_lowpass_exact(1.0 / (2.0 * Z), 1.0, n, h) != n) return SSDR_EINVAL;
-        for (int i = 0; i < n; i++) hf[zi][i] = (float)h[i];
-    }
+    for (int zi = 0; zi < 3; zi++) SSDR_TRY(zoom_taps(2u << zi, hf[zi]));      // the ctx-wide stage's taps (ssdr_set_wf_zoom), one table per Z
     for (int i = 0; i < 2; i++) {
         if (!c->d_wv[i]) HIP_TRY(hipMalloc(&c->d_wv[i], SSDR_WF_VIEWS_MAX * sizeof(SsdrWfView)));
         if (!c->d_wv_hist[i]) HIP_TRY(hipMalloc(&c->d_wv_hist[i], (size_t)SSDR_WF_VIEWS_MAX * SSDR_ZOOM_HIST * 4));
@@ -1499,21 +1547,16 @@ static int wfview_stage(ssdr_ctx *c, Batch &b)
     a.iq = b.d_iq; a.ch_stride = n_in; a.n_in = n_in; a.n_views = nv; a.hop = c->hop;
     a.views = c->d_wv[set]; a.taps = c->d_wv_taps; a.hist = c->d_wv_hist[set]; a.carry = c->d_wv_carry[set]; a.tail = c->d_wv_tail[set];
     a.stream = c->d_wv_stream; a.stream_stride = stride; a.wf_lines = c->d_wv_wf; a.lines_out = b.d_wv_lines;
-    SsdrWfArgs w;                            // the views as the channels of a small ctx: byte lines (N = 1), fp32 bins
-    w.iq = c->d_wv_stream; w.ch_stride = stride; w.n_ch = nv; w.n_lines = max_lines;
-    w.tail = c->hop == SSDR_NFFT / 2 ? c->d_wv_tail[set] : nullptr;
-    w.n_avg = 1; w.phase = 0; w.n_groups = max_lines; w.grp_run = 1;
-    w.out = c->d_wv_wf; w.acc_in = c->d_wv_acc; w.acc_out = c->d_wv_acc + (size_t)SSDR_WF_VIEWS_MAX * SSDR_NFFT;
-    w.consts = c->d_wv_consts; w.win = c->d_win; w.tw_stage = c->d_tw; w.lut = c->d_lut;
-    const uint64_t need = ((uint64_t)((nv + 1) / 2) * max_lines + SSDR_WF_BLOCK / 64 - 1) / (SSDR_WF_BLOCK / 64);
-    const uint32_t grid = (uint32_t)std::min<uint64_t>(std::max<uint64_t>(need, 1), c->wf_grid ? c->wf_grid : 1);
-    SSDR_TRY(timed_launch(c, kTimedWfView, c->stream, [&]() -> int {
+    // the views as the channels of a small ctx
+    const SsdrWfArgs w = wf_rows_args(c, c->d_wv_stream, stride, nv, max_lines, c->hop == SSDR_NFFT / 2 ? c->d_wv_tail[set] : nullptr,
+                                      c->d_wv_wf, c->d_wv_acc, SSDR_WF_VIEWS_MAX, c->d_wv_consts);
+    const uint32_t grid = wf_grid_for((uint64_t)((nv + 1) / 2) * max_lines, c->wf_grid);
+    SSDR_TRY(stage_launch(c, kTimedWfView, c->stream, [&]() -> int {
         HIP_TRY(ssdr_launch_wf_view_zoom(a, c->stream));
         if (max_lines) HIP_TRY(ssdr_launch_wf(w, grid, c->stream));
         HIP_TRY(ssdr_launch_wf_view_finish(a, c->stream));
         return SSDR_OK;
     }));
-    c->wv_launches++;
     c->h_wv_run_carry = c->h_wv_carry;
     for (uint32_t j = 0; j < nv; j++) c->h_wv_carry[j] = c->h_wv_carry[j] + n_in / c->h_wv[j].zoom - lines[j] * c->hop;
     b.wv_run_lines = lines;
@@ -1583,14 +1626,12 @@ static int wf_stage(ssdr_ctx *c, Batch &b, ChainPlan plan, SsdrWfArgs *one_read,
         a.grp_run = (uint32_t)run;
         items = (uint64_t)((c->n_ch + 1) / 2) * ((n_groups + run - 1) / run);
     }
-    const uint64_t need = (items + SSDR_WF_BLOCK / 64 - 1) / (SSDR_WF_BLOCK / 64);
-    const uint32_t grid = (uint32_t)(need < wf_grid ? need : wf_grid);
     if (plan.one_read) {                     // that kernel does this stage's work: the audio stage launches it
         *one_read = a;
     } else {
         SSDR_TRY(timed_begin(c));
         if (c->exact_bins) HIP_TRY(ssdr_launch_wf_exact(a, c->d_tw64, c->stream));
-        else HIP_TRY(ssdr_launch_wf(a, grid ? grid : 1, c->stream));
+        else HIP_TRY(ssdr_launch_wf(a, wf_grid_for(items, wf_grid), c->stream));
         SSDR_TRY(timed_end(c, SSDR_K_WF));
     }
     if (hop512 && !plan.one_read) // the batch's last half-line is the next batch's first: [n_ch] rows of 2 KB out of the input
@@ -1655,14 +1696,6 @@ static int subrx_alloc(ssdr_ctx *c)
     if (!c->d_sub_play) HIP_TRY(hipMalloc(&c->d_sub_play, SSDR_SUBRX_MAX * sizeof(ssdr_play_chan)));
     return SSDR_OK;
 }
-static ssdr_chan_state subrx_fresh(const ssdr_chan_consts &k)
-{
-    ssdr_chan_state st;
-    memset(&st, 0, sizeof st);
-    st.agc_d = k.agc_knee;                   // as ssdr_reset_state: the envelope starts at the knee
-    for (int j = 0; j < 8; j++) st.agc_m[j] = -1000.0f;
-    return st;
-}
 // row j of set `set` as ssdr_reset_state leaves a channel (queued on the main stream; the caller waits: *fresh is host memory)
 static int subrx_silence(ssdr_ctx *c, int set, uint32_t j, const ssdr_chan_state *fresh)
 {
@@ -1681,7 +1714,7 @@ static int subrx_restart(ssdr_ctx *c, uint32_t first, uint32_t count)
     for (size_t j = 0; j < c->h_sub.size(); j++) {
         const uint32_t ch = c->h_sub[j].channel;
         if (ch < first || ch - first >= count) continue;
-        fresh[j] = subrx_fresh(c->h_sub_consts[j]);
+        fresh[j] = fresh_state(c->h_sub_consts[j]);
         SSDR_TRY(subrx_silence(c, c->sub_set, (uint32_t)j, &fresh[j]));
         c->h_sub_started[j] = 0;
         any = true;
@@ -1737,12 +1770,11 @@ static int subrx_launch(ssdr_ctx *c, Batch &b, const SsdrAudioArgs &au, hipStrea
     a.parent = c->d_sub_parent;
     bool any_sam = false;                                  // rows in synchronous AM run the mode's own instantiation beside the others'
     for (const ssdr_chan_consts &k : c->h_sub_consts) any_sam = any_sam || k.mode == SSDR_MODE_SAM;
-    SSDR_TRY(timed_launch(c, kTimedSubRx, s, [&]() -> int {
+    SSDR_TRY(stage_launch(c, kTimedSubRx, s, [&]() -> int {
         HIP_TRY(ssdr_launch_audio_sub(a, c->decim, s));
         if (any_sam) HIP_TRY(ssdr_launch_audio_sub_sam(a, s));
         return SSDR_OK;
     }));
-    c->sub_launches++;
     std::fill(c->h_sub_started.begin(), c->h_sub_started.end(), (uint8_t)1);
     b.sub_run_rows = n;
     b.sub_run_frames = b.in_frames;
@@ -2571,9 +2603,7 @@ int ssdr_copy_from_device(ssdr_ctx *c, void *host_dst, const void *device_src, u
     if (!c || !host_dst || !device_src) return SSDR_EINVAL;
     HIP_TRY(hipSetDevice(c->device));
     SSDR_TRY(join_audio(c));
-    HIP_TRY(hipMemcpyAsync(host_dst, device_src, bytes, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    return SSDR_OK;
+    return copy_out(c, host_dst, device_src, bytes, 0, kSyncHost);
 } SSDR_UNGUARD
 
 int ssdr_audio_device(ssdr_ctx *c, int16_t **pcm, float **rssi) SSDR_GUARD
@@ -2591,8 +2621,8 @@ int ssdr_get_consts(ssdr_ctx *c, uint32_t first, uint32_t count, ssdr_chan_const
     if (!c || (uint64_t)first + count > c->n_ch) return SSDR_EINVAL;
     HIP_TRY(hipSetDevice(c->device));
     SSDR_TRY(join_audio(c));
-    if (consts) HIP_TRY(hipMemcpyAsync(consts, c->d_consts + first, count * sizeof(ssdr_chan_consts), hipMemcpyDeviceToHost, c->stream));
-    if (taps) HIP_TRY(hipMemcpyAsync(taps, c->d_taps + (size_t)first * SSDR_NTAP_MAX, (size_t)count * SSDR_NTAP_MAX * 4, hipMemcpyDeviceToHost, c->stream));
+    if (consts) SSDR_TRY(copy_out(c, consts, c->d_consts + first, count * sizeof(ssdr_chan_consts), 0, kSyncLater));
+    if (taps) SSDR_TRY(copy_out(c, taps, c->d_taps + (size_t)first * SSDR_NTAP_MAX, (size_t)count * SSDR_NTAP_MAX * 4, 0, kSyncLater));
     HIP_TRY(hipStreamSynchronize(c->stream));
     return SSDR_OK;
 } SSDR_UNGUARD
@@ -2602,8 +2632,8 @@ int ssdr_get_state(ssdr_ctx *c, uint32_t first, uint32_t count, ssdr_chan_state 
     if (!c || (uint64_t)first + count > c->n_ch) return SSDR_EINVAL;
     HIP_TRY(hipSetDevice(c->device));
     SSDR_TRY(join_audio(c));
-    if (state) HIP_TRY(hipMemcpyAsync(state, c->d_state + first, count * sizeof(ssdr_chan_state), hipMemcpyDeviceToHost, c->stream));
-    if (hist) HIP_TRY(hipMemcpyAsync(hist, c->d_hist + (size_t)first * SSDR_HIST, (size_t)count * SSDR_HIST * 4, hipMemcpyDeviceToHost, c->stream));
+    if (state) SSDR_TRY(copy_out(c, state, c->d_state + first, count * sizeof(ssdr_chan_state), 0, kSyncLater));
+    if (hist) SSDR_TRY(copy_out(c, hist, c->d_hist + (size_t)first * SSDR_HIST, (size_t)count * SSDR_HIST * 4, 0, kSyncLater));
     HIP_TRY(hipStreamSynchronize(c->stream));
     return SSDR_OK;
 } SSDR_UNGUARD
@@ -2615,8 +2645,7 @@ static int sam_carrier_read(ssdr_ctx *c, const ssdr_chan_state *d_rows, const ss
     HIP_TRY(hipSetDevice(c->device));
     SSDR_TRY(join_audio(c));
     std::vector<ssdr_chan_state> st(count);
-    HIP_TRY(hipMemcpyAsync(st.data(), d_rows, count * sizeof(ssdr_chan_state), hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
+    SSDR_TRY(copy_out(c, st.data(), d_rows, count * sizeof(ssdr_chan_state), 0, kSyncHost));
     const double two_pi = 6.283185307179586476925;
     for (uint32_t i = 0; i < count; i++) {
         const bool sam = k[i].mode == SSDR_MODE_SAM;
@@ -3004,30 +3033,7 @@ int ssdr_set_kiwi_rate(ssdr_ctx *c, uint32_t kiwi_rate) SSDR_GUARD
     if (!c || (kiwi_rate != SSDR_RATE && kiwi_rate != SSDR_RATE_WIDE)) return SSDR_EINVAL;
     if (kiwi_rate == c->kiwi_rate) return SSDR_OK;
     if (!c->feed.empty()) return SSDR_ESTATE;
-    HIP_TRY(hipSetDevice(c->device));
-    // the rate of the play-back stage AND of the IQ the channels receive: every channel's constants (NCO steps, filter,
-    // AGC time constants, NBFM scale) are compiled for it, and streams of the old rate mean nothing at the new one
-    std::vector<ssdr_chan_consts> sub_k;                          // the sub-receivers at the new rate, before anything changes
-    std::vector<float> sub_taps;
-    SSDR_TRY(subrx_compile(c, c->h_sub.data(), (uint32_t)c->h_sub.size(), c->decim, kiwi_rate, sub_k, sub_taps));
-    std::vector<ssdr_chan_params> all = c->h_params;
-    const uint32_t keep = c->kiwi_rate;
-    c->kiwi_rate = kiwi_rate;
-    c->ws_dirty = true;                                           // (the scopes' NCO steps, as ssdr_set_decimation)
-    c->de_dirty = true;                                           // the de-emphasis coefficients are the rate's
-    int rc = ssdr_set_params(c, 0, c->n_ch, all.data());
-    if (rc == SSDR_OK) {
-        c->own.have_input = false;
-        rc = ssdr_reset_state(c, 0, c->n_ch);
-        if (rc == SSDR_OK) rc = zoom_restart(c, 0, c->n_ch);
-        if (rc == SSDR_OK) rc = subrx_install(c, sub_k, sub_taps);
-    }
-    if (rc != SSDR_OK) {                                          // all or nothing, as ssdr_set_decimation
-        c->kiwi_rate = keep;
-        (void)ssdr_set_params(c, 0, c->n_ch, all.data());
-        (void)ssdr_reset_state(c, 0, c->n_ch);
-    }
-    return rc;
+    return change_input_rate(c, c->decim, kiwi_rate);            // the rate of the play-back stage AND of the IQ the channels receive
 } SSDR_UNGUARD
 
 int ssdr_playbuffer_frame_len(ssdr_ctx *c, uint32_t *samples_per_frame) SSDR_GUARD
@@ -3116,9 +3122,7 @@ int ssdr_wire_gps(ssdr_ctx *c, uint32_t *gps_out) SSDR_GUARD
     if (!c || !gps_out) return SSDR_EINVAL;
     if (!c->d_wire_gps || c->wire_run_frames == 0) return SSDR_ESTATE;
     HIP_TRY(hipSetDevice(c->device));
-    HIP_TRY(hipMemcpyAsync(gps_out, c->d_wire_gps, (size_t)c->n_ch * c->wire_run_frames * 4 * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    return SSDR_OK;
+    return copy_out(c, gps_out, c->d_wire_gps, (size_t)c->n_ch * c->wire_run_frames * 4 * sizeof(uint32_t), 0, kSyncHost);
 } SSDR_UNGUARD
 
 int ssdr_adpcm_decode(ssdr_ctx *c, const uint8_t *data, uint32_t n_streams, uint32_t n_bytes, int32_t *state, int16_t *out) SSDR_GUARD
@@ -3342,8 +3346,7 @@ int ssdr_audio_squelch(ssdr_ctx *c, uint8_t *closed_out, int out_is_device) SSDR
         return SSDR_OK;
     }
     std::vector<uint8_t> rows((size_t)c->sq_n * row);
-    HIP_TRY(hipMemcpyAsync(rows.data(), c->own.d_sq_closed, rows.size(), hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
+    SSDR_TRY(copy_out(c, rows.data(), c->own.d_sq_closed, rows.size(), 0, kSyncHost));
     memset(closed_out, 0, (size_t)c->n_ch * row);
     for (uint32_t i = 0; i < c->sq_n; i++) memcpy(closed_out + (size_t)c->h_sq_list[i] * row, rows.data() + (size_t)i * row, row);
     return SSDR_OK;
@@ -3404,20 +3407,12 @@ int ssdr_get_deemp_state(ssdr_ctx *c, uint32_t first, uint32_t count, int32_t *S
     if (!c->d_de_state) { memset(S, 0, (size_t)count * sizeof(int32_t)); return SSDR_OK; }
     HIP_TRY(hipSetDevice(c->device));
     SSDR_TRY(join_audio(c));
-    HIP_TRY(hipMemcpyAsync(S, c->d_de_state + first, (size_t)count * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    return SSDR_OK;
+    return copy_out(c, S, c->d_de_state + first, (size_t)count * sizeof(int32_t), 0, kSyncHost);
 } SSDR_UNGUARD
 
 int ssdr_deemphasis_stats(ssdr_ctx *c, float *total_ms, uint32_t *launches, int reset) SSDR_GUARD
 {
-    if (!c) return SSDR_EINVAL;
-    HIP_TRY(hipSetDevice(c->device));
-    SSDR_TRY(resolve_pending(c));
-    if (total_ms) *total_ms = c->de_ms;
-    if (launches) *launches = c->de_launches;
-    if (reset) { c->de_ms = 0.0f; c->de_launches = 0; }
-    return SSDR_OK;
+    return stage_stats(c, kTimedDeemp, total_ms, launches, reset);
 } SSDR_UNGUARD
 
 int ssdr_set_wf_views(ssdr_ctx *c, const ssdr_wf_view *views, uint32_t count) SSDR_GUARD
@@ -3471,10 +3466,7 @@ int ssdr_set_wf_views(ssdr_ctx *c, const ssdr_wf_view *views, uint32_t count) SS
 
 int ssdr_get_wf_views(ssdr_ctx *c, ssdr_wf_view *views, uint32_t *count) SSDR_GUARD
 {
-    if (!c || !count) return SSDR_EINVAL;
-    *count = (uint32_t)c->h_wv.size();
-    if (views) std::copy(c->h_wv.begin(), c->h_wv.end(), views);
-    return SSDR_OK;
+    return get_list(c, &ssdr_ctx::h_wv, views, count);
 } SSDR_UNGUARD
 
 int ssdr_wf_view_lines(ssdr_ctx *c, int16_t *lines_out, uint32_t *lines_per_view, uint32_t *total_lines, int out_is_device) SSDR_GUARD
@@ -3502,13 +3494,7 @@ int ssdr_read_wf_view(ssdr_ctx *c, uint32_t view_index, int16_t *iq_out, uint32_
 
 int ssdr_wf_view_stats(ssdr_ctx *c, float *total_ms, uint32_t *launches, int reset) SSDR_GUARD
 {
-    if (!c) return SSDR_EINVAL;
-    HIP_TRY(hipSetDevice(c->device));
-    SSDR_TRY(resolve_pending(c));
-    if (total_ms) *total_ms = c->wv_ms;
-    if (launches) *launches = c->wv_launches;
-    if (reset) { c->wv_ms = 0.0f; c->wv_launches = 0; }
-    return SSDR_OK;
+    return stage_stats(c, kTimedWfView, total_ms, launches, reset);
 } SSDR_UNGUARD
 
 int ssdr_set_subrx(ssdr_ctx *c, const ssdr_subrx *subs, uint32_t count) SSDR_GUARD
@@ -3549,7 +3535,7 @@ int ssdr_set_subrx(ssdr_ctx *c, const ssdr_subrx *subs, uint32_t count) SSDR_GUA
             if (k[j].mode == SSDR_MODE_SAM && c->h_sub_consts[i].mode != SSDR_MODE_SAM) SSDR_TRY(sam_loop_zero(c, c->d_sub_state[to] + j, 1));
             started[j] = 1;
         } else {                                            // new, or kept but not run yet: it starts at ITS knee (ssdr_set_params)
-            fresh[j] = subrx_fresh(k[j]);
+            fresh[j] = fresh_state(k[j]);
             SSDR_TRY(subrx_silence(c, to, j, &fresh[j]));
         }
     }
@@ -3565,10 +3551,7 @@ int ssdr_set_subrx(ssdr_ctx *c, const ssdr_subrx *subs, uint32_t count) SSDR_GUA
 
 int ssdr_get_subrx(ssdr_ctx *c, ssdr_subrx *subs, uint32_t *count) SSDR_GUARD
 {
-    if (!c || !count) return SSDR_EINVAL;
-    *count = (uint32_t)c->h_sub.size();
-    if (subs) std::copy(c->h_sub.begin(), c->h_sub.end(), subs);
-    return SSDR_OK;
+    return get_list(c, &ssdr_ctx::h_sub, subs, count);
 } SSDR_UNGUARD
 
 int ssdr_subrx_audio(ssdr_ctx *c, int16_t *pcm, float *rssi, uint8_t *flags, int out_is_device) SSDR_GUARD
@@ -3593,8 +3576,8 @@ int ssdr_get_subrx_state(ssdr_ctx *c, uint32_t first_row, uint32_t count, ssdr_c
     HIP_TRY(hipSetDevice(c->device));
     SSDR_TRY(join_audio(c));
     const int set = c->sub_set;
-    if (state) HIP_TRY(hipMemcpyAsync(state, c->d_sub_state[set] + first_row, count * sizeof(ssdr_chan_state), hipMemcpyDeviceToHost, c->stream));
-    if (hist) HIP_TRY(hipMemcpyAsync(hist, c->d_sub_hist[set] + (size_t)first_row * SSDR_HIST, (size_t)count * SSDR_HIST * 4, hipMemcpyDeviceToHost, c->stream));
+    if (state) SSDR_TRY(copy_out(c, state, c->d_sub_state[set] + first_row, count * sizeof(ssdr_chan_state), 0, kSyncLater));
+    if (hist) SSDR_TRY(copy_out(c, hist, c->d_sub_hist[set] + (size_t)first_row * SSDR_HIST, (size_t)count * SSDR_HIST * 4, 0, kSyncLater));
     HIP_TRY(hipStreamSynchronize(c->stream));
     return SSDR_OK;
 } SSDR_UNGUARD
@@ -3612,8 +3595,8 @@ int ssdr_get_subrx_consts(ssdr_ctx *c, uint32_t first_row, uint32_t count, ssdr_
     if (!count) return SSDR_OK;
     HIP_TRY(hipSetDevice(c->device));
     SSDR_TRY(join_audio(c));
-    if (consts) HIP_TRY(hipMemcpyAsync(consts, c->d_sub_consts + first_row, count * sizeof(ssdr_chan_consts), hipMemcpyDeviceToHost, c->stream));
-    if (taps) HIP_TRY(hipMemcpyAsync(taps, c->d_sub_taps + (size_t)first_row * SSDR_NTAP_MAX, (size_t)count * SSDR_NTAP_MAX * 4, hipMemcpyDeviceToHost, c->stream));
+    if (consts) SSDR_TRY(copy_out(c, consts, c->d_sub_consts + first_row, count * sizeof(ssdr_chan_consts), 0, kSyncLater));
+    if (taps) SSDR_TRY(copy_out(c, taps, c->d_sub_taps + (size_t)first_row * SSDR_NTAP_MAX, (size_t)count * SSDR_NTAP_MAX * 4, 0, kSyncLater));
     HIP_TRY(hipStreamSynchronize(c->stream));
     return SSDR_OK;
 } SSDR_UNGUARD
@@ -3642,27 +3625,11 @@ int ssdr_run_subrx_playbuffer(ssdr_ctx *c, const ssdr_play_chan *chans, int16_t 
 
 int ssdr_subrx_stats(ssdr_ctx *c, float *total_ms, uint32_t *launches, int reset) SSDR_GUARD
 {
-    if (!c) return SSDR_EINVAL;
-    HIP_TRY(hipSetDevice(c->device));
-    SSDR_TRY(resolve_pending(c));
-    if (total_ms) *total_ms = c->sub_ms;
-    if (launches) *launches = c->sub_launches;
-    if (reset) { c->sub_ms = 0.0f; c->sub_launches = 0; }
-    return SSDR_OK;
+    return stage_stats(c, kTimedSubRx, total_ms, launches, reset);
 } SSDR_UNGUARD
 
 // ---- wideband scopes: DDCs on the channeliser's wide streams, drawn by the waterfall kernel (ssdr_wb_scope.hip) -----------------
 static double ws_wide_rate(const ssdr_ctx *c) { return (double)SSDR_CHAN_BRANCHES * c->decim * c->kiwi_rate / c->chz_over; }
-// the taps of zoom z: 32 Z - 1 floats of design_lowpass, and a zero
-static int ws_make_taps(uint32_t z, float *out)
-{
-    const int n = (32 << z) - 1;
-    std::vector<double> h((size_t)n + 1);
-    if (ssdr_design_lowpass_exact(1.0 / (2.0 * (double)(1u << z)), 1.0, n, h.data()) != n) return SSDR_EINVAL;
-    for (int i = 0; i < n; i++) out[i] = (float)h[i];
-    out[n] = 0.0f;
-    return SSDR_OK;
-}
 // no scope: the list and the histories go (the small tables stay for the next list)
 static int ws_clear(ssdr_ctx *c)
 {
@@ -3768,15 +3735,10 @@ static int ws_stage(ssdr_ctx *c, const uint32_t *in, uint64_t in_stride, uint32_
     a.period = (uint32_t)(per_line * step);
     a.taps = c->d_ws_taps; a.hist = c->d_ws_hist; a.out = c->d_ws_out;
     a.slot_stream = c->d_ws_slot_stream; a.n_slots = (uint32_t)c->h_ws_streams.size();
-    SsdrWfArgs w;                            // every (scope, line) as a channel of a small ctx with one line: byte lines (N = 1), fp32 bins
-    w.iq = c->d_ws_out; w.ch_stride = SSDR_NFFT; w.n_ch = (uint32_t)rows; w.n_lines = 1;
-    w.tail = nullptr;
-    w.n_avg = 1; w.phase = 0; w.n_groups = 1; w.grp_run = 1;
-    w.out = c->d_ws_lines; w.acc_in = c->d_ws_acc; w.acc_out = c->d_ws_acc + c->ws_rows * SSDR_NFFT;
-    w.consts = c->d_ws_consts; w.win = c->d_win; w.tw_stage = c->d_tw; w.lut = c->d_lut;
-    const uint64_t need = ((uint64_t)((rows + 1) / 2) + SSDR_WF_BLOCK / 64 - 1) / (SSDR_WF_BLOCK / 64);
-    const uint32_t grid = (uint32_t)std::min<uint64_t>(std::max<uint64_t>(need, 1), c->wf_grid ? c->wf_grid : 1);
-    SSDR_TRY(timed_launch(c, kTimedScope, c->stream, [&]() -> int {
+    // every (scope, line) as a channel of a small ctx with one line
+    const SsdrWfArgs w = wf_rows_args(c, c->d_ws_out, SSDR_NFFT, (uint32_t)rows, 1, nullptr, c->d_ws_lines, c->d_ws_acc, c->ws_rows, c->d_ws_consts);
+    const uint32_t grid = wf_grid_for((rows + 1) / 2, c->wf_grid);
+    SSDR_TRY(stage_launch(c, kTimedScope, c->stream, [&]() -> int {
         if (lines) {
             HIP_TRY(ssdr_launch_wb_scope(a, c->stream));
             HIP_TRY(ssdr_launch_wf(w, grid, c->stream));
@@ -3785,7 +3747,6 @@ static int ws_stage(ssdr_ctx *c, const uint32_t *in, uint64_t in_stride, uint32_
         HIP_TRY(ssdr_launch_wb_scope_hist(a, c->stream));
         return SSDR_OK;
     }));
-    c->ws_launches++;
     c->ws_run_lines = lines;
     c->ws_run_valid = true;
     c->ws_run_wlog.resize(ns);
@@ -3859,10 +3820,7 @@ int ssdr_get_channelizer_state(ssdr_ctx *c, int16_t *hist, uint64_t *out_index) 
     if (!c->chz_streams) return SSDR_ESTATE;
     HIP_TRY(hipSetDevice(c->device));
     if (out_index) *out_index = c->chz_out_index;
-    if (hist) {
-        HIP_TRY(hipMemcpyAsync(hist, c->d_chz_hist, (size_t)c->chz_streams * c->chz_p * SSDR_CHAN_BRANCHES * 4, hipMemcpyDeviceToHost, c->stream));
-        HIP_TRY(hipStreamSynchronize(c->stream));
-    }
+    if (hist) SSDR_TRY(copy_out(c, hist, c->d_chz_hist, (size_t)c->chz_streams * c->chz_p * SSDR_CHAN_BRANCHES * 4, 0, kSyncHost));
     return SSDR_OK;
 } SSDR_UNGUARD
 
@@ -3891,8 +3849,7 @@ int ssdr_push_wideband(ssdr_ctx *c, const int16_t *iq, uint32_t n_frames, int is
     a.out = c->d_iq_own;
     a.out_stride = n_out;
     a.tw_stage = c->d_tw;
-    SSDR_TRY(timed_launch(c, kTimedChan, c->stream, [&]() -> int { HIP_TRY(ssdr_launch_channelize(a, c->stream)); return SSDR_OK; }));
-    c->chz_launches++;
+    SSDR_TRY(stage_launch(c, kTimedChan, c->stream, [&]() -> int { HIP_TRY(ssdr_launch_channelize(a, c->stream)); return SSDR_OK; }));
     SSDR_TRY(ws_stage(c, a.in, a.in_stride, a.n_in, n_out, c->chz_out_index));
     c->chz_out_index += n_out;
     own_input(c, c->d_iq_own, n_frames);
@@ -3901,13 +3858,7 @@ int ssdr_push_wideband(ssdr_ctx *c, const int16_t *iq, uint32_t n_frames, int is
 
 int ssdr_channelizer_stats(ssdr_ctx *c, float *total_ms, uint32_t *launches, int reset) SSDR_GUARD
 {
-    if (!c) return SSDR_EINVAL;
-    HIP_TRY(hipSetDevice(c->device));
-    SSDR_TRY(resolve_pending(c));
-    if (total_ms) *total_ms = c->chz_ms;
-    if (launches) *launches = c->chz_launches;
-    if (reset) { c->chz_ms = 0.0f; c->chz_launches = 0; }
-    return SSDR_OK;
+    return stage_stats(c, kTimedChan, total_ms, launches, reset);
 } SSDR_UNGUARD
 
 int ssdr_set_wb_scopes(ssdr_ctx *c, const ssdr_wb_scope *scopes, uint32_t count) SSDR_GUARD
@@ -3924,7 +3875,7 @@ int ssdr_set_wb_scopes(ssdr_ctx *c, const ssdr_wb_scope *scopes, uint32_t count)
     if (!count) return ws_clear(c);
     if (!c->d_ws_taps) {                                    // the first scope: the eleven tap tables and the small lists
         std::vector<float> t((size_t)32 * ((2u << SSDR_WB_SCOPE_ZOOM_MAX) - 1u));
-        for (uint32_t z = 0; z <= SSDR_WB_SCOPE_ZOOM_MAX; z++) SSDR_TRY(ws_make_taps(z, t.data() + 32u * ((1u << z) - 1u)));
+        for (uint32_t z = 0; z <= SSDR_WB_SCOPE_ZOOM_MAX; z++) SSDR_TRY(zoom_taps(1u << z, t.data() + 32u * ((1u << z) - 1u)));     // (32 Z - 1 taps and a zero)
         float *d = nullptr;
         HIP_TRY(hipMalloc(&d, t.size() * sizeof(float)));
         c->d_ws_taps = d;
@@ -3980,10 +3931,7 @@ int ssdr_set_wb_scope_detectors(ssdr_ctx *c, const uint32_t *det, uint32_t count
 
 int ssdr_get_wb_scope_detectors(ssdr_ctx *c, uint32_t *det, uint32_t *count) SSDR_GUARD
 {
-    if (!c || !count) return SSDR_EINVAL;
-    *count = (uint32_t)c->h_ws_det.size();
-    if (det) std::copy(c->h_ws_det.begin(), c->h_ws_det.end(), det);
-    return SSDR_OK;
+    return get_list(c, &ssdr_ctx::h_ws_det, det, count);
 } SSDR_UNGUARD
 
 int ssdr_wb_scope_windows(ssdr_ctx *c, uint32_t index, uint32_t *windows) SSDR_GUARD
@@ -4021,10 +3969,7 @@ int ssdr_read_wb_scope_windows(ssdr_ctx *c, uint32_t index, int16_t *iq_out, uin
 
 int ssdr_get_wb_scopes(ssdr_ctx *c, ssdr_wb_scope *scopes, uint32_t *count) SSDR_GUARD
 {
-    if (!c || !count) return SSDR_EINVAL;
-    *count = (uint32_t)c->h_ws.size();
-    if (scopes) std::copy(c->h_ws.begin(), c->h_ws.end(), scopes);
-    return SSDR_OK;
+    return get_list(c, &ssdr_ctx::h_ws, scopes, count);
 } SSDR_UNGUARD
 
 int ssdr_wb_scope_lines(ssdr_ctx *c, int16_t *lines_out, uint32_t *lines_per_scope, uint32_t *total, int out_is_device) SSDR_GUARD
@@ -4054,21 +3999,12 @@ int ssdr_read_wb_scope(ssdr_ctx *c, uint32_t index, int16_t *iq_out, uint32_t *s
 int ssdr_wb_scope_taps(uint32_t zoom, float *out) SSDR_GUARD
 {
     if (zoom > SSDR_WB_SCOPE_ZOOM_MAX || !out) return SSDR_EINVAL;
-    std::vector<float> t((size_t)32 << zoom);
-    SSDR_TRY(ws_make_taps(zoom, t.data()));
-    std::copy(t.begin(), t.end() - 1, out);
-    return SSDR_OK;
+    return zoom_taps(1u << zoom, out);
 } SSDR_UNGUARD
 
 int ssdr_wb_scope_stats(ssdr_ctx *c, float *total_ms, uint32_t *launches, int reset) SSDR_GUARD
 {
-    if (!c) return SSDR_EINVAL;
-    HIP_TRY(hipSetDevice(c->device));
-    SSDR_TRY(resolve_pending(c));
-    if (total_ms) *total_ms = c->ws_ms;
-    if (launches) *launches = c->ws_launches;
-    if (reset) { c->ws_ms = 0.0f; c->ws_launches = 0; }
-    return SSDR_OK;
+    return stage_stats(c, kTimedScope, total_ms, launches, reset);
 } SSDR_UNGUARD
 
 int ssdr_set_wf_lines(ssdr_ctx *c, const int16_t *wf_sum, uint32_t lines) SSDR_GUARD

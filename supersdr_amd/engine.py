@@ -402,11 +402,15 @@ class SsdrEngine:
               "ssdr_get_deemp_state")
         return out[:count]
 
+    def _stage_stats(self, entry, reset):
+        """-> (total_ms, launches) from one of the stages' own stats entry points (they share a signature)"""
+        ms, n = C.c_float(), C.c_uint32()
+        check(getattr(lib, entry)(self._ctx, C.byref(ms), C.byref(n), 1 if reset else 0), entry)
+        return ms.value, n.value
+
     def deemp_stats(self, reset=False):
         """-> (total_ms, launches) of the de-emphasis kernel since the last reset (the time only with set_profiling on)"""
-        ms, n = C.c_float(), C.c_uint32()
-        check(lib.ssdr_deemphasis_stats(self._ctx, C.byref(ms), C.byref(n), 1 if reset else 0), "ssdr_deemphasis_stats")
-        return ms.value, n.value
+        return self._stage_stats("ssdr_deemphasis_stats", reset)
 
     def set_wf_views(self, views):
         """The waterfall views, replacing the whole list: a sequence of (channel, zoom, offset_hz), channels ascending and unique, zoom
@@ -448,9 +452,7 @@ class SsdrEngine:
 
     def wf_view_stats(self, reset=False):
         """-> (total_ms, runs) of the view stage since the last reset (the time only with set_profiling on)"""
-        ms, n = C.c_float(), C.c_uint32()
-        check(lib.ssdr_wf_view_stats(self._ctx, C.byref(ms), C.byref(n), 1 if reset else 0), "ssdr_wf_view_stats")
-        return ms.value, n.value
+        return self._stage_stats("ssdr_wf_view_stats", reset)
 
     def set_subrx(self, subs):
         """The sub-receivers, replacing the whole list: a sequence of (id, channel, ChanParams), ids ascending and unique, at most 256;
@@ -527,9 +529,7 @@ class SsdrEngine:
 
     def subrx_stats(self, reset=False):
         """-> (total_ms, runs) of the sub-receiver stage since the last reset (the time only with set_profiling on)"""
-        ms, n = C.c_float(), C.c_uint32()
-        check(lib.ssdr_subrx_stats(self._ctx, C.byref(ms), C.byref(n), 1 if reset else 0), "ssdr_subrx_stats")
-        return ms.value, n.value
+        return self._stage_stats("ssdr_subrx_stats", reset)
 
     # ---- wideband channeliser: one wide IQ stream -> 1024 rows of the input batch
     def set_channelizer(self, n_streams, oversample=1, taps=None, branches=L.CHAN_BRANCHES):
@@ -590,9 +590,7 @@ class SsdrEngine:
 
     def channelizer_stats(self, reset=False):
         """-> (total_ms, runs) of the channeliser since the last reset (the time only with set_profiling on)"""
-        ms, n = C.c_float(), C.c_uint32()
-        check(lib.ssdr_channelizer_stats(self._ctx, C.byref(ms), C.byref(n), 1 if reset else 0), "ssdr_channelizer_stats")
-        return ms.value, n.value
+        return self._stage_stats("ssdr_channelizer_stats", reset)
 
     # ---- wideband scopes: zoomable waterfalls of the channeliser's wide streams
     def set_wb_scopes(self, scopes):
@@ -666,9 +664,7 @@ class SsdrEngine:
 
     def wb_scope_stats(self, reset=False):
         """-> (total_ms, runs) of the scope stage since the last reset (the time only with set_profiling on)"""
-        ms, n = C.c_float(), C.c_uint32()
-        check(lib.ssdr_wb_scope_stats(self._ctx, C.byref(ms), C.byref(n), 1 if reset else 0), "ssdr_wb_scope_stats")
-        return ms.value, n.value
+        return self._stage_stats("ssdr_wb_scope_stats", reset)
 
     def audio_iq(self):
         """-> int16 [n_ch, n_frames*512, 2]: I,Q of the channels in "iq" mode for the last run_audio (rows of other modes: 0)"""

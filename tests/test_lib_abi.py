@@ -218,10 +218,16 @@ def test_param_compile_for_a_decimating_front_end_equals_oracle(S, decim):
 # ---- include/ssdr.h:11-14 "never throws or aborts" (the reference's own policy: errors become a flag, utils_supersdr.py:1031-1036) ----
 
 def test_every_int_entry_point_is_a_function_try_block():
-    """every `int ssdr_*` definition inside csrc/ssdr_api.cpp's extern "C" block carries SSDR_GUARD ... SSDR_UNGUARD
-    (catch std::bad_alloc -> SSDR_ENOMEM, anything else -> SSDR_EHIP), and the header's functions are all defined there"""
-    src = open(os.path.join(ROOT, "supersdr_amd", "csrc", "ssdr_api.cpp")).read()
-    body = src[src.index('extern "C" {'):]
+    """every `int ssdr_*` definition inside the extern "C" block of a unit of the API's host code (csrc/ssdr_api*.cpp) carries
+    SSDR_GUARD ... SSDR_UNGUARD (catch std::bad_alloc -> SSDR_ENOMEM, anything else -> SSDR_EHIP), and the header's functions are all
+    defined there"""
+    import glob
+    units = sorted(glob.glob(os.path.join(ROOT, "supersdr_amd", "csrc", "ssdr_api*.cpp")))
+    assert units
+    body = ""
+    for u in units:                                     # each unit from its extern "C" { on
+        src = open(u).read()
+        body += src[src.index('extern "C" {'):]
     defs = re.findall(r"^int (ssdr_\w+)\([^;{]*?\)( SSDR_GUARD)?\n\{", body, flags=re.M)
     assert len(defs) >= 70
     unguarded = [n for n, g in defs if not g]
