@@ -107,7 +107,9 @@ typedef struct ssdr_chan_state {
     uint32_t pad[2];            /* SSDR_MODE_SAM: the carrier loop.  pad[0] = theta, the loop's phase as a 32-bit phase like phi1
                                  * (radians = 2 pi pad[0] / 2^32, it wraps by itself); pad[1] = the bits of a float32, omega in radians
                                  * per sample.  Both 0 after ssdr_reset_state and when ssdr_set_params moves a channel into the mode;
-                                 * channels of the other modes carry the two words through untouched. */
+                                 * channels of the other modes carry the two words through untouched.  The loop keeps omega within
+                                 * +-2 pi 500 / rate; a finite omega that ssdr_set_state puts outside is used as it is for the first
+                                 * block of the next frame and is inside again after that block's update. */
 } ssdr_chan_state;
 
 typedef struct ssdr_ctx ssdr_ctx;
@@ -847,7 +849,8 @@ int ssdr_get_state(ssdr_ctx *ctx, uint32_t first, uint32_t count, ssdr_chan_stat
 int ssdr_set_state(ssdr_ctx *ctx, uint32_t first, uint32_t count, const ssdr_chan_state *state, const int16_t *hist);
 /* The carrier loop of the SSDR_MODE_SAM channels [first, first + count) as the last audio run left it: offset_hz float [count] =
  * omega * rate / (2 pi), the carrier's offset from the tuned frequency as the loop reads it; phase_rad float [count] (may be NULL) =
- * theta in [-pi, pi).  Both 0 for channels of other modes.  SSDR_EINVAL for a range outside the ctx or a NULL offset_hz.  Ordered
+ * theta in [-pi, pi) (as a float as well: the phase words next to half a turn read the floats next to +-pi on the inside, never
+ * float(pi), which lies above pi).  Both 0 for channels of other modes.  SSDR_EINVAL for a range outside the ctx or a NULL offset_hz.  Ordered
  * behind the ctx's queued work, like ssdr_get_state. */
 int ssdr_get_sam_carrier(ssdr_ctx *ctx, uint32_t first, uint32_t count, float *offset_hz, float *phase_rad);
 /* Checkpoint: everything a ctx carries from one call to the next -- compiled channel constants and taps, NCO phases, FIR

@@ -2652,7 +2652,12 @@ static int sam_carrier_read(ssdr_ctx *c, const ssdr_chan_state *d_rows, const ss
         float om;
         memcpy(&om, &st[i].pad[1], sizeof om);
         offset_hz[i] = sam ? (float)((double)om * c->kiwi_rate / two_pi) : 0.0f;
-        if (phase_rad) phase_rad[i] = sam ? (float)((double)(int32_t)st[i].pad[0] * (two_pi / 4294967296.0)) : 0.0f;
+        if (!phase_rad) continue;
+        // theta in [-pi, pi) as a float: within half a float's step of either end the nearest float is float(+-pi), which lies outside
+        // (float(pi) > pi) -- there the value steps to the float next to it on the inside
+        float ph = (float)((double)(int32_t)st[i].pad[0] * (two_pi / 4294967296.0));
+        if ((double)ph >= two_pi / 2.0 || (double)ph < -(two_pi / 2.0)) ph = nextafterf(ph, 0.0f);
+        phase_rad[i] = sam ? ph : 0.0f;
     }
     return SSDR_OK;
 }

@@ -268,6 +268,13 @@ constexpr SamK sam_consts(double rate)
             (float)(2.0 * SAM_PI * SAM_PULL_HZ / rate), (float)(8.0 * SAM_U_PER_RAD)};
 }
 SSDR_DEV uint32_t sam_phase_u(float rad_times_scale) { return (uint32_t)__float2int_rn(rad_times_scale); }
+// The same for a step that may pass half a turn, where the conversion above saturates: 8 omega for an omega that ssdr_set_state put
+// outside the clamp (at 12 kHz 8 omega passes pi from 1.5 omega_max on), before the first update has brought it back.  Whole turns
+// come off first -- exactly, and none for a value within half a turn, whose result is sam_phase_u's to the bit.
+SSDR_DEV uint32_t sam_phase_u_wide(float rad_times_scale)
+{
+    return sam_phase_u(fmaf(-4294967296.0f, rintf(rad_times_scale * 2.3283064365386963e-10f), rad_times_scale));
+}
 
 // v = y e^{+j phi2} puts the tuned carrier at 0 Hz (demod_ssb's second NCO); u[n] = v[n] e^{-j omega0 n} takes the loop's frequency at
 // the frame's start out of the lane's eight samples -- one rotation chain for both, block phasor (c, s) and step S2 conj(W) -- and
@@ -294,6 +301,7 @@ SSDR_DEV void demod_sam(const float (&yr)[8], const float (&yi)[8], float c, flo
     }
     uint32_t th = theta, th_lane = 0;
     float om = omega;
+    uint32_t step = sam_phase_u_wide(om * k.eight_u);        // 8 omega of the block to come: the first one's omega is the state's, unclamped
 #pragma unroll 1
     for (uint32_t b = 0; b < 64; b++) {
         const float Tr = lane_f(tr, b), Ti = lane_f(ti, b);
@@ -301,8 +309,9 @@ SSDR_DEV void demod_sam(const float (&yr)[8], const float (&yi)[8], float c, flo
         ssdr_phasor32(th, pc, ps);
         const float e = ssdr_atan2p(fmaf(Ti, pc, -(Tr * ps)), fmaf(Tr, pc, Ti * ps));       // angle of T e^{-j theta}; 0 for T = 0
         th_lane = (uint32_t)l == b ? th : th_lane;
-        th += sam_phase_u(om * k.eight_u) + sam_phase_u(e * k.alpha_u);
+        th += step + sam_phase_u(e * k.alpha_u);
         om = __builtin_amdgcn_fmed3f(fmaf(k.beta, e, om), -k.wmax, k.wmax);
+        step = sam_phase_u(om * k.eight_u);
     }
     theta = th;
     omega = om;

@@ -67,7 +67,8 @@ def wrap(x):
 
 
 class SamChannel(O.AudioChannel):
-    """One SAM channel, sample-exact state carry across frames.  After process_frame: last_e (the 64 phase errors), last_I."""
+    """One SAM channel, sample-exact state carry across frames.  After process_frame: last_e (the 64 phase errors), last_I, and per
+    block last_omega (omega after the update), last_clipped (the update met +-omega_max), last_zero (S was exactly 0)."""
 
     def __init__(self, p, rate=O.RATE, fp32=False):
         self.fp32 = bool(fp32)
@@ -107,12 +108,15 @@ class SamChannel(O.AudioChannel):
         theta, omega = F(self.theta), w0
         th = np.empty(nb, F)
         e = np.empty(nb, F)
+        om, hit, nil = np.empty(nb), np.zeros(nb, bool), np.zeros(nb, bool)        # (recorded for the tests; no part of the arithmetic)
         for b in range(nb):
             S = CF(T[b] * CF(np.exp(-1j * np.float64(theta))))
             e[b] = F(0.0) if S == 0 else F(np.arctan2(S.imag, S.real))
             th[b] = theta
             theta = F(wrap(F(theta + F(BLOCK) * omega) + alpha * e[b]))
+            hit[b], nil[b] = abs(omega + beta * e[b]) > w_max, S == 0
             omega = F(min(max(omega + beta * e[b], -w_max), w_max))
+            om[b] = omega
         self.theta, self.omega = float(theta), float(omega)
         I = (u * np.exp(-1j * th.astype(np.float64)).astype(CF)[:, None]).real.reshape(-1).astype(F)
         # AM's DC estimate on I
@@ -126,6 +130,7 @@ class SamChannel(O.AudioChannel):
         aud = (I - m).astype(np.float64)
         self.prev = complex(z2[-1])
         self.last_e, self.last_I = e.astype(np.float64), I.astype(np.float64)
+        self.last_omega, self.last_clipped, self.last_zero = om, hit, nil
         # AGC, rounding, RSSI, carry: AudioChannel.process_frame's
         pb = np.maximum(p.reshape(-1, BLOCK).max(axis=1), O.P_FLOOR)
         a_l = np.log2(pb)
@@ -153,9 +158,12 @@ class SamChannel(O.AudioChannel):
         return pcm, rssi, y
 
     def process(self, iq):
-        """iq int16 [n_frames * 512, 2] -> (pcm, rssi); e_out [n_frames, 64], carrier_out [n_frames, 2] = (offset_hz, phase) per frame"""
+        """iq int16 [n_frames * 512, 2] -> (pcm, rssi); e_out [n_frames, 64], carrier_out [n_frames, 2] = (offset_hz, phase) per frame;
+        omega_out, clipped_out, zero_out [n_frames, 64]: omega after each block's update, whether the update was clipped, whether S was 0"""
         iq = np.asarray(iq, np.int16).reshape(-1, O.FRAME, 2)
         self.e_out = np.empty((iq.shape[0], O.FRAME // BLOCK))
+        self.omega_out = np.empty(self.e_out.shape)
+        self.clipped_out, self.zero_out = np.zeros(self.e_out.shape, bool), np.zeros(self.e_out.shape, bool)
         self.carrier_out = np.empty((iq.shape[0], 2))
         pcm = np.empty((iq.shape[0], O.FRAME), np.int16)
         rssi = np.empty(iq.shape[0], np.float32)
@@ -163,6 +171,7 @@ class SamChannel(O.AudioChannel):
         for f in range(iq.shape[0]):
             pcm[f], rssi[f], self.y_out[f] = self.process_frame(iq[f])
             self.e_out[f] = self.last_e
+            self.omega_out[f], self.clipped_out[f], self.zero_out[f] = self.last_omega, self.last_clipped, self.last_zero
             self.carrier_out[f] = self.carrier()
         return pcm.reshape(-1), rssi
 

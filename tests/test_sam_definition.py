@@ -87,6 +87,45 @@ def test_omega_never_leaves_its_range_under_a_2_khz_offset():
     assert worst > 0.0
 
 
+@pytest.mark.parametrize("rate", [12000, 20250])
+def test_omega_leans_on_the_clamp_and_never_passes_it(rate):
+    """The 2 kHz case above never reaches the clamp (no update of it is clipped): this one does.  The loop starts at -omega_max on a
+    carrier 510 Hz below the tuned frequency, so the error keeps pushing omega outward."""
+    w_max = R.loop_consts(rate)[2]
+    ch = R.SamChannel(R.params("sal", f_shift_hz=-1500.0), rate)
+    ch.omega = -w_max
+    ch.process(R.am_signal(12 * 512, rate, -1500.0 - 510.0))
+    hit = ch.clipped_out
+    print("%d Hz: %d of %d updates clipped, omega in [%.6f, %.6f] omega_max" % (rate, hit.sum(), hit.size, ch.omega_out.min() / w_max, ch.omega_out.max() / w_max))
+    assert hit.sum() * 4 >= hit.size                                           # at least a quarter of the updates
+    assert (np.abs(ch.omega_out[hit]) == w_max).all() and (ch.omega_out[hit] == -w_max).sum() * 4 >= hit.size      # exactly, and mostly on the low side
+    assert np.abs(ch.omega_out).max() <= w_max
+    # the mirror image leans on the other side
+    up = R.SamChannel(R.params("sau", f_shift_hz=1500.0), rate)
+    up.omega = w_max
+    up.process(R.am_signal(12 * 512, rate, 1500.0 + 510.0))
+    assert up.clipped_out.sum() * 4 >= up.clipped_out.size and (up.omega_out[up.clipped_out] == w_max).all() and np.abs(up.omega_out).max() <= w_max
+
+
+@pytest.mark.parametrize("rate", [12000, 20250])
+def test_the_loop_coasts_through_exact_silence(rate):
+    """S = 0 gives e = 0: omega holds, theta advances by 8 omega per block.  One silent frame drains the filter's history first."""
+    ch = R.SamChannel(R.params("sau", f_shift_hz=300.0), rate)
+    ch.process(R.am_signal(3 * 512, rate, 340.0))
+    ch.process(np.zeros((512, 2), np.int16))                                    # (the history's tail still passes the filter here)
+    theta0, omega0 = -3.0, 0.7 * R.loop_consts(rate)[2]
+    ch.theta, ch.omega = theta0, omega0
+    frames = 3
+    pcm, _ = ch.process(np.zeros((frames * 512, 2), np.int16))
+    assert not ch.e_out.any() and ch.zero_out.all() and not ch.clipped_out.any()
+    assert (ch.omega_out == omega0).all() and ch.omega == omega0
+    want = theta0
+    for _ in range(frames * 64):
+        want = R.wrap(want + 8.0 * omega0)                                      # the definition's own order of operations, block by block
+    assert ch.theta == want and abs(R.wrap(ch.theta - (theta0 + 8.0 * 64 * frames * omega0))) < 1e-9
+    assert pcm.any()                                                            # the audio is -m g: the DC estimate decays through the rising gain
+
+
 def test_a_one_sided_passband_removes_the_other_sidebands_interferer():
     # carrier at +25 Hz, 50 % AM at 437.5 Hz, and a tone 1000 Hz below the carrier at 0.3 of its amplitude
     sig = dict(tone_hz=437.5, extra=[(25.0 - 1000.0, 0.3 * 6000.0)])
