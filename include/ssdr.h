@@ -707,6 +707,68 @@ int ssdr_wb_scope_windows(ssdr_ctx *ctx, uint32_t index, uint32_t *windows);
  * otherwise, where ssdr_wb_scope_lines would refuse, and after ssdr_channelizer_reset. */
 int ssdr_read_wb_scope_windows(ssdr_ctx *ctx, uint32_t index, int16_t *iq_out, uint32_t *windows);
 
+/* -- tuned receivers: demodulators at any frequency of a channeliser's wide stream (the KiwiSDR's DDC tunes every user anywhere; the
+ *    channeliser's rows sit on a grid of F / 1024 * O, and a row is what the prototype filter leaves of it)
+ *
+ * A TUNED RECEIVER is a scope's DDC and a sub-receiver's audio chain joined: (id, stream w, offset_hz with |offset_hz| <= F / 2,
+ * parameters P).  With the channeliser's O, R = 1024 / O and F = 1024 * D * kiwi_rate / O take Z = R, z = 10 - log2(O), and dphi, zmix and
+ * h = the taps of zoom z exactly as the scopes' block above defines them (x[i] = 0 where the kept history does not reach).  A call of
+ * ssdr_push_wideband that takes the channeliser's output index from n0 to n0 + n (n = n_frames * 512 * D) produces the receiver's IQ ROW
+ *     y[m] = sum_k h[k] zmix[R m - k],   m = n0 .. n0 + n - 1,   stored (rint Re, rint Im), half-even, saturated to int16
+ * -- the stored outputs of a scope of zoom z at the same offset, at CONSECUTIVE m: a row at a row's rate (flat to 5 kHz, -6 dB at
+ * 6 kHz, -69 dB at 7 kHz of a 12 kHz row), sample-aligned with the channeliser's rows of the same call, centred anywhere.
+ * tests/wb_rx_ref.py is the definition; the kernel works in float32 in the scopes' summation order, so a row is bit-identical however
+ * the stream is cut into calls and whatever else is in either list.
+ * The audio is no new arithmetic: PCM, RSSI, flags and carried state (ssdr_chan_state, raw history) are bit for bit those of a
+ * channel of a ctx that is fed the stored row and holds P.  Like a sub-receiver it has no blanker, squelch, de-emphasis, ADPCM or
+ * SSDR_MODE_IQ; at D > 1 no parameters that compile to a shift path and no SSDR_MODE_SAM.
+ * State rules (the sub-receivers' for the audio, the scopes' for the DDC):
+ *   the DDC carries nothing: a new offset_hz of a kept receiver acts from the next push on and restarts nobody;
+ *   a receiver whose (id, stream) is in the old list keeps its audio stream and takes new parameters as ssdr_set_params does; a new
+ *   one starts in the state ssdr_reset_state leaves a channel in;
+ *   a stream keeps the scopes' history ring (SSDR_WB_SCOPE_HIST) while EITHER list names it: the first user of a stream starts it as
+ *   silence, a later one -- scope or receiver -- sees the kept past; with no tuned receiver the scopes' rules read as before;
+ *   ssdr_set_channelizer empties the list; ssdr_channelizer_reset keeps it and restarts every receiver's audio state; ssdr_reset_state
+ *   and ssdr_set_params on channels do not touch tuned receivers; ssdr_set_decimation / ssdr_set_kiwi_rate compile every receiver at
+ *   the new setting first, the offset bound included, return SSDR_EINVAL with nothing changed if one does not fit, and otherwise
+ *   recompile and restart all of them.
+ * Rows belong to a push, audio to the audio run behind it (ssdr_run_audio, every path of ssdr_run_chain; chain_plan does not look at
+ * the list and *fused reports what it reported).  After a list change the getters return SSDR_ESTATE until there has been a push
+ * and an audio run with the list as it is; an audio run on rows of an older list launches nothing for the receivers.  New parameters
+ * or a new offset of the same rows do not invalidate results.
+ * Kernels: ssdr_wb_rx_kernel (ssdr_wb_scope.hip: the scopes' body for every output of the call, on ssdr_push_wideband's stream
+ * behind the filter bank and in front of the launch that rewrites the rings), then the sub-receivers' audio kernels on the rows, on
+ * the audio stage's stream behind the sub-receivers and in front of squelch / de-emphasis / SND encoder.  With an empty list nothing
+ * is launched, before the first receiver nothing is allocated.  No SSDR_K_* slot: ssdr_wb_rx_stats is the stage's own. */
+#define SSDR_WB_RX_MAX 64
+typedef struct ssdr_wb_rx {
+    uint32_t id;            /* the caller's name for it: what makes a receiver "the same one" across lists */
+    uint32_t stream;        /* the wide stream it listens to */
+    double offset_hz;       /* centre, Hz from the wide stream's centre */
+    ssdr_chan_params params;
+} ssdr_wb_rx;               /* 104 B */
+/* Replaces the whole list: id ascending and unique, count <= SSDR_WB_RX_MAX; (NULL, 0) removes every receiver.  SSDR_EINVAL, and then
+ * nothing changes: a list out of order, a stream not below n_streams, offset_hz not finite or |offset_hz| > F / 2, anything
+ * ssdr_set_subrx would refuse in the parameters, a NULL list with count > 0.  SSDR_ESTATE without a channeliser. */
+int ssdr_set_wb_rx(ssdr_ctx *ctx, const ssdr_wb_rx *list, uint32_t count);
+int ssdr_get_wb_rx(ssdr_ctx *ctx, ssdr_wb_rx *list /* may be NULL */, uint32_t *count);
+/* The receivers' results of the last audio run, rows in list order (each pointer may be NULL): pcm int16 [count][n_frames * 512],
+ * rssi float [count][n_frames], flags uint8 [count][n_frames]. */
+int ssdr_wb_rx_audio(ssdr_ctx *ctx, int16_t *pcm, float *rssi, uint8_t *flags, int out_is_device);
+/* The stored IQ rows [first_row, first_row + count) of the last ssdr_push_wideband: iq_out int16 [count][n_frames * 512 * D][2] (host
+ * memory).  SSDR_ESTATE if there has been no push with the list as it is. */
+int ssdr_read_wb_rx(ssdr_ctx *ctx, uint32_t first_row, uint32_t count, int16_t *iq_out);
+/* Carried state, compiled constants and the SAM carrier of rows [first_row, first_row + count), as the sub-receivers' getters. */
+int ssdr_get_wb_rx_state(ssdr_ctx *ctx, uint32_t first_row, uint32_t count, ssdr_chan_state *state, int16_t *hist /* may be NULL */);
+int ssdr_get_wb_rx_consts(ssdr_ctx *ctx, uint32_t first_row, uint32_t count, ssdr_chan_consts *consts, float *taps /* may be NULL */);
+int ssdr_get_wb_rx_sam_carrier(ssdr_ctx *ctx, uint32_t first_row, uint32_t count, float *offset_hz, float *phase_rad /* may be NULL */);
+/* play_buffer of the receivers' PCM rows of the last audio run as the channels of a small ctx, as ssdr_run_subrx_playbuffer: the
+ * shipped kernels at either rate, a history array of the receivers' own that follows a kept receiver.  No recording block. */
+int ssdr_run_wb_rx_playbuffer(ssdr_ctx *ctx, const ssdr_play_chan *chans, int16_t *out, int out_is_device);
+/* The stage's runs since the last reset: launches [2] = DDC runs (one per ssdr_push_wideband while a receiver is set), audio runs;
+ * with ssdr_set_profiling on their summed times.  Every pointer may be NULL.  ssdr_wb_scope_stats and ssdr_subrx_stats do not move. */
+int ssdr_wb_rx_stats(ssdr_ctx *ctx, float *ddc_ms, float *audio_ms, uint32_t *launches, int reset);
+
 /* -- pipelined host feed: the path a live ingest takes (KiwiSDRStream._process_iq_samples -> batches, kiwi/client.py:493)
  *
  * ssdr_push_iq + ssdr_run_* from pageable host memory serialise copy-in, kernels and copy-out.  The feed keeps `depth`

@@ -110,6 +110,16 @@ class WbScope(C.Structure):
 
 
 assert C.sizeof(WbScope) == 16
+WB_RX_MAX = 64              # SSDR_WB_RX_MAX
+
+
+class WbRx(C.Structure):
+    """ssdr_wb_rx: one tuned receiver -- the caller's id for it, the wide stream it listens to, its centre in Hz from the stream's
+    centre, its own parameters"""
+    _fields_ = [("id", C.c_uint32), ("stream", C.c_uint32), ("offset_hz", C.c_double), ("params", ChanParams)]
+
+
+assert C.sizeof(WbRx) == 104
 
 
 class FeedListen(C.Structure):
@@ -217,6 +227,15 @@ _SIGS = {
     "ssdr_get_wb_scope_detectors": (C.c_int, [_P, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
     "ssdr_wb_scope_windows": (C.c_int, [_P, C.c_uint32, C.POINTER(C.c_uint32)]),
     "ssdr_read_wb_scope_windows": (C.c_int, [_P, C.c_uint32, _P, C.POINTER(C.c_uint32)]),
+    "ssdr_set_wb_rx": (C.c_int, [_P, C.POINTER(WbRx), C.c_uint32]),
+    "ssdr_get_wb_rx": (C.c_int, [_P, C.POINTER(WbRx), C.POINTER(C.c_uint32)]),
+    "ssdr_wb_rx_audio": (C.c_int, [_P, _P, _P, _P, C.c_int]),
+    "ssdr_read_wb_rx": (C.c_int, [_P, C.c_uint32, C.c_uint32, _P]),
+    "ssdr_get_wb_rx_state": (C.c_int, [_P, C.c_uint32, C.c_uint32, _P, _P]),
+    "ssdr_get_wb_rx_consts": (C.c_int, [_P, C.c_uint32, C.c_uint32, _P, _P]),
+    "ssdr_get_wb_rx_sam_carrier": (C.c_int, [_P, C.c_uint32, C.c_uint32, _P, _P]),
+    "ssdr_run_wb_rx_playbuffer": (C.c_int, [_P, C.POINTER(PlayChan), _P, C.c_int]),
+    "ssdr_wb_rx_stats": (C.c_int, [_P, C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_uint32 * 2), C.c_int]),
     "ssdr_feed_open": (C.c_int, [_P, C.c_uint32, C.c_uint32, C.c_uint32]),
     "ssdr_feed_slot": (C.c_int, [_P, C.POINTER(_P)]),
     "ssdr_feed_submit": (C.c_int, [_P]),
@@ -269,7 +288,9 @@ _NEWER_THAN_AB_LIBS = ("ssdr_feed_collect_listen", "ssdr_set_subrx", "ssdr_get_s
                        "ssdr_get_channelizer", "ssdr_channelizer_reset", "ssdr_push_wideband", "ssdr_get_channelizer_state",
                        "ssdr_channelizer_stats", "ssdr_set_wb_scopes", "ssdr_get_wb_scopes", "ssdr_wb_scope_lines", "ssdr_read_wb_scope",
                        "ssdr_wb_scope_taps", "ssdr_wb_scope_stats", "ssdr_set_wb_scope_detectors", "ssdr_get_wb_scope_detectors",
-                       "ssdr_wb_scope_windows", "ssdr_read_wb_scope_windows", "ssdr_get_sam_carrier", "ssdr_get_subrx_sam_carrier")      # entry points a library named by SSDR_LIB_PATH (A/B builds only) may predate
+                       "ssdr_wb_scope_windows", "ssdr_read_wb_scope_windows", "ssdr_get_sam_carrier", "ssdr_get_subrx_sam_carrier",
+                       "ssdr_set_wb_rx", "ssdr_get_wb_rx", "ssdr_wb_rx_audio", "ssdr_read_wb_rx", "ssdr_get_wb_rx_state", "ssdr_get_wb_rx_consts",
+                       "ssdr_get_wb_rx_sam_carrier", "ssdr_run_wb_rx_playbuffer", "ssdr_wb_rx_stats")      # entry points a library named by SSDR_LIB_PATH (A/B builds only) may predate
 
 
 def _load():

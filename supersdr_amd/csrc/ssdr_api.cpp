@@ -76,6 +76,14 @@ struct Batch {
     float *d_sub_rssi = nullptr; size_t sub_rssi_cap = 0;         // [rows][frames]
     uint8_t *d_sub_flags = nullptr; size_t sub_flags_cap = 0;     // [rows][frames]
     uint32_t sub_run_rows = 0, sub_run_frames = 0;                // extent of the last run
+    // the tuned receivers' IQ rows of the last ssdr_push_wideband (their validity: ssdr_ctx::wr_rows_valid) and their results of the
+    // audio run behind it (ssdr_ctx::wr_run_valid), rows in list order
+    uint32_t *d_wr_rows = nullptr; size_t wr_rows_cap = 0;        // [rows][frames * 512 * D] I | Q << 16; capacity in dwords
+    uint32_t wr_rows_n = 0, wr_rows_frames = 0;                   // extent of that push
+    int16_t *d_wr_pcm = nullptr; size_t wr_pcm_cap = 0;           // [rows][frames * 512]; capacities in rows * frames
+    float *d_wr_rssi = nullptr; size_t wr_rssi_cap = 0;           // [rows][frames]
+    uint8_t *d_wr_flags = nullptr; size_t wr_flags_cap = 0;       // [rows][frames]
+    uint32_t wr_run_rows = 0, wr_run_frames = 0;                  // extent of the last run
 };
 // What ssdr_run_chain decides for a batch (chain_plan), handed to the two stages
 struct ChainPlan {
@@ -89,7 +97,9 @@ constexpr int kTimedWfView = SSDR_K_COUNT + 1;          // the waterfall views' 
 constexpr int kTimedSubRx = SSDR_K_COUNT + 2;           // the sub-receivers' (ssdr_subrx_stats)
 constexpr int kTimedChan = SSDR_K_COUNT + 3;            // the wideband channeliser (ssdr_channelizer_stats)
 constexpr int kTimedScope = SSDR_K_COUNT + 4;           // the wideband scopes (ssdr_wb_scope_stats)
-constexpr int kTimedCount = SSDR_K_COUNT + 5;
+constexpr int kTimedWbRxDdc = SSDR_K_COUNT + 5;         // the tuned receivers' DDC and their audio (ssdr_wb_rx_stats)
+constexpr int kTimedWbRxAudio = SSDR_K_COUNT + 6;
+constexpr int kTimedCount = SSDR_K_COUNT + 7;
 
 struct ssdr_ctx {
     int device = 0;
@@ -345,6 +355,25 @@ struct ssdr_ctx {
     int16_t *d_ws_acc = nullptr;                        // [2][rows][1024] the waterfall kernel's partial sums (N = 1: never used)
     ssdr_chan_consts *d_ws_consts = nullptr;            // [rows] calibration 0 dB
     size_t ws_rows = 0;                                 // (scope, line) rows d_ws_out / d_ws_lines / d_ws_acc / d_ws_consts hold
+    // tuned receivers (ssdr_set_wb_rx): device memory at the first one; with none set nothing is launched.  The rings are the scopes'
+    // (h_ws_streams: the streams EITHER list names), the tap tables too; the audio arrays are the sub-receivers' layout, the receivers' own
+    std::vector<ssdr_wb_rx> h_wr;                       // the list as set, ids ascending
+    std::vector<ssdr_chan_consts> h_wr_consts;          // [rows] mirror of d_wr_consts
+    std::vector<uint8_t> h_wr_started;                  // [rows] the receiver's audio has run since it was created or restarted
+    bool wr_rows_valid = false;                         // the own batch's input is an ssdr_push_wideband's with the list as it is
+    bool wr_run_valid = false;                          // ... and there has been an audio run on its rows
+    int wr_set = 0;                                     // which of the two sets of state arrays is the current one (as sub_set)
+    SsdrWbScope *d_wr_list = nullptr;                   // [SSDR_WB_RX_MAX] the receivers as the DDC sees them (uploaded with the scopes': ws_dirty)
+    ssdr_chan_state *d_wr_state[2] = {nullptr, nullptr};        // [SSDR_WB_RX_MAX]
+    uint32_t *d_wr_hist[2] = {nullptr, nullptr};        // [SSDR_WB_RX_MAX][SSDR_HIST]
+    double *d_wr_phist[2] = {nullptr, nullptr};         // [SSDR_WB_RX_MAX][8] play_buffer history (ssdr_run_wb_rx_playbuffer)
+    double *d_wr_phist_alt = nullptr;
+    ssdr_chan_consts *d_wr_consts = nullptr;            // [SSDR_WB_RX_MAX]
+    float *d_wr_taps = nullptr;                         // [SSDR_WB_RX_MAX][SSDR_NTAP_MAX]
+    uint32_t *d_wr_parent = nullptr;                    // [SSDR_WB_RX_MAX] 0, 1, 2, ..: receiver r reads row r of the DDC's rows
+    ssdr_play_chan *d_wr_play = nullptr;                // [SSDR_WB_RX_MAX]
+    int16_t *d_wr_play_out = nullptr;
+    size_t wr_play_cap = 0;
 };
 // Every device buffer a ctx owns (a feed slot's block: ssdr_feed_close) -- what ssdr_destroy frees.  One line per section of the
 // struct above, in its order (the own batch's buffers where `own` stands): a new `d_` member joins its section's line HERE, and tests/test_gpu_parity.py's
@@ -376,6 +405,9 @@ static void free_owned(ssdr_ctx *c)
         c->d_chz_taps, c->d_chz_hist, c->d_chz_in,                                                                    // wideband channeliser
         c->d_ws_taps, c->d_ws_scopes, c->d_ws_slot_stream, c->d_ws_hist, c->d_ws_out, c->d_ws_lines, c->d_ws_acc, c->d_ws_consts,   // wideband scopes
         c->d_wd_win, c->d_wd_part,                                                                                    // ... their detectors' scratch
+        c->own.d_wr_rows, c->own.d_wr_pcm, c->own.d_wr_rssi, c->own.d_wr_flags,                                       // tuned receivers: the own batch's rows and results,
+        c->d_wr_list, c->d_wr_state[0], c->d_wr_state[1], c->d_wr_hist[0], c->d_wr_hist[1], c->d_wr_phist[0], c->d_wr_phist[1], c->d_wr_phist_alt,
+        c->d_wr_consts, c->d_wr_taps, c->d_wr_parent, c->d_wr_play, c->d_wr_play_out,                                 // ... state, constants, play_buffer
     };
     for (void *p : owned)
         if (p) (void)hipFree(p);
@@ -584,6 +616,9 @@ static int subrx_restart(ssdr_ctx *c, uint32_t first, uint32_t count);
 static int subrx_compile(const ssdr_ctx *c, const ssdr_subrx *subs, uint32_t count, uint32_t decim, uint32_t rate,
                          std::vector<ssdr_chan_consts> &k, std::vector<float> &taps);
 static int subrx_install(ssdr_ctx *c, const std::vector<ssdr_chan_consts> &k, const std::vector<float> &taps);
+static int wbrx_compile(const ssdr_ctx *c, const ssdr_wb_rx *list, uint32_t count, uint32_t decim, uint32_t rate,
+                        std::vector<ssdr_chan_consts> &k, std::vector<float> &taps);
+static int wbrx_install(ssdr_ctx *c, const std::vector<ssdr_chan_consts> &k, const std::vector<float> &taps);
 
 // ssdr_set_decimation / ssdr_set_kiwi_rate, once their own checks have passed: the IQ arrives at decim * kiwi_rate from now on.
 // Every channel's constants (NCO steps, filter, AGC time constants, NBFM scale) are compiled for that rate, and streams of the old
@@ -594,6 +629,9 @@ static int change_input_rate(ssdr_ctx *c, uint32_t decim, uint32_t kiwi_rate)
     std::vector<ssdr_chan_consts> sub_k;                          // the sub-receivers at the new rate, before anything changes
     std::vector<float> sub_taps;
     SSDR_TRY(subrx_compile(c, c->h_sub.data(), (uint32_t)c->h_sub.size(), decim, kiwi_rate, sub_k, sub_taps));
+    std::vector<ssdr_chan_consts> wr_k;                           // ... and the tuned receivers, their offsets within the new wide band
+    std::vector<float> wr_taps;
+    SSDR_TRY(wbrx_compile(c, c->h_wr.data(), (uint32_t)c->h_wr.size(), decim, kiwi_rate, wr_k, wr_taps));
     std::vector<ssdr_chan_params> all = c->h_params;              // recompile every channel for the new input rate
     const uint32_t keep_decim = c->decim, keep_rate = c->kiwi_rate;
     c->decim = decim;
@@ -606,6 +644,7 @@ static int change_input_rate(ssdr_ctx *c, uint32_t decim, uint32_t kiwi_rate)
         rc = ssdr_reset_state(c, 0, c->n_ch);                     // phases and histories of the old rate mean nothing now
         if (rc == SSDR_OK) rc = zoom_restart(c, 0, c->n_ch);
         if (rc == SSDR_OK) rc = subrx_install(c, sub_k, sub_taps);
+        if (rc == SSDR_OK) rc = wbrx_install(c, wr_k, wr_taps);
     }
     if (rc != SSDR_OK) {                                          // all or nothing: back to the old rate, streams restarted
         c->decim = keep_decim;
@@ -1197,7 +1236,12 @@ static int ensure_wf_out(ssdr_ctx *c, Batch &b, uint32_t lines)
 }
 
 // the ctx's own batch takes `n_frames` frames of input at `d_iq`
-static void own_input(ssdr_ctx *c, const uint32_t *d_iq, uint32_t n_frames) { c->own.d_iq = d_iq; c->own.in_frames = n_frames; c->own.have_input = true; }
+// (an input that is no ssdr_push_wideband's has no tuned receivers' rows: that call sets wr_rows_valid behind this)
+static void own_input(ssdr_ctx *c, const uint32_t *d_iq, uint32_t n_frames)
+{
+    c->own.d_iq = d_iq; c->own.in_frames = n_frames; c->own.have_input = true;
+    c->wr_rows_valid = false;
+}
 
 int ssdr_push_iq(ssdr_ctx *c, const int16_t *iq, uint32_t n_frames, int is_device) SSDR_GUARD
 {
@@ -1784,6 +1828,8 @@ static int subrx_launch(ssdr_ctx *c, Batch &b, const SsdrAudioArgs &au, hipStrea
 
 // the stream the audio stage runs on under a plan; and, once all the call puts there is queued, the mark that later work on the
 // main stream (next input, playbuffer) follows
+static int wbrx_prepare(ssdr_ctx *c, Batch &b);
+static int wbrx_launch(ssdr_ctx *c, Batch &b, const SsdrAudioArgs &au, hipStream_t s);
 static hipStream_t audio_stream(const ssdr_ctx *c, ChainPlan plan) { return plan.beside ? c->stream2 : c->stream; }
 static int audio_queued(ssdr_ctx *c, ChainPlan plan)
 {
@@ -1806,6 +1852,7 @@ static int audio_stage(ssdr_ctx *c, Batch &b, ChainPlan plan, const SsdrWfArgs *
     }
     SSDR_TRY(audio_tail_prepare(c, b));
     SSDR_TRY(subrx_prepare(c, b));
+    SSDR_TRY(wbrx_prepare(c, b));
     SsdrAudioArgs a;
     a.iq = b.d_iq;
     a.ch_stride = (uint64_t)in_len(c, b.in_frames);
@@ -1868,7 +1915,8 @@ static int audio_stage(ssdr_ctx *c, Batch &b, ChainPlan plan, const SsdrWfArgs *
         if (fa.wf.tail)          // hop 512: only now may the carried half-line (the kernel's line 0 read it) become this batch's last one
             HIP_TRY(hipMemcpy2DAsync(c->d_wf_tail, (SSDR_NFFT / 2) * 4, fa.wf.iq + (size_t)(fa.wf.n_lines - 1) * SSDR_FRAME,
                                      fa.wf.ch_stride * 4, (SSDR_NFFT / 2) * 4, c->n_ch, hipMemcpyDeviceToDevice, s));
-        SSDR_TRY(subrx_launch(c, b, a, s));        // behind the one-read kernel: the sub-receivers, the tail, and then the W/F encoder
+        SSDR_TRY(subrx_launch(c, b, a, s));        // behind the one-read kernel: the sub-receivers, the tuned receivers, the tail, and then the W/F encoder
+        SSDR_TRY(wbrx_launch(c, b, a, s));
         SSDR_TRY(audio_tail_launch(c, b, s));
         return adpcm_wf_launch(c, b, s, fa.wf.n_avg);
     }
@@ -1929,6 +1977,7 @@ static int audio_stage(ssdr_ctx *c, Batch &b, ChainPlan plan, const SsdrWfArgs *
         }
     }
     SSDR_TRY(subrx_launch(c, b, a, s));
+    SSDR_TRY(wbrx_launch(c, b, a, s));
     return audio_tail_launch(c, b, s);
 }
 
@@ -3635,15 +3684,90 @@ int ssdr_subrx_stats(ssdr_ctx *c, float *total_ms, uint32_t *launches, int reset
 
 // ---- wideband scopes: DDCs on the channeliser's wide streams, drawn by the waterfall kernel (ssdr_wb_scope.hip) -----------------
 static double ws_wide_rate(const ssdr_ctx *c) { return (double)SSDR_CHAN_BRANCHES * c->decim * c->kiwi_rate / c->chz_over; }
-// no scope: the list and the histories go (the small tables stay for the next list)
+// the streams either list names, ascending: the ones that keep a ring
+static std::vector<uint32_t> ws_streams_of(const ssdr_wb_scope *scopes, size_t n_scopes, const ssdr_wb_rx *rx, size_t n_rx)
+{
+    std::vector<uint32_t> streams;
+    for (size_t i = 0; i < n_scopes; i++) streams.push_back(scopes[i].stream);
+    for (size_t i = 0; i < n_rx; i++) streams.push_back(rx[i].stream);
+    std::sort(streams.begin(), streams.end());
+    streams.erase(std::unique(streams.begin(), streams.end()), streams.end());
+    return streams;
+}
+// The rings of a new set of streams (ascending): a stream that keeps a user -- a scope or a tuned receiver -- keeps its history
+// (device to device, behind whatever run is queued), one that gets its first starts as silence, one that lost its last is not
+// copied.  Nothing changes unless it succeeds.
+static int ws_set_rings(ssdr_ctx *c, std::vector<uint32_t> streams)
+{
+    if (streams == c->h_ws_streams) return SSDR_OK;
+    if (!c->d_ws_slot_stream) HIP_TRY(hipMalloc(&c->d_ws_slot_stream, (SSDR_WB_SCOPES_MAX + SSDR_WB_RX_MAX) * 4));
+    uint32_t *fresh = nullptr;
+    if (!streams.empty()) HIP_TRY(hipMalloc(&fresh, streams.size() * (size_t)SSDR_WB_SCOPE_HIST * 4));
+    int rc = [&]() -> int {
+        for (size_t s = 0; s < streams.size(); s++) {
+            const auto old = std::lower_bound(c->h_ws_streams.begin(), c->h_ws_streams.end(), streams[s]);
+            uint32_t *dst = fresh + s * (size_t)SSDR_WB_SCOPE_HIST;
+            if (old != c->h_ws_streams.end() && *old == streams[s])
+                HIP_TRY(hipMemcpyAsync(dst, c->d_ws_hist + (size_t)(old - c->h_ws_streams.begin()) * SSDR_WB_SCOPE_HIST, (size_t)SSDR_WB_SCOPE_HIST * 4,
+                                       hipMemcpyDeviceToDevice, c->stream));
+            else
+                HIP_TRY(hipMemsetAsync(dst, 0, (size_t)SSDR_WB_SCOPE_HIST * 4, c->stream));
+        }
+        return release(c, c->d_ws_hist);                // (waits for the copies)
+    }();
+    if (rc != SSDR_OK) { (void)hipStreamSynchronize(c->stream); if (fresh) (void)hipFree(fresh); return rc; }
+    c->d_ws_hist = fresh;
+    c->h_ws_streams.swap(streams);
+    c->ws_dirty = true;                                 // (the slots of both device lists)
+    return SSDR_OK;
+}
+// no scope: the list goes, and the histories of the streams no tuned receiver names (the small tables stay for the next list)
 static int ws_clear(ssdr_ctx *c)
 {
     c->h_ws.clear();
     c->h_ws_det.clear();
-    c->h_ws_streams.clear();
     c->ws_run_valid = false;
     c->ws_win_valid = false;
-    return release(c, c->d_ws_hist);
+    return ws_set_rings(c, ws_streams_of(nullptr, 0, c->h_wr.data(), c->h_wr.size()));
+}
+// both device lists (slots, NCO steps) and the rings' streams, before a run that follows a change of either
+static int ws_upload(ssdr_ctx *c)
+{
+    if (!c->ws_dirty) return SSDR_OK;
+    const uint32_t ns = (uint32_t)c->h_ws.size(), nr = (uint32_t)c->h_wr.size();
+    const auto slot_of = [&](uint32_t stream) {
+        return (uint32_t)(std::lower_bound(c->h_ws_streams.begin(), c->h_ws_streams.end(), stream) - c->h_ws_streams.begin());
+    };
+    uint32_t rx_zoom = SSDR_WB_SCOPE_ZOOM_MAX;              // z = 10 - log2(O)
+    for (uint32_t o = c->chz_over; o > 1; o >>= 1) rx_zoom--;
+    std::vector<SsdrWbScope> dev(ns), dev_rx(nr);
+    for (uint32_t j = 0; j < ns; j++) {
+        const ssdr_wb_scope &v = c->h_ws[j];
+        dev[j] = SsdrWbScope{v.stream, slot_of(v.stream), v.zoom, zoom_dphi(v.offset_hz, ws_wide_rate(c))};
+    }
+    for (uint32_t j = 0; j < nr; j++) {
+        const ssdr_wb_rx &v = c->h_wr[j];
+        dev_rx[j] = SsdrWbScope{v.stream, slot_of(v.stream), rx_zoom, zoom_dphi(v.offset_hz, ws_wide_rate(c))};
+    }
+    if (ns) HIP_TRY(hipMemcpyAsync(c->d_ws_scopes, dev.data(), ns * sizeof(SsdrWbScope), hipMemcpyHostToDevice, c->stream));
+    if (nr) HIP_TRY(hipMemcpyAsync(c->d_wr_list, dev_rx.data(), nr * sizeof(SsdrWbScope), hipMemcpyHostToDevice, c->stream));
+    if (!c->h_ws_streams.empty())
+        HIP_TRY(hipMemcpyAsync(c->d_ws_slot_stream, c->h_ws_streams.data(), c->h_ws_streams.size() * 4, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));               // (the lists are host memory)
+    c->ws_dirty = false;
+    return SSDR_OK;
+}
+// the eleven tap tables, that of Z at 32 (Z - 1): at the first scope or tuned receiver
+static int ws_taps(ssdr_ctx *c)
+{
+    if (c->d_ws_taps) return SSDR_OK;
+    std::vector<float> t((size_t)32 * ((2u << SSDR_WB_SCOPE_ZOOM_MAX) - 1u));
+    for (uint32_t z = 0; z <= SSDR_WB_SCOPE_ZOOM_MAX; z++) SSDR_TRY(zoom_taps(1u << z, t.data() + 32u * ((1u << z) - 1u)));     // (32 Z - 1 taps and a zero)
+    float *d = nullptr;
+    HIP_TRY(hipMalloc(&d, t.size() * sizeof(float)));
+    c->d_ws_taps = d;
+    HIP_TRY(hipMemcpy(c->d_ws_taps, t.data(), t.size() * sizeof(float), hipMemcpyHostToDevice));
+    return SSDR_OK;
 }
 // log2 of W = max(1, min(T, SSDR_WB_SCOPE_SPAN) / (1024 Z)) at the ctx's hop, D and O: everything is a power of two
 static uint32_t ws_windows_log(const ssdr_ctx *c, uint32_t zoom)
@@ -3700,18 +3824,7 @@ static int ws_stage(ssdr_ctx *c, const uint32_t *in, uint64_t in_stride, uint32_
     c->ws_win_valid = false;
     const bool any_det = std::any_of(c->h_ws_det.begin(), c->h_ws_det.end(), [](uint32_t v) { return v != SSDR_WB_DET_SAMPLE; });
     if (any_det) SSDR_TRY(ws_det_scratch(c));
-    if (c->ws_dirty) {
-        std::vector<SsdrWbScope> dev(ns);
-        for (uint32_t j = 0; j < ns; j++) {
-            const ssdr_wb_scope &v = c->h_ws[j];
-            const uint32_t slot = (uint32_t)(std::lower_bound(c->h_ws_streams.begin(), c->h_ws_streams.end(), v.stream) - c->h_ws_streams.begin());
-            dev[j] = SsdrWbScope{v.stream, slot, v.zoom, zoom_dphi(v.offset_hz, ws_wide_rate(c))};
-        }
-        HIP_TRY(hipMemcpyAsync(c->d_ws_scopes, dev.data(), ns * sizeof(SsdrWbScope), hipMemcpyHostToDevice, c->stream));
-        HIP_TRY(hipMemcpyAsync(c->d_ws_slot_stream, c->h_ws_streams.data(), c->h_ws_streams.size() * 4, hipMemcpyHostToDevice, c->stream));
-        HIP_TRY(hipStreamSynchronize(c->stream));                       // (`dev` is host memory)
-        c->ws_dirty = false;
-    }
+    SSDR_TRY(ws_upload(c));
     const size_t rows = (size_t)ns * lines;
     if (rows > c->ws_rows) {                                            // the four buffers share one capacity
         SSDR_TRY(release(c, c->d_ws_out));
@@ -3761,6 +3874,175 @@ static int ws_stage(ssdr_ctx *c, const uint32_t *in, uint64_t in_stride, uint32_
     return SSDR_OK;
 }
 
+// ---- tuned receivers: a scope's DDC for every output of the call, a sub-receiver's audio chain on its rows (ssdr_set_wb_rx) ----------
+// the list's parameters compiled at a decimation and rate, the offsets held to that wide band: SSDR_EINVAL for what ssdr_set_wb_rx
+// refuses, and nothing is touched
+static int wbrx_compile(const ssdr_ctx *c, const ssdr_wb_rx *list, uint32_t count, uint32_t decim, uint32_t rate,
+                        std::vector<ssdr_chan_consts> &k, std::vector<float> &taps)
+{
+    k.resize(count);
+    taps.assign((size_t)count * SSDR_NTAP_MAX, 0.0f);
+    const double half = 0.5 * (double)SSDR_CHAN_BRANCHES * decim * rate / c->chz_over;
+    for (uint32_t j = 0; j < count; j++) {
+        if (list[j].stream >= c->chz_streams || (j && list[j].id <= list[j - 1].id)) return SSDR_EINVAL;
+        if (!(std::fabs(list[j].offset_hz) <= half)) return SSDR_EINVAL;        // (a NaN fails the comparison)
+        if (list[j].params.mode == SSDR_MODE_IQ) return SSDR_EINVAL;            // no I,Q output, as a sub-receiver
+        // (whatever the compiler's code -- SSDR_MODE_SAM at D > 1 is SSDR_ESTATE for a channel -- a receiver that does not fit is SSDR_EINVAL)
+        if (ssdr_compile_params_host(&list[j].params, &k[j], taps.data() + (size_t)j * SSDR_NTAP_MAX, decim, rate) != SSDR_OK) return SSDR_EINVAL;
+        if (decim > 1 && ssdr_audio_path(k[j]) != SSDR_PATH_GENERAL) return SSDR_EINVAL;    // the decimating kernel is the general path
+    }
+    return SSDR_OK;
+}
+static int wbrx_alloc(ssdr_ctx *c)
+{
+    for (int i = 0; i < 2; i++) {
+        if (!c->d_wr_state[i]) HIP_TRY(hipMalloc(&c->d_wr_state[i], SSDR_WB_RX_MAX * sizeof(ssdr_chan_state)));
+        if (!c->d_wr_hist[i]) HIP_TRY(hipMalloc(&c->d_wr_hist[i], (size_t)SSDR_WB_RX_MAX * SSDR_HIST * 4));
+        if (!c->d_wr_phist[i]) HIP_TRY(hipMalloc(&c->d_wr_phist[i], (size_t)SSDR_WB_RX_MAX * 8 * sizeof(double)));
+    }
+    if (!c->d_wr_phist_alt) HIP_TRY(hipMalloc(&c->d_wr_phist_alt, (size_t)SSDR_WB_RX_MAX * 8 * sizeof(double)));
+    if (!c->d_wr_consts) HIP_TRY(hipMalloc(&c->d_wr_consts, SSDR_WB_RX_MAX * sizeof(ssdr_chan_consts)));
+    if (!c->d_wr_taps) HIP_TRY(hipMalloc(&c->d_wr_taps, (size_t)SSDR_WB_RX_MAX * SSDR_NTAP_MAX * sizeof(float)));
+    if (!c->d_wr_play) HIP_TRY(hipMalloc(&c->d_wr_play, SSDR_WB_RX_MAX * sizeof(ssdr_play_chan)));
+    if (!c->d_wr_list) HIP_TRY(hipMalloc(&c->d_wr_list, SSDR_WB_RX_MAX * sizeof(SsdrWbScope)));
+    if (!c->d_wr_parent) {                                  // receiver r reads row r of the DDC's rows: written once
+        uint32_t ident[SSDR_WB_RX_MAX];
+        for (uint32_t j = 0; j < SSDR_WB_RX_MAX; j++) ident[j] = j;
+        HIP_TRY(hipMalloc(&c->d_wr_parent, sizeof ident));
+        HIP_TRY(hipMemcpy(c->d_wr_parent, ident, sizeof ident, hipMemcpyHostToDevice));
+    }
+    if (!c->d_ws_scopes) HIP_TRY(hipMalloc(&c->d_ws_scopes, SSDR_WB_SCOPES_MAX * sizeof(SsdrWbScope)));
+    return ws_taps(c);
+}
+// row j of set `set` as ssdr_reset_state leaves a channel (queued on the main stream; the caller waits: *fresh is host memory)
+static int wbrx_silence(ssdr_ctx *c, int set, uint32_t j, const ssdr_chan_state *fresh)
+{
+    HIP_TRY(hipMemcpyAsync(c->d_wr_state[set] + j, fresh, sizeof *fresh, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemsetAsync(c->d_wr_hist[set] + (size_t)j * SSDR_HIST, 0, SSDR_HIST * 4, c->stream));
+    HIP_TRY(hipMemsetAsync(c->d_wr_phist[set] + (size_t)j * 8, 0, 8 * sizeof(double), c->stream));
+    return SSDR_OK;
+}
+// every receiver's audio starts over (ssdr_channelizer_reset, a new rate or decimation)
+static int wbrx_restart(ssdr_ctx *c)
+{
+    if (c->h_wr.empty()) return SSDR_OK;
+    SSDR_TRY(join_audio(c));
+    std::vector<ssdr_chan_state> fresh(c->h_wr.size());
+    for (size_t j = 0; j < c->h_wr.size(); j++) {
+        fresh[j] = fresh_state(c->h_wr_consts[j]);
+        SSDR_TRY(wbrx_silence(c, c->wr_set, (uint32_t)j, &fresh[j]));
+        c->h_wr_started[j] = 0;
+    }
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return SSDR_OK;
+}
+static int wbrx_upload_consts(ssdr_ctx *c, const std::vector<ssdr_chan_consts> &k, const std::vector<float> &taps)
+{
+    if (k.empty()) return SSDR_OK;
+    SSDR_TRY(join_audio(c));
+    HIP_TRY(hipMemcpyAsync(c->d_wr_consts, k.data(), k.size() * sizeof(ssdr_chan_consts), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(c->d_wr_taps, taps.data(), taps.size() * sizeof(float), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return SSDR_OK;
+}
+// the list recompiled for a new rate or decimation (wbrx_compile): every receiver takes its constants and starts over; the NCO
+// steps are the new wide rate's (ws_dirty: change_input_rate)
+static int wbrx_install(ssdr_ctx *c, const std::vector<ssdr_chan_consts> &k, const std::vector<float> &taps)
+{
+    if (c->h_wr.empty()) return SSDR_OK;
+    SSDR_TRY(wbrx_upload_consts(c, k, taps));
+    c->h_wr_consts = k;
+    c->wr_rows_valid = false;
+    c->wr_run_valid = false;
+    return wbrx_restart(c);
+}
+// The receivers' DDC of one ssdr_push_wideband, on the main stream behind the filter bank and in front of the scopes' stage, whose
+// last launch rewrites the rings (with no scope set that launch is made here): `in` the call's wide samples, n0 the output index
+// before the call.  One launch for every output of every receiver, timed with its own event pair.
+static int wbrx_ddc_stage(ssdr_ctx *c, const uint32_t *in, uint64_t in_stride, uint32_t n_in, uint64_t n_out, uint64_t n0, uint32_t n_frames)
+{
+    const uint32_t nr = (uint32_t)c->h_wr.size();
+    if (!nr) return SSDR_OK;
+    Batch &b = c->own;
+    c->wr_rows_valid = false;
+    c->wr_run_valid = false;
+    SSDR_TRY(ws_upload(c));
+    SSDR_TRY(grow(c, b.d_wr_rows, b.wr_rows_cap, (size_t)nr * n_out, 4));
+    const uint32_t step = SSDR_CHAN_BRANCHES / c->chz_over;            // R = 2^zoom
+    SsdrWbRxArgs a = {};
+    a.zoom = SSDR_WB_SCOPE_ZOOM_MAX;
+    while ((1u << a.zoom) > step) a.zoom--;
+    a.n_out = (uint32_t)n_out;
+    a.lead = (uint32_t)((SSDR_NFFT - n_out % SSDR_NFFT) % SSDR_NFFT);  // 0, or 512 for an odd number of half-windows
+    a.n_win = (uint32_t)((n_out + a.lead) / SSDR_NFFT);
+    a.s.in = in; a.s.in_stride = in_stride; a.s.n_in = n_in;
+    a.s.scopes = c->d_wr_list; a.s.n_scopes = nr;
+    a.s.i0 = n0 * step;
+    a.s.hist_pos = (uint32_t)(a.s.i0 % SSDR_WB_SCOPE_HIST);
+    a.s.taps = c->d_ws_taps; a.s.hist = c->d_ws_hist; a.s.out = b.d_wr_rows;
+    a.s.slot_stream = c->d_ws_slot_stream; a.s.n_slots = (uint32_t)c->h_ws_streams.size();
+    SSDR_TRY(stage_launch(c, kTimedWbRxDdc, c->stream, [&]() -> int {
+        HIP_TRY(ssdr_launch_wb_rx(a, c->stream));
+        if (c->h_ws.empty()) HIP_TRY(ssdr_launch_wb_scope_hist(a.s, c->stream));
+        return SSDR_OK;
+    }));
+    b.wr_rows_n = nr;
+    b.wr_rows_frames = n_frames;
+    return SSDR_OK;
+}
+// room for the results of the audio run, before anything of it is launched
+static int wbrx_prepare(ssdr_ctx *c, Batch &b)
+{
+    const size_t n = c->h_wr.size();
+    if (!n || &b != &c->own) return SSDR_OK;
+    c->wr_run_valid = false;
+    const size_t need = n * b.in_frames;
+    if (b.wr_pcm_cap < need || b.wr_rssi_cap < need || b.wr_flags_cap < need) SSDR_TRY(drain_audio(c));
+    SSDR_TRY(grow(c, b, b.d_wr_pcm, b.wr_pcm_cap, need, SSDR_FRAME * sizeof(int16_t)));
+    SSDR_TRY(grow(c, b, b.d_wr_rssi, b.wr_rssi_cap, need, sizeof(float)));
+    return grow(c, b, b.d_wr_flags, b.wr_flags_cap, need, 1);
+}
+// Every tuned receiver advanced by the batch, on the audio stage's stream `s` behind the sub-receivers: the sub-receivers' kernels on
+// the receivers' own arrays, reading the DDC's rows (row r for receiver r).  Nothing is launched unless the batch's input is an
+// ssdr_push_wideband's with the list as it is: rows of an older list are nobody's.  `au`: the audio stage's arguments.
+static int wbrx_launch(ssdr_ctx *c, Batch &b, const SsdrAudioArgs &au, hipStream_t s)
+{
+    const uint32_t n = (uint32_t)c->h_wr.size();
+    if (!n || &b != &c->own || !c->wr_rows_valid || b.wr_rows_n != n || b.wr_rows_frames != b.in_frames) return SSDR_OK;
+    SsdrSubArgs a;
+    a.au = au;
+    a.au.iq = b.d_wr_rows;                                 // (ch_stride is the channels': rows of the same length)
+    a.au.n_ch = n;
+    a.au.consts = c->d_wr_consts; a.au.taps = c->d_wr_taps;
+    a.au.state = c->d_wr_state[c->wr_set]; a.au.hist = c->d_wr_hist[c->wr_set];
+    a.au.pcm = b.d_wr_pcm; a.au.rssi = b.d_wr_rssi; a.au.flags = b.d_wr_flags;
+    a.au.iq_out = nullptr;
+    a.au.chan_list = nullptr; a.au.list_n = n;
+    a.parent = c->d_wr_parent;
+    bool any_sam = false;
+    for (const ssdr_chan_consts &k : c->h_wr_consts) any_sam = any_sam || k.mode == SSDR_MODE_SAM;
+    SSDR_TRY(stage_launch(c, kTimedWbRxAudio, s, [&]() -> int {
+        HIP_TRY(ssdr_launch_audio_sub(a, c->decim, s));
+        if (any_sam) HIP_TRY(ssdr_launch_audio_sub_sam(a, s));
+        return SSDR_OK;
+    }));
+    std::fill(c->h_wr_started.begin(), c->h_wr_started.end(), (uint8_t)1);
+    b.wr_run_rows = n;
+    b.wr_run_frames = b.in_frames;
+    c->wr_run_valid = true;
+    return SSDR_OK;
+}
+// no tuned receiver: the list goes (ssdr_set_wb_rx with none, ssdr_set_channelizer); the rings follow the scopes alone
+static int wbrx_clear(ssdr_ctx *c)
+{
+    c->h_wr.clear();
+    c->h_wr_consts.clear();
+    c->h_wr_started.clear();
+    c->wr_rows_valid = false;
+    c->wr_run_valid = false;
+    return ws_set_rings(c, ws_streams_of(c->h_ws.data(), c->h_ws.size(), nullptr, 0));
+}
+
 // ---- wideband channeliser: one IQ stream in, 1024 rows of the ctx's input out (ssdr_channelize.hip) ------------------------
 int ssdr_set_channelizer(ssdr_ctx *c, uint32_t n_streams, uint32_t branches, uint32_t oversample, const float *taps,
                          uint32_t taps_per_branch) SSDR_GUARD
@@ -3768,7 +4050,8 @@ int ssdr_set_channelizer(ssdr_ctx *c, uint32_t n_streams, uint32_t branches, uin
     if (!c) return SSDR_EINVAL;
     if (n_streams == 0) {                                               // (the buffers stay for the next one)
         HIP_TRY(hipSetDevice(c->device));
-        SSDR_TRY(ws_clear(c));                                          // the scopes go with their streams
+        SSDR_TRY(wbrx_clear(c));                                        // the tuned receivers and the scopes go with their streams
+        SSDR_TRY(ws_clear(c));
         c->chz_streams = 0;
         return SSDR_OK;
     }
@@ -3779,7 +4062,8 @@ int ssdr_set_channelizer(ssdr_ctx *c, uint32_t n_streams, uint32_t branches, uin
         if (!std::isfinite(taps[i])) return SSDR_EINVAL;
     if (!c->feed.empty()) return SSDR_ESTATE;
     HIP_TRY(hipSetDevice(c->device));
-    SSDR_TRY(ws_clear(c));                                              // a new channeliser starts without scopes
+    SSDR_TRY(wbrx_clear(c));                                            // a new channeliser starts without tuned receivers or scopes
+    SSDR_TRY(ws_clear(c));
     std::vector<float> h(taps, taps + n_taps);
     constexpr size_t kMaxTaps = (size_t)SSDR_CHAN_TAPS_PER_BRANCH_MAX * SSDR_CHAN_BRANCHES;
     if (!c->d_chz_taps) HIP_TRY(hipMalloc(&c->d_chz_taps, kMaxTaps * sizeof(float)));
@@ -3816,7 +4100,7 @@ int ssdr_channelizer_reset(ssdr_ctx *c) SSDR_GUARD
     if (c->d_ws_hist) HIP_TRY(hipMemsetAsync(c->d_ws_hist, 0, c->h_ws_streams.size() * SSDR_WB_SCOPE_HIST * 4, c->stream));   // the scopes' list stays
     c->ws_win_valid = false;
     c->chz_out_index = 0;
-    return SSDR_OK;
+    return wbrx_restart(c);                                             // the tuned receivers' list stays too; their audio starts over
 } SSDR_UNGUARD
 
 int ssdr_get_channelizer_state(ssdr_ctx *c, int16_t *hist, uint64_t *out_index) SSDR_GUARD
@@ -3855,9 +4139,11 @@ int ssdr_push_wideband(ssdr_ctx *c, const int16_t *iq, uint32_t n_frames, int is
     a.out_stride = n_out;
     a.tw_stage = c->d_tw;
     SSDR_TRY(stage_launch(c, kTimedChan, c->stream, [&]() -> int { HIP_TRY(ssdr_launch_channelize(a, c->stream)); return SSDR_OK; }));
+    SSDR_TRY(wbrx_ddc_stage(c, a.in, a.in_stride, a.n_in, n_out, c->chz_out_index, n_frames));      // (reads the rings the scopes' stage rewrites)
     SSDR_TRY(ws_stage(c, a.in, a.in_stride, a.n_in, n_out, c->chz_out_index));
     c->chz_out_index += n_out;
     own_input(c, c->d_iq_own, n_frames);
+    c->wr_rows_valid = !c->h_wr.empty();
     return SSDR_OK;
 } SSDR_UNGUARD
 
@@ -3878,41 +4164,9 @@ int ssdr_set_wb_scopes(ssdr_ctx *c, const ssdr_wb_scope *scopes, uint32_t count)
     }
     HIP_TRY(hipSetDevice(c->device));
     if (!count) return ws_clear(c);
-    if (!c->d_ws_taps) {                                    // the first scope: the eleven tap tables and the small lists
-        std::vector<float> t((size_t)32 * ((2u << SSDR_WB_SCOPE_ZOOM_MAX) - 1u));
-        for (uint32_t z = 0; z <= SSDR_WB_SCOPE_ZOOM_MAX; z++) SSDR_TRY(zoom_taps(1u << z, t.data() + 32u * ((1u << z) - 1u)));     // (32 Z - 1 taps and a zero)
-        float *d = nullptr;
-        HIP_TRY(hipMalloc(&d, t.size() * sizeof(float)));
-        c->d_ws_taps = d;
-        HIP_TRY(hipMemcpy(c->d_ws_taps, t.data(), t.size() * sizeof(float), hipMemcpyHostToDevice));
-    }
+    SSDR_TRY(ws_taps(c));                                   // the first scope: the eleven tap tables and the small lists
     if (!c->d_ws_scopes) HIP_TRY(hipMalloc(&c->d_ws_scopes, SSDR_WB_SCOPES_MAX * sizeof(SsdrWbScope)));
-    if (!c->d_ws_slot_stream) HIP_TRY(hipMalloc(&c->d_ws_slot_stream, SSDR_WB_SCOPES_MAX * 4));
-    std::vector<uint32_t> streams;
-    for (uint32_t i = 0; i < count; i++) streams.push_back(scopes[i].stream);
-    std::sort(streams.begin(), streams.end());
-    streams.erase(std::unique(streams.begin(), streams.end()), streams.end());
-    if (streams != c->h_ws_streams) {
-        // the rings of the new set of streams: a stream that keeps a scope keeps its history (device to device, behind whatever run
-        // is queued), one that gets its first starts as silence, one that lost its last is not copied
-        uint32_t *fresh = nullptr;
-        HIP_TRY(hipMalloc(&fresh, streams.size() * (size_t)SSDR_WB_SCOPE_HIST * 4));
-        int rc = [&]() -> int {
-            for (size_t s = 0; s < streams.size(); s++) {
-                const auto old = std::lower_bound(c->h_ws_streams.begin(), c->h_ws_streams.end(), streams[s]);
-                uint32_t *dst = fresh + s * (size_t)SSDR_WB_SCOPE_HIST;
-                if (old != c->h_ws_streams.end() && *old == streams[s])
-                    HIP_TRY(hipMemcpyAsync(dst, c->d_ws_hist + (size_t)(old - c->h_ws_streams.begin()) * SSDR_WB_SCOPE_HIST, (size_t)SSDR_WB_SCOPE_HIST * 4,
-                                           hipMemcpyDeviceToDevice, c->stream));
-                else
-                    HIP_TRY(hipMemsetAsync(dst, 0, (size_t)SSDR_WB_SCOPE_HIST * 4, c->stream));
-            }
-            return release(c, c->d_ws_hist);                // (waits for the copies)
-        }();
-        if (rc != SSDR_OK) { (void)hipStreamSynchronize(c->stream); (void)hipFree(fresh); return rc; }
-        c->d_ws_hist = fresh;
-        c->h_ws_streams.swap(streams);
-    }
+    SSDR_TRY(ws_set_rings(c, ws_streams_of(scopes, count, c->h_wr.data(), c->h_wr.size())));     // (a stream a tuned receiver names keeps its ring)
     c->h_ws.assign(scopes, scopes + count);
     c->h_ws_det.assign(count, SSDR_WB_DET_SAMPLE);
     c->ws_dirty = true;
@@ -4010,6 +4264,142 @@ int ssdr_wb_scope_taps(uint32_t zoom, float *out) SSDR_GUARD
 int ssdr_wb_scope_stats(ssdr_ctx *c, float *total_ms, uint32_t *launches, int reset) SSDR_GUARD
 {
     return stage_stats(c, kTimedScope, total_ms, launches, reset);
+} SSDR_UNGUARD
+
+int ssdr_set_wb_rx(ssdr_ctx *c, const ssdr_wb_rx *list, uint32_t count) SSDR_GUARD
+{
+    if (!c || count > SSDR_WB_RX_MAX || (count && !list)) return SSDR_EINVAL;
+    if (!c->chz_streams) return SSDR_ESTATE;
+    std::vector<ssdr_chan_consts> k;                        // all or nothing: every receiver is checked before the list is touched
+    std::vector<float> taps;
+    SSDR_TRY(wbrx_compile(c, list, count, c->decim, c->kiwi_rate, k, taps));
+    HIP_TRY(hipSetDevice(c->device));
+    if (!count) return wbrx_clear(c);                       // (the state arrays stay for the next list)
+    SSDR_TRY(wbrx_alloc(c));
+    SSDR_TRY(join_audio(c));                                // what is queued beside the main stream reads the current set and the constants
+    SSDR_TRY(ws_set_rings(c, ws_streams_of(c->h_ws.data(), c->h_ws.size(), list, count)));
+    // the audio state as ssdr_set_subrx keeps it: the new list is built in the other set of arrays, a receiver that stays is copied
+    // there with all it carries, a new one starts as after ssdr_reset_state.  The DDC has nothing to keep.
+    const int from = c->wr_set, to = from ^ 1;
+    std::vector<ssdr_chan_state> fresh(count);
+    std::vector<uint8_t> started(count, 0);
+    bool same_rows = c->h_wr.size() == count;
+    size_t i = 0;
+    for (uint32_t j = 0; j < count; j++) {
+        while (i < c->h_wr.size() && c->h_wr[i].id < list[j].id) i++;
+        const bool stays = i < c->h_wr.size() && c->h_wr[i].id == list[j].id && c->h_wr[i].stream == list[j].stream;
+        same_rows = same_rows && stays && i == j;
+        if (stays && c->h_wr_started[i]) {
+            const hipMemcpyKind d2d = hipMemcpyDeviceToDevice;
+            HIP_TRY(hipMemcpyAsync(c->d_wr_state[to] + j, c->d_wr_state[from] + i, sizeof(ssdr_chan_state), d2d, c->stream));
+            HIP_TRY(hipMemcpyAsync(c->d_wr_hist[to] + (size_t)j * SSDR_HIST, c->d_wr_hist[from] + i * SSDR_HIST, SSDR_HIST * 4, d2d, c->stream));
+            HIP_TRY(hipMemcpyAsync(c->d_wr_phist[to] + (size_t)j * 8, c->d_wr_phist[from] + i * 8, 8 * sizeof(double), d2d, c->stream));
+            if (k[j].mode == SSDR_MODE_SAM && c->h_wr_consts[i].mode != SSDR_MODE_SAM) SSDR_TRY(sam_loop_zero(c, c->d_wr_state[to] + j, 1));
+            started[j] = 1;
+        } else {                                            // new, or kept but not run yet: it starts at ITS knee (ssdr_set_params)
+            fresh[j] = fresh_state(k[j]);
+            SSDR_TRY(wbrx_silence(c, to, j, &fresh[j]));
+        }
+    }
+    SSDR_TRY(wbrx_upload_consts(c, k, taps));               // (waits: `fresh` is host memory)
+    c->h_wr.assign(list, list + count);
+    c->h_wr_consts = k;
+    c->h_wr_started = started;
+    c->wr_set = to;
+    c->ws_dirty = true;                                     // the offsets act from the next push on
+    if (!same_rows) { c->wr_rows_valid = false; c->wr_run_valid = false; }
+    return SSDR_OK;
+} SSDR_UNGUARD
+
+int ssdr_get_wb_rx(ssdr_ctx *c, ssdr_wb_rx *list, uint32_t *count) SSDR_GUARD
+{
+    return get_list(c, &ssdr_ctx::h_wr, list, count);
+} SSDR_UNGUARD
+
+int ssdr_wb_rx_audio(ssdr_ctx *c, int16_t *pcm, float *rssi, uint8_t *flags, int out_is_device) SSDR_GUARD
+{
+    if (!c) return SSDR_EINVAL;
+    if (c->h_wr.empty() || !c->wr_run_valid) return SSDR_ESTATE;
+    HIP_TRY(hipSetDevice(c->device));
+    SSDR_TRY(join_audio(c));
+    const Batch &b = c->own;
+    const size_t n = (size_t)b.wr_run_rows * b.wr_run_frames;
+    if (pcm) SSDR_TRY(copy_out(c, pcm, b.d_wr_pcm, n * SSDR_FRAME * sizeof(int16_t), out_is_device, kSyncLater));
+    if (rssi) SSDR_TRY(copy_out(c, rssi, b.d_wr_rssi, n * sizeof(float), out_is_device, kSyncLater));
+    if (flags) SSDR_TRY(copy_out(c, flags, b.d_wr_flags, n, out_is_device, kSyncLater));
+    if (!out_is_device) HIP_TRY(hipStreamSynchronize(c->stream));
+    return SSDR_OK;
+} SSDR_UNGUARD
+
+int ssdr_read_wb_rx(ssdr_ctx *c, uint32_t first_row, uint32_t count, int16_t *iq_out) SSDR_GUARD
+{
+    if (!c) return SSDR_EINVAL;
+    if (c->h_wr.empty() || !c->wr_rows_valid) return SSDR_ESTATE;
+    if ((uint64_t)first_row + count > c->own.wr_rows_n) return SSDR_EINVAL;
+    if (!count || !iq_out) return SSDR_OK;
+    HIP_TRY(hipSetDevice(c->device));
+    const size_t n = in_len(c, c->own.wr_rows_frames);
+    return copy_out(c, iq_out, c->own.d_wr_rows + first_row * n, count * n * 4, 0, kSyncHost);
+} SSDR_UNGUARD
+
+int ssdr_get_wb_rx_state(ssdr_ctx *c, uint32_t first_row, uint32_t count, ssdr_chan_state *state, int16_t *hist) SSDR_GUARD
+{
+    if (!c || (uint64_t)first_row + count > c->h_wr.size()) return SSDR_EINVAL;
+    if (!count) return SSDR_OK;
+    HIP_TRY(hipSetDevice(c->device));
+    SSDR_TRY(join_audio(c));
+    const int set = c->wr_set;
+    if (state) SSDR_TRY(copy_out(c, state, c->d_wr_state[set] + first_row, count * sizeof(ssdr_chan_state), 0, kSyncLater));
+    if (hist) SSDR_TRY(copy_out(c, hist, c->d_wr_hist[set] + (size_t)first_row * SSDR_HIST, (size_t)count * SSDR_HIST * 4, 0, kSyncLater));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return SSDR_OK;
+} SSDR_UNGUARD
+
+int ssdr_get_wb_rx_sam_carrier(ssdr_ctx *c, uint32_t first_row, uint32_t count, float *offset_hz, float *phase_rad) SSDR_GUARD
+{
+    if (!c || !offset_hz || (uint64_t)first_row + count > c->h_wr.size()) return SSDR_EINVAL;
+    if (!count) return SSDR_OK;
+    return sam_carrier_read(c, c->d_wr_state[c->wr_set] + first_row, c->h_wr_consts.data() + first_row, count, offset_hz, phase_rad);
+} SSDR_UNGUARD
+
+int ssdr_get_wb_rx_consts(ssdr_ctx *c, uint32_t first_row, uint32_t count, ssdr_chan_consts *consts, float *taps) SSDR_GUARD
+{
+    if (!c || (uint64_t)first_row + count > c->h_wr.size()) return SSDR_EINVAL;
+    if (!count) return SSDR_OK;
+    HIP_TRY(hipSetDevice(c->device));
+    SSDR_TRY(join_audio(c));
+    if (consts) SSDR_TRY(copy_out(c, consts, c->d_wr_consts + first_row, count * sizeof(ssdr_chan_consts), 0, kSyncLater));
+    if (taps) SSDR_TRY(copy_out(c, taps, c->d_wr_taps + (size_t)first_row * SSDR_NTAP_MAX, (size_t)count * SSDR_NTAP_MAX * 4, 0, kSyncLater));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return SSDR_OK;
+} SSDR_UNGUARD
+
+int ssdr_run_wb_rx_playbuffer(ssdr_ctx *c, const ssdr_play_chan *chans, int16_t *out, int out_is_device) SSDR_GUARD
+{
+    if (!c || !chans) return SSDR_EINVAL;
+    if (c->h_wr.empty() || !c->wr_run_valid) return SSDR_ESTATE;
+    HIP_TRY(hipSetDevice(c->device));
+    SSDR_TRY(join_audio(c));
+    const uint32_t n = c->own.wr_run_rows, nf = c->own.wr_run_frames;
+    const bool wide = c->kiwi_rate != SSDR_RATE;
+    const size_t per_frame = wide ? (size_t)SSDR_RS_OUT_PER_FRAME : 2048;
+    SSDR_TRY(ensure_play(c));                                 // (the tap tables are the ctx's)
+    SSDR_TRY(grow(c, c->d_wr_play_out, c->wr_play_cap, (size_t)n * nf, (size_t)2048 * 2 * sizeof(int16_t)));
+    HIP_TRY(hipMemcpyAsync(c->d_wr_play, chans, (size_t)n * sizeof(ssdr_play_chan), hipMemcpyHostToDevice, c->stream));
+    SsdrPlayArgs a;                                           // the receivers as the channels of a small ctx
+    a.pcm = c->own.d_wr_pcm; a.n_ch = n; a.n_frames = nf; a.chans = c->d_wr_play; a.taps = c->d_play_taps; a.rs_taps = c->d_play_rs_taps;
+    a.hist = c->d_wr_phist[c->wr_set]; a.hist_out = c->d_wr_phist_alt; a.sel = nullptr; a.n_sel = n; a.out = c->d_wr_play_out; a.mono = nullptr;
+    HIP_TRY(wide ? ssdr_launch_play_rs(a, c->stream) : ssdr_launch_play(a, c->stream));
+    if (!wide) std::swap(c->d_wr_phist[c->wr_set], c->d_wr_phist_alt);             // (the 64/27 branch carries no history)
+    if (out) SSDR_TRY(copy_out(c, out, c->d_wr_play_out, (size_t)n * nf * per_frame * 2 * sizeof(int16_t), out_is_device, kSyncLater));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return SSDR_OK;
+} SSDR_UNGUARD
+
+int ssdr_wb_rx_stats(ssdr_ctx *c, float *ddc_ms, float *audio_ms, uint32_t *launches, int reset) SSDR_GUARD
+{
+    SSDR_TRY(stage_stats(c, kTimedWbRxDdc, ddc_ms, launches, reset));
+    return stage_stats(c, kTimedWbRxAudio, audio_ms, launches ? launches + 1 : nullptr, reset);
 } SSDR_UNGUARD
 
 int ssdr_set_wf_lines(ssdr_ctx *c, const int16_t *wf_sum, uint32_t lines) SSDR_GUARD

@@ -290,6 +290,12 @@ struct SsdrWbDetArgs {
     const float2 *tw_stage;
     const uint32_t *lut;
 };
+// tuned receivers (ssdr_wb_scope.hip, ssdr_set_wb_rx): the scopes' DDC at zoom z = 10 - log2(O) for EVERY output of the call.  s: the
+// call as the scopes see it, s.scopes [s.n_scopes] the receivers (all of zoom `zoom`), s.out [s.n_scopes][n_out] I | Q << 16; of
+// s.n_lines, s.first_end, s.period, s.zoom_mask nothing is read.  A receiver's n_out = s.n_in >> zoom outputs are n_win windows of
+// 1024 that end with the call; the first one begins `lead` (0 or 512) outputs in front of it, and those are not computed.
+struct SsdrWbRxArgs { SsdrWbScopeArgs s; uint32_t zoom, n_out, n_win, lead; };
+hipError_t ssdr_launch_wb_rx(const SsdrWbRxArgs &a, hipStream_t stream);
 hipError_t ssdr_launch_wb_scope(const SsdrWbScopeArgs &a, hipStream_t stream);
 hipError_t ssdr_launch_wb_scope_win(const SsdrWbDetArgs &d, hipStream_t stream);
 hipError_t ssdr_launch_wb_scope_det(const SsdrWbDetArgs &d, hipStream_t stream);      // the chains, then the tree and the quantiser

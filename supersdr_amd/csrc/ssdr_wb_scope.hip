@@ -42,6 +42,8 @@
 // function sc_outputs, ssdr_wb_scope_kernel calls it for (scope, line) as before (its code did not change: profiles/
 // scope_det_isa_spills.txt) and ssdr_wb_scope_win_kernel for (item, window) -- an end at or before the call's first sample reads the ring
 // alone (rel < 0 everywhere; the oldest sample of the oldest window lies SSDR_WB_SCOPE_SPAN + 32 Z - 1 < H before the line's end).
+// Tuned receivers (ssdr_set_wb_rx) need every output of a call at z = 10 - log2(O), consecutive, into rows of their own:
+// ssdr_wb_rx_kernel is the same body once more, (receiver, window) x chunk, with the windows ending where the call ends.
 #include "ssdr_math.h"
 #include "ssdr_kernels.h"
 
@@ -174,6 +176,20 @@ __global__ __launch_bounds__(SC_BLOCK) void ssdr_wb_scope_win_kernel(SsdrWbDetAr
     sc_outputs(d.s, scope, [&]() { return (int32_t)(d.s.first_end + line * d.s.period) - (int32_t)(v << (10u + d.zoom)); }, d.win, row, s_part);
 }
 
+// Tuned receivers (ssdr_set_wb_rx): the same body for every output of the call.  At z = 9 and 10 a workgroup is one chunk of 128
+// outputs (per_wg = 1), so the grid is (receiver, window) x 8 chunks with the windows ending where the call ends: a call of an odd
+// number of half-windows (n_out = 512 at one frame, D = 1) begins in the middle of window 0, and the four workgroups in front of it
+// leave at once -- nothing nobody keeps is computed or stored.  Row and end are all that differs from a line: the order of the sums
+// is sc_outputs', so a row is bit-identical however the stream is cut into calls.
+__global__ __launch_bounds__(SC_BLOCK) void ssdr_wb_rx_kernel(SsdrWbRxArgs a)
+{
+    __shared__ float2 s_part[SC_PART];
+    const uint32_t rx = blockIdx.x / a.n_win, v = blockIdx.x - rx * a.n_win;
+    if (v == 0u && (blockIdx.y << 7) < a.lead) return;                               // (uniform)
+    const int64_t first = (int64_t)rx * a.n_out + (int64_t)v * SSDR_NFFT - (int64_t)a.lead;      // window v's output 0 in the rows
+    sc_outputs(a.s, rx, [&]() { return (int32_t)((((v + 1u) << 10) - a.lead) << a.zoom); }, a.s.out + first, 0u, s_part);
+}
+
 // the call's last min(n_in, H) samples of every scoped stream into its ring: the second launch (see the header)
 __global__ __launch_bounds__(256) void ssdr_wb_scope_hist_kernel(SsdrWbScopeArgs a)
 {
@@ -220,6 +236,18 @@ hipError_t ssdr_launch_wb_scope_win(const SsdrWbDetArgs &d, hipStream_t stream)
     const uint32_t ch_log = z <= 4u ? 5u : 7u, zw_log = z < 8u ? z : 8u;
     const uint32_t n_chunks = SSDR_NFFT >> ch_log, per_wg = (256u >> zw_log) < n_chunks ? (256u >> zw_log) : n_chunks;
     hipLaunchKernelGGL(ssdr_wb_scope_win_kernel, dim3(d.n_items << d.w_log, n_chunks / per_wg), dim3(SC_BLOCK), 0, stream, d);
+    return hipGetLastError();
+}
+
+// every output of the call for every tuned receiver: the windows end with the call, the grid's second axis is the 8 chunks of one
+hipError_t ssdr_launch_wb_rx(const SsdrWbRxArgs &a, hipStream_t stream)
+{
+    if (!a.s.n_scopes || !a.n_out) return hipSuccess;
+    if (a.s.n_scopes > SSDR_WB_RX_MAX || (a.zoom != 9u && a.zoom != 10u) || (a.lead != 0u && a.lead != SSDR_NFFT / 2u) || !a.n_win ||
+        (uint64_t)a.n_win * SSDR_NFFT != (uint64_t)a.n_out + a.lead || ((uint64_t)a.n_out << a.zoom) != a.s.n_in || a.s.n_in > 0x7FFFFFFFu ||
+        a.s.hist_pos >= SSDR_WB_SCOPE_HIST || !a.s.hist || !a.s.out || !a.s.in || !a.s.scopes || !a.s.taps)
+        return hipErrorInvalidValue;
+    hipLaunchKernelGGL(ssdr_wb_rx_kernel, dim3(a.s.n_scopes * a.n_win, SSDR_NFFT >> 7), dim3(SC_BLOCK), 0, stream, a);
     return hipGetLastError();
 }
 

@@ -666,6 +666,95 @@ class SsdrEngine:
         """-> (total_ms, runs) of the scope stage since the last reset (the time only with set_profiling on)"""
         return self._stage_stats("ssdr_wb_scope_stats", reset)
 
+    # ---- tuned receivers: demodulators at any frequency of the channeliser's wide streams
+    def set_wb_rx(self, receivers):
+        """The tuned receivers, replacing the whole list: a sequence of (id, stream, offset_hz, ChanParams), ids ascending and unique,
+        offset_hz the centre from the wide stream's centre (|offset_hz| <= F / 2), at most 64; an empty sequence removes them all.  A
+        receiver whose (id, stream) was in the old list keeps its audio stream and takes the new parameters as set_params would -- a new
+        offset acts from the next push_wideband on and restarts nobody; any other starts as after reset_state.  A value that does not
+        fit the struct raises ValueError before the library is called; a list the library refuses raises SsdrError (SSDR_EINVAL /
+        SSDR_ESTATE).  Either way nothing changes."""
+        rows = [(int(i), int(w), float(off), p) for i, w, off, p in receivers]
+        if any(not 0 <= i < 2 ** 32 or not 0 <= w < 2 ** 32 or not isinstance(p, ChanParams) for i, w, _, p in rows):
+            raise ValueError("tuned receivers %r: out of range" % (receivers,))
+        arr = (L.WbRx * max(len(rows), 1))(*[L.WbRx(*r) for r in rows])
+        check(lib.ssdr_set_wb_rx(self._ctx, arr if rows else None, len(rows)), "ssdr_set_wb_rx")
+
+    def get_wb_rx(self):
+        """-> [(id, stream, offset_hz, ChanParams), ...] the tuned receivers as set"""
+        n = C.c_uint32(0)
+        arr = (L.WbRx * L.WB_RX_MAX)()
+        check(lib.ssdr_get_wb_rx(self._ctx, arr, C.byref(n)), "ssdr_get_wb_rx")
+        out = []
+        for v in arr[:n.value]:
+            p = ChanParams()
+            C.memmove(C.byref(p), C.byref(v.params), C.sizeof(ChanParams))
+            out.append((v.id, v.stream, v.offset_hz, p))
+        return out
+
+    def _wb_rx_count(self):
+        n = C.c_uint32(0)
+        check(lib.ssdr_get_wb_rx(self._ctx, None, C.byref(n)), "ssdr_get_wb_rx")
+        return n.value
+
+    def read_wb_rx(self, first=0, count=None):
+        """-> int16 [count, n_frames * 512 * D, 2]: the IQ rows the receivers' DDC stored in the last push_wideband, in list order"""
+        count = self._wb_rx_count() - first if count is None else int(count)
+        out = np.empty((count, self.in_frames * L.FRAME * self.decim, 2), np.int16)
+        check(lib.ssdr_read_wb_rx(self._ctx, int(first), count, out.ctypes.data), "ssdr_read_wb_rx")
+        return out
+
+    def wb_rx_audio(self):
+        """-> (pcm int16 [n, n_frames*512], rssi float32 [n, n_frames], flags uint8 [n, n_frames]) of the last run_audio / run_chain
+        behind a push_wideband, rows in list order"""
+        n, nf = self._wb_rx_count(), self.audio_frames
+        pcm = np.empty((n, nf * L.FRAME), np.int16)
+        rssi = np.empty((n, nf), np.float32)
+        flags = np.empty((n, nf), np.uint8)
+        check(lib.ssdr_wb_rx_audio(self._ctx, pcm.ctypes.data, rssi.ctypes.data, flags.ctypes.data, 0), "ssdr_wb_rx_audio")
+        return pcm, rssi, flags
+
+    def wb_rx_state(self, first=0, count=None):
+        """-> (state, hist) of rows [first, first + count) of the list, as get_state"""
+        count = self._wb_rx_count() - first if count is None else int(count)
+        st = np.empty(count, STATE_DTYPE)
+        hist = np.empty((count, L.HIST, 2), np.int16)
+        check(lib.ssdr_get_wb_rx_state(self._ctx, int(first), count, st.ctypes.data, hist.ctypes.data), "ssdr_get_wb_rx_state")
+        return st, hist
+
+    def wb_rx_sam_carrier(self, first=0, count=None):
+        """-> (offset_hz, phase_rad) float32 arrays of rows [first, first + count) of the list, as sam_carrier"""
+        count = self._wb_rx_count() - first if count is None else int(count)
+        hz, ph = np.zeros(count, np.float32), np.zeros(count, np.float32)
+        check(lib.ssdr_get_wb_rx_sam_carrier(self._ctx, int(first), count, hz.ctypes.data, ph.ctypes.data), "ssdr_get_wb_rx_sam_carrier")
+        return hz, ph
+
+    def wb_rx_consts(self, first=0, count=None):
+        """-> (consts, taps) of rows [first, first + count) of the list, as get_consts"""
+        count = self._wb_rx_count() - first if count is None else int(count)
+        k = np.empty(count, CONSTS_DTYPE)
+        taps = np.empty((count, L.NTAP_MAX), np.float32)
+        check(lib.ssdr_get_wb_rx_consts(self._ctx, int(first), count, k.ctypes.data, taps.ctypes.data), "ssdr_get_wb_rx_consts")
+        return k, taps
+
+    def run_wb_rx_playbuffer(self, chans):
+        """play_buffer for the tuned receivers' frames of the last run -> int16 [n, n_frames*L, 2], L = playbuffer_frame_len().
+        chans: list of PlayChan, one per receiver in list order, or a ctypes array."""
+        n = self._wb_rx_count()
+        arr = chans if isinstance(chans, C.Array) else (PlayChan * max(n, 1))(*chans)
+        if len(arr) < n:
+            raise ValueError("run_wb_rx_playbuffer: %d settings for %d tuned receivers" % (len(arr), n))
+        out = np.empty((n, self.audio_frames * self.playbuffer_frame_len(), 2), np.int16)
+        check(lib.ssdr_run_wb_rx_playbuffer(self._ctx, arr, out.ctypes.data, 0), "ssdr_run_wb_rx_playbuffer")
+        return out
+
+    def wb_rx_stats(self, reset=False):
+        """-> (ddc_ms, audio_ms, ddc_runs, audio_runs) of the tuned receivers' stage since the last reset (the times only with
+        set_profiling on)"""
+        d, a, n = C.c_float(), C.c_float(), (C.c_uint32 * 2)()
+        check(lib.ssdr_wb_rx_stats(self._ctx, C.byref(d), C.byref(a), C.byref(n), 1 if reset else 0), "ssdr_wb_rx_stats")
+        return d.value, a.value, n[0], n[1]
+
     def audio_iq(self):
         """-> int16 [n_ch, n_frames*512, 2]: I,Q of the channels in "iq" mode for the last run_audio (rows of other modes: 0)"""
         out = np.empty((self.n_ch, self.audio_frames * L.FRAME, 2), np.int16)

@@ -143,6 +143,12 @@ class Channelizer:
             raise ValueError("zoom %r outside 0..%d" % (zoom, self.SCOPE_ZOOM_MAX))
         return float(rate) / (1 << int(zoom))
 
+    @property
+    def rx_zoom(self):
+        """the zoom whose DDC runs at a row's rate: 10 - log2(oversample).  A tuned receiver (ssdr_set_wb_rx) is that DDC at any centre
+        with an audio chain behind it; a scope of this zoom at the same offset shows what the receiver hears."""
+        return self.SCOPE_ZOOM_MAX - (self.oversample.bit_length() - 1)
+
     SCOPE_SPAN = 1024 * 1024                        # SSDR_WB_SCOPE_SPAN: the wide samples of a line period a detector looks at
 
     def scope_windows(self, zoom, hop=1024, D=1):

@@ -123,8 +123,10 @@ class SuperframeResult:
     sub_flags uint8 [n, frames] and, with gpu_post and a worker on one of them, sub_play int16 [n, frames*L, 2] have a row for each
     (all None: no sub-receiver is open).
     With wideband scopes (IQHub.open_scope): scope_ids lists them, ascending, and scope_lines int16 [n, k, 1024] holds the k byte lines
-    (N = 1) each completed in this feed_wideband, k >= 0 (both None: no scope is open)."""
-    __slots__ = ("seq", "wf", "n_avg", "color", "chans", "pcm", "rssi", "flags", "play", "mono", "iq", "wire_rssi", "post_channels", "out_channels",
+    (N = 1) each completed in this feed_wideband, k >= 0 (both None: no scope is open).
+    With tuned receivers (IQHub.open_tuned): tuned_ids lists them, ascending, and tuned_pcm / tuned_rssi / tuned_flags / tuned_play have
+    a row for each, as the sub-receivers' arrays do (all None: no tuned receiver is open, or the run was no feed_wideband)."""
+    __slots__ = ("tuned_ids", "tuned_pcm", "tuned_rssi", "tuned_flags", "tuned_play","seq", "wf", "n_avg", "color", "chans", "pcm", "rssi", "flags", "play", "mono", "iq", "wire_rssi", "post_channels", "out_channels",
                  "snd_adpcm", "wf_adpcm", "snd_adpcm_channels", "wf_adpcm_channels", "squelched", "view_lines", "view_channels",
                  "squelched_channels", "sub_ids", "sub_pcm", "sub_rssi", "sub_flags", "sub_play", "scope_ids", "scope_lines")
 
@@ -328,6 +330,10 @@ class IQHub:
         self._next_scope = 1
         self.scope_queue = {}                        # sid -> bounded queue of WfLine (N = 1), drop-oldest
         self.scope_clients = {}                      # sid -> the kiwi_waterfall on it (its display state for ssdr_db2col_line), or None
+        self._tuned = {}                             # tid -> (stream, offset_hz, ChanParams): the tuned receivers (open_tuned), the engine's rows in tid order
+        self._next_tid = 1                           # (the hub owns the ids and never reuses one)
+        self.tuned_queue = {}                        # tid -> bounded queue of Frame
+        self.tuned_clients = {}                      # tid -> the kiwi_sound on it (volume / balance for its play_buffer), or None
         self._want_n = np.ones(self.n_ch, np.int32)  # averaging_n asked for by each channel's waterfall client
         self._want_all = {1: self.n_ch}              # N -> channels that want it (all channels / channels with a client)
         self._want_cli = {}
@@ -453,14 +459,17 @@ class IQHub:
             self._params[int(channel)] = p
             (self._sq_act.add if acts else self._sq_act.discard)(int(channel))
 
-    def sam_carrier(self, channel=None, sub=None):
+    def sam_carrier(self, channel=None, sub=None, tuned=None):
         """-> (offset_hz, phase_rad) of the carrier loop of a channel in synchronous AM (sam / sal / sau) after the last block, or of
-        sub-receiver `sub`: the carrier's offset from the tuned frequency as the loop reads it, and the loop's phase in [-pi, pi).
-        (0.0, 0.0) in any other mode (ssdr_get_sam_carrier)."""
-        if (channel is None) == (sub is None):
-            raise ValueError("sam_carrier takes a channel or a sub-receiver id")
+        sub-receiver `sub`, or of tuned receiver `tuned`: the carrier's offset from the tuned frequency as the loop reads it, and the
+        loop's phase in [-pi, pi).  (0.0, 0.0) in any other mode (ssdr_get_sam_carrier)."""
+        if (channel is not None) + (sub is not None) + (tuned is not None) != 1:
+            raise ValueError("sam_carrier takes a channel, a sub-receiver id or a tuned receiver id")
         with self._lock:
-            if sub is not None:
+            if tuned is not None:
+                row = sorted(self._tuned).index(int(tuned))        # ValueError: no such tuned receiver
+                hz, ph = self.engine.wb_rx_sam_carrier(row, 1)
+            elif sub is not None:
                 row = sorted(self._subs).index(int(sub))           # ValueError: no such sub-receiver
                 hz, ph = self.engine.subrx_sam_carrier(row, 1)
             else:
@@ -671,6 +680,99 @@ class IQHub:
             self._set_subs(new)
             self.sub_queue.pop(sid, None)
             self.sub_clients.pop(sid, None)
+
+    # ---- tuned receivers: demodulators at any frequency of a channeliser's wide stream (ssdr_set_wb_rx)
+    def tuned(self, tid):
+        """-> (stream, offset_hz, ChanParams) of tuned receiver `tid`"""
+        with self._lock:
+            return self._tuned[int(tid)]
+
+    def wide_rate(self):
+        """the wide streams' sample rate under the channeliser that is set"""
+        return self.channelizer.wide_rate(self.kiwi_rate)
+
+    def _require_tuned(self):
+        if self.pipeline or self.wire:
+            raise ValueError("a tuned receiver needs the synchronous sample hub")
+        if getattr(self, "channelizer", None) is None:
+            raise ValueError("a tuned receiver needs a channeliser (set_channelizer)")
+        if not hasattr(self.engine, "set_wb_rx"):
+            raise ValueError("this engine has no tuned receivers (set_wb_rx)")
+
+    def _check_tuned(self, stream, offset_hz, p):
+        if p.mode == L.MODE_IQ:
+            raise ValueError("mod=iq on a tuned receiver: a tuned receiver has no I,Q output")
+        n_streams = self.n_ch // self.channelizer.BRANCHES
+        if not 0 <= stream < n_streams:
+            raise ValueError("wide stream %d of %d" % (stream, n_streams))
+        half = self.wide_rate() / 2.0
+        if not abs(offset_hz) <= half:               # (NaN fails as well)
+            raise ValueError("tuned receiver centre %r Hz is outside the +-%g Hz wide stream" % (offset_hz, half))
+
+    def _set_tuned(self, new):
+        """the whole list to the engine, ids ascending; refused by the library: the old list stays"""
+        try:
+            self.engine.set_wb_rx([(tid,) + new[tid] for tid in sorted(new)])
+        except L.SsdrError as e:
+            raise ValueError("tuned receivers refused: %s" % e)
+        self._tuned = new
+
+    def open_tuned(self, stream, offset_hz, params=None):
+        """A tuned receiver on wide stream `stream`: a DDC at a row's rate centred offset_hz from the stream's centre -- anywhere, not
+        on the channeliser's grid -- and an audio chain with parameters of its own behind it.  -> tid, the hub's name for it (never
+        reused): its frames arrive in tuned_queue[tid] with every feed_wideband, retune_tuned(tid, offset_hz) moves it (the DDC carries
+        nothing: nobody restarts), set_tuned_params(tid, p) changes the demodulator (state kept, like set_params), close_tuned(tid)
+        ends it.  ValueError on a pipelined or wire hub and without a channeliser (before the engine is touched), beyond 64 of them
+        (SSDR_WB_RX_MAX), for mod=iq, an offset outside the wide stream and parameters the library refuses; then nothing changes."""
+        self._require_tuned()
+        p = _copy_params(params if params is not None else self._default_params)
+        row = (int(stream), float(offset_hz), p)
+        self._check_tuned(*row)
+        with self._lock:
+            if len(self._tuned) >= L.WB_RX_MAX:
+                raise ValueError("a hub runs at most %d tuned receivers (SSDR_WB_RX_MAX)" % L.WB_RX_MAX)
+            tid = self._next_tid
+            new = dict(self._tuned)
+            new[tid] = row
+            self._set_tuned(new)
+            self._next_tid += 1
+            self.tuned_queue[tid] = queue.Queue(2 * self._max_queue)
+            self.tuned_clients[tid] = None
+            return tid
+
+    def retune_tuned(self, tid, offset_hz, params=None):
+        """moves tuned receiver `tid`: from the next feed_wideband on its row is centred offset_hz from the stream's centre; with
+        `params` the demodulator changes in the same step (both or neither)"""
+        tid = int(tid)
+        with self._lock:
+            stream, _, p = self._tuned[tid]          # KeyError: no such tuned receiver
+            if params is not None:
+                p = _copy_params(params)
+            self._check_tuned(stream, float(offset_hz), p)
+            new = dict(self._tuned)
+            new[tid] = (stream, float(offset_hz), p)
+            self._set_tuned(new)
+
+    def set_tuned_params(self, tid, p):
+        tid = int(tid)
+        with self._lock:
+            stream, off, _ = self._tuned[tid]        # KeyError: no such tuned receiver
+            q = _copy_params(p)
+            self._check_tuned(stream, off, q)
+            new = dict(self._tuned)
+            new[tid] = (stream, off, q)
+            self._set_tuned(new)                     # raises for parameters the library refuses; the old ones stay
+
+    def close_tuned(self, tid):
+        tid = int(tid)
+        with self._lock:
+            if tid not in self._tuned:
+                return                               # closing twice counts once
+            new = dict(self._tuned)
+            del new[tid]
+            self._set_tuned(new)
+            self.tuned_queue.pop(tid, None)
+            self.tuned_clients.pop(tid, None)
 
     # ---- wideband scopes: zoomable waterfalls of a channeliser's wide stream (the band scope of kiwi_waterfall; ssdr_set_wb_scopes)
     def scope(self, sid):
@@ -1009,6 +1111,9 @@ class IQHub:
             self._scope_det = {}
             self.scope_queue.clear()
             self.scope_clients.clear()
+            self._tuned = {}                         # ... and every tuned receiver
+            self.tuned_queue.clear()
+            self.tuned_clients.clear()
 
     def feed_wideband(self, block):
         """one superframe of every wide stream: int16 [n_streams, superframe samples * 1024 / oversample, 2] -> one GPU run, as if the
@@ -1067,8 +1172,17 @@ class IQHub:
             if self.gpu_post and any(s is not None for s in clients):
                 sub_play = eng.run_subrx_playbuffer([PlayChan(100.0, 0.0) if s is None else PlayChan(float(s.volume), float(s.audio_balance))
                                                      for s in clients])
+        tuned_ids = tuned_pcm = tuned_rssi = tuned_flags = tuned_play = None
+        if wideband and self._tuned:
+            tuned_ids = sorted(self._tuned)
+            tuned_pcm, tuned_rssi, tuned_flags = eng.wb_rx_audio()              # rows in tid order (open_tuned)
+            clients = [self.tuned_clients.get(tid) for tid in tuned_ids]
+            if self.gpu_post and any(s is not None for s in clients):
+                tuned_play = eng.run_wb_rx_playbuffer([PlayChan(100.0, 0.0) if s is None else PlayChan(float(s.volume), float(s.audio_balance))
+                                                       for s in clients])
         self.superframes += 1
-        self._hand_out(SuperframeResult(seq=self.superframes, wf=wf, n_avg=n_avg, color=color, chans=chans, pcm=pcm, rssi=rssi,
+        self._hand_out(SuperframeResult(seq=self.superframes, wf=wf, tuned_ids=tuned_ids, tuned_pcm=tuned_pcm, tuned_rssi=tuned_rssi,
+                                        tuned_flags=tuned_flags, tuned_play=tuned_play, n_avg=n_avg, color=color, chans=chans, pcm=pcm, rssi=rssi,
                                         sub_ids=sub_ids, sub_pcm=sub_pcm, sub_rssi=sub_rssi, sub_flags=sub_flags, sub_play=sub_play,
                                         flags=flags, play=play, mono=mono, iq=iqo, wire_rssi=wire_rssi, post_channels=self._post_sel,
                                         snd_adpcm=snd_adpcm, wf_adpcm=wf_adpcm, snd_adpcm_channels=snd_sel, wf_adpcm_channels=wf_sel,
@@ -1140,6 +1254,14 @@ class IQHub:
                 _put_drop_oldest(q, Frame.make(r.sub_pcm[i, f * L.FRAME:(f + 1) * L.FRAME], r.sub_rssi[i, f],
                                                r.sub_play[i, f * P:(f + 1) * P].copy() if r.sub_play is not None else None, None,
                                                r.sub_flags[i, f]))
+        for i, tid in enumerate(r.tuned_ids or ()):
+            q = self.tuned_queue.get(tid)
+            if q is None:
+                continue
+            for f in range(r.tuned_pcm.shape[1] // L.FRAME):
+                _put_drop_oldest(q, Frame.make(r.tuned_pcm[i, f * L.FRAME:(f + 1) * L.FRAME], r.tuned_rssi[i, f],
+                                               r.tuned_play[i, f * P:(f + 1) * P].copy() if r.tuned_play is not None else None, None,
+                                               r.tuned_flags[i, f]))
 
         for i, sid in enumerate(r.scope_ids or ()):
             q = self.scope_queue.get(sid)
@@ -1345,14 +1467,27 @@ class GpuStream:
     "SET de_emp=" and "SET compression=1" raise ValueError naming the sub-receiver: they are the channel's, not built for
     sub-receivers.
 
+    tuned=tid (an SND stream; IQHub.open_tuned): the stream is that of a TUNED RECEIVER on a wide stream of the hub's channeliser;
+    `channel` is that wide stream and center_khz its centre.  "SET mod= low_cut= high_cut= freq=" puts freq ANYWHERE in the wide stream:
+    the receiver's DDC moves (IQHub.retune_tuned) and f_shift_hz stays 0; a frequency outside the stream raises ValueError naming
+    the stream's span.  "SET agc=" goes to the receiver's parameters.  Its frames come from hub.tuned_queue[tid], close_connection
+    closes the receiver, and nb / squelch / de_emp / compression=1 / mod=iq raise ValueError naming the tuned receiver, as for a
+    sub-receiver.
+
     receive_message(): server -> client frames, byte for byte in the wire format the reference parses
     (utils_supersdr.py:782-784, 1065-1074): first what the constructors wait for ("MSG audio_init audio_rate= sample_rate=",
     then one empty W/F resp. SND frame), after that one frame per GPU result of this channel."""
 
-    def __init__(self, hub, channel, kind, center_khz, timeout=5.0, sub=None, scope=None):
+    def __init__(self, hub, channel, kind, center_khz, timeout=5.0, sub=None, scope=None, tuned=None):
         self.hub, self.channel, self.kind, self.center_khz, self.timeout = hub, int(channel), kind, float(center_khz), timeout
         self.sub = None if sub is None else int(sub)
         self.scope = None if scope is None else int(scope)
+        self.tuned = None if tuned is None else int(tuned)
+        if self.tuned is not None:
+            if kind != "SND" or sub is not None or scope is not None:
+                raise ValueError("a tuned receiver has an SND stream only")
+            if hub.tuned(self.tuned)[0] != self.channel:         # KeyError: no such tuned receiver
+                raise ValueError("tuned receiver %d listens to wide stream %d, not %d" % (self.tuned, hub.tuned(self.tuned)[0], self.channel))
         if self.scope is not None:
             if kind == "SND" or sub is not None:
                 raise ValueError("a wideband scope has a W/F stream only")
@@ -1369,7 +1504,7 @@ class GpuStream:
         self._squelch_on = False                     # ... and its squelch
         self._deemp_on = False                       # ... and its de-emphasis
         self._greeting = deque()
-        if self.sub is None and self.scope is None and hasattr(hub, "attach"):      # this channel has a listener now: its results are queued from here on
+        if self.sub is None and self.scope is None and self.tuned is None and hasattr(hub, "attach"):      # this channel has a listener now: its results are queued from here on
             hub.attach(self.channel, wf=(kind != "SND"), snd=(kind == "SND"))
         if kind != "SND" and self.scope is None and hasattr(hub, "_wf_listener_changed"):
             hub._wf_listener_changed(self.channel, +1)
@@ -1397,6 +1532,14 @@ class GpuStream:
             if "compression" in kv and "mod" not in kv and "agc" not in kv and int(kv["compression"]) != 0:
                 raise ValueError("SET compression=1 on sub-receiver %d of channel %d: a sub-receiver's frames are not ADPCM-encoded"
                                  % (self.sub, self.channel))
+        if self.tuned is not None:
+            for key in ("nb", "squelch", "de_emp"):
+                if key in kv and "mod" not in kv and "agc" not in kv:
+                    raise ValueError("SET %s= on tuned receiver %d of wide stream %d: there is no %s for tuned receivers"
+                                     % (key, self.tuned, self.channel, {"nb": "noise blanker", "squelch": "squelch", "de_emp": "de-emphasis"}[key]))
+            if "compression" in kv and "mod" not in kv and "agc" not in kv and int(kv["compression"]) != 0:
+                raise ValueError("SET compression=1 on tuned receiver %d of wide stream %d: a tuned receiver's frames are not ADPCM-encoded"
+                                 % (self.tuned, self.channel))
         if self.scope is not None and "interp" in kv:
             self.hub.set_scope_detector(self.scope, kiwi_interp_detector(kv["interp"]))
             return
@@ -1408,8 +1551,8 @@ class GpuStream:
                              agc_slope=float(kv.get("slope", 0)), agc_decay=float(kv.get("decay", 4000)),
                              agc_man_gain=float(kv.get("manGain", 50)))
             self._set_params(q)
-        elif self.sub is not None:
-            pass                                     # (compression=0, zoom=, ...: nothing to do for a sub-receiver)
+        elif self.sub is not None or self.tuned is not None:
+            pass                                     # (compression=0, zoom=, ...: nothing to do for a sub-receiver or a tuned receiver)
         elif "nb" in kv:
             if "th" not in kv:
                 raise ValueError("SET nb= without th=: %r" % (msg,))
@@ -1429,10 +1572,14 @@ class GpuStream:
             self.zoom, self.start = int(kv["zoom"]), int(kv.get("start", 0))
 
     def _params(self):
+        if self.tuned is not None:
+            return self.hub.tuned(self.tuned)[2]
         return self.hub.params(self.channel) if self.sub is None else self.hub.sub_params(self.sub)[1]
 
     def _set_params(self, q):
-        if self.sub is None:
+        if self.tuned is not None:
+            self.hub.set_tuned_params(self.tuned, q)
+        elif self.sub is None:
             self.hub.set_params(self.channel, q)
         else:
             self.hub.set_sub_params(self.sub, q)
@@ -1478,6 +1625,18 @@ class GpuStream:
             raise ValueError("radio_mode %r has no demodulator on the GPU path (am, lsb, usb, cw, nbfm, iq, sam, sal, sau)" % (kv["mod"],))
         freq = float(kv.get("freq", self.center_khz))
         f_shift = (freq - self.center_khz) * 1000.0
+        if self.tuned is not None:                   # anywhere in the wide stream: the DDC moves, the audio chain stays on its centre
+            if mode == "iq":
+                raise ValueError("SET mod=iq on tuned receiver %d of wide stream %d: a tuned receiver has no I,Q output" % (self.tuned, self.channel))
+            half = self.hub.wide_rate() / 2.0
+            if not abs(f_shift) <= half:
+                raise ValueError("tuning %.3f kHz is outside wide stream %d: %.3f .. %.3f kHz around %.3f kHz"
+                                 % (freq, self.channel, self.center_khz - half / 1000.0, self.center_khz + half / 1000.0, self.center_khz))
+            p = self._params()
+            q = _copy_params(p, mode=L.MODE_BY_NAME[mode], f_shift_hz=0.0, low_cut=float(kv.get("low_cut", p.low_cut)),
+                             high_cut=float(kv.get("high_cut", p.high_cut)))
+            self.hub.retune_tuned(self.tuned, f_shift, q)        # (refused: nothing moved)
+            return
         rate = float(getattr(self.hub, "kiwi_rate", L.RATE))
         if abs(f_shift) > rate / 2:
             raise ValueError("tuning %.3f kHz is outside the %g kHz IQ band around %.3f kHz that channel %d receives"
@@ -1494,8 +1653,9 @@ class GpuStream:
         if self.closed:
             return None
         try:
-            if self.sub is not None:
-                f = self.hub.sub_queue[self.sub].get(timeout=self.timeout)
+            if self.sub is not None or self.tuned is not None:
+                q = self.hub.sub_queue[self.sub] if self.sub is not None else self.hub.tuned_queue[self.tuned]
+                f = q.get(timeout=self.timeout)
                 return snd_frame(f, f.rssi, self._next_seq(), adc_overflow=f.adc_overflow)
             if self.kind == "SND":
                 f = self.hub.snd_queue[self.channel].get(timeout=self.timeout)
@@ -1524,6 +1684,10 @@ class GpuStream:
             self.hub.close_sub(self.sub)             # the sub-receiver goes with its stream
         if self.scope is not None and not self.closed:
             self.hub.close_scope(self.scope)         # ... and so does the scope
+        if self.tuned is not None and not self.closed:
+            self.hub.close_tuned(self.tuned)         # ... and the tuned receiver
+            self.closed = True
+            return
         if self._comp_on and not self.closed:        # the next connection's decoder starts from (0, 0): so does its encoder
             self._comp_on = False
             self.hub.set_compression(self.channel, **{("snd" if self.kind == "SND" else "wf"): False})
@@ -1792,17 +1956,36 @@ class SoundSeams:
     """In front of the maintainer's kiwi_sound: process_audio_stream, play_buffer and the constructor's socket part.
     sub=True: the object is a SUB-RECEIVER on `channel` (IQHub.open_sub) -- the reference's SUB RX, a second kiwi_sound beside the
     main one (supersdr.py:624-629) -- instead of taking the channel's own demodulator; `sub_id` is the hub's name for it.  The
-    default keeps the channel's own demodulator, whatever subrx_ says (subrx_ goes to the maintainer's constructor either way)."""
+    default keeps the channel's own demodulator, whatever subrx_ says (subrx_ goes to the maintainer's constructor either way).
+    tuned=True, stream=w: the object is a TUNED RECEIVER on wide stream w of the hub's channeliser (IQHub.open_tuned): freq_ may lie
+    anywhere in the wide stream around wide_center_khz (default: kiwi_wf's centre, for a waterfall that looks at the wide stream);
+    `tuned_id` is the hub's name for it."""
     _ref_module = None
 
     def __init__(self, freq_, mode_, lc_, hc_, password_, kiwi_wf, buffer_len, volume_=100, host_=None, port_=None,
-                 subrx_=False, hub=None, channel=None, timeout=5.0, sub=False):
+                 subrx_=False, hub=None, channel=None, timeout=5.0, sub=False, tuned=False, stream=0, wide_center_khz=None):
         self.hub = hub if hub is not None else kiwi_wf.hub
         self.channel = kiwi_wf.channel if channel is None else int(channel)
         self._timeout = timeout
         self.center_khz = float(getattr(kiwi_wf, "iq_center_khz", kiwi_wf.freq))   # the IQ band's centre: tuning is relative to it
         self.error = None                                # set by play_buffer when it has to give up
         self.late_flag = False                           # (the reference creates it in run(); play_buffer reads it)
+        self.sub_id = self.tuned_id = None
+        if tuned:
+            if sub:
+                raise ValueError("a kiwi_sound is a sub-receiver or a tuned receiver, not both")
+            if wide_center_khz is not None:
+                self.center_khz = float(wide_center_khz)
+            self.tuned_id = self.hub.open_tuned(int(stream), 0.0)
+            self._gpu_stream = GpuStream(self.hub, int(stream), "SND", self.center_khz, timeout, tuned=self.tuned_id)
+            try:
+                with _server_is_the_gpu(self._ref_module, self._gpu_stream):
+                    super().__init__(freq_, mode_, lc_, hc_, password_, kiwi_wf, buffer_len, volume_, host_, port_, subrx_)
+            except Exception:
+                self.hub.close_tuned(self.tuned_id)      # a receiver that could not be tuned does not stay behind
+                raise
+            self.hub.tuned_clients[self.tuned_id] = self
+            return
         self.sub_id = self.hub.open_sub(self.channel) if sub else None
         self._gpu_stream = GpuStream(self.hub, self.channel, "SND", self.center_khz, timeout, **({} if self.sub_id is None else {"sub": self.sub_id}))
         if self.sub_id is None and hasattr(self.hub, "snd_clients"):
@@ -1827,8 +2010,11 @@ class SoundSeams:
     # ---- seam: utils_supersdr.py:1044-1076
     def _next_frame(self):
         try:
-            q = self.hub.snd_queue[self.channel] if self.sub_id is None else self.hub.sub_queue.get(self.sub_id)
-            if q is None:                            # the sub-receiver was closed under the worker
+            if self.tuned_id is not None:
+                q = self.hub.tuned_queue.get(self.tuned_id)
+            else:
+                q = self.hub.snd_queue[self.channel] if self.sub_id is None else self.hub.sub_queue.get(self.sub_id)
+            if q is None:                            # the sub-receiver or tuned receiver was closed under the worker
                 raise queue.Empty
             return q.get(timeout=self._timeout)
         except queue.Empty:
