@@ -51,6 +51,13 @@ static int ssdr_caught(bool nomem) noexcept
 // The ctx owns the one of ssdr_push_iq / ssdr_run_* (`own`: what every getter and "the last run" reads; its buffers grow on demand);
 // a slot of the pipelined feed holds one whose buffers are parts of the slot's device block (`borrowed`).  The stages take the batch
 // they work on as a parameter and never ask whose it is.
+// a bank of extra receivers' results in a batch (RxBank below), rows in list order; capacities in rows * frames
+struct BankOut {
+    int16_t *d_pcm = nullptr; size_t pcm_cap = 0;                 // [rows][frames * 512]
+    float *d_rssi = nullptr; size_t rssi_cap = 0;                 // [rows][frames]
+    uint8_t *d_flags = nullptr; size_t flags_cap = 0;             // [rows][frames]
+    uint32_t run_rows = 0, run_frames = 0;                        // extent of the last run
+};
 struct Batch {
     bool borrowed = false;                    // the buffers are somebody else's memory and the capacities final: never freed or grown from here
     const uint32_t *d_iq = nullptr;
@@ -71,19 +78,11 @@ struct Batch {
     uint8_t *d_wf_adpcm = nullptr; size_t wf_adpcm_bytes = 0; bool wf_adpcm_valid = false; uint32_t wf_adpcm_lines = 0;        // [lines][comp_wf_n][517] W/F payloads
     int16_t *d_wv_lines = nullptr; size_t wv_lines_rows = 0;      // [total][1024] the views' lines, compact (their validity: ssdr_ctx::wv_run_valid)
     std::vector<uint32_t> wv_run_lines; uint32_t wv_run_total = 0;        // [views] lines of each view; their total
-    // the sub-receivers' results, rows in list order (their validity: ssdr_ctx::sub_run_valid): buffers, capacities in rows * frames
-    int16_t *d_sub_pcm = nullptr; size_t sub_pcm_cap = 0;         // [rows][frames * 512]
-    float *d_sub_rssi = nullptr; size_t sub_rssi_cap = 0;         // [rows][frames]
-    uint8_t *d_sub_flags = nullptr; size_t sub_flags_cap = 0;     // [rows][frames]
-    uint32_t sub_run_rows = 0, sub_run_frames = 0;                // extent of the last run
-    // the tuned receivers' IQ rows of the last ssdr_push_wideband (their validity: ssdr_ctx::wr_rows_valid) and their results of the
-    // audio run behind it (ssdr_ctx::wr_run_valid), rows in list order
+    // the two banks' results (their validity: ssdr_ctx::sub.run_valid / wr.run_valid); the tuned receivers' are those of the audio run
+    // behind the last ssdr_push_wideband, whose IQ rows stand here too (their validity: ssdr_ctx::wr_rows_valid)
+    BankOut sub, wr;
     uint32_t *d_wr_rows = nullptr; size_t wr_rows_cap = 0;        // [rows][frames * 512 * D] I | Q << 16; capacity in dwords
     uint32_t wr_rows_n = 0, wr_rows_frames = 0;                   // extent of that push
-    int16_t *d_wr_pcm = nullptr; size_t wr_pcm_cap = 0;           // [rows][frames * 512]; capacities in rows * frames
-    float *d_wr_rssi = nullptr; size_t wr_rssi_cap = 0;           // [rows][frames]
-    uint8_t *d_wr_flags = nullptr; size_t wr_flags_cap = 0;       // [rows][frames]
-    uint32_t wr_run_rows = 0, wr_run_frames = 0;                  // extent of the last run
 };
 // What ssdr_run_chain decides for a batch (chain_plan), handed to the two stages
 struct ChainPlan {
@@ -100,6 +99,30 @@ constexpr int kTimedScope = SSDR_K_COUNT + 4;           // the wideband scopes (
 constexpr int kTimedWbRxDdc = SSDR_K_COUNT + 5;         // the tuned receivers' DDC and their audio (ssdr_wb_rx_stats)
 constexpr int kTimedWbRxAudio = SSDR_K_COUNT + 6;
 constexpr int kTimedCount = SSDR_K_COUNT + 7;
+
+// A bank of extra receivers: audio chains that are no channels, rows in list order, run by the sub-receivers' kernels behind the
+// channels' audio stage.  The ctx holds two -- the sub-receivers (ssdr_set_subrx: each reads a channel's row of the input) and the
+// tuned receivers (ssdr_set_wb_rx: row r reads row r of their DDC's output) -- and the bank_* functions below say each step once.
+// The lists as set stay with the ctx (h_sub, h_wr): a bank knows its rows by their constants alone.
+struct RxBank {
+    const uint32_t cap;                                 // rows the arrays hold: SSDR_SUBRX_MAX, SSDR_WB_RX_MAX
+    const int timed;                                    // the kTimed* slot its audio launch is timed in
+    std::vector<ssdr_chan_consts> h_consts;             // [rows] mirror of d_consts: compiled from the list's parameters
+    std::vector<uint8_t> h_started;                     // [rows] the receiver has run since it was created or restarted
+    bool run_valid = false;                             // the last audio run was the ctx's own batch's, with the list as it is
+    int set = 0;                                        // which of the two sets of state arrays is the current one (a new list is built in the other, as wv_set)
+    ssdr_chan_state *d_state[2] = {nullptr, nullptr};   // [cap]
+    uint32_t *d_hist[2] = {nullptr, nullptr};           // [cap][SSDR_HIST]
+    double *d_phist[2] = {nullptr, nullptr};            // [cap][8] play_buffer history (bank_playbuffer)
+    double *d_phist_alt = nullptr;                      // the kernel reads the current set's and writes this one; swapped after every launch
+    ssdr_chan_consts *d_consts = nullptr;               // [cap]
+    float *d_taps = nullptr;                            // [cap][SSDR_NTAP_MAX]
+    uint32_t *d_parent = nullptr;                       // [cap] the row of the input each one reads
+    ssdr_play_chan *d_play = nullptr;                   // [cap]
+    int16_t *d_play_out = nullptr;
+    size_t play_cap = 0;                                // rows * frames d_play_out holds
+    uint32_t rows() const { return (uint32_t)h_consts.size(); }
+};
 
 struct ssdr_ctx {
     int device = 0;
@@ -312,20 +335,7 @@ struct ssdr_ctx {
     size_t wv_wf_rows = 0;
     // sub-receivers (ssdr_set_subrx): device memory at the first one; with none set nothing is launched
     std::vector<ssdr_subrx> h_sub;                      // the list as set, ids ascending
-    std::vector<ssdr_chan_consts> h_sub_consts;         // [rows] mirror of d_sub_consts
-    std::vector<uint8_t> h_sub_started;                 // [rows] the sub-receiver has run since it was created or restarted
-    bool sub_run_valid = false;                         // the last audio run was the ctx's own batch's, with the list as it is
-    int sub_set = 0;                                    // which of the two sets of state arrays is the current one (as wv_set)
-    ssdr_chan_state *d_sub_state[2] = {nullptr, nullptr};       // [SSDR_SUBRX_MAX]
-    uint32_t *d_sub_hist[2] = {nullptr, nullptr};       // [SSDR_SUBRX_MAX][SSDR_HIST]
-    double *d_sub_phist[2] = {nullptr, nullptr};        // [SSDR_SUBRX_MAX][8] play_buffer history (ssdr_run_subrx_playbuffer)
-    double *d_sub_phist_alt = nullptr;                  // the kernel reads the current set's and writes this one; swapped after every launch
-    ssdr_chan_consts *d_sub_consts = nullptr;           // [SSDR_SUBRX_MAX] compiled from the list's parameters
-    float *d_sub_taps = nullptr;                        // [SSDR_SUBRX_MAX][SSDR_NTAP_MAX]
-    uint32_t *d_sub_parent = nullptr;                   // [SSDR_SUBRX_MAX] the row of the input each one reads
-    ssdr_play_chan *d_sub_play = nullptr;               // [SSDR_SUBRX_MAX]
-    int16_t *d_sub_play_out = nullptr;
-    size_t sub_play_cap = 0;                            // rows * frames d_sub_play_out holds
+    RxBank sub{SSDR_SUBRX_MAX, kTimedSubRx};            // their rows: the parents are the list's channels, uploaded with every list
     // wideband channeliser (ssdr_set_channelizer): device memory at the first one set; with none set nothing is launched
     uint32_t chz_streams = 0, chz_over = 1, chz_p = 0;  // streams (0: none set), O, P
     std::vector<float> h_chz_taps;                      // [P * 1024] the prototype as set
@@ -356,24 +366,11 @@ struct ssdr_ctx {
     ssdr_chan_consts *d_ws_consts = nullptr;            // [rows] calibration 0 dB
     size_t ws_rows = 0;                                 // (scope, line) rows d_ws_out / d_ws_lines / d_ws_acc / d_ws_consts hold
     // tuned receivers (ssdr_set_wb_rx): device memory at the first one; with none set nothing is launched.  The rings are the scopes'
-    // (h_ws_streams: the streams EITHER list names), the tap tables too; the audio arrays are the sub-receivers' layout, the receivers' own
+    // (h_ws_streams: the streams EITHER list names), the tap tables too
     std::vector<ssdr_wb_rx> h_wr;                       // the list as set, ids ascending
-    std::vector<ssdr_chan_consts> h_wr_consts;          // [rows] mirror of d_wr_consts
-    std::vector<uint8_t> h_wr_started;                  // [rows] the receiver's audio has run since it was created or restarted
+    RxBank wr{SSDR_WB_RX_MAX, kTimedWbRxAudio};         // their audio rows: the parents are 0, 1, 2, .., written once (wbrx_alloc); run_valid: an audio run on the rows below
     bool wr_rows_valid = false;                         // the own batch's input is an ssdr_push_wideband's with the list as it is
-    bool wr_run_valid = false;                          // ... and there has been an audio run on its rows
-    int wr_set = 0;                                     // which of the two sets of state arrays is the current one (as sub_set)
     SsdrWbScope *d_wr_list = nullptr;                   // [SSDR_WB_RX_MAX] the receivers as the DDC sees them (uploaded with the scopes': ws_dirty)
-    ssdr_chan_state *d_wr_state[2] = {nullptr, nullptr};        // [SSDR_WB_RX_MAX]
-    uint32_t *d_wr_hist[2] = {nullptr, nullptr};        // [SSDR_WB_RX_MAX][SSDR_HIST]
-    double *d_wr_phist[2] = {nullptr, nullptr};         // [SSDR_WB_RX_MAX][8] play_buffer history (ssdr_run_wb_rx_playbuffer)
-    double *d_wr_phist_alt = nullptr;
-    ssdr_chan_consts *d_wr_consts = nullptr;            // [SSDR_WB_RX_MAX]
-    float *d_wr_taps = nullptr;                         // [SSDR_WB_RX_MAX][SSDR_NTAP_MAX]
-    uint32_t *d_wr_parent = nullptr;                    // [SSDR_WB_RX_MAX] 0, 1, 2, ..: receiver r reads row r of the DDC's rows
-    ssdr_play_chan *d_wr_play = nullptr;                // [SSDR_WB_RX_MAX]
-    int16_t *d_wr_play_out = nullptr;
-    size_t wr_play_cap = 0;
 };
 // Every device buffer a ctx owns (a feed slot's block: ssdr_feed_close) -- what ssdr_destroy frees.  One line per section of the
 // struct above, in its order (the own batch's buffers where `own` stands): a new `d_` member joins its section's line HERE, and tests/test_gpu_parity.py's
@@ -399,15 +396,15 @@ static void free_owned(ssdr_ctx *c)
         c->d_de_state, c->d_de_list,                                                                                  // de-emphasis
         c->d_wv[0], c->d_wv[1], c->d_wv_hist[0], c->d_wv_hist[1], c->d_wv_carry[0], c->d_wv_carry[1], c->d_wv_tail[0], c->d_wv_tail[1],
         c->d_wv_taps, c->d_wv_consts, c->d_wv_acc, c->d_wv_stream, c->d_wv_wf,                                        // waterfall views
-        c->own.d_sub_pcm, c->own.d_sub_rssi, c->own.d_sub_flags,                                                      // sub-receivers: the own batch's results,
-        c->d_sub_state[0], c->d_sub_state[1], c->d_sub_hist[0], c->d_sub_hist[1], c->d_sub_phist[0], c->d_sub_phist[1], c->d_sub_phist_alt,
-        c->d_sub_consts, c->d_sub_taps, c->d_sub_parent, c->d_sub_play, c->d_sub_play_out,                            // ... state, constants, play_buffer
+        c->own.sub.d_pcm, c->own.sub.d_rssi, c->own.sub.d_flags,                                                      // sub-receivers: the own batch's results,
+        c->sub.d_state[0], c->sub.d_state[1], c->sub.d_hist[0], c->sub.d_hist[1], c->sub.d_phist[0], c->sub.d_phist[1], c->sub.d_phist_alt,
+        c->sub.d_consts, c->sub.d_taps, c->sub.d_parent, c->sub.d_play, c->sub.d_play_out,                            // ... their bank: state, constants, play_buffer
         c->d_chz_taps, c->d_chz_hist, c->d_chz_in,                                                                    // wideband channeliser
         c->d_ws_taps, c->d_ws_scopes, c->d_ws_slot_stream, c->d_ws_hist, c->d_ws_out, c->d_ws_lines, c->d_ws_acc, c->d_ws_consts,   // wideband scopes
         c->d_wd_win, c->d_wd_part,                                                                                    // ... their detectors' scratch
-        c->own.d_wr_rows, c->own.d_wr_pcm, c->own.d_wr_rssi, c->own.d_wr_flags,                                       // tuned receivers: the own batch's rows and results,
-        c->d_wr_list, c->d_wr_state[0], c->d_wr_state[1], c->d_wr_hist[0], c->d_wr_hist[1], c->d_wr_phist[0], c->d_wr_phist[1], c->d_wr_phist_alt,
-        c->d_wr_consts, c->d_wr_taps, c->d_wr_parent, c->d_wr_play, c->d_wr_play_out,                                 // ... state, constants, play_buffer
+        c->own.d_wr_rows, c->own.wr.d_pcm, c->own.wr.d_rssi, c->own.wr.d_flags,                                       // tuned receivers: the own batch's rows and results,
+        c->d_wr_list, c->wr.d_state[0], c->wr.d_state[1], c->wr.d_hist[0], c->wr.d_hist[1], c->wr.d_phist[0], c->wr.d_phist[1], c->wr.d_phist_alt,
+        c->wr.d_consts, c->wr.d_taps, c->wr.d_parent, c->wr.d_play, c->wr.d_play_out,                                 // ... their bank: state, constants, play_buffer
     };
     for (void *p : owned)
         if (p) (void)hipFree(p);
@@ -606,19 +603,181 @@ static SsdrWfArgs wf_rows_args(const ssdr_ctx *c, const uint32_t *rows, uint64_t
     return w;
 }
 
+// the carrier loop (ssdr_chan_state.pad) of n consecutive state rows to 0, queued on the main stream
+static int sam_loop_zero(ssdr_ctx *c, ssdr_chan_state *d_rows, size_t n)
+{
+    HIP_TRY(hipMemset2DAsync(reinterpret_cast<char *>(d_rows) + offsetof(ssdr_chan_state, pad), sizeof(ssdr_chan_state), 0,
+                             sizeof(((ssdr_chan_state *)nullptr)->pad), n, c->stream));
+    return SSDR_OK;
+}
+
+
+// ---- a bank of extra receivers (RxBank): every step of the sub-receivers' and the tuned receivers' host side, said once ----------------
+// the state arrays (two sets: a new list is built in the other one, so that a receiver that stays keeps its stream), constants, parents
+static int bank_alloc(ssdr_ctx *c, RxBank &bk)
+{
+    const size_t n = bk.cap;
+    for (int i = 0; i < 2; i++) {
+        if (!bk.d_state[i]) HIP_TRY(hipMalloc(&bk.d_state[i], n * sizeof(ssdr_chan_state)));
+        if (!bk.d_hist[i]) HIP_TRY(hipMalloc(&bk.d_hist[i], n * SSDR_HIST * 4));
+        if (!bk.d_phist[i]) HIP_TRY(hipMalloc(&bk.d_phist[i], n * 8 * sizeof(double)));
+    }
+    if (!bk.d_phist_alt) HIP_TRY(hipMalloc(&bk.d_phist_alt, n * 8 * sizeof(double)));
+    if (!bk.d_consts) HIP_TRY(hipMalloc(&bk.d_consts, n * sizeof(ssdr_chan_consts)));
+    if (!bk.d_taps) HIP_TRY(hipMalloc(&bk.d_taps, n * SSDR_NTAP_MAX * sizeof(float)));
+    if (!bk.d_parent) HIP_TRY(hipMalloc(&bk.d_parent, n * sizeof(uint32_t)));
+    if (!bk.d_play) HIP_TRY(hipMalloc(&bk.d_play, n * sizeof(ssdr_play_chan)));
+    return SSDR_OK;
+}
+// row j of set `set` as ssdr_reset_state leaves a channel (queued on the main stream; the caller waits: *fresh is host memory)
+static int bank_silence(ssdr_ctx *c, RxBank &bk, int set, uint32_t j, const ssdr_chan_state *fresh)
+{
+    HIP_TRY(hipMemcpyAsync(bk.d_state[set] + j, fresh, sizeof *fresh, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemsetAsync(bk.d_hist[set] + (size_t)j * SSDR_HIST, 0, SSDR_HIST * 4, c->stream));
+    HIP_TRY(hipMemsetAsync(bk.d_phist[set] + (size_t)j * 8, 0, 8 * sizeof(double), c->stream));
+    return SSDR_OK;
+}
+// no receiver: the list went (the arrays stay for the next one)
+static void bank_clear(RxBank &bk)
+{
+    bk.h_consts.clear();
+    bk.h_started.clear();
+    bk.run_valid = false;
+}
+static bool every_row(uint32_t) { return true; }
+// the rows that `selected(row)` names start over; the stream is waited for only if there was one
+template <class F> static int bank_restart(ssdr_ctx *c, RxBank &bk, F selected)
+{
+    if (!bk.rows()) return SSDR_OK;
+    SSDR_TRY(join_audio(c));
+    std::vector<ssdr_chan_state> fresh(bk.rows());
+    bool any = false;
+    for (uint32_t j = 0; j < bk.rows(); j++) {
+        if (!selected(j)) continue;
+        fresh[j] = fresh_state(bk.h_consts[j]);
+        SSDR_TRY(bank_silence(c, bk, bk.set, j, &fresh[j]));
+        bk.h_started[j] = 0;
+        any = true;
+    }
+    if (any) HIP_TRY(hipStreamSynchronize(c->stream));
+    return SSDR_OK;
+}
+// the sub-receivers of channels [first, first + count) start over (ssdr_reset_state)
+static int subrx_restart(ssdr_ctx *c, uint32_t first, uint32_t count)
+{
+    if (!count) return SSDR_OK;
+    return bank_restart(c, c->sub, [&](uint32_t j) { return c->h_sub[j].channel >= first && c->h_sub[j].channel - first < count; });
+}
+// constants and taps of the whole list to the device, behind what is queued; there when the call returns
+static int bank_upload_consts(ssdr_ctx *c, RxBank &bk, const std::vector<ssdr_chan_consts> &k, const std::vector<float> &taps)
+{
+    if (k.empty()) return SSDR_OK;
+    SSDR_TRY(join_audio(c));
+    HIP_TRY(hipMemcpyAsync(bk.d_consts, k.data(), k.size() * sizeof(ssdr_chan_consts), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(bk.d_taps, taps.data(), taps.size() * sizeof(float), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return SSDR_OK;
+}
+// the list recompiled for a new rate or decimation (subrx_compile / wbrx_compile): every receiver takes its constants and starts over
+static int bank_install(ssdr_ctx *c, RxBank &bk, const std::vector<ssdr_chan_consts> &k, const std::vector<float> &taps)
+{
+    if (!bk.rows()) return SSDR_OK;
+    SSDR_TRY(bank_upload_consts(c, bk, k, taps));
+    bk.h_consts = k;
+    bk.run_valid = false;
+    return bank_restart(c, bk, every_row);
+}
+// room for the results of the run, before anything of it is launched
+static int bank_prepare(ssdr_ctx *c, RxBank &bk, Batch &b, BankOut &out)
+{
+    const size_t n = bk.rows();
+    if (!n) return SSDR_OK;
+    bk.run_valid = false;
+    const size_t need = n * b.in_frames;
+    if (out.pcm_cap < need || out.rssi_cap < need || out.flags_cap < need) SSDR_TRY(drain_audio(c));
+    SSDR_TRY(grow(c, b, out.d_pcm, out.pcm_cap, need, SSDR_FRAME * sizeof(int16_t)));
+    SSDR_TRY(grow(c, b, out.d_rssi, out.rssi_cap, need, sizeof(float)));
+    return grow(c, b, out.d_flags, out.flags_cap, need, 1);
+}
+// Every receiver of the bank advanced by the batch, on the audio stage's stream `s` behind the channels' kernels: one launch, timed
+// with the bank's own event pair; not an SSDR_K_* slot.  `au`: the audio stage's arguments (the extent; rows of the channels' length),
+// `iq`: the rows the parents index.
+static int bank_launch(ssdr_ctx *c, RxBank &bk, Batch &b, BankOut &out, const SsdrAudioArgs &au, const uint32_t *iq, hipStream_t s)
+{
+    const uint32_t n = bk.rows();
+    if (!n) return SSDR_OK;
+    SsdrSubArgs a;
+    a.au = au;
+    a.au.iq = iq;
+    a.au.n_ch = n;
+    a.au.consts = bk.d_consts; a.au.taps = bk.d_taps;
+    a.au.state = bk.d_state[bk.set]; a.au.hist = bk.d_hist[bk.set];
+    a.au.pcm = out.d_pcm; a.au.rssi = out.d_rssi; a.au.flags = out.d_flags;
+    a.au.iq_out = nullptr;
+    a.au.chan_list = nullptr; a.au.list_n = n;
+    a.parent = bk.d_parent;
+    bool any_sam = false;                                  // rows in synchronous AM run the mode's own instantiation beside the others'
+    for (const ssdr_chan_consts &k : bk.h_consts) any_sam = any_sam || k.mode == SSDR_MODE_SAM;
+    SSDR_TRY(stage_launch(c, bk.timed, s, [&]() -> int {
+        HIP_TRY(ssdr_launch_audio_sub(a, c->decim, s));
+        if (any_sam) HIP_TRY(ssdr_launch_audio_sub_sam(a, s));
+        return SSDR_OK;
+    }));
+    std::fill(bk.h_started.begin(), bk.h_started.end(), (uint8_t)1);
+    out.run_rows = n;
+    out.run_frames = b.in_frames;
+    bk.run_valid = &b == &c->own;
+    return SSDR_OK;
+}
+// A new list of `count` rows, compiled to (k, taps), takes the bank over.  It is built in the other set of state arrays: a receiver
+// that stays -- same(old row, new row): the family's notion of "the same receiver", ids ascending in both lists -- is copied there
+// with all it carries, device to device behind whatever run is queued, and starts its carrier loop at zero if it changes into
+// synchronous AM; a new one, or one kept but not run yet, starts at ITS knee as after ssdr_reset_state.  Nobody's stream waits for
+// anybody else's.  `parent`: the parent table to upload behind the rows, or null (it stands).  Returns when the device has it all;
+// *same_rows: every row is the receiver it was -- unless so, the last run's results are no longer the list's (the caller's marks).
+template <class T, class Same>
+static int bank_rebuild(ssdr_ctx *c, RxBank &bk, const std::vector<T> &old, const T *list, uint32_t count, const std::vector<ssdr_chan_consts> &k,
+                        const std::vector<float> &taps, const uint32_t *parent, Same same, bool *same_rows)
+{
+    const int from = bk.set, to = from ^ 1;
+    std::vector<ssdr_chan_state> fresh(count);
+    std::vector<uint8_t> started(count, 0);
+    *same_rows = old.size() == count;
+    size_t i = 0;
+    for (uint32_t j = 0; j < count; j++) {
+        while (i < old.size() && old[i].id < list[j].id) i++;
+        const bool stays = i < old.size() && old[i].id == list[j].id && same(old[i], list[j]);
+        *same_rows = *same_rows && stays && i == j;
+        if (stays && bk.h_started[i]) {
+            const hipMemcpyKind d2d = hipMemcpyDeviceToDevice;
+            HIP_TRY(hipMemcpyAsync(bk.d_state[to] + j, bk.d_state[from] + i, sizeof(ssdr_chan_state), d2d, c->stream));
+            HIP_TRY(hipMemcpyAsync(bk.d_hist[to] + (size_t)j * SSDR_HIST, bk.d_hist[from] + i * SSDR_HIST, SSDR_HIST * 4, d2d, c->stream));
+            HIP_TRY(hipMemcpyAsync(bk.d_phist[to] + (size_t)j * 8, bk.d_phist[from] + i * 8, 8 * sizeof(double), d2d, c->stream));
+            if (k[j].mode == SSDR_MODE_SAM && bk.h_consts[i].mode != SSDR_MODE_SAM) SSDR_TRY(sam_loop_zero(c, bk.d_state[to] + j, 1));
+            started[j] = 1;
+        } else {
+            fresh[j] = fresh_state(k[j]);
+            SSDR_TRY(bank_silence(c, bk, to, j, &fresh[j]));
+        }
+    }
+    if (parent) HIP_TRY(hipMemcpyAsync(bk.d_parent, parent, count * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
+    SSDR_TRY(bank_upload_consts(c, bk, k, taps));           // (waits: `fresh` and `parent` are host memory)
+    bk.h_consts = k;
+    bk.h_started = started;
+    bk.set = to;
+    return SSDR_OK;
+}
+
 // what the entry points below call across the sections of this file, further down
 static int zoom_restart(ssdr_ctx *c, uint32_t first, uint32_t count, bool restart_group = true);
 static int nb_upload(ssdr_ctx *c, uint32_t first, uint32_t count);
 static int squelch_upload(ssdr_ctx *c, uint32_t first, uint32_t count);
 static int deemp_reset(ssdr_ctx *c, uint32_t first, uint32_t count);
 static int wfview_restart(ssdr_ctx *c, uint32_t first, uint32_t count);
-static int subrx_restart(ssdr_ctx *c, uint32_t first, uint32_t count);
 static int subrx_compile(const ssdr_ctx *c, const ssdr_subrx *subs, uint32_t count, uint32_t decim, uint32_t rate,
                          std::vector<ssdr_chan_consts> &k, std::vector<float> &taps);
-static int subrx_install(ssdr_ctx *c, const std::vector<ssdr_chan_consts> &k, const std::vector<float> &taps);
 static int wbrx_compile(const ssdr_ctx *c, const ssdr_wb_rx *list, uint32_t count, uint32_t decim, uint32_t rate,
                         std::vector<ssdr_chan_consts> &k, std::vector<float> &taps);
-static int wbrx_install(ssdr_ctx *c, const std::vector<ssdr_chan_consts> &k, const std::vector<float> &taps);
 
 // ssdr_set_decimation / ssdr_set_kiwi_rate, once their own checks have passed: the IQ arrives at decim * kiwi_rate from now on.
 // Every channel's constants (NCO steps, filter, AGC time constants, NBFM scale) are compiled for that rate, and streams of the old
@@ -643,8 +802,11 @@ static int change_input_rate(ssdr_ctx *c, uint32_t decim, uint32_t kiwi_rate)
         c->own.have_input = false;                                // a batch pushed at the old rate has the wrong extent
         rc = ssdr_reset_state(c, 0, c->n_ch);                     // phases and histories of the old rate mean nothing now
         if (rc == SSDR_OK) rc = zoom_restart(c, 0, c->n_ch);
-        if (rc == SSDR_OK) rc = subrx_install(c, sub_k, sub_taps);
-        if (rc == SSDR_OK) rc = wbrx_install(c, wr_k, wr_taps);
+        if (rc == SSDR_OK) rc = bank_install(c, c->sub, sub_k, sub_taps);
+        if (rc == SSDR_OK) {
+            c->wr_rows_valid = false;                             // (the DDC's rows are the old rate's; its NCO steps the new one's: ws_dirty above)
+            rc = bank_install(c, c->wr, wr_k, wr_taps);
+        }
     }
     if (rc != SSDR_OK) {                                          // all or nothing: back to the old rate, streams restarted
         c->decim = keep_decim;
@@ -752,14 +914,6 @@ int ssdr_table(int which, float *out, uint32_t n) SSDR_GUARD
     default: return SSDR_EINVAL;
     }
 } SSDR_UNGUARD
-
-// the carrier loop (ssdr_chan_state.pad) of n consecutive state rows to 0, queued on the main stream
-static int sam_loop_zero(ssdr_ctx *c, ssdr_chan_state *d_rows, size_t n)
-{
-    HIP_TRY(hipMemset2DAsync(reinterpret_cast<char *>(d_rows) + offsetof(ssdr_chan_state, pad), sizeof(ssdr_chan_state), 0,
-                             sizeof(((ssdr_chan_state *)nullptr)->pad), n, c->stream));
-    return SSDR_OK;
-}
 
 int ssdr_reset_state(ssdr_ctx *c, uint32_t first, uint32_t count) SSDR_GUARD
 {
@@ -1725,107 +1879,6 @@ static int subrx_compile(const ssdr_ctx *c, const ssdr_subrx *subs, uint32_t cou
     }
     return SSDR_OK;
 }
-// the state arrays (two sets: a new list is built in the other one, so that a sub-receiver that stays keeps its stream), constants, parents
-static int subrx_alloc(ssdr_ctx *c)
-{
-    for (int i = 0; i < 2; i++) {
-        if (!c->d_sub_state[i]) HIP_TRY(hipMalloc(&c->d_sub_state[i], SSDR_SUBRX_MAX * sizeof(ssdr_chan_state)));
-        if (!c->d_sub_hist[i]) HIP_TRY(hipMalloc(&c->d_sub_hist[i], (size_t)SSDR_SUBRX_MAX * SSDR_HIST * 4));
-        if (!c->d_sub_phist[i]) HIP_TRY(hipMalloc(&c->d_sub_phist[i], (size_t)SSDR_SUBRX_MAX * 8 * sizeof(double)));
-    }
-    if (!c->d_sub_phist_alt) HIP_TRY(hipMalloc(&c->d_sub_phist_alt, (size_t)SSDR_SUBRX_MAX * 8 * sizeof(double)));
-    if (!c->d_sub_consts) HIP_TRY(hipMalloc(&c->d_sub_consts, SSDR_SUBRX_MAX * sizeof(ssdr_chan_consts)));
-    if (!c->d_sub_taps) HIP_TRY(hipMalloc(&c->d_sub_taps, (size_t)SSDR_SUBRX_MAX * SSDR_NTAP_MAX * sizeof(float)));
-    if (!c->d_sub_parent) HIP_TRY(hipMalloc(&c->d_sub_parent, SSDR_SUBRX_MAX * sizeof(uint32_t)));
-    if (!c->d_sub_play) HIP_TRY(hipMalloc(&c->d_sub_play, SSDR_SUBRX_MAX * sizeof(ssdr_play_chan)));
-    return SSDR_OK;
-}
-// row j of set `set` as ssdr_reset_state leaves a channel (queued on the main stream; the caller waits: *fresh is host memory)
-static int subrx_silence(ssdr_ctx *c, int set, uint32_t j, const ssdr_chan_state *fresh)
-{
-    HIP_TRY(hipMemcpyAsync(c->d_sub_state[set] + j, fresh, sizeof *fresh, hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(hipMemsetAsync(c->d_sub_hist[set] + (size_t)j * SSDR_HIST, 0, SSDR_HIST * 4, c->stream));
-    HIP_TRY(hipMemsetAsync(c->d_sub_phist[set] + (size_t)j * 8, 0, 8 * sizeof(double), c->stream));
-    return SSDR_OK;
-}
-// the sub-receivers of channels [first, first + count) start over
-static int subrx_restart(ssdr_ctx *c, uint32_t first, uint32_t count)
-{
-    if (c->h_sub.empty() || !count) return SSDR_OK;
-    SSDR_TRY(join_audio(c));
-    std::vector<ssdr_chan_state> fresh(c->h_sub.size());
-    bool any = false;
-    for (size_t j = 0; j < c->h_sub.size(); j++) {
-        const uint32_t ch = c->h_sub[j].channel;
-        if (ch < first || ch - first >= count) continue;
-        fresh[j] = fresh_state(c->h_sub_consts[j]);
-        SSDR_TRY(subrx_silence(c, c->sub_set, (uint32_t)j, &fresh[j]));
-        c->h_sub_started[j] = 0;
-        any = true;
-    }
-    if (any) HIP_TRY(hipStreamSynchronize(c->stream));
-    return SSDR_OK;
-}
-// constants and taps of the whole list to the device, behind what is queued; there when the call returns
-static int subrx_upload_consts(ssdr_ctx *c, const std::vector<ssdr_chan_consts> &k, const std::vector<float> &taps)
-{
-    if (k.empty()) return SSDR_OK;
-    SSDR_TRY(join_audio(c));
-    HIP_TRY(hipMemcpyAsync(c->d_sub_consts, k.data(), k.size() * sizeof(ssdr_chan_consts), hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(hipMemcpyAsync(c->d_sub_taps, taps.data(), taps.size() * sizeof(float), hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    return SSDR_OK;
-}
-// the list recompiled for a new rate or decimation (subrx_compile): every sub-receiver takes its constants and starts over
-static int subrx_install(ssdr_ctx *c, const std::vector<ssdr_chan_consts> &k, const std::vector<float> &taps)
-{
-    if (c->h_sub.empty()) return SSDR_OK;
-    SSDR_TRY(subrx_upload_consts(c, k, taps));
-    c->h_sub_consts = k;
-    c->sub_run_valid = false;
-    return subrx_restart(c, 0, c->n_ch);
-}
-// room for the results of the run, before anything of it is launched
-static int subrx_prepare(ssdr_ctx *c, Batch &b)
-{
-    const size_t n = c->h_sub.size();
-    if (!n) return SSDR_OK;
-    c->sub_run_valid = false;
-    const size_t need = n * b.in_frames;
-    if (b.sub_pcm_cap < need || b.sub_rssi_cap < need || b.sub_flags_cap < need) SSDR_TRY(drain_audio(c));
-    SSDR_TRY(grow(c, b, b.d_sub_pcm, b.sub_pcm_cap, need, SSDR_FRAME * sizeof(int16_t)));
-    SSDR_TRY(grow(c, b, b.d_sub_rssi, b.sub_rssi_cap, need, sizeof(float)));
-    return grow(c, b, b.d_sub_flags, b.sub_flags_cap, need, 1);
-}
-// Every sub-receiver advanced by the batch, on the audio stage's stream `s` behind the channels' kernels: one launch.  Timed with its
-// own event pair; not an SSDR_K_* slot.  `au`: the audio stage's arguments (the input and its extent).
-static int subrx_launch(ssdr_ctx *c, Batch &b, const SsdrAudioArgs &au, hipStream_t s)
-{
-    const uint32_t n = (uint32_t)c->h_sub.size();
-    if (!n) return SSDR_OK;
-    SsdrSubArgs a;
-    a.au = au;
-    a.au.n_ch = n;
-    a.au.consts = c->d_sub_consts; a.au.taps = c->d_sub_taps;
-    a.au.state = c->d_sub_state[c->sub_set]; a.au.hist = c->d_sub_hist[c->sub_set];
-    a.au.pcm = b.d_sub_pcm; a.au.rssi = b.d_sub_rssi; a.au.flags = b.d_sub_flags;
-    a.au.iq_out = nullptr;
-    a.au.chan_list = nullptr; a.au.list_n = n;
-    a.parent = c->d_sub_parent;
-    bool any_sam = false;                                  // rows in synchronous AM run the mode's own instantiation beside the others'
-    for (const ssdr_chan_consts &k : c->h_sub_consts) any_sam = any_sam || k.mode == SSDR_MODE_SAM;
-    SSDR_TRY(stage_launch(c, kTimedSubRx, s, [&]() -> int {
-        HIP_TRY(ssdr_launch_audio_sub(a, c->decim, s));
-        if (any_sam) HIP_TRY(ssdr_launch_audio_sub_sam(a, s));
-        return SSDR_OK;
-    }));
-    std::fill(c->h_sub_started.begin(), c->h_sub_started.end(), (uint8_t)1);
-    b.sub_run_rows = n;
-    b.sub_run_frames = b.in_frames;
-    c->sub_run_valid = &b == &c->own;
-    return SSDR_OK;
-}
-
 // the stream the audio stage runs on under a plan; and, once all the call puts there is queued, the mark that later work on the
 // main stream (next input, playbuffer) follows
 static int wbrx_prepare(ssdr_ctx *c, Batch &b);
@@ -1851,7 +1904,7 @@ static int audio_stage(ssdr_ctx *c, Batch &b, ChainPlan plan, const SsdrWfArgs *
         SSDR_TRY(grow(c, c->d_nb_mask, c->nb_mask_bytes, nb_mask_need, 1));
     }
     SSDR_TRY(audio_tail_prepare(c, b));
-    SSDR_TRY(subrx_prepare(c, b));
+    SSDR_TRY(bank_prepare(c, c->sub, b, b.sub));
     SSDR_TRY(wbrx_prepare(c, b));
     SsdrAudioArgs a;
     a.iq = b.d_iq;
@@ -1915,7 +1968,7 @@ static int audio_stage(ssdr_ctx *c, Batch &b, ChainPlan plan, const SsdrWfArgs *
         if (fa.wf.tail)          // hop 512: only now may the carried half-line (the kernel's line 0 read it) become this batch's last one
             HIP_TRY(hipMemcpy2DAsync(c->d_wf_tail, (SSDR_NFFT / 2) * 4, fa.wf.iq + (size_t)(fa.wf.n_lines - 1) * SSDR_FRAME,
                                      fa.wf.ch_stride * 4, (SSDR_NFFT / 2) * 4, c->n_ch, hipMemcpyDeviceToDevice, s));
-        SSDR_TRY(subrx_launch(c, b, a, s));        // behind the one-read kernel: the sub-receivers, the tuned receivers, the tail, and then the W/F encoder
+        SSDR_TRY(bank_launch(c, c->sub, b, b.sub, a, a.iq, s));        // behind the one-read kernel: the sub-receivers, the tuned receivers, the tail, and then the W/F encoder
         SSDR_TRY(wbrx_launch(c, b, a, s));
         SSDR_TRY(audio_tail_launch(c, b, s));
         return adpcm_wf_launch(c, b, s, fa.wf.n_avg);
@@ -1976,7 +2029,7 @@ static int audio_stage(ssdr_ctx *c, Batch &b, ChainPlan plan, const SsdrWfArgs *
             c->nb_mask_gen = c->nb_gen;
         }
     }
-    SSDR_TRY(subrx_launch(c, b, a, s));
+    SSDR_TRY(bank_launch(c, c->sub, b, b.sub, a, a.iq, s));
     SSDR_TRY(wbrx_launch(c, b, a, s));
     return audio_tail_launch(c, b, s);
 }
@@ -3551,6 +3604,73 @@ int ssdr_wf_view_stats(ssdr_ctx *c, float *total_ms, uint32_t *launches, int res
     return stage_stats(c, kTimedWfView, total_ms, launches, reset);
 } SSDR_UNGUARD
 
+// ---- the banks' read-backs: the bodies of the two families' five getters (the steps and the list change: bank_* in front of the entry points)
+// results of the last audio run -> pcm / rssi / flags (each may be null)
+static int bank_audio(ssdr_ctx *c, const RxBank &bk, const BankOut &out, int16_t *pcm, float *rssi, uint8_t *flags, int out_is_device)
+{
+    if (!bk.rows() || !bk.run_valid) return SSDR_ESTATE;
+    HIP_TRY(hipSetDevice(c->device));
+    SSDR_TRY(join_audio(c));
+    const size_t n = (size_t)out.run_rows * out.run_frames;
+    if (pcm) SSDR_TRY(copy_out(c, pcm, out.d_pcm, n * SSDR_FRAME * sizeof(int16_t), out_is_device, kSyncLater));
+    if (rssi) SSDR_TRY(copy_out(c, rssi, out.d_rssi, n * sizeof(float), out_is_device, kSyncLater));
+    if (flags) SSDR_TRY(copy_out(c, flags, out.d_flags, n, out_is_device, kSyncLater));
+    if (!out_is_device) HIP_TRY(hipStreamSynchronize(c->stream));
+    return SSDR_OK;
+}
+static bool bank_has_rows(const RxBank &bk, uint32_t first_row, uint32_t count) { return (uint64_t)first_row + count <= bk.rows(); }
+// rows [first_row, first_row + count) as ssdr_get_state / ssdr_get_sam_carrier / ssdr_get_consts read the channels
+static int bank_state(ssdr_ctx *c, const RxBank &bk, uint32_t first_row, uint32_t count, ssdr_chan_state *state, int16_t *hist)
+{
+    if (!bank_has_rows(bk, first_row, count)) return SSDR_EINVAL;
+    if (!count) return SSDR_OK;
+    HIP_TRY(hipSetDevice(c->device));
+    SSDR_TRY(join_audio(c));
+    if (state) SSDR_TRY(copy_out(c, state, bk.d_state[bk.set] + first_row, count * sizeof(ssdr_chan_state), 0, kSyncLater));
+    if (hist) SSDR_TRY(copy_out(c, hist, bk.d_hist[bk.set] + (size_t)first_row * SSDR_HIST, (size_t)count * SSDR_HIST * 4, 0, kSyncLater));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return SSDR_OK;
+}
+static int bank_sam_carrier(ssdr_ctx *c, const RxBank &bk, uint32_t first_row, uint32_t count, float *offset_hz, float *phase_rad)
+{
+    if (!offset_hz || !bank_has_rows(bk, first_row, count)) return SSDR_EINVAL;
+    if (!count) return SSDR_OK;
+    return sam_carrier_read(c, bk.d_state[bk.set] + first_row, bk.h_consts.data() + first_row, count, offset_hz, phase_rad);
+}
+static int bank_consts(ssdr_ctx *c, const RxBank &bk, uint32_t first_row, uint32_t count, ssdr_chan_consts *consts, float *taps)
+{
+    if (!bank_has_rows(bk, first_row, count)) return SSDR_EINVAL;
+    if (!count) return SSDR_OK;
+    HIP_TRY(hipSetDevice(c->device));
+    SSDR_TRY(join_audio(c));
+    if (consts) SSDR_TRY(copy_out(c, consts, bk.d_consts + first_row, count * sizeof(ssdr_chan_consts), 0, kSyncLater));
+    if (taps) SSDR_TRY(copy_out(c, taps, bk.d_taps + (size_t)first_row * SSDR_NTAP_MAX, (size_t)count * SSDR_NTAP_MAX * 4, 0, kSyncLater));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return SSDR_OK;
+}
+// play_buffer on the last run's frames, the receivers as the channels of a small ctx: the history is the bank's, the tap tables the ctx's
+static int bank_playbuffer(ssdr_ctx *c, RxBank &bk, const BankOut &res, const ssdr_play_chan *chans, int16_t *out, int out_is_device)
+{
+    if (!chans) return SSDR_EINVAL;
+    if (!bk.rows() || !bk.run_valid) return SSDR_ESTATE;
+    HIP_TRY(hipSetDevice(c->device));
+    SSDR_TRY(join_audio(c));
+    const uint32_t n = res.run_rows, nf = res.run_frames;
+    const bool wide = c->kiwi_rate != SSDR_RATE;
+    const size_t per_frame = wide ? (size_t)SSDR_RS_OUT_PER_FRAME : 2048;
+    SSDR_TRY(ensure_play(c));
+    SSDR_TRY(grow(c, bk.d_play_out, bk.play_cap, (size_t)n * nf, (size_t)2048 * 2 * sizeof(int16_t)));
+    HIP_TRY(hipMemcpyAsync(bk.d_play, chans, (size_t)n * sizeof(ssdr_play_chan), hipMemcpyHostToDevice, c->stream));
+    SsdrPlayArgs a;
+    a.pcm = res.d_pcm; a.n_ch = n; a.n_frames = nf; a.chans = bk.d_play; a.taps = c->d_play_taps; a.rs_taps = c->d_play_rs_taps;
+    a.hist = bk.d_phist[bk.set]; a.hist_out = bk.d_phist_alt; a.sel = nullptr; a.n_sel = n; a.out = bk.d_play_out; a.mono = nullptr;
+    HIP_TRY(wide ? ssdr_launch_play_rs(a, c->stream) : ssdr_launch_play(a, c->stream));
+    if (!wide) std::swap(bk.d_phist[bk.set], bk.d_phist_alt);                       // (the 64/27 branch carries no history)
+    if (out) SSDR_TRY(copy_out(c, out, bk.d_play_out, (size_t)n * nf * per_frame * 2 * sizeof(int16_t), out_is_device, kSyncLater));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return SSDR_OK;
+}
+
 int ssdr_set_subrx(ssdr_ctx *c, const ssdr_subrx *subs, uint32_t count) SSDR_GUARD
 {
     if (!c || count > SSDR_SUBRX_MAX || (count && !subs)) return SSDR_EINVAL;
@@ -3558,48 +3678,21 @@ int ssdr_set_subrx(ssdr_ctx *c, const ssdr_subrx *subs, uint32_t count) SSDR_GUA
     std::vector<float> taps;
     SSDR_TRY(subrx_compile(c, subs, count, c->decim, c->kiwi_rate, k, taps));
     if (count && !c->feed.empty()) return SSDR_ESTATE;
-    if (!count) {                                           // (the state arrays stay for the next list)
+    if (!count) {                                           // (the device is not touched)
         c->h_sub.clear();
-        c->h_sub_consts.clear();
-        c->h_sub_started.clear();
-        c->sub_run_valid = false;
+        bank_clear(c->sub);
         return SSDR_OK;
     }
     HIP_TRY(hipSetDevice(c->device));
-    SSDR_TRY(subrx_alloc(c));
+    SSDR_TRY(bank_alloc(c, c->sub));
     SSDR_TRY(join_audio(c));                                // what is queued beside the main stream reads the current set and the constants
-    // the new list is built in the other set of state arrays: a sub-receiver that stays is copied there with all it carries, device
-    // to device behind whatever run is queued; a new one starts as after ssdr_reset_state.  Nobody's stream waits for anybody else's.
-    const int from = c->sub_set, to = from ^ 1;
-    std::vector<ssdr_chan_state> fresh(count);
-    std::vector<uint8_t> started(count, 0);
     std::vector<uint32_t> parent(count);
-    bool same_rows = c->h_sub.size() == count;
-    size_t i = 0;
-    for (uint32_t j = 0; j < count; j++) {
-        parent[j] = subs[j].channel;
-        while (i < c->h_sub.size() && c->h_sub[i].id < subs[j].id) i++;
-        const bool stays = i < c->h_sub.size() && c->h_sub[i].id == subs[j].id && c->h_sub[i].channel == subs[j].channel;
-        same_rows = same_rows && stays && i == j;
-        if (stays && c->h_sub_started[i]) {
-            const hipMemcpyKind d2d = hipMemcpyDeviceToDevice;
-            HIP_TRY(hipMemcpyAsync(c->d_sub_state[to] + j, c->d_sub_state[from] + i, sizeof(ssdr_chan_state), d2d, c->stream));
-            HIP_TRY(hipMemcpyAsync(c->d_sub_hist[to] + (size_t)j * SSDR_HIST, c->d_sub_hist[from] + i * SSDR_HIST, SSDR_HIST * 4, d2d, c->stream));
-            HIP_TRY(hipMemcpyAsync(c->d_sub_phist[to] + (size_t)j * 8, c->d_sub_phist[from] + i * 8, 8 * sizeof(double), d2d, c->stream));
-            if (k[j].mode == SSDR_MODE_SAM && c->h_sub_consts[i].mode != SSDR_MODE_SAM) SSDR_TRY(sam_loop_zero(c, c->d_sub_state[to] + j, 1));
-            started[j] = 1;
-        } else {                                            // new, or kept but not run yet: it starts at ITS knee (ssdr_set_params)
-            fresh[j] = fresh_state(k[j]);
-            SSDR_TRY(subrx_silence(c, to, j, &fresh[j]));
-        }
-    }
-    HIP_TRY(hipMemcpyAsync(c->d_sub_parent, parent.data(), count * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
-    SSDR_TRY(subrx_upload_consts(c, k, taps));              // (waits: `fresh` and `parent` are host memory)
+    for (uint32_t j = 0; j < count; j++) parent[j] = subs[j].channel;
+    bool same_rows;
+    SSDR_TRY(bank_rebuild(c, c->sub, c->h_sub, subs, count, k, taps, parent.data(),
+                          [](const ssdr_subrx &a, const ssdr_subrx &b) { return a.channel == b.channel; }, &same_rows));
     c->h_sub.assign(subs, subs + count);
-    c->h_sub_consts = k;
-    c->h_sub_started = started;
-    c->sub_set = to;
-    if (!same_rows) c->sub_run_valid = false;               // (new parameters of the same rows leave the last run's results what they were)
+    if (!same_rows) c->sub.run_valid = false;               // (new parameters of the same rows leave the last run's results what they were)
     return SSDR_OK;
 } SSDR_UNGUARD
 
@@ -3610,71 +3703,27 @@ int ssdr_get_subrx(ssdr_ctx *c, ssdr_subrx *subs, uint32_t *count) SSDR_GUARD
 
 int ssdr_subrx_audio(ssdr_ctx *c, int16_t *pcm, float *rssi, uint8_t *flags, int out_is_device) SSDR_GUARD
 {
-    if (!c) return SSDR_EINVAL;
-    if (c->h_sub.empty() || !c->sub_run_valid) return SSDR_ESTATE;
-    HIP_TRY(hipSetDevice(c->device));
-    SSDR_TRY(join_audio(c));
-    const Batch &b = c->own;
-    const size_t n = (size_t)b.sub_run_rows * b.sub_run_frames;
-    if (pcm) SSDR_TRY(copy_out(c, pcm, b.d_sub_pcm, n * SSDR_FRAME * sizeof(int16_t), out_is_device, kSyncLater));
-    if (rssi) SSDR_TRY(copy_out(c, rssi, b.d_sub_rssi, n * sizeof(float), out_is_device, kSyncLater));
-    if (flags) SSDR_TRY(copy_out(c, flags, b.d_sub_flags, n, out_is_device, kSyncLater));
-    if (!out_is_device) HIP_TRY(hipStreamSynchronize(c->stream));
-    return SSDR_OK;
+    return c ? bank_audio(c, c->sub, c->own.sub, pcm, rssi, flags, out_is_device) : SSDR_EINVAL;
 } SSDR_UNGUARD
 
 int ssdr_get_subrx_state(ssdr_ctx *c, uint32_t first_row, uint32_t count, ssdr_chan_state *state, int16_t *hist) SSDR_GUARD
 {
-    if (!c || (uint64_t)first_row + count > c->h_sub.size()) return SSDR_EINVAL;
-    if (!count) return SSDR_OK;
-    HIP_TRY(hipSetDevice(c->device));
-    SSDR_TRY(join_audio(c));
-    const int set = c->sub_set;
-    if (state) SSDR_TRY(copy_out(c, state, c->d_sub_state[set] + first_row, count * sizeof(ssdr_chan_state), 0, kSyncLater));
-    if (hist) SSDR_TRY(copy_out(c, hist, c->d_sub_hist[set] + (size_t)first_row * SSDR_HIST, (size_t)count * SSDR_HIST * 4, 0, kSyncLater));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    return SSDR_OK;
+    return c ? bank_state(c, c->sub, first_row, count, state, hist) : SSDR_EINVAL;
 } SSDR_UNGUARD
 
 int ssdr_get_subrx_sam_carrier(ssdr_ctx *c, uint32_t first_row, uint32_t count, float *offset_hz, float *phase_rad) SSDR_GUARD
 {
-    if (!c || !offset_hz || (uint64_t)first_row + count > c->h_sub.size()) return SSDR_EINVAL;
-    if (!count) return SSDR_OK;
-    return sam_carrier_read(c, c->d_sub_state[c->sub_set] + first_row, c->h_sub_consts.data() + first_row, count, offset_hz, phase_rad);
+    return c ? bank_sam_carrier(c, c->sub, first_row, count, offset_hz, phase_rad) : SSDR_EINVAL;
 } SSDR_UNGUARD
 
 int ssdr_get_subrx_consts(ssdr_ctx *c, uint32_t first_row, uint32_t count, ssdr_chan_consts *consts, float *taps) SSDR_GUARD
 {
-    if (!c || (uint64_t)first_row + count > c->h_sub.size()) return SSDR_EINVAL;
-    if (!count) return SSDR_OK;
-    HIP_TRY(hipSetDevice(c->device));
-    SSDR_TRY(join_audio(c));
-    if (consts) SSDR_TRY(copy_out(c, consts, c->d_sub_consts + first_row, count * sizeof(ssdr_chan_consts), 0, kSyncLater));
-    if (taps) SSDR_TRY(copy_out(c, taps, c->d_sub_taps + (size_t)first_row * SSDR_NTAP_MAX, (size_t)count * SSDR_NTAP_MAX * 4, 0, kSyncLater));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    return SSDR_OK;
+    return c ? bank_consts(c, c->sub, first_row, count, consts, taps) : SSDR_EINVAL;
 } SSDR_UNGUARD
 
 int ssdr_run_subrx_playbuffer(ssdr_ctx *c, const ssdr_play_chan *chans, int16_t *out, int out_is_device) SSDR_GUARD
 {
-    if (!c || !chans) return SSDR_EINVAL;
-    if (c->h_sub.empty() || !c->sub_run_valid) return SSDR_ESTATE;
-    HIP_TRY(hipSetDevice(c->device));
-    SSDR_TRY(join_audio(c));
-    const uint32_t n = c->own.sub_run_rows, nf = c->own.sub_run_frames;
-    const bool wide = c->kiwi_rate != SSDR_RATE;
-    const size_t per_frame = wide ? (size_t)SSDR_RS_OUT_PER_FRAME : 2048;
-    SSDR_TRY(ensure_play(c));                                 // (the tap tables are the ctx's)
-    SSDR_TRY(grow(c, c->d_sub_play_out, c->sub_play_cap, (size_t)n * nf, (size_t)2048 * 2 * sizeof(int16_t)));
-    HIP_TRY(hipMemcpyAsync(c->d_sub_play, chans, (size_t)n * sizeof(ssdr_play_chan), hipMemcpyHostToDevice, c->stream));
-    SsdrPlayArgs a;                                           // the sub-receivers as the channels of a small ctx
-    a.pcm = c->own.d_sub_pcm; a.n_ch = n; a.n_frames = nf; a.chans = c->d_sub_play; a.taps = c->d_play_taps; a.rs_taps = c->d_play_rs_taps;
-    a.hist = c->d_sub_phist[c->sub_set]; a.hist_out = c->d_sub_phist_alt; a.sel = nullptr; a.n_sel = n; a.out = c->d_sub_play_out; a.mono = nullptr;
-    HIP_TRY(wide ? ssdr_launch_play_rs(a, c->stream) : ssdr_launch_play(a, c->stream));
-    if (!wide) std::swap(c->d_sub_phist[c->sub_set], c->d_sub_phist_alt);          // (the 64/27 branch carries no history)
-    if (out) SSDR_TRY(copy_out(c, out, c->d_sub_play_out, (size_t)n * nf * per_frame * 2 * sizeof(int16_t), out_is_device, kSyncLater));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    return SSDR_OK;
+    return c ? bank_playbuffer(c, c->sub, c->own.sub, chans, out, out_is_device) : SSDR_EINVAL;
 } SSDR_UNGUARD
 
 int ssdr_subrx_stats(ssdr_ctx *c, float *total_ms, uint32_t *launches, int reset) SSDR_GUARD
@@ -3893,68 +3942,19 @@ static int wbrx_compile(const ssdr_ctx *c, const ssdr_wb_rx *list, uint32_t coun
     }
     return SSDR_OK;
 }
+// the bank's arrays with the identity parent table (receiver r reads row r of the DDC's rows: written once), the DDC's list and tables
 static int wbrx_alloc(ssdr_ctx *c)
 {
-    for (int i = 0; i < 2; i++) {
-        if (!c->d_wr_state[i]) HIP_TRY(hipMalloc(&c->d_wr_state[i], SSDR_WB_RX_MAX * sizeof(ssdr_chan_state)));
-        if (!c->d_wr_hist[i]) HIP_TRY(hipMalloc(&c->d_wr_hist[i], (size_t)SSDR_WB_RX_MAX * SSDR_HIST * 4));
-        if (!c->d_wr_phist[i]) HIP_TRY(hipMalloc(&c->d_wr_phist[i], (size_t)SSDR_WB_RX_MAX * 8 * sizeof(double)));
-    }
-    if (!c->d_wr_phist_alt) HIP_TRY(hipMalloc(&c->d_wr_phist_alt, (size_t)SSDR_WB_RX_MAX * 8 * sizeof(double)));
-    if (!c->d_wr_consts) HIP_TRY(hipMalloc(&c->d_wr_consts, SSDR_WB_RX_MAX * sizeof(ssdr_chan_consts)));
-    if (!c->d_wr_taps) HIP_TRY(hipMalloc(&c->d_wr_taps, (size_t)SSDR_WB_RX_MAX * SSDR_NTAP_MAX * sizeof(float)));
-    if (!c->d_wr_play) HIP_TRY(hipMalloc(&c->d_wr_play, SSDR_WB_RX_MAX * sizeof(ssdr_play_chan)));
-    if (!c->d_wr_list) HIP_TRY(hipMalloc(&c->d_wr_list, SSDR_WB_RX_MAX * sizeof(SsdrWbScope)));
-    if (!c->d_wr_parent) {                                  // receiver r reads row r of the DDC's rows: written once
+    const bool first = !c->wr.d_parent;
+    SSDR_TRY(bank_alloc(c, c->wr));
+    if (first) {
         uint32_t ident[SSDR_WB_RX_MAX];
         for (uint32_t j = 0; j < SSDR_WB_RX_MAX; j++) ident[j] = j;
-        HIP_TRY(hipMalloc(&c->d_wr_parent, sizeof ident));
-        HIP_TRY(hipMemcpy(c->d_wr_parent, ident, sizeof ident, hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(c->wr.d_parent, ident, sizeof ident, hipMemcpyHostToDevice));
     }
+    if (!c->d_wr_list) HIP_TRY(hipMalloc(&c->d_wr_list, SSDR_WB_RX_MAX * sizeof(SsdrWbScope)));
     if (!c->d_ws_scopes) HIP_TRY(hipMalloc(&c->d_ws_scopes, SSDR_WB_SCOPES_MAX * sizeof(SsdrWbScope)));
     return ws_taps(c);
-}
-// row j of set `set` as ssdr_reset_state leaves a channel (queued on the main stream; the caller waits: *fresh is host memory)
-static int wbrx_silence(ssdr_ctx *c, int set, uint32_t j, const ssdr_chan_state *fresh)
-{
-    HIP_TRY(hipMemcpyAsync(c->d_wr_state[set] + j, fresh, sizeof *fresh, hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(hipMemsetAsync(c->d_wr_hist[set] + (size_t)j * SSDR_HIST, 0, SSDR_HIST * 4, c->stream));
-    HIP_TRY(hipMemsetAsync(c->d_wr_phist[set] + (size_t)j * 8, 0, 8 * sizeof(double), c->stream));
-    return SSDR_OK;
-}
-// every receiver's audio starts over (ssdr_channelizer_reset, a new rate or decimation)
-static int wbrx_restart(ssdr_ctx *c)
-{
-    if (c->h_wr.empty()) return SSDR_OK;
-    SSDR_TRY(join_audio(c));
-    std::vector<ssdr_chan_state> fresh(c->h_wr.size());
-    for (size_t j = 0; j < c->h_wr.size(); j++) {
-        fresh[j] = fresh_state(c->h_wr_consts[j]);
-        SSDR_TRY(wbrx_silence(c, c->wr_set, (uint32_t)j, &fresh[j]));
-        c->h_wr_started[j] = 0;
-    }
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    return SSDR_OK;
-}
-static int wbrx_upload_consts(ssdr_ctx *c, const std::vector<ssdr_chan_consts> &k, const std::vector<float> &taps)
-{
-    if (k.empty()) return SSDR_OK;
-    SSDR_TRY(join_audio(c));
-    HIP_TRY(hipMemcpyAsync(c->d_wr_consts, k.data(), k.size() * sizeof(ssdr_chan_consts), hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(hipMemcpyAsync(c->d_wr_taps, taps.data(), taps.size() * sizeof(float), hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    return SSDR_OK;
-}
-// the list recompiled for a new rate or decimation (wbrx_compile): every receiver takes its constants and starts over; the NCO
-// steps are the new wide rate's (ws_dirty: change_input_rate)
-static int wbrx_install(ssdr_ctx *c, const std::vector<ssdr_chan_consts> &k, const std::vector<float> &taps)
-{
-    if (c->h_wr.empty()) return SSDR_OK;
-    SSDR_TRY(wbrx_upload_consts(c, k, taps));
-    c->h_wr_consts = k;
-    c->wr_rows_valid = false;
-    c->wr_run_valid = false;
-    return wbrx_restart(c);
 }
 // The receivers' DDC of one ssdr_push_wideband, on the main stream behind the filter bank and in front of the scopes' stage, whose
 // last launch rewrites the rings (with no scope set that launch is made here): `in` the call's wide samples, n0 the output index
@@ -3965,7 +3965,7 @@ static int wbrx_ddc_stage(ssdr_ctx *c, const uint32_t *in, uint64_t in_stride, u
     if (!nr) return SSDR_OK;
     Batch &b = c->own;
     c->wr_rows_valid = false;
-    c->wr_run_valid = false;
+    c->wr.run_valid = false;
     SSDR_TRY(ws_upload(c));
     SSDR_TRY(grow(c, b.d_wr_rows, b.wr_rows_cap, (size_t)nr * n_out, 4));
     const uint32_t step = SSDR_CHAN_BRANCHES / c->chz_over;            // R = 2^zoom
@@ -3990,56 +3990,24 @@ static int wbrx_ddc_stage(ssdr_ctx *c, const uint32_t *in, uint64_t in_stride, u
     b.wr_rows_frames = n_frames;
     return SSDR_OK;
 }
-// room for the results of the audio run, before anything of it is launched
+// The tuned receivers' part of an audio run acts on the ctx's own batch alone (the DDC's rows are its): room for the results ...
 static int wbrx_prepare(ssdr_ctx *c, Batch &b)
 {
-    const size_t n = c->h_wr.size();
-    if (!n || &b != &c->own) return SSDR_OK;
-    c->wr_run_valid = false;
-    const size_t need = n * b.in_frames;
-    if (b.wr_pcm_cap < need || b.wr_rssi_cap < need || b.wr_flags_cap < need) SSDR_TRY(drain_audio(c));
-    SSDR_TRY(grow(c, b, b.d_wr_pcm, b.wr_pcm_cap, need, SSDR_FRAME * sizeof(int16_t)));
-    SSDR_TRY(grow(c, b, b.d_wr_rssi, b.wr_rssi_cap, need, sizeof(float)));
-    return grow(c, b, b.d_wr_flags, b.wr_flags_cap, need, 1);
+    return &b == &c->own ? bank_prepare(c, c->wr, b, b.wr) : SSDR_OK;
 }
-// Every tuned receiver advanced by the batch, on the audio stage's stream `s` behind the sub-receivers: the sub-receivers' kernels on
-// the receivers' own arrays, reading the DDC's rows (row r for receiver r).  Nothing is launched unless the batch's input is an
-// ssdr_push_wideband's with the list as it is: rows of an older list are nobody's.  `au`: the audio stage's arguments.
+// ... and every receiver advanced, behind the sub-receivers, on the DDC's rows.  Nothing is launched unless the batch's input is an
+// ssdr_push_wideband's with the list as it is: rows of an older list are nobody's.
 static int wbrx_launch(ssdr_ctx *c, Batch &b, const SsdrAudioArgs &au, hipStream_t s)
 {
-    const uint32_t n = (uint32_t)c->h_wr.size();
-    if (!n || &b != &c->own || !c->wr_rows_valid || b.wr_rows_n != n || b.wr_rows_frames != b.in_frames) return SSDR_OK;
-    SsdrSubArgs a;
-    a.au = au;
-    a.au.iq = b.d_wr_rows;                                 // (ch_stride is the channels': rows of the same length)
-    a.au.n_ch = n;
-    a.au.consts = c->d_wr_consts; a.au.taps = c->d_wr_taps;
-    a.au.state = c->d_wr_state[c->wr_set]; a.au.hist = c->d_wr_hist[c->wr_set];
-    a.au.pcm = b.d_wr_pcm; a.au.rssi = b.d_wr_rssi; a.au.flags = b.d_wr_flags;
-    a.au.iq_out = nullptr;
-    a.au.chan_list = nullptr; a.au.list_n = n;
-    a.parent = c->d_wr_parent;
-    bool any_sam = false;
-    for (const ssdr_chan_consts &k : c->h_wr_consts) any_sam = any_sam || k.mode == SSDR_MODE_SAM;
-    SSDR_TRY(stage_launch(c, kTimedWbRxAudio, s, [&]() -> int {
-        HIP_TRY(ssdr_launch_audio_sub(a, c->decim, s));
-        if (any_sam) HIP_TRY(ssdr_launch_audio_sub_sam(a, s));
-        return SSDR_OK;
-    }));
-    std::fill(c->h_wr_started.begin(), c->h_wr_started.end(), (uint8_t)1);
-    b.wr_run_rows = n;
-    b.wr_run_frames = b.in_frames;
-    c->wr_run_valid = true;
-    return SSDR_OK;
+    if (&b != &c->own || !c->wr_rows_valid || b.wr_rows_n != c->wr.rows() || b.wr_rows_frames != b.in_frames) return SSDR_OK;
+    return bank_launch(c, c->wr, b, b.wr, au, b.d_wr_rows, s);
 }
 // no tuned receiver: the list goes (ssdr_set_wb_rx with none, ssdr_set_channelizer); the rings follow the scopes alone
 static int wbrx_clear(ssdr_ctx *c)
 {
     c->h_wr.clear();
-    c->h_wr_consts.clear();
-    c->h_wr_started.clear();
+    bank_clear(c->wr);
     c->wr_rows_valid = false;
-    c->wr_run_valid = false;
     return ws_set_rings(c, ws_streams_of(c->h_ws.data(), c->h_ws.size(), nullptr, 0));
 }
 
@@ -4100,7 +4068,7 @@ int ssdr_channelizer_reset(ssdr_ctx *c) SSDR_GUARD
     if (c->d_ws_hist) HIP_TRY(hipMemsetAsync(c->d_ws_hist, 0, c->h_ws_streams.size() * SSDR_WB_SCOPE_HIST * 4, c->stream));   // the scopes' list stays
     c->ws_win_valid = false;
     c->chz_out_index = 0;
-    return wbrx_restart(c);                                             // the tuned receivers' list stays too; their audio starts over
+    return bank_restart(c, c->wr, every_row);                           // the tuned receivers' list stays too; their audio starts over
 } SSDR_UNGUARD
 
 int ssdr_get_channelizer_state(ssdr_ctx *c, int16_t *hist, uint64_t *out_index) SSDR_GUARD
@@ -4278,36 +4246,12 @@ int ssdr_set_wb_rx(ssdr_ctx *c, const ssdr_wb_rx *list, uint32_t count) SSDR_GUA
     SSDR_TRY(wbrx_alloc(c));
     SSDR_TRY(join_audio(c));                                // what is queued beside the main stream reads the current set and the constants
     SSDR_TRY(ws_set_rings(c, ws_streams_of(c->h_ws.data(), c->h_ws.size(), list, count)));
-    // the audio state as ssdr_set_subrx keeps it: the new list is built in the other set of arrays, a receiver that stays is copied
-    // there with all it carries, a new one starts as after ssdr_reset_state.  The DDC has nothing to keep.
-    const int from = c->wr_set, to = from ^ 1;
-    std::vector<ssdr_chan_state> fresh(count);
-    std::vector<uint8_t> started(count, 0);
-    bool same_rows = c->h_wr.size() == count;
-    size_t i = 0;
-    for (uint32_t j = 0; j < count; j++) {
-        while (i < c->h_wr.size() && c->h_wr[i].id < list[j].id) i++;
-        const bool stays = i < c->h_wr.size() && c->h_wr[i].id == list[j].id && c->h_wr[i].stream == list[j].stream;
-        same_rows = same_rows && stays && i == j;
-        if (stays && c->h_wr_started[i]) {
-            const hipMemcpyKind d2d = hipMemcpyDeviceToDevice;
-            HIP_TRY(hipMemcpyAsync(c->d_wr_state[to] + j, c->d_wr_state[from] + i, sizeof(ssdr_chan_state), d2d, c->stream));
-            HIP_TRY(hipMemcpyAsync(c->d_wr_hist[to] + (size_t)j * SSDR_HIST, c->d_wr_hist[from] + i * SSDR_HIST, SSDR_HIST * 4, d2d, c->stream));
-            HIP_TRY(hipMemcpyAsync(c->d_wr_phist[to] + (size_t)j * 8, c->d_wr_phist[from] + i * 8, 8 * sizeof(double), d2d, c->stream));
-            if (k[j].mode == SSDR_MODE_SAM && c->h_wr_consts[i].mode != SSDR_MODE_SAM) SSDR_TRY(sam_loop_zero(c, c->d_wr_state[to] + j, 1));
-            started[j] = 1;
-        } else {                                            // new, or kept but not run yet: it starts at ITS knee (ssdr_set_params)
-            fresh[j] = fresh_state(k[j]);
-            SSDR_TRY(wbrx_silence(c, to, j, &fresh[j]));
-        }
-    }
-    SSDR_TRY(wbrx_upload_consts(c, k, taps));               // (waits: `fresh` is host memory)
+    bool same_rows;                                         // (the DDC has nothing to keep; the parents stand)
+    SSDR_TRY(bank_rebuild(c, c->wr, c->h_wr, list, count, k, taps, nullptr,
+                          [](const ssdr_wb_rx &a, const ssdr_wb_rx &b) { return a.stream == b.stream; }, &same_rows));
     c->h_wr.assign(list, list + count);
-    c->h_wr_consts = k;
-    c->h_wr_started = started;
-    c->wr_set = to;
     c->ws_dirty = true;                                     // the offsets act from the next push on
-    if (!same_rows) { c->wr_rows_valid = false; c->wr_run_valid = false; }
+    if (!same_rows) { c->wr_rows_valid = false; c->wr.run_valid = false; }
     return SSDR_OK;
 } SSDR_UNGUARD
 
@@ -4318,17 +4262,7 @@ int ssdr_get_wb_rx(ssdr_ctx *c, ssdr_wb_rx *list, uint32_t *count) SSDR_GUARD
 
 int ssdr_wb_rx_audio(ssdr_ctx *c, int16_t *pcm, float *rssi, uint8_t *flags, int out_is_device) SSDR_GUARD
 {
-    if (!c) return SSDR_EINVAL;
-    if (c->h_wr.empty() || !c->wr_run_valid) return SSDR_ESTATE;
-    HIP_TRY(hipSetDevice(c->device));
-    SSDR_TRY(join_audio(c));
-    const Batch &b = c->own;
-    const size_t n = (size_t)b.wr_run_rows * b.wr_run_frames;
-    if (pcm) SSDR_TRY(copy_out(c, pcm, b.d_wr_pcm, n * SSDR_FRAME * sizeof(int16_t), out_is_device, kSyncLater));
-    if (rssi) SSDR_TRY(copy_out(c, rssi, b.d_wr_rssi, n * sizeof(float), out_is_device, kSyncLater));
-    if (flags) SSDR_TRY(copy_out(c, flags, b.d_wr_flags, n, out_is_device, kSyncLater));
-    if (!out_is_device) HIP_TRY(hipStreamSynchronize(c->stream));
-    return SSDR_OK;
+    return c ? bank_audio(c, c->wr, c->own.wr, pcm, rssi, flags, out_is_device) : SSDR_EINVAL;
 } SSDR_UNGUARD
 
 int ssdr_read_wb_rx(ssdr_ctx *c, uint32_t first_row, uint32_t count, int16_t *iq_out) SSDR_GUARD
@@ -4344,56 +4278,22 @@ int ssdr_read_wb_rx(ssdr_ctx *c, uint32_t first_row, uint32_t count, int16_t *iq
 
 int ssdr_get_wb_rx_state(ssdr_ctx *c, uint32_t first_row, uint32_t count, ssdr_chan_state *state, int16_t *hist) SSDR_GUARD
 {
-    if (!c || (uint64_t)first_row + count > c->h_wr.size()) return SSDR_EINVAL;
-    if (!count) return SSDR_OK;
-    HIP_TRY(hipSetDevice(c->device));
-    SSDR_TRY(join_audio(c));
-    const int set = c->wr_set;
-    if (state) SSDR_TRY(copy_out(c, state, c->d_wr_state[set] + first_row, count * sizeof(ssdr_chan_state), 0, kSyncLater));
-    if (hist) SSDR_TRY(copy_out(c, hist, c->d_wr_hist[set] + (size_t)first_row * SSDR_HIST, (size_t)count * SSDR_HIST * 4, 0, kSyncLater));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    return SSDR_OK;
+    return c ? bank_state(c, c->wr, first_row, count, state, hist) : SSDR_EINVAL;
 } SSDR_UNGUARD
 
 int ssdr_get_wb_rx_sam_carrier(ssdr_ctx *c, uint32_t first_row, uint32_t count, float *offset_hz, float *phase_rad) SSDR_GUARD
 {
-    if (!c || !offset_hz || (uint64_t)first_row + count > c->h_wr.size()) return SSDR_EINVAL;
-    if (!count) return SSDR_OK;
-    return sam_carrier_read(c, c->d_wr_state[c->wr_set] + first_row, c->h_wr_consts.data() + first_row, count, offset_hz, phase_rad);
+    return c ? bank_sam_carrier(c, c->wr, first_row, count, offset_hz, phase_rad) : SSDR_EINVAL;
 } SSDR_UNGUARD
 
 int ssdr_get_wb_rx_consts(ssdr_ctx *c, uint32_t first_row, uint32_t count, ssdr_chan_consts *consts, float *taps) SSDR_GUARD
 {
-    if (!c || (uint64_t)first_row + count > c->h_wr.size()) return SSDR_EINVAL;
-    if (!count) return SSDR_OK;
-    HIP_TRY(hipSetDevice(c->device));
-    SSDR_TRY(join_audio(c));
-    if (consts) SSDR_TRY(copy_out(c, consts, c->d_wr_consts + first_row, count * sizeof(ssdr_chan_consts), 0, kSyncLater));
-    if (taps) SSDR_TRY(copy_out(c, taps, c->d_wr_taps + (size_t)first_row * SSDR_NTAP_MAX, (size_t)count * SSDR_NTAP_MAX * 4, 0, kSyncLater));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    return SSDR_OK;
+    return c ? bank_consts(c, c->wr, first_row, count, consts, taps) : SSDR_EINVAL;
 } SSDR_UNGUARD
 
 int ssdr_run_wb_rx_playbuffer(ssdr_ctx *c, const ssdr_play_chan *chans, int16_t *out, int out_is_device) SSDR_GUARD
 {
-    if (!c || !chans) return SSDR_EINVAL;
-    if (c->h_wr.empty() || !c->wr_run_valid) return SSDR_ESTATE;
-    HIP_TRY(hipSetDevice(c->device));
-    SSDR_TRY(join_audio(c));
-    const uint32_t n = c->own.wr_run_rows, nf = c->own.wr_run_frames;
-    const bool wide = c->kiwi_rate != SSDR_RATE;
-    const size_t per_frame = wide ? (size_t)SSDR_RS_OUT_PER_FRAME : 2048;
-    SSDR_TRY(ensure_play(c));                                 // (the tap tables are the ctx's)
-    SSDR_TRY(grow(c, c->d_wr_play_out, c->wr_play_cap, (size_t)n * nf, (size_t)2048 * 2 * sizeof(int16_t)));
-    HIP_TRY(hipMemcpyAsync(c->d_wr_play, chans, (size_t)n * sizeof(ssdr_play_chan), hipMemcpyHostToDevice, c->stream));
-    SsdrPlayArgs a;                                           // the receivers as the channels of a small ctx
-    a.pcm = c->own.d_wr_pcm; a.n_ch = n; a.n_frames = nf; a.chans = c->d_wr_play; a.taps = c->d_play_taps; a.rs_taps = c->d_play_rs_taps;
-    a.hist = c->d_wr_phist[c->wr_set]; a.hist_out = c->d_wr_phist_alt; a.sel = nullptr; a.n_sel = n; a.out = c->d_wr_play_out; a.mono = nullptr;
-    HIP_TRY(wide ? ssdr_launch_play_rs(a, c->stream) : ssdr_launch_play(a, c->stream));
-    if (!wide) std::swap(c->d_wr_phist[c->wr_set], c->d_wr_phist_alt);             // (the 64/27 branch carries no history)
-    if (out) SSDR_TRY(copy_out(c, out, c->d_wr_play_out, (size_t)n * nf * per_frame * 2 * sizeof(int16_t), out_is_device, kSyncLater));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    return SSDR_OK;
+    return c ? bank_playbuffer(c, c->wr, c->own.wr, chans, out, out_is_device) : SSDR_EINVAL;
 } SSDR_UNGUARD
 
 int ssdr_wb_rx_stats(ssdr_ctx *c, float *ddc_ms, float *audio_ms, uint32_t *launches, int reset) SSDR_GUARD

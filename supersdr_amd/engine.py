@@ -454,6 +454,65 @@ class SsdrEngine:
         """-> (total_ms, runs) of the view stage since the last reset (the time only with set_profiling on)"""
         return self._stage_stats("ssdr_wf_view_stats", reset)
 
+    # ---- the two banks of extra receivers, sub-receivers and tuned receivers (csrc/ssdr_api.cpp: RxBank): what they share, by
+    # (the entry points' infix, the list's struct, its capacity, the noun of the messages)
+    _SUBRX = ("subrx", L.SubRx, L.SUBRX_MAX, "sub-receivers")
+    _WB_RX = ("wb_rx", L.WbRx, L.WB_RX_MAX, "tuned receivers")
+
+    def _bank_set(self, bank, rows):
+        name, struct = "ssdr_set_" + bank[0], bank[1]
+        arr = (struct * max(len(rows), 1))(*[struct(*r) for r in rows])
+        check(getattr(lib, name)(self._ctx, arr if rows else None, len(rows)), name)
+
+    def _bank_get(self, bank):
+        name, struct = "ssdr_get_" + bank[0], bank[1]
+        n = C.c_uint32(0)
+        arr = (struct * bank[2])()
+        check(getattr(lib, name)(self._ctx, arr, C.byref(n)), name)
+        out = []
+        for v in arr[:n.value]:
+            p = ChanParams()
+            C.memmove(C.byref(p), C.byref(v.params), C.sizeof(ChanParams))
+            out.append(tuple(getattr(v, f[0]) for f in struct._fields_[:-1]) + (p,))       # (the parameters are the last field)
+        return out
+
+    def _bank_count(self, bank):
+        name = "ssdr_get_" + bank[0]
+        n = C.c_uint32(0)
+        check(getattr(lib, name)(self._ctx, None, C.byref(n)), name)
+        return n.value
+
+    def _bank_audio(self, bank):
+        name = "ssdr_%s_audio" % bank[0]
+        n, nf = self._bank_count(bank), self.audio_frames
+        pcm = np.empty((n, nf * L.FRAME), np.int16)
+        rssi = np.empty((n, nf), np.float32)
+        flags = np.empty((n, nf), np.uint8)
+        check(getattr(lib, name)(self._ctx, pcm.ctypes.data, rssi.ctypes.data, flags.ctypes.data, 0), name)
+        return pcm, rssi, flags
+
+    def _bank_read(self, bank, what, first, count, *arrays):
+        """rows [first, first + count) through ssdr_get_<bank>_<what> -> one array per (shape of a row, dtype) of `arrays`"""
+        name = "ssdr_get_%s_%s" % (bank[0], what)
+        count = self._bank_count(bank) - first if count is None else int(count)
+        out = tuple(np.zeros((count,) + shape, dtype) for shape, dtype in arrays)
+        check(getattr(lib, name)(self._ctx, int(first), count, *[a.ctypes.data for a in out]), name)
+        return out
+
+    def _bank_playbuffer(self, bank, chans):
+        name = "run_%s_playbuffer" % bank[0]
+        n = self._bank_count(bank)
+        arr = chans if isinstance(chans, C.Array) else (PlayChan * max(n, 1))(*chans)
+        if len(arr) < n:
+            raise ValueError("%s: %d settings for %d %s" % (name, len(arr), n, bank[3]))
+        out = np.empty((n, self.audio_frames * self.playbuffer_frame_len(), 2), np.int16)
+        check(getattr(lib, "ssdr_" + name)(self._ctx, arr, out.ctypes.data, 0), "ssdr_" + name)
+        return out
+
+    _STATE_ROWS = (((), STATE_DTYPE), ((L.HIST, 2), np.int16))
+    _CARRIER_ROWS = (((), np.float32), ((), np.float32))
+    _CONSTS_ROWS = (((), CONSTS_DTYPE), ((L.NTAP_MAX,), np.float32))
+
     def set_subrx(self, subs):
         """The sub-receivers, replacing the whole list: a sequence of (id, channel, ChanParams), ids ascending and unique, at most 256;
         an empty sequence removes them all.  A sub-receiver whose (id, channel) was in the old list keeps its stream and takes the new
@@ -463,69 +522,33 @@ class SsdrEngine:
         rows = [(int(i), int(ch), p) for i, ch, p in subs]
         if any(not 0 <= i < 2 ** 32 or not 0 <= ch < 2 ** 32 or not isinstance(p, ChanParams) for i, ch, p in rows):
             raise ValueError("sub-receivers %r: out of range" % (subs,))
-        arr = (L.SubRx * max(len(rows), 1))(*[L.SubRx(*r) for r in rows])
-        check(lib.ssdr_set_subrx(self._ctx, arr if rows else None, len(rows)), "ssdr_set_subrx")
+        self._bank_set(self._SUBRX, rows)
 
     def get_subrx(self):
         """-> [(id, channel, ChanParams), ...] the sub-receivers as set"""
-        n = C.c_uint32(0)
-        arr = (L.SubRx * L.SUBRX_MAX)()
-        check(lib.ssdr_get_subrx(self._ctx, arr, C.byref(n)), "ssdr_get_subrx")
-        out = []
-        for v in arr[:n.value]:
-            p = ChanParams()
-            C.memmove(C.byref(p), C.byref(v.params), C.sizeof(ChanParams))
-            out.append((v.id, v.channel, p))
-        return out
-
-    def _subrx_count(self):
-        n = C.c_uint32(0)
-        check(lib.ssdr_get_subrx(self._ctx, None, C.byref(n)), "ssdr_get_subrx")
-        return n.value
+        return self._bank_get(self._SUBRX)
 
     def subrx_audio(self):
         """-> (pcm int16 [n_sub, n_frames*512], rssi float32 [n_sub, n_frames], flags uint8 [n_sub, n_frames]) of the last run_audio /
         run_chain, rows in list order"""
-        n, nf = self._subrx_count(), self.audio_frames
-        pcm = np.empty((n, nf * L.FRAME), np.int16)
-        rssi = np.empty((n, nf), np.float32)
-        flags = np.empty((n, nf), np.uint8)
-        check(lib.ssdr_subrx_audio(self._ctx, pcm.ctypes.data, rssi.ctypes.data, flags.ctypes.data, 0), "ssdr_subrx_audio")
-        return pcm, rssi, flags
+        return self._bank_audio(self._SUBRX)
 
     def subrx_state(self, first=0, count=None):
         """-> (state, hist) of rows [first, first + count) of the list, as get_state"""
-        count = self._subrx_count() - first if count is None else int(count)
-        st = np.empty(count, STATE_DTYPE)
-        hist = np.empty((count, L.HIST, 2), np.int16)
-        check(lib.ssdr_get_subrx_state(self._ctx, int(first), count, st.ctypes.data, hist.ctypes.data), "ssdr_get_subrx_state")
-        return st, hist
+        return self._bank_read(self._SUBRX, "state", first, count, *self._STATE_ROWS)
 
     def subrx_sam_carrier(self, first=0, count=None):
         """-> (offset_hz, phase_rad) float32 arrays of rows [first, first + count) of the list, as sam_carrier"""
-        count = self._subrx_count() - first if count is None else int(count)
-        hz, ph = np.zeros(count, np.float32), np.zeros(count, np.float32)
-        check(lib.ssdr_get_subrx_sam_carrier(self._ctx, int(first), count, hz.ctypes.data, ph.ctypes.data), "ssdr_get_subrx_sam_carrier")
-        return hz, ph
+        return self._bank_read(self._SUBRX, "sam_carrier", first, count, *self._CARRIER_ROWS)
 
     def subrx_consts(self, first=0, count=None):
         """-> (consts, taps) of rows [first, first + count) of the list, as get_consts"""
-        count = self._subrx_count() - first if count is None else int(count)
-        k = np.empty(count, CONSTS_DTYPE)
-        taps = np.empty((count, L.NTAP_MAX), np.float32)
-        check(lib.ssdr_get_subrx_consts(self._ctx, int(first), count, k.ctypes.data, taps.ctypes.data), "ssdr_get_subrx_consts")
-        return k, taps
+        return self._bank_read(self._SUBRX, "consts", first, count, *self._CONSTS_ROWS)
 
     def run_subrx_playbuffer(self, chans):
         """play_buffer for the sub-receivers' frames of the last run -> int16 [n_sub, n_frames*L, 2], L = playbuffer_frame_len().
         chans: list of PlayChan, one per sub-receiver in list order, or a ctypes array."""
-        n = self._subrx_count()
-        arr = chans if isinstance(chans, C.Array) else (PlayChan * max(n, 1))(*chans)
-        if len(arr) < n:
-            raise ValueError("run_subrx_playbuffer: %d settings for %d sub-receivers" % (len(arr), n))
-        out = np.empty((n, self.audio_frames * self.playbuffer_frame_len(), 2), np.int16)
-        check(lib.ssdr_run_subrx_playbuffer(self._ctx, arr, out.ctypes.data, 0), "ssdr_run_subrx_playbuffer")
-        return out
+        return self._bank_playbuffer(self._SUBRX, chans)
 
     def subrx_stats(self, reset=False):
         """-> (total_ms, runs) of the sub-receiver stage since the last reset (the time only with set_profiling on)"""
@@ -677,29 +700,15 @@ class SsdrEngine:
         rows = [(int(i), int(w), float(off), p) for i, w, off, p in receivers]
         if any(not 0 <= i < 2 ** 32 or not 0 <= w < 2 ** 32 or not isinstance(p, ChanParams) for i, w, _, p in rows):
             raise ValueError("tuned receivers %r: out of range" % (receivers,))
-        arr = (L.WbRx * max(len(rows), 1))(*[L.WbRx(*r) for r in rows])
-        check(lib.ssdr_set_wb_rx(self._ctx, arr if rows else None, len(rows)), "ssdr_set_wb_rx")
+        self._bank_set(self._WB_RX, rows)
 
     def get_wb_rx(self):
         """-> [(id, stream, offset_hz, ChanParams), ...] the tuned receivers as set"""
-        n = C.c_uint32(0)
-        arr = (L.WbRx * L.WB_RX_MAX)()
-        check(lib.ssdr_get_wb_rx(self._ctx, arr, C.byref(n)), "ssdr_get_wb_rx")
-        out = []
-        for v in arr[:n.value]:
-            p = ChanParams()
-            C.memmove(C.byref(p), C.byref(v.params), C.sizeof(ChanParams))
-            out.append((v.id, v.stream, v.offset_hz, p))
-        return out
-
-    def _wb_rx_count(self):
-        n = C.c_uint32(0)
-        check(lib.ssdr_get_wb_rx(self._ctx, None, C.byref(n)), "ssdr_get_wb_rx")
-        return n.value
+        return self._bank_get(self._WB_RX)
 
     def read_wb_rx(self, first=0, count=None):
         """-> int16 [count, n_frames * 512 * D, 2]: the IQ rows the receivers' DDC stored in the last push_wideband, in list order"""
-        count = self._wb_rx_count() - first if count is None else int(count)
+        count = self._bank_count(self._WB_RX) - first if count is None else int(count)
         out = np.empty((count, self.in_frames * L.FRAME * self.decim, 2), np.int16)
         check(lib.ssdr_read_wb_rx(self._ctx, int(first), count, out.ctypes.data), "ssdr_read_wb_rx")
         return out
@@ -707,46 +716,24 @@ class SsdrEngine:
     def wb_rx_audio(self):
         """-> (pcm int16 [n, n_frames*512], rssi float32 [n, n_frames], flags uint8 [n, n_frames]) of the last run_audio / run_chain
         behind a push_wideband, rows in list order"""
-        n, nf = self._wb_rx_count(), self.audio_frames
-        pcm = np.empty((n, nf * L.FRAME), np.int16)
-        rssi = np.empty((n, nf), np.float32)
-        flags = np.empty((n, nf), np.uint8)
-        check(lib.ssdr_wb_rx_audio(self._ctx, pcm.ctypes.data, rssi.ctypes.data, flags.ctypes.data, 0), "ssdr_wb_rx_audio")
-        return pcm, rssi, flags
+        return self._bank_audio(self._WB_RX)
 
     def wb_rx_state(self, first=0, count=None):
         """-> (state, hist) of rows [first, first + count) of the list, as get_state"""
-        count = self._wb_rx_count() - first if count is None else int(count)
-        st = np.empty(count, STATE_DTYPE)
-        hist = np.empty((count, L.HIST, 2), np.int16)
-        check(lib.ssdr_get_wb_rx_state(self._ctx, int(first), count, st.ctypes.data, hist.ctypes.data), "ssdr_get_wb_rx_state")
-        return st, hist
+        return self._bank_read(self._WB_RX, "state", first, count, *self._STATE_ROWS)
 
     def wb_rx_sam_carrier(self, first=0, count=None):
         """-> (offset_hz, phase_rad) float32 arrays of rows [first, first + count) of the list, as sam_carrier"""
-        count = self._wb_rx_count() - first if count is None else int(count)
-        hz, ph = np.zeros(count, np.float32), np.zeros(count, np.float32)
-        check(lib.ssdr_get_wb_rx_sam_carrier(self._ctx, int(first), count, hz.ctypes.data, ph.ctypes.data), "ssdr_get_wb_rx_sam_carrier")
-        return hz, ph
+        return self._bank_read(self._WB_RX, "sam_carrier", first, count, *self._CARRIER_ROWS)
 
     def wb_rx_consts(self, first=0, count=None):
         """-> (consts, taps) of rows [first, first + count) of the list, as get_consts"""
-        count = self._wb_rx_count() - first if count is None else int(count)
-        k = np.empty(count, CONSTS_DTYPE)
-        taps = np.empty((count, L.NTAP_MAX), np.float32)
-        check(lib.ssdr_get_wb_rx_consts(self._ctx, int(first), count, k.ctypes.data, taps.ctypes.data), "ssdr_get_wb_rx_consts")
-        return k, taps
+        return self._bank_read(self._WB_RX, "consts", first, count, *self._CONSTS_ROWS)
 
     def run_wb_rx_playbuffer(self, chans):
         """play_buffer for the tuned receivers' frames of the last run -> int16 [n, n_frames*L, 2], L = playbuffer_frame_len().
         chans: list of PlayChan, one per receiver in list order, or a ctypes array."""
-        n = self._wb_rx_count()
-        arr = chans if isinstance(chans, C.Array) else (PlayChan * max(n, 1))(*chans)
-        if len(arr) < n:
-            raise ValueError("run_wb_rx_playbuffer: %d settings for %d tuned receivers" % (len(arr), n))
-        out = np.empty((n, self.audio_frames * self.playbuffer_frame_len(), 2), np.int16)
-        check(lib.ssdr_run_wb_rx_playbuffer(self._ctx, arr, out.ctypes.data, 0), "ssdr_run_wb_rx_playbuffer")
-        return out
+        return self._bank_playbuffer(self._WB_RX, chans)
 
     def wb_rx_stats(self, reset=False):
         """-> (ddc_ms, audio_ms, ddc_runs, audio_runs) of the tuned receivers' stage since the last reset (the times only with

@@ -1168,18 +1168,14 @@ class IQHub:
         if self._subs:
             sub_ids = sorted(self._subs)
             sub_pcm, sub_rssi, sub_flags = eng.subrx_audio()                    # [n_sub, frames*512], [n_sub, frames] x 2 (open_sub)
-            clients = [self.sub_clients.get(sid) for sid in sub_ids]
-            if self.gpu_post and any(s is not None for s in clients):
-                sub_play = eng.run_subrx_playbuffer([PlayChan(100.0, 0.0) if s is None else PlayChan(float(s.volume), float(s.audio_balance))
-                                                     for s in clients])
+            vb = self._rx_play_chans(self.sub_clients, sub_ids)
+            sub_play = eng.run_subrx_playbuffer(vb) if vb else None
         tuned_ids = tuned_pcm = tuned_rssi = tuned_flags = tuned_play = None
         if wideband and self._tuned:
             tuned_ids = sorted(self._tuned)
             tuned_pcm, tuned_rssi, tuned_flags = eng.wb_rx_audio()              # rows in tid order (open_tuned)
-            clients = [self.tuned_clients.get(tid) for tid in tuned_ids]
-            if self.gpu_post and any(s is not None for s in clients):
-                tuned_play = eng.run_wb_rx_playbuffer([PlayChan(100.0, 0.0) if s is None else PlayChan(float(s.volume), float(s.audio_balance))
-                                                       for s in clients])
+            vb = self._rx_play_chans(self.tuned_clients, tuned_ids)
+            tuned_play = eng.run_wb_rx_playbuffer(vb) if vb else None
         self.superframes += 1
         self._hand_out(SuperframeResult(seq=self.superframes, wf=wf, tuned_ids=tuned_ids, tuned_pcm=tuned_pcm, tuned_rssi=tuned_rssi,
                                         tuned_flags=tuned_flags, tuned_play=tuned_play, n_avg=n_avg, color=color, chans=chans, pcm=pcm, rssi=rssi,
@@ -1188,6 +1184,24 @@ class IQHub:
                                         snd_adpcm=snd_adpcm, wf_adpcm=wf_adpcm, snd_adpcm_channels=snd_sel, wf_adpcm_channels=wf_sel,
                                         squelched=closed, view_lines=view_lines, view_channels=view_ch,
                                         scope_ids=scope_ids, scope_lines=scope_lines))
+
+    def _rx_play_chans(self, clients, ids):
+        """-> [PlayChan] of a receiver list's rows (neutral for a row nobody listens to); None: no play_buffer on the GPU, or no listener"""
+        rows = [clients.get(i) for i in ids]
+        if not self.gpu_post or all(s is None for s in rows):
+            return None
+        return [PlayChan(100.0, 0.0) if s is None else PlayChan(float(s.volume), float(s.audio_balance)) for s in rows]
+
+    def _hand_out_rx(self, queues, ids, pcm, rssi, flags, play):
+        """a receiver list's frames (rows in the order of `ids`) to the queues of those that have one"""
+        P = self.play_len
+        for i, rid in enumerate(ids or ()):
+            q = queues.get(rid)
+            if q is None:
+                continue
+            for f in range(pcm.shape[1] // L.FRAME):
+                _put_drop_oldest(q, Frame.make(pcm[i, f * L.FRAME:(f + 1) * L.FRAME], rssi[i, f],
+                                               play[i, f * P:(f + 1) * P].copy() if play is not None else None, None, flags[i, f]))
 
     def _hand_out(self, r):
         self.last = r
@@ -1246,23 +1260,8 @@ class IQHub:
                     if qc is not None and r.squelched[qc, f]:
                         fr.squelched = True
                 _put_drop_oldest(q, fr)
-        for i, sid in enumerate(r.sub_ids or ()):
-            q = self.sub_queue.get(sid)
-            if q is None:
-                continue
-            for f in range(r.sub_pcm.shape[1] // L.FRAME):
-                _put_drop_oldest(q, Frame.make(r.sub_pcm[i, f * L.FRAME:(f + 1) * L.FRAME], r.sub_rssi[i, f],
-                                               r.sub_play[i, f * P:(f + 1) * P].copy() if r.sub_play is not None else None, None,
-                                               r.sub_flags[i, f]))
-        for i, tid in enumerate(r.tuned_ids or ()):
-            q = self.tuned_queue.get(tid)
-            if q is None:
-                continue
-            for f in range(r.tuned_pcm.shape[1] // L.FRAME):
-                _put_drop_oldest(q, Frame.make(r.tuned_pcm[i, f * L.FRAME:(f + 1) * L.FRAME], r.tuned_rssi[i, f],
-                                               r.tuned_play[i, f * P:(f + 1) * P].copy() if r.tuned_play is not None else None, None,
-                                               r.tuned_flags[i, f]))
-
+        self._hand_out_rx(self.sub_queue, r.sub_ids, r.sub_pcm, r.sub_rssi, r.sub_flags, r.sub_play)
+        self._hand_out_rx(self.tuned_queue, r.tuned_ids, r.tuned_pcm, r.tuned_rssi, r.tuned_flags, r.tuned_play)
         for i, sid in enumerate(r.scope_ids or ()):
             q = self.scope_queue.get(sid)
             if q is None:

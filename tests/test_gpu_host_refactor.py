@@ -1,4 +1,4 @@
-"""What the shared helpers of the C API's host code (csrc/ssdr_api.cpp) must keep as it was, pinned on the GPU: the five
+"""What the shared helpers of the C API's host code (csrc/ssdr_api.cpp) must keep as it was, pinned on the GPU: the seven
 stage timers beside the SSDR_K_* slots are independent of each other and of those slots, and the two entry points that change
 the input rate keep their own order of refusals although they share one body (change_input_rate)."""
 import ctypes as C
@@ -22,8 +22,9 @@ def S():
 
 
 def test_stage_timers_are_independent(S):
-    """de-emphasis, views, sub-receivers, channeliser, scopes: each counts its own launches (with or without profiling), keeps its
-    own time (with profiling only), and a reset of one touches neither the other four nor an SSDR_K_* slot"""
+    """de-emphasis, views, sub-receivers, channeliser, scopes, the tuned receivers' DDC and their audio: each counts its own launches
+    (with or without profiling), keeps its own time (with profiling only), and a reset of one -- the tuned receivers' two go together
+    -- touches neither the others nor an SSDR_K_* slot"""
     from supersdr_amd import _lib as L
     with S.SsdrEngine(1024) as eng:                      # the channeliser's minimum: one stream
         eng.set_profiling(True)
@@ -32,8 +33,16 @@ def test_stage_timers_are_independent(S):
         eng.set_wf_views([(0, 2, 0.0)])
         eng.set_subrx([(1, 0, S.default_params("am"))])
         eng.set_deemphasis(0, [(1, 0)])                  # channel 0 is in AM: the setting acts
+        eng.set_wb_rx([(1, 0, 0.0, S.default_params("am"))])
+
+        def wb_rx(k):                                    # the tuned receivers' two timers, which ssdr_wb_rx_stats reads and resets together
+            def stats(reset=False):
+                got = eng.wb_rx_stats(reset=reset)
+                return got[k], got[2 + k]
+            return stats
+        together = {"wbrx_ddc", "wbrx_audio"}
         stages = {"deemp": eng.deemp_stats, "view": eng.wf_view_stats, "subrx": eng.subrx_stats,
-                  "chan": eng.channelizer_stats, "scope": eng.wb_scope_stats}
+                  "chan": eng.channelizer_stats, "scope": eng.wb_scope_stats, "wbrx_ddc": wb_rx(0), "wbrx_audio": wb_rx(1)}
         n_slots = 0                                      # SSDR_K_COUNT, asked of the library: the first `which` it refuses
         while L.lib.ssdr_kernel_stats(eng._ctx, n_slots, None, None, 0) == L.OK:
             n_slots += 1
@@ -47,7 +56,7 @@ def test_stage_timers_are_independent(S):
         eng.run_chain()
         eng.sync()
         # the launch counts of the commit before the helpers (one push, one chain run: one launch of every stage)
-        want = {"deemp": 1, "view": 1, "subrx": 1, "chan": 1, "scope": 1}
+        want = {"deemp": 1, "view": 1, "subrx": 1, "chan": 1, "scope": 1, "wbrx_ddc": 1, "wbrx_audio": 1}
         for name, stats in stages.items():
             ms, n = stats()
             print(name, ms, n)
@@ -58,8 +67,9 @@ def test_stage_timers_are_independent(S):
             before = {m: s() for m, s in stages.items()}
             assert stats(reset=True) == before[name]
             after = {m: s() for m, s in stages.items()}
-            assert after.pop(name) == (0.0, 0)
-            before.pop(name)
+            for gone in (together if name in together else {name}):
+                assert after.pop(gone) == (0.0, 0)
+                before.pop(gone)
             assert after == before, name
             assert slots() == k1, name
         eng.set_profiling(False)
@@ -69,6 +79,9 @@ def test_stage_timers_are_independent(S):
         for name, stats in stages.items():               # launches are counted without profiling, time is not
             assert stats() == (0.0, 1), name
         assert slots() == k1
+        eng.push_wideband(iq)                            # the DDC counts a launch per push, the receivers' audio one per run
+        eng.sync()
+        assert stages["wbrx_ddc"]() == (0.0, 2) and stages["wbrx_audio"]() == (0.0, 1) and stages["subrx"]() == (0.0, 1)
 
 
 def test_rate_changes_keep_their_own_refusal_order(S):
