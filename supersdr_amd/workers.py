@@ -126,9 +126,10 @@ class SuperframeResult:
     (N = 1) each completed in this feed_wideband, k >= 0 (both None: no scope is open).
     With tuned receivers (IQHub.open_tuned): tuned_ids lists them, ascending, and tuned_pcm / tuned_rssi / tuned_flags / tuned_play have
     a row for each, as the sub-receivers' arrays do (all None: no tuned receiver is open, or the run was no feed_wideband)."""
-    __slots__ = ("tuned_ids", "tuned_pcm", "tuned_rssi", "tuned_flags", "tuned_play","seq", "wf", "n_avg", "color", "chans", "pcm", "rssi", "flags", "play", "mono", "iq", "wire_rssi", "post_channels", "out_channels",
+    __slots__ = ("seq", "wf", "n_avg", "color", "chans", "pcm", "rssi", "flags", "play", "mono", "iq", "wire_rssi", "post_channels", "out_channels",
                  "snd_adpcm", "wf_adpcm", "snd_adpcm_channels", "wf_adpcm_channels", "squelched", "view_lines", "view_channels",
-                 "squelched_channels", "sub_ids", "sub_pcm", "sub_rssi", "sub_flags", "sub_play", "scope_ids", "scope_lines")
+                 "squelched_channels", "sub_ids", "sub_pcm", "sub_rssi", "sub_flags", "sub_play", "scope_ids", "scope_lines",
+                 "tuned_ids", "tuned_pcm", "tuned_rssi", "tuned_flags", "tuned_play")
 
     def __init__(self, **kw):
         for k in self.__slots__:
@@ -166,6 +167,54 @@ class _Queues:
 
     def attached(self, c):
         return self._q.get(c)
+
+
+class _Listeners:
+    """One family of the hub's extra listeners (sub-receivers, tuned receivers, wideband scopes): the table id -> row, the next id
+    (ids count from 1 and are never reused), and per id a bounded result queue and a client slot (the worker on it, or None).
+    `send(rows)` hands a whole table to the engine, ids ascending, and raises when it is refused; every change here is copy the
+    table, change one entry, send, and only then commit -- the old table stays if refused.  `queue` and `clients` are the dicts the
+    hub publishes (sub_queue, sub_clients, ...): they live as long as the hub, workers hold them."""
+
+    def __init__(self, nouns, capacity, capacity_name, send, queue_len):
+        self.nouns, self.capacity, self.capacity_name, self._send, self._queue_len = nouns, capacity, capacity_name, send, queue_len
+        self.rows, self.next_id, self.queue, self.clients = {}, 1, {}, {}
+
+    def ids(self):
+        return sorted(self.rows)
+
+    def open(self, row):
+        """-> the new id; ValueError at capacity (before the engine is touched)"""
+        if len(self.rows) >= self.capacity:
+            raise ValueError("a hub runs at most %d %s (%s)" % (self.capacity, self.nouns, self.capacity_name))
+        i = self.next_id
+        self.replace(i, row)
+        self.next_id += 1
+        self.queue[i] = queue.Queue(self._queue_len)
+        self.clients[i] = None
+        return i
+
+    def replace(self, i, row):
+        new = dict(self.rows)
+        new[i] = row
+        self._send(new)
+        self.rows = new
+
+    def close(self, i):
+        if i not in self.rows:
+            return                                   # closing twice counts once
+        new = dict(self.rows)
+        del new[i]
+        self._send(new)
+        self.rows = new
+        self.queue.pop(i, None)
+        self.clients.pop(i, None)
+
+    def clear(self):
+        """the engine emptied its list: every listener of the family is closed"""
+        self.rows = {}
+        self.queue.clear()
+        self.clients.clear()
 
 
 class IQHub:
@@ -321,19 +370,17 @@ class IQHub:
         self._comp_snd, self._comp_wf = [], []       # channels with "SET compression=1" / "SET wf_comp=1", sorted (the engine's row order)
         self._views = {}                             # channel -> (zoom, offset_hz): the waterfall views (set_wf_view)
         self._wf_listeners = {}                      # channel -> W/F streams open on it (the last one to close takes the view with it)
-        self._subs = {}                              # sid -> (channel, ChanParams): the sub-receivers (open_sub), the engine's rows in sid order
-        self._next_sid = 1
-        self.sub_queue = {}                          # sid -> bounded queue of Frame
-        self.sub_clients = {}                        # sid -> the kiwi_sound on it (volume / balance for its play_buffer), or None
-        self._scopes = {}                            # sid -> (stream, zoom, offset_hz): the wideband scopes (open_scope), the engine's list in sid order
-        self._scope_det = {}                         # sid -> "sample" | "average" | "peak" | "min": the scopes' detectors (set_scope_detector)
-        self._next_scope = 1
-        self.scope_queue = {}                        # sid -> bounded queue of WfLine (N = 1), drop-oldest
-        self.scope_clients = {}                      # sid -> the kiwi_waterfall on it (its display state for ssdr_db2col_line), or None
-        self._tuned = {}                             # tid -> (stream, offset_hz, ChanParams): the tuned receivers (open_tuned), the engine's rows in tid order
-        self._next_tid = 1                           # (the hub owns the ids and never reuses one)
-        self.tuned_queue = {}                        # tid -> bounded queue of Frame
-        self.tuned_clients = {}                      # tid -> the kiwi_sound on it (volume / balance for its play_buffer), or None
+        self.channelizer = None                      # the wideband channeliser in front of the hub (set_channelizer)
+        # the extra listeners, a table per family (the engine's rows in id order), and the dicts they publish:
+        #   sub-receivers    sid -> (channel, ChanParams);                 sub_queue[sid]: Frame,   sub_clients[sid]: the kiwi_sound on it
+        #   tuned receivers  tid -> (stream, offset_hz, ChanParams);       tuned_queue[tid]: Frame, tuned_clients[tid]: the kiwi_sound on it
+        #   wideband scopes  sid -> (stream, zoom, offset_hz, detector);   scope_queue[sid]: WfLine (N = 1), scope_clients[sid]: the kiwi_waterfall on it
+        self._subs = _Listeners("sub-receivers", L.SUBRX_MAX, "SSDR_SUBRX_MAX", self._send_subs, 2 * self._max_queue)
+        self._tuned = _Listeners("tuned receivers", L.WB_RX_MAX, "SSDR_WB_RX_MAX", self._send_tuned, 2 * self._max_queue)
+        self._scopes = _Listeners("wideband scopes", L.WB_SCOPES_MAX, "SSDR_WB_SCOPES_MAX", self._send_scopes, 2 * self._max_queue)
+        self.sub_queue, self.sub_clients = self._subs.queue, self._subs.clients
+        self.tuned_queue, self.tuned_clients = self._tuned.queue, self._tuned.clients
+        self.scope_queue, self.scope_clients = self._scopes.queue, self._scopes.clients
         self._want_n = np.ones(self.n_ch, np.int32)  # averaging_n asked for by each channel's waterfall client
         self._want_all = {1: self.n_ch}              # N -> channels that want it (all channels / channels with a client)
         self._want_cli = {}
@@ -467,10 +514,10 @@ class IQHub:
             raise ValueError("sam_carrier takes a channel, a sub-receiver id or a tuned receiver id")
         with self._lock:
             if tuned is not None:
-                row = sorted(self._tuned).index(int(tuned))        # ValueError: no such tuned receiver
+                row = self._tuned.ids().index(int(tuned))          # ValueError: no such tuned receiver
                 hz, ph = self.engine.wb_rx_sam_carrier(row, 1)
             elif sub is not None:
-                row = sorted(self._subs).index(int(sub))           # ValueError: no such sub-receiver
+                row = self._subs.ids().index(int(sub))             # ValueError: no such sub-receiver
                 hz, ph = self.engine.subrx_sam_carrier(row, 1)
             else:
                 c = int(channel)
@@ -619,12 +666,12 @@ class IQHub:
     def sub_params(self, sid):
         """-> (channel, ChanParams) of sub-receiver `sid`"""
         with self._lock:
-            return self._subs[int(sid)]
+            return self._subs.rows[int(sid)]
 
-    def _set_subs(self, new):
-        """the whole list to the engine, ids ascending; refused by the library: the old list stays"""
-        self.engine.set_subrx([(sid,) + new[sid] for sid in sorted(new)])
-        self._subs = new
+    def _send_subs(self, rows):
+        if not hasattr(self.engine, "set_subrx"):    # (only an open can meet this: without it no sub-receiver is open)
+            raise ValueError("this engine has no sub-receivers (set_subrx)")
+        self.engine.set_subrx([(sid,) + rows[sid] for sid in sorted(rows)])
 
     def _check_sub_params(self, p):
         if p.mode == L.MODE_IQ:
@@ -646,58 +693,40 @@ class IQHub:
         p = _copy_params(params if params is not None else self._default_params)
         self._check_sub_params(p)
         with self._lock:
-            if len(self._subs) >= L.SUBRX_MAX:
-                raise ValueError("a hub runs at most %d sub-receivers (SSDR_SUBRX_MAX)" % L.SUBRX_MAX)
-            if not hasattr(self.engine, "set_subrx"):
-                raise ValueError("this engine has no sub-receivers (set_subrx)")
-            sid = self._next_sid
-            new = dict(self._subs)
-            new[sid] = (c, p)
             try:
-                self._set_subs(new)
+                return self._subs.open((c, p))
             except L.SsdrError as e:
                 raise ValueError("sub-receiver on channel %d refused: %s" % (c, e))
-            self._next_sid += 1
-            self.sub_queue[sid] = queue.Queue(2 * self._max_queue)
-            self.sub_clients[sid] = None
-            return sid
 
     def set_sub_params(self, sid, p):
         sid = int(sid)
         self._check_sub_params(p)
         with self._lock:
-            new = dict(self._subs)
-            new[sid] = (self._subs[sid][0], _copy_params(p))       # KeyError: no such sub-receiver
-            self._set_subs(new)                      # raises for parameters the library refuses; the old ones stay
+            channel = self._subs.rows[sid][0]        # KeyError: no such sub-receiver
+            self._subs.replace(sid, (channel, _copy_params(p)))      # raises for parameters the library refuses; the old ones stay
 
     def close_sub(self, sid):
-        sid = int(sid)
         with self._lock:
-            if sid not in self._subs:
-                return                               # closing twice counts once
-            new = dict(self._subs)
-            del new[sid]
-            self._set_subs(new)
-            self.sub_queue.pop(sid, None)
-            self.sub_clients.pop(sid, None)
+            self._subs.close(int(sid))
 
     # ---- tuned receivers: demodulators at any frequency of a channeliser's wide stream (ssdr_set_wb_rx)
     def tuned(self, tid):
         """-> (stream, offset_hz, ChanParams) of tuned receiver `tid`"""
         with self._lock:
-            return self._tuned[int(tid)]
+            return self._tuned.rows[int(tid)]
 
     def wide_rate(self):
         """the wide streams' sample rate under the channeliser that is set"""
         return self.channelizer.wide_rate(self.kiwi_rate)
 
-    def _require_tuned(self):
+    def _require_wide_stream(self, noun, setter):
+        """what a listener on a wide stream (a tuned receiver, a wideband scope) needs, checked before the engine is touched"""
         if self.pipeline or self.wire:
-            raise ValueError("a tuned receiver needs the synchronous sample hub")
-        if getattr(self, "channelizer", None) is None:
-            raise ValueError("a tuned receiver needs a channeliser (set_channelizer)")
-        if not hasattr(self.engine, "set_wb_rx"):
-            raise ValueError("this engine has no tuned receivers (set_wb_rx)")
+            raise ValueError("a %s needs the synchronous sample hub" % noun)
+        if self.channelizer is None:
+            raise ValueError("a %s needs a channeliser (set_channelizer)" % noun)
+        if not hasattr(self.engine, setter):
+            raise ValueError("this engine has no %ss (%s)" % (noun, setter))
 
     def _check_tuned(self, stream, offset_hz, p):
         if p.mode == L.MODE_IQ:
@@ -709,13 +738,11 @@ class IQHub:
         if not abs(offset_hz) <= half:               # (NaN fails as well)
             raise ValueError("tuned receiver centre %r Hz is outside the +-%g Hz wide stream" % (offset_hz, half))
 
-    def _set_tuned(self, new):
-        """the whole list to the engine, ids ascending; refused by the library: the old list stays"""
+    def _send_tuned(self, rows):
         try:
-            self.engine.set_wb_rx([(tid,) + new[tid] for tid in sorted(new)])
+            self.engine.set_wb_rx([(tid,) + rows[tid] for tid in sorted(rows)])
         except L.SsdrError as e:
             raise ValueError("tuned receivers refused: %s" % e)
-        self._tuned = new
 
     def open_tuned(self, stream, offset_hz, params=None):
         """A tuned receiver on wide stream `stream`: a DDC at a row's rate centred offset_hz from the stream's centre -- anywhere, not
@@ -724,98 +751,70 @@ class IQHub:
         nothing: nobody restarts), set_tuned_params(tid, p) changes the demodulator (state kept, like set_params), close_tuned(tid)
         ends it.  ValueError on a pipelined or wire hub and without a channeliser (before the engine is touched), beyond 64 of them
         (SSDR_WB_RX_MAX), for mod=iq, an offset outside the wide stream and parameters the library refuses; then nothing changes."""
-        self._require_tuned()
+        self._require_wide_stream("tuned receiver", "set_wb_rx")
         p = _copy_params(params if params is not None else self._default_params)
         row = (int(stream), float(offset_hz), p)
         self._check_tuned(*row)
         with self._lock:
-            if len(self._tuned) >= L.WB_RX_MAX:
-                raise ValueError("a hub runs at most %d tuned receivers (SSDR_WB_RX_MAX)" % L.WB_RX_MAX)
-            tid = self._next_tid
-            new = dict(self._tuned)
-            new[tid] = row
-            self._set_tuned(new)
-            self._next_tid += 1
-            self.tuned_queue[tid] = queue.Queue(2 * self._max_queue)
-            self.tuned_clients[tid] = None
-            return tid
+            return self._tuned.open(row)
 
     def retune_tuned(self, tid, offset_hz, params=None):
         """moves tuned receiver `tid`: from the next feed_wideband on its row is centred offset_hz from the stream's centre; with
         `params` the demodulator changes in the same step (both or neither)"""
         tid = int(tid)
         with self._lock:
-            stream, _, p = self._tuned[tid]          # KeyError: no such tuned receiver
+            stream, _, p = self._tuned.rows[tid]     # KeyError: no such tuned receiver
             if params is not None:
                 p = _copy_params(params)
-            self._check_tuned(stream, float(offset_hz), p)
-            new = dict(self._tuned)
-            new[tid] = (stream, float(offset_hz), p)
-            self._set_tuned(new)
+            row = (stream, float(offset_hz), p)
+            self._check_tuned(*row)
+            self._tuned.replace(tid, row)
 
     def set_tuned_params(self, tid, p):
         tid = int(tid)
         with self._lock:
-            stream, off, _ = self._tuned[tid]        # KeyError: no such tuned receiver
-            q = _copy_params(p)
-            self._check_tuned(stream, off, q)
-            new = dict(self._tuned)
-            new[tid] = (stream, off, q)
-            self._set_tuned(new)                     # raises for parameters the library refuses; the old ones stay
+            stream, off, _ = self._tuned.rows[tid]   # KeyError: no such tuned receiver
+            row = (stream, off, _copy_params(p))
+            self._check_tuned(*row)
+            self._tuned.replace(tid, row)            # raises for parameters the library refuses; the old ones stay
 
     def close_tuned(self, tid):
-        tid = int(tid)
         with self._lock:
-            if tid not in self._tuned:
-                return                               # closing twice counts once
-            new = dict(self._tuned)
-            del new[tid]
-            self._set_tuned(new)
-            self.tuned_queue.pop(tid, None)
-            self.tuned_clients.pop(tid, None)
+            self._tuned.close(int(tid))
 
     # ---- wideband scopes: zoomable waterfalls of a channeliser's wide stream (the band scope of kiwi_waterfall; ssdr_set_wb_scopes)
     def scope(self, sid):
         """-> (stream, zoom, offset_hz) of scope `sid`"""
         with self._lock:
-            return self._scopes[int(sid)]
+            return self._scopes.rows[int(sid)][:3]
 
-    def _require_scopes(self):
-        if self.pipeline or self.wire:
-            raise ValueError("a wideband scope needs the synchronous sample hub")
-        if getattr(self, "channelizer", None) is None:
-            raise ValueError("a wideband scope needs a channeliser (set_channelizer)")
-        if not hasattr(self.engine, "set_wb_scopes"):
-            raise ValueError("this engine has no wideband scopes (set_wb_scopes)")
-
-    def _set_scopes(self, new, det=None):
-        """the whole list to the engine, in sid order, and then the detectors (the library puts a new list on sample; all on sample:
-        nothing to send); refused by the library: the old list and the old detectors stay"""
-        det = {sid: (self._scope_det if det is None else det).get(sid, "sample") for sid in new}
-        order = sorted(new)
-        codes = [SCOPE_DETECTORS[det[sid]] for sid in order]
+    def _send_scopes(self, rows):
+        """the list in sid order and then the detectors, the rows' fourth entry (the library puts a new list on sample; all on sample:
+        nothing to send); the detectors refused: the old list and the old detectors go back to the library"""
+        def lists(rows):
+            order = sorted(rows)
+            return [rows[sid][:3] for sid in order], [SCOPE_DETECTORS[rows[sid][3]] for sid in order]
+        scopes, codes = lists(rows)
         if any(codes) and not hasattr(self.engine, "set_wb_scope_detectors"):
             raise ValueError("this engine has no scope detectors (set_wb_scope_detectors)")
         try:
-            self.engine.set_wb_scopes([new[sid] for sid in order])
+            self.engine.set_wb_scopes(scopes)
         except L.SsdrError as e:
             raise ValueError("wideband scopes refused: %s" % e)
         try:
             if any(codes):
                 self.engine.set_wb_scope_detectors(codes)
         except L.SsdrError as e:                     # back to what was: the list, then its detectors
-            old = sorted(self._scopes)
-            self.engine.set_wb_scopes([self._scopes[sid] for sid in old])
-            if any(self._scope_det.get(sid, "sample") != "sample" for sid in old):
-                self.engine.set_wb_scope_detectors([SCOPE_DETECTORS[self._scope_det.get(sid, "sample")] for sid in old])
+            scopes, codes = lists(self._scopes.rows)
+            self.engine.set_wb_scopes(scopes)
+            if any(codes):
+                self.engine.set_wb_scope_detectors(codes)
             raise ValueError("scope detectors refused: %s" % e)
-        self._scopes, self._scope_det = new, det
 
     def scope_detector(self, sid):
         """-> "sample" | "average" | "peak" | "min" of scope `sid`"""
         with self._lock:
-            self._scopes[int(sid)]                   # KeyError: no such scope
-            return self._scope_det.get(int(sid), "sample")
+            return self._scopes.rows[int(sid)][3]    # KeyError: no such scope
 
     def set_scope_detector(self, sid, detector):
         """The detector of scope `sid` over the windows of a line period (ssdr_set_wb_scope_detectors): "sample" (the last 1024 outputs
@@ -823,10 +822,8 @@ class IQHub:
         restarted.  Another name is a ValueError before the engine is touched."""
         sid, name = int(sid), check_scope_detector(detector)
         with self._lock:
-            self._scopes[sid]                        # KeyError: no such scope
-            det = dict(self._scope_det)
-            det[sid] = name
-            self._set_scopes(dict(self._scopes), det)
+            row = self._scopes.rows[sid]             # KeyError: no such scope
+            self._scopes.replace(sid, row[:3] + (name,))
 
     def open_scope(self, stream, zoom, offset_hz=0.0, detector="sample"):
         """A scope on wide stream `stream`: the wide rate / 2^zoom around offset_hz (Hz from the stream's centre), zoom 0 .. 10.  -> sid:
@@ -836,46 +833,22 @@ class IQHub:
         end), "average", "peak" or "min" over every window of the line period (set_scope_detector).  ValueError on a pipelined or wire hub and
         without a channeliser (before the engine is touched), beyond 64 scopes and for what the library refuses; then nothing changes."""
         name = check_scope_detector(detector)                # (before the engine is touched)
-        self._require_scopes()
-        row = (int(stream), int(zoom), float(offset_hz))
+        self._require_wide_stream("wideband scope", "set_wb_scopes")
+        row = (int(stream), int(zoom), float(offset_hz), name)
         with self._lock:
-            if len(self._scopes) >= L.WB_SCOPES_MAX:
-                raise ValueError("a hub runs at most %d wideband scopes (SSDR_WB_SCOPES_MAX)" % L.WB_SCOPES_MAX)
-            sid = self._next_scope
-            new = dict(self._scopes)
-            new[sid] = row
-            det = dict(self._scope_det)
-            det[sid] = name
-            self._set_scopes(new, det)
-            self._next_scope += 1
-            self.scope_queue[sid] = queue.Queue(2 * self._max_queue)
-            self.scope_clients[sid] = None
-            return sid
+            return self._scopes.open(row)
 
     def retune_scope(self, sid, zoom, offset_hz, detector=None):
         """moves scope `sid`; detector None keeps its detector"""
         sid = int(sid)
         name = None if detector is None else check_scope_detector(detector)
         with self._lock:
-            new = dict(self._scopes)
-            new[sid] = (self._scopes[sid][0], int(zoom), float(offset_hz))       # KeyError: no such scope
-            det = dict(self._scope_det)
-            if name is not None:
-                det[sid] = name
-            self._set_scopes(new, det)
+            old = self._scopes.rows[sid]             # KeyError: no such scope
+            self._scopes.replace(sid, (old[0], int(zoom), float(offset_hz), old[3] if name is None else name))
 
     def close_scope(self, sid):
-        sid = int(sid)
         with self._lock:
-            if sid not in self._scopes:
-                return                               # closing twice counts once
-            new = dict(self._scopes)
-            del new[sid]
-            det = dict(self._scope_det)
-            det.pop(sid, None)
-            self._set_scopes(new, det)
-            self.scope_queue.pop(sid, None)
-            self.scope_clients.pop(sid, None)
+            self._scopes.close(int(sid))
 
     def db2col_scope_line(self, sid, wf_sum, n):
         """db2col_line for a scope's client: the display state is that of the kiwi_waterfall on the scope"""
@@ -1107,20 +1080,15 @@ class IQHub:
             else:
                 self.engine.set_channelizer(self.n_ch // channelizer.BRANCHES, channelizer.oversample, channelizer.taps)
             self.channelizer = channelizer
-            self._scopes = {}                        # the library emptied its list: every scope is closed
-            self._scope_det = {}
-            self.scope_queue.clear()
-            self.scope_clients.clear()
-            self._tuned = {}                         # ... and every tuned receiver
-            self.tuned_queue.clear()
-            self.tuned_clients.clear()
+            self._scopes.clear()                     # the library emptied its lists: every scope is closed, and every tuned receiver
+            self._tuned.clear()
 
     def feed_wideband(self, block):
         """one superframe of every wide stream: int16 [n_streams, superframe samples * 1024 / oversample, 2] -> one GPU run, as if the
         rows the channeliser cuts from it had been fed channel by channel"""
         if self.pipeline or self.wire:
             raise ValueError("feed_wideband needs the synchronous sample hub")
-        ch = getattr(self, "channelizer", None)
+        ch = self.channelizer
         if ch is None:
             raise ValueError("no channeliser is set (set_channelizer)")
         block = np.asarray(block, np.int16)
@@ -1138,8 +1106,9 @@ class IQHub:
             wire_rssi = eng.push_wideband(batch)        # (None: the rows carry no SND headers)
         else:
             wire_rssi = eng.push_iq_wire(batch) if self.wire else eng.push_iq(batch)
-        scope_ids = sorted(self._scopes) if wideband and self._scopes else None
-        scope_lines = eng.wb_scope_lines() if scope_ids else None               # [n, k, 1024], k >= 0 (open_scope)
+        extra = {}                                    # the extra listeners' results: a family without a listener leaves its fields None
+        if wideband and self._scopes.rows:
+            extra.update(scope_ids=self._scopes.ids(), scope_lines=eng.wb_scope_lines())      # [n, k, 1024], k >= 0 (open_scope)
         n_avg = self.averaging_n
         wf = eng.run_wf()                             # [lines, n_ch, 1024]
         wf_sel = list(self._comp_wf) if self._comp_wf else None
@@ -1164,33 +1133,27 @@ class IQHub:
             play = eng.run_playbuffer(self._play_arr)
             if rec:
                 mono = eng.playbuffer_mono()
-        sub_ids = sub_pcm = sub_rssi = sub_flags = sub_play = None
-        if self._subs:
-            sub_ids = sorted(self._subs)
-            sub_pcm, sub_rssi, sub_flags = eng.subrx_audio()                    # [n_sub, frames*512], [n_sub, frames] x 2 (open_sub)
-            vb = self._rx_play_chans(self.sub_clients, sub_ids)
-            sub_play = eng.run_subrx_playbuffer(vb) if vb else None
-        tuned_ids = tuned_pcm = tuned_rssi = tuned_flags = tuned_play = None
-        if wideband and self._tuned:
-            tuned_ids = sorted(self._tuned)
-            tuned_pcm, tuned_rssi, tuned_flags = eng.wb_rx_audio()              # rows in tid order (open_tuned)
-            vb = self._rx_play_chans(self.tuned_clients, tuned_ids)
-            tuned_play = eng.run_wb_rx_playbuffer(vb) if vb else None
+        if self._subs.rows:                           # [n, frames*512], [n, frames] x 2, rows in sid order (open_sub)
+            extra.update(self._rx_results("sub", self._subs, eng.subrx_audio, eng.run_subrx_playbuffer))
+        if wideband and self._tuned.rows:             # ... in tid order (open_tuned)
+            extra.update(self._rx_results("tuned", self._tuned, eng.wb_rx_audio, eng.run_wb_rx_playbuffer))
         self.superframes += 1
-        self._hand_out(SuperframeResult(seq=self.superframes, wf=wf, tuned_ids=tuned_ids, tuned_pcm=tuned_pcm, tuned_rssi=tuned_rssi,
-                                        tuned_flags=tuned_flags, tuned_play=tuned_play, n_avg=n_avg, color=color, chans=chans, pcm=pcm, rssi=rssi,
-                                        sub_ids=sub_ids, sub_pcm=sub_pcm, sub_rssi=sub_rssi, sub_flags=sub_flags, sub_play=sub_play,
+        self._hand_out(SuperframeResult(seq=self.superframes, wf=wf, n_avg=n_avg, color=color, chans=chans, pcm=pcm, rssi=rssi,
                                         flags=flags, play=play, mono=mono, iq=iqo, wire_rssi=wire_rssi, post_channels=self._post_sel,
                                         snd_adpcm=snd_adpcm, wf_adpcm=wf_adpcm, snd_adpcm_channels=snd_sel, wf_adpcm_channels=wf_sel,
-                                        squelched=closed, view_lines=view_lines, view_channels=view_ch,
-                                        scope_ids=scope_ids, scope_lines=scope_lines))
+                                        squelched=closed, view_lines=view_lines, view_channels=view_ch, **extra))
 
-    def _rx_play_chans(self, clients, ids):
-        """-> [PlayChan] of a receiver list's rows (neutral for a row nobody listens to); None: no play_buffer on the GPU, or no listener"""
-        rows = [clients.get(i) for i in ids]
-        if not self.gpu_post or all(s is None for s in rows):
-            return None
-        return [PlayChan(100.0, 0.0) if s is None else PlayChan(float(s.volume), float(s.audio_balance)) for s in rows]
+    def _rx_results(self, name, table, audio, playbuffer):
+        """-> a receiver table's fields of the SuperframeResult (name_ids, name_pcm, name_rssi, name_flags, name_play) after a run: the
+        engine's audio of its rows and, with gpu_post and a listener on one of them, their play_buffer blocks (a row nobody listens
+        to plays at the neutral setting)"""
+        ids = table.ids()
+        pcm, rssi, flags = audio()
+        rows = [table.clients.get(i) for i in ids]
+        play = None
+        if self.gpu_post and any(s is not None for s in rows):
+            play = playbuffer([PlayChan(100.0, 0.0) if s is None else PlayChan(float(s.volume), float(s.audio_balance)) for s in rows])
+        return {name + "_ids": ids, name + "_pcm": pcm, name + "_rssi": rssi, name + "_flags": flags, name + "_play": play}
 
     def _hand_out_rx(self, queues, ids, pcm, rssi, flags, play):
         """a receiver list's frames (rows in the order of `ids`) to the queues of those that have one"""
@@ -1482,20 +1445,27 @@ class GpuStream:
         self.sub = None if sub is None else int(sub)
         self.scope = None if scope is None else int(scope)
         self.tuned = None if tuned is None else int(tuned)
+        # a sub-receiver's or a tuned receiver's stream: the EXTRA RECEIVER it stands for (None: the channel's own demodulator, or a
+        # scope).  Its row in the hub starts with what it sits on and ends with its ChanParams.
+        self._rx = None
         if self.tuned is not None:
-            if kind != "SND" or sub is not None or scope is not None:
-                raise ValueError("a tuned receiver has an SND stream only")
-            if hub.tuned(self.tuned)[0] != self.channel:         # KeyError: no such tuned receiver
-                raise ValueError("tuned receiver %d listens to wide stream %d, not %d" % (self.tuned, hub.tuned(self.tuned)[0], self.channel))
+            self._rx = types.SimpleNamespace(
+                noun="tuned receiver", id=self.tuned, on="wide stream", no_stage="there is no %s for tuned receivers", queues=hub.tuned_queue,
+                row=lambda: hub.tuned(self.tuned), set_params=lambda q: hub.set_tuned_params(self.tuned, q), close=lambda: hub.close_tuned(self.tuned))
+        elif self.sub is not None and scope is None:
+            self._rx = types.SimpleNamespace(
+                noun="sub-receiver", id=self.sub, on="channel", no_stage="the %s is the channel's, there is none for sub-receivers", queues=hub.sub_queue,
+                row=lambda: hub.sub_params(self.sub), set_params=lambda q: hub.set_sub_params(self.sub, q), close=lambda: hub.close_sub(self.sub))
+        if self._rx is not None:
+            rx = self._rx
+            if kind != "SND" or (sub is not None) + (scope is not None) + (tuned is not None) != 1:
+                raise ValueError("a %s has an SND stream only" % rx.noun)
+            if rx.row()[0] != self.channel:          # KeyError: no such receiver
+                raise ValueError("%s %d listens to %s %d, not %d" % (rx.noun, rx.id, rx.on, rx.row()[0], self.channel))
         if self.scope is not None:
             if kind == "SND" or sub is not None:
                 raise ValueError("a wideband scope has a W/F stream only")
             hub.scope(self.scope)                    # KeyError: no such scope
-        if self.sub is not None:
-            if kind != "SND":
-                raise ValueError("a sub-receiver has an SND stream only")
-            if hub.sub_params(self.sub)[0] != self.channel:
-                raise ValueError("sub-receiver %d listens to channel %d, not %d" % (self.sub, hub.sub_params(self.sub)[0], self.channel))
         self.zoom = self.start = None
         self.seq = 0
         self.closed = False
@@ -1503,7 +1473,7 @@ class GpuStream:
         self._squelch_on = False                     # ... and its squelch
         self._deemp_on = False                       # ... and its de-emphasis
         self._greeting = deque()
-        if self.sub is None and self.scope is None and self.tuned is None and hasattr(hub, "attach"):      # this channel has a listener now: its results are queued from here on
+        if self._rx is None and self.scope is None and hasattr(hub, "attach"):      # this channel has a listener now: its results are queued from here on
             hub.attach(self.channel, wf=(kind != "SND"), snd=(kind == "SND"))
         if kind != "SND" and self.scope is None and hasattr(hub, "_wf_listener_changed"):
             hub._wf_listener_changed(self.channel, +1)
@@ -1523,22 +1493,14 @@ class GpuStream:
         if len(words) < 2 or words[0] != "SET":
             return
         kv = dict(w.split("=", 1) for w in words[1:] if "=" in w)
-        if self.sub is not None:
-            for key in ("nb", "squelch", "de_emp"):
-                if key in kv and "mod" not in kv and "agc" not in kv:
-                    raise ValueError("SET %s= on sub-receiver %d of channel %d: the %s is the channel's, there is none for sub-receivers"
-                                     % (key, self.sub, self.channel, {"nb": "noise blanker", "squelch": "squelch", "de_emp": "de-emphasis"}[key]))
-            if "compression" in kv and "mod" not in kv and "agc" not in kv and int(kv["compression"]) != 0:
-                raise ValueError("SET compression=1 on sub-receiver %d of channel %d: a sub-receiver's frames are not ADPCM-encoded"
-                                 % (self.sub, self.channel))
-        if self.tuned is not None:
-            for key in ("nb", "squelch", "de_emp"):
-                if key in kv and "mod" not in kv and "agc" not in kv:
-                    raise ValueError("SET %s= on tuned receiver %d of wide stream %d: there is no %s for tuned receivers"
-                                     % (key, self.tuned, self.channel, {"nb": "noise blanker", "squelch": "squelch", "de_emp": "de-emphasis"}[key]))
-            if "compression" in kv and "mod" not in kv and "agc" not in kv and int(kv["compression"]) != 0:
-                raise ValueError("SET compression=1 on tuned receiver %d of wide stream %d: a tuned receiver's frames are not ADPCM-encoded"
-                                 % (self.tuned, self.channel))
+        rx = self._rx
+        if rx is not None and "mod" not in kv and "agc" not in kv:       # the channel's stages: an extra receiver has none of them
+            for key, stage in (("nb", "noise blanker"), ("squelch", "squelch"), ("de_emp", "de-emphasis")):
+                if key in kv:
+                    raise ValueError(("SET %s= on %s %d of %s %d: " + rx.no_stage) % (key, rx.noun, rx.id, rx.on, self.channel, stage))
+            if "compression" in kv and int(kv["compression"]) != 0:
+                raise ValueError("SET compression=1 on %s %d of %s %d: a %s's frames are not ADPCM-encoded"
+                                 % (rx.noun, rx.id, rx.on, self.channel, rx.noun))
         if self.scope is not None and "interp" in kv:
             self.hub.set_scope_detector(self.scope, kiwi_interp_detector(kv["interp"]))
             return
@@ -1550,7 +1512,7 @@ class GpuStream:
                              agc_slope=float(kv.get("slope", 0)), agc_decay=float(kv.get("decay", 4000)),
                              agc_man_gain=float(kv.get("manGain", 50)))
             self._set_params(q)
-        elif self.sub is not None or self.tuned is not None:
+        elif rx is not None:
             pass                                     # (compression=0, zoom=, ...: nothing to do for a sub-receiver or a tuned receiver)
         elif "nb" in kv:
             if "th" not in kv:
@@ -1571,17 +1533,13 @@ class GpuStream:
             self.zoom, self.start = int(kv["zoom"]), int(kv.get("start", 0))
 
     def _params(self):
-        if self.tuned is not None:
-            return self.hub.tuned(self.tuned)[2]
-        return self.hub.params(self.channel) if self.sub is None else self.hub.sub_params(self.sub)[1]
+        return self.hub.params(self.channel) if self._rx is None else self._rx.row()[-1]
 
     def _set_params(self, q):
-        if self.tuned is not None:
-            self.hub.set_tuned_params(self.tuned, q)
-        elif self.sub is None:
+        if self._rx is None:
             self.hub.set_params(self.channel, q)
         else:
-            self.hub.set_sub_params(self.sub, q)
+            self._rx.set_params(q)
 
     def _set_squelch(self, kv, msg):
         """both spellings: "squelch=<v> max=<m>" (the NBFM noise squelch) and "squelch=<v> param=<tail_s>" (the RSSI squelch)"""
@@ -1652,9 +1610,8 @@ class GpuStream:
         if self.closed:
             return None
         try:
-            if self.sub is not None or self.tuned is not None:
-                q = self.hub.sub_queue[self.sub] if self.sub is not None else self.hub.tuned_queue[self.tuned]
-                f = q.get(timeout=self.timeout)
+            if self._rx is not None:
+                f = self._rx.queues[self._rx.id].get(timeout=self.timeout)
                 return snd_frame(f, f.rssi, self._next_seq(), adc_overflow=f.adc_overflow)
             if self.kind == "SND":
                 f = self.hub.snd_queue[self.channel].get(timeout=self.timeout)
@@ -1679,14 +1636,13 @@ class GpuStream:
         return self.seq
 
     def close_connection(self, *a, **k):
-        if self.sub is not None and not self.closed:
-            self.hub.close_sub(self.sub)             # the sub-receiver goes with its stream
-        if self.scope is not None and not self.closed:
-            self.hub.close_scope(self.scope)         # ... and so does the scope
-        if self.tuned is not None and not self.closed:
-            self.hub.close_tuned(self.tuned)         # ... and the tuned receiver
+        if self._rx is not None:                     # the extra receiver goes with its stream; nothing of the channel's was this stream's
+            if not self.closed:
+                self._rx.close()
             self.closed = True
             return
+        if self.scope is not None and not self.closed:
+            self.hub.close_scope(self.scope)         # ... and so does a scope
         if self._comp_on and not self.closed:        # the next connection's decoder starts from (0, 0): so does its encoder
             self._comp_on = False
             self.hub.set_compression(self.channel, **{("snd" if self.kind == "SND" else "wf"): False})
@@ -1970,35 +1926,32 @@ class SoundSeams:
         self.error = None                                # set by play_buffer when it has to give up
         self.late_flag = False                           # (the reference creates it in run(); play_buffer reads it)
         self.sub_id = self.tuned_id = None
+        # the listener opened here, if any: what its stream sits on, its keyword for GpuStream, and the hub's close and client slots for it
+        on, kw, rid, close, clients = self.channel, {}, None, None, None
         if tuned:
             if sub:
                 raise ValueError("a kiwi_sound is a sub-receiver or a tuned receiver, not both")
             if wide_center_khz is not None:
                 self.center_khz = float(wide_center_khz)
-            self.tuned_id = self.hub.open_tuned(int(stream), 0.0)
-            self._gpu_stream = GpuStream(self.hub, int(stream), "SND", self.center_khz, timeout, tuned=self.tuned_id)
-            try:
-                with _server_is_the_gpu(self._ref_module, self._gpu_stream):
-                    super().__init__(freq_, mode_, lc_, hc_, password_, kiwi_wf, buffer_len, volume_, host_, port_, subrx_)
-            except Exception:
-                self.hub.close_tuned(self.tuned_id)      # a receiver that could not be tuned does not stay behind
-                raise
-            self.hub.tuned_clients[self.tuned_id] = self
-            return
-        self.sub_id = self.hub.open_sub(self.channel) if sub else None
-        self._gpu_stream = GpuStream(self.hub, self.channel, "SND", self.center_khz, timeout, **({} if self.sub_id is None else {"sub": self.sub_id}))
-        if self.sub_id is None and hasattr(self.hub, "snd_clients"):
+            on = int(stream)
+            rid = self.tuned_id = self.hub.open_tuned(on, 0.0)
+            kw, close, clients = {"tuned": rid}, self.hub.close_tuned, self.hub.tuned_clients
+        elif sub:
+            rid = self.sub_id = self.hub.open_sub(self.channel)
+            kw, close, clients = {"sub": rid}, self.hub.close_sub, self.hub.sub_clients
+        self._gpu_stream = GpuStream(self.hub, on, "SND", self.center_khz, timeout, **kw)
+        if rid is None and hasattr(self.hub, "snd_clients"):
             self.hub.snd_clients[self.channel] = None
         try:
             with _server_is_the_gpu(self._ref_module, self._gpu_stream):
                 # the maintainer's constructor sends "SET mod= ..." and "SET agc= ..." itself (:975-980): the channel is tuned by it
                 super().__init__(freq_, mode_, lc_, hc_, password_, kiwi_wf, buffer_len, volume_, host_, port_, subrx_)
         except Exception:
-            if self.sub_id is not None:              # a sub-receiver that could not be tuned does not stay behind
-                self.hub.close_sub(self.sub_id)
+            if rid is not None:                      # a receiver that could not be tuned does not stay behind
+                close(rid)
             raise
-        if self.sub_id is not None:
-            self.hub.sub_clients[self.sub_id] = self
+        if rid is not None:
+            clients[rid] = self
         elif hasattr(self.hub, "snd_clients"):
             self.hub.snd_clients[self.channel] = self
 

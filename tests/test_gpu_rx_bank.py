@@ -266,3 +266,45 @@ def test_each_bank_keeps_its_own_play_buffer_history(S, pushes):
         assert len(got["both"][bank]) == 2 and _same(got["both"][bank], got[bank][bank]), bank
         assert all(x.shape == (2, 2 * L_, 2) and x.any(axis=(1, 2)).all() for x in got["both"][bank]), bank
     assert not np.array_equal(got["both"]["sub"][1], got["both"]["wb"][1])
+
+
+def test_the_hub_hands_each_family_its_own_rows_of_the_engines_results(S):
+    """a synchronous hub of one wide stream (O = 2) with a sub-receiver, a tuned receiver and a scope open, one feed_wideband: the
+    hub's sub_* / tuned_* / scope_lines are, bit for bit, what the engine's own getters return after the run, and each queue holds
+    its row's frames or lines"""
+    from supersdr_amd.iqstream import Channelizer
+    from supersdr_amd.workers import IQHub
+    n = M * 512
+    rng = np.random.default_rng(51)
+    i = np.arange(n, dtype=np.float64)
+    x = rng.integers(-300, 301, (1, n, 2)).astype(np.float64)
+    ph = 2 * np.pi * ((0.01 * i) % 1.0)                     # a tone 61.44 kHz above the stream's centre: 1440 Hz above row 522's (rows 6 kHz apart)
+    x[0, :, 0] += 4000.0 * np.cos(ph)
+    x[0, :, 1] += 4000.0 * np.sin(ph)
+    iq = np.rint(x).astype(np.int16)
+    hub = IQHub(M, gpu_post=False, lazy=True)
+    try:
+        hub.set_channelizer(Channelizer(2, 4))
+        sid = hub.open_sub(522, S.default_params("usb", f_shift_hz=500.0))
+        tid = hub.open_tuned(0, 61440.0 - 1000.0, S.default_params("usb"))
+        cid = hub.open_scope(0, 0)
+        hub.feed_wideband(iq)
+        r, eng = hub.last, hub.engine
+        assert r.sub_ids == [sid] and r.tuned_ids == [tid] and r.scope_ids == [cid]
+        assert _same((r.sub_pcm, r.sub_rssi, r.sub_flags), eng.subrx_audio())
+        assert _same((r.tuned_pcm, r.tuned_rssi, r.tuned_flags), eng.wb_rx_audio())
+        assert _same((r.scope_lines,), (eng.wb_scope_lines(),))
+        assert r.sub_pcm.shape == (1, 2 * 512) and r.tuned_pcm.shape == (1, 2 * 512) and r.scope_lines.shape[0] == 1 and r.scope_lines.shape[2] == 1024
+        assert r.sub_pcm.any() and r.tuned_pcm.any() and len(r.scope_lines[0]) >= 1 and r.scope_lines.any()
+        assert r.sub_play is None and r.tuned_play is None
+        for q, pcm, rssi, flags in ((hub.sub_queue[sid], r.sub_pcm, r.sub_rssi, r.sub_flags), (hub.tuned_queue[tid], r.tuned_pcm, r.tuned_rssi, r.tuned_flags)):
+            assert q.qsize() == 2
+            for f in range(2):
+                fr = q.get_nowait()
+                assert np.asarray(fr).tobytes() == pcm[0, f * 512:(f + 1) * 512].tobytes() and np.float32(fr.rssi) == rssi[0, f]
+                assert fr.adc_overflow == bool(flags[0, f]) and fr.play_block is None
+        assert hub.scope_queue[cid].qsize() == len(r.scope_lines[0])
+        for line in r.scope_lines[0]:
+            assert np.asarray(hub.scope_queue[cid].get_nowait()).tobytes() == line.tobytes()
+    finally:
+        hub.close()
