@@ -524,8 +524,8 @@ int ssdr_wf_view_stats(ssdr_ctx *ctx, float *total_ms, uint32_t *launches, int r
  * on which somebody listens to a second signal; the list can be replaced while the streams run.  Sub-receiver j on channel c with
  * parameters P produces, bit for bit, the PCM, RSSI, flags and carried state (ssdr_chan_state, raw history) of a channel of a ctx
  * that is fed channel c's IQ and holds P: no new arithmetic (oracle/ssdr_oracle.py:audio_chain, oracle/ssdr_twin.c, the shipped
- * audio kernels).  It sees the input as it came: the channel's noise blanker does not act on it and it has none of its own; nor
- * squelch, de-emphasis, ADPCM or SSDR_MODE_IQ.
+ * audio kernels).  It sees the input as it came: the channel's noise blanker does not act on it and it has none of its own, nor
+ * SSDR_MODE_IQ; squelch, de-emphasis and the SND encoder are its own (ssdr_set_subrx_stages, further down), off until set.
  *   every ssdr_run_audio and every path of ssdr_run_chain (*fused = 0, 1, 2) advances every sub-receiver by the batch;
  *   which kernel the channels get (chain_plan) does not depend on the list, and their results, state and timing are untouched.
  * Kernels: ssdr_audio.hip, ssdr_audio_sub_kernel (12 kHz: one launch, a wave per sub-receiver, all three frame paths) and
@@ -720,8 +720,8 @@ int ssdr_read_wb_scope_windows(ssdr_ctx *ctx, uint32_t index, int16_t *iq_out, u
  * tests/wb_rx_ref.py is the definition; the kernel works in float32 in the scopes' summation order, so a row is bit-identical however
  * the stream is cut into calls and whatever else is in either list.
  * The audio is no new arithmetic: PCM, RSSI, flags and carried state (ssdr_chan_state, raw history) are bit for bit those of a
- * channel of a ctx that is fed the stored row and holds P.  Like a sub-receiver it has no blanker, squelch, de-emphasis, ADPCM or
- * SSDR_MODE_IQ; at D > 1 no parameters that compile to a shift path and no SSDR_MODE_SAM.
+ * channel of a ctx that is fed the stored row and holds P.  Like a sub-receiver it has no blanker and no SSDR_MODE_IQ, and squelch,
+ * de-emphasis and SND encoder of its own (ssdr_set_wb_rx_stages), off until set; at D > 1 no parameters that compile to a shift path and no SSDR_MODE_SAM.
  * State rules (the sub-receivers' for the audio, the scopes' for the DDC):
  *   the DDC carries nothing: a new offset_hz of a kept receiver acts from the next push on and restarts nobody;
  *   a receiver whose (id, stream) is in the old list keeps its audio stream and takes new parameters as ssdr_set_params does; a new
@@ -768,6 +768,66 @@ int ssdr_run_wb_rx_playbuffer(ssdr_ctx *ctx, const ssdr_play_chan *chans, int16_
 /* The stage's runs since the last reset: launches [2] = DDC runs (one per ssdr_push_wideband while a receiver is set), audio runs;
  * with ssdr_set_profiling on their summed times.  Every pointer may be NULL.  ssdr_wb_scope_stats and ssdr_subrx_stats do not move. */
 int ssdr_wb_rx_stats(ssdr_ctx *ctx, float *ddc_ms, float *audio_ms, uint32_t *launches, int reset);
+
+/* -- squelch, de-emphasis and SND compression for the extra receivers (sub-receivers and tuned receivers)
+ *
+ * No new arithmetic.  For every row of either bank the closed flags, the PCM behind the stages, the 256-byte-per-frame ADPCM payload
+ * and the carried stage state (squelch state, de-emphasis S, encoder {index, prev}) are bit for bit those of a channel of an ordinary
+ * ctx that is fed the receiver's input row -- a sub-receiver's: its parent channel's raw IQ; a tuned receiver's: the stored row
+ * ssdr_read_wb_rx returns -- holds the receiver's parameters and the same three settings (ssdr_set_squelch, ssdr_set_deemphasis,
+ * ssdr_set_compression's SND flag) and is run with the same cut of the stream into calls.  Order and rules are the channel's, above:
+ * squelch on the AGC's output (SSDR_MODE_NBFM: the noise squelch; every other mode a bank can hold, SSDR_MODE_SAM included: the RSSI
+ * squelch; a closed frame is zeroed, RSSI and flags stay), then the de-emphasis (a closed frame reaches it as zeros; the acting setting
+ * is picked as for a channel: nfm for SSDR_MODE_NBFM, am for SSDR_MODE_AM and -- as the channels' stage does -- SSDR_MODE_SAM, none for
+ * LSB, USB, CW), then the encoder, whose state is the receiver's own.  tests/squelch_ref.py, tests/deemp_ref.py and tests/adpcm_ref.py
+ * stay the definitions.  ssdr_subrx_audio / ssdr_wb_rx_audio and ssdr_run_subrx_playbuffer / ssdr_run_wb_rx_playbuffer read the PCM
+ * behind the stages, as ssdr_run_audio's copies and ssdr_run_playbuffer do for a channel.  The noise blanker is not part of this: an
+ * extra receiver has none.
+ * Kernel: ssdr_rx_tail.hip, all three stages of the rows with at least one acting stage in ONE launch per bank and run (a wave per
+ * row), on the audio stage's stream behind that bank's audio launch and in front of the channels' squelch / de-emphasis / encoder, so
+ * every call that waits for the audio stage waits for it.  With no acting row nothing is launched; before the first nonzero setting
+ * nothing is allocated; a ctx that never calls the setters launches what it launched before they existed.  No SSDR_K_* slot:
+ * ssdr_rx_tail_stats is the stage's own.  Cost on an MI355X at 16 frames per call with all three stages on every row: 1.07 ms for 1 receiver,
+ * 1.26 ms for 64, 2.52 ms for 256 + 64 (two launches) -- one serial lane's latency over the call's samples per launch, the encoder's table walk
+ * most of it; the channels' three kernels take 1.33 ms for as many channels (profiles/rx_tail_probe.txt).
+ * The feed and checkpoint refusals that any extra receiver causes stand as they are (so the stages never meet a pipelined feed). */
+typedef struct ssdr_rx_stages {
+    ssdr_squelch_params squelch;   /* 16 B: as ssdr_set_squelch takes it */
+    ssdr_deemp_params   deemp;     /*  8 B: as ssdr_set_deemphasis takes it */
+    uint32_t            snd_adpcm; /* 0 off, else on: the receiver's SND frames are encoded too */
+    uint32_t            reserved;  /* 0, else SSDR_EINVAL */
+} ssdr_rx_stages;                  /* 32 B */
+/* The settings of every row of the bank, a parallel array in list order: count must equal the list's length.  SSDR_EINVAL, and then
+ * nothing changes: another count, a value outside the ranges ssdr_set_squelch / ssdr_set_deemphasis accept, a non-zero `reserved`,
+ * NULL with count > 0.  Unlike the channels' setters, which restart every channel they name, a row's stage starts over only if its
+ * setting DIFFERS from the row's current one (squelch: any of the four values; de-emphasis: either value): a row given the setting it
+ * already has keeps its state, so nobody's stream restarts for somebody else's change.  snd_adpcm going 0 -> 1 starts that row's
+ * encoder at (0, 0); one that is already on, or goes off, leaves the state alone.
+ * A list change (ssdr_set_subrx / ssdr_set_wb_rx): settings and stage state follow a receiver across it exactly as its audio state does
+ * -- (id, channel), (id, stream) -- a new receiver starts with everything off and zero state, and a kept receiver whose new parameters
+ * change its MODE has its squelch state and S reset (ssdr_set_params' rule for a channel); the encoder's state stays.  Whatever restarts
+ * a receiver's audio state -- ssdr_reset_state on a sub-receiver's parent channel, ssdr_set_kiwi_rate / ssdr_set_decimation (which also
+ * pick the new rate's coefficient), ssdr_channelizer_reset for the tuned receivers -- resets its squelch state and S and leaves the
+ * encoder's state alone.  An empty list forgets the settings. */
+int ssdr_set_subrx_stages(ssdr_ctx *ctx, const ssdr_rx_stages *st, uint32_t count);
+int ssdr_get_subrx_stages(ssdr_ctx *ctx, ssdr_rx_stages *st /* may be NULL */, uint32_t *count);
+/* The stages' results of the last audio run, rows in list order: closed uint8 [rows][n_frames], 1 = the frame was zeroed; adpcm uint8
+ * [rows][n_frames * 256], low nibble first.  A row whose stage is off (or does not act in the row's mode) is all zero.  Either pointer
+ * may be NULL.  SSDR_ESTATE if the bank is empty, if no row has an acting stage, or if there has been no audio run with list and
+ * settings as they are. */
+int ssdr_subrx_stage_results(ssdr_ctx *ctx, uint8_t *closed, uint8_t *adpcm, int out_is_device);
+/* Carried state of rows [first_row, first_row + count) (tests): deemp_S int32 [count], adpcm_state int32 [count][2] = index, prev; each
+ * may be NULL.  Zero before the first nonzero setting.  SSDR_EINVAL for rows outside the list. */
+int ssdr_get_subrx_stage_state(ssdr_ctx *ctx, uint32_t first_row, uint32_t count, int32_t *deemp_S, int32_t *adpcm_state);
+/* The same four for the tuned receivers. */
+int ssdr_set_wb_rx_stages(ssdr_ctx *ctx, const ssdr_rx_stages *st, uint32_t count);
+int ssdr_get_wb_rx_stages(ssdr_ctx *ctx, ssdr_rx_stages *st /* may be NULL */, uint32_t *count);
+int ssdr_wb_rx_stage_results(ssdr_ctx *ctx, uint8_t *closed, uint8_t *adpcm, int out_is_device);
+int ssdr_get_wb_rx_stage_state(ssdr_ctx *ctx, uint32_t first_row, uint32_t count, int32_t *deemp_S, int32_t *adpcm_state);
+/* The fused launch of one bank (0: sub-receivers, 1: tuned receivers; anything else SSDR_EINVAL): its launches since the last reset,
+ * and with ssdr_set_profiling on their summed time (a HIP-event pair per launch; launches made with profiling off count, and add no
+ * time).  ssdr_subrx_stats and ssdr_wb_rx_stats do not move. */
+int ssdr_rx_tail_stats(ssdr_ctx *ctx, int bank, float *total_ms, uint32_t *launches, int reset);
 
 /* -- pipelined host feed: the path a live ingest takes (KiwiSDRStream._process_iq_samples -> batches, kiwi/client.py:493)
  *

@@ -122,6 +122,15 @@ class WbRx(C.Structure):
 assert C.sizeof(WbRx) == 104
 
 
+class RxStages(C.Structure):
+    """ssdr_rx_stages: squelch, de-emphasis and SND compression of one extra receiver (a row of ssdr_set_subrx_stages /
+    ssdr_set_wb_rx_stages), the settings a channel takes through ssdr_set_squelch / ssdr_set_deemphasis / ssdr_set_compression"""
+    _fields_ = [("squelch", SquelchParams), ("deemp", DeempParams), ("snd_adpcm", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+assert C.sizeof(RxStages) == 32
+
+
 class FeedListen(C.Structure):
     """ssdr_feed_listen: the listener parts of a batch of a SSDR_FEED_LISTEN feed -- counts, the lists latched at its submit, and
     pinned host pointers (NULL for an empty part)"""
@@ -236,6 +245,15 @@ _SIGS = {
     "ssdr_get_wb_rx_sam_carrier": (C.c_int, [_P, C.c_uint32, C.c_uint32, _P, _P]),
     "ssdr_run_wb_rx_playbuffer": (C.c_int, [_P, C.POINTER(PlayChan), _P, C.c_int]),
     "ssdr_wb_rx_stats": (C.c_int, [_P, C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_uint32 * 2), C.c_int]),
+    "ssdr_set_subrx_stages": (C.c_int, [_P, C.POINTER(RxStages), C.c_uint32]),
+    "ssdr_get_subrx_stages": (C.c_int, [_P, C.POINTER(RxStages), C.POINTER(C.c_uint32)]),
+    "ssdr_subrx_stage_results": (C.c_int, [_P, _P, _P, C.c_int]),
+    "ssdr_get_subrx_stage_state": (C.c_int, [_P, C.c_uint32, C.c_uint32, _P, _P]),
+    "ssdr_set_wb_rx_stages": (C.c_int, [_P, C.POINTER(RxStages), C.c_uint32]),
+    "ssdr_get_wb_rx_stages": (C.c_int, [_P, C.POINTER(RxStages), C.POINTER(C.c_uint32)]),
+    "ssdr_wb_rx_stage_results": (C.c_int, [_P, _P, _P, C.c_int]),
+    "ssdr_get_wb_rx_stage_state": (C.c_int, [_P, C.c_uint32, C.c_uint32, _P, _P]),
+    "ssdr_rx_tail_stats": (C.c_int, [_P, C.c_int, C.POINTER(C.c_float), C.POINTER(C.c_uint32), C.c_int]),
     "ssdr_feed_open": (C.c_int, [_P, C.c_uint32, C.c_uint32, C.c_uint32]),
     "ssdr_feed_slot": (C.c_int, [_P, C.POINTER(_P)]),
     "ssdr_feed_submit": (C.c_int, [_P]),
@@ -290,7 +308,9 @@ _NEWER_THAN_AB_LIBS = ("ssdr_feed_collect_listen", "ssdr_set_subrx", "ssdr_get_s
                        "ssdr_wb_scope_taps", "ssdr_wb_scope_stats", "ssdr_set_wb_scope_detectors", "ssdr_get_wb_scope_detectors",
                        "ssdr_wb_scope_windows", "ssdr_read_wb_scope_windows", "ssdr_get_sam_carrier", "ssdr_get_subrx_sam_carrier",
                        "ssdr_set_wb_rx", "ssdr_get_wb_rx", "ssdr_wb_rx_audio", "ssdr_read_wb_rx", "ssdr_get_wb_rx_state", "ssdr_get_wb_rx_consts",
-                       "ssdr_get_wb_rx_sam_carrier", "ssdr_run_wb_rx_playbuffer", "ssdr_wb_rx_stats")      # entry points a library named by SSDR_LIB_PATH (A/B builds only) may predate
+                       "ssdr_get_wb_rx_sam_carrier", "ssdr_run_wb_rx_playbuffer", "ssdr_wb_rx_stats", "ssdr_set_subrx_stages", "ssdr_get_subrx_stages",
+                       "ssdr_subrx_stage_results", "ssdr_get_subrx_stage_state", "ssdr_set_wb_rx_stages", "ssdr_get_wb_rx_stages",
+                       "ssdr_wb_rx_stage_results", "ssdr_get_wb_rx_stage_state", "ssdr_rx_tail_stats")      # entry points a library named by SSDR_LIB_PATH (A/B builds only) may predate
 
 
 def _load():

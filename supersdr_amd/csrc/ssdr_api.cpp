@@ -56,6 +56,8 @@ struct BankOut {
     int16_t *d_pcm = nullptr; size_t pcm_cap = 0;                 // [rows][frames * 512]
     float *d_rssi = nullptr; size_t rssi_cap = 0;                 // [rows][frames]
     uint8_t *d_flags = nullptr; size_t flags_cap = 0;             // [rows][frames]
+    uint8_t *d_closed = nullptr; size_t closed_cap = 0;           // [rows][frames] the tail's closed flags (ssdr_set_subrx_stages / _wb_rx_stages)
+    uint8_t *d_adpcm = nullptr; size_t adpcm_cap = 0;             // [rows][frames * 256] ... and its SND payloads; capacity in frames
     uint32_t run_rows = 0, run_frames = 0;                        // extent of the last run
 };
 struct Batch {
@@ -98,7 +100,9 @@ constexpr int kTimedChan = SSDR_K_COUNT + 3;            // the wideband channeli
 constexpr int kTimedScope = SSDR_K_COUNT + 4;           // the wideband scopes (ssdr_wb_scope_stats)
 constexpr int kTimedWbRxDdc = SSDR_K_COUNT + 5;         // the tuned receivers' DDC and their audio (ssdr_wb_rx_stats)
 constexpr int kTimedWbRxAudio = SSDR_K_COUNT + 6;
-constexpr int kTimedCount = SSDR_K_COUNT + 7;
+constexpr int kTimedSubTail = SSDR_K_COUNT + 7;         // the banks' fused squelch / de-emphasis / encoder launch (ssdr_rx_tail_stats)
+constexpr int kTimedWbRxTail = SSDR_K_COUNT + 8;
+constexpr int kTimedCount = SSDR_K_COUNT + 9;
 
 // A bank of extra receivers: audio chains that are no channels, rows in list order, run by the sub-receivers' kernels behind the
 // channels' audio stage.  The ctx holds two -- the sub-receivers (ssdr_set_subrx: each reads a channel's row of the input) and the
@@ -107,6 +111,7 @@ constexpr int kTimedCount = SSDR_K_COUNT + 7;
 struct RxBank {
     const uint32_t cap;                                 // rows the arrays hold: SSDR_SUBRX_MAX, SSDR_WB_RX_MAX
     const int timed;                                    // the kTimed* slot its audio launch is timed in
+    const int timed_tail;                               // ... and the one of its tail (ssdr_rx_tail.hip)
     std::vector<ssdr_chan_consts> h_consts;             // [rows] mirror of d_consts: compiled from the list's parameters
     std::vector<uint8_t> h_started;                     // [rows] the receiver has run since it was created or restarted
     bool run_valid = false;                             // the last audio run was the ctx's own batch's, with the list as it is
@@ -121,6 +126,17 @@ struct RxBank {
     ssdr_play_chan *d_play = nullptr;                   // [cap]
     int16_t *d_play_out = nullptr;
     size_t play_cap = 0;                                // rows * frames d_play_out holds
+    // squelch, de-emphasis and SND encoder of the rows (ssdr_set_subrx_stages / ssdr_set_wb_rx_stages): host settings at the first call,
+    // device memory at the first nonzero setting; with no acting row nothing is launched
+    std::vector<ssdr_rx_stages> h_st;                   // [rows] as set (empty: never set -- everything off)
+    uint32_t st_set_n = 0;                              // rows with a nonzero setting, acting or not
+    std::vector<SsdrRxTailRow> h_tail;                  // the rows with an acting stage, ascending (mirror of d_tail)
+    bool tail_dirty = false;                            // settings, modes or the rate changed since the list was made
+    bool st_valid = false;                              // the last audio run was the ctx's own batch's, with list and settings as they are
+    SsdrSquelchChan *d_sq = nullptr;                    // [cap] settings + carried state, as a channel's
+    int32_t *d_de = nullptr;                            // [cap] S
+    int32_t *d_enc = nullptr;                           // [cap][2] the encoder's (index, prev)
+    SsdrRxTailRow *d_tail = nullptr;                    // [cap]
     uint32_t rows() const { return (uint32_t)h_consts.size(); }
 };
 
@@ -335,7 +351,7 @@ struct ssdr_ctx {
     size_t wv_wf_rows = 0;
     // sub-receivers (ssdr_set_subrx): device memory at the first one; with none set nothing is launched
     std::vector<ssdr_subrx> h_sub;                      // the list as set, ids ascending
-    RxBank sub{SSDR_SUBRX_MAX, kTimedSubRx};            // their rows: the parents are the list's channels, uploaded with every list
+    RxBank sub{SSDR_SUBRX_MAX, kTimedSubRx, kTimedSubTail};   // their rows: the parents are the list's channels, uploaded with every list
     // wideband channeliser (ssdr_set_channelizer): device memory at the first one set; with none set nothing is launched
     uint32_t chz_streams = 0, chz_over = 1, chz_p = 0;  // streams (0: none set), O, P
     std::vector<float> h_chz_taps;                      // [P * 1024] the prototype as set
@@ -368,7 +384,7 @@ struct ssdr_ctx {
     // tuned receivers (ssdr_set_wb_rx): device memory at the first one; with none set nothing is launched.  The rings are the scopes'
     // (h_ws_streams: the streams EITHER list names), the tap tables too
     std::vector<ssdr_wb_rx> h_wr;                       // the list as set, ids ascending
-    RxBank wr{SSDR_WB_RX_MAX, kTimedWbRxAudio};         // their audio rows: the parents are 0, 1, 2, .., written once (wbrx_alloc); run_valid: an audio run on the rows below
+    RxBank wr{SSDR_WB_RX_MAX, kTimedWbRxAudio, kTimedWbRxTail};   // their audio rows: the parents are 0, 1, 2, .., written once (wbrx_alloc); run_valid: an audio run on the rows below
     bool wr_rows_valid = false;                         // the own batch's input is an ssdr_push_wideband's with the list as it is
     SsdrWbScope *d_wr_list = nullptr;                   // [SSDR_WB_RX_MAX] the receivers as the DDC sees them (uploaded with the scopes': ws_dirty)
 };
@@ -396,13 +412,15 @@ static void free_owned(ssdr_ctx *c)
         c->d_de_state, c->d_de_list,                                                                                  // de-emphasis
         c->d_wv[0], c->d_wv[1], c->d_wv_hist[0], c->d_wv_hist[1], c->d_wv_carry[0], c->d_wv_carry[1], c->d_wv_tail[0], c->d_wv_tail[1],
         c->d_wv_taps, c->d_wv_consts, c->d_wv_acc, c->d_wv_stream, c->d_wv_wf,                                        // waterfall views
-        c->own.sub.d_pcm, c->own.sub.d_rssi, c->own.sub.d_flags,                                                      // sub-receivers: the own batch's results,
+        c->own.sub.d_pcm, c->own.sub.d_rssi, c->own.sub.d_flags, c->own.sub.d_closed, c->own.sub.d_adpcm,             // sub-receivers: the own batch's results,
+        c->sub.d_sq, c->sub.d_de, c->sub.d_enc, c->sub.d_tail,                                                        // ... their tail's state,
         c->sub.d_state[0], c->sub.d_state[1], c->sub.d_hist[0], c->sub.d_hist[1], c->sub.d_phist[0], c->sub.d_phist[1], c->sub.d_phist_alt,
         c->sub.d_consts, c->sub.d_taps, c->sub.d_parent, c->sub.d_play, c->sub.d_play_out,                            // ... their bank: state, constants, play_buffer
         c->d_chz_taps, c->d_chz_hist, c->d_chz_in,                                                                    // wideband channeliser
         c->d_ws_taps, c->d_ws_scopes, c->d_ws_slot_stream, c->d_ws_hist, c->d_ws_out, c->d_ws_lines, c->d_ws_acc, c->d_ws_consts,   // wideband scopes
         c->d_wd_win, c->d_wd_part,                                                                                    // ... their detectors' scratch
-        c->own.d_wr_rows, c->own.wr.d_pcm, c->own.wr.d_rssi, c->own.wr.d_flags,                                       // tuned receivers: the own batch's rows and results,
+        c->own.d_wr_rows, c->own.wr.d_pcm, c->own.wr.d_rssi, c->own.wr.d_flags, c->own.wr.d_closed, c->own.wr.d_adpcm, // tuned receivers: the own batch's rows and results,
+        c->wr.d_sq, c->wr.d_de, c->wr.d_enc, c->wr.d_tail,                                                            // ... their tail's state,
         c->d_wr_list, c->wr.d_state[0], c->wr.d_state[1], c->wr.d_hist[0], c->wr.d_hist[1], c->wr.d_phist[0], c->wr.d_phist[1], c->wr.d_phist_alt,
         c->wr.d_consts, c->wr.d_taps, c->wr.d_parent, c->wr.d_play, c->wr.d_play_out,                                 // ... their bank: state, constants, play_buffer
     };
@@ -472,7 +490,7 @@ template <class F> static int stage_launch(ssdr_ctx *c, int which, hipStream_t s
     c->stage[which - SSDR_K_COUNT].launches++;
     return SSDR_OK;
 }
-// behind the five ssdr_*_stats entry points of those stages
+// behind the ssdr_*_stats entry points of those stages
 static int stage_stats(ssdr_ctx *c, int which, float *total_ms, uint32_t *launches, int reset)
 {
     if (!c) return SSDR_EINVAL;
@@ -613,6 +631,12 @@ static int sam_loop_zero(ssdr_ctx *c, ssdr_chan_state *d_rows, size_t n)
 
 
 // ---- a bank of extra receivers (RxBank): every step of the sub-receivers' and the tuned receivers' host side, said once ----------------
+// the bank's tail (squelch, de-emphasis, SND encoder: further down, behind the channels' three stages), where the steps below meet it
+static int bank_tail_fresh(ssdr_ctx *c, RxBank &bk, const std::vector<uint32_t> &rows, bool squelch, bool deemp, bool encoder);
+static int bank_tail_follow(ssdr_ctx *c, RxBank &bk, const std::vector<int32_t> &kept, const std::vector<ssdr_chan_consts> &k);
+static void bank_tail_clear(RxBank &bk);
+static int bank_tail_prepare(ssdr_ctx *c, RxBank &bk, Batch &b, BankOut &out);
+static int bank_tail_launch(ssdr_ctx *c, RxBank &bk, Batch &b, BankOut &out, hipStream_t s);
 // the state arrays (two sets: a new list is built in the other one, so that a receiver that stays keeps its stream), constants, parents
 static int bank_alloc(ssdr_ctx *c, RxBank &bk)
 {
@@ -643,6 +667,7 @@ static void bank_clear(RxBank &bk)
     bk.h_consts.clear();
     bk.h_started.clear();
     bk.run_valid = false;
+    bank_tail_clear(bk);
 }
 static bool every_row(uint32_t) { return true; }
 // the rows that `selected(row)` names start over; the stream is waited for only if there was one
@@ -651,16 +676,16 @@ template <class F> static int bank_restart(ssdr_ctx *c, RxBank &bk, F selected)
     if (!bk.rows()) return SSDR_OK;
     SSDR_TRY(join_audio(c));
     std::vector<ssdr_chan_state> fresh(bk.rows());
-    bool any = false;
+    std::vector<uint32_t> rows;
     for (uint32_t j = 0; j < bk.rows(); j++) {
         if (!selected(j)) continue;
         fresh[j] = fresh_state(bk.h_consts[j]);
         SSDR_TRY(bank_silence(c, bk, bk.set, j, &fresh[j]));
         bk.h_started[j] = 0;
-        any = true;
+        rows.push_back(j);
     }
-    if (any) HIP_TRY(hipStreamSynchronize(c->stream));
-    return SSDR_OK;
+    if (!rows.empty()) HIP_TRY(hipStreamSynchronize(c->stream));
+    return bank_tail_fresh(c, bk, rows, true, true, false);     // their squelch state and S as well, as a channel's; the encoder is the link's
 }
 // the sub-receivers of channels [first, first + count) start over (ssdr_reset_state)
 static int subrx_restart(ssdr_ctx *c, uint32_t first, uint32_t count)
@@ -685,6 +710,7 @@ static int bank_install(ssdr_ctx *c, RxBank &bk, const std::vector<ssdr_chan_con
     SSDR_TRY(bank_upload_consts(c, bk, k, taps));
     bk.h_consts = k;
     bk.run_valid = false;
+    bk.tail_dirty = true;                                       // (the de-emphasis coefficients are the rate's)
     return bank_restart(c, bk, every_row);
 }
 // room for the results of the run, before anything of it is launched
@@ -697,7 +723,8 @@ static int bank_prepare(ssdr_ctx *c, RxBank &bk, Batch &b, BankOut &out)
     if (out.pcm_cap < need || out.rssi_cap < need || out.flags_cap < need) SSDR_TRY(drain_audio(c));
     SSDR_TRY(grow(c, b, out.d_pcm, out.pcm_cap, need, SSDR_FRAME * sizeof(int16_t)));
     SSDR_TRY(grow(c, b, out.d_rssi, out.rssi_cap, need, sizeof(float)));
-    return grow(c, b, out.d_flags, out.flags_cap, need, 1);
+    SSDR_TRY(grow(c, b, out.d_flags, out.flags_cap, need, 1));
+    return bank_tail_prepare(c, bk, b, out);
 }
 // Every receiver of the bank advanced by the batch, on the audio stage's stream `s` behind the channels' kernels: one launch, timed
 // with the bank's own event pair; not an SSDR_K_* slot.  `au`: the audio stage's arguments (the extent; rows of the channels' length),
@@ -727,7 +754,7 @@ static int bank_launch(ssdr_ctx *c, RxBank &bk, Batch &b, BankOut &out, const Ss
     out.run_rows = n;
     out.run_frames = b.in_frames;
     bk.run_valid = &b == &c->own;
-    return SSDR_OK;
+    return bank_tail_launch(c, bk, b, out, s);
 }
 // A new list of `count` rows, compiled to (k, taps), takes the bank over.  It is built in the other set of state arrays: a receiver
 // that stays -- same(old row, new row): the family's notion of "the same receiver", ids ascending in both lists -- is copied there
@@ -742,12 +769,14 @@ static int bank_rebuild(ssdr_ctx *c, RxBank &bk, const std::vector<T> &old, cons
     const int from = bk.set, to = from ^ 1;
     std::vector<ssdr_chan_state> fresh(count);
     std::vector<uint8_t> started(count, 0);
+    std::vector<int32_t> kept(count, -1);                  // the old row of every receiver that stays
     *same_rows = old.size() == count;
     size_t i = 0;
     for (uint32_t j = 0; j < count; j++) {
         while (i < old.size() && old[i].id < list[j].id) i++;
         const bool stays = i < old.size() && old[i].id == list[j].id && same(old[i], list[j]);
         *same_rows = *same_rows && stays && i == j;
+        if (stays) kept[j] = (int32_t)i;
         if (stays && bk.h_started[i]) {
             const hipMemcpyKind d2d = hipMemcpyDeviceToDevice;
             HIP_TRY(hipMemcpyAsync(bk.d_state[to] + j, bk.d_state[from] + i, sizeof(ssdr_chan_state), d2d, c->stream));
@@ -762,6 +791,7 @@ static int bank_rebuild(ssdr_ctx *c, RxBank &bk, const std::vector<T> &old, cons
     }
     if (parent) HIP_TRY(hipMemcpyAsync(bk.d_parent, parent, count * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
     SSDR_TRY(bank_upload_consts(c, bk, k, taps));           // (waits: `fresh` and `parent` are host memory)
+    SSDR_TRY(bank_tail_follow(c, bk, kept, k));             // settings and stage state go with the receivers (bk.h_consts: still the old modes)
     bk.h_consts = k;
     bk.h_started = started;
     bk.set = to;
@@ -1523,17 +1553,25 @@ static inline bool squelch_acts(const ssdr_squelch_params &q, uint32_t mode)
     if (mode == SSDR_MODE_IQ) return false;
     return mode == SSDR_MODE_NBFM ? q.fm_level != 0 : q.rssi_level != 0;
 }
+// a channel's (or an extra receiver's) device record with the settings `p` and the state a reset leaves: open, nothing stored
+static SsdrSquelchChan squelch_fresh(const ssdr_squelch_params &p)
+{
+    SsdrSquelchChan q;
+    memset(&q, 0, sizeof q);
+    q.fm_level = p.fm_level; q.fm_max = p.fm_max; q.rssi_level = p.rssi_level; q.tail_frames = p.tail_frames;
+    q.open = 1u;
+    return q;
+}
+static inline bool squelch_in_range(const ssdr_squelch_params &p)
+{
+    return p.fm_level <= 99 && p.fm_max <= 65535 && p.rssi_level <= 99 && p.tail_frames <= 1024;
+}
 // the settings of channels [first, first + count) as set, their state started over
 static int squelch_upload(ssdr_ctx *c, uint32_t first, uint32_t count)
 {
     if (!c->d_sq || !count) return SSDR_OK;
     std::vector<SsdrSquelchChan> q(count);
-    for (uint32_t i = 0; i < count; i++) {
-        memset(&q[i], 0, sizeof q[i]);
-        const ssdr_squelch_params &p = c->h_sq[first + i];
-        q[i].fm_level = p.fm_level; q[i].fm_max = p.fm_max; q[i].rssi_level = p.rssi_level; q[i].tail_frames = p.tail_frames;
-        q[i].open = 1u;
-    }
+    for (uint32_t i = 0; i < count; i++) q[i] = squelch_fresh(c->h_sq[first + i]);
     SSDR_TRY(join_audio(c));
     HIP_TRY(hipMemcpyAsync(c->d_sq + first, q.data(), count * sizeof(SsdrSquelchChan), hipMemcpyHostToDevice, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
@@ -1656,6 +1694,230 @@ static int audio_tail_launch(ssdr_ctx *c, Batch &b, hipStream_t s)
     SSDR_TRY(squelch_launch(c, b, s));
     SSDR_TRY(deemp_launch(c, b, s));
     return adpcm_snd_launch(c, b, s);
+}
+
+// ---- the banks' tail: the same three stages for a bank of extra receivers, one launch (ssdr_rx_tail.hip; ssdr_set_subrx_stages / _wb_rx_stages)
+static inline bool stages_any(const ssdr_rx_stages &t)
+{
+    return t.squelch.fm_level || t.squelch.rssi_level || t.deemp.am || t.deemp.nfm || t.snd_adpcm;
+}
+static inline bool squelch_same(const ssdr_squelch_params &a, const ssdr_squelch_params &b)
+{
+    return a.fm_level == b.fm_level && a.fm_max == b.fm_max && a.rssi_level == b.rssi_level && a.tail_frames == b.tail_frames;
+}
+// the first nonzero setting: state of every row the arrays can hold as after a reset, everything off
+static int bank_tail_alloc(ssdr_ctx *c, RxBank &bk)
+{
+    if (bk.d_sq && bk.d_de && bk.d_enc && bk.d_tail) return SSDR_OK;
+    SSDR_TRY(join_audio(c));
+    const size_t n = bk.cap;
+    if (!bk.d_sq) HIP_TRY(hipMalloc(&bk.d_sq, n * sizeof(SsdrSquelchChan)));
+    if (!bk.d_de) HIP_TRY(hipMalloc(&bk.d_de, n * sizeof(int32_t)));
+    if (!bk.d_enc) HIP_TRY(hipMalloc(&bk.d_enc, n * 2 * sizeof(int32_t)));
+    if (!bk.d_tail) HIP_TRY(hipMalloc(&bk.d_tail, n * sizeof(SsdrRxTailRow)));
+    const std::vector<SsdrSquelchChan> q(n, squelch_fresh(ssdr_squelch_params{0u, 0u, 0u, 0u}));
+    HIP_TRY(hipMemcpyAsync(bk.d_sq, q.data(), n * sizeof(SsdrSquelchChan), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemsetAsync(bk.d_de, 0, n * sizeof(int32_t), c->stream));
+    HIP_TRY(hipMemsetAsync(bk.d_enc, 0, n * 2 * sizeof(int32_t), c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return SSDR_OK;
+}
+// the named stages of `rows` start over with the settings the rows hold; there when the call returns.  Before the first nonzero
+// setting there is nothing to start over.
+static int bank_tail_fresh(ssdr_ctx *c, RxBank &bk, const std::vector<uint32_t> &rows, bool squelch, bool deemp, bool encoder)
+{
+    if (rows.empty() || !bk.d_sq || bk.h_st.empty()) return SSDR_OK;
+    SSDR_TRY(join_audio(c));
+    std::vector<SsdrSquelchChan> q(rows.size());
+    for (size_t i = 0; i < rows.size(); i++) {
+        const uint32_t j = rows[i];
+        if (squelch) {
+            q[i] = squelch_fresh(bk.h_st[j].squelch);
+            HIP_TRY(hipMemcpyAsync(bk.d_sq + j, &q[i], sizeof q[i], hipMemcpyHostToDevice, c->stream));
+        }
+        if (deemp) HIP_TRY(hipMemsetAsync(bk.d_de + j, 0, sizeof(int32_t), c->stream));
+        if (encoder) HIP_TRY(hipMemsetAsync(bk.d_enc + 2 * (size_t)j, 0, 2 * sizeof(int32_t), c->stream));
+    }
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return SSDR_OK;
+}
+static void bank_tail_clear(RxBank &bk)
+{
+    bk.h_st.clear();
+    bk.h_tail.clear();
+    bk.st_set_n = 0;
+    bk.tail_dirty = false;
+    bk.st_valid = false;
+}
+// A new list takes the bank over (bank_rebuild, before the bank's constants become the new ones): row j of it is old row kept[j], or
+// a new receiver (-1).  Settings and stage state follow a kept receiver; one whose mode changes has its squelch state and S reset, the
+// channel's rule on ssdr_set_params, and keeps its encoder; a new one has everything off and zero state.  A list change is no hot
+// path: the state makes a round trip through the host.
+static int bank_tail_follow(ssdr_ctx *c, RxBank &bk, const std::vector<int32_t> &kept, const std::vector<ssdr_chan_consts> &k)
+{
+    if (bk.h_st.empty()) return SSDR_OK;                    // never set: everybody is off, and stays so
+    const size_t n_old = bk.h_st.size(), n = kept.size();
+    const ssdr_rx_stages off = {{0u, 0u, 0u, 0u}, {0u, 0u}, 0u, 0u};
+    std::vector<ssdr_rx_stages> st(n, off);
+    for (size_t j = 0; j < n; j++)
+        if (kept[j] >= 0) st[j] = bk.h_st[(size_t)kept[j]];
+    if (bk.d_sq) {
+        SSDR_TRY(join_audio(c));
+        std::vector<SsdrSquelchChan> sq_old(n_old), sq(n);
+        std::vector<int32_t> de_old(n_old), de(n, 0), enc_old(2 * n_old), enc(2 * n, 0);
+        SSDR_TRY(copy_out(c, sq_old.data(), bk.d_sq, n_old * sizeof(SsdrSquelchChan), 0, kSyncLater));
+        SSDR_TRY(copy_out(c, de_old.data(), bk.d_de, n_old * sizeof(int32_t), 0, kSyncLater));
+        SSDR_TRY(copy_out(c, enc_old.data(), bk.d_enc, 2 * n_old * sizeof(int32_t), 0, kSyncAlways));
+        for (size_t j = 0; j < n; j++) {
+            const int32_t i = kept[j];
+            const bool same_mode = i >= 0 && bk.h_consts[(size_t)i].mode == k[j].mode;
+            sq[j] = same_mode ? sq_old[(size_t)i] : squelch_fresh(st[j].squelch);
+            if (same_mode) de[j] = de_old[(size_t)i];
+            if (i >= 0) { enc[2 * j] = enc_old[2 * (size_t)i]; enc[2 * j + 1] = enc_old[2 * (size_t)i + 1]; }
+        }
+        HIP_TRY(hipMemcpyAsync(bk.d_sq, sq.data(), n * sizeof(SsdrSquelchChan), hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(hipMemcpyAsync(bk.d_de, de.data(), n * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(hipMemcpyAsync(bk.d_enc, enc.data(), 2 * n * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(hipStreamSynchronize(c->stream));
+    }
+    bk.h_st = st;
+    bk.st_set_n = 0;
+    for (const ssdr_rx_stages &t : st) bk.st_set_n += stages_any(t) ? 1u : 0u;
+    bk.tail_dirty = true;
+    bk.st_valid = false;
+    return SSDR_OK;
+}
+// the list of the rows with an acting stage up to date, and room for the results of an audio run of the current batch
+static int bank_tail_prepare(ssdr_ctx *c, RxBank &bk, Batch &b, BankOut &out)
+{
+    bk.st_valid = false;
+    if (!bk.st_set_n && !bk.tail_dirty) return SSDR_OK;
+    if (bk.tail_dirty) {
+        bk.h_tail.clear();
+        for (uint32_t j = 0; bk.st_set_n && j < bk.rows(); j++) {
+            const ssdr_rx_stages &t = bk.h_st[j];
+            const uint32_t mode = bk.h_consts[j].mode;
+            SsdrRxTailRow r;
+            r.row = j;
+            r.squelch = !squelch_acts(t.squelch, mode) ? SSDR_RX_TAIL_OFF : mode == SSDR_MODE_NBFM ? SSDR_RX_TAIL_NOISE : SSDR_RX_TAIL_RSSI;
+            const uint32_t setting = deemp_acting(t.deemp, mode);
+            r.coef = setting ? deemp_coeff(setting, c->kiwi_rate) : 0u;
+            r.adpcm = t.snd_adpcm ? 1u : 0u;
+            if (r.squelch || r.coef || r.adpcm) bk.h_tail.push_back(r);
+        }
+        if (!bk.h_tail.empty()) {
+            SSDR_TRY(join_audio(c));
+            HIP_TRY(hipMemcpyAsync(bk.d_tail, bk.h_tail.data(), bk.h_tail.size() * sizeof(SsdrRxTailRow), hipMemcpyHostToDevice, c->stream));
+            HIP_TRY(hipStreamSynchronize(c->stream));
+        }
+        bk.tail_dirty = false;
+    }
+    if (bk.h_tail.empty()) return SSDR_OK;
+    const size_t need = (size_t)bk.rows() * b.in_frames;
+    if (out.closed_cap < need || out.adpcm_cap < need) SSDR_TRY(drain_audio(c));
+    SSDR_TRY(grow(c, b, out.d_closed, out.closed_cap, need, 1));
+    return grow(c, b, out.d_adpcm, out.adpcm_cap, need, SSDR_FRAME / 2);
+}
+// the three stages on the bank's audio just queued on `s`, behind it on the same stream: one launch, timed with its own event pair
+static int bank_tail_launch(ssdr_ctx *c, RxBank &bk, Batch &b, BankOut &out, hipStream_t s)
+{
+    if (bk.h_tail.empty()) return SSDR_OK;
+    SsdrRxTailArgs t;
+    t.pcm = out.d_pcm;
+    t.rssi = out.d_rssi;
+    t.n_frames = b.in_frames;
+    t.list = bk.d_tail;
+    t.list_n = (uint32_t)bk.h_tail.size();
+    t.sq = bk.d_sq;
+    t.de_state = bk.d_de;
+    t.enc_state = bk.d_enc;
+    t.closed = out.d_closed;
+    t.adpcm = out.d_adpcm;
+    SSDR_TRY(stage_launch(c, bk.timed_tail, s, [&]() -> int { HIP_TRY(ssdr_launch_rx_tail(t, s)); return SSDR_OK; }));
+    bk.st_valid = &b == &c->own;
+    return SSDR_OK;
+}
+// behind ssdr_set_subrx_stages / ssdr_set_wb_rx_stages: all or nothing; a stage whose setting differs starts over, every other keeps its state
+static int bank_set_stages(ssdr_ctx *c, RxBank &bk, const ssdr_rx_stages *st, uint32_t count)
+{
+    if (count != bk.rows() || (count && !st)) return SSDR_EINVAL;
+    bool any = false;
+    for (uint32_t j = 0; j < count; j++) {
+        if (!squelch_in_range(st[j].squelch) || st[j].deemp.am > 2 || st[j].deemp.nfm > 2 || st[j].reserved) return SSDR_EINVAL;
+        any = any || stages_any(st[j]);
+    }
+    if (!count) return SSDR_OK;
+    HIP_TRY(hipSetDevice(c->device));
+    if (any) SSDR_TRY(bank_tail_alloc(c, bk));
+    const ssdr_rx_stages off = {{0u, 0u, 0u, 0u}, {0u, 0u}, 0u, 0u};
+    if (bk.h_st.empty()) bk.h_st.assign(count, off);
+    std::vector<uint32_t> sq_rows, de_rows, enc_rows;
+    bool changed = false;
+    for (uint32_t j = 0; j < count; j++) {
+        ssdr_rx_stages &was = bk.h_st[j];
+        if (!squelch_same(was.squelch, st[j].squelch)) sq_rows.push_back(j);
+        if (was.deemp.am != st[j].deemp.am || was.deemp.nfm != st[j].deemp.nfm) de_rows.push_back(j);
+        if (!was.snd_adpcm && st[j].snd_adpcm) enc_rows.push_back(j);       // 0 -> 1: a new decoder starts at (0, 0)
+        changed = changed || !squelch_same(was.squelch, st[j].squelch) || was.deemp.am != st[j].deemp.am || was.deemp.nfm != st[j].deemp.nfm ||
+                  (was.snd_adpcm != 0) != (st[j].snd_adpcm != 0);
+        bk.st_set_n = bk.st_set_n - (stages_any(was) ? 1u : 0u) + (stages_any(st[j]) ? 1u : 0u);
+        was = st[j];
+    }
+    if (!changed) return SSDR_OK;
+    bk.tail_dirty = true;
+    bk.st_valid = false;
+    SSDR_TRY(bank_tail_fresh(c, bk, sq_rows, true, false, false));
+    SSDR_TRY(bank_tail_fresh(c, bk, de_rows, false, true, false));
+    return bank_tail_fresh(c, bk, enc_rows, false, false, true);
+}
+static int bank_get_stages(const RxBank &bk, ssdr_rx_stages *st, uint32_t *count)
+{
+    if (!count) return SSDR_EINVAL;
+    *count = bk.rows();
+    const ssdr_rx_stages off = {{0u, 0u, 0u, 0u}, {0u, 0u}, 0u, 0u};
+    for (uint32_t j = 0; st && j < bk.rows(); j++) st[j] = bk.h_st.empty() ? off : bk.h_st[j];
+    return SSDR_OK;
+}
+// one result of the last run, `unit` bytes per row and frame, to the caller: the rows whose stage acts (on[row]) as the kernel wrote
+// them, every other row zero
+static int bank_stage_rows(ssdr_ctx *c, const BankOut &out, const uint8_t *d_src, const std::vector<uint8_t> &on, size_t unit, uint8_t *dst, int out_is_device)
+{
+    const size_t row = (size_t)out.run_frames * unit;
+    SSDR_TRY(copy_out(c, dst, d_src, on.size() * row, out_is_device, kSyncAlways));
+    for (size_t j = 0; j < on.size(); j++) {
+        if (on[j]) continue;
+        if (out_is_device) HIP_TRY(hipMemsetAsync(dst + j * row, 0, row, c->stream));
+        else memset(dst + j * row, 0, row);
+    }
+    if (out_is_device) HIP_TRY(hipStreamSynchronize(c->stream));
+    return SSDR_OK;
+}
+static int bank_stage_results(ssdr_ctx *c, const RxBank &bk, const BankOut &out, uint8_t *closed, uint8_t *adpcm, int out_is_device)
+{
+    if (!bk.rows() || bk.tail_dirty || bk.h_tail.empty() || !bk.run_valid || !bk.st_valid) return SSDR_ESTATE;
+    HIP_TRY(hipSetDevice(c->device));
+    SSDR_TRY(join_audio(c));
+    std::vector<uint8_t> sq_on(out.run_rows, 0), enc_on(out.run_rows, 0);
+    for (const SsdrRxTailRow &r : bk.h_tail) { sq_on[r.row] = r.squelch != 0; enc_on[r.row] = r.adpcm != 0; }
+    if (closed) SSDR_TRY(bank_stage_rows(c, out, out.d_closed, sq_on, 1, closed, out_is_device));
+    if (adpcm) SSDR_TRY(bank_stage_rows(c, out, out.d_adpcm, enc_on, SSDR_FRAME / 2, adpcm, out_is_device));
+    return SSDR_OK;
+}
+static int bank_stage_state(ssdr_ctx *c, const RxBank &bk, uint32_t first_row, uint32_t count, int32_t *S, int32_t *enc)
+{
+    if ((uint64_t)first_row + count > bk.rows()) return SSDR_EINVAL;
+    if (!count) return SSDR_OK;
+    if (!bk.d_de) {                                         // nothing has ever been on
+        if (S) memset(S, 0, (size_t)count * sizeof(int32_t));
+        if (enc) memset(enc, 0, (size_t)count * 2 * sizeof(int32_t));
+        return SSDR_OK;
+    }
+    HIP_TRY(hipSetDevice(c->device));
+    SSDR_TRY(join_audio(c));
+    if (S) SSDR_TRY(copy_out(c, S, bk.d_de + first_row, (size_t)count * sizeof(int32_t), 0, kSyncLater));
+    if (enc) SSDR_TRY(copy_out(c, enc, bk.d_enc + 2 * (size_t)first_row, (size_t)count * 2 * sizeof(int32_t), 0, kSyncLater));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return SSDR_OK;
 }
 
 // ---- waterfall views: a per-channel zoom stage beside the waterfall stage (ssdr_set_wf_views) ---------------------------------
@@ -3396,7 +3658,7 @@ int ssdr_set_squelch(ssdr_ctx *c, uint32_t first, uint32_t count, const ssdr_squ
 {
     if (!c || (uint64_t)first + count > c->n_ch || (count && !p)) return SSDR_EINVAL;
     for (uint32_t i = 0; i < count; i++)                    // all or nothing: every channel is checked before any is changed
-        if (p[i].fm_level > 99 || p[i].fm_max > 65535 || p[i].rssi_level > 99 || p[i].tail_frames > 1024) return SSDR_EINVAL;
+        if (!squelch_in_range(p[i])) return SSDR_EINVAL;
     if (!c->feed.empty() && !c->feed_listen) return SSDR_ESTATE;
     if (!count) return SSDR_OK;
     HIP_TRY(hipSetDevice(c->device));
@@ -3729,6 +3991,32 @@ int ssdr_run_subrx_playbuffer(ssdr_ctx *c, const ssdr_play_chan *chans, int16_t 
 int ssdr_subrx_stats(ssdr_ctx *c, float *total_ms, uint32_t *launches, int reset) SSDR_GUARD
 {
     return stage_stats(c, kTimedSubRx, total_ms, launches, reset);
+} SSDR_UNGUARD
+
+int ssdr_set_subrx_stages(ssdr_ctx *c, const ssdr_rx_stages *st, uint32_t count) SSDR_GUARD
+{
+    return c ? bank_set_stages(c, c->sub, st, count) : SSDR_EINVAL;
+} SSDR_UNGUARD
+
+int ssdr_get_subrx_stages(ssdr_ctx *c, ssdr_rx_stages *st, uint32_t *count) SSDR_GUARD
+{
+    return c ? bank_get_stages(c->sub, st, count) : SSDR_EINVAL;
+} SSDR_UNGUARD
+
+int ssdr_subrx_stage_results(ssdr_ctx *c, uint8_t *closed, uint8_t *adpcm, int out_is_device) SSDR_GUARD
+{
+    return c ? bank_stage_results(c, c->sub, c->own.sub, closed, adpcm, out_is_device) : SSDR_EINVAL;
+} SSDR_UNGUARD
+
+int ssdr_get_subrx_stage_state(ssdr_ctx *c, uint32_t first_row, uint32_t count, int32_t *deemp_S, int32_t *adpcm_state) SSDR_GUARD
+{
+    return c ? bank_stage_state(c, c->sub, first_row, count, deemp_S, adpcm_state) : SSDR_EINVAL;
+} SSDR_UNGUARD
+
+int ssdr_rx_tail_stats(ssdr_ctx *c, int bank, float *total_ms, uint32_t *launches, int reset) SSDR_GUARD
+{
+    if (bank != 0 && bank != 1) return SSDR_EINVAL;
+    return stage_stats(c, bank == 0 ? kTimedSubTail : kTimedWbRxTail, total_ms, launches, reset);
 } SSDR_UNGUARD
 
 // ---- wideband scopes: DDCs on the channeliser's wide streams, drawn by the waterfall kernel (ssdr_wb_scope.hip) -----------------
@@ -4300,6 +4588,26 @@ int ssdr_wb_rx_stats(ssdr_ctx *c, float *ddc_ms, float *audio_ms, uint32_t *laun
 {
     SSDR_TRY(stage_stats(c, kTimedWbRxDdc, ddc_ms, launches, reset));
     return stage_stats(c, kTimedWbRxAudio, audio_ms, launches ? launches + 1 : nullptr, reset);
+} SSDR_UNGUARD
+
+int ssdr_set_wb_rx_stages(ssdr_ctx *c, const ssdr_rx_stages *st, uint32_t count) SSDR_GUARD
+{
+    return c ? bank_set_stages(c, c->wr, st, count) : SSDR_EINVAL;
+} SSDR_UNGUARD
+
+int ssdr_get_wb_rx_stages(ssdr_ctx *c, ssdr_rx_stages *st, uint32_t *count) SSDR_GUARD
+{
+    return c ? bank_get_stages(c->wr, st, count) : SSDR_EINVAL;
+} SSDR_UNGUARD
+
+int ssdr_wb_rx_stage_results(ssdr_ctx *c, uint8_t *closed, uint8_t *adpcm, int out_is_device) SSDR_GUARD
+{
+    return c ? bank_stage_results(c, c->wr, c->own.wr, closed, adpcm, out_is_device) : SSDR_EINVAL;
+} SSDR_UNGUARD
+
+int ssdr_get_wb_rx_stage_state(ssdr_ctx *c, uint32_t first_row, uint32_t count, int32_t *deemp_S, int32_t *adpcm_state) SSDR_GUARD
+{
+    return c ? bank_stage_state(c, c->wr, first_row, count, deemp_S, adpcm_state) : SSDR_EINVAL;
 } SSDR_UNGUARD
 
 int ssdr_set_wf_lines(ssdr_ctx *c, const int16_t *wf_sum, uint32_t lines) SSDR_GUARD

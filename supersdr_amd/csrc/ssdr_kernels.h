@@ -206,7 +206,25 @@ struct SsdrDeempArgs {
     int32_t *state;                          // [n_ch] S
 };
 hipError_t ssdr_launch_deemp(const SsdrDeempArgs &a, hipStream_t stream);
-#define SSDR_ZOOM_HIST 256                  // raw input samples carried per channel (>= 32 Z - 2 for Z <= 8)
+// the three stages above for a bank of extra receivers in one launch (ssdr_rx_tail.hip, ssdr_set_subrx_stages / ssdr_set_wb_rx_stages):
+// one wave per listed row.  The list holds the rows with at least one acting stage and what acts on each: which squelch (the row's mode
+// has chosen), the de-emphasis coefficient a (0: off) and the encoder's flag.  16 B.
+enum { SSDR_RX_TAIL_OFF = 0, SSDR_RX_TAIL_NOISE = 1, SSDR_RX_TAIL_RSSI = 2 };
+struct SsdrRxTailRow { uint32_t row, squelch, coef, adpcm; };
+struct SsdrRxTailArgs {
+    int16_t *pcm;                            // [rows][n_frames*512] the bank's audio just run, 16-byte aligned: staged in place
+    const float *rssi;                       // [rows][n_frames]
+    uint32_t n_frames;                       // >= 1
+    const SsdrRxTailRow *list;               // [list_n] rows ascending
+    uint32_t list_n;
+    SsdrSquelchChan *sq;                     // [rows] settings + carried state, as a channel's
+    int32_t *de_state;                       // [rows] S
+    int32_t *enc_state;                      // [rows][2] index, prev
+    uint8_t *closed;                         // [rows][n_frames] written for the listed rows that squelch
+    uint8_t *adpcm;                          // [rows][n_frames*256] written for the listed rows that encode, 16-byte aligned
+};
+hipError_t ssdr_launch_rx_tail(const SsdrRxTailArgs &a, hipStream_t stream);
+#define SSDR_ZOOM_HIST 256                 // raw input samples carried per channel (>= 32 Z - 2 for Z <= 8)
 #define SSDR_ZOOM_TAPS_MAX 255
 struct SsdrZoomArgs {
     const uint32_t *iq;                      // [n_ch][ch_stride] input dwords

@@ -509,6 +509,33 @@ class SsdrEngine:
         check(getattr(lib, "ssdr_" + name)(self._ctx, arr, out.ctypes.data, 0), "ssdr_" + name)
         return out
 
+    def _bank_set_stages(self, bank, stages):
+        """stages: one (squelch, deemp, snd_adpcm) per row in list order, squelch = (fm_level, fm_max, rssi_level, tail_frames) and
+        deemp = (am, nfm) as set_squelch / set_deemphasis take them"""
+        name = "ssdr_set_%s_stages" % bank[0]
+        rows = [(tuple(int(v) for v in sq), tuple(int(v) for v in de), 1 if on else 0) for sq, de, on in stages]
+        if any(len(sq) != 4 or len(de) != 2 or any(not 0 <= v < 2 ** 32 for v in sq + de) for sq, de, _ in rows):
+            raise ValueError("stage settings %r: out of range" % (stages,))
+        arr = (L.RxStages * max(len(rows), 1))(*[L.RxStages(L.SquelchParams(*sq), L.DeempParams(*de), on, 0) for sq, de, on in rows])
+        check(getattr(lib, name)(self._ctx, arr if rows else None, len(rows)), name)
+
+    def _bank_stages(self, bank):
+        name = "ssdr_get_%s_stages" % bank[0]
+        n = C.c_uint32(0)
+        arr = (L.RxStages * bank[2])()
+        check(getattr(lib, name)(self._ctx, arr, C.byref(n)), name)
+        return [((t.squelch.fm_level, t.squelch.fm_max, t.squelch.rssi_level, t.squelch.tail_frames), (t.deemp.am, t.deemp.nfm),
+                 t.snd_adpcm) for t in arr[:n.value]]
+
+    def _bank_stage_results(self, bank):
+        name = "ssdr_%s_stage_results" % bank[0]
+        n, nf = self._bank_count(bank), self.audio_frames
+        closed = np.empty((n, nf), np.uint8)
+        adpcm = np.empty((n, nf * (L.FRAME // 2)), np.uint8)
+        check(getattr(lib, name)(self._ctx, closed.ctypes.data, adpcm.ctypes.data, 0), name)
+        return closed, adpcm
+
+    _STAGE_STATE_ROWS = (((), np.int32), ((2,), np.int32))
     _STATE_ROWS = (((), STATE_DTYPE), ((L.HIST, 2), np.int16))
     _CARRIER_ROWS = (((), np.float32), ((), np.float32))
     _CONSTS_ROWS = (((), CONSTS_DTYPE), ((L.NTAP_MAX,), np.float32))
@@ -553,6 +580,34 @@ class SsdrEngine:
     def subrx_stats(self, reset=False):
         """-> (total_ms, runs) of the sub-receiver stage since the last reset (the time only with set_profiling on)"""
         return self._stage_stats("ssdr_subrx_stats", reset)
+
+    def set_subrx_stages(self, stages):
+        """Squelch, de-emphasis and SND compression of the sub-receivers: one (squelch, deemp, snd_adpcm) per row in list order, squelch =
+        (fm_level, fm_max, rssi_level, tail_frames) and deemp = (am, nfm) as set_squelch / set_deemphasis take them.  A stage whose
+        setting differs from the row's current one starts over; every other keeps its state.  A value that does not fit the struct
+        raises ValueError before the library is called; what the library refuses (another count than the list's, a value out of range)
+        raises SsdrError (SSDR_EINVAL).  Either way nothing changes."""
+        self._bank_set_stages(self._SUBRX, stages)
+
+    def subrx_stages(self):
+        """-> [((fm_level, fm_max, rssi_level, tail_frames), (am, nfm), snd_adpcm), ...] the sub-receivers' stage settings, in list order"""
+        return self._bank_stages(self._SUBRX)
+
+    def subrx_stage_results(self):
+        """-> (closed uint8 [n_sub, n_frames], adpcm uint8 [n_sub, n_frames*256]) of the last run_audio / run_chain, rows in list order; a
+        row whose stage is off is zero"""
+        return self._bank_stage_results(self._SUBRX)
+
+    def subrx_stage_state(self, first=0, count=None):
+        """-> (S int32 [count], (index, prev) int32 [count, 2]): de-emphasis and encoder state of rows [first, first + count)"""
+        return self._bank_read(self._SUBRX, "stage_state", first, count, *self._STAGE_STATE_ROWS)
+
+    def rx_tail_stats(self, bank, reset=False):
+        """-> (total_ms, launches) of the fused squelch / de-emphasis / encoder launch of a bank ("sub" or "tuned") since the last reset
+        (the time only with set_profiling on)"""
+        ms, n = C.c_float(), C.c_uint32()
+        check(lib.ssdr_rx_tail_stats(self._ctx, {"sub": 0, "tuned": 1}[bank], C.byref(ms), C.byref(n), 1 if reset else 0), "ssdr_rx_tail_stats")
+        return ms.value, n.value
 
     # ---- wideband channeliser: one wide IQ stream -> 1024 rows of the input batch
     def set_channelizer(self, n_streams, oversample=1, taps=None, branches=L.CHAN_BRANCHES):
@@ -741,6 +796,22 @@ class SsdrEngine:
         d, a, n = C.c_float(), C.c_float(), (C.c_uint32 * 2)()
         check(lib.ssdr_wb_rx_stats(self._ctx, C.byref(d), C.byref(a), C.byref(n), 1 if reset else 0), "ssdr_wb_rx_stats")
         return d.value, a.value, n[0], n[1]
+
+    def set_wb_rx_stages(self, stages):
+        """Squelch, de-emphasis and SND compression of the tuned receivers, as set_subrx_stages"""
+        self._bank_set_stages(self._WB_RX, stages)
+
+    def wb_rx_stages(self):
+        """-> the tuned receivers' stage settings in list order, as subrx_stages"""
+        return self._bank_stages(self._WB_RX)
+
+    def wb_rx_stage_results(self):
+        """-> (closed uint8 [n_rx, n_frames], adpcm uint8 [n_rx, n_frames*256]) of the last run_audio / run_chain, as subrx_stage_results"""
+        return self._bank_stage_results(self._WB_RX)
+
+    def wb_rx_stage_state(self, first=0, count=None):
+        """-> (S, (index, prev)) of rows [first, first + count), as subrx_stage_state"""
+        return self._bank_read(self._WB_RX, "stage_state", first, count, *self._STAGE_STATE_ROWS)
 
     def audio_iq(self):
         """-> int16 [n_ch, n_frames*512, 2]: I,Q of the channels in "iq" mode for the last run_audio (rows of other modes: 0)"""

@@ -125,11 +125,14 @@ class SuperframeResult:
     With wideband scopes (IQHub.open_scope): scope_ids lists them, ascending, and scope_lines int16 [n, k, 1024] holds the k byte lines
     (N = 1) each completed in this feed_wideband, k >= 0 (both None: no scope is open).
     With tuned receivers (IQHub.open_tuned): tuned_ids lists them, ascending, and tuned_pcm / tuned_rssi / tuned_flags / tuned_play have
-    a row for each, as the sub-receivers' arrays do (all None: no tuned receiver is open, or the run was no feed_wideband)."""
+    a row for each, as the sub-receivers' arrays do (all None: no tuned receiver is open, or the run was no feed_wideband).
+    On a hub built with rx_stages=True: sub_closed / tuned_closed uint8 [n, frames], 1 where a receiver's squelch zeroed the frame, and
+    sub_adpcm / tuned_adpcm uint8 [n, frames*256], rows as sub_ids / tuned_ids, a row whose stage is off all zero (each None: no
+    receiver of the family squelches, resp. compresses)."""
     __slots__ = ("seq", "wf", "n_avg", "color", "chans", "pcm", "rssi", "flags", "play", "mono", "iq", "wire_rssi", "post_channels", "out_channels",
                  "snd_adpcm", "wf_adpcm", "snd_adpcm_channels", "wf_adpcm_channels", "squelched", "view_lines", "view_channels",
                  "squelched_channels", "sub_ids", "sub_pcm", "sub_rssi", "sub_flags", "sub_play", "scope_ids", "scope_lines",
-                 "tuned_ids", "tuned_pcm", "tuned_rssi", "tuned_flags", "tuned_play")
+                 "tuned_ids", "tuned_pcm", "tuned_rssi", "tuned_flags", "tuned_play", "sub_closed", "sub_adpcm", "tuned_closed", "tuned_adpcm")
 
     def __init__(self, **kw):
         for k in self.__slots__:
@@ -255,6 +258,9 @@ class IQHub:
     listen=True (with pipeline=True; SSDR_FEED_LISTEN) runs the listener stages in the slot pipeline: set_squelch, set_deemphasis,
     set_compression and set_wf_view then work as on the synchronous hub, on the superframes submitted after the call, and
     Frame.squelched, Frame.adpcm, a line's .adpcm and a view's lines reach the queues `depth - 1` superframes late with everything else.
+    rx_stages=True gives the extra receivers (open_sub, open_tuned) squelch, de-emphasis and SND compression of their own
+    (set_rx_squelch, set_rx_deemphasis, set_rx_compression; ssdr_set_subrx_stages / ssdr_set_wb_rx_stages): without it those
+    methods refuse before the engine is touched and the hub sends the engine nothing it did not send before they existed.
     `batch_superframes=K` runs K superframes per GPU call (K lines + 2K audio frames per channel and call): latency for
     launch efficiency at very large channel counts.  `exact_bins=True`: the waterfall stage in float64 (ssdr_set_exact_bins).  `copy_threads=T` splits feed_block's copy of a large block over T threads (default: up to 8 on hubs of 8192+ receivers).
     """
@@ -263,7 +269,7 @@ class IQHub:
 
     def __init__(self, n_channels, device=0, engine=None, max_queue=64, gpu_post=True, kiwi_rate=12000, trace_rows=0,
                  backlog_superframes=8, stall_superframes=4, pipeline=False, depth=3, hop=1024, zoom=1, lazy=None,
-                 batch_superframes=1, wire=False, copy_threads=None, exact_bins=False, lazy_out=False, listen=False):
+                 batch_superframes=1, wire=False, copy_threads=None, exact_bins=False, lazy_out=False, listen=False, rx_stages=False):
         self.n_ch = int(n_channels)
         # argument combinations that cannot work are refused BEFORE an engine (a GPU context) exists
         self._lazy = (self.n_ch > self.LAZY_ABOVE) if lazy is None else bool(lazy)
@@ -378,6 +384,11 @@ class IQHub:
         self._subs = _Listeners("sub-receivers", L.SUBRX_MAX, "SSDR_SUBRX_MAX", self._send_subs, 2 * self._max_queue)
         self._tuned = _Listeners("tuned receivers", L.WB_RX_MAX, "SSDR_WB_RX_MAX", self._send_tuned, 2 * self._max_queue)
         self._scopes = _Listeners("wideband scopes", L.WB_SCOPES_MAX, "SSDR_WB_SCOPES_MAX", self._send_scopes, 2 * self._max_queue)
+        # ... and, on a hub built with rx_stages=True, a receiver's stage settings by family and id: (squelch 4-tuple, (am, nfm), snd);
+        # a family's parallel array goes to the engine behind every list the hub sends once one of its receivers has had a setting
+        self._rx_stages = bool(rx_stages)
+        self._rx_tables = {"sub": self._subs, "tuned": self._tuned}
+        self._rx_st = {"sub": {}, "tuned": {}}
         self.sub_queue, self.sub_clients = self._subs.queue, self._subs.clients
         self.tuned_queue, self.tuned_clients = self._tuned.queue, self._tuned.clients
         self.scope_queue, self.scope_clients = self._scopes.queue, self._scopes.clients
@@ -672,6 +683,7 @@ class IQHub:
         if not hasattr(self.engine, "set_subrx"):    # (only an open can meet this: without it no sub-receiver is open)
             raise ValueError("this engine has no sub-receivers (set_subrx)")
         self.engine.set_subrx([(sid,) + rows[sid] for sid in sorted(rows)])
+        self._resend_rx_stages("sub", rows)
 
     def _check_sub_params(self, p):
         if p.mode == L.MODE_IQ:
@@ -708,6 +720,7 @@ class IQHub:
     def close_sub(self, sid):
         with self._lock:
             self._subs.close(int(sid))
+            self._rx_st["sub"].pop(int(sid), None)
 
     # ---- tuned receivers: demodulators at any frequency of a channeliser's wide stream (ssdr_set_wb_rx)
     def tuned(self, tid):
@@ -743,6 +756,7 @@ class IQHub:
             self.engine.set_wb_rx([(tid,) + rows[tid] for tid in sorted(rows)])
         except L.SsdrError as e:
             raise ValueError("tuned receivers refused: %s" % e)
+        self._resend_rx_stages("tuned", rows)
 
     def open_tuned(self, stream, offset_hz, params=None):
         """A tuned receiver on wide stream `stream`: a DDC at a row's rate centred offset_hz from the stream's centre -- anywhere, not
@@ -781,6 +795,102 @@ class IQHub:
     def close_tuned(self, tid):
         with self._lock:
             self._tuned.close(int(tid))
+            self._rx_st["tuned"].pop(int(tid), None)
+
+    # ---- squelch, de-emphasis and SND compression of the extra receivers (ssdr_set_subrx_stages / ssdr_set_wb_rx_stages): one
+    # implementation for both families, rx = ("sub", sid) or ("tuned", tid)
+    _RX_OFF = ((0, 0, 0, 0), (0, 0), 0)
+    _RX_SETTERS = {"sub": "set_subrx_stages", "tuned": "set_wb_rx_stages"}
+
+    def _rx(self, rx):
+        """-> (family, id) of a receiver that is open; ValueError without rx_stages=True, before the engine is touched"""
+        if not self._rx_stages:
+            raise ValueError("squelch, de-emphasis and compression of a sub-receiver or tuned receiver need a hub built with rx_stages=True")
+        kind, rid = rx
+        if kind not in self._rx_tables:
+            raise ValueError("receiver family %r: 'sub' or 'tuned'" % (kind,))
+        if int(rid) not in self._rx_tables[kind].rows:
+            raise KeyError("no %s %r" % (self._rx_tables[kind].nouns[:-1], rid))
+        return kind, int(rid)
+
+    def _rx_array(self, kind, ids, settings):
+        return [settings.get(i, self._RX_OFF) for i in ids]
+
+    def _resend_rx_stages(self, kind, rows):
+        """behind a list the hub has just sent: the family's settings in the new list's order, so that a caller never sees list order
+        (the library carries them along by id as well; a family nobody has given a setting sends nothing)"""
+        if self._rx_stages and self._rx_st[kind] and rows:
+            getattr(self.engine, self._RX_SETTERS[kind])(self._rx_array(kind, sorted(rows), self._rx_st[kind]))
+
+    def _set_rx_stage(self, kind, rid, st):
+        """one receiver's settings to the engine as the family's parallel array; committed only if the engine took it"""
+        setter = getattr(self.engine, self._RX_SETTERS[kind], None)
+        if setter is None:
+            raise ValueError("this engine has no stages for %s (%s)" % (self._rx_tables[kind].nouns, self._RX_SETTERS[kind]))
+        new = dict(self._rx_st[kind])
+        new[rid] = st
+        setter(self._rx_array(kind, self._rx_tables[kind].ids(), new))
+        self._rx_st[kind] = new
+
+    def rx_squelch(self, rx):
+        """-> (fm_level, fm_max, rssi_level, tail_frames) of an extra receiver as set"""
+        with self._lock:
+            kind, rid = self._rx(rx)
+            return self._rx_st[kind].get(rid, self._RX_OFF)[0]
+
+    def rx_deemphasis(self, rx):
+        """-> (am, nfm) of an extra receiver as set"""
+        with self._lock:
+            kind, rid = self._rx(rx)
+            return self._rx_st[kind].get(rid, self._RX_OFF)[1]
+
+    def rx_compression(self, rx):
+        """-> whether an extra receiver's SND frames are IMA-ADPCM compressed"""
+        with self._lock:
+            kind, rid = self._rx(rx)
+            return bool(self._rx_st[kind].get(rid, self._RX_OFF)[2])
+
+    def set_rx_squelch(self, rx, fm_level=None, fm_max=None, rssi_level=None, tail_frames=None):
+        """set_squelch for an extra receiver, rx = ("sub", sid) or ("tuned", tid); None leaves a value as it is.  The receiver's mode
+        picks the setting that acts (NBFM: the noise squelch; any other: the RSSI squelch).  ValueError out of range, and then nothing
+        changes; a changed setting resets that receiver's squelch state alone."""
+        with self._lock:
+            kind, rid = self._rx(rx)
+            old = self._rx_st[kind].get(rid, self._RX_OFF)
+            new = tuple(int(o if v is None else v) for o, v in zip(old[0], (fm_level, fm_max, rssi_level, tail_frames)))
+            check_squelch(*new)
+            self._set_rx_stage(kind, rid, (new, old[1], old[2]))
+
+    def set_rx_deemphasis(self, rx, am=None, nfm=None):
+        """set_deemphasis for an extra receiver; None leaves a value as it is.  ValueError out of range, and then nothing changes; a
+        changed setting resets that receiver's filter state alone."""
+        check_deemphasis(am, nfm)
+        with self._lock:
+            kind, rid = self._rx(rx)
+            old = self._rx_st[kind].get(rid, self._RX_OFF)
+            new = tuple(int(o if v is None else v) for o, v in zip(old[1], (am, nfm)))
+            self._set_rx_stage(kind, rid, (old[0], new, old[2]))
+
+    def set_rx_compression(self, rx, on):
+        """"SET compression=" of an extra receiver: its frames carry their ADPCM payload (Frame.adpcm) from the next superframe on.
+        Turning it on restarts the receiver's encoder at (0, 0); a request that changes nothing does not reach the engine."""
+        with self._lock:
+            kind, rid = self._rx(rx)
+            old = self._rx_st[kind].get(rid, self._RX_OFF)
+            if bool(on) != bool(old[2]):
+                self._set_rx_stage(kind, rid, (old[0], old[1], 1 if on else 0))
+
+    def _rx_stage_results(self, name, kind, table, results):
+        """-> a family's name_closed / name_adpcm of the SuperframeResult, each None unless some receiver's stage acts"""
+        st = self._rx_st[kind]
+        rows = [(st.get(i, self._RX_OFF), table.rows[i][-1].mode) for i in table.ids()]
+        squelches = any(_squelch_acts(t[0], m) for t, m in rows)
+        filters = any((t[1][1] if m == L.MODE_NBFM else t[1][0] if m in (L.MODE_AM, L.MODE_SAM) else 0) for t, m in rows)
+        compresses = any(t[2] for t, _ in rows)
+        if not (squelches or filters or compresses):
+            return {}
+        closed, adpcm = results()
+        return {name + "_closed": closed if squelches else None, name + "_adpcm": adpcm if compresses else None}
 
     # ---- wideband scopes: zoomable waterfalls of a channeliser's wide stream (the band scope of kiwi_waterfall; ssdr_set_wb_scopes)
     def scope(self, sid):
@@ -1135,8 +1245,12 @@ class IQHub:
                 mono = eng.playbuffer_mono()
         if self._subs.rows:                           # [n, frames*512], [n, frames] x 2, rows in sid order (open_sub)
             extra.update(self._rx_results("sub", self._subs, eng.subrx_audio, eng.run_subrx_playbuffer))
+            if self._rx_st["sub"]:
+                extra.update(self._rx_stage_results("sub", "sub", self._subs, eng.subrx_stage_results))
         if wideband and self._tuned.rows:             # ... in tid order (open_tuned)
             extra.update(self._rx_results("tuned", self._tuned, eng.wb_rx_audio, eng.run_wb_rx_playbuffer))
+            if self._rx_st["tuned"]:
+                extra.update(self._rx_stage_results("tuned", "tuned", self._tuned, eng.wb_rx_stage_results))
         self.superframes += 1
         self._hand_out(SuperframeResult(seq=self.superframes, wf=wf, n_avg=n_avg, color=color, chans=chans, pcm=pcm, rssi=rssi,
                                         flags=flags, play=play, mono=mono, iq=iqo, wire_rssi=wire_rssi, post_channels=self._post_sel,
@@ -1155,16 +1269,23 @@ class IQHub:
             play = playbuffer([PlayChan(100.0, 0.0) if s is None else PlayChan(float(s.volume), float(s.audio_balance)) for s in rows])
         return {name + "_ids": ids, name + "_pcm": pcm, name + "_rssi": rssi, name + "_flags": flags, name + "_play": play}
 
-    def _hand_out_rx(self, queues, ids, pcm, rssi, flags, play):
-        """a receiver list's frames (rows in the order of `ids`) to the queues of those that have one"""
-        P = self.play_len
+    def _hand_out_rx(self, queues, ids, pcm, rssi, flags, play, closed=None, adpcm=None, settings=None):
+        """a receiver list's frames (rows in the order of `ids`) to the queues of those that have one; a compressing receiver's carry
+        their payload, a squelched frame its mark, as a channel's do"""
+        P, H = self.play_len, L.FRAME // 2
         for i, rid in enumerate(ids or ()):
             q = queues.get(rid)
             if q is None:
                 continue
+            comp = adpcm is not None and bool((settings or {}).get(rid, self._RX_OFF)[2])
             for f in range(pcm.shape[1] // L.FRAME):
-                _put_drop_oldest(q, Frame.make(pcm[i, f * L.FRAME:(f + 1) * L.FRAME], rssi[i, f],
-                                               play[i, f * P:(f + 1) * P].copy() if play is not None else None, None, flags[i, f]))
+                fr = Frame.make(pcm[i, f * L.FRAME:(f + 1) * L.FRAME], rssi[i, f],
+                                play[i, f * P:(f + 1) * P].copy() if play is not None else None, None, flags[i, f])
+                if comp:
+                    fr.adpcm = adpcm[i, f * H:(f + 1) * H].tobytes()
+                if closed is not None and closed[i, f]:
+                    fr.squelched = True
+                _put_drop_oldest(q, fr)
 
     def _hand_out(self, r):
         self.last = r
@@ -1223,8 +1344,9 @@ class IQHub:
                     if qc is not None and r.squelched[qc, f]:
                         fr.squelched = True
                 _put_drop_oldest(q, fr)
-        self._hand_out_rx(self.sub_queue, r.sub_ids, r.sub_pcm, r.sub_rssi, r.sub_flags, r.sub_play)
-        self._hand_out_rx(self.tuned_queue, r.tuned_ids, r.tuned_pcm, r.tuned_rssi, r.tuned_flags, r.tuned_play)
+        self._hand_out_rx(self.sub_queue, r.sub_ids, r.sub_pcm, r.sub_rssi, r.sub_flags, r.sub_play, r.sub_closed, r.sub_adpcm, self._rx_st["sub"])
+        self._hand_out_rx(self.tuned_queue, r.tuned_ids, r.tuned_pcm, r.tuned_rssi, r.tuned_flags, r.tuned_play, r.tuned_closed, r.tuned_adpcm,
+                          self._rx_st["tuned"])
         for i, sid in enumerate(r.scope_ids or ()):
             q = self.scope_queue.get(sid)
             if q is None:
@@ -1450,11 +1572,11 @@ class GpuStream:
         self._rx = None
         if self.tuned is not None:
             self._rx = types.SimpleNamespace(
-                noun="tuned receiver", id=self.tuned, on="wide stream", no_stage="there is no %s for tuned receivers", queues=hub.tuned_queue,
+                noun="tuned receiver", id=self.tuned, key=("tuned", self.tuned), on="wide stream", no_stage="there is no %s for tuned receivers", queues=hub.tuned_queue,
                 row=lambda: hub.tuned(self.tuned), set_params=lambda q: hub.set_tuned_params(self.tuned, q), close=lambda: hub.close_tuned(self.tuned))
         elif self.sub is not None and scope is None:
             self._rx = types.SimpleNamespace(
-                noun="sub-receiver", id=self.sub, on="channel", no_stage="the %s is the channel's, there is none for sub-receivers", queues=hub.sub_queue,
+                noun="sub-receiver", id=self.sub, key=("sub", self.sub), on="channel", no_stage="the %s is the channel's, there is none for sub-receivers", queues=hub.sub_queue,
                 row=lambda: hub.sub_params(self.sub), set_params=lambda q: hub.set_sub_params(self.sub, q), close=lambda: hub.close_sub(self.sub))
         if self._rx is not None:
             rx = self._rx
@@ -1494,11 +1616,12 @@ class GpuStream:
             return
         kv = dict(w.split("=", 1) for w in words[1:] if "=" in w)
         rx = self._rx
+        staged = rx is not None and getattr(self.hub, "_rx_stages", False)      # a hub built with rx_stages=True: the receiver has all but the blanker
         if rx is not None and "mod" not in kv and "agc" not in kv:       # the channel's stages: an extra receiver has none of them
             for key, stage in (("nb", "noise blanker"), ("squelch", "squelch"), ("de_emp", "de-emphasis")):
-                if key in kv:
+                if key in kv and not (staged and key != "nb"):
                     raise ValueError(("SET %s= on %s %d of %s %d: " + rx.no_stage) % (key, rx.noun, rx.id, rx.on, self.channel, stage))
-            if "compression" in kv and int(kv["compression"]) != 0:
+            if "compression" in kv and int(kv["compression"]) != 0 and not staged:
                 raise ValueError("SET compression=1 on %s %d of %s %d: a %s's frames are not ADPCM-encoded"
                                  % (rx.noun, rx.id, rx.on, self.channel, rx.noun))
         if self.scope is not None and "interp" in kv:
@@ -1512,7 +1635,7 @@ class GpuStream:
                              agc_slope=float(kv.get("slope", 0)), agc_decay=float(kv.get("decay", 4000)),
                              agc_man_gain=float(kv.get("manGain", 50)))
             self._set_params(q)
-        elif rx is not None:
+        elif rx is not None and not (staged and ("squelch" in kv or "de_emp" in kv or "compression" in kv)):
             pass                                     # (compression=0, zoom=, ...: nothing to do for a sub-receiver or a tuned receiver)
         elif "nb" in kv:
             if "th" not in kv:
@@ -1541,6 +1664,22 @@ class GpuStream:
         else:
             self._rx.set_params(q)
 
+    def _stage_setters(self):
+        """where this stream's squelch / de_emp / compression commands go -> (set_squelch(**new), squelch(), set_deemphasis(**new),
+        deemphasis(), compression(), set_compression(on)), each None where the hub has no such method: the channel's, or -- on a
+        hub built with rx_stages=True -- the extra receiver's this stream stands for"""
+        hub = self.hub
+        if self._rx is not None:
+            k = self._rx.key
+            return (lambda **new: hub.set_rx_squelch(k, **new), lambda: hub.rx_squelch(k), lambda **new: hub.set_rx_deemphasis(k, **new),
+                    lambda: hub.rx_deemphasis(k), lambda: hub.rx_compression(k), lambda on: hub.set_rx_compression(k, on))
+        c, which = self.channel, "snd" if self.kind == "SND" else "wf"
+        i = 0 if self.kind == "SND" else 1
+        have = lambda name: hasattr(hub, name)      # noqa: E731
+        return (None if not have("set_squelch") else lambda **new: hub.set_squelch(c, **new), lambda: hub.squelch(c),
+                None if not have("set_deemphasis") else lambda **new: hub.set_deemphasis(c, **new), lambda: hub.deemphasis(c),
+                (lambda: hub.compression(c)[i]) if have("compression") else (lambda: False), lambda on: hub.set_compression(c, **{which: on}))
+
     def _set_squelch(self, kv, msg):
         """both spellings: "squelch=<v> max=<m>" (the NBFM noise squelch) and "squelch=<v> param=<tail_s>" (the RSSI squelch)"""
         from .engine import squelch_tail_frames
@@ -1552,9 +1691,10 @@ class GpuStream:
         else:
             new = dict(rssi_level=level, tail_frames=squelch_tail_frames(float(kv["param"]), int(getattr(self.hub, "kiwi_rate", L.RATE))))
         check_squelch(**new)
-        if hasattr(self.hub, "set_squelch"):
-            self.hub.set_squelch(self.channel, **new)
-            now = self.hub.squelch(self.channel)
+        set_squelch, squelch = self._stage_setters()[:2]
+        if set_squelch is not None:
+            set_squelch(**new)
+            now = squelch()
             self._squelch_on = bool(now[0] or now[2])
 
     def _set_deemphasis(self, kv, msg):
@@ -1564,16 +1704,16 @@ class GpuStream:
             raise ValueError("SET de_emp= with nfm outside 0..1: %r" % (msg,))
         new = dict(nfm=n) if nfm else dict(am=n)
         check_deemphasis(**new)
-        if hasattr(self.hub, "set_deemphasis"):
-            self.hub.set_deemphasis(self.channel, **new)
-            self._deemp_on = any(self.hub.deemphasis(self.channel))
+        set_deemphasis, deemphasis = self._stage_setters()[2:4]
+        if set_deemphasis is not None:
+            set_deemphasis(**new)
+            self._deemp_on = any(deemphasis())
 
     def _set_compression(self, on):
         """the channel's flag for this stream's kind; the hub (and its engine) only hear of a change"""
-        i = 0 if self.kind == "SND" else 1
-        now = self.hub.compression(self.channel)[i] if hasattr(self.hub, "compression") else False
-        if on != now:
-            self.hub.set_compression(self.channel, **{("snd" if i == 0 else "wf"): on})
+        compression, set_compression = self._stage_setters()[4:]
+        if on != compression():
+            set_compression(on)
         self._comp_on = on
 
     def _retune(self, kv):
@@ -1612,6 +1752,8 @@ class GpuStream:
         try:
             if self._rx is not None:
                 f = self._rx.queues[self._rx.id].get(timeout=self.timeout)
+                if getattr(f, "adpcm", None) is not None:      # produced with "SET compression=1" on a hub built with rx_stages=True
+                    return snd_adpcm_frame(f.adpcm, f.rssi, self._next_seq(), adc_overflow=f.adc_overflow)
                 return snd_frame(f, f.rssi, self._next_seq(), adc_overflow=f.adc_overflow)
             if self.kind == "SND":
                 f = self.hub.snd_queue[self.channel].get(timeout=self.timeout)
@@ -1638,6 +1780,15 @@ class GpuStream:
     def close_connection(self, *a, **k):
         if self._rx is not None:                     # the extra receiver goes with its stream; nothing of the channel's was this stream's
             if not self.closed:
+                # what this stream switched on goes off first, as for a channel below (the receiver may belong to somebody who keeps it)
+                set_squelch, _, set_deemphasis, _, _, set_compression = self._stage_setters()
+                if self._comp_on:
+                    set_compression(False)
+                if self._squelch_on:
+                    set_squelch(fm_level=0, rssi_level=0)
+                if self._deemp_on:
+                    set_deemphasis(am=0, nfm=0)
+                self._comp_on = self._squelch_on = self._deemp_on = False
                 self._rx.close()
             self.closed = True
             return
