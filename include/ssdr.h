@@ -524,8 +524,9 @@ int ssdr_wf_view_stats(ssdr_ctx *ctx, float *total_ms, uint32_t *launches, int r
  * on which somebody listens to a second signal; the list can be replaced while the streams run.  Sub-receiver j on channel c with
  * parameters P produces, bit for bit, the PCM, RSSI, flags and carried state (ssdr_chan_state, raw history) of a channel of a ctx
  * that is fed channel c's IQ and holds P: no new arithmetic (oracle/ssdr_oracle.py:audio_chain, oracle/ssdr_twin.c, the shipped
- * audio kernels).  It sees the input as it came: the channel's noise blanker does not act on it and it has none of its own, nor
- * SSDR_MODE_IQ; squelch, de-emphasis and the SND encoder are its own (ssdr_set_subrx_stages, further down), off until set.
+ * audio kernels).  The channel's noise blanker does not act on it; it has one of its own (ssdr_set_subrx_noise_blanker, further
+ * down), off until set, which acts on nobody else.  No SSDR_MODE_IQ; squelch, de-emphasis and the SND encoder are its own
+ * (ssdr_set_subrx_stages, further down), off until set.
  *   every ssdr_run_audio and every path of ssdr_run_chain (*fused = 0, 1, 2) advances every sub-receiver by the batch;
  *   which kernel the channels get (chain_plan) does not depend on the list, and their results, state and timing are untouched.
  * Kernels: ssdr_audio.hip, ssdr_audio_sub_kernel (12 kHz: one launch, a wave per sub-receiver, all three frame paths) and
@@ -720,8 +721,8 @@ int ssdr_read_wb_scope_windows(ssdr_ctx *ctx, uint32_t index, int16_t *iq_out, u
  * tests/wb_rx_ref.py is the definition; the kernel works in float32 in the scopes' summation order, so a row is bit-identical however
  * the stream is cut into calls and whatever else is in either list.
  * The audio is no new arithmetic: PCM, RSSI, flags and carried state (ssdr_chan_state, raw history) are bit for bit those of a
- * channel of a ctx that is fed the stored row and holds P.  Like a sub-receiver it has no blanker and no SSDR_MODE_IQ, and squelch,
- * de-emphasis and SND encoder of its own (ssdr_set_wb_rx_stages), off until set; at D > 1 no parameters that compile to a shift path and no SSDR_MODE_SAM.
+ * channel of a ctx that is fed the stored row and holds P.  Like a sub-receiver it has no SSDR_MODE_IQ, and a noise blanker
+ * (ssdr_set_wb_rx_noise_blanker), squelch, de-emphasis and SND encoder (ssdr_set_wb_rx_stages) of its own, off until set; at D > 1 no parameters that compile to a shift path and no SSDR_MODE_SAM.
  * State rules (the sub-receivers' for the audio, the scopes' for the DDC):
  *   the DDC carries nothing: a new offset_hz of a kept receiver acts from the next push on and restarts nobody;
  *   a receiver whose (id, stream) is in the old list keeps its audio stream and takes new parameters as ssdr_set_params does; a new
@@ -782,7 +783,7 @@ int ssdr_wb_rx_stats(ssdr_ctx *ctx, float *ddc_ms, float *audio_ms, uint32_t *la
  * LSB, USB, CW), then the encoder, whose state is the receiver's own.  tests/squelch_ref.py, tests/deemp_ref.py and tests/adpcm_ref.py
  * stay the definitions.  ssdr_subrx_audio / ssdr_wb_rx_audio and ssdr_run_subrx_playbuffer / ssdr_run_wb_rx_playbuffer read the PCM
  * behind the stages, as ssdr_run_audio's copies and ssdr_run_playbuffer do for a channel.  The noise blanker is not part of this: an
- * extra receiver has none.
+ * extra receiver's sits in front of its channel filter (ssdr_set_subrx_noise_blanker, below), and the stages read the blanked chain's PCM.
  * Kernel: ssdr_rx_tail.hip, all three stages of the rows with at least one acting stage in ONE launch per bank and run (a wave per
  * row), on the audio stage's stream behind that bank's audio launch and in front of the channels' squelch / de-emphasis / encoder, so
  * every call that waits for the audio stage waits for it.  With no acting row nothing is launched; before the first nonzero setting
@@ -828,6 +829,41 @@ int ssdr_get_wb_rx_stage_state(ssdr_ctx *ctx, uint32_t first_row, uint32_t count
  * and with ssdr_set_profiling on their summed time (a HIP-event pair per launch; launches made with profiling off count, and add no
  * time).  ssdr_subrx_stats and ssdr_wb_rx_stats do not move. */
 int ssdr_rx_tail_stats(ssdr_ctx *ctx, int bank, float *total_ms, uint32_t *launches, int reset);
+
+/* -- the noise blanker for the extra receivers (sub-receivers and tuned receivers)
+ *
+ * No new arithmetic: tests/nb_ref.py and the text above ssdr_set_noise_blanker stay the definition.  For row r of either bank with the
+ * setting (gate_us, thresh), the PCM and RSSI, the carried ssdr_chan_state and FIR history, the SAM carrier read-back and -- where the
+ * stages above are on -- closed flags, ADPCM payload and stage state are bit for bit those of a channel of an ordinary ctx with the same
+ * D and kiwi_rate that holds the receiver's parameters, has ssdr_set_noise_blanker(gate_us, thresh) set and is fed the receiver's input
+ * row (a sub-receiver's: its parent channel's raw IQ; a tuned receiver's: the stored row ssdr_read_wb_rx returns) cut into the same
+ * calls.  The ADC-overflow flags see the input as it came; the gate is G = ssdr_nb_gate_samples(gate_us, D, kiwi_rate).  A channel's own
+ * blanker still does not act on its sub-receivers, and a sub-receiver's acts on nobody else: not on the parent's audio or waterfall,
+ * not on a sibling on the same parent, not on the shared input row in memory.
+ * The setters take parallel arrays in list order, as ssdr_set_subrx_stages does: count must equal the list's length (0 on an empty bank
+ * is SSDR_OK).  Ranges are the channel's: gate_us 1..10000, thresh 2..1000, either being 0 means off.  SSDR_EINVAL, and then nothing
+ * changes: another count, a value out of range, NULL with count > 0.
+ * State rules (those of the stages above, not the channel setter's): a row given the setting it already has keeps its blanker state
+ * (the two sums and the samples left to blank); a row whose setting differs starts over alone.  Settings and state follow a receiver
+ * across ssdr_set_subrx / ssdr_set_wb_rx by (id, channel) / (id, stream), as its audio state does; a new receiver starts off; a kept
+ * receiver's new parameters, a mode change included, leave its blanker state alone.  Whatever restarts a receiver's audio state --
+ * ssdr_reset_state on the parent channel, ssdr_set_decimation, ssdr_set_kiwi_rate, ssdr_channelizer_reset -- resets its blanker state and
+ * recomputes G from gate_us.  An empty list forgets the settings.
+ * Kernels (ssdr_audio.hip): once any row of a bank blanks, the whole bank runs on the blanker twins of the sub-receiver kernels
+ * (ssdr_audio_sub_nb_kernel: the three frame paths and synchronous AM in one launch; ssdr_audio_sub_dec_nb_kernel<D>), a row whose
+ * blanker is off never triggering -- bit for bit the plain kernel.  The launch takes the place of the bank's audio launch, in its stats
+ * slot (ssdr_subrx_stats, ssdr_wb_rx_stats' audio figure) and in front of the bank's tail.  A bank with no blanking row launches what it
+ * launched before the setters existed, and a ctx that never calls them allocates nothing.  chain_plan does not look at the banks. */
+int ssdr_set_subrx_noise_blanker(ssdr_ctx *ctx, const uint32_t *gate_us, const uint32_t *thresh, uint32_t count);
+int ssdr_get_subrx_noise_blanker(ssdr_ctx *ctx, uint32_t *gate_us /* may be NULL */, uint32_t *thresh /* may be NULL */, uint32_t *count);
+/* The rows' blank masks of the last audio run, as ssdr_audio_nb_mask packs a channel's: uint8 [rows][n_frames * 512 * D / 8], rows in
+ * list order, rows with the blanker off zero.  SSDR_ESTATE if the bank is empty, if no row blanks, or if there has been no run of the
+ * ctx's own batch with list and settings as they are. */
+int ssdr_subrx_nb_mask(ssdr_ctx *ctx, uint8_t *mask_out, int out_is_device);
+/* The same three for the tuned receivers. */
+int ssdr_set_wb_rx_noise_blanker(ssdr_ctx *ctx, const uint32_t *gate_us, const uint32_t *thresh, uint32_t count);
+int ssdr_get_wb_rx_noise_blanker(ssdr_ctx *ctx, uint32_t *gate_us /* may be NULL */, uint32_t *thresh /* may be NULL */, uint32_t *count);
+int ssdr_wb_rx_nb_mask(ssdr_ctx *ctx, uint8_t *mask_out, int out_is_device);
 
 /* -- pipelined host feed: the path a live ingest takes (KiwiSDRStream._process_iq_samples -> batches, kiwi/client.py:493)
  *

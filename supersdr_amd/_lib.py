@@ -254,6 +254,12 @@ _SIGS = {
     "ssdr_wb_rx_stage_results": (C.c_int, [_P, _P, _P, C.c_int]),
     "ssdr_get_wb_rx_stage_state": (C.c_int, [_P, C.c_uint32, C.c_uint32, _P, _P]),
     "ssdr_rx_tail_stats": (C.c_int, [_P, C.c_int, C.POINTER(C.c_float), C.POINTER(C.c_uint32), C.c_int]),
+    "ssdr_set_subrx_noise_blanker": (C.c_int, [_P, _P, _P, C.c_uint32]),
+    "ssdr_get_subrx_noise_blanker": (C.c_int, [_P, _P, _P, C.POINTER(C.c_uint32)]),
+    "ssdr_subrx_nb_mask": (C.c_int, [_P, _P, C.c_int]),
+    "ssdr_set_wb_rx_noise_blanker": (C.c_int, [_P, _P, _P, C.c_uint32]),
+    "ssdr_get_wb_rx_noise_blanker": (C.c_int, [_P, _P, _P, C.POINTER(C.c_uint32)]),
+    "ssdr_wb_rx_nb_mask": (C.c_int, [_P, _P, C.c_int]),
     "ssdr_feed_open": (C.c_int, [_P, C.c_uint32, C.c_uint32, C.c_uint32]),
     "ssdr_feed_slot": (C.c_int, [_P, C.POINTER(_P)]),
     "ssdr_feed_submit": (C.c_int, [_P]),
@@ -310,7 +316,9 @@ _NEWER_THAN_AB_LIBS = ("ssdr_feed_collect_listen", "ssdr_set_subrx", "ssdr_get_s
                        "ssdr_set_wb_rx", "ssdr_get_wb_rx", "ssdr_wb_rx_audio", "ssdr_read_wb_rx", "ssdr_get_wb_rx_state", "ssdr_get_wb_rx_consts",
                        "ssdr_get_wb_rx_sam_carrier", "ssdr_run_wb_rx_playbuffer", "ssdr_wb_rx_stats", "ssdr_set_subrx_stages", "ssdr_get_subrx_stages",
                        "ssdr_subrx_stage_results", "ssdr_get_subrx_stage_state", "ssdr_set_wb_rx_stages", "ssdr_get_wb_rx_stages",
-                       "ssdr_wb_rx_stage_results", "ssdr_get_wb_rx_stage_state", "ssdr_rx_tail_stats")      # entry points a library named by SSDR_LIB_PATH (A/B builds only) may predate
+                       "ssdr_wb_rx_stage_results", "ssdr_get_wb_rx_stage_state", "ssdr_rx_tail_stats", "ssdr_set_subrx_noise_blanker",
+                       "ssdr_get_subrx_noise_blanker", "ssdr_subrx_nb_mask", "ssdr_set_wb_rx_noise_blanker", "ssdr_get_wb_rx_noise_blanker",
+                       "ssdr_wb_rx_nb_mask")      # entry points a library named by SSDR_LIB_PATH (A/B builds only) may predate
 
 
 def _load():

@@ -58,6 +58,7 @@ struct BankOut {
     uint8_t *d_flags = nullptr; size_t flags_cap = 0;             // [rows][frames]
     uint8_t *d_closed = nullptr; size_t closed_cap = 0;           // [rows][frames] the tail's closed flags (ssdr_set_subrx_stages / _wb_rx_stages)
     uint8_t *d_adpcm = nullptr; size_t adpcm_cap = 0;             // [rows][frames * 256] ... and its SND payloads; capacity in frames
+    uint8_t *d_nb_mask = nullptr; size_t nb_mask_cap = 0;         // [rows][frames * 64 D] the rows' blank masks (ssdr_set_subrx_noise_blanker / _wb_rx_); capacity in frames at D = 4
     uint32_t run_rows = 0, run_frames = 0;                        // extent of the last run
 };
 struct Batch {
@@ -137,6 +138,13 @@ struct RxBank {
     int32_t *d_de = nullptr;                            // [cap] S
     int32_t *d_enc = nullptr;                           // [cap][2] the encoder's (index, prev)
     SsdrRxTailRow *d_tail = nullptr;                    // [cap]
+    // the rows' noise blankers (ssdr_set_subrx_noise_blanker / ssdr_set_wb_rx_noise_blanker): host settings at the first call, device
+    // memory at the first nonzero setting; while no row blanks the bank launches the kernels it launched before the setters existed
+    std::vector<uint32_t> h_nb_gate_us, h_nb_thresh;    // [rows] as set, 0: off (empty: never set -- everybody off)
+    uint32_t nb_on = 0;                                 // rows whose blanker is on
+    bool nb_valid = false;                              // the last audio run was the ctx's own batch's, blanking, with list and settings as they are
+    uint32_t nb_run_decim = 1;                          // D of that run (the mask's row length)
+    SsdrNbChan *d_nb = nullptr;                         // [cap] gate in samples, threshold, carried sums and samples left to blank
     uint32_t rows() const { return (uint32_t)h_consts.size(); }
 };
 
@@ -414,6 +422,7 @@ static void free_owned(ssdr_ctx *c)
         c->d_wv_taps, c->d_wv_consts, c->d_wv_acc, c->d_wv_stream, c->d_wv_wf,                                        // waterfall views
         c->own.sub.d_pcm, c->own.sub.d_rssi, c->own.sub.d_flags, c->own.sub.d_closed, c->own.sub.d_adpcm,             // sub-receivers: the own batch's results,
         c->sub.d_sq, c->sub.d_de, c->sub.d_enc, c->sub.d_tail,                                                        // ... their tail's state,
+        c->own.sub.d_nb_mask, c->sub.d_nb, c->own.wr.d_nb_mask, c->wr.d_nb,                                           // ... both banks' blankers: masks and state,
         c->sub.d_state[0], c->sub.d_state[1], c->sub.d_hist[0], c->sub.d_hist[1], c->sub.d_phist[0], c->sub.d_phist[1], c->sub.d_phist_alt,
         c->sub.d_consts, c->sub.d_taps, c->sub.d_parent, c->sub.d_play, c->sub.d_play_out,                            // ... their bank: state, constants, play_buffer
         c->d_chz_taps, c->d_chz_hist, c->d_chz_in,                                                                    // wideband channeliser
@@ -637,6 +646,10 @@ static int bank_tail_follow(ssdr_ctx *c, RxBank &bk, const std::vector<int32_t> 
 static void bank_tail_clear(RxBank &bk);
 static int bank_tail_prepare(ssdr_ctx *c, RxBank &bk, Batch &b, BankOut &out);
 static int bank_tail_launch(ssdr_ctx *c, RxBank &bk, Batch &b, BankOut &out, hipStream_t s);
+// ... and the rows' noise blankers (behind the tail)
+static int bank_nb_fresh(ssdr_ctx *c, RxBank &bk, const std::vector<uint32_t> &rows);
+static int bank_nb_follow(ssdr_ctx *c, RxBank &bk, const std::vector<int32_t> &kept);
+static void bank_nb_clear(RxBank &bk);
 // the state arrays (two sets: a new list is built in the other one, so that a receiver that stays keeps its stream), constants, parents
 static int bank_alloc(ssdr_ctx *c, RxBank &bk)
 {
@@ -668,6 +681,7 @@ static void bank_clear(RxBank &bk)
     bk.h_started.clear();
     bk.run_valid = false;
     bank_tail_clear(bk);
+    bank_nb_clear(bk);
 }
 static bool every_row(uint32_t) { return true; }
 // the rows that `selected(row)` names start over; the stream is waited for only if there was one
@@ -685,7 +699,8 @@ template <class F> static int bank_restart(ssdr_ctx *c, RxBank &bk, F selected)
         rows.push_back(j);
     }
     if (!rows.empty()) HIP_TRY(hipStreamSynchronize(c->stream));
-    return bank_tail_fresh(c, bk, rows, true, true, false);     // their squelch state and S as well, as a channel's; the encoder is the link's
+    SSDR_TRY(bank_tail_fresh(c, bk, rows, true, true, false));  // their squelch state and S as well, as a channel's; the encoder is the link's
+    return bank_nb_fresh(c, bk, rows);                          // ... and their blankers, the gate at the current input rate
 }
 // the sub-receivers of channels [first, first + count) start over (ssdr_reset_state)
 static int subrx_restart(ssdr_ctx *c, uint32_t first, uint32_t count)
@@ -719,11 +734,16 @@ static int bank_prepare(ssdr_ctx *c, RxBank &bk, Batch &b, BankOut &out)
     const size_t n = bk.rows();
     if (!n) return SSDR_OK;
     bk.run_valid = false;
+    bk.nb_valid = false;
     const size_t need = n * b.in_frames;
     if (out.pcm_cap < need || out.rssi_cap < need || out.flags_cap < need) SSDR_TRY(drain_audio(c));
     SSDR_TRY(grow(c, b, out.d_pcm, out.pcm_cap, need, SSDR_FRAME * sizeof(int16_t)));
     SSDR_TRY(grow(c, b, out.d_rssi, out.rssi_cap, need, sizeof(float)));
     SSDR_TRY(grow(c, b, out.d_flags, out.flags_cap, need, 1));
+    if (bk.nb_on) {                                             // one bit per input sample of every row
+        if (out.nb_mask_cap < need) SSDR_TRY(drain_audio(c));
+        SSDR_TRY(grow(c, b, out.d_nb_mask, out.nb_mask_cap, need, 64 * 4));
+    }
     return bank_tail_prepare(c, bk, b, out);
 }
 // Every receiver of the bank advanced by the batch, on the audio stage's stream `s` behind the channels' kernels: one launch, timed
@@ -745,11 +765,18 @@ static int bank_launch(ssdr_ctx *c, RxBank &bk, Batch &b, BankOut &out, const Ss
     a.parent = bk.d_parent;
     bool any_sam = false;                                  // rows in synchronous AM run the mode's own instantiation beside the others'
     for (const ssdr_chan_consts &k : bk.h_consts) any_sam = any_sam || k.mode == SSDR_MODE_SAM;
+    const SsdrSubNbArgs na = {a.au, a.parent, bk.d_nb, out.d_nb_mask};
     SSDR_TRY(stage_launch(c, bk.timed, s, [&]() -> int {
+        if (bk.nb_on) {                                    // once a row blanks: every row on the blanker twins, the mode's rows in the same launch
+            HIP_TRY(ssdr_launch_audio_sub_nb(na, c->decim, s));
+            return SSDR_OK;
+        }
         HIP_TRY(ssdr_launch_audio_sub(a, c->decim, s));
         if (any_sam) HIP_TRY(ssdr_launch_audio_sub_sam(a, s));
         return SSDR_OK;
     }));
+    bk.nb_valid = bk.nb_on && &b == &c->own;
+    bk.nb_run_decim = c->decim;
     std::fill(bk.h_started.begin(), bk.h_started.end(), (uint8_t)1);
     out.run_rows = n;
     out.run_frames = b.in_frames;
@@ -792,6 +819,7 @@ static int bank_rebuild(ssdr_ctx *c, RxBank &bk, const std::vector<T> &old, cons
     if (parent) HIP_TRY(hipMemcpyAsync(bk.d_parent, parent, count * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
     SSDR_TRY(bank_upload_consts(c, bk, k, taps));           // (waits: `fresh` and `parent` are host memory)
     SSDR_TRY(bank_tail_follow(c, bk, kept, k));             // settings and stage state go with the receivers (bk.h_consts: still the old modes)
+    SSDR_TRY(bank_nb_follow(c, bk, kept));                  // ... and so do the blankers', whatever the modes do
     bk.h_consts = k;
     bk.h_started = started;
     bk.set = to;
@@ -1918,6 +1946,128 @@ static int bank_stage_state(ssdr_ctx *c, const RxBank &bk, uint32_t first_row, u
     if (enc) SSDR_TRY(copy_out(c, enc, bk.d_enc + 2 * (size_t)first_row, (size_t)count * 2 * sizeof(int32_t), 0, kSyncLater));
     HIP_TRY(hipStreamSynchronize(c->stream));
     return SSDR_OK;
+}
+
+// ---- the banks' noise blankers: a blanker per row, inside the sub-receiver kernels' twins (ssdr_audio.hip; ssdr_set_subrx_noise_blanker /
+// ssdr_set_wb_rx_noise_blanker).  The rules are the tail's, not the channel setter's: a row restarts only where its setting differs.
+static SsdrNbChan bank_nb_chan(const ssdr_ctx *c, uint32_t gate_us, uint32_t thresh)
+{
+    SsdrNbChan q;
+    memset(&q, 0, sizeof q);
+    if (thresh && ssdr_nb_gate_samples(gate_us, c->decim, c->kiwi_rate, &q.gate) == SSDR_OK) q.thresh = thresh;
+    else q.gate = 0;
+    return q;
+}
+// the blankers of `rows` start over with the settings the rows hold, the gate at the current input rate; there when the call returns.
+// Before the first nonzero setting there is nothing to start over.
+static int bank_nb_fresh(ssdr_ctx *c, RxBank &bk, const std::vector<uint32_t> &rows)
+{
+    if (rows.empty() || !bk.d_nb || bk.h_nb_thresh.empty()) return SSDR_OK;
+    SSDR_TRY(join_audio(c));
+    std::vector<SsdrNbChan> q(rows.size());
+    for (size_t i = 0; i < rows.size(); i++) {
+        const uint32_t j = rows[i];
+        q[i] = bank_nb_chan(c, bk.h_nb_gate_us[j], bk.h_nb_thresh[j]);
+        HIP_TRY(hipMemcpyAsync(bk.d_nb + j, &q[i], sizeof q[i], hipMemcpyHostToDevice, c->stream));
+    }
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return SSDR_OK;
+}
+static void bank_nb_clear(RxBank &bk)
+{
+    bk.h_nb_gate_us.clear();
+    bk.h_nb_thresh.clear();
+    bk.nb_on = 0;
+    bk.nb_valid = false;
+}
+// A new list takes the bank over (bank_rebuild): row j of it is old row kept[j], or a new receiver (-1).  Setting and blanker state
+// follow a kept receiver, a mode change included; a new one is off.  As the tail's state: one array, a round trip through the host.
+static int bank_nb_follow(ssdr_ctx *c, RxBank &bk, const std::vector<int32_t> &kept)
+{
+    if (bk.h_nb_thresh.empty()) return SSDR_OK;            // never set: everybody is off, and stays so
+    const size_t n_old = bk.h_nb_thresh.size(), n = kept.size();
+    bool same = n == n_old;
+    for (size_t j = 0; same && j < n; j++) same = kept[j] == (int32_t)j;
+    if (same) return SSDR_OK;                               // every row is the receiver it was: nothing moves
+    std::vector<uint32_t> gate(n, 0u), th(n, 0u);
+    uint32_t on = 0;
+    for (size_t j = 0; j < n; j++)
+        if (kept[j] >= 0) { gate[j] = bk.h_nb_gate_us[(size_t)kept[j]]; th[j] = bk.h_nb_thresh[(size_t)kept[j]]; on += th[j] != 0; }
+    if (bk.d_nb) {
+        SSDR_TRY(join_audio(c));
+        std::vector<SsdrNbChan> old(n_old), q(n);
+        SSDR_TRY(copy_out(c, old.data(), bk.d_nb, n_old * sizeof(SsdrNbChan), 0, kSyncAlways));
+        for (size_t j = 0; j < n; j++) {
+            if (kept[j] >= 0) q[j] = old[(size_t)kept[j]];
+            else memset(&q[j], 0, sizeof q[j]);
+        }
+        HIP_TRY(hipMemcpyAsync(bk.d_nb, q.data(), n * sizeof(SsdrNbChan), hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(hipStreamSynchronize(c->stream));
+    }
+    bk.h_nb_gate_us = gate;
+    bk.h_nb_thresh = th;
+    bk.nb_on = on;
+    bk.nb_valid = false;
+    return SSDR_OK;
+}
+// behind ssdr_set_subrx_noise_blanker / ssdr_set_wb_rx_noise_blanker: all or nothing; a row whose setting differs starts over alone
+static int bank_set_nb(ssdr_ctx *c, RxBank &bk, const uint32_t *gate_us, const uint32_t *thresh, uint32_t count)
+{
+    if (count != bk.rows() || (count && (!gate_us || !thresh))) return SSDR_EINVAL;
+    bool any = false;
+    for (uint32_t j = 0; j < count; j++) {
+        if (gate_us[j] == 0 || thresh[j] == 0) continue;    // off
+        if (gate_us[j] > 10000 || thresh[j] < 2 || thresh[j] > 1000) return SSDR_EINVAL;
+        any = true;
+    }
+    if (!count) return SSDR_OK;
+    HIP_TRY(hipSetDevice(c->device));
+    if (any && !bk.d_nb) {                                  // the first nonzero setting: every row the array can hold off, zero state
+        HIP_TRY(hipMalloc(&bk.d_nb, (size_t)bk.cap * sizeof(SsdrNbChan)));
+        HIP_TRY(hipMemsetAsync(bk.d_nb, 0, (size_t)bk.cap * sizeof(SsdrNbChan), c->stream));
+        HIP_TRY(hipStreamSynchronize(c->stream));
+    }
+    if (bk.h_nb_thresh.empty()) {                           // the first call on this list: whatever an earlier list left in the array goes
+        if (bk.d_nb) {
+            SSDR_TRY(join_audio(c));
+            HIP_TRY(hipMemsetAsync(bk.d_nb, 0, (size_t)bk.cap * sizeof(SsdrNbChan), c->stream));
+            HIP_TRY(hipStreamSynchronize(c->stream));
+        }
+        bk.h_nb_gate_us.assign(count, 0u);
+        bk.h_nb_thresh.assign(count, 0u);
+    }
+    std::vector<uint32_t> rows;
+    for (uint32_t j = 0; j < count; j++) {
+        const bool is = gate_us[j] != 0 && thresh[j] != 0;
+        const uint32_t g = is ? gate_us[j] : 0u, t = is ? thresh[j] : 0u;
+        if (g == bk.h_nb_gate_us[j] && t == bk.h_nb_thresh[j]) continue;
+        bk.nb_on = bk.nb_on - (bk.h_nb_thresh[j] ? 1u : 0u) + (is ? 1u : 0u);
+        bk.h_nb_gate_us[j] = g;
+        bk.h_nb_thresh[j] = t;
+        rows.push_back(j);
+    }
+    if (rows.empty()) return SSDR_OK;
+    bk.nb_valid = false;
+    return bank_nb_fresh(c, bk, rows);
+}
+static int bank_get_nb(const RxBank &bk, uint32_t *gate_us, uint32_t *thresh, uint32_t *count)
+{
+    if (!count) return SSDR_EINVAL;
+    *count = bk.rows();
+    for (uint32_t j = 0; j < bk.rows(); j++) {
+        if (gate_us) gate_us[j] = bk.h_nb_gate_us.empty() ? 0u : bk.h_nb_gate_us[j];
+        if (thresh) thresh[j] = bk.h_nb_thresh.empty() ? 0u : bk.h_nb_thresh[j];
+    }
+    return SSDR_OK;
+}
+// the rows' blank masks of the last run (a row whose blanker is off never triggers: the kernel wrote its zeros)
+static int bank_nb_mask(ssdr_ctx *c, const RxBank &bk, const BankOut &out, uint8_t *mask_out, int out_is_device)
+{
+    if (!mask_out) return SSDR_EINVAL;
+    if (!bk.rows() || !bk.nb_on || !bk.run_valid || !bk.nb_valid || !out.d_nb_mask) return SSDR_ESTATE;
+    HIP_TRY(hipSetDevice(c->device));
+    SSDR_TRY(join_audio(c));
+    return copy_out(c, mask_out, out.d_nb_mask, (size_t)out.run_rows * out.run_frames * 64 * bk.nb_run_decim, out_is_device, kSyncAlways);
 }
 
 // ---- waterfall views: a per-channel zoom stage beside the waterfall stage (ssdr_set_wf_views) ---------------------------------
@@ -4013,6 +4163,21 @@ int ssdr_get_subrx_stage_state(ssdr_ctx *c, uint32_t first_row, uint32_t count, 
     return c ? bank_stage_state(c, c->sub, first_row, count, deemp_S, adpcm_state) : SSDR_EINVAL;
 } SSDR_UNGUARD
 
+int ssdr_set_subrx_noise_blanker(ssdr_ctx *c, const uint32_t *gate_us, const uint32_t *thresh, uint32_t count) SSDR_GUARD
+{
+    return c ? bank_set_nb(c, c->sub, gate_us, thresh, count) : SSDR_EINVAL;
+} SSDR_UNGUARD
+
+int ssdr_get_subrx_noise_blanker(ssdr_ctx *c, uint32_t *gate_us, uint32_t *thresh, uint32_t *count) SSDR_GUARD
+{
+    return c ? bank_get_nb(c->sub, gate_us, thresh, count) : SSDR_EINVAL;
+} SSDR_UNGUARD
+
+int ssdr_subrx_nb_mask(ssdr_ctx *c, uint8_t *mask_out, int out_is_device) SSDR_GUARD
+{
+    return c ? bank_nb_mask(c, c->sub, c->own.sub, mask_out, out_is_device) : SSDR_EINVAL;
+} SSDR_UNGUARD
+
 int ssdr_rx_tail_stats(ssdr_ctx *c, int bank, float *total_ms, uint32_t *launches, int reset) SSDR_GUARD
 {
     if (bank != 0 && bank != 1) return SSDR_EINVAL;
@@ -4608,6 +4773,21 @@ int ssdr_wb_rx_stage_results(ssdr_ctx *c, uint8_t *closed, uint8_t *adpcm, int o
 int ssdr_get_wb_rx_stage_state(ssdr_ctx *c, uint32_t first_row, uint32_t count, int32_t *deemp_S, int32_t *adpcm_state) SSDR_GUARD
 {
     return c ? bank_stage_state(c, c->wr, first_row, count, deemp_S, adpcm_state) : SSDR_EINVAL;
+} SSDR_UNGUARD
+
+int ssdr_set_wb_rx_noise_blanker(ssdr_ctx *c, const uint32_t *gate_us, const uint32_t *thresh, uint32_t count) SSDR_GUARD
+{
+    return c ? bank_set_nb(c, c->wr, gate_us, thresh, count) : SSDR_EINVAL;
+} SSDR_UNGUARD
+
+int ssdr_get_wb_rx_noise_blanker(ssdr_ctx *c, uint32_t *gate_us, uint32_t *thresh, uint32_t *count) SSDR_GUARD
+{
+    return c ? bank_get_nb(c->wr, gate_us, thresh, count) : SSDR_EINVAL;
+} SSDR_UNGUARD
+
+int ssdr_wb_rx_nb_mask(ssdr_ctx *c, uint8_t *mask_out, int out_is_device) SSDR_GUARD
+{
+    return c ? bank_nb_mask(c, c->wr, c->own.wr, mask_out, out_is_device) : SSDR_EINVAL;
 } SSDR_UNGUARD
 
 int ssdr_set_wf_lines(ssdr_ctx *c, const int16_t *wf_sum, uint32_t lines) SSDR_GUARD

@@ -422,6 +422,42 @@ __global__ __launch_bounds__(SSDR_AUDIO_BLOCK) __attribute__((amdgpu_waves_per_e
                                         RowAt{a.au.iq + (uint64_t)a.parent[r] * a.au.ch_stride});
 }
 
+// The sub-receiver kernels with the noise blanker (ssdr_set_subrx_noise_blanker / ssdr_set_wb_rx_noise_blanker): once a row of a bank
+// blanks, the whole bank runs on these -- a row whose blanker is off never triggers, bit for bit the kernels above -- with the ROW's
+// blanker state and the ROW's mask (a.nb, a.mask: [list_n], rows in list order; the parent's own blanker is the parent's business).
+// At 12 kHz one kernel takes the three frame paths and synchronous AM as a fourth wave-uniform branch: a launch, not occupancy, is
+// what a bank of at most SSDR_SUBRX_MAX waves pays for.  Registers: profiles/rx_nb_isa_spills.txt.
+__global__ __launch_bounds__(SSDR_AUDIO_BLOCK) __attribute__((amdgpu_waves_per_eu(1, 4))) void ssdr_audio_sub_nb_kernel(SsdrSubNbArgs a)
+{
+    __shared__ __attribute__((aligned(16))) float2 s_z[NOCT * OCT];
+    __shared__ __attribute__((aligned(16))) float s_taps[SSDR_NTAP_MAX + 8];
+    const int l = threadIdx.x;
+    const uint32_t r = blockIdx.x;
+    if (r >= a.au.list_n) return;
+    const RowAt in_row = {a.au.iq + (uint64_t)a.parent[r] * a.au.ch_stride};
+    const ssdr_chan_consts kc = a.au.consts[r];
+    uint8_t *mask = a.mask + (uint64_t)r * a.au.n_frames * 64;
+    const int path = ssdr_audio_path(kc);                // wave-uniform (SSDR_MODE_SAM compiles to the general path)
+    if (kc.mode == SSDR_MODE_SAM) channel_frames<PATH_GENERAL, NoTap, true, RowAt, true>(a.au, r, l, kc, s_z, s_taps, NoTap(), a.nb, mask, in_row);
+    else if (path == SSDR_PATH_GENERAL) channel_frames<PATH_GENERAL, NoTap, true, RowAt>(a.au, r, l, kc, s_z, s_taps, NoTap(), a.nb, mask, in_row);
+    else if (path == SSDR_PATH_DELAY4) channel_frames<PATH_DELAY4, NoTap, true, RowAt>(a.au, r, l, kc, s_z, s_taps, NoTap(), a.nb, mask, in_row);
+    else channel_frames<PATH_AM_RAW, NoTap, true, RowAt>(a.au, r, l, kc, s_z, s_taps, NoTap(), a.nb, mask, in_row);
+}
+
+template <int D>
+__global__ __launch_bounds__(SSDR_AUDIO_BLOCK) __attribute__((amdgpu_waves_per_eu(dec_phased(D) ? 1 : 2, dec_phased(D) ? 2 : 8))) void ssdr_audio_sub_dec_nb_kernel(SsdrSubNbArgs a)
+{
+    constexpr int HOCT_S = SSDR_HIST / D / 8;
+    __shared__ __attribute__((aligned(16))) float2 s_z[dec_streams_per_phase(D) * (HOCT_S + 64) * OCT];
+    __shared__ __attribute__((aligned(16))) float2 s_h[dec_phased(D) ? D * HOCT_S * OCT : 1];
+    __shared__ __attribute__((aligned(16))) float s_taps[SSDR_NTAP_MAX + 8];
+    const int l = threadIdx.x;
+    const uint32_t r = blockIdx.x;
+    if (r >= a.au.list_n) return;
+    channel_frames_dec<D, true, RowAt>(a.au, r, l, a.au.consts[r], s_z, s_h, s_taps, a.nb, a.mask + (uint64_t)r * a.au.n_frames * 64 * D,
+                                       RowAt{a.au.iq + (uint64_t)a.parent[r] * a.au.ch_stride});
+}
+
 // ---------------------------------------------------------------- synthetic IQ (bench input)
 SSDR_DEV uint32_t fmix32(uint32_t h)
 {
@@ -571,6 +607,17 @@ hipError_t ssdr_launch_audio_sub_sam(const SsdrSubArgs &a, hipStream_t stream)
 {
     if (!a.au.list_n) return hipSuccess;
     hipLaunchKernelGGL(ssdr_audio_sub_sam_kernel, dim3(a.au.list_n), dim3(SSDR_AUDIO_BLOCK), 0, stream, a);
+    return hipGetLastError();
+}
+
+hipError_t ssdr_launch_audio_sub_nb(const SsdrSubNbArgs &a, uint32_t decim, hipStream_t stream)
+{
+    if (!a.au.list_n) return hipSuccess;
+    const dim3 grid(a.au.list_n), block(SSDR_AUDIO_BLOCK);
+    if (decim == 1) hipLaunchKernelGGL(ssdr_audio_sub_nb_kernel, grid, block, 0, stream, a);
+    else if (decim == 2) hipLaunchKernelGGL(ssdr_audio_sub_dec_nb_kernel<2>, grid, block, 0, stream, a);
+    else if (decim == 4) hipLaunchKernelGGL(ssdr_audio_sub_dec_nb_kernel<4>, grid, block, 0, stream, a);
+    else return hipErrorInvalidValue;
     return hipGetLastError();
 }
 

@@ -65,6 +65,9 @@ struct SsdrNbArgs { SsdrAudioArgs au; SsdrNbChan *nb; uint8_t *mask; };
 // the audio kernels over a list of sub-receivers (ssdr_audio_sub_kernel / ssdr_audio_sub_dec_kernel, ssdr_set_subrx): row r of the
 // chain's arguments -- constants, taps, state, history, PCM, RSSI, flags, all [list_n] -- reads row parent[r] of au.iq
 struct SsdrSubArgs { SsdrAudioArgs au; const uint32_t *parent; };
+// the same with the noise blanker (ssdr_audio_sub_nb_kernel / ssdr_audio_sub_dec_nb_kernel, ssdr_set_subrx_noise_blanker): the ROWS'
+// blanker state nb [list_n] and blank masks [list_n][n_frames * 64 D]; a row whose blanker is off (gate = thresh = 0) never triggers
+struct SsdrSubNbArgs { SsdrAudioArgs au; const uint32_t *parent; SsdrNbChan *nb; uint8_t *mask; };
 // frame paths of the audio kernel (ssdr_audio.hip): chosen per channel from its compiled constants (SSDR_MODE_SAM compiles with
 // fir_flags 0: always the general path)
 enum { SSDR_PATH_GENERAL = 0, SSDR_PATH_DELAY4 = 1, SSDR_PATH_AM_RAW = 2, SSDR_PATH_COUNT = 3 };
@@ -344,6 +347,7 @@ hipError_t ssdr_launch_audio_nb(const SsdrNbArgs &a, int path, hipStream_t strea
 hipError_t ssdr_launch_audio_dec_nb(const SsdrNbArgs &a, uint32_t decim, hipStream_t stream);
 hipError_t ssdr_launch_audio_sub(const SsdrSubArgs &a, uint32_t decim, hipStream_t stream);   // every row of the list, any path (decim 1) or D = 2 / 4
 hipError_t ssdr_launch_audio_sub_sam(const SsdrSubArgs &a, hipStream_t stream);               // the list's SSDR_MODE_SAM rows, which the kernel above leaves alone
+hipError_t ssdr_launch_audio_sub_nb(const SsdrSubNbArgs &a, uint32_t decim, hipStream_t stream);   // every row, SSDR_MODE_SAM rows included: one launch
 hipError_t ssdr_launch_synth(const SsdrSynthArgs &a, hipStream_t stream);
 hipError_t ssdr_launch_sqrt_selftest(unsigned long long *mismatch, hipStream_t stream);
 hipError_t ssdr_launch_sqrt_values(const float *in, float *out_scaled, float *out_int, uint32_t n, hipStream_t stream);

@@ -535,6 +535,27 @@ class SsdrEngine:
         check(getattr(lib, name)(self._ctx, closed.ctypes.data, adpcm.ctypes.data, 0), name)
         return closed, adpcm
 
+    def _bank_set_nb(self, bank, gates, threshs):
+        name = "ssdr_set_%s_noise_blanker" % bank[0]
+        if np.size(gates) != np.size(threshs):
+            raise ValueError("%s: %d gates for %d thresholds" % (name, np.size(gates), np.size(threshs)))
+        n = int(np.size(gates))
+        g, t = _nb_array(np.ravel(gates), n, "gate"), _nb_array(np.ravel(threshs), n, "threshold")
+        check(getattr(lib, name)(self._ctx, g.ctypes.data if n else None, t.ctypes.data if n else None, n), name)
+
+    def _bank_nb(self, bank):
+        name = "ssdr_get_%s_noise_blanker" % bank[0]
+        n = C.c_uint32(0)
+        g, t = np.zeros(bank[2], np.uint32), np.zeros(bank[2], np.uint32)
+        check(getattr(lib, name)(self._ctx, g.ctypes.data, t.ctypes.data, C.byref(n)), name)
+        return [(int(a), int(b)) for a, b in zip(g[:n.value], t[:n.value])]
+
+    def _bank_nb_mask(self, bank):
+        name = "ssdr_%s_nb_mask" % bank[0]
+        out = np.empty((self._bank_count(bank), self.audio_frames * L.FRAME * self.decim // 8), np.uint8)
+        check(getattr(lib, name)(self._ctx, out.ctypes.data, 0), name)
+        return out
+
     _STAGE_STATE_ROWS = (((), np.int32), ((2,), np.int32))
     _STATE_ROWS = (((), STATE_DTYPE), ((L.HIST, 2), np.int16))
     _CARRIER_ROWS = (((), np.float32), ((), np.float32))
@@ -601,6 +622,22 @@ class SsdrEngine:
     def subrx_stage_state(self, first=0, count=None):
         """-> (S int32 [count], (index, prev) int32 [count, 2]): de-emphasis and encoder state of rows [first, first + count)"""
         return self._bank_read(self._SUBRX, "stage_state", first, count, *self._STAGE_STATE_ROWS)
+
+    def set_subrx_noise_blanker(self, gates, threshs):
+        """The sub-receivers' impulse noise blankers ("SET nb=<gate_us> th=<thresh>" on a sub-receiver's stream): one gate_us and one thresh
+        per row in list order, ranges as set_noise_blanker's, either 0 = off.  A row whose setting differs from its current one starts
+        over; every other keeps its blanker state.  A value that is no uint32 raises ValueError before the library is called; what the
+        library refuses (another count than the list's, a value out of range) raises SsdrError (SSDR_EINVAL).  Either way nothing changes."""
+        self._bank_set_nb(self._SUBRX, gates, threshs)
+
+    def subrx_noise_blanker(self):
+        """-> [(gate_us, thresh), ...] the sub-receivers' blanker settings in list order, (0, 0) = off"""
+        return self._bank_nb(self._SUBRX)
+
+    def subrx_nb_mask(self):
+        """-> uint8 [n_sub, n_frames*512*D/8]: the samples the rows' blankers zeroed in the last run_audio / run_chain, packed as
+        audio_nb_mask's (rows whose blanker is off: 0)"""
+        return self._bank_nb_mask(self._SUBRX)
 
     def rx_tail_stats(self, bank, reset=False):
         """-> (total_ms, launches) of the fused squelch / de-emphasis / encoder launch of a bank ("sub" or "tuned") since the last reset
@@ -812,6 +849,18 @@ class SsdrEngine:
     def wb_rx_stage_state(self, first=0, count=None):
         """-> (S, (index, prev)) of rows [first, first + count), as subrx_stage_state"""
         return self._bank_read(self._WB_RX, "stage_state", first, count, *self._STAGE_STATE_ROWS)
+
+    def set_wb_rx_noise_blanker(self, gates, threshs):
+        """The tuned receivers' impulse noise blankers, as set_subrx_noise_blanker"""
+        self._bank_set_nb(self._WB_RX, gates, threshs)
+
+    def wb_rx_noise_blanker(self):
+        """-> [(gate_us, thresh), ...] the tuned receivers' blanker settings in list order, as subrx_noise_blanker"""
+        return self._bank_nb(self._WB_RX)
+
+    def wb_rx_nb_mask(self):
+        """-> uint8 [n_rx, n_frames*512*D/8]: the tuned receivers' blank masks of the last run, as subrx_nb_mask"""
+        return self._bank_nb_mask(self._WB_RX)
 
     def audio_iq(self):
         """-> int16 [n_ch, n_frames*512, 2]: I,Q of the channels in "iq" mode for the last run_audio (rows of other modes: 0)"""

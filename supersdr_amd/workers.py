@@ -261,6 +261,8 @@ class IQHub:
     rx_stages=True gives the extra receivers (open_sub, open_tuned) squelch, de-emphasis and SND compression of their own
     (set_rx_squelch, set_rx_deemphasis, set_rx_compression; ssdr_set_subrx_stages / ssdr_set_wb_rx_stages): without it those
     methods refuse before the engine is touched and the hub sends the engine nothing it did not send before they existed.
+    rx_blanker=True, independent of rx_stages, gives them the impulse noise blanker (set_rx_noise_blanker; ssdr_set_subrx_noise_blanker /
+    ssdr_set_wb_rx_noise_blanker), in front of the receiver's channel filter as a channel's is; the same opt-in rule.
     `batch_superframes=K` runs K superframes per GPU call (K lines + 2K audio frames per channel and call): latency for
     launch efficiency at very large channel counts.  `exact_bins=True`: the waterfall stage in float64 (ssdr_set_exact_bins).  `copy_threads=T` splits feed_block's copy of a large block over T threads (default: up to 8 on hubs of 8192+ receivers).
     """
@@ -269,7 +271,8 @@ class IQHub:
 
     def __init__(self, n_channels, device=0, engine=None, max_queue=64, gpu_post=True, kiwi_rate=12000, trace_rows=0,
                  backlog_superframes=8, stall_superframes=4, pipeline=False, depth=3, hop=1024, zoom=1, lazy=None,
-                 batch_superframes=1, wire=False, copy_threads=None, exact_bins=False, lazy_out=False, listen=False, rx_stages=False):
+                 batch_superframes=1, wire=False, copy_threads=None, exact_bins=False, lazy_out=False, listen=False, rx_stages=False,
+                 rx_blanker=False):
         self.n_ch = int(n_channels)
         # argument combinations that cannot work are refused BEFORE an engine (a GPU context) exists
         self._lazy = (self.n_ch > self.LAZY_ABOVE) if lazy is None else bool(lazy)
@@ -389,6 +392,8 @@ class IQHub:
         self._rx_stages = bool(rx_stages)
         self._rx_tables = {"sub": self._subs, "tuned": self._tuned}
         self._rx_st = {"sub": {}, "tuned": {}}
+        self._rx_blanker = bool(rx_blanker)
+        self._rx_nb = {"sub": {}, "tuned": {}}       # id -> (gate_us, thresh) of the receivers whose blanker somebody has set
         self.sub_queue, self.sub_clients = self._subs.queue, self._subs.clients
         self.tuned_queue, self.tuned_clients = self._tuned.queue, self._tuned.clients
         self.scope_queue, self.scope_clients = self._scopes.queue, self._scopes.clients
@@ -684,6 +689,7 @@ class IQHub:
             raise ValueError("this engine has no sub-receivers (set_subrx)")
         self.engine.set_subrx([(sid,) + rows[sid] for sid in sorted(rows)])
         self._resend_rx_stages("sub", rows)
+        self._resend_rx_nb("sub", rows)
 
     def _check_sub_params(self, p):
         if p.mode == L.MODE_IQ:
@@ -721,6 +727,7 @@ class IQHub:
         with self._lock:
             self._subs.close(int(sid))
             self._rx_st["sub"].pop(int(sid), None)
+            self._rx_nb["sub"].pop(int(sid), None)
 
     # ---- tuned receivers: demodulators at any frequency of a channeliser's wide stream (ssdr_set_wb_rx)
     def tuned(self, tid):
@@ -757,6 +764,7 @@ class IQHub:
         except L.SsdrError as e:
             raise ValueError("tuned receivers refused: %s" % e)
         self._resend_rx_stages("tuned", rows)
+        self._resend_rx_nb("tuned", rows)
 
     def open_tuned(self, stream, offset_hz, params=None):
         """A tuned receiver on wide stream `stream`: a DDC at a row's rate centred offset_hz from the stream's centre -- anywhere, not
@@ -796,15 +804,19 @@ class IQHub:
         with self._lock:
             self._tuned.close(int(tid))
             self._rx_st["tuned"].pop(int(tid), None)
+            self._rx_nb["tuned"].pop(int(tid), None)
 
     # ---- squelch, de-emphasis and SND compression of the extra receivers (ssdr_set_subrx_stages / ssdr_set_wb_rx_stages): one
     # implementation for both families, rx = ("sub", sid) or ("tuned", tid)
     _RX_OFF = ((0, 0, 0, 0), (0, 0), 0)
     _RX_SETTERS = {"sub": "set_subrx_stages", "tuned": "set_wb_rx_stages"}
 
-    def _rx(self, rx):
-        """-> (family, id) of a receiver that is open; ValueError without rx_stages=True, before the engine is touched"""
-        if not self._rx_stages:
+    def _rx(self, rx, blanker=False):
+        """-> (family, id) of a receiver that is open; ValueError without rx_stages=True (the blanker: rx_blanker=True), before the
+        engine is touched"""
+        if blanker and not self._rx_blanker:
+            raise ValueError("the noise blanker of a sub-receiver or tuned receiver needs a hub built with rx_blanker=True")
+        if not blanker and not self._rx_stages:
             raise ValueError("squelch, de-emphasis and compression of a sub-receiver or tuned receiver need a hub built with rx_stages=True")
         kind, rid = rx
         if kind not in self._rx_tables:
@@ -879,6 +891,41 @@ class IQHub:
             old = self._rx_st[kind].get(rid, self._RX_OFF)
             if bool(on) != bool(old[2]):
                 self._set_rx_stage(kind, rid, (old[0], old[1], 1 if on else 0))
+
+    # ---- the extra receivers' noise blanker (ssdr_set_subrx_noise_blanker / ssdr_set_wb_rx_noise_blanker): the same shape
+    _RX_NB_SETTERS = {"sub": "set_subrx_noise_blanker", "tuned": "set_wb_rx_noise_blanker"}
+
+    def _rx_nb_arrays(self, ids, settings):
+        rows = [settings.get(i, (0, 0)) for i in ids]
+        return [g for g, _ in rows], [t for _, t in rows]
+
+    def _resend_rx_nb(self, kind, rows):
+        """behind a list the hub has just sent: the family's blanker settings in the new list's order, as _resend_rx_stages"""
+        if self._rx_blanker and self._rx_nb[kind] and rows:
+            getattr(self.engine, self._RX_NB_SETTERS[kind])(*self._rx_nb_arrays(sorted(rows), self._rx_nb[kind]))
+
+    def rx_noise_blanker(self, rx):
+        """-> (gate_us, thresh) of an extra receiver as set, (0, 0) = off"""
+        with self._lock:
+            kind, rid = self._rx(rx, blanker=True)
+            return self._rx_nb[kind].get(rid, (0, 0))
+
+    def set_rx_noise_blanker(self, rx, gate_us, thresh):
+        """set_noise_blanker for an extra receiver, rx = ("sub", sid) or ("tuned", tid): "SET nb=<gate_us> th=<thresh>" on its stream,
+        either 0 = off.  It blanks the receiver's own input in front of its channel filter and nobody else's: not the parent channel,
+        not a sibling.  ValueError out of range and on a hub built without rx_blanker=True (before the engine is touched), and then
+        nothing changes; a changed setting restarts that receiver's blanker alone."""
+        with self._lock:
+            kind, rid = self._rx(rx, blanker=True)
+            check_noise_blanker(gate_us, thresh)
+            st = (int(gate_us), int(thresh)) if int(gate_us) and int(thresh) else (0, 0)
+            setter = getattr(self.engine, self._RX_NB_SETTERS[kind], None)
+            if setter is None:
+                raise ValueError("this engine has no noise blanker for %s (%s)" % (self._rx_tables[kind].nouns, self._RX_NB_SETTERS[kind]))
+            new = dict(self._rx_nb[kind])
+            new[rid] = st
+            setter(*self._rx_nb_arrays(self._rx_tables[kind].ids(), new))      # committed only if the engine took it
+            self._rx_nb[kind] = new
 
     def _rx_stage_results(self, name, kind, table, results):
         """-> a family's name_closed / name_adpcm of the SuperframeResult, each None unless some receiver's stage acts"""
@@ -1548,15 +1595,17 @@ class GpuStream:
     "SET mod= low_cut= high_cut= freq=" and "SET agc= ..." then go to IQHub.set_sub_params (with the same refusal of frequencies
     outside the channel's IQ band, and of mod=iq), its frames come from hub.sub_queue[sid], and close_connection closes the
     sub-receiver.  "SET compression=0" and everything without a meaning here are accepted as on any stream; "SET nb=", "SET squelch=",
-    "SET de_emp=" and "SET compression=1" raise ValueError naming the sub-receiver: they are the channel's, not built for
-    sub-receivers.
+    "SET de_emp=" and "SET compression=1" raise ValueError naming the sub-receiver: they are the channel's -- unless the hub was
+    built with rx_stages=True (squelch, de_emp, compression go to the receiver's own stages: IQHub.set_rx_squelch, ...) or
+    rx_blanker=True ("SET nb=<g> th=<t>" goes to IQHub.set_rx_noise_blanker with a channel's checks -- th= required, the ranges of
+    check_noise_blanker; "SET nb algo=..." stays ignored).
 
     tuned=tid (an SND stream; IQHub.open_tuned): the stream is that of a TUNED RECEIVER on a wide stream of the hub's channeliser;
     `channel` is that wide stream and center_khz its centre.  "SET mod= low_cut= high_cut= freq=" puts freq ANYWHERE in the wide stream:
     the receiver's DDC moves (IQHub.retune_tuned) and f_shift_hz stays 0; a frequency outside the stream raises ValueError naming
     the stream's span.  "SET agc=" goes to the receiver's parameters.  Its frames come from hub.tuned_queue[tid], close_connection
     closes the receiver, and nb / squelch / de_emp / compression=1 / mod=iq raise ValueError naming the tuned receiver, as for a
-    sub-receiver.
+    sub-receiver -- with the same two opt-ins of the hub (rx_stages=True, rx_blanker=True; mod=iq stays refused).
 
     receive_message(): server -> client frames, byte for byte in the wire format the reference parses
     (utils_supersdr.py:782-784, 1065-1074): first what the constructors wait for ("MSG audio_init audio_rate= sample_rate=",
@@ -1616,10 +1665,11 @@ class GpuStream:
             return
         kv = dict(w.split("=", 1) for w in words[1:] if "=" in w)
         rx = self._rx
-        staged = rx is not None and getattr(self.hub, "_rx_stages", False)      # a hub built with rx_stages=True: the receiver has all but the blanker
+        staged = rx is not None and getattr(self.hub, "_rx_stages", False)      # a hub built with rx_stages=True: the receiver has squelch, de-emphasis, encoder
+        blanks = rx is not None and getattr(self.hub, "_rx_blanker", False)     # ... with rx_blanker=True: the blanker
         if rx is not None and "mod" not in kv and "agc" not in kv:       # the channel's stages: an extra receiver has none of them
             for key, stage in (("nb", "noise blanker"), ("squelch", "squelch"), ("de_emp", "de-emphasis")):
-                if key in kv and not (staged and key != "nb"):
+                if key in kv and not (blanks if key == "nb" else staged):
                     raise ValueError(("SET %s= on %s %d of %s %d: " + rx.no_stage) % (key, rx.noun, rx.id, rx.on, self.channel, stage))
             if "compression" in kv and int(kv["compression"]) != 0 and not staged:
                 raise ValueError("SET compression=1 on %s %d of %s %d: a %s's frames are not ADPCM-encoded"
@@ -1635,14 +1685,17 @@ class GpuStream:
                              agc_slope=float(kv.get("slope", 0)), agc_decay=float(kv.get("decay", 4000)),
                              agc_man_gain=float(kv.get("manGain", 50)))
             self._set_params(q)
-        elif rx is not None and not (staged and ("squelch" in kv or "de_emp" in kv or "compression" in kv)):
+        elif rx is not None and not (staged and ("squelch" in kv or "de_emp" in kv or "compression" in kv)) and not (blanks and "nb" in kv):
             pass                                     # (compression=0, zoom=, ...: nothing to do for a sub-receiver or a tuned receiver)
         elif "nb" in kv:
             if "th" not in kv:
                 raise ValueError("SET nb= without th=: %r" % (msg,))
             gate, thresh = int(kv["nb"]), int(kv["th"])
             check_noise_blanker(gate, thresh)
-            self.hub.set_noise_blanker(self.channel, gate, thresh)
+            if rx is not None:
+                self.hub.set_rx_noise_blanker(rx.key, gate, thresh)
+            else:
+                self.hub.set_noise_blanker(self.channel, gate, thresh)
         elif "squelch" in kv:
             self._set_squelch(kv, msg)
         elif "de_emp" in kv:
