@@ -525,7 +525,7 @@ int ssdr_wf_view_stats(ssdr_ctx *ctx, float *total_ms, uint32_t *launches, int r
  * parameters P produces, bit for bit, the PCM, RSSI, flags and carried state (ssdr_chan_state, raw history) of a channel of a ctx
  * that is fed channel c's IQ and holds P: no new arithmetic (oracle/ssdr_oracle.py:audio_chain, oracle/ssdr_twin.c, the shipped
  * audio kernels).  The channel's noise blanker does not act on it; it has one of its own (ssdr_set_subrx_noise_blanker, further
- * down), off until set, which acts on nobody else.  No SSDR_MODE_IQ; squelch, de-emphasis and the SND encoder are its own
+ * down), off until set, which acts on nobody else.  No SSDR_MODE_IQ until ssdr_set_rx_iq (further down) turns it on; squelch, de-emphasis and the SND encoder are its own
  * (ssdr_set_subrx_stages, further down), off until set.
  *   every ssdr_run_audio and every path of ssdr_run_chain (*fused = 0, 1, 2) advances every sub-receiver by the batch;
  *   which kernel the channels get (chain_plan) does not depend on the list, and their results, state and timing are untouched.
@@ -721,7 +721,7 @@ int ssdr_read_wb_scope_windows(ssdr_ctx *ctx, uint32_t index, int16_t *iq_out, u
  * tests/wb_rx_ref.py is the definition; the kernel works in float32 in the scopes' summation order, so a row is bit-identical however
  * the stream is cut into calls and whatever else is in either list.
  * The audio is no new arithmetic: PCM, RSSI, flags and carried state (ssdr_chan_state, raw history) are bit for bit those of a
- * channel of a ctx that is fed the stored row and holds P.  Like a sub-receiver it has no SSDR_MODE_IQ, and a noise blanker
+ * channel of a ctx that is fed the stored row and holds P.  Like a sub-receiver it has no SSDR_MODE_IQ until ssdr_set_rx_iq, and a noise blanker
  * (ssdr_set_wb_rx_noise_blanker), squelch, de-emphasis and SND encoder (ssdr_set_wb_rx_stages) of its own, off until set; at D > 1 no parameters that compile to a shift path and no SSDR_MODE_SAM.
  * State rules (the sub-receivers' for the audio, the scopes' for the DDC):
  *   the DDC carries nothing: a new offset_hz of a kept receiver acts from the next push on and restarts nobody;
@@ -864,6 +864,41 @@ int ssdr_subrx_nb_mask(ssdr_ctx *ctx, uint8_t *mask_out, int out_is_device);
 int ssdr_set_wb_rx_noise_blanker(ssdr_ctx *ctx, const uint32_t *gate_us, const uint32_t *thresh, uint32_t count);
 int ssdr_get_wb_rx_noise_blanker(ssdr_ctx *ctx, uint32_t *gate_us /* may be NULL */, uint32_t *thresh /* may be NULL */, uint32_t *count);
 int ssdr_wb_rx_nb_mask(ssdr_ctx *ctx, uint8_t *mask_out, int out_is_device);
+
+/* -- SSDR_MODE_IQ for the extra receivers (sub-receivers and tuned receivers): opt-in
+ *
+ * The filtered, gain-controlled complex baseband of an extra receiver as I,Q pairs ("SET mod=iq" on its stream), at every rate the
+ * banks run at (12 kHz, 20.25 kHz, D = 2, D = 4), with or without the row's noise blanker.  No new arithmetic: a row in SSDR_MODE_IQ
+ * is, bit for bit, a channel in SSDR_MODE_IQ of an ordinary ctx with the same D and kiwi_rate that is fed the receiver's input row (a
+ * sub-receiver's: its parent channel's raw IQ; a tuned receiver's: the stored row ssdr_read_wb_rx returns), holds the receiver's
+ * parameters and is run with the same cut of the stream into calls: PCM row (it carries I), I,Q pairs (ssdr_audio_iq), RSSI, flags,
+ * carried ssdr_chan_state and FIR history.
+ * The switch: `bank` is 0 for the sub-receivers and 1 for the tuned receivers, as in ssdr_rx_tail_stats; anything else, a NULL ctx or a
+ * NULL `on` of the getter is SSDR_EINVAL.  Off is the default, and a ctx that never turns it on refuses, allocates and launches what
+ * it did before the switch existed.  While it is on, that bank's list setter (ssdr_set_subrx / ssdr_set_wb_rx) takes SSDR_MODE_IQ
+ * rows; every other check of the setter stays as it is.  SSDR_ESTATE, and then nothing changes: turning it off while the bank's list
+ * holds a row in SSDR_MODE_IQ; either direction while a pipelined feed is open, as for the list setters.  An empty list, a new
+ * channeliser, ssdr_set_decimation and ssdr_set_kiwi_rate leave the switch as it is.
+ * State across lists and modes: a kept receiver -- (id, channel) or (id, stream) -- that moves into or out of SSDR_MODE_IQ follows
+ * ssdr_set_params' rule for a channel that changes mode: its audio state (AGC, phases, FIR history) stays; with stages set its squelch
+ * state and de-emphasis S start over and its encoder's state stays; its blanker's setting and state stay.
+ * Stages on a row in SSDR_MODE_IQ (ssdr_set_subrx_stages / ssdr_set_wb_rx_stages): the channel's rules.  No squelch acts and its state
+ * does not move, no de-emphasis acts, and snd_adpcm does not encode the row -- I,Q goes out raw: the row of ssdr_*_stage_results is
+ * zero and the encoder's state is left alone.  A bank whose only rows with settings are such rows launches no tail.  The noise
+ * blanker (ssdr_set_subrx_noise_blanker / ssdr_set_wb_rx_noise_blanker) acts, in front of the filter, as on a channel in SSDR_MODE_IQ.
+ * Kernels: none of its own.  channel_frames / channel_frames_dec (ssdr_audio_chan.h, ssdr_audio.hip) store the pairs of a row in
+ * SSDR_MODE_IQ at SsdrAudioArgs::iq_out, indexed by the row they are given -- for a bank the list row; every launch of a bank with such
+ * a row (ssdr_audio_sub_kernel, ssdr_audio_sub_dec_kernel<2|4>, their blanker twins) is handed the bank's own buffer, which is
+ * allocated when the bank first runs with such a row, grown like the channels', and cleared per run while rows of other modes stand
+ * beside them.  A bank without such a row is handed NULL, as before.  The channels' own buffer (ssdr_audio_iq) is untouched.
+ * The results mirror ssdr_audio_iq: int16 [rows][n_frames * 512][2] of the last audio run in list order, rows of other modes zero.
+ * SSDR_ESTATE if the bank is empty or holds no row in SSDR_MODE_IQ, or if there has been no audio run of the ctx's own batch with
+ * the list as it is (another set of rows, or other rows in SSDR_MODE_IQ, since the run): the rule of ssdr_subrx_stage_results.
+ * SSDR_EINVAL for a NULL ctx or iq_out.  Not on the pipelined feed, not in checkpoints (the banks are in neither). */
+int ssdr_set_rx_iq(ssdr_ctx *ctx, int bank, int on);
+int ssdr_get_rx_iq(ssdr_ctx *ctx, int bank, int *on);
+int ssdr_subrx_audio_iq(ssdr_ctx *ctx, int16_t *iq_out, int out_is_device);
+int ssdr_wb_rx_audio_iq(ssdr_ctx *ctx, int16_t *iq_out, int out_is_device);
 
 /* -- pipelined host feed: the path a live ingest takes (KiwiSDRStream._process_iq_samples -> batches, kiwi/client.py:493)
  *

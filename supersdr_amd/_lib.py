@@ -260,6 +260,10 @@ _SIGS = {
     "ssdr_set_wb_rx_noise_blanker": (C.c_int, [_P, _P, _P, C.c_uint32]),
     "ssdr_get_wb_rx_noise_blanker": (C.c_int, [_P, _P, _P, C.POINTER(C.c_uint32)]),
     "ssdr_wb_rx_nb_mask": (C.c_int, [_P, _P, C.c_int]),
+    "ssdr_set_rx_iq": (C.c_int, [_P, C.c_int, C.c_int]),
+    "ssdr_get_rx_iq": (C.c_int, [_P, C.c_int, C.POINTER(C.c_int)]),
+    "ssdr_subrx_audio_iq": (C.c_int, [_P, _P, C.c_int]),
+    "ssdr_wb_rx_audio_iq": (C.c_int, [_P, _P, C.c_int]),
     "ssdr_feed_open": (C.c_int, [_P, C.c_uint32, C.c_uint32, C.c_uint32]),
     "ssdr_feed_slot": (C.c_int, [_P, C.POINTER(_P)]),
     "ssdr_feed_submit": (C.c_int, [_P]),
@@ -318,7 +322,7 @@ _NEWER_THAN_AB_LIBS = ("ssdr_feed_collect_listen", "ssdr_set_subrx", "ssdr_get_s
                        "ssdr_subrx_stage_results", "ssdr_get_subrx_stage_state", "ssdr_set_wb_rx_stages", "ssdr_get_wb_rx_stages",
                        "ssdr_wb_rx_stage_results", "ssdr_get_wb_rx_stage_state", "ssdr_rx_tail_stats", "ssdr_set_subrx_noise_blanker",
                        "ssdr_get_subrx_noise_blanker", "ssdr_subrx_nb_mask", "ssdr_set_wb_rx_noise_blanker", "ssdr_get_wb_rx_noise_blanker",
-                       "ssdr_wb_rx_nb_mask")      # entry points a library named by SSDR_LIB_PATH (A/B builds only) may predate
+                       "ssdr_wb_rx_nb_mask", "ssdr_set_rx_iq", "ssdr_get_rx_iq", "ssdr_subrx_audio_iq", "ssdr_wb_rx_audio_iq")      # entry points a library named by SSDR_LIB_PATH (A/B builds only) may predate
 
 
 def _load():

@@ -59,6 +59,7 @@ struct BankOut {
     uint8_t *d_closed = nullptr; size_t closed_cap = 0;           // [rows][frames] the tail's closed flags (ssdr_set_subrx_stages / _wb_rx_stages)
     uint8_t *d_adpcm = nullptr; size_t adpcm_cap = 0;             // [rows][frames * 256] ... and its SND payloads; capacity in frames
     uint8_t *d_nb_mask = nullptr; size_t nb_mask_cap = 0;         // [rows][frames * 64 D] the rows' blank masks (ssdr_set_subrx_noise_blanker / _wb_rx_); capacity in frames at D = 4
+    uint32_t *d_iq = nullptr; size_t iq_cap = 0;                  // [rows][frames * 512] I | Q << 16 of the rows in SSDR_MODE_IQ (ssdr_set_rx_iq), every other row zero
     uint32_t run_rows = 0, run_frames = 0;                        // extent of the last run
 };
 struct Batch {
@@ -145,6 +146,15 @@ struct RxBank {
     bool nb_valid = false;                              // the last audio run was the ctx's own batch's, blanking, with list and settings as they are
     uint32_t nb_run_decim = 1;                          // D of that run (the mask's row length)
     SsdrNbChan *d_nb = nullptr;                         // [cap] gate in samples, threshold, carried sums and samples left to blank
+    // rows in SSDR_MODE_IQ (ssdr_set_rx_iq): refused until the switch is on; the pairs' buffer (BankOut::d_iq) comes with the first such row
+    bool iq_ok = false;                                 // the list setter takes SSDR_MODE_IQ rows
+    bool iq_valid = false;                              // the last audio run was the ctx's own batch's, with the rows that are in SSDR_MODE_IQ now
+    uint32_t iq_rows() const
+    {
+        uint32_t n = 0;
+        for (const ssdr_chan_consts &k : h_consts) n += k.mode == SSDR_MODE_IQ;
+        return n;
+    }
     uint32_t rows() const { return (uint32_t)h_consts.size(); }
 };
 
@@ -423,6 +433,7 @@ static void free_owned(ssdr_ctx *c)
         c->own.sub.d_pcm, c->own.sub.d_rssi, c->own.sub.d_flags, c->own.sub.d_closed, c->own.sub.d_adpcm,             // sub-receivers: the own batch's results,
         c->sub.d_sq, c->sub.d_de, c->sub.d_enc, c->sub.d_tail,                                                        // ... their tail's state,
         c->own.sub.d_nb_mask, c->sub.d_nb, c->own.wr.d_nb_mask, c->wr.d_nb,                                           // ... both banks' blankers: masks and state,
+        c->own.sub.d_iq, c->own.wr.d_iq,                                                                              // ... and their I,Q pairs,
         c->sub.d_state[0], c->sub.d_state[1], c->sub.d_hist[0], c->sub.d_hist[1], c->sub.d_phist[0], c->sub.d_phist[1], c->sub.d_phist_alt,
         c->sub.d_consts, c->sub.d_taps, c->sub.d_parent, c->sub.d_play, c->sub.d_play_out,                            // ... their bank: state, constants, play_buffer
         c->d_chz_taps, c->d_chz_hist, c->d_chz_in,                                                                    // wideband channeliser
@@ -680,6 +691,7 @@ static void bank_clear(RxBank &bk)
     bk.h_consts.clear();
     bk.h_started.clear();
     bk.run_valid = false;
+    bk.iq_valid = false;                                        // (the switch is the ctx's, not the list's: it stays)
     bank_tail_clear(bk);
     bank_nb_clear(bk);
 }
@@ -744,6 +756,11 @@ static int bank_prepare(ssdr_ctx *c, RxBank &bk, Batch &b, BankOut &out)
         if (out.nb_mask_cap < need) SSDR_TRY(drain_audio(c));
         SSDR_TRY(grow(c, b, out.d_nb_mask, out.nb_mask_cap, need, 64 * 4));
     }
+    bk.iq_valid = false;
+    if (bk.iq_rows()) {                                         // the pairs of every row: the kernels index them by the list row
+        if (out.iq_cap < need) SSDR_TRY(drain_audio(c));
+        SSDR_TRY(grow(c, b, out.d_iq, out.iq_cap, need, SSDR_FRAME * 4));
+    }
     return bank_tail_prepare(c, bk, b, out);
 }
 // Every receiver of the bank advanced by the batch, on the audio stage's stream `s` behind the channels' kernels: one launch, timed
@@ -760,13 +777,15 @@ static int bank_launch(ssdr_ctx *c, RxBank &bk, Batch &b, BankOut &out, const Ss
     a.au.consts = bk.d_consts; a.au.taps = bk.d_taps;
     a.au.state = bk.d_state[bk.set]; a.au.hist = bk.d_hist[bk.set];
     a.au.pcm = out.d_pcm; a.au.rssi = out.d_rssi; a.au.flags = out.d_flags;
-    a.au.iq_out = nullptr;
+    const uint32_t n_iq = bk.iq_rows();                    // rows in SSDR_MODE_IQ store their pairs as a channel does, at their list row
+    a.au.iq_out = n_iq ? out.d_iq : nullptr;
     a.au.chan_list = nullptr; a.au.list_n = n;
     a.parent = bk.d_parent;
     bool any_sam = false;                                  // rows in synchronous AM run the mode's own instantiation beside the others'
     for (const ssdr_chan_consts &k : bk.h_consts) any_sam = any_sam || k.mode == SSDR_MODE_SAM;
     const SsdrSubNbArgs na = {a.au, a.parent, bk.d_nb, out.d_nb_mask};
     SSDR_TRY(stage_launch(c, bk.timed, s, [&]() -> int {
+        if (n_iq && n_iq < n) HIP_TRY(hipMemsetAsync(out.d_iq, 0, (size_t)n * b.in_frames * SSDR_FRAME * 4, s));     // rows of the other modes
         if (bk.nb_on) {                                    // once a row blanks: every row on the blanker twins, the mode's rows in the same launch
             HIP_TRY(ssdr_launch_audio_sub_nb(na, c->decim, s));
             return SSDR_OK;
@@ -777,6 +796,7 @@ static int bank_launch(ssdr_ctx *c, RxBank &bk, Batch &b, BankOut &out, const Ss
     }));
     bk.nb_valid = bk.nb_on && &b == &c->own;
     bk.nb_run_decim = c->decim;
+    bk.iq_valid = n_iq && &b == &c->own;
     std::fill(bk.h_started.begin(), bk.h_started.end(), (uint8_t)1);
     out.run_rows = n;
     out.run_frames = b.in_frames;
@@ -820,6 +840,9 @@ static int bank_rebuild(ssdr_ctx *c, RxBank &bk, const std::vector<T> &old, cons
     SSDR_TRY(bank_upload_consts(c, bk, k, taps));           // (waits: `fresh` and `parent` are host memory)
     SSDR_TRY(bank_tail_follow(c, bk, kept, k));             // settings and stage state go with the receivers (bk.h_consts: still the old modes)
     SSDR_TRY(bank_nb_follow(c, bk, kept));                  // ... and so do the blankers', whatever the modes do
+    bool same_iq = *same_rows;                              // the last run's pairs are the list's only while the same rows are in SSDR_MODE_IQ
+    for (uint32_t j = 0; same_iq && j < count; j++) same_iq = (k[j].mode == SSDR_MODE_IQ) == (bk.h_consts[j].mode == SSDR_MODE_IQ);
+    if (!same_iq) bk.iq_valid = false;
     bk.h_consts = k;
     bk.h_started = started;
     bk.set = to;
@@ -1830,7 +1853,7 @@ static int bank_tail_prepare(ssdr_ctx *c, RxBank &bk, Batch &b, BankOut &out)
             r.squelch = !squelch_acts(t.squelch, mode) ? SSDR_RX_TAIL_OFF : mode == SSDR_MODE_NBFM ? SSDR_RX_TAIL_NOISE : SSDR_RX_TAIL_RSSI;
             const uint32_t setting = deemp_acting(t.deemp, mode);
             r.coef = setting ? deemp_coeff(setting, c->kiwi_rate) : 0u;
-            r.adpcm = t.snd_adpcm ? 1u : 0u;
+            r.adpcm = t.snd_adpcm && mode != SSDR_MODE_IQ ? 1u : 0u;            // (I,Q goes out raw: a zero row, the state left alone, as the channels' encoder)
             if (r.squelch || r.coef || r.adpcm) bk.h_tail.push_back(r);
         }
         if (!bk.h_tail.empty()) {
@@ -2070,6 +2093,24 @@ static int bank_nb_mask(ssdr_ctx *c, const RxBank &bk, const BankOut &out, uint8
     return copy_out(c, mask_out, out.d_nb_mask, (size_t)out.run_rows * out.run_frames * 64 * bk.nb_run_decim, out_is_device, kSyncAlways);
 }
 
+// ---- the banks' rows in SSDR_MODE_IQ (ssdr_set_rx_iq): the switch, and the pairs of the last run
+static RxBank *bank_of(ssdr_ctx *c, int bank) { return bank == 0 ? &c->sub : bank == 1 ? &c->wr : nullptr; }
+static int bank_set_iq(ssdr_ctx *c, RxBank &bk, int on)
+{
+    if (!c->feed.empty()) return SSDR_ESTATE;
+    if (!on && bk.iq_rows()) return SSDR_ESTATE;            // the list holds a row the setter would refuse from now on
+    bk.iq_ok = on != 0;
+    return SSDR_OK;
+}
+static int bank_audio_iq(ssdr_ctx *c, const RxBank &bk, const BankOut &out, int16_t *iq_out, int out_is_device)
+{
+    if (!iq_out) return SSDR_EINVAL;
+    if (!bk.rows() || !bk.iq_rows() || !bk.run_valid || !bk.iq_valid || !out.d_iq) return SSDR_ESTATE;
+    HIP_TRY(hipSetDevice(c->device));
+    SSDR_TRY(join_audio(c));
+    return copy_out(c, iq_out, out.d_iq, (size_t)out.run_rows * out.run_frames * SSDR_FRAME * 4, out_is_device, kSyncHost);
+}
+
 // ---- waterfall views: a per-channel zoom stage beside the waterfall stage (ssdr_set_wf_views) ---------------------------------
 // the state arrays (two sets: a new list is built in the other one, so that a view that stays keeps its stream) and the tap tables
 static int wfview_alloc(ssdr_ctx *c)
@@ -2285,7 +2326,7 @@ static int subrx_compile(const ssdr_ctx *c, const ssdr_subrx *subs, uint32_t cou
     taps.assign((size_t)count * SSDR_NTAP_MAX, 0.0f);
     for (uint32_t j = 0; j < count; j++) {
         if (subs[j].channel >= c->n_ch || (j && subs[j].id <= subs[j - 1].id)) return SSDR_EINVAL;
-        if (subs[j].params.mode == SSDR_MODE_IQ) return SSDR_EINVAL;            // a sub-receiver has no I,Q output
+        if (subs[j].params.mode == SSDR_MODE_IQ && !c->sub.iq_ok) return SSDR_EINVAL;      // a sub-receiver has no I,Q output until ssdr_set_rx_iq
         SSDR_TRY(ssdr_compile_params_host(&subs[j].params, &k[j], taps.data() + (size_t)j * SSDR_NTAP_MAX, decim, rate));
         if (decim > 1 && ssdr_audio_path(k[j]) != SSDR_PATH_GENERAL) return SSDR_EINVAL;    // the decimating kernel is the general path (audio_stage)
     }
@@ -4178,6 +4219,30 @@ int ssdr_subrx_nb_mask(ssdr_ctx *c, uint8_t *mask_out, int out_is_device) SSDR_G
     return c ? bank_nb_mask(c, c->sub, c->own.sub, mask_out, out_is_device) : SSDR_EINVAL;
 } SSDR_UNGUARD
 
+int ssdr_set_rx_iq(ssdr_ctx *c, int bank, int on) SSDR_GUARD
+{
+    RxBank *bk = c ? bank_of(c, bank) : nullptr;
+    return bk ? bank_set_iq(c, *bk, on) : SSDR_EINVAL;
+} SSDR_UNGUARD
+
+int ssdr_get_rx_iq(ssdr_ctx *c, int bank, int *on) SSDR_GUARD
+{
+    RxBank *bk = c ? bank_of(c, bank) : nullptr;
+    if (!bk || !on) return SSDR_EINVAL;
+    *on = bk->iq_ok ? 1 : 0;
+    return SSDR_OK;
+} SSDR_UNGUARD
+
+int ssdr_subrx_audio_iq(ssdr_ctx *c, int16_t *iq_out, int out_is_device) SSDR_GUARD
+{
+    return c ? bank_audio_iq(c, c->sub, c->own.sub, iq_out, out_is_device) : SSDR_EINVAL;
+} SSDR_UNGUARD
+
+int ssdr_wb_rx_audio_iq(ssdr_ctx *c, int16_t *iq_out, int out_is_device) SSDR_GUARD
+{
+    return c ? bank_audio_iq(c, c->wr, c->own.wr, iq_out, out_is_device) : SSDR_EINVAL;
+} SSDR_UNGUARD
+
 int ssdr_rx_tail_stats(ssdr_ctx *c, int bank, float *total_ms, uint32_t *launches, int reset) SSDR_GUARD
 {
     if (bank != 0 && bank != 1) return SSDR_EINVAL;
@@ -4388,7 +4453,7 @@ static int wbrx_compile(const ssdr_ctx *c, const ssdr_wb_rx *list, uint32_t coun
     for (uint32_t j = 0; j < count; j++) {
         if (list[j].stream >= c->chz_streams || (j && list[j].id <= list[j - 1].id)) return SSDR_EINVAL;
         if (!(std::fabs(list[j].offset_hz) <= half)) return SSDR_EINVAL;        // (a NaN fails the comparison)
-        if (list[j].params.mode == SSDR_MODE_IQ) return SSDR_EINVAL;            // no I,Q output, as a sub-receiver
+        if (list[j].params.mode == SSDR_MODE_IQ && !c->wr.iq_ok) return SSDR_EINVAL;       // no I,Q output until ssdr_set_rx_iq, as a sub-receiver
         // (whatever the compiler's code -- SSDR_MODE_SAM at D > 1 is SSDR_ESTATE for a channel -- a receiver that does not fit is SSDR_EINVAL)
         if (ssdr_compile_params_host(&list[j].params, &k[j], taps.data() + (size_t)j * SSDR_NTAP_MAX, decim, rate) != SSDR_OK) return SSDR_EINVAL;
         if (decim > 1 && ssdr_audio_path(k[j]) != SSDR_PATH_GENERAL) return SSDR_EINVAL;    // the decimating kernel is the general path

@@ -646,6 +646,39 @@ class SsdrEngine:
         check(lib.ssdr_rx_tail_stats(self._ctx, {"sub": 0, "tuned": 1}[bank], C.byref(ms), C.byref(n), 1 if reset else 0), "ssdr_rx_tail_stats")
         return ms.value, n.value
 
+    _RX_BANKS = {"sub": 0, "tuned": 1}
+
+    def set_rx_iq(self, bank, on):
+        """Let the list setter of a bank ("sub" or "tuned") take rows in "iq" mode ("SET mod=iq" on an extra receiver's stream), or stop
+        it.  Off until set.  SsdrError (SSDR_ESTATE), and nothing changes: turning it off while the list holds such a row, either
+        direction while a feed is open.  Another bank name raises ValueError before the library is called."""
+        if bank not in self._RX_BANKS:
+            raise ValueError("bank %r: 'sub' or 'tuned'" % (bank,))
+        check(lib.ssdr_set_rx_iq(self._ctx, self._RX_BANKS[bank], 1 if on else 0), "ssdr_set_rx_iq")
+
+    def get_rx_iq(self, bank):
+        """-> whether the bank's ("sub" or "tuned") list setter takes rows in "iq" mode"""
+        if bank not in self._RX_BANKS:
+            raise ValueError("bank %r: 'sub' or 'tuned'" % (bank,))
+        on = C.c_int(0)
+        check(lib.ssdr_get_rx_iq(self._ctx, self._RX_BANKS[bank], C.byref(on)), "ssdr_get_rx_iq")
+        return bool(on.value)
+
+    def _bank_audio_iq(self, bank):
+        name = "ssdr_%s_audio_iq" % bank[0]
+        out = np.empty((self._bank_count(bank), self.audio_frames * L.FRAME, 2), np.int16)
+        check(getattr(lib, name)(self._ctx, out.ctypes.data, 0), name)
+        return out
+
+    def subrx_audio_iq(self):
+        """-> int16 [n_sub, n_frames*512, 2]: I,Q of the sub-receivers in "iq" mode for the last run_audio / run_chain, rows in list
+        order (rows of other modes: 0), as audio_iq.  SsdrError (SSDR_ESTATE) with no such row, or before a run with the list as it is."""
+        return self._bank_audio_iq(self._SUBRX)
+
+    def wb_rx_audio_iq(self):
+        """-> int16 [n_rx, n_frames*512, 2]: I,Q of the tuned receivers in "iq" mode for the last run, as subrx_audio_iq"""
+        return self._bank_audio_iq(self._WB_RX)
+
     # ---- wideband channeliser: one wide IQ stream -> 1024 rows of the input batch
     def set_channelizer(self, n_streams, oversample=1, taps=None, branches=L.CHAN_BRANCHES):
         """A polyphase filter bank in front of the ctx: every wideband stream fills 1024 rows (n_streams * 1024 == n_ch).  taps:

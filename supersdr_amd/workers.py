@@ -128,11 +128,14 @@ class SuperframeResult:
     a row for each, as the sub-receivers' arrays do (all None: no tuned receiver is open, or the run was no feed_wideband).
     On a hub built with rx_stages=True: sub_closed / tuned_closed uint8 [n, frames], 1 where a receiver's squelch zeroed the frame, and
     sub_adpcm / tuned_adpcm uint8 [n, frames*256], rows as sub_ids / tuned_ids, a row whose stage is off all zero (each None: no
-    receiver of the family squelches, resp. compresses)."""
+    receiver of the family squelches, resp. compresses).
+    On a hub built with rx_iq=True: sub_iq / tuned_iq int16 [n, frames*512, 2], rows as sub_ids / tuned_ids, the I,Q of the receivers
+    in "SET mod=iq" and zero for every other (each None: no receiver of the family is in that mode)."""
     __slots__ = ("seq", "wf", "n_avg", "color", "chans", "pcm", "rssi", "flags", "play", "mono", "iq", "wire_rssi", "post_channels", "out_channels",
                  "snd_adpcm", "wf_adpcm", "snd_adpcm_channels", "wf_adpcm_channels", "squelched", "view_lines", "view_channels",
                  "squelched_channels", "sub_ids", "sub_pcm", "sub_rssi", "sub_flags", "sub_play", "scope_ids", "scope_lines",
-                 "tuned_ids", "tuned_pcm", "tuned_rssi", "tuned_flags", "tuned_play", "sub_closed", "sub_adpcm", "tuned_closed", "tuned_adpcm")
+                 "tuned_ids", "tuned_pcm", "tuned_rssi", "tuned_flags", "tuned_play", "sub_closed", "sub_adpcm", "tuned_closed", "tuned_adpcm",
+                 "sub_iq", "tuned_iq")
 
     def __init__(self, **kw):
         for k in self.__slots__:
@@ -263,6 +266,9 @@ class IQHub:
     methods refuse before the engine is touched and the hub sends the engine nothing it did not send before they existed.
     rx_blanker=True, independent of rx_stages, gives them the impulse noise blanker (set_rx_noise_blanker; ssdr_set_subrx_noise_blanker /
     ssdr_set_wb_rx_noise_blanker), in front of the receiver's channel filter as a channel's is; the same opt-in rule.
+    rx_iq=True, a third independent switch, lets them take mode "iq" (open_sub, set_sub_params, open_tuned, retune_tuned,
+    set_tuned_params; ssdr_set_rx_iq, set once when the hub is built): their frames then carry iq_block as a channel's do.  Without it
+    mod=iq is refused before the engine is touched, with the texts it always had.
     `batch_superframes=K` runs K superframes per GPU call (K lines + 2K audio frames per channel and call): latency for
     launch efficiency at very large channel counts.  `exact_bins=True`: the waterfall stage in float64 (ssdr_set_exact_bins).  `copy_threads=T` splits feed_block's copy of a large block over T threads (default: up to 8 on hubs of 8192+ receivers).
     """
@@ -272,7 +278,7 @@ class IQHub:
     def __init__(self, n_channels, device=0, engine=None, max_queue=64, gpu_post=True, kiwi_rate=12000, trace_rows=0,
                  backlog_superframes=8, stall_superframes=4, pipeline=False, depth=3, hop=1024, zoom=1, lazy=None,
                  batch_superframes=1, wire=False, copy_threads=None, exact_bins=False, lazy_out=False, listen=False, rx_stages=False,
-                 rx_blanker=False):
+                 rx_blanker=False, rx_iq=False):
         self.n_ch = int(n_channels)
         # argument combinations that cannot work are refused BEFORE an engine (a GPU context) exists
         self._lazy = (self.n_ch > self.LAZY_ABOVE) if lazy is None else bool(lazy)
@@ -394,6 +400,12 @@ class IQHub:
         self._rx_st = {"sub": {}, "tuned": {}}
         self._rx_blanker = bool(rx_blanker)
         self._rx_nb = {"sub": {}, "tuned": {}}       # id -> (gate_us, thresh) of the receivers whose blanker somebody has set
+        # rx_iq=True: the extra receivers take "SET mod=iq".  The engine's switch is set here, once, for both families (a pipelined
+        # hub has no extra receivers; an engine without the switch refuses the mode where it is asked for: _check_rx_iq)
+        self._rx_iq = bool(rx_iq)
+        if self._rx_iq and not self.pipeline and hasattr(self.engine, "set_rx_iq"):
+            self.engine.set_rx_iq("sub", True)
+            self.engine.set_rx_iq("tuned", True)
         self.sub_queue, self.sub_clients = self._subs.queue, self._subs.clients
         self.tuned_queue, self.tuned_clients = self._tuned.queue, self._tuned.clients
         self.scope_queue, self.scope_clients = self._scopes.queue, self._scopes.clients
@@ -691,9 +703,17 @@ class IQHub:
         self._resend_rx_stages("sub", rows)
         self._resend_rx_nb("sub", rows)
 
+    def _check_rx_iq(self, noun, reader):
+        """mode "iq" on an extra receiver: the refusal it always met unless the hub was built with rx_iq=True, and -- as for synchronous
+        AM -- on an engine from before the mode; before the engine is touched"""
+        if not getattr(self, "_rx_iq", False):
+            raise ValueError("mod=iq on a %s: a %s has no I,Q output" % (noun, noun))
+        if not hasattr(self.engine, "set_rx_iq") or not hasattr(self.engine, reader):
+            raise ValueError("mod=iq on a %s: this engine's %ss have no I,Q output (no set_rx_iq / %s)" % (noun, noun, reader))
+
     def _check_sub_params(self, p):
         if p.mode == L.MODE_IQ:
-            raise ValueError("mod=iq on a sub-receiver: a sub-receiver has no I,Q output")
+            self._check_rx_iq("sub-receiver", "subrx_audio_iq")
         if p.mode == L.MODE_SAM and not hasattr(self.engine, "subrx_sam_carrier"):
             raise ValueError("synchronous AM (sam, sal, sau) has no demodulator on this engine's sub-receivers (no subrx_sam_carrier)")
 
@@ -702,7 +722,7 @@ class IQHub:
         of its own, beside the channel's own demodulator, which does not notice.  -> sid, the hub's name for it: its frames arrive
         in sub_queue[sid], set_sub_params(sid, p) retunes it (state kept, like set_params), close_sub(sid) ends it.  The other
         sub-receivers keep their streams.  ValueError on a pipelined hub (before the engine is touched), beyond 256 of them (SSDR_SUBRX_MAX), for
-        mod=iq and for parameters the library refuses; then nothing changes."""
+        mod=iq (unless the hub was built with rx_iq=True) and for parameters the library refuses; then nothing changes."""
         c = int(channel)
         if not 0 <= c < self.n_ch:
             raise IndexError("channel %d of %d" % (c, self.n_ch))
@@ -750,7 +770,7 @@ class IQHub:
 
     def _check_tuned(self, stream, offset_hz, p):
         if p.mode == L.MODE_IQ:
-            raise ValueError("mod=iq on a tuned receiver: a tuned receiver has no I,Q output")
+            self._check_rx_iq("tuned receiver", "wb_rx_audio_iq")
         n_streams = self.n_ch // self.channelizer.BRANCHES
         if not 0 <= stream < n_streams:
             raise ValueError("wide stream %d of %d" % (stream, n_streams))
@@ -772,7 +792,7 @@ class IQHub:
         reused): its frames arrive in tuned_queue[tid] with every feed_wideband, retune_tuned(tid, offset_hz) moves it (the DDC carries
         nothing: nobody restarts), set_tuned_params(tid, p) changes the demodulator (state kept, like set_params), close_tuned(tid)
         ends it.  ValueError on a pipelined or wire hub and without a channeliser (before the engine is touched), beyond 64 of them
-        (SSDR_WB_RX_MAX), for mod=iq, an offset outside the wide stream and parameters the library refuses; then nothing changes."""
+        (SSDR_WB_RX_MAX), for mod=iq (unless the hub was built with rx_iq=True), an offset outside the wide stream and parameters the library refuses; then nothing changes."""
         self._require_wide_stream("tuned receiver", "set_wb_rx")
         p = _copy_params(params if params is not None else self._default_params)
         row = (int(stream), float(offset_hz), p)
@@ -933,7 +953,7 @@ class IQHub:
         rows = [(st.get(i, self._RX_OFF), table.rows[i][-1].mode) for i in table.ids()]
         squelches = any(_squelch_acts(t[0], m) for t, m in rows)
         filters = any((t[1][1] if m == L.MODE_NBFM else t[1][0] if m in (L.MODE_AM, L.MODE_SAM) else 0) for t, m in rows)
-        compresses = any(t[2] for t, _ in rows)
+        compresses = any(t[2] and m != L.MODE_IQ for t, m in rows)     # (I,Q goes out raw: the library does not encode such a row)
         if not (squelches or filters or compresses):
             return {}
         closed, adpcm = results()
@@ -1294,10 +1314,14 @@ class IQHub:
             extra.update(self._rx_results("sub", self._subs, eng.subrx_audio, eng.run_subrx_playbuffer))
             if self._rx_st["sub"]:
                 extra.update(self._rx_stage_results("sub", "sub", self._subs, eng.subrx_stage_results))
+            if self._rx_iq and self._rx_in_iq(self._subs):     # rows' I,Q only while some row is in "SET mod=iq"
+                extra.update(sub_iq=eng.subrx_audio_iq())
         if wideband and self._tuned.rows:             # ... in tid order (open_tuned)
             extra.update(self._rx_results("tuned", self._tuned, eng.wb_rx_audio, eng.run_wb_rx_playbuffer))
             if self._rx_st["tuned"]:
                 extra.update(self._rx_stage_results("tuned", "tuned", self._tuned, eng.wb_rx_stage_results))
+            if self._rx_iq and self._rx_in_iq(self._tuned):
+                extra.update(tuned_iq=eng.wb_rx_audio_iq())
         self.superframes += 1
         self._hand_out(SuperframeResult(seq=self.superframes, wf=wf, n_avg=n_avg, color=color, chans=chans, pcm=pcm, rssi=rssi,
                                         flags=flags, play=play, mono=mono, iq=iqo, wire_rssi=wire_rssi, post_channels=self._post_sel,
@@ -1316,18 +1340,26 @@ class IQHub:
             play = playbuffer([PlayChan(100.0, 0.0) if s is None else PlayChan(float(s.volume), float(s.audio_balance)) for s in rows])
         return {name + "_ids": ids, name + "_pcm": pcm, name + "_rssi": rssi, name + "_flags": flags, name + "_play": play}
 
-    def _hand_out_rx(self, queues, ids, pcm, rssi, flags, play, closed=None, adpcm=None, settings=None):
+    @staticmethod
+    def _rx_in_iq(table):
+        """-> the ids of a receiver table's rows in "SET mod=iq" (a row ends with its ChanParams)"""
+        return [i for i, row in table.rows.items() if row[-1].mode == L.MODE_IQ]
+
+    def _hand_out_rx(self, queues, ids, pcm, rssi, flags, play, closed=None, adpcm=None, settings=None, iq=None, table=None):
         """a receiver list's frames (rows in the order of `ids`) to the queues of those that have one; a compressing receiver's carry
-        their payload, a squelched frame its mark, as a channel's do"""
+        their payload, a squelched frame its mark, one in "SET mod=iq" its I,Q pairs (and never a payload), as a channel's do"""
         P, H = self.play_len, L.FRAME // 2
+        in_iq = set(self._rx_in_iq(table)) if iq is not None else ()
         for i, rid in enumerate(ids or ()):
             q = queues.get(rid)
             if q is None:
                 continue
-            comp = adpcm is not None and bool((settings or {}).get(rid, self._RX_OFF)[2])
+            iq_mode = rid in in_iq
+            comp = adpcm is not None and not iq_mode and bool((settings or {}).get(rid, self._RX_OFF)[2])
             for f in range(pcm.shape[1] // L.FRAME):
                 fr = Frame.make(pcm[i, f * L.FRAME:(f + 1) * L.FRAME], rssi[i, f],
-                                play[i, f * P:(f + 1) * P].copy() if play is not None else None, None, flags[i, f])
+                                play[i, f * P:(f + 1) * P].copy() if play is not None else None, None, flags[i, f],
+                                iq[i, f * L.FRAME:(f + 1) * L.FRAME].copy() if iq_mode else None)
                 if comp:
                     fr.adpcm = adpcm[i, f * H:(f + 1) * H].tobytes()
                 if closed is not None and closed[i, f]:
@@ -1391,9 +1423,10 @@ class IQHub:
                     if qc is not None and r.squelched[qc, f]:
                         fr.squelched = True
                 _put_drop_oldest(q, fr)
-        self._hand_out_rx(self.sub_queue, r.sub_ids, r.sub_pcm, r.sub_rssi, r.sub_flags, r.sub_play, r.sub_closed, r.sub_adpcm, self._rx_st["sub"])
+        self._hand_out_rx(self.sub_queue, r.sub_ids, r.sub_pcm, r.sub_rssi, r.sub_flags, r.sub_play, r.sub_closed, r.sub_adpcm, self._rx_st["sub"],
+                          r.sub_iq, self._subs)
         self._hand_out_rx(self.tuned_queue, r.tuned_ids, r.tuned_pcm, r.tuned_rssi, r.tuned_flags, r.tuned_play, r.tuned_closed, r.tuned_adpcm,
-                          self._rx_st["tuned"])
+                          self._rx_st["tuned"], r.tuned_iq, self._tuned)
         for i, sid in enumerate(r.scope_ids or ()):
             q = self.scope_queue.get(sid)
             if q is None:
@@ -1605,7 +1638,10 @@ class GpuStream:
     the receiver's DDC moves (IQHub.retune_tuned) and f_shift_hz stays 0; a frequency outside the stream raises ValueError naming
     the stream's span.  "SET agc=" goes to the receiver's parameters.  Its frames come from hub.tuned_queue[tid], close_connection
     closes the receiver, and nb / squelch / de_emp / compression=1 / mod=iq raise ValueError naming the tuned receiver, as for a
-    sub-receiver -- with the same two opt-ins of the hub (rx_stages=True, rx_blanker=True; mod=iq stays refused).
+    sub-receiver -- with the same two opt-ins of the hub (rx_stages=True, rx_blanker=True).
+    On a hub built with rx_iq=True either kind of stream takes "SET mod=iq low_cut= high_cut= freq=" (the tuned stream still moves the
+    DDC and keeps f_shift_hz at 0): its SND frames then carry the receiver's I,Q pairs behind a GNSS stamp, raw whatever
+    "SET compression=" says, as a channel's do.  Without it the refusals above stand with their texts.
 
     receive_message(): server -> client frames, byte for byte in the wire format the reference parses
     (utils_supersdr.py:782-784, 1065-1074): first what the constructors wait for ("MSG audio_init audio_rate= sample_rate=",
@@ -1776,7 +1812,7 @@ class GpuStream:
         freq = float(kv.get("freq", self.center_khz))
         f_shift = (freq - self.center_khz) * 1000.0
         if self.tuned is not None:                   # anywhere in the wide stream: the DDC moves, the audio chain stays on its centre
-            if mode == "iq":
+            if mode == "iq" and not getattr(self.hub, "_rx_iq", False):     # (a hub built with rx_iq=True: the mode goes to the hub like any other)
                 raise ValueError("SET mod=iq on tuned receiver %d of wide stream %d: a tuned receiver has no I,Q output" % (self.tuned, self.channel))
             half = self.hub.wide_rate() / 2.0
             if not abs(f_shift) <= half:
@@ -1805,6 +1841,8 @@ class GpuStream:
         try:
             if self._rx is not None:
                 f = self._rx.queues[self._rx.id].get(timeout=self.timeout)
+                if getattr(f, "iq_block", None) is not None:      # the receiver is in "SET mod=iq" (a hub built with rx_iq=True): raw pairs, whatever compression= says
+                    return snd_iq_frame(f.iq_block, f.rssi, self._next_seq(), adc_overflow=f.adc_overflow)
                 if getattr(f, "adpcm", None) is not None:      # produced with "SET compression=1" on a hub built with rx_stages=True
                     return snd_adpcm_frame(f.adpcm, f.rssi, self._next_seq(), adc_overflow=f.adc_overflow)
                 return snd_frame(f, f.rssi, self._next_seq(), adc_overflow=f.adc_overflow)
