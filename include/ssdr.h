@@ -536,7 +536,8 @@ int ssdr_wf_view_stats(ssdr_ctx *ctx, float *total_ms, uint32_t *launches, int r
  * ssdr_subrx_stats is the stage's own.  Cost beside a 65536-channel general-path audio stage of 1.32 ms at 16 frames per call: 0.05 ms
  * for 1 to 256 sub-receivers -- one wave's latency over its frames, not arithmetic (profiles/subrx_probe.txt).
  * While any sub-receiver is set ssdr_feed_open (with or without SSDR_FEED_LISTEN) and ssdr_checkpoint_save / _load return
- * SSDR_ESTATE; while a pipelined feed is open ssdr_set_subrx with count > 0 returns SSDR_ESTATE.  ssdr_reset_state restarts the
+ * SSDR_ESTATE; while a pipelined feed is open ssdr_set_subrx with count > 0 returns SSDR_ESTATE -- the feed's two refusals unless
+ * ssdr_set_feed_subrx (further down) is on and the feed was opened with SSDR_FEED_LISTEN.  ssdr_reset_state restarts the
  * sub-receivers of the channels it names; ssdr_set_kiwi_rate and ssdr_set_decimation recompile and restart all of them, and return
  * SSDR_EINVAL with nothing changed if a sub-receiver's parameters do not compile at the new setting; ssdr_set_params on the parent
  * channel does not touch them. */
@@ -791,7 +792,8 @@ int ssdr_wb_rx_stats(ssdr_ctx *ctx, float *ddc_ms, float *audio_ms, uint32_t *la
  * ssdr_rx_tail_stats is the stage's own.  Cost on an MI355X at 16 frames per call with all three stages on every row: 1.07 ms for 1 receiver,
  * 1.26 ms for 64, 2.52 ms for 256 + 64 (two launches) -- one serial lane's latency over the call's samples per launch, the encoder's table walk
  * most of it; the channels' three kernels take 1.33 ms for as many channels (profiles/rx_tail_probe.txt).
- * The feed and checkpoint refusals that any extra receiver causes stand as they are (so the stages never meet a pipelined feed). */
+ * The feed and checkpoint refusals that any extra receiver causes stand as they are: a tuned receiver's stages never meet a pipelined
+ * feed, a sub-receiver's only that of ssdr_set_feed_subrx, whose slots hold their results (ssdr_feed_collect_subrx). */
 typedef struct ssdr_rx_stages {
     ssdr_squelch_params squelch;   /* 16 B: as ssdr_set_squelch takes it */
     ssdr_deemp_params   deemp;     /*  8 B: as ssdr_set_deemphasis takes it */
@@ -894,7 +896,8 @@ int ssdr_wb_rx_nb_mask(ssdr_ctx *ctx, uint8_t *mask_out, int out_is_device);
  * The results mirror ssdr_audio_iq: int16 [rows][n_frames * 512][2] of the last audio run in list order, rows of other modes zero.
  * SSDR_ESTATE if the bank is empty or holds no row in SSDR_MODE_IQ, or if there has been no audio run of the ctx's own batch with
  * the list as it is (another set of rows, or other rows in SSDR_MODE_IQ, since the run): the rule of ssdr_subrx_stage_results.
- * SSDR_EINVAL for a NULL ctx or iq_out.  Not on the pipelined feed, not in checkpoints (the banks are in neither). */
+ * SSDR_EINVAL for a NULL ctx or iq_out.  Not in checkpoints; on the pipelined feed only the sub-receivers', with ssdr_set_feed_subrx
+ * (the pairs are a part of the slot when the switch was on at ssdr_feed_open: ssdr_feed_collect_subrx). */
 int ssdr_set_rx_iq(ssdr_ctx *ctx, int bank, int on);
 int ssdr_get_rx_iq(ssdr_ctx *ctx, int bank, int *on);
 int ssdr_subrx_audio_iq(ssdr_ctx *ctx, int16_t *iq_out, int out_is_device);
@@ -985,6 +988,54 @@ typedef struct ssdr_feed_listen {
     const int16_t *view_lines;          /* [view_total_lines][1024], one view after the other */
 } ssdr_feed_listen;                     /* 96 B */
 int ssdr_feed_collect_listen(ssdr_ctx *ctx, ssdr_feed_listen *out);
+/* The sub-receivers in the slot pipeline: opt-in, a switch of the ctx and not a flag of the feed.  Off is the
+ * default, and a ctx that never turns it on refuses, allocates, lays out its slots and launches exactly what it did before the switch
+ * existed.  SSDR_EINVAL for a NULL ctx or a NULL `on`; SSDR_ESTATE, with nothing changed, in either direction while a feed is open (the
+ * rule of ssdr_set_rx_iq).  It acts on a feed opened with SSDR_FEED_LISTEN and on no other:
+ *   - ssdr_feed_open succeeds with sub-receivers set, and while the feed is open ssdr_set_subrx (any count up to SSDR_SUBRX_MAX),
+ *     ssdr_set_subrx_stages and ssdr_set_subrx_noise_blanker are accepted, their argument checks, all-or-nothing behaviour and state
+ *     rules unchanged.  A setter acts on every batch submitted after the call and on none submitted before it, in flight or not: it
+ *     waits for the ctx's kernel streams, never for the copies out.  ssdr_set_rx_iq stays refused while any feed is open: a caller who
+ *     wants SSDR_MODE_IQ rows turns it on before ssdr_feed_open.
+ *   - every slot holds the sub-receivers' parts in device and in pinned host memory, each sized for SSDR_SUBRX_MAX rows of n_frames and
+ *     placed at a multiple of 256 bytes: PCM, RSSI, flags, closed flags, SND payloads and blank masks (about 0.33 MiB per frame of
+ *     n_frames), the I,Q pairs if ssdr_set_rx_iq(ctx, 0, 1) was in force at the open (0.5 MiB per frame more), the play blocks with
+ *     SSDR_FEED_POST (2 MiB per frame more).  With the switch off the slot's two blocks are byte for byte as large as without it.
+ *   - a submit advances the bank on the slot's batch -- the shipped kernels of ssdr_run_chain, behind the channels' kernels or the
+ *     one-read kernel -- and every non-empty part comes back with one copy of the rows in force times n_frames.  With no sub-receiver
+ *     set nothing more is launched or copied than on a plain listen feed.
+ *   - while the feed is open, and after its close until a synchronous audio run, ssdr_subrx_audio, ssdr_subrx_stage_results,
+ *     ssdr_subrx_audio_iq, ssdr_subrx_nb_mask and ssdr_run_subrx_playbuffer return SSDR_ESTATE (the ctx's own buffers hold no batch of
+ *     the feed); ssdr_get_subrx, _state, _consts, _sam_carrier, _stages, _stage_state and _noise_blanker keep working, ordered behind
+ *     the ctx's work.  ssdr_feed_close leaves list, settings and state, and a synchronous run carries the same streams on.
+ * A feed without SSDR_FEED_LISTEN, the channeliser (tuned receivers, scopes), D != 1, ssdr_set_concurrent, ssdr_set_wf_zoom > 1 and the
+ * checkpoint calls refuse as before. */
+int ssdr_set_feed_subrx(ssdr_ctx *ctx, int on);
+int ssdr_get_feed_subrx(ssdr_ctx *ctx, int *on);
+/* Volume and balance of the rows for the batches submitted from now on, on a feed with SSDR_FEED_POST and the switch on (SSDR_ESTATE
+ * otherwise): chans [count], count equal to the list's length (else SSDR_EINVAL); (NULL, 0) means no play blocks.  While set, a submit
+ * runs play_buffer (the kernels and the history of ssdr_run_subrx_playbuffer; the history follows a kept row) on the slot's
+ * sub-receiver PCM behind the bank's tail.  A list change to another length clears the setting. */
+int ssdr_feed_subrx_play(ssdr_ctx *ctx, const ssdr_play_chan *chans, uint32_t count);
+/* The sub-receivers' results of the batch ssdr_feed_collect returned last, with what was latched at its submit; rows in list order,
+ * pinned host memory, valid as long as ssdr_feed_collect's pointers.  n = 0 and every pointer NULL for a batch that ran with an empty
+ * list.  SSDR_ESTATE before the first collect, with the switch off, or on a feed without SSDR_FEED_LISTEN; SSDR_EINVAL for a NULL
+ * argument. */
+typedef struct ssdr_feed_subrx {
+    uint32_t n;                         /* rows */
+    uint32_t reserved;                  /* 0 */
+    const ssdr_subrx *list;             /* [n] the list the batch ran with */
+    const ssdr_rx_stages *stages;       /* [n] the rows' settings; NULL if ssdr_set_subrx_stages was never called on the list */
+    const int16_t *pcm;                 /* [n][n_frames * 512] */
+    const float *rssi;                  /* [n][n_frames] */
+    const uint8_t *flags;               /* [n][n_frames] */
+    const uint8_t *closed;              /* [n][n_frames]; NULL if no row had an acting stage; a row whose squelch is off is zero */
+    const uint8_t *adpcm;               /* [n][n_frames * 256]; NULL with closed; a row whose encoder is off is zero */
+    const int16_t *iq;                  /* [n][n_frames * 512][2]; NULL if no row was in SSDR_MODE_IQ; rows of other modes are zero */
+    const uint8_t *nb_mask;             /* [n][n_frames * 64]; NULL if no row blanked */
+    const int16_t *play;                /* [n][n_frames * ssdr_playbuffer_frame_len][2]; NULL unless ssdr_feed_subrx_play is set */
+} ssdr_feed_subrx;                      /* 88 B */
+int ssdr_feed_collect_subrx(ssdr_ctx *ctx, ssdr_feed_subrx *out);
 int ssdr_feed_open(ssdr_ctx *ctx, uint32_t n_frames, uint32_t depth, uint32_t flags);
 int ssdr_feed_slot(ssdr_ctx *ctx, void **host_in);
 int ssdr_feed_submit(ssdr_ctx *ctx);

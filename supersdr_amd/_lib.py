@@ -143,6 +143,19 @@ class FeedListen(C.Structure):
 
 
 assert C.sizeof(FeedListen) == 96
+
+
+class FeedSubRx(C.Structure):
+    """ssdr_feed_subrx: the sub-receivers' results of a batch of a feed with ssdr_set_feed_subrx -- the row count, the list and the
+    settings latched at its submit, and pinned host pointers (NULL for a part the batch did not fill)"""
+    _fields_ = [("n", C.c_uint32), ("reserved", C.c_uint32),
+                ("list", C.POINTER(SubRx)), ("stages", C.POINTER(RxStages)),
+                ("pcm", C.POINTER(C.c_int16)), ("rssi", C.POINTER(C.c_float)), ("flags", C.POINTER(C.c_uint8)),
+                ("closed", C.POINTER(C.c_uint8)), ("adpcm", C.POINTER(C.c_uint8)), ("iq", C.POINTER(C.c_int16)),
+                ("nb_mask", C.POINTER(C.c_uint8)), ("play", C.POINTER(C.c_int16))]
+
+
+assert C.sizeof(FeedSubRx) == 88
 assert C.sizeof(ChanConsts) == 64 and C.sizeof(ChanState) == 64 and C.sizeof(ChanParams) == 88
 assert C.sizeof(Db2colChan) == 48 and C.sizeof(PlayChan) == 16
 WIRE_BODY = 17 + FRAME * 4
@@ -275,6 +288,10 @@ _SIGS = {
     "ssdr_feed_post": (C.c_int, [_P, C.POINTER(Db2colChan), C.POINTER(PlayChan)]),
     "ssdr_feed_collect_post": (C.c_int, [_P, C.POINTER(_P), C.POINTER(_P), C.POINTER(_P), C.POINTER(_P)]),
     "ssdr_feed_collect_listen": (C.c_int, [_P, C.POINTER(FeedListen)]),
+    "ssdr_set_feed_subrx": (C.c_int, [_P, C.c_int]),
+    "ssdr_get_feed_subrx": (C.c_int, [_P, C.POINTER(C.c_int)]),
+    "ssdr_feed_subrx_play": (C.c_int, [_P, C.POINTER(PlayChan), C.c_uint32]),
+    "ssdr_feed_collect_subrx": (C.c_int, [_P, C.POINTER(FeedSubRx)]),
     "ssdr_feed_close": (C.c_int, [_P]),
     "ssdr_copy_from_device": (C.c_int, [_P, _P, _P, C.c_uint64]),
     "ssdr_wf_device": (C.c_int, [_P, C.POINTER(_P), C.POINTER(C.c_uint32)]),
@@ -322,7 +339,8 @@ _NEWER_THAN_AB_LIBS = ("ssdr_feed_collect_listen", "ssdr_set_subrx", "ssdr_get_s
                        "ssdr_subrx_stage_results", "ssdr_get_subrx_stage_state", "ssdr_set_wb_rx_stages", "ssdr_get_wb_rx_stages",
                        "ssdr_wb_rx_stage_results", "ssdr_get_wb_rx_stage_state", "ssdr_rx_tail_stats", "ssdr_set_subrx_noise_blanker",
                        "ssdr_get_subrx_noise_blanker", "ssdr_subrx_nb_mask", "ssdr_set_wb_rx_noise_blanker", "ssdr_get_wb_rx_noise_blanker",
-                       "ssdr_wb_rx_nb_mask", "ssdr_set_rx_iq", "ssdr_get_rx_iq", "ssdr_subrx_audio_iq", "ssdr_wb_rx_audio_iq")      # entry points a library named by SSDR_LIB_PATH (A/B builds only) may predate
+                       "ssdr_wb_rx_nb_mask", "ssdr_set_rx_iq", "ssdr_get_rx_iq", "ssdr_subrx_audio_iq", "ssdr_wb_rx_audio_iq",
+                       "ssdr_set_feed_subrx", "ssdr_get_feed_subrx", "ssdr_feed_subrx_play", "ssdr_feed_collect_subrx")      # entry points a library named by SSDR_LIB_PATH (A/B builds only) may predate
 
 
 def _load():

@@ -251,6 +251,19 @@ struct ssdr_ctx {
         int16_t *h_wv_lines = nullptr;
         std::vector<uint32_t> sq_list, snd_list, wf_list;
         std::vector<ssdr_wf_view> wv;
+        // ssdr_set_feed_subrx: where the sub-receivers' results of `b.sub` arrive on the host, their play blocks, and what the batch
+        // ran with -- the list, the rows' stage settings (empty: never set), the rows whose squelch / encoder acted, which parts it filled
+        int16_t *h_sub_pcm = nullptr;
+        float *h_sub_rssi = nullptr;
+        uint8_t *h_sub_flags = nullptr, *h_sub_closed = nullptr, *h_sub_adpcm = nullptr, *h_sub_nb_mask = nullptr;
+        uint32_t *h_sub_iq = nullptr;
+        int16_t *d_sub_play = nullptr, *h_sub_play = nullptr;
+        ssdr_play_chan *h_sub_playchan = nullptr;
+        std::vector<ssdr_subrx> sub_list;
+        std::vector<ssdr_rx_stages> sub_st;
+        std::vector<uint8_t> sub_sq_on, sub_enc_on;
+        bool sub_tail = false, sub_nb = false, sub_iq = false, sub_play = false;
+        bool sub_zeroed = false;                         // the rows of h_sub_closed / h_sub_adpcm whose stage did not act have been cleared
     };
     std::vector<FeedSlot> feed;
     uint32_t feed_frames = 0, feed_head = 0, feed_tail = 0, feed_inflight = 0;
@@ -260,6 +273,9 @@ struct ssdr_ctx {
     bool feed_lazy = false;                              // SSDR_FEED_LAZY_OUT: only the selected channels' results are copied back
     uint32_t feed_lazy_max = 0;                          // rows the compact buffers hold
     bool feed_listen = false;                            // SSDR_FEED_LISTEN: the listener stages run in the slot pipeline
+    bool feed_sub_ok = false;                            // ssdr_set_feed_subrx: a listen feed takes the sub-receivers into its slots
+    bool feed_sub = false;                               // ... and the open feed is such a one
+    std::vector<ssdr_play_chan> feed_subplay;            // ssdr_feed_subrx_play: the rows' volume and balance for the next submits (empty: no play blocks)
     std::vector<ssdr_db2col_chan> feed_dbchan;           // display state for the next submits (ssdr_feed_post)
     std::vector<ssdr_play_chan> feed_playchan;
     int feed_last = -1;                                  // slot ssdr_feed_collect returned last
@@ -2780,6 +2796,8 @@ static int play_launch(ssdr_ctx *c, const int16_t *pcm, uint32_t nf, int16_t *ou
     return timed_end(c, SSDR_K_PLAY);
 }
 
+static int bank_play_launch(ssdr_ctx *c, RxBank &bk, const int16_t *pcm, uint32_t n, uint32_t nf, const ssdr_play_chan *chans, int16_t *out);
+
 // ---- pipelined host feed ------------------------------------------------------------------------------------
 // Three streams: host->device copy of batch k+1, the two kernels of batch k, device->host copy of batch k-1.
 // The kernels stay on the ctx stream, in batch order, so the per-channel state and the waterfall's partial sums
@@ -2833,6 +2851,22 @@ static void feed_slot_layout(const ssdr_ctx *c, uint32_t nf, uint32_t flags, ssd
     if (listen) { b.sq_closed_bytes = sq_b; b.snd_adpcm_bytes = snd_b; b.wf_adpcm_bytes = wfa_b; b.wv_lines_rows = wv_rows; }
     both(b.d_sq_closed, s.h_sq_closed, sq_b, listen); both(b.d_snd_adpcm, s.h_snd_adpcm, snd_b, listen);
     both(b.d_wf_adpcm, s.h_wf_adpcm, wfa_b, listen); both(b.d_wv_lines, s.h_wv_lines, wv_rows * SSDR_NFFT * 2, listen);
+    // ssdr_set_feed_subrx (with SSDR_FEED_LISTEN): the sub-receivers' results, every part for SSDR_SUBRX_MAX rows of nf frames -- PCM |
+    // RSSI | flags | closed flags | SND payloads | blank masks (D = 1) | I,Q pairs, if ssdr_set_rx_iq is on for them | play blocks
+    // (SSDR_FEED_POST; the x4 form, either rate fits) with the rows' settings on the host.  Without the switch: not a byte.
+    const bool sub = listen && c->feed_sub_ok, sub_iq = sub && c->sub.iq_ok, sub_play = sub && post;
+    const size_t sub_rf = (size_t)SSDR_SUBRX_MAX * nf;
+    if (sub) {
+        BankOut &o = b.sub;
+        o.pcm_cap = o.rssi_cap = o.flags_cap = o.closed_cap = o.adpcm_cap = o.nb_mask_cap = sub_rf;
+        if (sub_iq) o.iq_cap = sub_rf;
+    }
+    both(b.sub.d_pcm, s.h_sub_pcm, sub_rf * SSDR_FRAME * 2, sub); both(b.sub.d_rssi, s.h_sub_rssi, sub_rf * sizeof(float), sub);
+    both(b.sub.d_flags, s.h_sub_flags, sub_rf, sub); both(b.sub.d_closed, s.h_sub_closed, sub_rf, sub);
+    both(b.sub.d_adpcm, s.h_sub_adpcm, sub_rf * (SSDR_FRAME / 2), sub); both(b.sub.d_nb_mask, s.h_sub_nb_mask, sub_rf * 64, sub);
+    both(b.sub.d_iq, s.h_sub_iq, sub_rf * SSDR_FRAME * 4, sub_iq);
+    both(s.d_sub_play, s.h_sub_play, sub_rf * 2048 * 2 * sizeof(int16_t), sub_play);
+    host(s.h_sub_playchan, (size_t)SSDR_SUBRX_MAX * sizeof(ssdr_play_chan), sub_play);
     if (d_bytes) *d_bytes = d_off;
     if (h_bytes) *h_bytes = h_off;
 }
@@ -2860,6 +2894,8 @@ int ssdr_feed_close(ssdr_ctx *c) SSDR_GUARD
     c->feed_post = false;
     c->feed_lazy = false;
     c->feed_listen = false;
+    c->feed_sub = false;
+    c->feed_subplay.clear();
     c->feed_last = -1;
     return SSDR_OK;
 } SSDR_UNGUARD
@@ -2871,7 +2907,8 @@ int ssdr_feed_open(ssdr_ctx *c, uint32_t n_frames, uint32_t depth, uint32_t flag
     if (!c->feed.empty() || c->concurrent || c->decim != 1 || c->zoom != 1) return SSDR_ESTATE;
     // no wire compression, squelch, de-emphasis or waterfall view in the slot pipeline, unless it was opened for them
     const bool listen = (flags & SSDR_FEED_LISTEN) != 0;
-    if (!c->h_sub.empty()) return SSDR_ESTATE;               // nor a sub-receiver, whatever it was opened for
+    const bool sub = listen && c->feed_sub_ok;               // ssdr_set_feed_subrx: the sub-receivers run in the slots of a listen feed
+    if (!c->h_sub.empty() && !sub) return SSDR_ESTATE;       // without it: no sub-receiver, whatever it was opened for
     if (c->chz_streams) return SSDR_ESTATE;                  // nor a channeliser: it fills the ctx's own batch, not a slot
     if (!listen && (c->comp_snd_n || c->comp_wf_n || c->sq_set_n || c->de_set_n || !c->h_wv.empty())) return SSDR_ESTATE;
     HIP_TRY(hipSetDevice(c->device));
@@ -2897,6 +2934,8 @@ int ssdr_feed_open(ssdr_ctx *c, uint32_t n_frames, uint32_t depth, uint32_t flag
     // the ctx's own listener results are from before the feed, and the streams go on in the slots: no getter hands them out again,
     // after the close either, until a synchronous run has made new ones
     if (listen) c->own.sq_valid = c->own.snd_adpcm_valid = c->own.wf_adpcm_valid = c->wv_run_valid = false;
+    c->feed_sub = sub;                       // ... and so with the sub-receivers' results
+    if (sub) c->sub.run_valid = c->sub.st_valid = c->sub.iq_valid = c->sub.nb_valid = false;
     bool ok = hipStreamCreateWithFlags(&c->feed_s_in, hipStreamNonBlocking) == hipSuccess &&
               hipStreamCreateWithFlags(&c->feed_s_out, hipStreamNonBlocking) == hipSuccess;
     for (auto &s : c->feed) {
@@ -2979,6 +3018,23 @@ static int feed_submit_impl(ssdr_ctx *c, const void *host_in)
         HIP_TRY(hipMemcpyAsync(c->d_play, s.h_playchan, (size_t)c->n_post * sizeof(ssdr_play_chan), hipMemcpyHostToDevice, c->stream));
         SSDR_TRY(play_launch(c, b.d_pcm, nf, s.d_play, c->recording ? s.d_mono : nullptr));
     }
+    if (c->feed_sub) {                                      // what the sub-receivers ran with: a setter changes the ctx's, not these
+        RxBank &bk = c->sub;
+        const uint32_t n = bk.rows();
+        s.sub_list = c->h_sub;
+        s.sub_st = bk.h_st;
+        s.sub_tail = n && !bk.h_tail.empty();
+        s.sub_nb = n && bk.nb_on;
+        s.sub_iq = n && bk.iq_rows();
+        s.sub_sq_on.assign(n, 0); s.sub_enc_on.assign(n, 0);
+        if (s.sub_tail) for (const SsdrRxTailRow &r : bk.h_tail) { s.sub_sq_on[r.row] = r.squelch != 0; s.sub_enc_on[r.row] = r.adpcm != 0; }
+        s.sub_zeroed = false;
+        s.sub_play = n && c->feed_post && c->feed_subplay.size() == n;
+        if (s.sub_play) {                                   // play_buffer of the rows' PCM, behind the bank's tail, on the bank's own history
+            memcpy(s.h_sub_playchan, c->feed_subplay.data(), (size_t)n * sizeof(ssdr_play_chan));
+            SSDR_TRY(bank_play_launch(c, bk, b.sub.d_pcm, n, nf, s.h_sub_playchan, s.d_sub_play));
+        }
+    }
     s.lines = lines;
     // what goes back: every channel's rows, or (SSDR_FEED_LAZY_OUT) the selected channels' rows gathered into compact ones
     const int16_t *o_wf = b.d_wf_out, *o_pcm = b.d_pcm;
@@ -3026,6 +3082,18 @@ static int feed_submit_impl(ssdr_ctx *c, const void *host_in)
             {s.h_wv_lines, b.d_wv_lines, (size_t)b.wv_run_total * SSDR_NFFT * 2}};
         for (const auto &p : part)
             if (p.bytes) HIP_TRY(hipMemcpyAsync(p.h, p.d, p.bytes, hipMemcpyDeviceToHost, c->feed_s_out));
+    }
+    if (c->feed_sub && !s.sub_list.empty()) {               // ... and per part of the sub-receivers': the rows in force, never the capacity
+        const size_t rf = s.sub_list.size() * nf;
+        const size_t per_frame = c->kiwi_rate != SSDR_RATE ? (size_t)SSDR_RS_OUT_PER_FRAME : 2048;
+        const struct { void *h; const void *d; size_t bytes; bool on; } part[8] = {
+            {s.h_sub_pcm, b.sub.d_pcm, rf * SSDR_FRAME * 2, true}, {s.h_sub_rssi, b.sub.d_rssi, rf * sizeof(float), true},
+            {s.h_sub_flags, b.sub.d_flags, rf, true}, {s.h_sub_closed, b.sub.d_closed, rf, s.sub_tail},
+            {s.h_sub_adpcm, b.sub.d_adpcm, rf * (SSDR_FRAME / 2), s.sub_tail}, {s.h_sub_nb_mask, b.sub.d_nb_mask, rf * 64, s.sub_nb},
+            {s.h_sub_iq, b.sub.d_iq, rf * SSDR_FRAME * 4, s.sub_iq},
+            {s.h_sub_play, s.d_sub_play, rf * per_frame * 2 * sizeof(int16_t), s.sub_play}};
+        for (const auto &p : part)
+            if (p.on) HIP_TRY(hipMemcpyAsync(p.h, p.d, p.bytes, hipMemcpyDeviceToHost, c->feed_s_out));
     }
     HIP_TRY(hipEventRecord(s.ev_out, c->feed_s_out));
     c->feed_head = (c->feed_head + 1) % (uint32_t)c->feed.size();
@@ -4101,7 +4169,20 @@ static int bank_consts(ssdr_ctx *c, const RxBank &bk, uint32_t first_row, uint32
     HIP_TRY(hipStreamSynchronize(c->stream));
     return SSDR_OK;
 }
-// play_buffer on the last run's frames, the receivers as the channels of a small ctx: the history is the bank's, the tap tables the ctx's
+// play_buffer of `n` rows of `nf` frames at `pcm` under the settings at `chans` (host), to `out`, queued on the main stream: the
+// history is the bank's, the tap tables the ctx's (ensure_play has made them)
+static int bank_play_launch(ssdr_ctx *c, RxBank &bk, const int16_t *pcm, uint32_t n, uint32_t nf, const ssdr_play_chan *chans, int16_t *out)
+{
+    const bool wide = c->kiwi_rate != SSDR_RATE;
+    HIP_TRY(hipMemcpyAsync(bk.d_play, chans, (size_t)n * sizeof(ssdr_play_chan), hipMemcpyHostToDevice, c->stream));
+    SsdrPlayArgs a;
+    a.pcm = pcm; a.n_ch = n; a.n_frames = nf; a.chans = bk.d_play; a.taps = c->d_play_taps; a.rs_taps = c->d_play_rs_taps;
+    a.hist = bk.d_phist[bk.set]; a.hist_out = bk.d_phist_alt; a.sel = nullptr; a.n_sel = n; a.out = out; a.mono = nullptr;
+    HIP_TRY(wide ? ssdr_launch_play_rs(a, c->stream) : ssdr_launch_play(a, c->stream));
+    if (!wide) std::swap(bk.d_phist[bk.set], bk.d_phist_alt);                       // (the 64/27 branch carries no history)
+    return SSDR_OK;
+}
+// play_buffer on the last run's frames, the receivers as the channels of a small ctx
 static int bank_playbuffer(ssdr_ctx *c, RxBank &bk, const BankOut &res, const ssdr_play_chan *chans, int16_t *out, int out_is_device)
 {
     if (!chans) return SSDR_EINVAL;
@@ -4113,12 +4194,7 @@ static int bank_playbuffer(ssdr_ctx *c, RxBank &bk, const BankOut &res, const ss
     const size_t per_frame = wide ? (size_t)SSDR_RS_OUT_PER_FRAME : 2048;
     SSDR_TRY(ensure_play(c));
     SSDR_TRY(grow(c, bk.d_play_out, bk.play_cap, (size_t)n * nf, (size_t)2048 * 2 * sizeof(int16_t)));
-    HIP_TRY(hipMemcpyAsync(bk.d_play, chans, (size_t)n * sizeof(ssdr_play_chan), hipMemcpyHostToDevice, c->stream));
-    SsdrPlayArgs a;
-    a.pcm = res.d_pcm; a.n_ch = n; a.n_frames = nf; a.chans = bk.d_play; a.taps = c->d_play_taps; a.rs_taps = c->d_play_rs_taps;
-    a.hist = bk.d_phist[bk.set]; a.hist_out = bk.d_phist_alt; a.sel = nullptr; a.n_sel = n; a.out = bk.d_play_out; a.mono = nullptr;
-    HIP_TRY(wide ? ssdr_launch_play_rs(a, c->stream) : ssdr_launch_play(a, c->stream));
-    if (!wide) std::swap(bk.d_phist[bk.set], bk.d_phist_alt);                       // (the 64/27 branch carries no history)
+    SSDR_TRY(bank_play_launch(c, bk, res.d_pcm, n, nf, chans, bk.d_play_out));
     if (out) SSDR_TRY(copy_out(c, out, bk.d_play_out, (size_t)n * nf * per_frame * 2 * sizeof(int16_t), out_is_device, kSyncLater));
     HIP_TRY(hipStreamSynchronize(c->stream));
     return SSDR_OK;
@@ -4130,8 +4206,9 @@ int ssdr_set_subrx(ssdr_ctx *c, const ssdr_subrx *subs, uint32_t count) SSDR_GUA
     std::vector<ssdr_chan_consts> k;                        // all or nothing: every sub-receiver is checked before the list is touched
     std::vector<float> taps;
     SSDR_TRY(subrx_compile(c, subs, count, c->decim, c->kiwi_rate, k, taps));
-    if (count && !c->feed.empty()) return SSDR_ESTATE;
+    if (count && !c->feed.empty() && !c->feed_sub) return SSDR_ESTATE;      // (a feed with ssdr_set_feed_subrx runs them in its slots)
     if (!count) {                                           // (the device is not touched)
+        c->feed_subplay.clear();
         c->h_sub.clear();
         bank_clear(c->sub);
         return SSDR_OK;
@@ -4146,6 +4223,58 @@ int ssdr_set_subrx(ssdr_ctx *c, const ssdr_subrx *subs, uint32_t count) SSDR_GUA
                           [](const ssdr_subrx &a, const ssdr_subrx &b) { return a.channel == b.channel; }, &same_rows));
     c->h_sub.assign(subs, subs + count);
     if (!same_rows) c->sub.run_valid = false;               // (new parameters of the same rows leave the last run's results what they were)
+    if (c->feed_subplay.size() != count) c->feed_subplay.clear();           // ssdr_feed_subrx_play: a list of another length forgets it
+    return SSDR_OK;
+} SSDR_UNGUARD
+
+// ---- the sub-receivers on the pipelined feed (ssdr_set_feed_subrx): the switch, the rows' play settings, a batch's results
+int ssdr_set_feed_subrx(ssdr_ctx *c, int on) SSDR_GUARD
+{
+    if (!c) return SSDR_EINVAL;
+    if (!c->feed.empty()) return SSDR_ESTATE;               // the slots are laid out for the switch as it stood at the open
+    c->feed_sub_ok = on != 0;
+    return SSDR_OK;
+} SSDR_UNGUARD
+
+int ssdr_get_feed_subrx(ssdr_ctx *c, int *on) SSDR_GUARD
+{
+    if (!c || !on) return SSDR_EINVAL;
+    *on = c->feed_sub_ok ? 1 : 0;
+    return SSDR_OK;
+} SSDR_UNGUARD
+
+int ssdr_feed_subrx_play(ssdr_ctx *c, const ssdr_play_chan *chans, uint32_t count) SSDR_GUARD
+{
+    if (!c || (count && !chans)) return SSDR_EINVAL;
+    if (c->feed.empty() || !c->feed_post || !c->feed_sub) return SSDR_ESTATE;
+    if (count && count != c->h_sub.size()) return SSDR_EINVAL;
+    c->feed_subplay.assign(chans, chans + count);
+    return SSDR_OK;
+} SSDR_UNGUARD
+
+int ssdr_feed_collect_subrx(ssdr_ctx *c, ssdr_feed_subrx *out) SSDR_GUARD
+{
+    if (!c || !out) return SSDR_EINVAL;
+    if (c->feed.empty() || !c->feed_sub || c->feed_last < 0) return SSDR_ESTATE;
+    auto &s = c->feed[c->feed_last];
+    memset(out, 0, sizeof *out);
+    const size_t n = s.sub_list.size(), nf = c->feed_frames;
+    if (!n) return SSDR_OK;
+    if (s.sub_tail && !s.sub_zeroed) {                      // a row whose stage did not act is zero, as ssdr_subrx_stage_results hands it out
+        for (size_t j = 0; j < n; j++) {
+            if (!s.sub_sq_on[j]) memset(s.h_sub_closed + j * nf, 0, nf);
+            if (!s.sub_enc_on[j]) memset(s.h_sub_adpcm + j * nf * (SSDR_FRAME / 2), 0, nf * (SSDR_FRAME / 2));
+        }
+        s.sub_zeroed = true;
+    }
+    out->n = (uint32_t)n;
+    out->list = s.sub_list.data();
+    out->stages = s.sub_st.empty() ? nullptr : s.sub_st.data();
+    out->pcm = s.h_sub_pcm; out->rssi = s.h_sub_rssi; out->flags = s.h_sub_flags;
+    if (s.sub_tail) { out->closed = s.h_sub_closed; out->adpcm = s.h_sub_adpcm; }
+    if (s.sub_iq) out->iq = reinterpret_cast<const int16_t *>(s.h_sub_iq);
+    if (s.sub_nb) out->nb_mask = s.h_sub_nb_mask;
+    if (s.sub_play) out->play = s.h_sub_play;
     return SSDR_OK;
 } SSDR_UNGUARD
 

@@ -1075,6 +1075,57 @@ class SsdrEngine:
                 "views": [(v.channel, v.zoom, v.offset_hz) for v in o.views[:o.view_n]],
                 "view_lines": [lines[cuts[i]:cuts[i + 1]] for i in range(o.view_n)]}
 
+    def set_feed_subrx(self, on):
+        """Let a listen feed (feed_open(listen=True)) run the sub-receivers in its slots, or stop it.  Off until set.  With it on,
+        feed_open succeeds with sub-receivers set, and set_subrx / set_subrx_stages / set_subrx_noise_blanker are accepted while the
+        feed is open and act on the batches submitted after the call; feed_collect_subrx hands out a batch's rows.  SsdrError
+        (SSDR_ESTATE), and nothing changes, in either direction while a feed is open."""
+        check(lib.ssdr_set_feed_subrx(self._ctx, 1 if on else 0), "ssdr_set_feed_subrx")
+
+    def feed_subrx(self):
+        """-> whether a listen feed takes the sub-receivers into its slots"""
+        on = C.c_int(0)
+        check(lib.ssdr_get_feed_subrx(self._ctx, C.byref(on)), "ssdr_get_feed_subrx")
+        return bool(on.value)
+
+    def feed_subrx_play(self, chans):
+        """Volume and balance of the sub-receivers for the batches submitted from now on, on a feed with post=True and set_feed_subrx:
+        a list of PlayChan, one per sub-receiver in list order (or a ctypes array); None or an empty list: no play blocks.  A list
+        change to another length clears the setting."""
+        n = 0 if chans is None else len(chans)
+        arr = None if n == 0 else chans if isinstance(chans, C.Array) else (PlayChan * n)(*chans)
+        check(lib.ssdr_feed_subrx_play(self._ctx, arr, n), "ssdr_feed_subrx_play")
+
+    def feed_collect_subrx(self):
+        """of the batch feed_collect returned last, on a feed with set_feed_subrx -> dict of the sub-receivers' rows in the order of
+        the list latched at that batch's submit, as views of pinned memory (valid as long as feed_collect's arrays): n; ids, channels,
+        modes (lists), params [ChanParams], stages (as subrx_stages, or None if never set); pcm int16 [n, n_frames*512], rssi float32
+        [n, n_frames], flags uint8 [n, n_frames]; closed uint8 [n, n_frames] and adpcm uint8 [n, n_frames*256] (None if no row had an
+        acting stage); iq int16 [n, n_frames*512, 2] (None if no row was in "iq" mode); nb_mask uint8 [n, n_frames*64] (None if no row
+        blanked); play int16 [n, n_frames*L, 2] (None unless feed_subrx_play is set)"""
+        o = L.FeedSubRx()
+        check(lib.ssdr_feed_collect_subrx(self._ctx, C.byref(o)), "ssdr_feed_collect_subrx")
+        n, nf = int(o.n), self._feed_frames
+
+        def view(ptr, shape):
+            return np.ctypeslib.as_array(ptr, shape=(int(np.prod(shape)),)).reshape(shape) if n and ptr else None
+
+        params = []
+        for v in o.list[:n]:
+            p = ChanParams()
+            C.memmove(C.byref(p), C.byref(v.params), C.sizeof(ChanParams))
+            params.append(p)
+        stages = None
+        if n and o.stages:
+            stages = [((t.squelch.fm_level, t.squelch.fm_max, t.squelch.rssi_level, t.squelch.tail_frames), (t.deemp.am, t.deemp.nfm),
+                       t.snd_adpcm) for t in o.stages[:n]]
+        return {"n": n, "ids": [int(v.id) for v in o.list[:n]], "channels": [int(v.channel) for v in o.list[:n]],
+                "modes": [int(p.mode) for p in params], "params": params, "stages": stages,
+                "pcm": view(o.pcm, (n, nf * L.FRAME)), "rssi": view(o.rssi, (n, nf)), "flags": view(o.flags, (n, nf)),
+                "closed": view(o.closed, (n, nf)), "adpcm": view(o.adpcm, (n, nf * L.FRAME // 2)),
+                "iq": view(o.iq, (n, nf * L.FRAME, 2)), "nb_mask": view(o.nb_mask, (n, nf * 64)),
+                "play": view(o.play, (n, nf * self.playbuffer_frame_len(), 2))}
+
     def feed_close(self):
         check(lib.ssdr_feed_close(self._ctx), "ssdr_feed_close")
 

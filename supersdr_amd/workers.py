@@ -130,12 +130,15 @@ class SuperframeResult:
     sub_adpcm / tuned_adpcm uint8 [n, frames*256], rows as sub_ids / tuned_ids, a row whose stage is off all zero (each None: no
     receiver of the family squelches, resp. compresses).
     On a hub built with rx_iq=True: sub_iq / tuned_iq int16 [n, frames*512, 2], rows as sub_ids / tuned_ids, the I,Q of the receivers
-    in "SET mod=iq" and zero for every other (each None: no receiver of the family is in that mode)."""
+    in "SET mod=iq" and zero for every other (each None: no receiver of the family is in that mode).
+    On a pipelined hub built with sub_feed=True the sub_* fields are the batch's own (ssdr_feed_collect_subrx): sub_ids as latched at
+    its submit, and sub_latched maps each of them to (mode, stages) as the batch ran with them (None on every other hub: the table
+    as it is now says it)."""
     __slots__ = ("seq", "wf", "n_avg", "color", "chans", "pcm", "rssi", "flags", "play", "mono", "iq", "wire_rssi", "post_channels", "out_channels",
                  "snd_adpcm", "wf_adpcm", "snd_adpcm_channels", "wf_adpcm_channels", "squelched", "view_lines", "view_channels",
                  "squelched_channels", "sub_ids", "sub_pcm", "sub_rssi", "sub_flags", "sub_play", "scope_ids", "scope_lines",
                  "tuned_ids", "tuned_pcm", "tuned_rssi", "tuned_flags", "tuned_play", "sub_closed", "sub_adpcm", "tuned_closed", "tuned_adpcm",
-                 "sub_iq", "tuned_iq")
+                 "sub_iq", "tuned_iq", "sub_latched")
 
     def __init__(self, **kw):
         for k in self.__slots__:
@@ -269,6 +272,11 @@ class IQHub:
     rx_iq=True, a third independent switch, lets them take mode "iq" (open_sub, set_sub_params, open_tuned, retune_tuned,
     set_tuned_params; ssdr_set_rx_iq, set once when the hub is built): their frames then carry iq_block as a channel's do.  Without it
     mod=iq is refused before the engine is touched, with the texts it always had.
+    sub_feed=True (with pipeline=True and listen=True; ssdr_set_feed_subrx) runs the sub-receivers in the slot pipeline: open_sub,
+    set_sub_params, close_sub and -- with rx_stages / rx_blanker / rx_iq -- their stages, blanker and mod=iq then work as on the
+    synchronous hub, on the superframes submitted after the call.  A batch's rows reach sub_queue `depth - 1` superframes late under
+    the ids, modes and settings latched at its submit: a sub-receiver opened after a batch left gets nothing from it, one closed while
+    its batch was in flight has its rows dropped.  Without it a pipelined hub refuses sub-receivers as it always did.
     `batch_superframes=K` runs K superframes per GPU call (K lines + 2K audio frames per channel and call): latency for
     launch efficiency at very large channel counts.  `exact_bins=True`: the waterfall stage in float64 (ssdr_set_exact_bins).  `copy_threads=T` splits feed_block's copy of a large block over T threads (default: up to 8 on hubs of 8192+ receivers).
     """
@@ -278,7 +286,7 @@ class IQHub:
     def __init__(self, n_channels, device=0, engine=None, max_queue=64, gpu_post=True, kiwi_rate=12000, trace_rows=0,
                  backlog_superframes=8, stall_superframes=4, pipeline=False, depth=3, hop=1024, zoom=1, lazy=None,
                  batch_superframes=1, wire=False, copy_threads=None, exact_bins=False, lazy_out=False, listen=False, rx_stages=False,
-                 rx_blanker=False, rx_iq=False):
+                 rx_blanker=False, rx_iq=False, sub_feed=False):
         self.n_ch = int(n_channels)
         # argument combinations that cannot work are refused BEFORE an engine (a GPU context) exists
         self._lazy = (self.n_ch > self.LAZY_ABOVE) if lazy is None else bool(lazy)
@@ -288,7 +296,14 @@ class IQHub:
             raise ValueError("lazy_out needs the pipelined feed and a lazy hub (pipeline=True, lazy=True)")
         if listen and not pipeline:
             raise ValueError("listen needs the pipelined feed (pipeline=True): the synchronous hub runs the listener stages as it is")
+        if sub_feed and not (pipeline and listen):
+            raise ValueError("sub_feed needs the pipelined listen feed (pipeline=True, listen=True): the synchronous hub runs sub-receivers as it is")
         self.engine = engine if engine is not None else SsdrEngine(self.n_ch, device)
+        # sub_feed (ssdr_set_feed_subrx): the pipelined listen feed runs the sub-receivers in its slots
+        self._sub_feed = bool(sub_feed)
+        if self._sub_feed and not hasattr(self.engine, "set_feed_subrx"):
+            raise ValueError("sub_feed needs an engine with set_feed_subrx")
+        self._sub_play_set = False                   # feed_subrx_play holds a setting: somebody listens to a sub-receiver
         # waterfall zoom ("SET zoom=", utils_supersdr.py:741, 839): the lines then span 1/zoom of the IQ band around each
         # channel's zoom centre (set_wf_center) and one line needs `zoom` superframes: the hub batches that many per GPU run
         self.zoom = int(zoom)
@@ -401,11 +416,13 @@ class IQHub:
         self._rx_blanker = bool(rx_blanker)
         self._rx_nb = {"sub": {}, "tuned": {}}       # id -> (gate_us, thresh) of the receivers whose blanker somebody has set
         # rx_iq=True: the extra receivers take "SET mod=iq".  The engine's switch is set here, once, for both families (a pipelined
-        # hub has no extra receivers; an engine without the switch refuses the mode where it is asked for: _check_rx_iq)
+        # hub has no extra receivers but the sub-receivers of sub_feed=True, whose switch must be on before the feed opens; an engine
+        # without the switch refuses the mode where it is asked for: _check_rx_iq)
         self._rx_iq = bool(rx_iq)
-        if self._rx_iq and not self.pipeline and hasattr(self.engine, "set_rx_iq"):
+        if self._rx_iq and (not self.pipeline or self._sub_feed) and hasattr(self.engine, "set_rx_iq"):
             self.engine.set_rx_iq("sub", True)
-            self.engine.set_rx_iq("tuned", True)
+            if not self.pipeline:
+                self.engine.set_rx_iq("tuned", True)
         self.sub_queue, self.sub_clients = self._subs.queue, self._subs.clients
         self.tuned_queue, self.tuned_clients = self._tuned.queue, self._tuned.clients
         self.scope_queue, self.scope_clients = self._scopes.queue, self._scopes.clients
@@ -416,6 +433,8 @@ class IQHub:
         self._recording = False
         self._lock = threading.RLock()
         self.superframes = 0
+        if self._sub_feed:
+            self.engine.set_feed_subrx(True)
         if self.pipeline:
             self.engine.feed_open(2 * self.zoom * self.batch_superframes, self._depth, post=self.gpu_post, **({"wire": True} if self.wire else {}),
                                   **({"lazy_out": True} if self._lazy_out else {}), **({"listen": True} if self._listen else {}))
@@ -721,12 +740,12 @@ class IQHub:
         """A sub-receiver on `channel`: a further audio chain (NCO, filter, demodulator, AGC) on the channel's raw IQ with parameters
         of its own, beside the channel's own demodulator, which does not notice.  -> sid, the hub's name for it: its frames arrive
         in sub_queue[sid], set_sub_params(sid, p) retunes it (state kept, like set_params), close_sub(sid) ends it.  The other
-        sub-receivers keep their streams.  ValueError on a pipelined hub (before the engine is touched), beyond 256 of them (SSDR_SUBRX_MAX), for
+        sub-receivers keep their streams.  ValueError on a pipelined hub built without sub_feed=True (before the engine is touched), beyond 256 of them (SSDR_SUBRX_MAX), for
         mod=iq (unless the hub was built with rx_iq=True) and for parameters the library refuses; then nothing changes."""
         c = int(channel)
         if not 0 <= c < self.n_ch:
             raise IndexError("channel %d of %d" % (c, self.n_ch))
-        if self.pipeline:
+        if self.pipeline and not getattr(self, "_sub_feed", False):
             raise ValueError("a sub-receiver needs the synchronous hub (the pipelined feed does not run sub-receivers)")
         p = _copy_params(params if params is not None else self._default_params)
         self._check_sub_params(p)
@@ -1345,11 +1364,17 @@ class IQHub:
         """-> the ids of a receiver table's rows in "SET mod=iq" (a row ends with its ChanParams)"""
         return [i for i, row in table.rows.items() if row[-1].mode == L.MODE_IQ]
 
-    def _hand_out_rx(self, queues, ids, pcm, rssi, flags, play, closed=None, adpcm=None, settings=None, iq=None, table=None):
+    def _hand_out_rx(self, queues, ids, pcm, rssi, flags, play, closed=None, adpcm=None, settings=None, iq=None, table=None, latched=None):
         """a receiver list's frames (rows in the order of `ids`) to the queues of those that have one; a compressing receiver's carry
-        their payload, a squelched frame its mark, one in "SET mod=iq" its I,Q pairs (and never a payload), as a channel's do"""
+        their payload, a squelched frame its mark, one in "SET mod=iq" its I,Q pairs (and never a payload), as a channel's do.
+        `latched` (a pipelined batch: id -> (mode, stages) at its submit) takes the place of the table and the settings as they are
+        now: a row's marks are those of the batch"""
         P, H = self.play_len, L.FRAME // 2
-        in_iq = set(self._rx_in_iq(table)) if iq is not None else ()
+        if latched is not None:
+            settings = {i: st for i, (_, st) in latched.items() if st is not None}
+            in_iq = {i for i, (mode, _) in latched.items() if mode == L.MODE_IQ} if iq is not None else ()
+        else:
+            in_iq = set(self._rx_in_iq(table)) if iq is not None else ()
         for i, rid in enumerate(ids or ()):
             q = queues.get(rid)
             if q is None:
@@ -1424,7 +1449,7 @@ class IQHub:
                         fr.squelched = True
                 _put_drop_oldest(q, fr)
         self._hand_out_rx(self.sub_queue, r.sub_ids, r.sub_pcm, r.sub_rssi, r.sub_flags, r.sub_play, r.sub_closed, r.sub_adpcm, self._rx_st["sub"],
-                          r.sub_iq, self._subs)
+                          r.sub_iq, self._subs, r.sub_latched)
         self._hand_out_rx(self.tuned_queue, r.tuned_ids, r.tuned_pcm, r.tuned_rssi, r.tuned_flags, r.tuned_play, r.tuned_closed, r.tuned_adpcm,
                           self._rx_st["tuned"], r.tuned_iq, self._tuned)
         for i, sid in enumerate(r.scope_ids or ()):
@@ -1442,6 +1467,13 @@ class IQHub:
             eng.feed_post(self._db_arr, self._play_arr)
         if self._post_dirty:                          # (without gpu_post nobody else re-derives it: lazy_out's rows follow the attached channels)
             self._apply_post_selection()
+        if self._sub_feed and self.gpu_post:          # the sub-receivers' play blocks, while somebody listens to one: latched now as well
+            rows = [self._subs.clients.get(i) for i in self._subs.ids()]
+            listened = any(s is not None for s in rows)
+            if listened or self._sub_play_set:        # (a row nobody listens to plays at the neutral setting, as on the synchronous hub)
+                eng.feed_subrx_play([PlayChan(100.0, 0.0) if s is None else PlayChan(float(s.volume), float(s.audio_balance)) for s in rows]
+                                    if listened else None)
+                self._sub_play_set = listened
         if hasattr(eng, "feed_submit_from"):
             eng.feed_submit_from(batch)               # the H2D copy reads the hub's slot itself
         else:
@@ -1480,6 +1512,13 @@ class IQHub:
                 listen.update(squelched=li["sq_closed"], squelched_channels=[int(c) for c in li["sq_channels"]])
             if li["views"]:
                 listen.update(view_lines=li["view_lines"], view_channels=[int(v[0]) for v in li["views"]])
+        if self._sub_feed:                            # the sub-receivers' rows, with the ids, modes and settings latched at the batch's submit
+            su = eng.feed_collect_subrx()
+            if su["n"]:
+                stages = su["stages"] or [None] * su["n"]
+                listen.update(sub_ids=list(su["ids"]), sub_pcm=su["pcm"], sub_rssi=su["rssi"], sub_flags=su["flags"], sub_play=su["play"],
+                              sub_closed=su["closed"], sub_adpcm=su["adpcm"], sub_iq=su["iq"],
+                              sub_latched={i: (m, st) for i, m, st in zip(su["ids"], su["modes"], stages)})
         self._hand_out(SuperframeResult(seq=self.superframes - self._inflight, wf=wf, n_avg=n_avg, color=color, chans=chans, pcm=pcm,
                                         rssi=rssi, flags=flags, play=play, mono=mono, wire_rssi=got[3] if len(got) > 3 else None,
                                         post_channels=sel, out_channels=sel if self._lazy_out else None, **listen))
