@@ -1,7 +1,7 @@
 // abi_fault_harness.cpp -- test infrastructure for include/ssdr.h:11-14 ("never throws or aborts").
 //
 // Built by tests/test_lib_abi.py with g++ -rdynamic and run as a subprocess.  It replaces the global operator new of the
-// process; libssdr.so's own allocations (std::vector in csrc/ssdr_api.cpp: their call sites are instantiated inside the
+// process; libssdr.so's own allocations (std::vector in csrc/ssdr_api*.cpp: their call sites are instantiated inside the
 // library, so the return address lies in its text) bind to this replacement through the dynamic symbol table.  When armed,
 // the K-th allocation made FROM libssdr.so throws std::bad_alloc -- the HIP runtime's allocations are left alone.
 //

@@ -1,4 +1,4 @@
-"""Waterfall views off the beaten path (ssdr_set_wf_views, csrc/ssdr_wf_view.hip and its host code in ssdr_api.cpp).
+"""Waterfall views off the beaten path (ssdr_set_wf_views, csrc/ssdr_wf_view.hip and its host code in ssdr_api_wfview.cpp).
 
 The cases come from tests/wf_view_cases.py; tests/test_wf_view_edges_inputs.py proves without a GPU that each of them shows what it is
 there for and that the fp32 twin meets the float64 rule on all of them.  Here every call of every case is held, per view, bit for

@@ -36,6 +36,22 @@ def test_header_and_library_agree(S):
     assert sorted(L.EXPORTS) == names          # the ctypes binding covers exactly the header
 
 
+def test_only_the_header_functions_are_exported(S):
+    """a guard on the exported surface: the defined text symbols of the library's dynamic table are the functions include/ssdr.h
+    declares and C++ names that carry none of the host code's own types.  It held while the host code was one file of static functions;
+    it fails if a function that the units of csrc/ssdr_api*.cpp share leaves ssdr_api_internal.h's hidden visibility"""
+    import shutil
+    import subprocess
+    from supersdr_amd import _lib as L
+    if not shutil.which("nm"):
+        pytest.skip("nm is not on the path")
+    out = subprocess.run(["nm", "-D", "--defined-only", L.LIB_PATH], capture_output=True, text=True, check=True).stdout
+    text = [f[2] for f in (line.split() for line in out.splitlines()) if len(f) == 3 and f[1] == "T"]
+    assert sorted(n for n in text if not n.startswith("_Z")) == declared_functions()
+    internal = [n for n in text if n.startswith("_Z") and any(t in n for t in ("8ssdr_ctx", "6RxBank", "5Batch", "7BankOut"))]
+    assert not internal, internal
+
+
 def test_struct_layouts(S):
     from supersdr_amd import _lib as L
     assert C.sizeof(L.ChanParams) == 88 and C.sizeof(L.ChanConsts) == 64 and C.sizeof(L.ChanState) == 64
