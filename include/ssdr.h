@@ -1122,6 +1122,9 @@ int ssdr_selftest_sqrt(ssdr_ctx *ctx, uint64_t *mismatches);        /* AM envelo
 /* the same two square roots (scaled form; integer-power form, valid for 0 and [1, 2^33)) on n caller-chosen arguments, for
  * a check against an IEEE sqrt that is not the device's own */
 int ssdr_selftest_sqrt_values(ssdr_ctx *ctx, const float *in, float *out_scaled, float *out_int, uint32_t n);
+/* the kernels' log2 (which = 0: every positive normal float) and exp2 (which = 1: every float of [-130, 130]) against the
+ * compare-and-select and convert-to-integer forms they replaced, exhaustively and bit for bit; any other which: SSDR_EINVAL */
+int ssdr_selftest_math(ssdr_ctx *ctx, int which, uint64_t *mismatches);
 
 const char *ssdr_strerror(int code);
 const char *ssdr_last_hip_error(void);

@@ -323,6 +323,7 @@ _SIGS = {
     "ssdr_selftest_quantiser": (C.c_int, [_P, C.POINTER(C.c_uint64)]),
     "ssdr_selftest_sqrt": (C.c_int, [_P, C.POINTER(C.c_uint64)]),
     "ssdr_selftest_sqrt_values": (C.c_int, [_P, _P, _P, _P, C.c_uint32]),
+    "ssdr_selftest_math": (C.c_int, [_P, C.c_int, C.POINTER(C.c_uint64)]),
     "ssdr_strerror": (C.c_char_p, [C.c_int]),
     "ssdr_last_hip_error": (C.c_char_p, []),
     "ssdr_version": (C.c_char_p, []),
@@ -340,7 +341,8 @@ _NEWER_THAN_AB_LIBS = ("ssdr_feed_collect_listen", "ssdr_set_subrx", "ssdr_get_s
                        "ssdr_wb_rx_stage_results", "ssdr_get_wb_rx_stage_state", "ssdr_rx_tail_stats", "ssdr_set_subrx_noise_blanker",
                        "ssdr_get_subrx_noise_blanker", "ssdr_subrx_nb_mask", "ssdr_set_wb_rx_noise_blanker", "ssdr_get_wb_rx_noise_blanker",
                        "ssdr_wb_rx_nb_mask", "ssdr_set_rx_iq", "ssdr_get_rx_iq", "ssdr_subrx_audio_iq", "ssdr_wb_rx_audio_iq",
-                       "ssdr_set_feed_subrx", "ssdr_get_feed_subrx", "ssdr_feed_subrx_play", "ssdr_feed_collect_subrx")      # entry points a library named by SSDR_LIB_PATH (A/B builds only) may predate
+                       "ssdr_set_feed_subrx", "ssdr_get_feed_subrx", "ssdr_feed_subrx_play", "ssdr_feed_collect_subrx",
+                       "ssdr_selftest_math")      # entry points a library named by SSDR_LIB_PATH (A/B builds only) may predate
 
 
 def _load():

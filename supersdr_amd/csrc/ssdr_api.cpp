@@ -4210,4 +4210,17 @@ int ssdr_selftest_sqrt(ssdr_ctx *c, uint64_t *mismatches) SSDR_GUARD
     return SSDR_OK;
 } SSDR_UNGUARD
 
+int ssdr_selftest_math(ssdr_ctx *c, int which, uint64_t *mismatches) SSDR_GUARD
+{
+    if (!c || !mismatches || which < 0 || which > 1) return SSDR_EINVAL;
+    HIP_TRY(hipSetDevice(c->device));
+    HIP_TRY(hipMemsetAsync(c->d_scratch, 0, 8, c->stream));
+    HIP_TRY(ssdr_launch_math_selftest(which, c->d_scratch, c->stream));
+    unsigned long long v = 0;
+    HIP_TRY(hipMemcpyAsync(&v, c->d_scratch, 8, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    *mismatches = v;
+    return SSDR_OK;
+} SSDR_UNGUARD
+
 } // extern "C"

@@ -522,6 +522,51 @@ __global__ void ssdr_sqrt_selftest_kernel(unsigned long long *mismatch)
         bad += (__float_as_uint(ssdr_sqrt_rn_int(p)) != __float_as_uint(sqrtf(p)));
     }
     if (blockIdx.x == 0 && threadIdx.x == 0) bad += (__float_as_uint(ssdr_sqrt_rn_int(0.0f)) != 0u);
+    // the fused kernel's eight roots at a time (output modifiers under a flushing, non-IEEE MODE): the same floats, eight
+    // consecutive ones per call (0x50000000 - 0x3F800000 is a multiple of 8), then zero in every one of the eight places;
+    // behind the block MODE must be the kernel's own again: a subnormal product survives
+    for (uint64_t u = 0x3F800000ull + 8ull * ((uint64_t)blockIdx.x * blockDim.x + threadIdx.x); u < 0x50000000ull; u += 8ull * stride) {
+        float p[8], r[8];
+#pragma unroll
+        for (int j = 0; j < 8; j++) p[j] = __uint_as_float((uint32_t)u + (uint32_t)j);
+        ssdr_sqrt_rn_int8(p, r);
+#pragma unroll
+        for (int j = 0; j < 8; j++) bad += (__float_as_uint(r[j]) != __float_as_uint(sqrtf(p[j])));
+    }
+    if (blockIdx.x == 0 && threadIdx.x < 8) {
+        float p[8], r[8];
+#pragma unroll
+        for (int j = 0; j < 8; j++) p[j] = (j == (int)threadIdx.x) ? 0.0f : 1.0f + (float)j;
+        ssdr_sqrt_rn_int8(p, r);
+#pragma unroll
+        for (int j = 0; j < 8; j++) bad += (__float_as_uint(r[j]) != __float_as_uint(sqrtf(p[j])));
+        uint32_t tb = 0x00800000u + 2u * threadIdx.x;
+        asm("" : "+v"(tb) : "v"(r[0]));                                              // orders the product behind the block
+        bad += (__float_as_uint(__uint_as_float(tb) * 0.5f) != (tb >> 1));           // exact, subnormal
+    }
+    if (bad) atomicAdd(mismatch, bad);
+}
+
+// exhaustive check of ssdr_log2p (which = 0: every positive normal float) and ssdr_exp2p (which = 1: every float of
+// [-130, 130], both signs of zero and the denormals included) against the forms they replaced, bit for bit
+template <int WHICH>
+__global__ void ssdr_math_selftest_kernel(unsigned long long *mismatch)
+{
+    unsigned long long bad = 0;
+    const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
+    const uint64_t first = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (WHICH == 0) {
+        for (uint64_t u = 0x00800000ull + first; u < 0x7F800000ull; u += stride) {
+            const float x = __uint_as_float((uint32_t)u);
+            bad += (__float_as_uint(ssdr_log2p(x)) != __float_as_uint(ssdr_log2p_ref(x)));
+        }
+    } else {
+        for (uint64_t u = first; u <= 0x43020000ull; u += stride) {          // 0x43020000 = 130.0f
+            const float y = __uint_as_float((uint32_t)u), yn = __uint_as_float((uint32_t)u | 0x80000000u);
+            bad += (__float_as_uint(ssdr_exp2p(y)) != __float_as_uint(ssdr_exp2p_ref(y)));
+            bad += (__float_as_uint(ssdr_exp2p(yn)) != __float_as_uint(ssdr_exp2p_ref(yn)));
+        }
+    }
     if (bad) atomicAdd(mismatch, bad);
 }
 
@@ -545,6 +590,14 @@ hipError_t ssdr_launch_sqrt_values(const float *in, float *out_scaled, float *ou
 hipError_t ssdr_launch_sqrt_selftest(unsigned long long *mismatch, hipStream_t stream)
 {
     hipLaunchKernelGGL(ssdr_sqrt_selftest_kernel, dim3(2048), dim3(256), 0, stream, mismatch);
+    return hipGetLastError();
+}
+
+hipError_t ssdr_launch_math_selftest(int which, unsigned long long *mismatch, hipStream_t stream)
+{
+    if (which == 0) hipLaunchKernelGGL(ssdr_math_selftest_kernel<0>, dim3(2048), dim3(256), 0, stream, mismatch);
+    else if (which == 1) hipLaunchKernelGGL(ssdr_math_selftest_kernel<1>, dim3(2048), dim3(256), 0, stream, mismatch);
+    else return hipErrorInvalidValue;
     return hipGetLastError();
 }
 

@@ -512,12 +512,11 @@ SSDR_DEV void demod_am_tab(const float (&p)[8], float &dc, float (&aud)[8], cons
 {
     constexpr float DC_APOW[8] = SSDR_DC_APOW_INIT;
     float env[8], loc[8];
-    env[0] = ssdr_sqrt_rn_int(p[0]);
+    ssdr_sqrt_rn_int8(p, env);
     float s = SSDR_DC_AL * env[0];
     loc[0] = s;
 #pragma unroll
     for (int j = 1; j < 8; j++) {
-        env[j] = ssdr_sqrt_rn_int(p[j]);
         s = fmaf(SSDR_DC_A, s, SSDR_DC_AL * env[j]);
         loc[j] = s;
     }

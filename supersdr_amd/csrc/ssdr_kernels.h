@@ -350,6 +350,7 @@ hipError_t ssdr_launch_audio_sub_sam(const SsdrSubArgs &a, hipStream_t stream); 
 hipError_t ssdr_launch_audio_sub_nb(const SsdrSubNbArgs &a, uint32_t decim, hipStream_t stream);   // every row, SSDR_MODE_SAM rows included: one launch
 hipError_t ssdr_launch_synth(const SsdrSynthArgs &a, hipStream_t stream);
 hipError_t ssdr_launch_sqrt_selftest(unsigned long long *mismatch, hipStream_t stream);
+hipError_t ssdr_launch_math_selftest(int which, unsigned long long *mismatch, hipStream_t stream);   // 0: ssdr_log2p, 1: ssdr_exp2p
 hipError_t ssdr_launch_sqrt_values(const float *in, float *out_scaled, float *out_int, uint32_t n, hipStream_t stream);
 hipError_t ssdr_launch_quant_selftest(const float *thr, const uint32_t *lut, unsigned long long *mismatch, hipStream_t stream);
 

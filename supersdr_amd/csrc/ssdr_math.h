@@ -68,7 +68,30 @@ SSDR_DEV float ssdr_rcp_1to2p42(float d)
 }
 
 // log2(x) for normal x > 0: exponent split + atanh series in s = (m-1)/(m+1).
+// The split puts m in (0.7071, 1.4142] with integers alone: T = 0x3FB504F3 is the float 1.41421356f, and adding
+// 0x00800000 - (T + 1 - 0x3F800000) = 0x004AFB0C to the bits carries out of the mantissa field exactly for the mantissas
+// above T's, which are the ones that halve and count one exponent up.  The bias is folded into the same constant
+// (- 0x3F800000), so an arithmetic shift leaves e; the mantissa field that stays behind is off by the constant's low 23 bits in
+// either case, and 0x3F800000 - 0x004AFB0C = 0x3F3504F4 puts back both that and the exponent field of [0.5, 2).  Four integer
+// instructions for the seven of ssdr_log2p_ref below (same m, same e for every positive normal x: ssdr_selftest_math).
 SSDR_DEV float ssdr_log2p(float x)
+{
+    const float L1 = 0.33333333333f, L2 = 0.2f, L3 = 0.14285714286f, L4 = 0.11111111111f;
+    const uint32_t ix = __float_as_uint(x) + 0xC0CAFB0Cu;
+    const int32_t e = (int32_t)ix >> 23;
+    const float m = __uint_as_float((ix & 0x007FFFFFu) + 0x3F3504F4u);
+    float s = (m - 1.0f) * ssdr_rcp_1to2p42(m + 1.0f);      // m + 1 in [1.707, 2.414]
+    float z = s * s;
+    float t = fmaf(z, L4, L3);
+    t = fmaf(z, t, L2);
+    t = fmaf(z, t, L1);
+    t = z * t;
+    float sk = s * SSDR_K2_LN2;
+    return (float)e + fmaf(sk, t, sk);
+}
+
+// The form ssdr_log2p had before (compare-and-select range reduction), kept for ssdr_selftest_math only.
+SSDR_DEV float ssdr_log2p_ref(float x)
 {
     const float L1 = 0.33333333333f, L2 = 0.2f, L3 = 0.14285714286f, L4 = 0.11111111111f;
     uint32_t I = __float_as_uint(x);
@@ -86,7 +109,32 @@ SSDR_DEV float ssdr_log2p(float x)
 }
 
 // 2^y, |y| <= 126
+// n = rint(y) comes from the add of 1.5 * 2^23: in [2^23, 2^24) a float's ulp is 1, so the sum is y rounded to nearest-even
+// (1.5 * 2^23 is even, ties fall as rintf's do) and its bits are 0x4B400000 + n.  Subtracting the constant again is exact and
+// gives n as a float; shifted left by 23 the constant's own bits leave the word, so the sum's bits serve as n for the
+// exponent field as they are and the conversion to integer is not needed.  (y = -0 gives f = -0 where rintf gave +0; a zero of
+// either sign leaves every fmaf below at its addend.)  Same result as ssdr_exp2p_ref for every float: ssdr_selftest_math.
 SSDR_DEV float ssdr_exp2p(float y)
+{
+    const float E1 = 0.69314718056f, E2 = 0.24022650696f, E3 = 0.055504108665f,
+                E4 = 0.0096181291076f, E5 = 0.0013333558146f, E6 = 0.00015403530393f,
+                E7 = 0.000015252733805f;
+    y = __builtin_amdgcn_fmed3f(y, -126.0f, 126.0f);       // clamp in one instruction (same value as min(max()))
+    const float t = y + 12582912.0f;
+    const float n = t - 12582912.0f;
+    float f = y - n;
+    float r = fmaf(E7, f, E6);
+    r = fmaf(r, f, E5);
+    r = fmaf(r, f, E4);
+    r = fmaf(r, f, E3);
+    r = fmaf(r, f, E2);
+    r = fmaf(r, f, E1);
+    r = fmaf(r, f, 1.0f);
+    return __uint_as_float(__float_as_uint(r) + (__float_as_uint(t) << 23));
+}
+
+// The form ssdr_exp2p had before (v_rndne_f32, v_cvt_i32_f32), kept for ssdr_selftest_math only.
+SSDR_DEV float ssdr_exp2p_ref(float y)
 {
     const float E1 = 0.69314718056f, E2 = 0.24022650696f, E3 = 0.055504108665f,
                 E4 = 0.0096181291076f, E5 = 0.0013333558146f, E6 = 0.00015403530393f,
@@ -165,4 +213,55 @@ SSDR_DEV float ssdr_sqrt_rn_int(float p)
     asm("v_rsq_f32_e64 %0, %1 clamp" : "=v"(y) : "v"(p));
     const float s = p * y, h = 0.5f * y;
     return fmaf(fmaf(-s, s, p), h, s);
+}
+
+// Eight of those roots in four instructions each: the halving rides on the output modifiers, h = rsq(p) / 2 (div:2) and
+// s = (p h) 2 (mul:2), both exact scalings of what the five-instruction form rounds, so r and s' are the same values.  The hardware
+// applies output modifiers only while the wave's MODE has IEEE clear and fp32 denormals flushed, so the block clears both in front
+// (one s_setreg_imm32_b32 over MODE[9:4]: fp32 denormals 0, fp64/fp16 denormals 3, DX10_CLAMP 1, IEEE 0) and puts the kernels' own
+// setting back behind (3, 3, 1, 1: what hipcc gives every kernel of this library, .amdhsa_float_denorm_mode_32 3 / .amdhsa_ieee_mode 1).
+// Flushing changes nothing inside: for p == 0 or 1 <= p < 2^33 no operand or result of the four operations is subnormal (h >= 2^-17.5,
+// |r| is 0 or >= 2^-46, a unit of s^2).  p == 0: rsq = +inf, halved +inf, clamped to 1.0; s = 0, r = 0, result +0.
+// One asm statement, so that nothing else can be scheduled between the two mode writes; the roots are laid out by hand, each
+// v_rsq_f32 eight instructions ahead of its first use.  Checked like the form above by ssdr_selftest_sqrt.
+SSDR_DEV void ssdr_sqrt_rn_int8(const float (&p)[8], float (&env)[8])
+{
+    float h0, h1, h2, h3, h4, h5, h6, h7, ra, rb;
+    asm("s_setreg_imm32_b32 hwreg(HW_REG_MODE, 4, 6), 0x1c\n\t"
+        "v_rsq_f32_e64 %8, %18 clamp div:2\n\t"
+        "v_rsq_f32_e64 %9, %19 clamp div:2\n\t"
+        "v_rsq_f32_e64 %10, %20 clamp div:2\n\t"
+        "v_rsq_f32_e64 %11, %21 clamp div:2\n\t"
+        "v_rsq_f32_e64 %12, %22 clamp div:2\n\t"
+        "v_rsq_f32_e64 %13, %23 clamp div:2\n\t"
+        "v_rsq_f32_e64 %14, %24 clamp div:2\n\t"
+        "v_rsq_f32_e64 %15, %25 clamp div:2\n\t"
+        "v_mul_f32_e64 %0, %18, %8 mul:2\n\t"
+        "v_mul_f32_e64 %1, %19, %9 mul:2\n\t"
+        "v_mul_f32_e64 %2, %20, %10 mul:2\n\t"
+        "v_mul_f32_e64 %3, %21, %11 mul:2\n\t"
+        "v_mul_f32_e64 %4, %22, %12 mul:2\n\t"
+        "v_mul_f32_e64 %5, %23, %13 mul:2\n\t"
+        "v_mul_f32_e64 %6, %24, %14 mul:2\n\t"
+        "v_mul_f32_e64 %7, %25, %15 mul:2\n\t"
+        "v_fma_f32 %16, -%0, %0, %18\n\t"
+        "v_fma_f32 %17, -%1, %1, %19\n\t"
+        "v_fmac_f32_e32 %0, %16, %8\n\t"
+        "v_fmac_f32_e32 %1, %17, %9\n\t"
+        "v_fma_f32 %16, -%2, %2, %20\n\t"
+        "v_fma_f32 %17, -%3, %3, %21\n\t"
+        "v_fmac_f32_e32 %2, %16, %10\n\t"
+        "v_fmac_f32_e32 %3, %17, %11\n\t"
+        "v_fma_f32 %16, -%4, %4, %22\n\t"
+        "v_fma_f32 %17, -%5, %5, %23\n\t"
+        "v_fmac_f32_e32 %4, %16, %12\n\t"
+        "v_fmac_f32_e32 %5, %17, %13\n\t"
+        "v_fma_f32 %16, -%6, %6, %24\n\t"
+        "v_fma_f32 %17, -%7, %7, %25\n\t"
+        "v_fmac_f32_e32 %6, %16, %14\n\t"
+        "v_fmac_f32_e32 %7, %17, %15\n\t"
+        "s_setreg_imm32_b32 hwreg(HW_REG_MODE, 4, 6), 0x3f"
+        : "=&v"(env[0]), "=&v"(env[1]), "=&v"(env[2]), "=&v"(env[3]), "=&v"(env[4]), "=&v"(env[5]), "=&v"(env[6]), "=&v"(env[7]),
+          "=&v"(h0), "=&v"(h1), "=&v"(h2), "=&v"(h3), "=&v"(h4), "=&v"(h5), "=&v"(h6), "=&v"(h7), "=&v"(ra), "=&v"(rb)
+        : "v"(p[0]), "v"(p[1]), "v"(p[2]), "v"(p[3]), "v"(p[4]), "v"(p[5]), "v"(p[6]), "v"(p[7]));
 }

@@ -1396,6 +1396,12 @@ class SsdrEngine:
         check(lib.ssdr_selftest_sqrt(self._ctx, C.byref(n)), "ssdr_selftest_sqrt")
         return n.value
 
+    def selftest_math(self, which):
+        """mismatches of ssdr_log2p (which = 0) / ssdr_exp2p (which = 1) against the forms they replaced, over their whole domains"""
+        n = C.c_uint64(0)
+        check(lib.ssdr_selftest_math(self._ctx, int(which), C.byref(n)), "ssdr_selftest_math")
+        return n.value
+
     def sqrt_values(self, x):
         """float32[n] -> (ssdr_sqrt_rn(x), ssdr_sqrt_rn_int(x)) as the device computes them"""
         x = np.ascontiguousarray(x, np.float32)
