@@ -615,6 +615,65 @@ int ssdr_get_channelizer_state(ssdr_ctx *ctx, int16_t *hist, uint64_t *out_index
  * HIP-event pair around the stage: the filter bank's kernel and the small one that rewrites the history rows). */
 int ssdr_channelizer_stats(ssdr_ctx *ctx, float *total_ms, uint32_t *launches, int reset);
 
+/* -- wideband noise blanker: an impulse blanker on the wide stream, IN FRONT of the channeliser (a lightning crash or an ignition pulse
+ *    is a few samples long at the wide rate; behind the prototype it is at least P samples long in each of the 1024 rows, and the row
+ *    blankers -- ssdr_set_noise_blanker, ssdr_set_subrx_noise_blanker, ssdr_set_wb_rx_noise_blanker -- see it smeared)
+ *
+ * Per wide stream, in integers (tests/wb_nb_ref.py is the definition, the kernels are held to it bit for bit).  The stream's samples
+ * are cut into blocks of W = SSDR_WB_NB_BLOCK = 4096, aligned to its absolute sample index since the last channeliser reset (a call
+ * always holds whole blocks):
+ *     p[n]    = I*I + Q*Q                               uint32, exact; (-32768, -32768) gives 2^31
+ *     S_b     = sum over ALL samples of block b of floor(p[n] / W)                             uint32 (at most 2^31)
+ *     L_b     = min(S_{b-1}, S_{b-2})                   both 0 after a reset: the first two blocks blank nothing
+ *     trigger = L_b > 0 and p[n] > thresh * L_b         compared in 64 bits
+ *     blank[n]: some trigger m <= n (this block, an earlier one, or an earlier call) has n - m < G
+ *     x'[n]   = (0, 0) where blank[n], else x[n]
+ * G is the gate in WIDE SAMPLES, 1 .. W; thresh 2 .. 1000.  State per stream: S_{-1}, S_{-2} and the samples still to blank at the
+ * start of the next call (left < G).  Two deliberate differences from the channel blanker (ssdr_set_noise_blanker):
+ *   * the level sums the RAW block, impulses included -- the minimum of the two previous blocks keeps a pulse in one of them out of
+ *     the level.  Every S_b is then independent of every mask and a call's blocks are worked on all at once; the channel blanker's sum
+ *     over unblanked samples is a serial chain from frame to frame;
+ *   * the gate is given in samples, not microseconds: the ctx's rate setters describe the channels, not the wide stream, and keep not
+ *     touching it.  ssdr_wb_nb_gate_samples converts.
+ * Rules:
+ *   ssdr_set_wb_noise_blanker: streams first_stream .. first_stream + count - 1; gate_samples = 0 or thresh = 0 turns a stream's
+ *     blanker off.  SSDR_EINVAL: a value outside the ranges, a range of streams beyond the channeliser's, count = 0, a NULL pointer;
+ *     SSDR_ESTATE: no channeliser.  In both cases no stream is changed.  Every stream the call names has its blanker state reset
+ *     (s1 = s2 = left = 0); nothing else of the stream is touched -- not its channeliser history, its output index or its scope rings.
+ *   ssdr_channelizer_reset resets every stream's blanker state and keeps the settings; ssdr_set_channelizer, with any arguments, clears
+ *     settings and state; ssdr_set_decimation / ssdr_set_kiwi_rate / ssdr_set_hop / ssdr_reset_state leave both alone.
+ *   While any stream blanks, ssdr_push_wideband runs the stage on the main stream in front of the filter bank; the filter bank, the
+ *     tuned receivers' DDC and the scopes' stage then read the blanked samples, so the channeliser's history
+ *     (ssdr_get_channelizer_state) and the scopes' rings hold blanked samples.  A stream whose blanker is off passes through bit for
+ *     bit; its mask row and counts are zero.  The blanked samples go to a buffer of the ctx: a caller's device buffer (is_device = 1)
+ *     is never written.
+ *   With no stream blanking nothing is launched and nothing is allocated, and the stages read the caller's pointer or the staging
+ *     buffer exactly as without this section; ssdr_wb_nb_mask and ssdr_wb_nb_counts return SSDR_ESTATE then, as they do when the last
+ *     ssdr_push_wideband ran without the blanker (or there has been none).
+ *   The wide blanker is independent of the row blankers: a row, a sub-receiver or a tuned receiver may blank again behind it.  Feed
+ *     and checkpoint refuse a channeliser as before.  No SSDR_K_* slot: ssdr_wb_nb_stats is the stage's own.
+ * Kernels: ssdr_wb_nb.hip (block sums; mask and apply; counts), DESIGN.md section 26. */
+#define SSDR_WB_NB_BLOCK 4096
+/* gate_samples, thresh: uint32 [count] */
+int ssdr_set_wb_noise_blanker(ssdr_ctx *ctx, uint32_t first_stream, uint32_t count, const uint32_t *gate_samples, const uint32_t *thresh);
+/* the settings of every stream, [*n_streams] each (0, 0: off); gate_samples / thresh may be NULL.  *n_streams = 0 without a
+ * channeliser.  SSDR_EINVAL: ctx or n_streams NULL. */
+int ssdr_get_wb_noise_blanker(ssdr_ctx *ctx, uint32_t *gate_samples, uint32_t *thresh, uint32_t *n_streams);
+/* Host only, no ctx: *g = ceil(gate_us * wide_rate_hz / 1e6) in float64.  SSDR_EINVAL (and *g untouched): g NULL, an argument that
+ * is not finite and positive, a result outside 1 .. SSDR_WB_NB_BLOCK. */
+int ssdr_wb_nb_gate_samples(double gate_us, double wide_rate_hz, uint32_t *g);
+/* The blank mask of the last ssdr_push_wideband: uint8 [n_streams][n_in / 8], n_in the wide samples per stream of that call, bit i of
+ * byte j = sample 8 j + i (a stream whose blanker is off: zero). */
+int ssdr_wb_nb_mask(ssdr_ctx *ctx, uint8_t *mask_out, int out_is_device);
+/* The samples blanked and the triggers in the last ssdr_push_wideband, [n_streams] each; either may be NULL. */
+int ssdr_wb_nb_counts(ssdr_ctx *ctx, uint64_t *blanked, uint64_t *triggers);
+/* The carried state, [n_streams] each (any may be NULL): S_{-1}, S_{-2}, samples still to blank.  All zero before any stream was set.
+ * SSDR_ESTATE without a channeliser. */
+int ssdr_get_wb_nb_state(ssdr_ctx *ctx, uint32_t *s1, uint32_t *s2, uint32_t *left);
+/* The stage's runs since the last reset (one per ssdr_push_wideband while a stream blanks), and with ssdr_set_profiling on their
+ * summed time (one HIP-event pair around the stage's three kernels). */
+int ssdr_wb_nb_stats(ssdr_ctx *ctx, float *total_ms, uint32_t *launches, int reset);
+
 /* -- wideband scopes: zoomable waterfalls of a channeliser's wide stream (the reference's kiwi_waterfall looks at the server's whole
  *    band and zooms into it: SET zoom=%d start=%d / cf=, utils_supersdr.py:741, 815-845; span = band / 2^zoom, kiwi/client.py:277-280)
  *

@@ -99,6 +99,7 @@ class SubRx(C.Structure):
 
 assert C.sizeof(SubRx) == 96
 CHAN_BRANCHES, CHAN_TAPS_PER_BRANCH_MAX = 1024, 16      # SSDR_CHAN_BRANCHES, SSDR_CHAN_TAPS_PER_BRANCH_MAX
+WB_NB_BLOCK = 4096                                      # SSDR_WB_NB_BLOCK: the wideband noise blanker's block, and its longest gate, in wide samples
 WB_SCOPES_MAX, WB_SCOPE_ZOOM_MAX, WB_SCOPE_HIST = 64, 10, 1056 * 1024      # SSDR_WB_SCOPES_MAX, SSDR_WB_SCOPE_ZOOM_MAX, SSDR_WB_SCOPE_HIST
 WB_DET_SAMPLE, WB_DET_AVERAGE, WB_DET_PEAK, WB_DET_MIN = 0, 1, 2, 3          # SSDR_WB_DET_*
 WB_SCOPE_SPAN = 1024 * 1024                                                # SSDR_WB_SCOPE_SPAN
@@ -239,6 +240,13 @@ _SIGS = {
     "ssdr_push_wideband": (C.c_int, [_P, _P, C.c_uint32, C.c_int]),
     "ssdr_get_channelizer_state": (C.c_int, [_P, _P, C.POINTER(C.c_uint64)]),
     "ssdr_channelizer_stats": (C.c_int, [_P, C.POINTER(C.c_float), C.POINTER(C.c_uint32), C.c_int]),
+    "ssdr_set_wb_noise_blanker": (C.c_int, [_P, C.c_uint32, C.c_uint32, _P, _P]),
+    "ssdr_get_wb_noise_blanker": (C.c_int, [_P, _P, _P, C.POINTER(C.c_uint32)]),
+    "ssdr_wb_nb_gate_samples": (C.c_int, [C.c_double, C.c_double, C.POINTER(C.c_uint32)]),
+    "ssdr_wb_nb_mask": (C.c_int, [_P, _P, C.c_int]),
+    "ssdr_wb_nb_counts": (C.c_int, [_P, _P, _P]),
+    "ssdr_get_wb_nb_state": (C.c_int, [_P, _P, _P, _P]),
+    "ssdr_wb_nb_stats": (C.c_int, [_P, C.POINTER(C.c_float), C.POINTER(C.c_uint32), C.c_int]),
     "ssdr_set_wb_scopes": (C.c_int, [_P, C.POINTER(WbScope), C.c_uint32]),
     "ssdr_get_wb_scopes": (C.c_int, [_P, C.POINTER(WbScope), C.POINTER(C.c_uint32)]),
     "ssdr_wb_scope_lines": (C.c_int, [_P, _P, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.c_int]),
@@ -342,7 +350,8 @@ _NEWER_THAN_AB_LIBS = ("ssdr_feed_collect_listen", "ssdr_set_subrx", "ssdr_get_s
                        "ssdr_get_subrx_noise_blanker", "ssdr_subrx_nb_mask", "ssdr_set_wb_rx_noise_blanker", "ssdr_get_wb_rx_noise_blanker",
                        "ssdr_wb_rx_nb_mask", "ssdr_set_rx_iq", "ssdr_get_rx_iq", "ssdr_subrx_audio_iq", "ssdr_wb_rx_audio_iq",
                        "ssdr_set_feed_subrx", "ssdr_get_feed_subrx", "ssdr_feed_subrx_play", "ssdr_feed_collect_subrx",
-                       "ssdr_selftest_math")      # entry points a library named by SSDR_LIB_PATH (A/B builds only) may predate
+                       "ssdr_selftest_math", "ssdr_set_wb_noise_blanker", "ssdr_get_wb_noise_blanker", "ssdr_wb_nb_gate_samples",
+                       "ssdr_wb_nb_mask", "ssdr_wb_nb_counts", "ssdr_get_wb_nb_state", "ssdr_wb_nb_stats")      # entry points a library named by SSDR_LIB_PATH (A/B builds only) may predate
 
 
 def _load():

@@ -4,6 +4,7 @@
 // templates, the small inline helpers of the per-batch path and the declarations of what one unit calls in another).  The units:
 //   ssdr_api_wfview.cpp      the waterfall views
 //   ssdr_api_checkpoint.cpp  the checkpoint
+//   ssdr_api_wbnb.cpp        the wideband noise blanker in front of the channeliser
 //   ssdr_api.cpp             this one, everything else: error plumbing, create / destroy / params / rate / zoom / input, the waterfall and
 //                            audio stages and ssdr_run_chain, the listener stages, the banks of extra receivers, the wideband side, the
 //                            pipelined feed, the post kernels, the selftests
@@ -57,6 +58,7 @@ static void free_owned(ssdr_ctx *c)
         c->sub.d_state[0], c->sub.d_state[1], c->sub.d_hist[0], c->sub.d_hist[1], c->sub.d_phist[0], c->sub.d_phist[1], c->sub.d_phist_alt,
         c->sub.d_consts, c->sub.d_taps, c->sub.d_parent, c->sub.d_play, c->sub.d_play_out,                            // ... their bank: state, constants, play_buffer
         c->d_chz_taps, c->d_chz_hist, c->d_chz_in,                                                                    // wideband channeliser
+        c->d_wbnb_cfg, c->d_wbnb_state[0], c->d_wbnb_state[1], c->d_wbnb_out, c->d_wbnb_mask, c->d_wbnb_sums, c->d_wbnb_blk, c->d_wbnb_counts,   // ... its noise blanker
         c->d_ws_taps, c->d_ws_scopes, c->d_ws_slot_stream, c->d_ws_hist, c->d_ws_out, c->d_ws_lines, c->d_ws_acc, c->d_ws_consts,   // wideband scopes
         c->d_wd_win, c->d_wd_part,                                                                                    // ... their detectors' scratch
         c->own.d_wr_rows, c->own.wr.d_pcm, c->own.wr.d_rssi, c->own.wr.d_flags, c->own.wr.d_closed, c->own.wr.d_adpcm, // tuned receivers: the own batch's rows and results,
@@ -3839,6 +3841,7 @@ int ssdr_set_channelizer(ssdr_ctx *c, uint32_t n_streams, uint32_t branches, uin
         HIP_TRY(hipSetDevice(c->device));
         SSDR_TRY(wbrx_clear(c));                                        // the tuned receivers and the scopes go with their streams
         SSDR_TRY(ws_clear(c));
+        SSDR_TRY(wbnb_clear(c));                                        // ... and the wide blanker's settings
         c->chz_streams = 0;
         return SSDR_OK;
     }
@@ -3851,6 +3854,7 @@ int ssdr_set_channelizer(ssdr_ctx *c, uint32_t n_streams, uint32_t branches, uin
     HIP_TRY(hipSetDevice(c->device));
     SSDR_TRY(wbrx_clear(c));                                            // a new channeliser starts without tuned receivers or scopes
     SSDR_TRY(ws_clear(c));
+    SSDR_TRY(wbnb_clear(c));                                            // ... and with no stream blanking
     std::vector<float> h(taps, taps + n_taps);
     constexpr size_t kMaxTaps = (size_t)SSDR_CHAN_TAPS_PER_BRANCH_MAX * SSDR_CHAN_BRANCHES;
     if (!c->d_chz_taps) HIP_TRY(hipMalloc(&c->d_chz_taps, kMaxTaps * sizeof(float)));
@@ -3887,6 +3891,7 @@ int ssdr_channelizer_reset(ssdr_ctx *c) SSDR_GUARD
     if (c->d_ws_hist) HIP_TRY(hipMemsetAsync(c->d_ws_hist, 0, c->h_ws_streams.size() * SSDR_WB_SCOPE_HIST * 4, c->stream));   // the scopes' list stays
     c->ws_win_valid = false;
     c->chz_out_index = 0;
+    SSDR_TRY(wbnb_reset(c));                                            // the wide blanker keeps its settings and starts over
     return bank_restart(c, c->wr, every_row);                           // the tuned receivers' list stays too; their audio starts over
 } SSDR_UNGUARD
 
@@ -3917,6 +3922,7 @@ int ssdr_push_wideband(ssdr_ctx *c, const int16_t *iq, uint32_t n_frames, int is
     SsdrChanArgs a;
     a.in = is_device ? reinterpret_cast<const uint32_t *>(iq) : c->d_chz_in;
     a.in_stride = n_in;
+    SSDR_TRY(wbnb_stage(c, a.in, a.in_stride, (uint32_t)n_in));         // while a stream blanks: a.in becomes the blanked copy (same stride)
     a.n_streams = c->chz_streams; a.n_in = (uint32_t)n_in; a.n_out = (uint32_t)n_out;
     a.oversample = c->chz_over; a.n_taps = c->chz_p * SSDR_CHAN_BRANCHES;
     a.taps = c->d_chz_taps;

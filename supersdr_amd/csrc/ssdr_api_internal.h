@@ -103,7 +103,8 @@ constexpr int kTimedWbRxDdc = SSDR_K_COUNT + 5;         // the tuned receivers' 
 constexpr int kTimedWbRxAudio = SSDR_K_COUNT + 6;
 constexpr int kTimedSubTail = SSDR_K_COUNT + 7;         // the banks' fused squelch / de-emphasis / encoder launch (ssdr_rx_tail_stats)
 constexpr int kTimedWbRxTail = SSDR_K_COUNT + 8;
-constexpr int kTimedCount = SSDR_K_COUNT + 9;
+constexpr int kTimedWbNb = SSDR_K_COUNT + 9;            // the wideband noise blanker (ssdr_wb_nb_stats)
+constexpr int kTimedCount = SSDR_K_COUNT + 10;
 
 // A bank of extra receivers: audio chains that are no channels, rows in list order, run by the sub-receivers' kernels behind the
 // channels' audio stage.  The ctx holds two -- the sub-receivers (ssdr_set_subrx: each reads a channel's row of the input) and the
@@ -393,6 +394,20 @@ struct ssdr_ctx {
     uint32_t *d_chz_in = nullptr;                       // a host caller's wideband samples of the call
     size_t chz_in_dwords = 0;
     uint64_t chz_out_index = 0;                         // output instants since the streams last started from silence
+    // wideband noise blanker (ssdr_set_wb_noise_blanker; ssdr_api_wbnb.cpp): host settings at the first call, device memory at the first
+    // nonzero setting; while no stream blanks nothing is launched and ssdr_push_wideband hands on the pointer it handed on before
+    std::vector<uint32_t> h_wbnb_gate, h_wbnb_thresh;   // [streams] as set, 0: off (empty: never set -- everybody off)
+    uint32_t wbnb_on = 0;                               // streams whose blanker is on
+    SsdrWbNbStream *d_wbnb_cfg = nullptr;               // [n_ch / 1024]
+    SsdrWbNbState *d_wbnb_state[2] = {nullptr, nullptr};// [n_ch / 1024] a launch reads set wbnb_set and writes the other; swapped behind it
+    int wbnb_set = 0;
+    uint32_t *d_wbnb_out = nullptr;                     // [streams][n_in] the blanked copy of the call's wide samples
+    size_t wbnb_out_dwords = 0;
+    uint8_t *d_wbnb_mask = nullptr;                     // [streams][n_in / 8]; the capacity follows d_wbnb_out's
+    uint32_t *d_wbnb_sums = nullptr, *d_wbnb_blk = nullptr;     // [streams][n_in / 4096] the blocks' sums and counts; likewise
+    uint64_t *d_wbnb_counts = nullptr;                  // [n_ch / 1024][2]
+    bool wbnb_run_valid = false;                        // the last ssdr_push_wideband ran the blanker
+    uint32_t wbnb_run_n_in = 0;                         // wide samples per stream of that run
     // wideband scopes (ssdr_set_wb_scopes): device memory at the first scope; with none set nothing is launched
     std::vector<ssdr_wb_scope> h_ws;                    // the list as set
     std::vector<uint32_t> h_ws_det;                     // the detectors, parallel to it (ssdr_set_wb_scope_detectors; a new list: all SAMPLE)
@@ -429,6 +444,11 @@ int zoom_taps(uint32_t Z, float *out);
 SsdrWfArgs wf_rows_args(const ssdr_ctx *c, const uint32_t *rows, uint64_t stride, uint32_t n_rows, uint32_t n_lines, const uint32_t *tail,
                         int16_t *out, int16_t *acc, size_t acc_rows, const ssdr_chan_consts *consts);
 uint32_t zoom_dphi(double offset_hz, double fs_in);
+
+// ssdr_api_wbnb.cpp
+int wbnb_stage(ssdr_ctx *c, const uint32_t *&in, uint64_t in_stride, uint32_t n_in);
+int wbnb_reset(ssdr_ctx *c);
+int wbnb_clear(ssdr_ctx *c);
 
 // ssdr_api_wfview.cpp
 int wfview_restart(ssdr_ctx *c, uint32_t first, uint32_t count);

@@ -321,6 +321,25 @@ hipError_t ssdr_launch_wb_scope(const SsdrWbScopeArgs &a, hipStream_t stream);
 hipError_t ssdr_launch_wb_scope_win(const SsdrWbDetArgs &d, hipStream_t stream);
 hipError_t ssdr_launch_wb_scope_det(const SsdrWbDetArgs &d, hipStream_t stream);      // the chains, then the tree and the quantiser
 hipError_t ssdr_launch_wb_scope_hist(const SsdrWbScopeArgs &a, hipStream_t stream);
+// wideband noise blanker (ssdr_wb_nb.hip, ssdr_set_wb_noise_blanker): a blanked COPY of the call's wide samples, in front of everything
+// that reads them.  A stream's settings (both 0: off) and its carried state: the raw block sums S_{-1}, S_{-2} and the samples still to
+// blank at the start of the next call.  The kernels read one set of state words and write another: the host swaps them after a launch.
+struct SsdrWbNbStream { uint32_t gate, thresh; };               // gate in wide samples.  8 B
+struct SsdrWbNbState { uint32_t s1, s2, left, pad; };           // 16 B
+struct SsdrWbNbArgs {
+    const uint32_t *in;                      // [n_streams][in_stride] the call's wideband dwords, 16-byte aligned rows: only read
+    uint64_t in_stride;
+    uint32_t n_streams, n_blocks;            // blocks of SSDR_WB_NB_BLOCK samples per stream in this call (n_in = n_blocks * 4096)
+    const SsdrWbNbStream *cfg;               // [n_streams]
+    const SsdrWbNbState *state_in;           // [n_streams]
+    SsdrWbNbState *state_out;                // [n_streams] another array: block 0 reads state_in in the launch whose last block writes this
+    uint32_t *sums;                          // [n_streams][n_blocks] S_b of the call's blocks (first launch out, second in)
+    uint32_t *out;                           // [n_streams][n_blocks * 4096] the blanked samples; never the same memory as `in`
+    uint8_t *mask;                           // [n_streams][n_blocks * 512] bit i of byte j: sample 8 j + i was zeroed
+    uint32_t *blk;                           // [n_streams][n_blocks] blanked samples | triggers << 16 of every block
+    uint64_t *counts;                        // [n_streams][2] their sums over the call: blanked, triggers (third launch)
+};
+hipError_t ssdr_launch_wb_nb(const SsdrWbNbArgs &a, hipStream_t stream);          // sums, then mask and apply, then the counts
 struct SsdrFusedArgs { SsdrWfArgs wf; SsdrAudioArgs au; uint32_t *ticket; uint32_t ticket_base; };
 // ticket: ssdr_chain_ws_kernel's pair counter; it stands at ticket_base at launch and is never reset: every trio draws its pairs and one ticket
 // beyond the last pair, so a launch of `grid` workgroups leaves it at ticket_base + pairs + grid * SSDR_WS_AUDIO_WAVES / 2 (ssdr_api.cpp)

@@ -740,6 +740,55 @@ class SsdrEngine:
         """-> (total_ms, runs) of the channeliser since the last reset (the time only with set_profiling on)"""
         return self._stage_stats("ssdr_channelizer_stats", reset)
 
+    # ---- wideband noise blanker: an impulse blanker on the wide streams, in front of the channeliser
+    def set_wb_noise_blanker(self, first_stream, gate_samples, thresh):
+        """The wide blanker of streams first_stream, first_stream + 1, ...: gate_samples 1..4096 (wide samples: Channelizer.nb_gate_samples
+        converts from microseconds), thresh 2..1000, either 0 = off (array-likes, one entry per stream; a scalar with the other's length).
+        Resets those streams' blanker state and nothing else of them.  A value that is not a uint32 raises ValueError before the library
+        is called; what the library refuses raises SsdrError (SSDR_EINVAL: outside the ranges, streams the channeliser does not have;
+        SSDR_ESTATE: no channeliser).  Either way no stream is changed."""
+        n = max(np.size(gate_samples), np.size(thresh))
+        g, t = _nb_array(gate_samples, n, "gate"), _nb_array(thresh, n, "threshold")
+        check(lib.ssdr_set_wb_noise_blanker(self._ctx, int(first_stream), n, g.ctypes.data, t.ctypes.data), "ssdr_set_wb_noise_blanker")
+
+    def _wb_streams(self):
+        n = C.c_uint32()
+        check(lib.ssdr_get_wb_noise_blanker(self._ctx, None, None, C.byref(n)), "ssdr_get_wb_noise_blanker")
+        return n.value
+
+    def get_wb_noise_blanker(self):
+        """-> (gate_samples uint32 [n_streams], thresh uint32 [n_streams]) as set, 0 = off; empty without a channeliser"""
+        n = C.c_uint32(self._wb_streams())
+        g, t = np.zeros(max(n.value, 1), np.uint32), np.zeros(max(n.value, 1), np.uint32)
+        check(lib.ssdr_get_wb_noise_blanker(self._ctx, g.ctypes.data, t.ctypes.data, C.byref(n)), "ssdr_get_wb_noise_blanker")
+        return g[:n.value], t[:n.value]
+
+    def wb_nb_mask(self):
+        """-> uint8 [n_streams, n_in / 8]: the wide samples the blanker zeroed in the last push_wideband, bit i of byte j = sample 8 j + i
+        (rows of streams whose blanker is off: 0).  SsdrError (SSDR_ESTATE) when that push ran without the blanker."""
+        n_streams, per_frame = self._wideband_per_frame()
+        out = np.empty((n_streams, self.in_frames * per_frame // 8), np.uint8)
+        check(lib.ssdr_wb_nb_mask(self._ctx, out.ctypes.data, 0), "ssdr_wb_nb_mask")
+        return out
+
+    def wb_nb_counts(self):
+        """-> (blanked uint64 [n_streams], triggers uint64 [n_streams]) of the last push_wideband; SsdrError (SSDR_ESTATE) as wb_nb_mask"""
+        n = max(self._wb_streams(), 1)
+        b, t = np.zeros(n, np.uint64), np.zeros(n, np.uint64)
+        check(lib.ssdr_wb_nb_counts(self._ctx, b.ctypes.data, t.ctypes.data), "ssdr_wb_nb_counts")
+        return b[:self._wb_streams()], t[:self._wb_streams()]
+
+    def wb_nb_state(self):
+        """-> uint32 [n_streams, 3]: the carried S_{-1}, S_{-2} and the samples still to blank at the start of the next push"""
+        n = self._wb_streams()
+        s = np.zeros((3, max(n, 1)), np.uint32)
+        check(lib.ssdr_get_wb_nb_state(self._ctx, s[0].ctypes.data, s[1].ctypes.data, s[2].ctypes.data), "ssdr_get_wb_nb_state")
+        return np.ascontiguousarray(s[:, :n].T)
+
+    def wb_nb_stats(self, reset=False):
+        """-> (total_ms, runs) of the wide blanker since the last reset (the time only with set_profiling on)"""
+        return self._stage_stats("ssdr_wb_nb_stats", reset)
+
     # ---- wideband scopes: zoomable waterfalls of the channeliser's wide streams
     def set_wb_scopes(self, scopes):
         """The wideband scopes, replacing the whole list: a sequence of (stream, zoom, offset_hz) in any order, several per stream

@@ -137,6 +137,17 @@ class Channelizer:
         """the inverse of row_rate: the wide stream's sample rate for rows that run at `row_rate` (D * kiwi_rate)"""
         return float(row_rate) * self.BRANCHES / self.oversample
 
+    NB_BLOCK = 4096                                 # SSDR_WB_NB_BLOCK: the wide blanker's block, and its longest gate, in wide samples
+
+    def nb_gate_samples(self, gate_us, rate):
+        """the wide blanker's gate (ssdr_set_wb_noise_blanker) in wide samples for `gate_us` microseconds of a wide stream sampled at
+        `rate`: ceil(gate_us * rate / 1e6) in float64, the arithmetic of ssdr_wb_nb_gate_samples.  ValueError outside 1 .. 4096."""
+        gate_us, rate = float(gate_us), float(rate)
+        x = gate_us * rate / 1e6
+        if not (np.isfinite(x) and gate_us > 0.0 and rate > 0.0 and 1.0 <= np.ceil(x) <= self.NB_BLOCK):
+            raise ValueError("a gate of %r us at %r Hz is outside 1..%d wide samples" % (gate_us, rate, self.NB_BLOCK))
+        return int(np.ceil(x))
+
     def scope_span(self, zoom, rate):
         """Hz a scope of `zoom` shows of a wide stream sampled at `rate`"""
         if not 0 <= int(zoom) <= self.SCOPE_ZOOM_MAX:

@@ -401,6 +401,8 @@ class IQHub:
         self._views = {}                             # channel -> (zoom, offset_hz): the waterfall views (set_wf_view)
         self._wf_listeners = {}                      # channel -> W/F streams open on it (the last one to close takes the view with it)
         self.channelizer = None                      # the wideband channeliser in front of the hub (set_channelizer)
+        self._wb_nb = {}                             # stream -> (gate_us, thresh, gate in wide samples): the wide blankers that are on (set_wideband_blanker)
+        self._wb_nb_counts = None                    # (blanked [streams], triggers [streams]) of the last feed_wideband that blanked
         # the extra listeners, a table per family (the engine's rows in id order), and the dicts they publish:
         #   sub-receivers    sid -> (channel, ChanParams);                 sub_queue[sid]: Frame,   sub_clients[sid]: the kiwi_sound on it
         #   tuned receivers  tid -> (stream, offset_hz, ChanParams);       tuned_queue[tid]: Frame, tuned_clients[tid]: the kiwi_sound on it
@@ -1278,6 +1280,49 @@ class IQHub:
             self.channelizer = channelizer
             self._scopes.clear()                     # the library emptied its lists: every scope is closed, and every tuned receiver
             self._tuned.clear()
+            self._wb_nb = {}                         # ... and cleared the wide blankers' settings
+            self._wb_nb_counts = None
+
+    def set_wideband_blanker(self, stream, gate_us, thresh):
+        """The impulse blanker of wide stream `stream`, IN FRONT of the channeliser: a gate of gate_us microseconds (at most 4096 wide
+        samples) behind every sample whose power exceeds thresh (2..1000) times the stream's level; either 0 turns it off.  An
+        operator's setting of the hub -- it changes what all 1024 receivers, the scopes and the tuned receivers of that stream hear and
+        see -- and no listener's "SET nb=" reaches it (those go to the row blankers as before).  Resets the stream's blanker state and
+        nothing else.  ValueError, before the engine is touched, on a pipelined or wire hub, without a channeliser, for an engine
+        without the setter, a stream that does not exist and a value out of range; then nothing changes."""
+        self._require_wide_stream("wideband blanker", "set_wb_noise_blanker")
+        stream = int(stream)
+        n_streams = self.n_ch // self.channelizer.BRANCHES
+        if not 0 <= stream < n_streams:
+            raise ValueError("wide stream %d of %d" % (stream, n_streams))
+        on = bool(gate_us) and bool(thresh)
+        g = t = 0
+        if on:
+            g, t = self.channelizer.nb_gate_samples(gate_us, self.wide_rate()), int(thresh)
+            if t != thresh or not 2 <= t <= 1000:
+                raise ValueError("wideband blanker threshold %r outside 2..1000" % (thresh,))
+        with self._lock:
+            try:
+                self.engine.set_wb_noise_blanker(stream, g, t)
+            except L.SsdrError as e:
+                raise ValueError("wideband blanker refused: %s" % e)
+            if on:
+                self._wb_nb[stream] = (float(gate_us), t, g)
+            else:
+                self._wb_nb.pop(stream, None)
+            self._wb_nb_counts = None
+
+    def wideband_blanker(self, stream):
+        """-> (gate_us, thresh) of wide stream `stream` as set; (0.0, 0) while it is off"""
+        with self._lock:
+            gate_us, thresh, _ = self._wb_nb.get(int(stream), (0.0, 0, 0))
+        return gate_us, thresh
+
+    def wideband_blank_counts(self):
+        """-> (blanked, triggers): uint64 [n_streams] each, the wide samples zeroed and the triggers in the last feed_wideband (for an
+        "NB active" light); None while no stream blanks or before the first feed_wideband with the settings as they are"""
+        with self._lock:
+            return self._wb_nb_counts
 
     def feed_wideband(self, block):
         """one superframe of every wide stream: int16 [n_streams, superframe samples * 1024 / oversample, 2] -> one GPU run, as if the
@@ -1300,6 +1345,7 @@ class IQHub:
         eng = self.engine
         if wideband:
             wire_rssi = eng.push_wideband(batch)        # (None: the rows carry no SND headers)
+            self._wb_nb_counts = eng.wb_nb_counts() if self._wb_nb else None
         else:
             wire_rssi = eng.push_iq_wire(batch) if self.wire else eng.push_iq(batch)
         extra = {}                                    # the extra listeners' results: a family without a listener leaves its fields None
