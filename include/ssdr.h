@@ -674,6 +674,66 @@ int ssdr_get_wb_nb_state(ssdr_ctx *ctx, uint32_t *s1, uint32_t *s2, uint32_t *le
  * summed time (one HIP-event pair around the stage's three kernels). */
 int ssdr_wb_nb_stats(ssdr_ctx *ctx, float *total_ms, uint32_t *launches, int reset);
 
+/* -- real-sample front end: ADC samples in.  ssdr_push_wideband takes the wide stream as complex int16 at rate F; an HF receiver's ADC
+ *    (the KiwiSDR's own, every direct-sampling receiver) delivers REAL int16 samples at 2F, and the complex stream exists only behind
+ *    the first step of a DDC: a mix by a quarter of the sample rate, a half-band low-pass, a decimation by 2.  That step, on the GPU,
+ *    in front of the wide blanker and everything behind it.  A real stream at 2F has exactly the bytes of a complex stream at F.
+ *
+ * Per wide stream, in integers (tests/wb_real_ref.py is the definition, the kernel is held to it bit for bit).  r[m] is the real
+ * sample, m its absolute index since the last channeliser reset, r[m] = 0 for m < 0.  The taps: N = SSDR_WB_REAL_TAPS = 103, centre
+ * c = 51,
+ *     q[t] = rint(16384 * sinc((t - c) / 2) * kaiser(103, beta = 8)[t])
+ * -- a gain-2 half-band low-pass in Q14: symmetric, q[51] = 16384 exactly, q[51 +- 2k] = 0 for k >= 1; 50 nonzero side taps that sum
+ * to 44014 in magnitude, the largest 10415 (ssdr_wb_real_taps returns the table; tools/gen_wb_real_taps.py writes it).  The zone z of
+ * a stream: 0, the first Nyquist zone, RF 0 .. F, s = +1; 1, the second, RF F .. 2F, which the ADC delivers spectrum-reversed, s = -1.
+ *     a[m] = (-1)^floor(m/2) * r[m]
+ *     I[n] = sat16((sum over even t of q[t] * a[2n - t] + 8192) >> 14)        arithmetic shift (floor)
+ *     Q[n] = sat16(-s * a[2n - 51])                                           the centre tap: an exact delay; -(-32768) gives 32767
+ * sat16 clamps to -32768 .. 32767.  This is y[n] = sum_t q[t] u[2n - t], u[m] = r[m] (-+j)^m, rounded.  44014 * 32768 + 8192 =
+ * 1442258944 < 2^31: a 32-bit accumulator is exact.  A real carrier of amplitude A at RF f becomes a complex carrier of amplitude A
+ * at f - F/2 from the stream's centre in zone 0 (row r of the stream is centred on RF r * F / 1024) and at f - 3F/2 in zone 1 (row r
+ * is centred on F + r * F / 1024: not mirrored).
+ * USABLE BAND.  The image of a component is 74.7 dB down, and the passband flat within +-0.002 dB, for offsets |f - centre| <= 0.45 F
+ * (roughly rows 52 .. 972).  In the outer 0.05 F at either edge the image is NOT suppressed -- 0.04 F from the edge it is 43.9 dB
+ * down, 0.01 F from it less than 8 dB, at the edge itself it is as strong as the component -- as behind any half-band decimator.
+ * A call of n_frames holds 2 * n_in real samples per stream, n_in the complex samples per stream of an ssdr_push_wideband of n_frames
+ * (always a multiple of 512 * 512).  State per stream: its last 102 real samples and the input index.
+ * Rules:
+ *   After ssdr_push_wideband_real everything downstream -- the wide blanker, the rows, the channeliser's state, the scopes' rings and
+ *     lines, the tuned receivers, ssdr_run_* -- behaves exactly as after an ssdr_push_wideband of the definition's converted samples.
+ *     Those go to a buffer of the ctx (ssdr_read_wb_real); a caller's device buffer (is_device = 1: 16-byte aligned) is never written;
+ *     host input is staged where ssdr_push_wideband's is.
+ *   SSDR_EINVAL, and then nothing changes: a NULL pointer, n_frames = 0, a zone above 1, a range of streams beyond the channeliser's,
+ *     count = 0, a misaligned device pointer.  SSDR_ESTATE: no channeliser; ssdr_read_wb_real also unless the last push was a real one.
+ *     A real push that fails later -- SSDR_ENOMEM or SSDR_EHIP from a buffer or a launch behind the conversion -- leaves the front end's
+ *     history and index as they were in front of the call (the stages behind it are where ssdr_push_wideband's failure leaves them);
+ *     the converted buffer has been rewritten by then, and ssdr_read_wb_real returns SSDR_ESTATE until the next real push.
+ *   ssdr_set_wb_real_zone acts from the next call on and resets no state.  ssdr_channelizer_reset zeroes history and index and keeps
+ *     the zones; ssdr_set_channelizer, with any arguments, clears zones and state; ssdr_set_decimation / ssdr_set_kiwi_rate /
+ *     ssdr_set_hop / ssdr_reset_state leave both alone.  A complex ssdr_push_wideband neither reads nor changes this state.  Feed and
+ *     checkpoint refuse a channeliser as before.
+ *   Nothing is allocated before the first ssdr_push_wideband_real and nothing is launched by a complex push.  The converted copy is
+ *     n_streams * n_in * 4 bytes (64 streams x 16 frames at O = 1: 2 GiB), the history 2 x 208 bytes per stream.
+ *   No SSDR_K_* slot: ssdr_wb_real_stats is the stage's own.
+ * Kernel: ssdr_wb_real.hip, DESIGN.md section 27. */
+#define SSDR_WB_REAL_TAPS 103
+/* Host only, no ctx: out int32 [SSDR_WB_REAL_TAPS] = q.  SSDR_EINVAL: out NULL. */
+int ssdr_wb_real_taps(int32_t *out);
+/* zone: uint32 [count], 0 or 1, of streams first_stream .. first_stream + count - 1; every stream starts in zone 0 */
+int ssdr_set_wb_real_zone(ssdr_ctx *ctx, uint32_t first_stream, uint32_t count, const uint32_t *zone);
+/* the zone of every stream, [*n_streams] (zone may be NULL).  *n_streams = 0 without a channeliser.  SSDR_EINVAL: ctx or n_streams NULL. */
+int ssdr_get_wb_real_zone(ssdr_ctx *ctx, uint32_t *zone, uint32_t *n_streams);
+/* The counterpart of ssdr_push_wideband for real samples: x int16 [n_streams][2 * n_in] */
+int ssdr_push_wideband_real(ssdr_ctx *ctx, const int16_t *x, uint32_t n_frames, int is_device);
+/* The converted samples of the last ssdr_push_wideband_real: iq_out int16 [n_streams][n_in][2] */
+int ssdr_read_wb_real(ssdr_ctx *ctx, int16_t *iq_out, int out_is_device);
+/* The carried state: hist int16 [n_streams][102] each stream's last 102 real samples, oldest first (may be NULL); the real samples
+ * taken per stream since the last reset (may be NULL).  All zero before the first real push.  SSDR_ESTATE without a channeliser. */
+int ssdr_get_wb_real_state(ssdr_ctx *ctx, int16_t *hist, uint64_t *in_index);
+/* The stage's runs since the last reset (one per ssdr_push_wideband_real), and with ssdr_set_profiling on their summed time (one
+ * HIP-event pair around the stage's kernel). */
+int ssdr_wb_real_stats(ssdr_ctx *ctx, float *total_ms, uint32_t *launches, int reset);
+
 /* -- wideband scopes: zoomable waterfalls of a channeliser's wide stream (the reference's kiwi_waterfall looks at the server's whole
  *    band and zooms into it: SET zoom=%d start=%d / cf=, utils_supersdr.py:741, 815-845; span = band / 2^zoom, kiwi/client.py:277-280)
  *

@@ -100,6 +100,7 @@ class SubRx(C.Structure):
 assert C.sizeof(SubRx) == 96
 CHAN_BRANCHES, CHAN_TAPS_PER_BRANCH_MAX = 1024, 16      # SSDR_CHAN_BRANCHES, SSDR_CHAN_TAPS_PER_BRANCH_MAX
 WB_NB_BLOCK = 4096                                      # SSDR_WB_NB_BLOCK: the wideband noise blanker's block, and its longest gate, in wide samples
+WB_REAL_TAPS = 103                                      # SSDR_WB_REAL_TAPS: the real-sample front end's half-band low-pass (ssdr_wb_real_taps)
 WB_SCOPES_MAX, WB_SCOPE_ZOOM_MAX, WB_SCOPE_HIST = 64, 10, 1056 * 1024      # SSDR_WB_SCOPES_MAX, SSDR_WB_SCOPE_ZOOM_MAX, SSDR_WB_SCOPE_HIST
 WB_DET_SAMPLE, WB_DET_AVERAGE, WB_DET_PEAK, WB_DET_MIN = 0, 1, 2, 3          # SSDR_WB_DET_*
 WB_SCOPE_SPAN = 1024 * 1024                                                # SSDR_WB_SCOPE_SPAN
@@ -247,6 +248,13 @@ _SIGS = {
     "ssdr_wb_nb_counts": (C.c_int, [_P, _P, _P]),
     "ssdr_get_wb_nb_state": (C.c_int, [_P, _P, _P, _P]),
     "ssdr_wb_nb_stats": (C.c_int, [_P, C.POINTER(C.c_float), C.POINTER(C.c_uint32), C.c_int]),
+    "ssdr_wb_real_taps": (C.c_int, [_P]),
+    "ssdr_set_wb_real_zone": (C.c_int, [_P, C.c_uint32, C.c_uint32, _P]),
+    "ssdr_get_wb_real_zone": (C.c_int, [_P, _P, C.POINTER(C.c_uint32)]),
+    "ssdr_push_wideband_real": (C.c_int, [_P, _P, C.c_uint32, C.c_int]),
+    "ssdr_read_wb_real": (C.c_int, [_P, _P, C.c_int]),
+    "ssdr_get_wb_real_state": (C.c_int, [_P, _P, C.POINTER(C.c_uint64)]),
+    "ssdr_wb_real_stats": (C.c_int, [_P, C.POINTER(C.c_float), C.POINTER(C.c_uint32), C.c_int]),
     "ssdr_set_wb_scopes": (C.c_int, [_P, C.POINTER(WbScope), C.c_uint32]),
     "ssdr_get_wb_scopes": (C.c_int, [_P, C.POINTER(WbScope), C.POINTER(C.c_uint32)]),
     "ssdr_wb_scope_lines": (C.c_int, [_P, _P, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.c_int]),
@@ -351,7 +359,9 @@ _NEWER_THAN_AB_LIBS = ("ssdr_feed_collect_listen", "ssdr_set_subrx", "ssdr_get_s
                        "ssdr_wb_rx_nb_mask", "ssdr_set_rx_iq", "ssdr_get_rx_iq", "ssdr_subrx_audio_iq", "ssdr_wb_rx_audio_iq",
                        "ssdr_set_feed_subrx", "ssdr_get_feed_subrx", "ssdr_feed_subrx_play", "ssdr_feed_collect_subrx",
                        "ssdr_selftest_math", "ssdr_set_wb_noise_blanker", "ssdr_get_wb_noise_blanker", "ssdr_wb_nb_gate_samples",
-                       "ssdr_wb_nb_mask", "ssdr_wb_nb_counts", "ssdr_get_wb_nb_state", "ssdr_wb_nb_stats")      # entry points a library named by SSDR_LIB_PATH (A/B builds only) may predate
+                       "ssdr_wb_nb_mask", "ssdr_wb_nb_counts", "ssdr_get_wb_nb_state", "ssdr_wb_nb_stats", "ssdr_wb_real_taps",
+                       "ssdr_set_wb_real_zone", "ssdr_get_wb_real_zone", "ssdr_push_wideband_real", "ssdr_read_wb_real",
+                       "ssdr_get_wb_real_state", "ssdr_wb_real_stats")      # entry points a library named by SSDR_LIB_PATH (A/B builds only) may predate
 
 
 def _load():

@@ -5,6 +5,7 @@
 //   ssdr_api_wfview.cpp      the waterfall views
 //   ssdr_api_checkpoint.cpp  the checkpoint
 //   ssdr_api_wbnb.cpp        the wideband noise blanker in front of the channeliser
+//   ssdr_api_wbreal.cpp      the real-sample front end in front of that
 //   ssdr_api.cpp             this one, everything else: error plumbing, create / destroy / params / rate / zoom / input, the waterfall and
 //                            audio stages and ssdr_run_chain, the listener stages, the banks of extra receivers, the wideband side, the
 //                            pipelined feed, the post kernels, the selftests
@@ -59,6 +60,7 @@ static void free_owned(ssdr_ctx *c)
         c->sub.d_consts, c->sub.d_taps, c->sub.d_parent, c->sub.d_play, c->sub.d_play_out,                            // ... their bank: state, constants, play_buffer
         c->d_chz_taps, c->d_chz_hist, c->d_chz_in,                                                                    // wideband channeliser
         c->d_wbnb_cfg, c->d_wbnb_state[0], c->d_wbnb_state[1], c->d_wbnb_out, c->d_wbnb_mask, c->d_wbnb_sums, c->d_wbnb_blk, c->d_wbnb_counts,   // ... its noise blanker
+        c->d_wbreal_zone, c->d_wbreal_hist[0], c->d_wbreal_hist[1], c->d_wbreal_out,                                  // ... its real-sample front end
         c->d_ws_taps, c->d_ws_scopes, c->d_ws_slot_stream, c->d_ws_hist, c->d_ws_out, c->d_ws_lines, c->d_ws_acc, c->d_ws_consts,   // wideband scopes
         c->d_wd_win, c->d_wd_part,                                                                                    // ... their detectors' scratch
         c->own.d_wr_rows, c->own.wr.d_pcm, c->own.wr.d_rssi, c->own.wr.d_flags, c->own.wr.d_closed, c->own.wr.d_adpcm, // tuned receivers: the own batch's rows and results,
@@ -3842,6 +3844,7 @@ int ssdr_set_channelizer(ssdr_ctx *c, uint32_t n_streams, uint32_t branches, uin
         SSDR_TRY(wbrx_clear(c));                                        // the tuned receivers and the scopes go with their streams
         SSDR_TRY(ws_clear(c));
         SSDR_TRY(wbnb_clear(c));                                        // ... and the wide blanker's settings
+        SSDR_TRY(wbreal_clear(c));                                      // ... and the real front end's zones and state
         c->chz_streams = 0;
         return SSDR_OK;
     }
@@ -3855,6 +3858,7 @@ int ssdr_set_channelizer(ssdr_ctx *c, uint32_t n_streams, uint32_t branches, uin
     SSDR_TRY(wbrx_clear(c));                                            // a new channeliser starts without tuned receivers or scopes
     SSDR_TRY(ws_clear(c));
     SSDR_TRY(wbnb_clear(c));                                            // ... and with no stream blanking
+    SSDR_TRY(wbreal_clear(c));                                          // ... every stream in zone 0, the real front end's state zero
     std::vector<float> h(taps, taps + n_taps);
     constexpr size_t kMaxTaps = (size_t)SSDR_CHAN_TAPS_PER_BRANCH_MAX * SSDR_CHAN_BRANCHES;
     if (!c->d_chz_taps) HIP_TRY(hipMalloc(&c->d_chz_taps, kMaxTaps * sizeof(float)));
@@ -3892,6 +3896,7 @@ int ssdr_channelizer_reset(ssdr_ctx *c) SSDR_GUARD
     c->ws_win_valid = false;
     c->chz_out_index = 0;
     SSDR_TRY(wbnb_reset(c));                                            // the wide blanker keeps its settings and starts over
+    SSDR_TRY(wbreal_reset(c));                                          // ... as does the real front end: the zones stay
     return bank_restart(c, c->wr, every_row);                           // the tuned receivers' list stays too; their audio starts over
 } SSDR_UNGUARD
 
@@ -3905,22 +3910,13 @@ int ssdr_get_channelizer_state(ssdr_ctx *c, int16_t *hist, uint64_t *out_index) 
     return SSDR_OK;
 } SSDR_UNGUARD
 
-int ssdr_push_wideband(ssdr_ctx *c, const int16_t *iq, uint32_t n_frames, int is_device) SSDR_GUARD
+// ssdr_push_wideband behind its input (ssdr_push_wideband_real hands in the converted samples): the wide blanker, the filter bank, the
+// tuned receivers' DDC, the scopes
+int push_wideband_from(ssdr_ctx *c, const uint32_t *in, uint32_t n_frames, uint64_t n_in, uint64_t n_out)
 {
-    if (!c || !iq || n_frames == 0) return SSDR_EINVAL;
-    if (!c->chz_streams) return SSDR_ESTATE;
-    const uint64_t n_out = in_len(c, n_frames);
-    const uint64_t n_in = n_out * (SSDR_CHAN_BRANCHES / c->chz_over);
-    if (n_in > 0x7FFFFFFFull || (is_device && (reinterpret_cast<uintptr_t>(iq) & 15u))) return SSDR_EINVAL;
-    HIP_TRY(hipSetDevice(c->device));
-    SSDR_TRY(join_audio(c));
-    if (!is_device) {
-        SSDR_TRY(grow(c, c->d_chz_in, c->chz_in_dwords, (size_t)c->chz_streams * n_in, 4));
-        HIP_TRY(hipMemcpyAsync(c->d_chz_in, iq, (size_t)c->chz_streams * n_in * 4, hipMemcpyHostToDevice, c->stream));
-    }
     SSDR_TRY(ensure_input(c, n_frames));
     SsdrChanArgs a;
-    a.in = is_device ? reinterpret_cast<const uint32_t *>(iq) : c->d_chz_in;
+    a.in = in;
     a.in_stride = n_in;
     SSDR_TRY(wbnb_stage(c, a.in, a.in_stride, (uint32_t)n_in));         // while a stream blanks: a.in becomes the blanked copy (same stride)
     a.n_streams = c->chz_streams; a.n_in = (uint32_t)n_in; a.n_out = (uint32_t)n_out;
@@ -3937,6 +3933,24 @@ int ssdr_push_wideband(ssdr_ctx *c, const int16_t *iq, uint32_t n_frames, int is
     c->chz_out_index += n_out;
     own_input(c, c->d_iq_own, n_frames);
     c->wr_rows_valid = !c->h_wr.empty();
+    return SSDR_OK;
+}
+
+int ssdr_push_wideband(ssdr_ctx *c, const int16_t *iq, uint32_t n_frames, int is_device) SSDR_GUARD
+{
+    if (!c || !iq || n_frames == 0) return SSDR_EINVAL;
+    if (!c->chz_streams) return SSDR_ESTATE;
+    const uint64_t n_out = in_len(c, n_frames);
+    const uint64_t n_in = n_out * (SSDR_CHAN_BRANCHES / c->chz_over);
+    if (n_in > 0x7FFFFFFFull || (is_device && (reinterpret_cast<uintptr_t>(iq) & 15u))) return SSDR_EINVAL;
+    HIP_TRY(hipSetDevice(c->device));
+    SSDR_TRY(join_audio(c));
+    if (!is_device) {
+        SSDR_TRY(grow(c, c->d_chz_in, c->chz_in_dwords, (size_t)c->chz_streams * n_in, 4));
+        HIP_TRY(hipMemcpyAsync(c->d_chz_in, iq, (size_t)c->chz_streams * n_in * 4, hipMemcpyHostToDevice, c->stream));
+    }
+    SSDR_TRY(push_wideband_from(c, is_device ? reinterpret_cast<const uint32_t *>(iq) : c->d_chz_in, n_frames, n_in, n_out));
+    c->wbreal_run_valid = false;                                        // (the converted samples are no longer the last push's)
     return SSDR_OK;
 } SSDR_UNGUARD
 

@@ -104,7 +104,8 @@ constexpr int kTimedWbRxAudio = SSDR_K_COUNT + 6;
 constexpr int kTimedSubTail = SSDR_K_COUNT + 7;         // the banks' fused squelch / de-emphasis / encoder launch (ssdr_rx_tail_stats)
 constexpr int kTimedWbRxTail = SSDR_K_COUNT + 8;
 constexpr int kTimedWbNb = SSDR_K_COUNT + 9;            // the wideband noise blanker (ssdr_wb_nb_stats)
-constexpr int kTimedCount = SSDR_K_COUNT + 10;
+constexpr int kTimedWbReal = SSDR_K_COUNT + 10;         // the real-sample front end (ssdr_wb_real_stats)
+constexpr int kTimedCount = SSDR_K_COUNT + 11;
 
 // A bank of extra receivers: audio chains that are no channels, rows in list order, run by the sub-receivers' kernels behind the
 // channels' audio stage.  The ctx holds two -- the sub-receivers (ssdr_set_subrx: each reads a channel's row of the input) and the
@@ -408,6 +409,18 @@ struct ssdr_ctx {
     uint64_t *d_wbnb_counts = nullptr;                  // [n_ch / 1024][2]
     bool wbnb_run_valid = false;                        // the last ssdr_push_wideband ran the blanker
     uint32_t wbnb_run_n_in = 0;                         // wide samples per stream of that run
+    // real-sample front end (ssdr_push_wideband_real; ssdr_api_wbreal.cpp): host settings at the first call of the zone setter, device
+    // memory at the first real push; a complex push launches nothing of it and touches none of its state
+    std::vector<uint32_t> h_wbreal_zone;                // [streams] as set (empty: never set -- everybody in zone 0)
+    bool wbreal_zone_dirty = true;                      // d_wbreal_zone is to be uploaded before the next launch
+    uint32_t *d_wbreal_zone = nullptr;                  // [n_ch / 1024]
+    uint32_t *d_wbreal_hist[2] = {nullptr, nullptr};    // [n_ch / 1024][SSDR_WB_REAL_HALO] pairs; a launch reads set wbreal_set and writes the other; swapped behind it
+    int wbreal_set = 0;
+    uint64_t wbreal_index = 0;                          // real samples taken per stream since the last reset
+    uint32_t *d_wbreal_out = nullptr;                   // [streams][n_in] the converted samples of the call
+    size_t wbreal_out_dwords = 0;
+    bool wbreal_run_valid = false;                      // the last push was an ssdr_push_wideband_real
+    uint32_t wbreal_run_n_in = 0;                       // complex samples per stream of that push
     // wideband scopes (ssdr_set_wb_scopes): device memory at the first scope; with none set nothing is launched
     std::vector<ssdr_wb_scope> h_ws;                    // the list as set
     std::vector<uint32_t> h_ws_det;                     // the detectors, parallel to it (ssdr_set_wb_scope_detectors; a new list: all SAMPLE)
@@ -449,6 +462,14 @@ uint32_t zoom_dphi(double offset_hz, double fs_in);
 int wbnb_stage(ssdr_ctx *c, const uint32_t *&in, uint64_t in_stride, uint32_t n_in);
 int wbnb_reset(ssdr_ctx *c);
 int wbnb_clear(ssdr_ctx *c);
+
+// ssdr_api.cpp: ssdr_push_wideband behind its input -- `in` [streams][n_in] wide dwords on the device, rows n_in apart.  (Defined among
+// the entry points, behind the static helpers it calls: C linkage like theirs, and hidden like everything here.)
+extern "C" int push_wideband_from(ssdr_ctx *c, const uint32_t *in, uint32_t n_frames, uint64_t n_in, uint64_t n_out);
+
+// ssdr_api_wbreal.cpp
+int wbreal_reset(ssdr_ctx *c);
+int wbreal_clear(ssdr_ctx *c);
 
 // ssdr_api_wfview.cpp
 int wfview_restart(ssdr_ctx *c, uint32_t first, uint32_t count);

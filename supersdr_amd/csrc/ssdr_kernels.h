@@ -340,6 +340,21 @@ struct SsdrWbNbArgs {
     uint64_t *counts;                        // [n_streams][2] their sums over the call: blanked, triggers (third launch)
 };
 hipError_t ssdr_launch_wb_nb(const SsdrWbNbArgs &a, hipStream_t stream);          // sums, then mask and apply, then the counts
+// real-sample front end (ssdr_wb_real.hip, ssdr_push_wideband_real): real int16 at 2F -> the complex int16 stream at F, in front of the
+// wide blanker.  A dword of the input is a PAIR (r[2k], r[2k+1]); a stream carries its last SSDR_WB_REAL_HALO pairs (the last 102 real
+// samples and two more in front of them, so that a row is thirteen 16-byte pieces).  The kernel reads one set of history rows and
+// writes the other: the host swaps them after a launch.
+#define SSDR_WB_REAL_HALO 52u
+#define SSDR_WB_REAL_TILE 2048u              // outputs (= input pairs) a workgroup makes; a call holds a multiple of 512 * 512
+struct SsdrWbRealArgs {
+    const uint32_t *in;                      // [n_streams][n_in] the call's pairs, 16-byte aligned rows: only read
+    uint32_t n_streams, n_in;                // complex samples out = pairs in, per stream
+    const uint32_t *zone;                    // [n_streams] 0: first Nyquist zone, 1: second (Q negated)
+    const uint32_t *hist_in;                 // [n_streams][SSDR_WB_REAL_HALO] the pairs in front of the call
+    uint32_t *hist_out;                      // [n_streams][SSDR_WB_REAL_HALO] another array: tile 0 reads hist_in in the launch whose last tile writes this
+    uint32_t *out;                           // [n_streams][n_in] I | Q << 16; never the same memory as `in`
+};
+hipError_t ssdr_launch_wb_real(const SsdrWbRealArgs &a, hipStream_t stream);
 struct SsdrFusedArgs { SsdrWfArgs wf; SsdrAudioArgs au; uint32_t *ticket; uint32_t ticket_base; };
 // ticket: ssdr_chain_ws_kernel's pair counter; it stands at ticket_base at launch and is never reset: every trio draws its pairs and one ticket
 // beyond the last pair, so a launch of `grid` workgroups leaves it at ticket_base + pairs + grid * SSDR_WS_AUDIO_WAVES / 2 (ssdr_api.cpp)

@@ -789,6 +789,69 @@ class SsdrEngine:
         """-> (total_ms, runs) of the wide blanker since the last reset (the time only with set_profiling on)"""
         return self._stage_stats("ssdr_wb_nb_stats", reset)
 
+    # ---- real-sample front end: ADC samples at twice the wide rate in, the complex wide stream made on the GPU
+    @staticmethod
+    def wb_real_taps():
+        """-> int32 [103]: the half-band low-pass of the real-sample front end, Q14 (ssdr_wb_real_taps)"""
+        q = np.zeros(L.WB_REAL_TAPS, np.int32)
+        check(lib.ssdr_wb_real_taps(q.ctypes.data), "ssdr_wb_real_taps")
+        return q
+
+    def set_wb_real_zone(self, first_stream, zone):
+        """The Nyquist zone of streams first_stream, first_stream + 1, ...: 0 (RF 0 .. F) or 1 (RF F .. 2F) each (an array-like, one
+        entry per stream, or a scalar).  Acts from the next push_wideband_real on and resets no state.  A value that is not a uint32
+        raises ValueError before the library is called; what the library refuses raises SsdrError (SSDR_EINVAL: a zone above 1,
+        streams the channeliser does not have; SSDR_ESTATE: no channeliser).  Either way no stream is changed."""
+        n = np.size(zone)
+        a = np.broadcast_to(np.asarray(zone, np.int64).ravel(), (n,))
+        if ((a < 0) | (a >= 2 ** 32)).any():
+            raise ValueError("zone %r: out of range" % (zone,))
+        z = np.ascontiguousarray(a, np.uint32)
+        check(lib.ssdr_set_wb_real_zone(self._ctx, int(first_stream), n, z.ctypes.data), "ssdr_set_wb_real_zone")
+
+    def get_wb_real_zone(self):
+        """-> uint32 [n_streams]: every stream's zone as set; empty without a channeliser"""
+        n = C.c_uint32(self._wb_streams())
+        z = np.zeros(max(n.value, 1), np.uint32)
+        check(lib.ssdr_get_wb_real_zone(self._ctx, z.ctypes.data, C.byref(n)), "ssdr_get_wb_real_zone")
+        return z[:n.value]
+
+    def push_wideband_real(self, x):
+        """x: int16 [n_streams, n_frames * 2 * 512 * D * R] host array of REAL samples at twice the wide rate, R = 1024 / oversample;
+        converted on the GPU, it becomes the input batch of n_frames frames as the converted samples' push_wideband would make it"""
+        n_streams, per_frame = self._wideband_per_frame()
+        x = np.ascontiguousarray(x, dtype=np.int16)
+        if x.ndim != 2 or x.shape[0] != n_streams or x.shape[1] == 0 or x.shape[1] % (2 * per_frame):
+            raise ValueError("x must be int16[n_streams=%d, k*%d], got %r" % (n_streams, 2 * per_frame, x.shape))
+        n_frames = x.shape[1] // (2 * per_frame)
+        check(lib.ssdr_push_wideband_real(self._ctx, x.ctypes.data, n_frames, 0), "ssdr_push_wideband_real")
+        self.in_frames = n_frames
+        self.sync()             # the host buffer may be released by the caller after this returns
+
+    def push_wideband_real_device(self, dev_ptr, n_frames):
+        check(lib.ssdr_push_wideband_real(self._ctx, int(dev_ptr), int(n_frames), 1), "ssdr_push_wideband_real")
+        self.in_frames = int(n_frames)
+
+    def read_wb_real(self):
+        """-> int16 [n_streams, n_in, 2]: the converted samples of the last push_wideband_real.  SsdrError (SSDR_ESTATE) unless the
+        last push was a real one."""
+        n_streams, per_frame = self._wideband_per_frame()
+        out = np.empty((n_streams, self.in_frames * per_frame, 2), np.int16)
+        check(lib.ssdr_read_wb_real(self._ctx, out.ctypes.data, 0), "ssdr_read_wb_real")
+        return out
+
+    def wb_real_state(self):
+        """-> (hist int16 [n_streams, 102]: each stream's last 102 real samples, oldest first; real samples taken per stream since the
+        last reset)"""
+        n = self._wb_streams()
+        hist, idx = np.zeros((max(n, 1), L.WB_REAL_TAPS - 1), np.int16), C.c_uint64()
+        check(lib.ssdr_get_wb_real_state(self._ctx, hist.ctypes.data, C.byref(idx)), "ssdr_get_wb_real_state")
+        return hist[:n], idx.value
+
+    def wb_real_stats(self, reset=False):
+        """-> (total_ms, runs) of the real-sample front end since the last reset (the time only with set_profiling on)"""
+        return self._stage_stats("ssdr_wb_real_stats", reset)
+
     # ---- wideband scopes: zoomable waterfalls of the channeliser's wide streams
     def set_wb_scopes(self, scopes):
         """The wideband scopes, replacing the whole list: a sequence of (stream, zoom, offset_hz) in any order, several per stream

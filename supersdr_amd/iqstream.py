@@ -148,6 +148,38 @@ class Channelizer:
             raise ValueError("a gate of %r us at %r Hz is outside 1..%d wide samples" % (gate_us, rate, self.NB_BLOCK))
         return int(np.ceil(x))
 
+    # the real-sample front end (ssdr_push_wideband_real): an ADC's real samples at 2 * rate become the complex wide stream at `rate`
+    REAL_USABLE = 0.45                              # of the wide rate, either side of the centre: further out the image is not suppressed
+
+    def real_rate(self, rate):
+        """the ADC's sample rate for a wide stream sampled at `rate`"""
+        return 2.0 * float(rate)
+
+    def real_offset_of(self, rf_hz, rate, zone=0):
+        """an RF frequency at the ADC's input -> its offset from the wide stream's centre: rf_hz - rate / 2 in zone 0 (RF 0 .. rate),
+        rf_hz - 3 rate / 2 in zone 1 (RF rate .. 2 rate; the front end undoes the ADC's spectrum reversal).  ValueError outside the zone."""
+        rate, rf = float(rate), float(rf_hz)
+        if zone not in (0, 1):
+            raise ValueError("zone %r: 0 or 1" % (zone,))
+        if not zone * rate <= rf < (zone + 1) * rate:
+            raise ValueError("%g Hz is outside zone %d (%g .. %g Hz)" % (rf, zone, zone * rate, (zone + 1) * rate))
+        return rf - (zone + 0.5) * rate
+
+    def real_usable(self, rf_hz, rate, zone=0):
+        """-> whether the half-band filter suppresses the image of a signal at rf_hz (74.7 dB): within 0.45 * rate of the stream's
+        centre.  In the outer 0.05 * rate at either edge of the zone -- and outside the zone -- it does not: False."""
+        try:
+            return abs(self.real_offset_of(rf_hz, rate, zone)) <= self.REAL_USABLE * float(rate)
+        except ValueError:
+            if zone not in (0, 1):
+                raise
+            return False
+
+    def real_row_of(self, rf_hz, rate, zone=0):
+        """row_of for an RF frequency at the ADC's input: (row within the stream, residual Hz); row r of zone z is centred on
+        z * rate + r * rate / 1024"""
+        return self.row_of(self.real_offset_of(rf_hz, rate, zone), rate)
+
     def scope_span(self, zoom, rate):
         """Hz a scope of `zoom` shows of a wide stream sampled at `rate`"""
         if not 0 <= int(zoom) <= self.SCOPE_ZOOM_MAX:

@@ -403,6 +403,7 @@ class IQHub:
         self.channelizer = None                      # the wideband channeliser in front of the hub (set_channelizer)
         self._wb_nb = {}                             # stream -> (gate_us, thresh, gate in wide samples): the wide blankers that are on (set_wideband_blanker)
         self._wb_nb_counts = None                    # (blanked [streams], triggers [streams]) of the last feed_wideband that blanked
+        self._wb_zone = {}                           # stream -> 1: the wide streams whose ADC samples are the second Nyquist zone's (set_wideband_zone)
         # the extra listeners, a table per family (the engine's rows in id order), and the dicts they publish:
         #   sub-receivers    sid -> (channel, ChanParams);                 sub_queue[sid]: Frame,   sub_clients[sid]: the kiwi_sound on it
         #   tuned receivers  tid -> (stream, offset_hz, ChanParams);       tuned_queue[tid]: Frame, tuned_clients[tid]: the kiwi_sound on it
@@ -1282,6 +1283,7 @@ class IQHub:
             self._tuned.clear()
             self._wb_nb = {}                         # ... and cleared the wide blankers' settings
             self._wb_nb_counts = None
+            self._wb_zone = {}                       # ... and the real front end's zones
 
     def set_wideband_blanker(self, stream, gate_us, thresh):
         """The impulse blanker of wide stream `stream`, IN FRONT of the channeliser: a gate of gate_us microseconds (at most 4096 wide
@@ -1341,10 +1343,58 @@ class IQHub:
                 raise ValueError("channels have samples buffered from feed(): a hub is fed either way, not both")
             self._run_superframe(block, wideband=True)
 
-    def _run_superframe(self, batch, wideband=False):
+    def set_wideband_zone(self, stream, zone):
+        """The Nyquist zone the ADC samples of wide stream `stream` are taken from (feed_wideband_real): 0, RF 0 .. F, or 1, RF F .. 2F,
+        F the wide rate.  An operator's setting of the hub, like the wide blanker: it says what antenna filter stands in front of the
+        ADC, and no listener's command reaches it.  Acts from the next feed_wideband_real on and resets nothing.  ValueError, before
+        the engine is touched, on a pipelined or wire hub, without a channeliser, for an engine without the setter, a stream that does
+        not exist and a zone other than 0 or 1; then nothing changes."""
+        self._require_wide_stream("wideband zone", "set_wb_real_zone")
+        stream = int(stream)
+        n_streams = self.n_ch // self.channelizer.BRANCHES
+        if not 0 <= stream < n_streams:
+            raise ValueError("wide stream %d of %d" % (stream, n_streams))
+        if zone not in (0, 1):
+            raise ValueError("wideband zone %r: 0 or 1" % (zone,))
+        with self._lock:
+            try:
+                self.engine.set_wb_real_zone(stream, int(zone))
+            except L.SsdrError as e:
+                raise ValueError("wideband zone refused: %s" % e)
+            if zone:
+                self._wb_zone[stream] = 1
+            else:
+                self._wb_zone.pop(stream, None)
+
+    def wideband_zone(self, stream):
+        """-> the zone of wide stream `stream` as set (0 until set)"""
+        with self._lock:
+            return self._wb_zone.get(int(stream), 0)
+
+    def feed_wideband_real(self, block):
+        """feed_wideband for an ADC: one superframe of every wide stream as REAL samples at twice the wide rate, int16 [n_streams,
+        2 * superframe samples * 1024 / oversample]; the engine makes the complex wide stream of it (a quarter-rate mix, a half-band
+        low-pass, a decimation by 2: Channelizer.real_row_of says where an RF frequency lands) and runs as feed_wideband does"""
+        if self.pipeline or self.wire:
+            raise ValueError("feed_wideband_real needs the synchronous sample hub")
+        ch = self.channelizer
+        if ch is None:
+            raise ValueError("no channeliser is set (set_channelizer)")
+        if not hasattr(self.engine, "push_wideband_real"):
+            raise ValueError("this engine has no real-sample front end (push_wideband_real)")
+        block = np.asarray(block, np.int16)
+        want = (self.n_ch // ch.BRANCHES, 2 * self._sf * ch.step)
+        if block.shape != want:
+            raise ValueError("feed_wideband_real takes int16 %r (one superframe of every stream), got %r" % (want, block.shape))
+        with self._lock:
+            if self._gmax > self._base * self._U:
+                raise ValueError("channels have samples buffered from feed(): a hub is fed either way, not both")
+            self._run_superframe(block, wideband=True, real=True)
+
+    def _run_superframe(self, batch, wideband=False, real=False):
         eng = self.engine
         if wideband:
-            wire_rssi = eng.push_wideband(batch)        # (None: the rows carry no SND headers)
+            wire_rssi = eng.push_wideband_real(batch) if real else eng.push_wideband(batch)        # (None: the rows carry no SND headers)
             self._wb_nb_counts = eng.wb_nb_counts() if self._wb_nb else None
         else:
             wire_rssi = eng.push_iq_wire(batch) if self.wire else eng.push_iq(batch)
